@@ -2,7 +2,7 @@
 """
 bench.py -- log_likelihood evaluations per second on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
@@ -33,7 +33,9 @@ step still does all of its work, and K steps are timed between the same barriers
 All inputs are resident in HBM when the timed region starts.  (mu_y, Sigma_y) come
 from tests/golden (the upstream integrals are outside the hot path).
 
-Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for every field).
+Prints ONE JSON line on rank 0 (see DESIGN.md section 6 for every field).  --dump-outputs DIR: rank 0 also
+writes what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs), so that two builds
+can be compared output for output on the same inputs.
 """
 import argparse
 import json
@@ -45,9 +47,6 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# one hardware queue per stream in flight (engine._want_hw_queues would do the same when the slots are asked
-# for; here before anything can have touched the GPU, and visible in the file the driver runs)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 YDEG, UDEG, K, STARS_PER_GPU, COVPTS = 15, 2, 1000, int(os.environ.get("SP_BENCH_STARS", "64")), 300
 FP64_PEAK_TFLOPS = 78.6  # MI355X fp64 matrix = vector peak (AMD CDNA4 datasheet)
@@ -542,6 +541,21 @@ def launch_ranks(n, argv):
     return rc
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: array} as dirname/<name>.npy, float64 (every output of the timed path fits in it exactly:
+    the log-likelihoods are fp64, the status words small integers).  At most DUMP_MAX_BYTES in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("bench.py: %d bytes of outputs to dump, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def _stub_lnlike(s, step_id):
     return -0.5 * (s + 1) ** 1.5 + np.cos(s) + 1e-3 * step_id
 
@@ -614,6 +628,8 @@ def main_stub(args, rank, world):
     sid, g = slots[(args.steps - 1) % F].history[-1]
     ref = np.array([_stub_lnlike(s, sid) for s in range(world * S)])
     ok = bool(np.array_equal(g.numpy(), ref))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"lnlike": g.numpy()})
     per_rank = per_rank_ms(torch, dist, world, h.local_elapsed, args.steps, None)
     if rank == 0:
         print(json.dumps({
@@ -652,10 +668,16 @@ def main():
                          "entries in every step) instead of sp_plan_data + sp_lnlike_ensemble_planned")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the cfg5-shape and conditional-branch measurements (after the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (per-star log-likelihoods and status words; "
+                         "N > 1: also the all-gathered log-likelihoods) as DIR/<name>.npy, float64, on rank 0")
     args = ap.parse_args()
 
     if args.gpus < 1:
         print("bench.py: --gpus must be at least 1", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be at least 1 and --warmup at least 0", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: be the launcher (this process makes no GPU call, before or after)
@@ -752,6 +774,13 @@ def main():
             sl.e.profile_begin(nev, timed_kinds)
 
     elapsed, host_enqueue, prewarm_steps = timed_steps(harness, args.steps, args.warmup, args.prewarm_ms, arm)
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs on the slot of the last timed step and overwrites its outputs)
+        last = slots[(args.steps - 1) % F]
+        dumped = {"lnlike": last.out.cpu().numpy(), "status": last.status.cpu().numpy()}
+        if use_dist:
+            dumped["lnlike_all_ranks"] = last.gathered.cpu().numpy()
+        dump_outputs(args.dump_outputs, dumped)
     timed_prof = prof_summary([sl.e for sl in slots], timed_kinds)
     per_rank = per_rank_ms(torch, dist, world, harness.local_elapsed, args.steps, e.device) if use_dist else None
     # N > 1: what the all-gather costs a step (untimed repeat, the collective of every step between two events on

@@ -30,8 +30,8 @@ __all__ = ["get_log_prob", "get_log_prob_ensemble", "EnsembleLogProb", "SampleBa
 
 # Independent evaluations in flight on one GPU.  Four is where the throughput peaks; a fifth stream LOSES 10-25 %
 # (108k against 120k evaluations/s at cfg3's shape, bench.py; EnsembleLogProb 0.584 -> 0.818 ms per sample with
-# four likelihood streams + the upstream's own, tools/attic/elp_modes.py, round 5) -- next to GPU_MAX_HW_QUEUES
-# (engine._want_hw_queues).  Callers' ``depth`` is clamped to it, with one warning.
+# four likelihood streams + the upstream's own, tools/attic/elp_modes.py, round 5).  Callers' ``depth`` is clamped
+# to it, with one warning.
 MAX_STREAMS = 4
 # ... except for steps that carry their upstream (SampleBatches: a third of a step's time on a stream is the samples'
 # moments and tables, light kernels that leave the GPU to the other streams): 88-92k evaluations/s of one K = 1000

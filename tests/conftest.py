@@ -9,8 +9,6 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-# (five streams in flight in some tests: a hardware queue each -- read by the HIP runtime when it initialises)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 
 def pytest_configure(config):

@@ -169,6 +169,28 @@ def test_bench_py_starts_its_own_ranks():
     assert np.isfinite(rec["value"]) and rec["value"] > 0
 
 
+def test_bench_py_dumps_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: rank 0 writes the all-gathered values of the LAST timed step (the stub's step id says
+    which step that was: its slot is (steps - 1) mod F) as DIR/lnlike.npy, float64.  --steps 0 is refused."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    steps, F = 7, 3
+    r = _run_bench(["--gpus", "2", "--steps", str(steps), "--warmup", "2", "--in-flight", str(F),
+                    "--dump-outputs", str(tmp_path)], {})
+    assert r.returncode == 0, r.stderr
+    got = np.load(str(tmp_path / "lnlike.npy"))
+    assert got.dtype == np.float64 and got.shape == (128,)
+    step_id = (got[0] - bench._stub_lnlike(0, 0)) / 1e-3
+    assert abs(step_id - round(step_id)) < 1e-6
+    step_id = int(round(step_id))
+    assert step_id % 16 == (steps - 1) % F
+    assert np.array_equal(got, np.array([bench._stub_lnlike(s, step_id) for s in range(128)]))
+
+    r = _run_bench(["--steps", "0"], {})
+    assert r.returncode == 2 and "--steps" in r.stderr and "{" not in r.stdout
+
+
 def test_bench_py_refuses_a_world_that_is_not_gpus():
     r = _run_bench(["--gpus", "2", "--steps", "3", "--warmup", "1"], {"WORLD_SIZE": "1", "RANK": "0"})
     assert r.returncode == 2 and "WORLD_SIZE" in r.stderr and "{" not in r.stdout

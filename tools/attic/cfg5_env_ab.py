@@ -11,7 +11,6 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 CHILD = r"""
 import json, os, sys
 sys.path.insert(0, %r)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch, torch.distributed as dist
 import bench
 out = {}

@@ -6,7 +6,6 @@ O=gpurun_out/cfg5_trace; rm -rf $O
 cat > /tmp/cfg5_run.py <<PY
 import json, os, sys
 sys.path.insert(0, "$ROOT")
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch, torch.distributed as dist
 import bench
 r = bench.bench_shape(torch, dist, ydeg=20, Kc=3000, S=32, tspan=30.0, tau=3.0, u=(0.4, 0.2), conditional=False, F=1, steps=4, device=0, planned=True)
