@@ -437,6 +437,38 @@ int sp_gp_condition(sp_handle *h, int K, int Ks, const double *Ktt_dev, const do
                     double *Kss_dev, const double *r_dev, double *mu_dev, int32_t *info_dev,
                     void *stream);
 
+/* ---- posterior of the spherical-harmonic map given a light curve (sp.py:518-641, sample_ylm_conditional) ----
+ * For S stars with the conditional path's design matrices A_s = sp_design_matrix(t, stars, rta1) [K, N]:
+ *   W   = Sigma_y^-1 + A^T C^-1 A,   C = diag(data var) + baseline_var 1 1^T     (sp.py:601-628)
+ *   ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)),   ycov = W^-1 = cho_solve(W, I),
+ *   ycho = cho_factor(ycov)                                                       (sp.py:631-641)
+ * C enters through Sherman-Morrison only (no K x K object; A^T D^-1 A on the matrix cores: csrc/sp_ylm.hip).
+ *   flux_dev [S,K]; diag_dev [S,K] per-cadence data variances or NULL (then stars[s].data_var); stars_dev [S]
+ *   (period, inc, table, baseline_mean, baseline_var, data_var, nobs); rta1_dev: the flux operators of
+ *   sp_design_matrix; sinv_dev [N,N] = Sigma_y^-1 (the lower triangle is read), sinvmu_dev [N] = Sigma_y^-1 mu_y
+ *   (the caller forms them once per moment set: sp_set_ylm_moments keeps its cost);
+ *   ymu_dev [S,N], ycov_dev [S,N,N], ycho_dev [S,N,N] (lower factor; may be NULL); status_dev [S] (may be NULL).
+ * The kernel needs every variance > 0: a star with a variance <= 0 or 1 + baseline_var sum 1/d <= 0 gets NaN in
+ * all three outputs and SP_STAR_NOT_PD, and so does a W that is not positive definite.  With every variance > 0
+ * that is exactly the case of a C that is not positive definite; with a variance <= 0 and baseline_var > 0, C may
+ * still be positive definite -- pass such a star through sp_ylm_conditional_whitened (what the Python facade does); a ycov that does not factor gives a NaN ycho and
+ * SP_STAR_NOT_PD (the reference's on_error NaN, math.py:82-91).  A ragged star (nobs not 0 or K) gets NaN and
+ * SP_STAR_NAN.  workspace_dev: sp_ylm_conditional_workspace_bytes(h, S, K) bytes (about S K (N + roundup(N, 64))
+ * doubles).  All launches go to `stream`; nothing is synchronised.                                           */
+size_t sp_ylm_conditional_workspace_bytes(sp_handle *h, int S, int K);
+int sp_ylm_conditional_batched(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                               const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev,
+                               const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev, double *ycov_dev,
+                               double *ycho_dev, uint32_t *status_dev, void *workspace_dev, void *stream);
+/* The same posterior for a data covariance given as a full matrix C = L L^T: the caller whitens,
+ * B_dev [S,K,N] = L^-1 A and r_dev [S,K] = L^-1 (flux - baseline_mean) (sp_cho_factor + sp_tri_solve; the
+ * baseline variance already added to C, as sp.py:613 does), and W = Sigma_y^-1 + B^T B, rhs = Sigma_y^-1 mu_y
+ * + B^T r take the same route with unit weights.  Outputs, status and workspace as above.                  */
+int sp_ylm_conditional_whitened(sp_handle *h, int S, int K, const double *B_dev, const double *r_dev,
+                                const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev,
+                                double *ycov_dev, double *ycho_dev, uint32_t *status_dev, void *workspace_dev,
+                                void *stream);
+
 /* ---- upstream of the hot path, host only ---------------- */
 /* LatitudeIntegralOp values (ops/latitude/latitude.py, ops/include/latitude.h:
  * 21-173): q [N], Q [N x N] for Beta shape parameters alpha, beta.  The

@@ -91,6 +91,9 @@ PROTOTYPES = {
     "sp_lnlike_grad_marginal_multi": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                            _V, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_ylm_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
+    "sp_ylm_conditional_batched": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_ylm_conditional_whitened": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "sp_alpha_beta": (_I, [_D, _I, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sp_set_marginal_constants": (_I, [_V, _V, _V]),
     "sp_set_ylm_moments": (_I, [_V, _V, _V]),

@@ -1,6 +1,7 @@
 // extern "C" entry points (include/starry_process_amd.h) and the fused
 // log-likelihood driver.  Host logic only: argument checks, workspace layout,
 // kernel sequencing on the caller's stream.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -80,6 +81,12 @@ int sp_launch_pad_out(const double *sys, int Kp, double *A, int K, long lda,
                       long strideA, const int32_t *info, int S, hipStream_t st);
 int sp_launch_cho_solve(const double *L, int K, long ldl, long strideL, double *B,
                         int nrhs, int batch, hipStream_t st);
+int sp_launch_ylm_gram(int S, int K, int N, const double *A, const double *flux, const double *diag,
+                       const sp_star *stars, int whitened, const double *sinv, const double *sinvmu, double *Bt,
+                       double *G, double *gh, double *sq, uint32_t *flags, double *W, double *rhs, hipStream_t st);
+int sp_launch_ylm_eye(int S, int N, double *out, hipStream_t st);
+int sp_launch_ylm_status(int S, const uint32_t *flags, const int32_t *info1, const int32_t *info2, uint32_t *status,
+                         hipStream_t st);
 
 static thread_local char g_hip_err[256] = "";
 
@@ -1459,6 +1466,98 @@ int sp_gp_condition(sp_handle *h, int K, int Ks, const double *Ktt_dev, const do
   if (info_dev)
     SP_HIP(hipMemcpyAsync(info_dev, info, sizeof(int32_t), hipMemcpyDeviceToDevice, st));
   return SP_OK;
+}
+
+// ---- posterior of the Ylm map given a light curve (sp.py:518-641; sp_ylm.hip) ----------------------------------
+// Caller workspace: [A (design matrices; reused for G = A^T D^-1 A)] [Bt (reused for W)] [g, h] [s, q] [flags,
+// info of W, info of ycov].  The factorisations and solves of the N x N systems are the library's own entry points.
+namespace {
+struct YlmLayout {
+  size_t A, Bt, gh, sq, flags, info1, info2, total;
+};
+YlmLayout ylm_layout(int S, int K, int N) {
+  const size_t Kp = sp_roundup(K, 32), Np = sp_roundup(N, 64), s = (size_t)S;
+  const size_t r0 = std::max(s * K * N, s * Np * Np), r1 = std::max(s * Np * Kp, s * N * N);
+  YlmLayout L;
+  size_t off = 0;
+  L.A = off, off += align_up(sizeof(double) * r0);
+  L.Bt = off, off += align_up(sizeof(double) * r1);
+  L.gh = off, off += align_up(sizeof(double) * s * 2 * N);
+  L.sq = off, off += align_up(sizeof(double) * s * 2);
+  L.flags = off, off += align_up(sizeof(uint32_t) * s);
+  L.info1 = off, off += align_up(sizeof(int32_t) * s);
+  L.info2 = off, off += align_up(sizeof(int32_t) * s);
+  L.total = off;
+  return L;
+}
+
+// from W, rhs in the workspace: ymu, ycov (and ycho), status
+int ylm_finish(sp_handle *h, int S, const YlmLayout &L, void *ws, double *ymu_dev, double *ycov_dev,
+               double *ycho_dev, uint32_t *status_dev, hipStream_t st) {
+  const int N = h->N;
+  double *W = at<double>(ws, L.Bt);
+  int32_t *info1 = at<int32_t>(ws, L.info1), *info2 = at<int32_t>(ws, L.info2);
+  int rc;
+  // W = L_W L_W^T (a W that is not positive definite comes back NaN, and so does every solve with it)
+  if ((rc = sp_cho_factor(h, W, N, N, (long)N * N, S, info1, st))) return rc;
+  if ((rc = sp_cho_solve(h, W, N, N, (long)N * N, ymu_dev, 1, S, st))) return rc;
+  // ycov = W^-1 = cho_solve(W, I), as the reference forms it
+  if ((rc = sp_launch_ylm_eye(S, N, ycov_dev, st))) return rc;
+  if ((rc = sp_cho_solve(h, W, N, N, (long)N * N, ycov_dev, N, S, st))) return rc;
+  if (ycho_dev) {
+    SP_HIP(hipMemcpyAsync(ycho_dev, ycov_dev, sizeof(double) * (size_t)S * N * N, hipMemcpyDeviceToDevice, st));
+    if ((rc = sp_cho_factor(h, ycho_dev, N, N, (long)N * N, S, info2, st))) return rc;
+  }
+  return sp_launch_ylm_status(S, at<uint32_t>(ws, L.flags), info1, ycho_dev ? info2 : nullptr, status_dev, st);
+}
+}  // namespace
+
+size_t sp_ylm_conditional_workspace_bytes(sp_handle *h, int S, int K) {
+  if (!h || S < 0 || K < 1) return 0;
+  return ylm_layout(S, K, h->N).total;
+}
+
+int sp_ylm_conditional_batched(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                               const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev,
+                               const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev, double *ycov_dev,
+                               double *ycho_dev, uint32_t *status_dev, void *workspace_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || K < 1 || !t_dev || !flux_dev || !stars_dev || !rta1_dev || !sinv_dev || !sinvmu_dev ||
+      !ymu_dev || !ycov_dev || !workspace_dev)
+    return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const YlmLayout L = ylm_layout(S, K, h->N);
+  void *ws = workspace_dev;
+  double *A = at<double>(ws, L.A);
+  int rc;
+  if ((rc = sp_design_matrix(h, S, K, t_dev, stars_dev, rta1_dev, A, st))) return rc;
+  if ((rc = sp_launch_ylm_gram(S, K, h->N, A, flux_dev, diag_dev, stars_dev, 0, sinv_dev, sinvmu_dev,
+                               at<double>(ws, L.Bt), A, at<double>(ws, L.gh), at<double>(ws, L.sq),
+                               at<uint32_t>(ws, L.flags), at<double>(ws, L.Bt), ymu_dev, st)))
+    return rc;
+  return ylm_finish(h, S, L, ws, ymu_dev, ycov_dev, ycho_dev, status_dev, st);
+}
+
+int sp_ylm_conditional_whitened(sp_handle *h, int S, int K, const double *B_dev, const double *r_dev,
+                                const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev,
+                                double *ycov_dev, double *ycho_dev, uint32_t *status_dev, void *workspace_dev,
+                                void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || K < 1 || !B_dev || !r_dev || !sinv_dev || !sinvmu_dev || !ymu_dev || !ycov_dev ||
+      !workspace_dev)
+    return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const YlmLayout L = ylm_layout(S, K, h->N);
+  void *ws = workspace_dev;
+  int rc;
+  if ((rc = sp_launch_ylm_gram(S, K, h->N, B_dev, r_dev, nullptr, nullptr, 1, sinv_dev, sinvmu_dev,
+                               at<double>(ws, L.Bt), at<double>(ws, L.A), at<double>(ws, L.gh),
+                               at<double>(ws, L.sq), at<uint32_t>(ws, L.flags), at<double>(ws, L.Bt), ymu_dev,
+                               st)))
+    return rc;
+  return ylm_finish(h, S, L, ws, ymu_dev, ycov_dev, ycho_dev, status_dev, st);
 }
 
 // The one collective of the path.  RCCL is resolved in the running

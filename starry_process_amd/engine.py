@@ -580,6 +580,51 @@ class Engine(object):
                                       self._p(r), self._p(mu), self._p(info), self._stream()))
         return mu, Kpost, info
 
+    def ylm_precision(self, mean_ylm, cov_ylm):
+        """(Sigma_y^-1, Sigma_y^-1 mu_y) the way the reference forms them (sp.py:267-271: cho_factor, then
+        cho_solve against I and mu_y), on the device.  NaN if Sigma_y is not positive definite."""
+        torch = _torch()
+        L, _ = self.cho_factor(cov_ylm)
+        sinv = self.cho_solve(L, torch.eye(self.N, dtype=torch.float64, device=self.device))
+        sinvmu = self.cho_solve(L, self.f64(mean_ylm).reshape(-1))
+        return sinv, sinvmu
+
+    def _ylm_buffers(self, S, K, with_cho):
+        torch = _torch()
+        nbytes = int(self._L.sp_ylm_conditional_workspace_bytes(self._h, S, K))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ymu, ycov = self.empty(S, self.N), self.empty(S, self.N, self.N)
+        ycho = self.empty(S, self.N, self.N) if with_cho else None
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        return ws, ymu, ycov, ycho, status
+
+    def ylm_conditional(self, t, flux, stars, rta1, sinv, sinvmu, diag=None, with_cho=True):
+        """Posterior of the Ylm map of S stars given their light curves (sp_ylm_conditional_batched):
+        t, flux [S, K]; stars (host sp_star records: period, inc, table, baseline_mean, baseline_var, data_var);
+        diag [S, K] per-cadence variances or None; sinv, sinvmu from ylm_precision.
+        Returns (ymu [S, N], ycov [S, N, N], ycho [S, N, N] or None, status [S])."""
+        t, flux = self.f64(t), self.f64(flux)
+        S, K = flux.shape
+        sd = self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        ws, ymu, ycov, ycho, status = self._ylm_buffers(S, K, with_cho)
+        check(self._L.sp_ylm_conditional_batched(
+            self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(self.f64(rta1)),
+            self._p(self.f64(sinv)), self._p(self.f64(sinvmu)), self._p(ymu), self._p(ycov), self._p(ycho),
+            self._p(status), self._p(ws), self._stream()))
+        return ymu, ycov, ycho, status
+
+    def ylm_conditional_whitened(self, B, r, sinv, sinvmu, with_cho=True):
+        """The same posterior for whitened data (sp_ylm_conditional_whitened): B [S, K, N] = L^-1 A,
+        r [S, K] = L^-1 (flux - baseline_mean) for a full data covariance C = L L^T."""
+        B, r = self.f64(B), self.f64(r)
+        S, K, _ = B.shape
+        ws, ymu, ycov, ycho, status = self._ylm_buffers(S, K, with_cho)
+        check(self._L.sp_ylm_conditional_whitened(
+            self._h, S, K, self._p(B), self._p(r), self._p(self.f64(sinv)), self._p(self.f64(sinvmu)),
+            self._p(ymu), self._p(ycov), self._p(ycho), self._p(status), self._p(ws), self._stream()))
+        return ymu, ycov, ycho, status
+
     # -- fused likelihood ----------------------------------------------------------
     def workspace(self, S, K, M):
         torch = _torch()

@@ -494,6 +494,168 @@ class StarryProcess(object):
         z = np.random.RandomState(seed).randn(Kpost.shape[0], int(nsamples))
         return Eager(np.array(mu)[None, :] + (L @ z).T)
 
+    # -- posterior of the surface map (sp.py:518-641) -------------------------------------
+    # W = Sigma_y^-1 + A^T C^-1 A, ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)), ycov = W^-1,
+    # with A the design matrix at (t, i, p, u) whatever marginalize_over_inclination says (sp.py:620), as in
+    # the reference.  A scalar or vector data_cov of positive variances with a scalar baseline_var never forms C
+    # (Sherman-Morrison, sp_ylm_conditional_batched); a full matrix, or a variance <= 0, is factored and the data
+    # whitened first.
+    def _ylm_precision(self):
+        """(Sigma_y^-1, Sigma_y^-1 mu_y) on the device, formed once per moment set (sp.py:267-271)."""
+        prec = self.__dict__.get("_ylm_prec")
+        if prec is None:
+            mu, cov = self._dev_moments if self._dev_moments is not None else self._host_moments
+            prec = self._ylm_prec = self._engine.ylm_precision(mu, cov)
+        return prec
+
+    def _ylm_check(self):
+        if self._normalized:
+            raise NotImplementedError("Method not implemented when the flux is normalized.")
+        if self._time_variable:
+            raise NotImplementedError("Method not implemented for time-variable maps.")
+
+    def _ylm_posterior(self, t, flux, data_cov, i, p, u, baseline_mean, baseline_var, with_cho, full=False):
+        self._ylm_check()
+        e, f = self._engine, self._flux
+        t, i, p, u = f._ingest(t, i, p, u)
+        K = t.shape[0]
+        r = np.asarray(flux, dtype=np.float64).reshape(-1) - np.asarray(baseline_mean, dtype=np.float64)
+        if r.shape != (K,):
+            raise ValueError("`flux` must have one value per time")
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        bvar = np.asarray(baseline_var, dtype=np.float64)
+        sinv, sinvmu = self._ylm_precision()
+        rta1 = f._rta1(u)
+        # the Sherman-Morrison kernel needs every variance > 0; a star with one <= 0 may still have a positive
+        # definite C = D + b 1 1^T, so it is factored as such (the reference's cho_factor decides, sp.py:616)
+        if not full and data_cov.ndim <= 1 and bvar.ndim == 0 and np.all(data_cov > 0):
+            stars = make_stars(1, period=p, inc_deg=i, baseline_var=float(bvar),
+                               data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
+            diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (K,))[None, :]
+            ymu, ycov, ycho, _ = e.ylm_conditional(t[None, :], r[None, :], stars, rta1, sinv, sinvmu, diag=diag,
+                                                   with_cho=with_cho)
+        else:
+            # full data covariance (or a matrix baseline_var): C = data_cov + baseline_var (sp.py:601-613),
+            # C = L L^T, then the same posterior on L^-1 A and L^-1 r
+            if data_cov.ndim == 0:
+                C = data_cov * np.eye(K)
+            elif data_cov.ndim == 1:
+                C = np.diag(np.broadcast_to(data_cov, (K,)))
+            else:
+                C = data_cov
+            L, _ = e.cho_factor(C + bvar)
+            A = e.design_matrix(t[None, :], make_stars(1, period=p, inc_deg=i), rta1)[0]
+            B = e.tri_solve(L, A)
+            rw = e.tri_solve(L, e.f64(r))
+            ymu, ycov, ycho, _ = e.ylm_conditional_whitened(B[None], rw[None], sinv, sinvmu, with_cho=with_cho)
+        return ymu[0], ycov[0], (None if ycho is None else ycho[0])
+
+    def ylm_conditional(self, t, flux, data_cov, i=defaults["i"], p=defaults["p"],
+                        u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                        baseline_var=defaults["baseline_var"]):
+        """Mean (nylm,) and covariance (nylm, nylm) of the spherical-harmonic coefficients conditioned on the
+        observed flux: the Gaussian ``sample_ylm_conditional`` draws from (sp.py:601-636), which the reference
+        computes but does not return.  NaN if a covariance on the way is not positive definite."""
+        ymu, ycov, _ = self._ylm_posterior(t, flux, data_cov, i, p, u, baseline_mean, baseline_var, False)
+        return Eager(ymu.cpu().numpy()), Eager(ycov.cpu().numpy())
+
+    def sample_ylm_conditional(self, t, flux, data_cov, i=defaults["i"], p=defaults["p"],
+                               u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                               baseline_var=defaults["baseline_var"], nsamples=1, seed=None):
+        """Samples of the spherical-harmonic coefficients conditioned on the observed flux, shape
+        (nsamples, nylm) (sp.py:518-641): ymu + cho_factor(ycov) z with
+        z = RandomState(seed).normal(size=(nylm, nsamples)) -- the constructor's ``seed`` when ``seed`` is None,
+        which is what the reference draws on a fresh instance.  Not implemented for normalized or
+        time-variable processes, as in the reference."""
+        e = self._engine
+        ymu, _, ycho = self._ylm_posterior(t, flux, data_cov, i, p, u, baseline_mean, baseline_var, True)
+        z = self._rng(seed).normal(size=(self._nylm, int(nsamples)))
+        out = e.gemm_nt(e.f64(np.ascontiguousarray(z.T)), ycho)      # (ycho z)^T
+        out += ymu[None, :]
+        return Eager(out.cpu().numpy())
+
+    def _ensemble_args(self, t, flux, data_cov, i, p, u, baseline_mean, baseline_var, nobs=0):
+        """Inputs of the ensemble calls, checked against flux's (S, K) shape: t (S, K) contiguous, the star records
+        (period, inclination, baselines, scalar variances, limb-darkening table, nobs), the distinct limb-darkening
+        sets utab and the per-cadence variances diag ((S, K) or None)."""
+        flux = np.asarray(flux, dtype=np.float64)
+        if flux.ndim != 2:
+            raise ValueError("`flux` must be (S, K)")
+        S, K = flux.shape
+        t = np.asarray(t, dtype=np.float64)
+        if t.shape not in ((K,), (S, K)):
+            raise ValueError("`t` must be (K,) or (S, K) like `flux` (%d, %d), not %s" % (S, K, t.shape))
+        t = np.ascontiguousarray(np.broadcast_to(t, (S, K)) if t.ndim == 1 else t)
+        p = np.broadcast_to(np.asarray(defaults["p"] if p is None else p, dtype=np.float64), (S,))
+        i = np.broadcast_to(np.asarray(defaults["i"] if i is None else i, dtype=np.float64), (S,))
+        if np.any(p < -1e-6):
+            raise ValueError("p out of bounds")
+        if np.any(i * np.pi / 180 < -1e-6) or np.any(i * np.pi / 180 > 0.5 * np.pi + 1e-6):
+            raise ValueError("i out of bounds")
+        u = np.asarray(defaults["u"][: self._udeg] if u is None else u, dtype=np.float64)
+        if u.ndim == 1:
+            utab, table = u[None, : self._udeg], np.zeros(S, dtype=np.int32)
+        elif u.ndim == 2 and u.shape[0] == S:
+            utab, table = np.unique(u[:, : self._udeg], axis=0, return_inverse=True)
+            table = table.astype(np.int32).reshape(-1)
+        else:
+            raise ValueError("`u` must be (udeg,) or (S, udeg)")
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        diag = None
+        dvar = 0.0
+        if data_cov.ndim == 2:
+            if data_cov.shape != (S, K):
+                raise ValueError("a 2-D `data_cov` must be (S, K) like `flux` (%d, %d), not %s" % (S, K, data_cov.shape))
+            diag = np.ascontiguousarray(data_cov)
+        elif data_cov.ndim <= 1 and data_cov.size in (1, S):
+            dvar = np.broadcast_to(data_cov.reshape(-1) if data_cov.ndim else data_cov, (S,))
+        else:
+            raise ValueError("`data_cov` must be a scalar, (S,) or (S, K)")
+        stars = make_stars(S, period=p, inc_deg=i, tau=self._tau,
+                           baseline_var=np.broadcast_to(np.asarray(baseline_var, float), (S,)),
+                           baseline_mean=np.broadcast_to(np.asarray(baseline_mean, float), (S,)),
+                           data_var=dvar, table=table, nobs=nobs)
+        return t, flux, stars, utab, diag
+
+    def ylm_conditional_ensemble(self, t, flux, data_cov, i=None, p=None, u=None, baseline_mean=0.0,
+                                 baseline_var=0.0, nsamples=0, seed=None):
+        """Posteriors of the surface maps of S stars in one device call.
+
+        t: (K,) or (S, K); flux: (S, K); data_cov: scalar, (S,) or (S, K); i, p: scalars or (S,);
+        u: (udeg,) shared or (S, udeg); baseline_mean, baseline_var: scalars or (S,).
+        Returns (ymu (S, nylm), ycov (S, nylm, nylm)) and, with nsamples > 0, samples (S, nsamples, nylm)
+        drawn with z = RandomState(seed).normal(size=(S, nylm, nsamples))."""
+        self._ylm_check()
+        e = self._engine
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, i, p, u, baseline_mean, baseline_var)
+        S = flux.shape[0]
+        sinv, sinvmu = self._ylm_precision()
+        rta1 = e.f64(e.rTA1L(utab))
+        nsamples = int(nsamples)
+        ymu, ycov, ycho, _ = e.ylm_conditional(t, flux, stars, rta1, sinv, sinvmu, diag=diag,
+                                               with_cho=nsamples > 0)
+        # stars with a variance <= 0 (or not a number): C = D + b 1 1^T may still be positive definite, which
+        # the kernel's rule does not decide -- they take the exact route of a full data covariance
+        var = diag if diag is not None else stars["data_var"][:, None]
+        incs = np.broadcast_to(np.asarray(defaults["i"] if i is None else i, dtype=np.float64), (S,))
+        for s_ in np.nonzero(~np.all(var > 0, axis=1))[0]:
+            dc = diag[s_] if diag is not None else stars["data_var"][s_]
+            m1, c1, l1 = self._ylm_posterior(t[s_], flux[s_], dc, incs[s_], stars["period"][s_],
+                                             utab[stars["table"][s_]], stars["baseline_mean"][s_],
+                                             stars["baseline_var"][s_], nsamples > 0, full=True)
+            ymu[s_], ycov[s_] = m1, c1
+            if ycho is not None:
+                ycho[s_] = l1
+        out = (Eager(ymu.cpu().numpy()), Eager(ycov.cpu().numpy()))
+        if nsamples > 0:
+            z = self._rng(seed).normal(size=(S, self._nylm, nsamples))
+            zt = e.f64(np.ascontiguousarray(np.swapaxes(z, 1, 2)))
+            smp = e.empty(S, nsamples, self._nylm)
+            e.gemm_nt_batched(zt, ycho, smp)                          # (ycho_s z_s)^T
+            smp += ymu[:, None, :]
+            out = out + (Eager(smp.cpu().numpy()),)
+        return out
+
     def log_likelihood_ensemble(self, t, flux, data_cov, i=None, p=None, u=None,
                                 baseline_mean=0.0, baseline_var=0.0):
         """Per-star log-likelihoods of S independent stars in one device call.
@@ -529,33 +691,10 @@ class StarryProcess(object):
                     dp[s_, : lens[s_]] = np.asarray(data_cov[s_], dtype=np.float64)
                 data_cov = dp
             t, flux, nobs = tp, fp, lens
-        flux = np.asarray(flux, dtype=np.float64)
-        S, K = flux.shape
-        t = np.asarray(t, dtype=np.float64)
-        t = np.broadcast_to(t, (S, K)) if t.ndim == 1 else t
-        p = np.broadcast_to(np.asarray(defaults["p"] if p is None else p, dtype=np.float64), (S,))
-        i = np.broadcast_to(np.asarray(defaults["i"] if i is None else i, dtype=np.float64), (S,))
-        if np.any(p < -1e-6):
-            raise ValueError("p out of bounds")
-        if np.any(i * np.pi / 180 < -1e-6) or np.any(i * np.pi / 180 > 0.5 * np.pi + 1e-6):
-            raise ValueError("i out of bounds")
-        u = np.asarray(defaults["u"][: self._udeg] if u is None else u, dtype=np.float64)
-        if u.ndim == 1:
-            utab, table = u[None, : self._udeg], np.zeros(S, dtype=np.int32)
-        else:
-            utab, table = np.unique(u[:, : self._udeg], axis=0, return_inverse=True)
-            table = table.astype(np.int32).reshape(-1)
-        data_cov = np.asarray(data_cov, dtype=np.float64)
-        diag = None
-        dvar = 0.0
-        if data_cov.ndim == 2:
-            diag = e.f64(np.ascontiguousarray(data_cov))
-        else:
-            dvar = np.broadcast_to(data_cov, (S,))
-        stars = make_stars(S, period=p, inc_deg=i, tau=self._tau,
-                           baseline_var=np.broadcast_to(np.asarray(baseline_var, float), (S,)),
-                           baseline_mean=np.broadcast_to(np.asarray(baseline_mean, float), (S,)),
-                           data_var=dvar, table=table, nobs=nobs)
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, i, p, u, baseline_mean, baseline_var,
+                                                         nobs=nobs)
+        if diag is not None:
+            diag = e.f64(diag)
         f._bind()
         rta1 = e.f64(e.rTA1L(utab))
         tab = mv = None
