@@ -246,8 +246,6 @@ __global__ void get_gpmean_kernel(int S, const double *__restrict__ coef,
   if (s < S) out[s] = coef[8 * s + 6] - 1.0;  // mu - 1 = flux mean
 }
 
-inline size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
   int S, K, M, Kp, N, NWIG;
   int Kr;   // rows per star of the design-matrix buffers A, B1: roundup(K, 64), the rows beyond K zero
@@ -260,8 +258,9 @@ struct Layout {
 #define SP_DEFER_ROWS 2
 
 // lean: no design-matrix buffers and no raw covariance (the SPD inverse and the gradient's sweep touch neither: at cfg3's
-// shape they were 1.5 GB of the 3.5 GB those calls asked for -- ADVICE r04)
-Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool lean = false) {
+// shape they were 1.5 GB of the 3.5 GB those calls asked for -- ADVICE r04).
+// s0 > 0: the same layout seen by the stars s0, s0 + 1, ... only (a star group of sp_lnlike_ensemble; the caller sets S)
+Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool lean = false, int s0 = 0) {
   Layout L;
   L.S = S;
   L.K = K;
@@ -272,68 +271,53 @@ Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool 
   L.N = h->N;
   L.NWIG = h->NWIG;
   L.Kr = sp_roundup(K, SP_NB);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off += align_up(bytes);
-    return o;
-  };
+  // every region holds S blocks of `star` bytes, one per star
+  SpCarve c;
+  auto take = [&](size_t star) { return c.take(S * star) + s0 * star; };
   const size_t d = sizeof(double);
-  L.theta = take(d * S * K);
-  L.rowsum = take(d * S * K);
-  L.qv = take(d * S * K);
-  L.coef = take(d * S * 8);
-  L.rscal = take(d * S * (SP_RSCAL_HEAD + (size_t)M));
-  L.info = take(sizeof(int32_t) * S);
-  L.status = take(sizeof(uint32_t) * S);
-  L.condmean = take(d * S);
-  L.cs = take(d * S * 2);
-  L.vrow = take(d * S * L.N);
-  L.Rinc = take(d * S * L.NWIG);
-  L.invL = take(d * (size_t)S * sp_lt_stride(L.Kp));
-  L.A = take(lean ? 0 : d * (size_t)S * L.Kr * L.N);
-  L.B1 = take(lean ? 0 : d * (size_t)S * L.Kr * L.N);
-  L.raw = take(lean ? 0 : d * (size_t)S * K * K);
-  L.part = with_sys ? take(d * (size_t)S * (L.Kp / SP_NB) * K) : off;
-  L.sys = with_sys ? take(d * (size_t)S * L.Kp * L.Kp) : off;
-  L.total = off;
+  L.theta = take(d * K);
+  L.rowsum = take(d * K);
+  L.qv = take(d * K);
+  L.coef = take(d * 8);
+  L.rscal = take(d * (SP_RSCAL_HEAD + (size_t)M));
+  L.info = take(sizeof(int32_t));
+  L.status = take(sizeof(uint32_t));
+  L.condmean = take(d);
+  L.cs = take(d * 2);
+  L.vrow = take(d * L.N);
+  L.Rinc = take(d * L.NWIG);
+  L.invL = take(d * sp_lt_stride(L.Kp));
+  L.A = take(lean ? 0 : d * L.Kr * L.N);
+  L.B1 = take(lean ? 0 : d * L.Kr * L.N);
+  L.raw = take(lean ? 0 : d * K * K);
+  L.part = with_sys ? take(d * (L.Kp / SP_NB) * K) : c.off;
+  L.sys = with_sys ? take(d * L.Kp * L.Kp) : c.off;
+  L.total = c.off;
   return L;
 }
-
-template <typename T>
-T *at(void *base, size_t off) {
-  return reinterpret_cast<T *>(reinterpret_cast<char *>(base) + off);
-}
-
-// grow-only device scratch owned by the handle (non-fused ops only)
-int ensure_big(sp_handle *h, size_t bytes, void **out);
 
 int check_handle(const sp_handle *h) { return h ? SP_OK : SP_ERR_INVALID; }
 
 }  // namespace
 
-// (the handle's grow-only scratch for the other translation units)
-int ensure_big_scratch(sp_handle *h, size_t bytes, void **out) { return ensure_big(h, bytes, out); }
-
-namespace {
-// (growing synchronises the device: the old buffer may still be in use by launches of this
-//  handle on any stream; steady-state calls never get here)
-int ensure_big(sp_handle *h, size_t bytes, void **out) {
-  if (h->big_bytes < bytes) {
+int sp_ensure_scratch(SpScratch &s, size_t bytes, void **out) {
+  if (s.bytes < bytes) {
     SP_HIP(hipDeviceSynchronize());
-    if (h->big_ptr) SP_HIP(hipFree(h->big_ptr));
-    h->big_ptr = nullptr;
-    h->big_bytes = 0;
-    hipError_t e = hipMalloc(&h->big_ptr, bytes);
+    if (s.ptr) SP_HIP(hipFree(s.ptr));
+    s.ptr = nullptr;
+    s.bytes = 0;
+    hipError_t e = hipMalloc(&s.ptr, bytes);
     if (e != hipSuccess) {
       sp_set_hip_error(e, "hipMalloc(scratch)");
       return SP_ERR_ALLOC;
     }
-    h->big_bytes = bytes;
+    s.bytes = bytes;
   }
-  *out = h->big_ptr;
+  *out = s.ptr;
   return SP_OK;
 }
+
+namespace {
 
 // design matrix for S stars into A_out (uses L.theta already filled); Kr rows per star in A_out and
 // in the scratch L.B1 (Kr == K: contiguous stars; Kr > K: the rows beyond K are zeroed)
@@ -385,31 +369,6 @@ int build_conditional_raw(sp_handle *h, const Layout &L, void *ws, hipStream_t s
 }  // namespace
 
 namespace {
-
-// the same layout seen by the stars s0 .. s0+Sg-1 only
-Layout sub_layout(const Layout &L, int s0, int Sg) {
-  Layout G = L;
-  const size_t d = sizeof(double), z = (size_t)s0;
-  G.S = Sg;
-  G.theta += z * L.K * d;
-  G.rowsum += z * L.K * d;
-  G.qv += z * L.K * d;
-  G.coef += z * 8 * d;
-  G.rscal += z * (SP_RSCAL_HEAD + (size_t)L.M) * d;
-  G.info += z * sizeof(int32_t);
-  G.status += z * sizeof(uint32_t);
-  G.condmean += z * d;
-  G.cs += z * 2 * d;
-  G.vrow += z * L.N * d;
-  G.Rinc += z * L.NWIG * d;
-  G.invL += z * sp_lt_stride(L.Kp) * d;
-  G.A += z * L.Kr * L.N * d;
-  G.B1 += z * L.Kr * L.N * d;
-  G.raw += z * (size_t)L.K * L.K * d;
-  G.part += z * (size_t)(L.Kp / SP_NB) * L.K * d;
-  G.sys += z * (size_t)L.Kp * L.Kp * d;
-  return G;
-}
 
 // stage A: everything up to the assembled systems, for one group on its stream
 int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const double *t_dev,
@@ -596,39 +555,7 @@ int sp_create(int ydeg, int udeg, int device, sp_handle **out) {
   h->N = (ydeg + 1) * (ydeg + 1);
   h->NWIG = sp_nwig_of(ydeg);
   h->device = device;
-  h->have_marginal = false;
-  h->have_moments = false;
-  h->xp_covpts = -1;
-  h->d_l_of = h->d_m_of = h->d_mirror = h->d_blk = nullptr;
-  h->d_Rx90 = h->d_wnp = h->d_Wnp = h->d_xp = nullptr;
-  h->d_mean_ylm = h->d_cov_ylm = h->d_ez = h->d_Ez = h->d_tmpNN = nullptr;
-  h->d_scratch = nullptr;
-  h->scratch_bytes = 0;
-  h->d_tab_scratch = nullptr;
-  h->tab_scratch_bytes = 0;
-  h->table_attr_done = false;
-  h->big_ptr = nullptr;
-  h->big_bytes = 0;
-  h->cs_ring.assign(4, sp_handle::CsSlot{nullptr, nullptr, 0, nullptr, false});
-  h->cs_next = 0;
-  h->superpanel = 0;
-  h->groups = 1;
-  h->gfork = nullptr;
-  h->prof_on = false;
-  h->prof_mask = 1u;
-  h->prof_used = 0;
-  h->defer_norm = 1;
-  h->lazy_cov = 1;
-  h->ncu = 256;
-  h->look_ahead = 1;
-  h->panel_layout = 1;
-  h->fuse_reduce = 1;
-  h->d_Rxm90 = nullptr;
-  h->d_lamcs = nullptr;
-  h->lamcs_Q = 0;
-  h->d_size_basis = nullptr;
-  h->size_spts = 0;
-  h->size_sfac = 0.0;
+  h->cs_ring.resize(4);
   const int N = h->N;
   h->l_of.resize(N);
   h->m_of.resize(N);
@@ -658,7 +585,6 @@ int sp_create(int ydeg, int udeg, int device, sp_handle **out) {
   SP_HIP(hipMalloc((void **)&h->d_tmpNN, d * N * N));
   h->scratch_bytes = d * (4 * (size_t)N + 64);
   SP_HIP(hipMalloc((void **)&h->d_scratch, h->scratch_bytes));
-  h->d_xp = nullptr;
   SP_HIP(hipMemcpy(h->d_l_of, h->l_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));
   SP_HIP(hipMemcpy(h->d_m_of, h->m_of.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));
   SP_HIP(hipMemcpy(h->d_mirror, h->mirror.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));
@@ -707,13 +633,13 @@ void sp_destroy(sp_handle *h) {
   (void)hipDeviceSynchronize();
   void *ptrs[] = {h->d_l_of, h->d_m_of,   h->d_mirror, h->d_blk,   h->d_Rx90,
                   h->d_wnp,  h->d_Wnp,    h->d_mean_ylm, h->d_cov_ylm, h->d_ez,
-                  h->d_Ez,   h->d_tmpNN,  h->d_scratch, h->d_xp, h->d_tab_scratch, h->d_Rxm90, h->d_lamcs,
+                  h->d_Ez,   h->d_tmpNN,  h->d_scratch, h->d_xp, h->tab_scratch.ptr, h->d_Rxm90, h->d_lamcs,
                   h->d_size_basis};
   for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->gdone) (void)hipEventDestroy(e);
   for (hipStream_t s2 : h->gstream) (void)hipStreamDestroy(s2);
   if (h->gfork) (void)hipEventDestroy(h->gfork);
-  if (h->big_ptr) (void)hipFree(h->big_ptr);
+  if (h->big.ptr) (void)hipFree(h->big.ptr);
   for (auto &c : h->cs_ring) {
     if (c.host) (void)hipHostFree(c.host);
     if (c.dev) (void)hipFree(c.dev);
@@ -731,7 +657,8 @@ int sp_nwig(const sp_handle *h) { return h ? h->NWIG : SP_ERR_INVALID; }
 
 }  // extern "C"
 
-int sp_stage_acquire(sp_handle *h, size_t doubles, sp_handle::CsSlot **out) {
+namespace {
+int sp_stage_acquire(sp_handle *h, size_t doubles, int *slot) {
   const size_t n = h->cs_ring.size();
   int pick = -1;
   for (size_t k = 0; k < n && pick < 0; ++k) {
@@ -746,7 +673,7 @@ int sp_stage_acquire(sp_handle *h, size_t doubles, sp_handle::CsSlot **out) {
     }
   }
   if (pick < 0 && n < SP_STAGE_MAX) {
-    h->cs_ring.push_back(sp_handle::CsSlot{nullptr, nullptr, 0, nullptr, false});
+    h->cs_ring.emplace_back();
     pick = (int)n;
   }
   if (pick < 0) {
@@ -767,8 +694,44 @@ int sp_stage_acquire(sp_handle *h, size_t doubles, sp_handle::CsSlot **out) {
   }
   if (!c.done) SP_HIP(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
   h->cs_next = (pick + 1) % (int)h->cs_ring.size();
-  *out = &c;
+  *slot = pick;
   return SP_OK;
+}
+}  // namespace
+
+SpStage::SpStage(sp_handle *h, size_t doubles) : h_(h), n_(doubles) {
+  rc = sp_stage_acquire(h, doubles, &slot_);
+  if (rc) return;
+  sp_handle::CsSlot &c = h->cs_ring[slot_];
+  c.used = true;
+  host = c.host;
+}
+
+const double *SpStage::upload(hipStream_t st) {
+  sp_handle::CsSlot &c = h_->cs_ring[slot_];
+  const hipError_t e = hipMemcpyAsync(c.dev, c.host, sizeof(double) * n_, hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) {
+    sp_set_hip_error(e, "hipMemcpyAsync(stage)");
+    return nullptr;
+  }
+  st_ = st;
+  sent_ = true;
+  return c.dev;
+}
+
+SpStage::~SpStage() {
+  if (slot_ < 0) return;
+  sp_handle::CsSlot &c = h_->cs_ring[slot_];
+  if (!sent_) {
+    c.used = false;
+    return;
+  }
+  const hipError_t e = hipEventRecord(c.done, st_);
+  if (e != hipSuccess) {
+    // (the slot's event does not follow the copy, which may still be in flight: drained here instead)
+    sp_set_hip_error(e, "hipEventRecord(stage)");
+    (void)hipStreamSynchronize(st_);
+  }
 }
 
 extern "C" {
@@ -789,22 +752,15 @@ int sp_Rx(sp_handle *h, const double *theta_host, int nangles, double *R_dev,
   // cos/sin on the host with libm, like the reference (wigner.h:153-154), staged through the
   // handle's ring: the slot's previous use is waited for on the host (long finished in
   // practice), nothing is allocated, freed or synchronised once the ring has grown
-  const size_t need = 2 * (size_t)nangles;
-  sp_handle::CsSlot *cp = nullptr;
-  {
-    int rc = sp_stage_acquire(h, need, &cp);
-    if (rc) return rc;
-  }
-  sp_handle::CsSlot &c = *cp;
+  SpStage cs(h, 2 * (size_t)nangles);
+  if (cs.rc) return cs.rc;
   for (int i = 0; i < nangles; ++i) {
-    c.host[2 * i] = std::cos(theta_host[i]);
-    c.host[2 * i + 1] = std::sin(theta_host[i]);
+    cs.host[2 * i] = std::cos(theta_host[i]);
+    cs.host[2 * i + 1] = std::sin(theta_host[i]);
   }
-  SP_HIP(hipMemcpyAsync(c.dev, c.host, sizeof(double) * need, hipMemcpyHostToDevice, st));
-  int rc = sp_launch_Rx(h, c.dev, nangles, R_dev, dR_dev, st);
-  SP_HIP(hipEventRecord(c.done, st));
-  c.used = true;
-  return rc;
+  const double *dcs = cs.upload(st);
+  if (!dcs) return SP_ERR_HIP;
+  return sp_launch_Rx(h, dcs, nangles, R_dev, dR_dev, st);
 }
 
 int sp_rTA1(sp_handle *h, double *rta1_host) {
@@ -1031,7 +987,7 @@ int sp_cov_marginal_batched(sp_handle *h, int S, int K, const double *t_dev,
   Layout L = make_layout(h, S, K, 0, false);
   // only the small per-star arrays are needed here
   void *ws = nullptr;
-  int rc = ensure_big(h, L.condmean + 256, &ws);
+  int rc = sp_ensure_scratch(h->big, L.condmean + 256, &ws);
   if (rc) return rc;
   double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
   double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
@@ -1066,7 +1022,7 @@ int sp_design_matrix(sp_handle *h, int S, int K, const double *t_dev,
   hipStream_t st = (hipStream_t)stream;
   Layout L = make_layout(h, S, K, 0, false);
   void *ws = nullptr;
-  int rc = ensure_big(h, L.raw, &ws);  // up to and including B1
+  int rc = sp_ensure_scratch(h->big, L.raw, &ws);  // up to and including B1
   if (rc) return rc;
   if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, at<double>(ws, L.theta), st)))
     return rc;
@@ -1087,7 +1043,7 @@ int sp_cov_conditional_batched(sp_handle *h, int S, int K, const double *t_dev,
   hipStream_t st = (hipStream_t)stream;
   Layout L = make_layout(h, S, K, 0, false);
   void *ws = nullptr;
-  int rc = ensure_big(h, L.total, &ws);
+  int rc = sp_ensure_scratch(h->big, L.total, &ws);
   if (rc) return rc;
   double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
   double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
@@ -1127,14 +1083,15 @@ int sp_cho_factor(sp_handle *h, double *A_dev, int K, long lda, long strideA,
   if (batch == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   const int Kp = sp_roundup(K, SP_NB);
-  const size_t sysb = align_up(sizeof(double) * (size_t)batch * Kp * Kp);
-  const size_t invb = align_up(sizeof(double) * (size_t)batch * sp_lt_stride(Kp));
+  SpCarve c;
+  const size_t osys = c.take(sizeof(double) * (size_t)batch * Kp * Kp),
+               oinv = c.take(sizeof(double) * (size_t)batch * sp_lt_stride(Kp)), oinfo = c.take(sizeof(int32_t) * batch);
   void *ws = nullptr;
-  int rc = ensure_big(h, sysb + invb + align_up(sizeof(int32_t) * batch), &ws);
+  int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
-  double *sys = at<double>(ws, 0);
-  double *invL = at<double>(ws, sysb);
-  int32_t *info = at<int32_t>(ws, sysb + invb);
+  double *sys = at<double>(ws, osys);
+  double *invL = at<double>(ws, oinv);
+  int32_t *info = at<int32_t>(ws, oinfo);
   SP_HIP(hipMemsetAsync(info, 0, sizeof(int32_t) * batch, st));
   if ((rc = sp_launch_pad_in(A_dev, K, lda, strideA, sys, Kp, 0, nullptr, batch, st)))
     return rc;
@@ -1200,11 +1157,13 @@ int sp_cholesky_rev(sp_handle *h, const double *L_dev, int K, long ldl, long str
   if (batch == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   const long kk = (long)K * K;
-  const size_t mb = align_up(sizeof(double) * (size_t)batch * kk);
+  const size_t mb = sizeof(double) * (size_t)batch * kk;
+  SpCarve c;
+  const size_t oLt = c.take(mb), oLbt = c.take(mb), oP = c.take(mb);
   void *ws = nullptr;
-  int rc = ensure_big(h, 3 * mb, &ws);
+  int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
-  double *Lt = at<double>(ws, 0), *Lbt = at<double>(ws, mb), *P = at<double>(ws, 2 * mb);
+  double *Lt = at<double>(ws, oLt), *Lbt = at<double>(ws, oLbt), *P = at<double>(ws, oP);
   // P = L^T L_bar
   if ((rc = sp_launch_transpose(L_dev, ldl, strideL, Lt, K, batch, st))) return rc;
   if ((rc = sp_launch_transpose(Lbar_dev, K, kk, Lbt, K, batch, st))) return rc;
@@ -1273,7 +1232,8 @@ int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
   for (int g = 0; g < G; ++g) {
     const int s0 = (int)((long)S * g / G), s1 = (int)((long)S * (g + 1) / G);
     first[g] = s0;
-    LG[g] = sub_layout(L, s0, s1 - s0);
+    LG[g] = make_layout(h, S, K, M, true, false, s0);
+    LG[g].S = s1 - s0;
     hipStream_t sg = g == 0 ? st : h->gstream[g - 1];
     if (g > 0) SP_HIP(hipStreamWaitEvent(sg, h->gfork, 0));
     CG[g] = sp_chol_group{at<double>(ws, LG[g].sys), at<int32_t>(ws, LG[g].info),
@@ -1442,15 +1402,15 @@ int sp_gp_condition(sp_handle *h, int K, int Ks, const double *Ktt_dev, const do
     return SP_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int M = Ks + 1, Kp = sp_roundup(K + M, SP_NB);
-  const size_t sysb = align_up(sizeof(double) * (size_t)Kp * Kp);
-  const size_t resb = align_up(sizeof(double) * (size_t)M * K);
-  const size_t invb = align_up(sizeof(double) * sp_lt_stride(Kp));
+  SpCarve c;
+  const size_t osys = c.take(sizeof(double) * (size_t)Kp * Kp), ores = c.take(sizeof(double) * (size_t)M * K),
+               olt = c.take(sizeof(double) * sp_lt_stride(Kp)), oinfo = c.take(sizeof(int32_t));
   void *ws = nullptr;
-  int rc = ensure_big(h, sysb + resb + invb + 256, &ws);
+  int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
-  double *sys = at<double>(ws, 0), *res = at<double>(ws, sysb);
-  double *lt = at<double>(ws, sysb + resb);
-  int32_t *info = at<int32_t>(ws, sysb + resb + invb);
+  double *sys = at<double>(ws, osys), *res = at<double>(ws, ores);
+  double *lt = at<double>(ws, olt);
+  int32_t *info = at<int32_t>(ws, oinfo);
   SP_HIP(hipMemsetAsync(info, 0, sizeof(int32_t), st));
   SP_HIP(hipMemcpyAsync(res, Kst_dev, sizeof(double) * (size_t)Ks * K, hipMemcpyDeviceToDevice, st));
   SP_HIP(hipMemcpyAsync(res + (size_t)Ks * K, r_dev, sizeof(double) * K, hipMemcpyDeviceToDevice,
@@ -1479,15 +1439,15 @@ YlmLayout ylm_layout(int S, int K, int N) {
   const size_t Kp = sp_roundup(K, 32), Np = sp_roundup(N, 64), s = (size_t)S;
   const size_t r0 = std::max(s * K * N, s * Np * Np), r1 = std::max(s * Np * Kp, s * N * N);
   YlmLayout L;
-  size_t off = 0;
-  L.A = off, off += align_up(sizeof(double) * r0);
-  L.Bt = off, off += align_up(sizeof(double) * r1);
-  L.gh = off, off += align_up(sizeof(double) * s * 2 * N);
-  L.sq = off, off += align_up(sizeof(double) * s * 2);
-  L.flags = off, off += align_up(sizeof(uint32_t) * s);
-  L.info1 = off, off += align_up(sizeof(int32_t) * s);
-  L.info2 = off, off += align_up(sizeof(int32_t) * s);
-  L.total = off;
+  SpCarve c;
+  L.A = c.take(sizeof(double) * r0);
+  L.Bt = c.take(sizeof(double) * r1);
+  L.gh = c.take(sizeof(double) * s * 2 * N);
+  L.sq = c.take(sizeof(double) * s * 2);
+  L.flags = c.take(sizeof(uint32_t) * s);
+  L.info1 = c.take(sizeof(int32_t) * s);
+  L.info2 = c.take(sizeof(int32_t) * s);
+  L.total = c.off;
   return L;
 }
 
@@ -1646,25 +1606,20 @@ struct GradLayout {
 GradLayout grad_layout(sp_handle *h, int S, int K, int M, int covpts) {
   const int Kr = sp_roundup(K, SP_NB);
   GradLayout G;
-  size_t off = 0;
-  auto take = [&](size_t b) {
-    size_t o = off;
-    off += align_up(b);
-    return o;
-  };
+  SpCarve c;
   const size_t d = sizeof(double);
-  G.inv = take(make_layout(h, S, K, Kr, true, true).total);
-  G.cinv = take(d * (size_t)S * Kr * Kr);
-  G.vec = take(d * (size_t)S * (M + 3) * K);       // C^-1 [p, q, 1, r_0 .. r_{M-1}]
-  G.dots = take(d * (size_t)S * M * 2);
-  G.hcoef = take(d * S);
-  G.logdet = take(d * S);
+  G.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
+  G.cinv = c.take(d * (size_t)S * Kr * Kr);
+  G.vec = c.take(d * (size_t)S * (M + 3) * K);       // C^-1 [p, q, 1, r_0 .. r_{M-1}]
+  G.dots = c.take(d * (size_t)S * M * 2);
+  G.hcoef = c.take(d * S);
+  G.logdet = c.take(d * S);
   {
     // the scatter's bins per lower tile; before that, the row parts of the products with C^-1 ([S][ntr][4][K])
     const size_t ntr = Kr / SP_NB, bins = ntr * (ntr + 1) / 2 * (covpts + 4), rows = ntr * 4 * (size_t)K;
-    G.partial = take(d * (size_t)S * (bins > rows ? bins : rows));
+    G.partial = c.take(d * (size_t)S * (bins > rows ? bins : rows));
   }
-  G.total = off;
+  G.total = c.off;
   return G;
 }
 }  // namespace

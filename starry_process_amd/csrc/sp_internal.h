@@ -18,8 +18,14 @@
 // SP_NB rows (the right-hand sides ride along as extra rows).
 #define SP_NB 64
 
+// grow-only device buffer owned by a handle (sp_ensure_scratch)
+struct SpScratch {
+  void *ptr = nullptr;
+  size_t bytes = 0;
+};
+
 struct sp_handle {
-  int ydeg, udeg, N, NWIG, device;
+  int ydeg = 0, udeg = 0, N = 0, NWIG = 0, device = 0;
   // host constants
   std::vector<int32_t> l_of, m_of, mirror, m0, blk;
   std::vector<double> rT;       // phase-curve solution vector, degree ydeg+udeg
@@ -27,63 +33,61 @@ struct sp_handle {
   std::vector<double> U1;       // ((udeg+1)^2 x (udeg+1)) limb-darkening basis
   std::vector<double> rta1;     // rT . A1 at degree ydeg (N)
   // device constants
-  int32_t *d_l_of, *d_m_of, *d_mirror, *d_blk;
-  double *d_Rx90;               // packed Rx(pi/2)
-  double *d_Rxm90;              // packed Rx(-pi/2) (sp_upstream.hip; first use)
-  double *d_lamcs;              // cos / sin (m lam_q) of the lamcs_Q equispaced longitudes (sp_upstream.hip)
-  int lamcs_Q;
-  double *d_size_basis;         // spot-size basis Bp [ydeg + 1][spts], then the colatitude grid [spts] (sp_set_size_basis)
-  int size_spts;
-  double size_sfac;
-  double *d_wnp, *d_Wnp;        // marginalisation constants (flux.py:121-179)
-  bool have_marginal;
-  double *d_xp;                 // lag grid of the last kernel table
-  int xp_covpts;
+  int32_t *d_l_of = nullptr, *d_m_of = nullptr, *d_mirror = nullptr, *d_blk = nullptr;
+  double *d_Rx90 = nullptr;     // packed Rx(pi/2)
+  double *d_Rxm90 = nullptr;    // packed Rx(-pi/2) (sp_upstream.hip; first use)
+  double *d_lamcs = nullptr;    // cos / sin (m lam_q) of the lamcs_Q equispaced longitudes (sp_upstream.hip)
+  int lamcs_Q = 0;
+  double *d_size_basis = nullptr;   // spot-size basis Bp [ydeg + 1][spts], then the colatitude grid [spts] (sp_set_size_basis)
+  int size_spts = 0;
+  double size_sfac = 0.0;
+  double *d_wnp = nullptr, *d_Wnp = nullptr;   // marginalisation constants (flux.py:121-179)
+  bool have_marginal = false;
+  double *d_xp = nullptr;       // lag grid of the last kernel table
+  int xp_covpts = -1;
   std::vector<double> xp_host;  // its host copy (re-upload only on change)
   // device state: Ylm moments
-  double *d_mean_ylm, *d_cov_ylm, *d_ez, *d_Ez, *d_tmpNN;
-  bool have_moments;
+  double *d_mean_ylm = nullptr, *d_cov_ylm = nullptr, *d_ez = nullptr, *d_Ez = nullptr, *d_tmpNN = nullptr;
+  bool have_moments = false;
   // small device scratch owned by the handle
-  double *d_scratch;
-  size_t scratch_bytes;
-  double *d_tab_scratch;        // [ntab][2][N] row reductions of the kernel table
-  size_t tab_scratch_bytes;
-  bool table_attr_done;         // dynamic-LDS opt-in of table_finish_kernel made on this handle's device
+  double *d_scratch = nullptr;
+  size_t scratch_bytes = 0;
+  SpScratch tab_scratch;        // [ntab][2][N] row reductions of the kernel table
+  bool table_attr_done = false; // dynamic-LDS opt-in of table_finish_kernel made on this handle's device
   // grow-only device scratch of the non-fused ops (sp_cov_*_batched, sp_cho_factor, ...): owned
   // by the handle, so two handles on one GPU never share it
-  void *big_ptr;
-  size_t big_bytes;
-  // cos / sin staging of sp_Rx: a ring of pinned host + device buffer pairs, each guarded by the
+  SpScratch big;
+  // host -> device staging (SpStage): a ring of pinned host + device buffer pairs, each guarded by the
   // event of its last use (no allocation, no stream synchronisation in the launch path)
   struct CsSlot {
-    double *host;
-    double *dev;
-    size_t cap;                 // doubles
-    hipEvent_t done;
-    bool used;
+    double *host = nullptr;
+    double *dev = nullptr;
+    size_t cap = 0;             // doubles
+    hipEvent_t done = nullptr;
+    bool used = false;
   };
-  std::vector<CsSlot> cs_ring;  // (sp_stage_acquire: grows while every slot is still in flight, up to SP_STAGE_MAX)
-  int cs_next;
-  int superpanel;               // panels per super-panel (SP_SUPER; 0 = chosen from K)
-  int groups;                   // concurrent star groups (SP_GROUPS, default 1)
-  int ncu;                      // compute units of the device
-  int look_ahead;               // panel launches carry a look-ahead item (sp_cholesky.hip; SP_PANEL_LA, default 1)
-  int panel_layout;             // panel launches laid out by CU (sp_panel.hip; SP_PANEL_LAYOUT, default 1)
-  int fuse_reduce;              // the reduction rides in the last panel launch's tail where it can (SP_FUSE_REDUCE, default 1)
+  std::vector<CsSlot> cs_ring;  // (grows while every slot is still in flight, up to SP_STAGE_MAX)
+  int cs_next = 0;
+  int superpanel = 0;           // panels per super-panel (SP_SUPER; 0 = chosen from K)
+  int groups = 1;               // concurrent star groups (SP_GROUPS, default 1)
+  int ncu = 256;                // compute units of the device
+  int look_ahead = 1;           // panel launches carry a look-ahead item (sp_cholesky.hip; SP_PANEL_LA, default 1)
+  int panel_layout = 1;         // panel launches laid out by CU (sp_panel.hip; SP_PANEL_LAYOUT, default 1)
+  int fuse_reduce = 1;          // the reduction rides in the last panel launch's tail where it can (SP_FUSE_REDUCE, default 1)
   std::vector<hipStream_t> gstream;
   std::vector<hipEvent_t> gdone;
-  hipEvent_t gfork;
-  int defer_norm;               // likelihood path: deferred normalisation (SP_DEFER_NORM, default 1)
-  int lazy_cov;                 // ... with covariance tiles formed at first touch (SP_LAZY_COV, default 1)
+  hipEvent_t gfork = nullptr;
+  int defer_norm = 1;           // likelihood path: deferred normalisation (SP_DEFER_NORM, default 1)
+  int lazy_cov = 1;             // ... with covariance tiles formed at first touch (SP_LAZY_COV, default 1)
   // optional per-launch timing of the factorisation's launches by kind (bench roofline)
-  bool prof_on;
-  unsigned prof_mask;                // kinds that are bracketed (bit k = kind k)
+  bool prof_on = false;
+  unsigned prof_mask = 1u;           // kinds that are bracketed (bit k = kind k)
   std::vector<hipEvent_t> prof_ev;   // pairs (start, stop)
   std::vector<int> prof_kind;        // kind of pair i
   std::vector<double> prof_fl;       // algorithmic flops of pair i, counted on the K cadences (+ the M riding residual rows)
   std::vector<double> prof_flp;      // the same count on the PADDED system (rows up to roundup(K + M + 2, 64)): what runs
   std::vector<int> prof_n;           // launches bracketed by pair i
-  size_t prof_used;                  // events handed out so far
+  size_t prof_used = 0;              // events handed out so far
 };
 
 // kinds of timed launches (sp_profile_kind; 1 and 3 were round 2's strip solves and assembly)
@@ -139,14 +143,51 @@ struct SpProfScope {
 
 const char *sp_set_hip_error(hipError_t e, const char *what);
 
-// A staging slot of at least `doubles` doubles (pinned host + device buffer) that no copy in flight still reads: the
-// oldest slot whose event has completed (hipEventQuery -- never a host wait: hipEventSynchronize on an event recorded
-// behind a kernel launch waits until the stream has DRAINED, the runtime gives kernels no completion signal of their
-// own: 0.9 ms per call with a step's launches queued, round 6), a new slot while all are busy, and only with
-// SP_STAGE_MAX slots in flight a wait for the oldest.  The caller fills c->host, enqueues its copy and records c->done
-// behind the last launch that reads c->dev, then sets c->used.
+// One staged host -> device upload through the handle's ring.  The constructor takes a slot of at least `doubles`
+// doubles that no copy in flight still reads (the oldest slot whose event has completed -- hipEventQuery, never a host
+// wait: hipEventSynchronize on an event recorded behind a kernel launch waits until the stream has DRAINED, the runtime
+// gives kernels no completion signal of their own: 0.9 ms per call with a step's launches queued, round 6 --, a new
+// slot while all are busy, and only with SP_STAGE_MAX slots in flight a wait for the oldest) and marks it busy.  The
+// caller fills `host`; upload() enqueues the one copy and returns the device copy.  The destructor records the slot's
+// event on the upload's stream, on every return path, so the scope must cover every launch that reads the device copy
+// (and holds no other SpStage of the handle); a slot whose copy was never enqueued stays free.
 #define SP_STAGE_MAX 64
-int sp_stage_acquire(sp_handle *h, size_t doubles, sp_handle::CsSlot **out);
+struct SpStage {
+  int rc;                   // SP_OK, or why no slot could be had (then `host` is null)
+  double *host = nullptr;
+  SpStage(sp_handle *h, size_t doubles);
+  ~SpStage();
+  const double *upload(hipStream_t st);   // null: the copy could not be enqueued (sp_last_hip_error says why)
+  SpStage(const SpStage &) = delete;
+  SpStage &operator=(const SpStage &) = delete;
+
+ private:
+  sp_handle *h_;
+  size_t n_;
+  int slot_ = -1;
+  hipStream_t st_ = nullptr;
+  bool sent_ = false;
+};
+
+// grows `s` to at least `bytes` (draining the device first: launches of the handle on any stream may still use the old
+// buffer; steady-state calls never grow it)
+int sp_ensure_scratch(SpScratch &s, size_t bytes, void **out);
+
+// Regions carved one after another out of one buffer, each on a 256-byte boundary.  The workspace layouts are ABI:
+// callers allocate by the sp_*_workspace_bytes answers.
+static inline size_t sp_align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+struct SpCarve {
+  size_t off = 0;   // bytes carved so far: the buffer's size once every region is taken
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off += sp_align_up(bytes);
+    return o;
+  }
+};
+template <typename T>
+static inline T *at(void *base, size_t off) {
+  return reinterpret_cast<T *>(static_cast<char *>(base) + off);
+}
 
 #define SP_HIP(call)                                   \
   do {                                                 \
@@ -221,7 +262,7 @@ struct SpCoef {
   double mu;       // 1 + flux mean
   double d1;       // direct: unused                     deferred: d_1 = baseline_var / c1
 };
-static_assert(sizeof(SpCoef) == 64, "8 doubles per star (Layout::coef, sub_layout)");
+static_assert(sizeof(SpCoef) == 64, "8 doubles per star (Layout::coef)");
 
 // The data plan of the likelihood step (sp_plan.hip; include/starry_process_amd.h: sp_plan_data): device pointers
 struct PlanDev {

@@ -177,21 +177,19 @@ int sp_plan_data(sp_handle *h, int S, int K, int M, const double *t_dev, const d
   p->S = S; p->K = K; p->M = M; p->covpts = covpts; p->temporal = temporal; p->has_diag = diag_dev != nullptr;
   p->t = t_dev; p->flux = flux_dev; p->diag = diag_dev; p->nrep = 0;
   const size_t d = sizeof(double);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_theta = 0, o_wbar = o_theta + up(d * S * K), o_sflux = o_wbar + up(d * S * np),
-               o_sdv = o_sflux + up(d * S * M), o_key = o_sdv + up(d * S), o_ord = o_key + up(d * S * 3),
-               total = o_ord + up(d * S);
-  p->bytes = total;
-  hipError_t e = hipMalloc(&p->buf, total);
+  SpCarve c;
+  const size_t o_theta = c.take(d * S * K), o_wbar = c.take(d * S * np), o_sflux = c.take(d * S * M),
+               o_sdv = c.take(d * S), o_key = c.take(d * S * 3), o_ord = c.take(d * S);
+  p->bytes = c.off;
+  hipError_t e = hipMalloc(&p->buf, c.off);
   if (e != hipSuccess) {
     sp_set_hip_error(e, "hipMalloc(plan)");
     delete p;
     return SP_ERR_ALLOC;
   }
-  char *base = static_cast<char *>(p->buf);
-  double *theta = reinterpret_cast<double *>(base + o_theta), *wbar = reinterpret_cast<double *>(base + o_wbar);
-  double *sflux = reinterpret_cast<double *>(base + o_sflux), *sdv = reinterpret_cast<double *>(base + o_sdv);
-  double *key = reinterpret_cast<double *>(base + o_key), *inorder = reinterpret_cast<double *>(base + o_ord);
+  double *theta = at<double>(p->buf, o_theta), *wbar = at<double>(p->buf, o_wbar);
+  double *sflux = at<double>(p->buf, o_sflux), *sdv = at<double>(p->buf, o_sdv);
+  double *key = at<double>(p->buf, o_key), *inorder = at<double>(p->buf, o_ord);
   p->dev = PlanDev{theta, wbar, sflux, sdv, key, inorder};
   auto fail = [&](int rc) {
     (void)hipFree(p->buf);
@@ -255,36 +253,35 @@ int sp_plan_replicate(sp_handle *h, const sp_plan *src, int B, void *stream, sp_
   p->nrep = B;
   p->buf = nullptr;
   const size_t d = sizeof(double), S = (size_t)p->S;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_theta = 0, o_wbar = o_theta + up(d * S * K), o_sflux = o_wbar + up(d * S * np),
-               o_sdv = o_sflux + up(d * S * M), o_key = o_sdv + up(d * S), o_ord = o_key + up(d * S * 3),
-               o_t = o_ord + up(d * S), o_flux = o_t + up(d * S * K), o_diag = o_flux + up(d * S * M * K),
-               total = o_diag + (src->has_diag ? up(d * S * K) : 0);
-  p->bytes = total;
-  hipError_t e = hipMalloc(&p->buf, total);
+  SpCarve c;
+  const size_t o_theta = c.take(d * S * K), o_wbar = c.take(d * S * np), o_sflux = c.take(d * S * M),
+               o_sdv = c.take(d * S), o_key = c.take(d * S * 3), o_ord = c.take(d * S), o_t = c.take(d * S * K),
+               o_flux = c.take(d * S * M * K), o_diag = src->has_diag ? c.take(d * S * K) : c.off;
+  p->bytes = c.off;
+  hipError_t e = hipMalloc(&p->buf, c.off);
   if (e != hipSuccess) {
     sp_set_hip_error(e, "hipMalloc(plan replica)");
     delete p;
     return SP_ERR_ALLOC;
   }
-  char *base = static_cast<char *>(p->buf);
-  auto at = [&](size_t o) { return reinterpret_cast<double *>(base + o); };
-  p->dev = PlanDev{at(o_theta), at(o_wbar), at(o_sflux), at(o_sdv), at(o_key), at(o_ord)};
-  p->t = at(o_t);
-  p->flux = at(o_flux);
-  p->diag = src->has_diag ? at(o_diag) : nullptr;
+  void *buf = p->buf;
+  p->dev = PlanDev{at<double>(buf, o_theta), at<double>(buf, o_wbar), at<double>(buf, o_sflux),
+                   at<double>(buf, o_sdv), at<double>(buf, o_key), at<double>(buf, o_ord)};
+  p->t = at<double>(buf, o_t);
+  p->flux = at<double>(buf, o_flux);
+  p->diag = src->has_diag ? at<double>(buf, o_diag) : nullptr;
   auto rep = [&](const double *from, size_t n, double *to) {
     hipLaunchKernelGGL(replicate_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, st, from, (long)n, to);
   };
-  rep(src->dev.theta, (size_t)S0 * K, at(o_theta));
-  rep(src->dev.wbar, (size_t)S0 * np, at(o_wbar));
-  rep(src->dev.sflux, (size_t)S0 * M, at(o_sflux));
-  rep(src->dev.sdv, (size_t)S0, at(o_sdv));
-  rep(src->dev.key, (size_t)S0 * 3, at(o_key));
-  rep(src->dev.inorder, (size_t)S0, at(o_ord));
-  rep(src->t, (size_t)S0 * K, at(o_t));
-  rep(src->flux, (size_t)S0 * M * K, at(o_flux));
-  if (src->has_diag) rep(src->diag, (size_t)S0 * K, at(o_diag));
+  rep(src->dev.theta, (size_t)S0 * K, at<double>(buf, o_theta));
+  rep(src->dev.wbar, (size_t)S0 * np, at<double>(buf, o_wbar));
+  rep(src->dev.sflux, (size_t)S0 * M, at<double>(buf, o_sflux));
+  rep(src->dev.sdv, (size_t)S0, at<double>(buf, o_sdv));
+  rep(src->dev.key, (size_t)S0 * 3, at<double>(buf, o_key));
+  rep(src->dev.inorder, (size_t)S0, at<double>(buf, o_ord));
+  rep(src->t, (size_t)S0 * K, at<double>(buf, o_t));
+  rep(src->flux, (size_t)S0 * M * K, at<double>(buf, o_flux));
+  if (src->has_diag) rep(src->diag, (size_t)S0 * K, at<double>(buf, o_diag));
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   if (e != hipSuccess) {

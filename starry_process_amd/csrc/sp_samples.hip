@@ -30,8 +30,6 @@
 
 #include "sp_internal.h"
 
-int ensure_big_scratch(sp_handle *h, size_t bytes, void **out);   // sp_api.hip
-
 namespace {
 
 constexpr int SM_TK = 64;     // columns of a sample's row block T (its 2 (ydeg + 2) <= 64 rotations, zero padded)
@@ -261,8 +259,6 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__
   if (j == 0) ez[(size_t)b * N + i] = scal[4 * b + 1] * eb[i];
 }
 
-inline size_t sm_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 extern "C" {
@@ -304,33 +300,30 @@ int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, do
   hipStream_t st = (hipStream_t)stream;
   SP_HIP(hipSetDevice(h->device));
   // scratch: svec [B][nl] | cs [B nq][2] | sc [B][2][P] | scal [B][4] | T [B][N][64] | M [B][N][N] | e1 [B][N]
-  size_t off = 0;
-  auto take = [&](size_t doubles) { size_t o = off; off += sm_align(sizeof(double) * doubles); return o; };
-  const size_t oS = take((size_t)B * nl), oC = take((size_t)B * nq * 2),
-               oSc = take((size_t)B * 2 * P), oSl = take((size_t)B * 4), oT = take((size_t)B * N * SM_TK),
-               oM = take((size_t)B * N * N), oE = take((size_t)B * N);
+  const size_t d = sizeof(double);
+  SpCarve c;
+  const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
+               oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N);
   void *ws = nullptr;
-  int rc = ensure_big_scratch(h, off, &ws);
+  int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
-  auto at = [&](size_t o) { return reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + o); };
-  double *svec = at(oS), *cs = at(oC), *sc = at(oSc), *scal = at(oSl), *T = at(oT), *M = at(oM),
-         *e1 = at(oE);
-  // ONE staged upload: the samples
-  const size_t need = 5 * (size_t)B;
-  sp_handle::CsSlot *cp = nullptr;
-  if ((rc = sp_stage_acquire(h, need, &cp))) return rc;
-  sp_handle::CsSlot &c = *cp;
-  memcpy(c.host, samples_host, sizeof(double) * need);
-  SP_HIP(hipMemcpyAsync(c.dev, c.host, sizeof(double) * need, hipMemcpyHostToDevice, st));
+  double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
+         *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE);
   const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);      // (+ 256 ints of flags)
   if (lds1 > 64 * 1024)
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds1);
-  hipLaunchKernelGGL(sm_prepare_kernel, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, h->d_size_basis, c.dev,
-                     svec, cs, sc, scal);
-  SP_LAUNCH_CHECK();
-  SP_HIP(hipEventRecord(c.done, st));
-  c.used = true;
+  {
+    // ONE staged upload: the samples (read by sm_prepare_kernel only)
+    SpStage stage(h, 5 * (size_t)B);
+    if (stage.rc) return stage.rc;
+    memcpy(stage.host, samples_host, sizeof(double) * 5 * B);
+    const double *samp = stage.upload(st);
+    if (!samp) return SP_ERR_HIP;
+    hipLaunchKernelGGL(sm_prepare_kernel, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, h->d_size_basis, samp,
+                       svec, cs, sc, scal);
+    SP_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
                      svec, cs, h->d_Rx90, sc, T);
   SP_LAUNCH_CHECK();

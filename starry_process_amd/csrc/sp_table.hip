@@ -186,15 +186,10 @@ int sp_launch_kernel_table(sp_handle *h, const double *rta1_dev, int ntab,
       sizeof(double) * ((size_t)3 * h->N + covpts + 4 + 2 * (h->ydeg + 1) + 4);
   if (lds > 150 * 1024) return SP_ERR_INVALID;
   // row-reduction scratch [ntab][2][N], grown on demand (rare: new ntab)
-  const size_t need = sizeof(double) * (size_t)ntab * nb * 3 * h->N;
-  if (h->tab_scratch_bytes < need) {
-    SP_HIP(hipDeviceSynchronize());
-    if (h->d_tab_scratch) SP_HIP(hipFree(h->d_tab_scratch));
-    h->d_tab_scratch = nullptr;
-    h->tab_scratch_bytes = 0;
-    SP_HIP(hipMalloc((void **)&h->d_tab_scratch, need));
-    h->tab_scratch_bytes = need;
-  }
+  void *ws = nullptr;
+  int rc = sp_ensure_scratch(h->tab_scratch, sizeof(double) * (size_t)ntab * nb * 3 * h->N, &ws);
+  if (rc) return rc;
+  double *rows = static_cast<double *>(ws);
   // (the attribute is per device: remembered per handle, a handle lives on one device)
   if (!h->table_attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(table_finish_kernel),
@@ -203,10 +198,10 @@ int sp_launch_kernel_table(sp_handle *h, const double *rta1_dev, int ntab,
   }
   hipLaunchKernelGGL(table_rows_kernel, dim3((h->N + 3) / 4, ntab, nb), dim3(256), 0, st,
                      h->N, h->d_l_of, h->d_mirror, h->d_Wnp, Ez, rta1_dev,
-                     h->d_tab_scratch, h->d_blk, h->d_wnp, ez);
+                     rows, h->d_blk, h->d_wnp, ez);
   SP_LAUNCH_CHECK();
   hipLaunchKernelGGL(table_finish_kernel, dim3(ntab, nb), dim3(256), lds, st, h->ydeg, h->N,
-                     h->d_l_of, h->d_blk, h->d_wnp, ez, rta1_dev, h->d_tab_scratch,
+                     h->d_l_of, h->d_blk, h->d_wnp, ez, rta1_dev, rows,
                      covpts, xp_dev, tab_dev, meanvar_dev);
   SP_LAUNCH_CHECK();
   return SP_OK;

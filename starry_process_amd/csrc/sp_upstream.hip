@@ -105,11 +105,38 @@ __global__ void up_finish_kernel(int N, int nc, const double *__restrict__ parts
   if (j == 0) mean[i] = sqrt_n * m1[i];
 }
 
-inline size_t up_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// constants of the handle: Rx(-pi/2) and the cos / sin (m lam_q) table of the Q longitudes
+int up_handle_constants(sp_handle *h, int Q, void *stream) {
+  if (!h->d_Rxm90) {
+    SP_HIP(hipMalloc((void **)&h->d_Rxm90, sizeof(double) * h->NWIG));
+    const double th = -0.5 * M_PI;
+    int rc = sp_Rx(h, &th, 1, h->d_Rxm90, nullptr, stream);
+    if (rc) return rc;
+  }
+  if (h->lamcs_Q != Q) {
+    // (a change of Q while launches that read the old table are in flight: drained first; never in a sampler loop)
+    if (h->d_lamcs) {
+      SP_HIP(hipStreamSynchronize((hipStream_t)stream));
+      SP_HIP(hipFree(h->d_lamcs));
+      h->d_lamcs = nullptr;
+    }
+    const int nm = h->ydeg + 1;
+    std::vector<double> tab((size_t)Q * 2 * nm);
+    for (int q = 0; q < Q; ++q) {
+      const double lam = 2.0 * M_PI * q / Q;
+      for (int k = 0; k < nm; ++k) {
+        tab[(size_t)q * 2 * nm + k] = std::cos(k * lam);
+        tab[(size_t)q * 2 * nm + nm + k] = std::sin(k * lam);
+      }
+    }
+    SP_HIP(hipMalloc((void **)&h->d_lamcs, sizeof(double) * tab.size()));
+    SP_HIP(hipMemcpy(h->d_lamcs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    h->lamcs_Q = Q;
+  }
+  return SP_OK;
+}
 
 }  // namespace
-
-int ensure_big_scratch(sp_handle *h, size_t bytes, void **out);   // sp_api.hip
 
 extern "C" int sp_ylm_moments_quadrature(sp_handle *h, const double *vecs_host, int mv, int first_is_col,
                                          const double *phi_host, const double *w_host, int P, int Q,
@@ -133,54 +160,26 @@ extern "C" int sp_ylm_moments_quadrature(sp_handle *h, const double *vecs_host, 
   const int KC = 128;
   const int ld2 = (int)((R2 + KC - 1) / KC * KC), nchunk = ld2 / KC;
   SP_HIP(hipSetDevice(h->device));
-
-  // constants of the handle: Rx(-pi/2) and the cos / sin (m lam_q) table of the Q longitudes
-  if (!h->d_Rxm90) {
-    SP_HIP(hipMalloc((void **)&h->d_Rxm90, sizeof(double) * NWIG));
-    const double th = -0.5 * M_PI;
-    int rc = sp_Rx(h, &th, 1, h->d_Rxm90, nullptr, stream);
-    if (rc) return rc;
-  }
-  if (h->lamcs_Q != Q) {
-    // (a change of Q while launches that read the old table are in flight: drained first; never in a sampler loop)
-    if (h->d_lamcs) {
-      SP_HIP(hipStreamSynchronize(st));
-      SP_HIP(hipFree(h->d_lamcs));
-      h->d_lamcs = nullptr;
-    }
-    std::vector<double> tab((size_t)Q * 2 * nm);
-    for (int q = 0; q < Q; ++q) {
-      const double lam = 2.0 * M_PI * q / Q;
-      for (int k = 0; k < nm; ++k) {
-        tab[(size_t)q * 2 * nm + k] = std::cos(k * lam);
-        tab[(size_t)q * 2 * nm + nm + k] = std::sin(k * lam);
-      }
-    }
-    SP_HIP(hipMalloc((void **)&h->d_lamcs, sizeof(double) * tab.size()));
-    SP_HIP(hipMemcpy(h->d_lamcs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    h->lamcs_Q = Q;
-  }
+  int rc = up_handle_constants(h, Q, stream);
+  if (rc) return rc;
 
   // scratch: Rphi [P, NWIG] | M0, V [P, mv, N] | U [R, N] | U2, A [RR, N] | T [N, ld2] | m1 [N]
-  size_t off = 0;
-  auto take = [&](size_t doubles) { size_t o = off; off += up_align(sizeof(double) * doubles); return o; };
-  const size_t oR = take((size_t)P * NWIG), oM0 = take((size_t)R * N), oV = take((size_t)R * N),
-               oU = take((size_t)R * N), oU2 = take((size_t)RR * N), oA = take((size_t)RR * N),
-               oT = take((size_t)N * ld2), om1 = take(N), opart = take((size_t)Q * N),
-               oC = take((size_t)nchunk * N * N);
+  const size_t d = sizeof(double);
+  SpCarve c;
+  const size_t oR = c.take(d * P * NWIG), oM0 = c.take(d * R * N), oV = c.take(d * R * N), oU = c.take(d * R * N),
+               oU2 = c.take(d * RR * N), oA = c.take(d * RR * N), oT = c.take(d * N * ld2), om1 = c.take(d * N),
+               opart = c.take(d * Q * N), oC = c.take(d * nchunk * N * N);
   void *ws = nullptr;
-  int rc = ensure_big_scratch(h, off, &ws);
-  if (rc) return rc;
-  auto at = [&](size_t o) { return reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + o); };
-  double *Rphi = at(oR), *M0 = at(oM0), *V = at(oV), *U = at(oU), *U2 = at(oU2), *A = at(oA), *T = at(oT),
-         *m1 = at(om1), *part = at(opart), *Cp = at(oC);
+  if ((rc = sp_ensure_scratch(h->big, c.off, &ws))) return rc;
+  double *Rphi = at<double>(ws, oR), *M0 = at<double>(ws, oM0), *V = at<double>(ws, oV), *U = at<double>(ws, oU),
+         *U2 = at<double>(ws, oU2), *A = at<double>(ws, oA), *T = at<double>(ws, oT), *m1 = at<double>(ws, om1),
+         *part = at<double>(ws, opart), *Cp = at<double>(ws, oC);
 
-  // ONE staged upload: cos / sin of the latitudes, sqrt weights, plain weights, the vectors
-  const size_t need = 2 * (size_t)P + 2 * (size_t)P + (size_t)mv * N;
-  sp_handle::CsSlot *cp = nullptr;
-  if ((rc = sp_stage_acquire(h, need, &cp))) return rc;
-  sp_handle::CsSlot &c = *cp;
-  double *hcs = c.host, *hsw = hcs + 2 * P, *hw = hsw + P, *hv = hw + P;
+  // ONE staged upload: cos / sin of the latitudes, sqrt weights, plain weights, the vectors (read up to
+  // up_first_moment_kernel: the stage's scope is the rest of the call)
+  SpStage stage(h, 2 * (size_t)P + 2 * (size_t)P + (size_t)mv * N);
+  if (stage.rc) return stage.rc;
+  double *hcs = stage.host, *hsw = hcs + 2 * P, *hw = hsw + P, *hv = hw + P;
   for (int k = 0; k < P; ++k) {
     hcs[2 * k] = std::cos(phi_host[k]);
     hcs[2 * k + 1] = std::sin(phi_host[k]);
@@ -188,8 +187,9 @@ extern "C" int sp_ylm_moments_quadrature(sp_handle *h, const double *vecs_host, 
     hw[k] = std::sqrt(w_host[k] / Q);          // sqrt(W_kq):  m1 = sum sqrt(W) (g sqrt(W) row)
   }
   memcpy(hv, vecs_host, sizeof(double) * (size_t)mv * N);
-  SP_HIP(hipMemcpyAsync(c.dev, c.host, sizeof(double) * need, hipMemcpyHostToDevice, st));
-  const double *dcs = c.dev, *dsw = dcs + 2 * P, *dw = dsw + P, *dv = dw + P;
+  const double *dcs = stage.upload(st);
+  if (!dcs) return SP_ERR_HIP;
+  const double *dsw = dcs + 2 * P, *dw = dsw + P, *dv = dw + P;
 
   // (the latitudes come in pairs +phi, -phi -- phi_host[k + P/2] = -phi_host[k], checked below --: one
   //  Wigner recursion per pair, the second rotation of a pair uses the transposed blocks)
@@ -197,8 +197,6 @@ extern "C" int sp_ylm_moments_quadrature(sp_handle *h, const double *vecs_host, 
   if ((rc = sp_launch_Rx(h, dcs, Ph, Rphi, nullptr, st))) return rc;
   hipLaunchKernelGGL(up_outer_kernel, dim3((mv * N + 255) / 256, P), dim3(256), 0, st, dsw, dv, mv, N, M0);
   SP_LAUNCH_CHECK();
-  SP_HIP(hipEventRecord(c.done, st));
-  c.used = true;
   // V = M0 Rx(phi_k), rotation by rotation; U = V Rx(pi/2); U2 = Rz(lam_q) on every row; A = U2 Rx(-pi/2)
   if ((rc = sp_launch_dotRx(h, M0, (long)mv * N, N, 1, mv, Rphi, NWIG, V, Ph, st))) return rc;
   if (paired &&
@@ -343,51 +341,26 @@ extern "C" int sp_ylm_moments_quadrature_grad(sp_handle *h, const double *s_host
   const int KC = 128;
   const int ld2 = (int)((R2 + KC - 1) / KC * KC), nchunk = ld2 / KC;
   SP_HIP(hipSetDevice(h->device));
-  if (!h->d_Rxm90) {
-    SP_HIP(hipMalloc((void **)&h->d_Rxm90, sizeof(double) * NWIG));
-    const double th = -0.5 * M_PI;
-    int rc = sp_Rx(h, &th, 1, h->d_Rxm90, nullptr, stream);
-    if (rc) return rc;
-  }
-  if (h->lamcs_Q != Q) {
-    if (h->d_lamcs) {
-      SP_HIP(hipStreamSynchronize(st));
-      SP_HIP(hipFree(h->d_lamcs));
-      h->d_lamcs = nullptr;
-    }
-    std::vector<double> tab((size_t)Q * 2 * nm);
-    for (int q = 0; q < Q; ++q) {
-      const double lam = 2.0 * M_PI * q / Q;
-      for (int k = 0; k < nm; ++k) {
-        tab[(size_t)q * 2 * nm + k] = std::cos(k * lam);
-        tab[(size_t)q * 2 * nm + nm + k] = std::sin(k * lam);
-      }
-    }
-    SP_HIP(hipMalloc((void **)&h->d_lamcs, sizeof(double) * tab.size()));
-    SP_HIP(hipMemcpy(h->d_lamcs, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
-    h->lamcs_Q = Q;
-  }
-  // scratch: Rphi, dRphi [Ph, NWIG] | V, U [R, N] | U2, A [RR, N] | T [UPG][N, ld2] | m1 [UPG][N] | part | C [UPG][nchunk][N][N]
-  size_t off = 0;
-  auto take = [&](size_t doubles) { size_t o = off; off += up_align(sizeof(double) * doubles); return o; };
-  const size_t oR = take((size_t)Ph * NWIG), odR = take((size_t)Ph * NWIG), oV = take((size_t)R * N),
-               oU = take((size_t)R * N), oU2 = take((size_t)RR * N), oA = take((size_t)RR * N),
-               oT = take((size_t)UPG * N * ld2), om1 = take((size_t)UPG * N), opart = take((size_t)Q * UPG * N),
-               oC = take((size_t)UPG * nchunk * N * N);
-  void *ws = nullptr;
-  int rc = ensure_big_scratch(h, off, &ws);
+  int rc = up_handle_constants(h, Q, stream);
   if (rc) return rc;
-  auto at = [&](size_t o) { return reinterpret_cast<double *>(reinterpret_cast<char *>(ws) + o); };
-  double *Rphi = at(oR), *dRphi = at(odR), *V = at(oV), *U = at(oU), *U2 = at(oU2), *A = at(oA), *T = at(oT),
-         *m1 = at(om1), *part = at(opart), *Cp = at(oC);
+  // scratch: Rphi, dRphi [Ph, NWIG] | V, U [R, N] | U2, A [RR, N] | T [UPG][N, ld2] | m1 [UPG][N] | part | C [UPG][nchunk][N][N]
+  const size_t d = sizeof(double);
+  SpCarve c;
+  const size_t oR = c.take(d * Ph * NWIG), odR = c.take(d * Ph * NWIG), oV = c.take(d * R * N), oU = c.take(d * R * N),
+               oU2 = c.take(d * RR * N), oA = c.take(d * RR * N), oT = c.take(d * UPG * N * ld2),
+               om1 = c.take(d * UPG * N), opart = c.take(d * Q * UPG * N), oC = c.take(d * UPG * nchunk * N * N);
+  void *ws = nullptr;
+  if ((rc = sp_ensure_scratch(h->big, c.off, &ws))) return rc;
+  double *Rphi = at<double>(ws, oR), *dRphi = at<double>(ws, odR), *V = at<double>(ws, oV), *U = at<double>(ws, oU),
+         *U2 = at<double>(ws, oU2), *A = at<double>(ws, oA), *T = at<double>(ws, oT), *m1 = at<double>(ws, om1),
+         *part = at<double>(ws, opart), *Cp = at<double>(ws, oC);
 
   // ONE staged upload: cos / sin of the Ph latitudes | coefficients [P][UPG][3] | sqrt weights [P] | their
-  // derivatives [UPG][P] | s, ds/dr [2][N]
-  const size_t need = 2 * (size_t)Ph + (size_t)P * UPG * 3 + (size_t)P + (size_t)UPG * P + 2 * (size_t)N;
-  sp_handle::CsSlot *cp = nullptr;
-  if ((rc = sp_stage_acquire(h, need, &cp))) return rc;
-  sp_handle::CsSlot &c = *cp;
-  double *hcs = c.host, *hco = hcs + 2 * Ph, *hsq = hco + (size_t)P * UPG * 3, *hdsq = hsq + P, *hsv = hdsq + (size_t)UPG * P;
+  // derivatives [UPG][P] | s, ds/dr [2][N] (read up to up_first_moment_grad_kernel: the stage's scope is the rest of
+  // the call)
+  SpStage stage(h, 2 * (size_t)Ph + (size_t)P * UPG * 3 + (size_t)P + (size_t)UPG * P + 2 * (size_t)N);
+  if (stage.rc) return stage.rc;
+  double *hcs = stage.host, *hco = hcs + 2 * Ph, *hsq = hco + (size_t)P * UPG * 3, *hdsq = hsq + P, *hsv = hdsq + (size_t)UPG * P;
   for (int k = 0; k < Ph; ++k) {
     hcs[2 * k] = std::cos(phi_host[k]);
     hcs[2 * k + 1] = std::sin(phi_host[k]);
@@ -410,8 +383,9 @@ extern "C" int sp_ylm_moments_quadrature_grad(sp_handle *h, const double *s_host
   }
   memcpy(hsv, s_host, sizeof(double) * N);
   memcpy(hsv + N, ds_dr_host, sizeof(double) * N);
-  SP_HIP(hipMemcpyAsync(c.dev, c.host, sizeof(double) * need, hipMemcpyHostToDevice, st));
-  const double *dcs = c.dev, *dco = dcs + 2 * Ph, *dsq = dco + (size_t)P * UPG * 3, *ddsq = dsq + P,
+  const double *dcs = stage.upload(st);
+  if (!dcs) return SP_ERR_HIP;
+  const double *dco = dcs + 2 * Ph, *dsq = dco + (size_t)P * UPG * 3, *ddsq = dsq + P,
                *dsv = ddsq + (size_t)UPG * P;
   if ((rc = sp_launch_Rx(h, dcs, Ph, Rphi, dRphi, st))) return rc;
   hipLaunchKernelGGL(up_tangent_rows_kernel, dim3((N + 255) / 256, UPG, P), dim3(256), 0, st, N, Ph, h->d_l_of, h->d_blk,
@@ -425,8 +399,6 @@ extern "C" int sp_ylm_moments_quadrature_grad(sp_handle *h, const double *s_host
   hipLaunchKernelGGL(up_first_moment_grad_kernel, dim3((N + 255) / 256, Q, UPG), dim3(256), 0, st, N, P, dsq, ddsq, A,
                      part);
   SP_LAUNCH_CHECK();
-  SP_HIP(hipEventRecord(c.done, st));
-  c.used = true;
   hipLaunchKernelGGL(up_first_moment_grad_sum_kernel, dim3((N + 255) / 256, UPG), dim3(256), 0, st, N, Q, part, m1);
   SP_LAUNCH_CHECK();
   for (int tau = 0; tau < UPG; ++tau) {

@@ -158,6 +158,19 @@ def test_look_ahead_and_super_panel_width_do_not_change_the_answer(monkeypatch):
         assert np.max(np.abs(v / ref - 1)) < 1e-10, k
 
 
+def test_star_groups_do_not_change_the_answer(monkeypatch):
+    """SP_GROUPS = 2: the stars split into two groups on their own streams, each with its view of the workspace
+    (groups only form with S >= 16): the same values as one group."""
+    res = []
+    for groups in ("1", "2"):
+        monkeypatch.setenv("SP_GROUPS", groups)
+        e = make_engine(15)
+        v, st = lnl(e, 1000, range(16))
+        assert not st.any()
+        res.append(v)
+    assert np.max(np.abs(res[1] / res[0] - 1)) < 1e-12
+
+
 @pytest.mark.parametrize("K,M,S", [(1000, 1, 64), (1000, 3, 16), (700, 1, 8), (1345, 1, 24), (960, 70, 8), (200, 1, 40)])
 def test_layout_by_cu_and_fused_reduction_do_not_change_a_bit(K, M, S):
     """The panel launches laid out by CU (chain items first, sleepers, the other items on the other CUs) against

@@ -148,6 +148,30 @@ def test_bad_arguments_are_rejected():
     assert L.sp_index_tables(-1, None, None, None, None, None) == -1
 
 
+def test_workspace_sizes_are_pinned():
+    """Callers allocate by the sp_*_workspace_bytes answers (ABI): every region keeps its order and 256-byte
+    alignment.  golden/workspace_bytes.npz holds the answers over a grid of shapes, recorded from the library before
+    its workspace carving was unified."""
+    ws = golden("workspace_bytes")
+    L = _lib.lib()
+    for a, ydeg in enumerate(LS):
+        h = ctypes.c_void_p()
+        _lib.check(L.sp_create(ydeg, 2, -1, ctypes.byref(h)))
+        try:
+            for b, S in enumerate((1, 7, 64)):
+                for c, K in enumerate((1, 63, 64, 1000, 3000)):
+                    at = (ydeg, S, K)
+                    assert L.sp_spd_inverse_workspace_bytes(h, S, K) == ws["spd_inverse"][a, b, c], at
+                    assert L.sp_ylm_conditional_workspace_bytes(h, S, K) == ws["ylm_conditional"][a, b, c], at
+                    assert L.sp_lnlike_grad_workspace_bytes(h, S, K, 300) == ws["lnlike_grad"][a, b, c], at
+                    for d, M in enumerate((1, 3)):
+                        assert L.sp_lnlike_workspace_bytes(h, S, K, M) == ws["lnlike"][a, b, c, d], at + (M,)
+                        assert (L.sp_lnlike_grad_workspace_bytes_multi(h, S, K, M, 300)
+                                == ws["lnlike_grad_multi"][a, b, c, d]), at + (M,)
+        finally:
+            L.sp_destroy(h)
+
+
 def test_header_is_plain_c_and_links(tmp_path):
     """include/starry_process_amd.h is the drop-in boundary: it must compile as C (no C++, no
     torch types) and a C program must be able to link libsp_hip.so and call it.  Only host
