@@ -238,12 +238,18 @@ int sp_cov_conditional_batched(sp_handle *h, int S, int K, const double *t_dev,
 /* In-place lower Cholesky of `batch` K x K matrices (row-major, leading
  * dimension lda, stride strideA).  The strict upper triangle is zeroed like
  * scipy.linalg.cholesky(lower=True).  A non positive definite matrix is
- * filled with NaN (math.py:88-91) and info_dev[b] (may be NULL) set to 1.    */
+ * filled with NaN (math.py:88-91) and info_dev[b] (may be NULL) set to 1.
+ * Only the lower triangle enters the factor: a finite strict upper triangle is
+ * ignored, as LAPACK potrf('L') does.  A NaN or inf ANYWHERE in the K x K
+ * part, strict upper triangle included, also gives the all-NaN factor and
+ * info 1 (scipy's check_finite: ValueError, which math.py:83-91 turns into
+ * NaN).  batch = 0 is SP_OK and touches nothing.                              */
 int sp_cho_factor(sp_handle *h, double *A_dev, int K, long lda, long strideA,
                   int batch, int32_t *info_dev, void *stream);
 /* x = (L L^T)^{-1} b: b_dev is [batch, K, nrhs] row-major (like the
  * reference's (K, M) right-hand sides), overwritten with the solution.
- * NaN in -> NaN out (math.py:27-31).                                         */
+ * Only the lower triangle of L is read.  NaN in -> NaN out (math.py:27-31).
+ * nrhs and batch are at most 65535 (SP_ERR_INVALID, b untouched).            */
 int sp_cho_solve(sp_handle *h, const double *L_dev, int K, long ldl,
                  long strideL, double *b_dev, int nrhs, int batch,
                  void *stream);
@@ -251,7 +257,8 @@ int sp_cho_solve(sp_handle *h, const double *L_dev, int K, long ldl,
 /* One triangular sweep: trans = 0 solves L x = b (the reference's
  * Solve(A_structure="lower_triangular")(L, b), math.py:98), trans = 1 solves
  * L^T x = b (Solve("upper_triangular")(L.T, .), math.py:99).  Only the lower
- * triangle of L is read.  b_dev as in sp_cho_solve, overwritten.             */
+ * triangle of L is read.  b_dev as in sp_cho_solve, overwritten.  batch is at
+ * most 65535 (SP_ERR_INVALID, b untouched); nrhs has no such limit.          */
 int sp_tri_solve(sp_handle *h, const double *L_dev, int K, long ldl,
                  long strideL, double *b_dev, int nrhs, int batch, int trans,
                  void *stream);

@@ -76,7 +76,8 @@ int sp_launch_lnlike_reduce(const double *sys, int S, int K, int M, int Kp,
                             const sp_star *stars = nullptr, const void *defer_coef = nullptr,
                             const double *rscal = nullptr, int dvec = 0);
 int sp_launch_pad_in(const double *A, int K, long lda, long strideA, double *sys,
-                     int Kp, int M, const double *resid, int S, hipStream_t st, int ident = 0);
+                     int Kp, int M, const double *resid, int S, hipStream_t st, int ident = 0,
+                     int32_t *nonfinite = nullptr);
 int sp_launch_pad_out(const double *sys, int Kp, double *A, int K, long lda,
                       long strideA, const int32_t *info, int S, hipStream_t st);
 int sp_launch_cho_solve(const double *L, int K, long ldl, long strideL, double *B,
@@ -1093,7 +1094,8 @@ int sp_cho_factor(sp_handle *h, double *A_dev, int K, long lda, long strideA,
   double *invL = at<double>(ws, oinv);
   int32_t *info = at<int32_t>(ws, oinfo);
   SP_HIP(hipMemsetAsync(info, 0, sizeof(int32_t) * batch, st));
-  if ((rc = sp_launch_pad_in(A_dev, K, lda, strideA, sys, Kp, 0, nullptr, batch, st)))
+  // (a NaN or inf anywhere in a matrix, strict upper triangle included, flags it: all NaN out, info 1)
+  if ((rc = sp_launch_pad_in(A_dev, K, lda, strideA, sys, Kp, 0, nullptr, batch, st, 0, info)))
     return rc;
   if ((rc = sp_launch_cholesky_systems(h, sys, batch, K, Kp, info, invL, st))) return rc;
   if ((rc = sp_launch_pad_out(sys, Kp, A_dev, K, lda, strideA, info, batch, st)))

@@ -42,19 +42,23 @@ __global__ __launch_bounds__(256) void lnlike_reduce_kernel(
                             rscal ? rscal + (size_t)s * (SP_RSCAL_HEAD + M) : nullptr, dvec, red, threadIdx.x);
 }
 
-// copy a batch of K x K matrices into zero/identity padded Kp x Kp systems
+// copy a batch of K x K matrices into zero/identity padded Kp x Kp systems; nonfinite (may be NULL): set to 1 for a
+// matrix with a NaN or inf anywhere in its K x K part -- the factorisation reads the lower triangle only, so one in
+// the strict upper triangle would not reach a pivot (sp_cho_factor: scipy's check_finite, math.py:83-91)
 __global__ __launch_bounds__(256) void pad_in_kernel(const double *__restrict__ A,
                                                      int K, long lda, long strideA,
                                                      double *__restrict__ sys, int Kp,
                                                      long strideS, int M,
-                                                     const double *__restrict__ resid, int ident) {
+                                                     const double *__restrict__ resid, int ident,
+                                                     int32_t *__restrict__ nonfinite) {
   const int s = blockIdx.z, i = blockIdx.y;
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= Kp) return;
   double v = 0.0;
-  if (i < K && j < K)
+  if (i < K && j < K) {
     v = A[(size_t)s * strideA + (size_t)i * lda + j];
-  else if (i >= K && i < K + M && j < K && resid)
+    if (nonfinite && !isfinite(v)) nonfinite[s] = 1;
+  } else if (i >= K && i < K + M && j < K && resid)
     v = resid[((size_t)s * M + (i - K)) * K + j];
   else if (ident && i >= K + M)
     v = (j == i - (K + M) && j < K) ? 1.0 : 0.0;   // the identity riding along below the M residual rows (no unit diagonal
@@ -377,9 +381,10 @@ int sp_launch_lnlike_reduce(const double *sys, int S, int K, int M, int Kp,
 }
 
 int sp_launch_pad_in(const double *A, int K, long lda, long strideA, double *sys,
-                     int Kp, int M, const double *resid, int S, hipStream_t st, int ident) {
+                     int Kp, int M, const double *resid, int S, hipStream_t st, int ident,
+                     int32_t *nonfinite) {
   hipLaunchKernelGGL(pad_in_kernel, dim3((Kp + 255) / 256, Kp, S), dim3(256), 0,
-                     st, A, K, lda, strideA, sys, Kp, (long)Kp * Kp, M, resid, ident);
+                     st, A, K, lda, strideA, sys, Kp, (long)Kp * Kp, M, resid, ident, nonfinite);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

@@ -137,7 +137,7 @@ def test_likelihood_gradient_closed_form():
     assert np.abs(r_bar + 0.5 * x).max() < 1e-12 * np.abs(x).max()
 
 
-@pytest.mark.parametrize("K,B", [(64, 3), (100, 2), (129, 1), (500, 4), (1000, 8)])
+@pytest.mark.parametrize("K,B", [(64, 3), (100, 2), (129, 1), (500, 4), (960, 2), (961, 2), (1000, 8), (1025, 3)])
 def test_spd_inverse_batched(K, B):
     """sp_spd_inverse_batched (the identity riding through the blocked factorisation, C^-1 = L^-T L^-1) against
     NumPy: inverse to 1e-10 of its norm, log-determinant to 1e-12 relative; a matrix that is not positive
