@@ -476,6 +476,31 @@ int sp_ylm_conditional_whitened(sp_handle *h, int S, int K, const double *B_dev,
                                 double *ycov_dev, double *ycho_dev, uint32_t *status_dev, void *workspace_dev,
                                 void *stream);
 
+/* ---- the process in pixel space (sp.py:443-487 mean_pix / cov_pix, sp.py:1199-1235 mollweide) ----------------
+ * M [npts, N] (row stride ldm >= N) is the Ylm -> intensity transform at npts points (x, y, z) of the unit sphere,
+ *   M = pi pT(x, y, z) A1       (visualize.py:78-91: latlon_transform, mollweide_transform)
+ * with pT the polynomial basis of the reference's computepT (ops/include/flux.h:597-648; a NaN z makes its row
+ * NaN, as the reference's xterm += 0 z does) and A1 the change of basis at degree ydeg.  xyz_dev [3, npts] (the
+ * x row, the y row, the z row: what compute_moll_grid returns).  The handle uploads A1 once, at its first call.
+ * Columns N .. ldm - 1 of M are not touched.  workspace_dev: sp_pixel_transform_workspace_bytes(h, npts) bytes. */
+size_t sp_pixel_transform_workspace_bytes(sp_handle *h, int npts);
+int sp_pixel_transform(sp_handle *h, int npts, const double *xyz_dev, double *M_dev, long ldm, void *workspace_dev,
+                       void *stream);
+/* S pixel covariances out[s] = (M cov[s]) M^T (sp.py:487, tt.dot(tt.dot(A, cov_ylm), A.T)): cov_dev [S, N, N]
+ * (strideCov doubles apart; symmetric -- its rows are read as the columns of cov), out_dev [S, npts, npts] (row
+ * stride ldo >= npts, strideOut doubles apart).  The lower triangle is formed and mirrored: out is exactly
+ * symmetric, and no entry of it is read before it is written.  workspace_dev: sp_pixel_cov_workspace_bytes(h, S,
+ * npts) bytes (S npts roundup(N, 32) doubles).                                                                  */
+size_t sp_pixel_cov_workspace_bytes(sp_handle *h, int S, int npts);
+int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, long ldm, const double *cov_dev,
+                         long strideCov, double *out_dev, long ldo, long strideOut, void *workspace_dev, void *stream);
+/* nmaps images out[i] = M y[i] (sp.py:1229-1231, tensordot(M, y^T)): y_dev [nmaps, N], out_dev [nmaps, npix]
+ * (contiguous), M [npix, N] with row stride ldm.  unit_background != 0 adds 1 to y[i][0] first (sp.py:1225-1228),
+ * i.e. M[:, 0] to the image: 1 on the grid and NaN off it.  out is written, never read.  The packed copy of y
+ * lives in the handle's scratch.  nmaps = 0 is SP_OK and touches nothing.                                        */
+int sp_pixel_render(sp_handle *h, int nmaps, int npix, const double *y_dev, const double *M_dev, long ldm,
+                    int unit_background, double *out_dev, void *stream);
+
 /* ---- upstream of the hot path, host only ---------------- */
 /* LatitudeIntegralOp values (ops/latitude/latitude.py, ops/include/latitude.h:
  * 21-173): q [N], Q [N x N] for Beta shape parameters alpha, beta.  The

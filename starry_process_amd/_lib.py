@@ -94,6 +94,11 @@ PROTOTYPES = {
     "sp_ylm_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_conditional_batched": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "sp_ylm_conditional_whitened": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_pixel_transform_workspace_bytes": (ctypes.c_size_t, [_V, _I]),
+    "sp_pixel_transform": (_I, [_V, _I, _V, _V, _L, _V, _V]),
+    "sp_pixel_cov_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
+    "sp_pixel_cov_batched": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _L, _L, _V, _V]),
+    "sp_pixel_render": (_I, [_V, _I, _I, _V, _V, _L, _I, _V, _V]),
     "sp_alpha_beta": (_I, [_D, _I, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sp_set_marginal_constants": (_I, [_V, _V, _V]),
     "sp_set_ylm_moments": (_I, [_V, _V, _V]),

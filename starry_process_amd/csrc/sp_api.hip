@@ -641,6 +641,7 @@ void sp_destroy(sp_handle *h) {
   for (hipStream_t s2 : h->gstream) (void)hipStreamDestroy(s2);
   if (h->gfork) (void)hipEventDestroy(h->gfork);
   if (h->big.ptr) (void)hipFree(h->big.ptr);
+  if (h->pix_A1T.ptr) (void)hipFree(h->pix_A1T.ptr);
   for (auto &c : h->cs_ring) {
     if (c.host) (void)hipHostFree(c.host);
     if (c.dev) (void)hipFree(c.dev);

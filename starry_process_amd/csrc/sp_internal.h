@@ -57,6 +57,9 @@ struct sp_handle {
   // grow-only device scratch of the non-fused ops (sp_cov_*_batched, sp_cho_factor, ...): owned
   // by the handle, so two handles on one GPU never share it
   SpScratch big;
+  // A1^T at degree ydeg, rows padded to a multiple of 32 (sp_pixel.hip; uploaded at the first pixel transform)
+  SpScratch pix_A1T;
+  bool pix_A1T_ready = false;
   // host -> device staging (SpStage): a ring of pinned host + device buffer pairs, each guarded by the
   // event of its last use (no allocation, no stream synchronisation in the launch path)
   struct CsSlot {

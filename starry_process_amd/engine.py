@@ -625,6 +625,53 @@ class Engine(object):
             self._p(ymu), self._p(ycov), self._p(ycho), self._p(status), self._p(ws), self._stream()))
         return ymu, ycov, ycho, status
 
+    # -- pixel space (sp_pixel_*; sp.py:443-487, 1199-1235) ------------------------------
+    def pixel_transform(self, xyz):
+        """M [npts, N] = pi pT(x, y, z) A1, the Ylm -> intensity transform at the points xyz [3, npts] of the unit
+        sphere (sp_pixel_transform; NaN rows where z is NaN)."""
+        torch = _torch()
+        xyz = self.f64(xyz)
+        if xyz.dim() != 2 or xyz.shape[0] != 3 or xyz.shape[1] < 1:
+            raise ValueError("xyz must be (3, npts)")
+        npts = int(xyz.shape[1])
+        ws = torch.empty(int(self._L.sp_pixel_transform_workspace_bytes(self._h, npts)), dtype=torch.uint8,
+                         device=self.device)
+        M = self.empty(npts, self.N)
+        check(self._L.sp_pixel_transform(self._h, npts, self._p(xyz), self._p(M), self.N, self._p(ws),
+                                         self._stream()))
+        return M
+
+    def pixel_cov(self, M, cov):
+        """(M cov) M^T, exactly symmetric (sp_pixel_cov_batched): cov [N, N] -> [npts, npts], or a stack of S
+        covariances [S, N, N] -> [S, npts, npts] in one call.  M [npts, N] from pixel_transform."""
+        torch = _torch()
+        M, cov = self.f64(M), self.f64(cov)
+        npts, N = M.shape
+        assert N == self.N and cov.shape[-2:] == (N, N)
+        single = cov.dim() == 2
+        cov = cov.reshape(-1, N, N).contiguous()
+        S = int(cov.shape[0])
+        out = self.empty(S, npts, npts)
+        ws = torch.empty(int(self._L.sp_pixel_cov_workspace_bytes(self._h, S, npts)), dtype=torch.uint8,
+                         device=self.device)
+        check(self._L.sp_pixel_cov_batched(self._h, S, npts, self._p(M), N, self._p(cov), N * N, self._p(out), npts,
+                                           npts * npts, self._p(ws), self._stream()))
+        return out[0] if single else out
+
+    def pixel_render(self, M, y, unit_background=True):
+        """Images M y (sp_pixel_render): y [..., N] -> [..., npix]; unit_background adds 1 to y_0 first, i.e. the
+        column M[:, 0] (1 on a grid, NaN off it).  M [npix, N] from pixel_transform."""
+        M, y = self.f64(M), self.f64(y)
+        npix, N = M.shape
+        if y.dim() < 1 or y.shape[-1] != N:
+            raise ValueError("the last dimension of y must be the number of Ylm coefficients (%d)" % N)
+        lead = tuple(y.shape[:-1])
+        y2 = y.reshape(-1, N).contiguous()
+        out = self.empty(*(lead + (npix,)))
+        check(self._L.sp_pixel_render(self._h, int(y2.shape[0]), npix, self._p(y2), self._p(M), N,
+                                      int(bool(unit_background)), self._p(out), self._stream()))
+        return out
+
     # -- fused likelihood ----------------------------------------------------------
     def workspace(self, S, K, M):
         torch = _torch()

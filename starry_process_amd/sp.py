@@ -27,7 +27,8 @@ import numpy as np
 from .defaults import defaults
 from .engine import get_engine, make_stars
 from .flux import FluxIntegral
-from .ops import AlphaBetaOp, CheckBoundsOp, Eager
+from .ops import AlphaBetaOp, CheckBoundsOp, Eager, _is_torch
+from .pixel import latlon_to_xyz, mollweide_grid
 from .temporal import kernel_id
 
 __all__ = ["StarryProcess", "StarryProcessSum"]
@@ -131,6 +132,10 @@ class StarryProcess(object):
             device=kwargs.get("device"),
         )
         self._z = None
+        # Mollweide image size (sp.py:243-244) and its transform, formed on the device at first use
+        self._mx = int(kwargs.get("mx", defaults["mx"]))
+        self._my = int(kwargs.get("my", defaults["my"]))
+        self._M = None
 
     def _moments_np(self):
         if self._host_moments is None:
@@ -387,6 +392,38 @@ class StarryProcess(object):
         L, info = self._engine.cho_factor(self._cov_ylm)
         L = L.cpu().numpy()
         return Eager(np.full_like(L, np.nan) if int(info.reshape(-1)[0].item()) else L)
+
+    # -- the process in pixel space (sp.py:443-487, 1199-1235) --------------------------------
+    def _moments_dev(self):
+        return self._dev_moments if self._dev_moments is not None else self._host_moments
+
+    def _latlon_transform(self, latlon):
+        """M at the lat/lon points (degrees, shape (..., 2), flattened) on the device (visualize.py:86-91)."""
+        assert not _is_torch(latlon), "Input must be a numerical ndarray."
+        lat, lon = np.asarray(latlon).reshape(-1, 2).T
+        return self._engine.pixel_transform(latlon_to_xyz(lat * np.pi / 180, lon * np.pi / 180).reshape(3, -1))
+
+    def mean_pix(self, latlon):
+        """The prior mean at lat/lon points in degrees, ``latlon`` of shape (..., 2): shape (npts,)
+        (sp.py:443-464, A mu_y)."""
+        M = self._latlon_transform(latlon)
+        return Eager(self._engine.pixel_render(M, self._moments_dev()[0], unit_background=False).cpu().numpy())
+
+    def cov_pix(self, latlon):
+        """The prior covariance at lat/lon points in degrees, ``latlon`` of shape (..., 2): shape (npts, npts),
+        exactly symmetric (sp.py:466-487, (A Sigma_y) A^T)."""
+        M = self._latlon_transform(latlon)
+        return Eager(self._engine.pixel_cov(M, self._moments_dev()[1]).cpu().numpy())
+
+    def mollweide(self, y, unit_background=True):
+        """Mollweide images of the Ylm vectors ``y`` (any shape (..., nylm)): shape (..., my, mx), NaN off the
+        ellipse (sp.py:1199-1235).  ``unit_background`` adds 1 to y_0, so an unspotted surface is 1.  The image size
+        comes from the constructor keywords ``mx`` and ``my``; the grid's transform is formed once per instance."""
+        e = self._engine
+        if self._M is None:
+            self._M = e.pixel_transform(mollweide_grid(self._my, self._mx))
+        img = e.pixel_render(self._M, y, unit_background=unit_background)
+        return Eager(img.cpu().numpy().reshape(tuple(img.shape[:-1]) + (self._my, self._mx)))
 
     def sample_ylm(self, t=None, nsamples=1, seed=None):
         """Samples of the spherical-harmonic coefficients from the prior, shape
