@@ -50,6 +50,9 @@ typedef enum {
 #define SP_STAR_NAN 4u      /* NaN reached the final value (sp.py:1186-1188)  */
 #define SP_STAR_STALE_PLAN 8u /* sp_lnlike_ensemble_planned: the star's period, tau
                                or nobs differ from the planned ones; value = NaN   */
+#define SP_STAR_NO_BASIS 16u  /* sp_lnlike_inclinations: a variance <= 0 or G = T^T D^-1 T
+                               does not factor (fewer than 2 ydeg + 1 distinct phases);
+                               value = NaN: evaluate the star another way            */
 
 /* temporal kernels (reference temporal.py:8-16) */
 #define SP_TEMPORAL_NONE 0
@@ -500,6 +503,46 @@ int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, lon
  * lives in the handle's scratch.  nmaps = 0 is SP_OK and touches nothing.                                        */
 int sp_pixel_render(sp_handle *h, int nmaps, int npix, const double *y_dev, const double *M_dev, long ldm,
                     int unit_background, double *out_dev, void *stream);
+
+/* ---- conditional log-likelihoods on a grid of inclinations (calibrate/inclination.py:9-76) -------------------
+ * lnlike[s][j][p] = sp_lnlike_ensemble(conditional = 1) of star s with the moment set select[s][j] (mu_y, Sigma_y)
+ * at inclination inc[p], every (s, j, p) at once -- without a K x K matrix.  Row k of the design matrix is
+ * T(theta_k) Q_i R with T = [1, cos theta, sin theta, ..., cos L theta, sin L theta] (L = ydeg, n = 2 L + 1), so
+ * the flux covariance has rank n and the likelihood reduces to n x n algebra (csrc/sp_incl.hip):
+ *   plan (per star, once per data set)   G = T^T D^-1 T = L_G L_G^T, w_m = L_G^-1 T^T D^-1 r_m, the least-squares
+ *                                        residual, T^T 1, T(theta_0), sum log d;
+ *   model (per set, operator, inclination)  M = (Q R) Sigma_y (Q R)^T and Q R mu_y;
+ *   triple (per star, set, inclination)  the normalisation (sp.py:705-727) assembled into M, H = I + L_G^T M L_G,
+ *                                        its Cholesky factor and the value.
+ * Inputs: t_dev [S,K], flux_dev [S,M,K], diag_dev [S,K] or NULL (then stars[s].data_var), stars_dev [S] (period,
+ * table, baseline_mean, baseline_var, data_var, nobs; inc is not read), rta1_dev [ntab,N] the flux operators,
+ * mean_ylm_dev [B,N] and cov_ylm_dev [B,N,N] the moment sets (DEVICE), select_dev [S,J] int32 (which set each
+ * of a star's J evaluations uses) or NULL with J = B (every set), inc_rad_dev [P] inclinations in RADIANS.
+ * Output lnlike_dev [S,J,P], status_dev [S,J,P] (may be NULL).  zmax and NaN -> -inf as sp_lnlike_ensemble.  A
+ * star that the plan rejects (a variance <= 0 or not finite, or G does not factor: fewer than n distinct
+ * phases, e.g. K < n) gets NaN and SP_STAR_NO_BASIS in every entry: the caller evaluates it another way.
+ * Each value is computed from its own star, set and inclination alone: the same bits in any batch.
+ * ydeg <= 30; B, P and ntab at most 65535.  workspace_dev: sp_lnlike_inclinations_workspace_bytes(h, S, M, ntab,
+ * B, P) bytes (B N^2 + B ntab P n^2 doubles and less).  All launches go to `stream`; nothing is synchronised.   */
+size_t sp_lnlike_inclinations_workspace_bytes(sp_handle *h, int S, int M, int ntab, int B, int P);
+int sp_lnlike_inclinations(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                           const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, int ntab, int B,
+                           const double *mean_ylm_dev, const double *cov_ylm_dev, int J, const int32_t *select_dev,
+                           int P, const double *inc_rad_dev, int normalized, int norm_order, double zmax,
+                           double *lnlike_dev, uint32_t *status_dev, void *workspace_dev, void *stream);
+/* The same in two steps, for a data set evaluated many times: sp_incl_plan_data writes the per-star plan
+ * (sp_incl_plan_bytes(h, S, M) bytes of caller memory; status_dev [S] gets SP_STAR_NO_BASIS or 0, may be NULL);
+ * sp_lnlike_inclinations_planned evaluates from it.  The plan fixes t, flux, the variances, period,
+ * baseline_mean and nobs; baseline_var and table are read from stars_dev at evaluation.  Same workspace.   */
+size_t sp_incl_plan_bytes(sp_handle *h, int S, int M);
+int sp_incl_plan_data(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                      const double *diag_dev, const sp_star *stars_dev, void *plan_dev, uint32_t *status_dev,
+                      void *stream);
+int sp_lnlike_inclinations_planned(sp_handle *h, int S, int M, const void *plan_dev, const sp_star *stars_dev,
+                                   const double *rta1_dev, int ntab, int B, const double *mean_ylm_dev,
+                                   const double *cov_ylm_dev, int J, const int32_t *select_dev, int P,
+                                   const double *inc_rad_dev, int normalized, int norm_order, double zmax,
+                                   double *lnlike_dev, uint32_t *status_dev, void *workspace_dev, void *stream);
 
 /* ---- upstream of the hot path, host only ---------------- */
 /* LatitudeIntegralOp values (ops/latitude/latitude.py, ops/include/latitude.h:

@@ -50,7 +50,7 @@ STAR_DTYPE = np.dtype(
 )
 assert STAR_DTYPE.itemsize == ctypes.sizeof(sp_star) == 56
 
-SP_STAR_NOT_PD, SP_STAR_ZMAX, SP_STAR_NAN, SP_STAR_STALE_PLAN = 1, 2, 4, 8
+SP_STAR_NOT_PD, SP_STAR_ZMAX, SP_STAR_NAN, SP_STAR_STALE_PLAN, SP_STAR_NO_BASIS = 1, 2, 4, 8, 16
 TEMPORAL = {None: 0, "none": 0, "matern32": 1, "expsquared": 2}
 
 # name -> (restype, argtypes); every symbol the header declares
@@ -99,6 +99,13 @@ PROTOTYPES = {
     "sp_pixel_cov_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_pixel_cov_batched": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _L, _L, _V, _V]),
     "sp_pixel_render": (_I, [_V, _I, _I, _V, _V, _L, _I, _V, _V]),
+    "sp_lnlike_inclinations_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
+    "sp_lnlike_inclinations": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _I, _D,
+                                    _V, _V, _V, _V]),
+    "sp_incl_plan_bytes": (ctypes.c_size_t, [_V, _I, _I]),
+    "sp_incl_plan_data": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_lnlike_inclinations_planned": (_I, [_V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _I, _D, _V,
+                                            _V, _V, _V]),
     "sp_alpha_beta": (_I, [_D, _I, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sp_set_marginal_constants": (_I, [_V, _V, _V]),
     "sp_set_ylm_moments": (_I, [_V, _V, _V]),

@@ -17,6 +17,10 @@ callable (log_prob.py:93-102):  [flux,] r, a, b, c, n [, m] [, v] [, i].
 inclination / limb darkening / noise per light curve, one covariance each),
 sharded over the ranks of a ``torch.distributed`` job when one is initialised.
 
+``compute_inclination_pdf`` is the reference's per-star inclination posterior (calibrate/inclination.py:9-76):
+the conditional branch of ``get_log_prob`` at every (light curve, posterior sample, inclination) triple, in one
+device call (``sp_lnlike_inclinations``).
+
 ``EnsembleLogProb`` is the same quantity for MANY hyperparameter samples at once
 (the positions of all walkers / live points of an iteration -- emcee's
 ``vectorize=True``): the data stay on the GPU, the moments come from the device
@@ -26,7 +30,8 @@ import numpy as np
 
 from .sp import StarryProcess
 
-__all__ = ["get_log_prob", "get_log_prob_ensemble", "EnsembleLogProb", "SampleBatches", "MAX_STREAMS"]
+__all__ = ["get_log_prob", "get_log_prob_ensemble", "EnsembleLogProb", "SampleBatches", "MAX_STREAMS",
+           "compute_inclination_pdf"]
 
 # Independent evaluations in flight on one GPU.  Four is where the throughput peaks; a fifth stream LOSES 10-25 %
 # (108k against 120k evaluations/s at cfg3's shape, bench.py; EnsembleLogProb 0.584 -> 0.818 ms per sample with
@@ -414,3 +419,111 @@ class EnsembleLogProb(object):
 
             total = total + log_jac_samples(samples[:, 1], samples[:, 2])
         return total
+
+
+def inclination_sample_indices(nsamples, nlc, ninc_samples, weights=None, seed=None):
+    """Which posterior sample each (light curve, draw) of ``compute_inclination_pdf`` uses: (equal [nsamples] or None,
+    idx [nlc, ninc_samples]).  One ``RandomState(seed)``: with ``weights``, first the systematic resampling to equal
+    weight (one uniform offset, the positions (offset + arange(nsamples)) / nsamples against the normalised cumulative
+    weights -- what the reference takes from dynesty.utils.resample_equal), ``equal`` being the resampled rows; then
+    ``randint(nsamples)`` in the reference's loop order, light curve outer, draw inner (inclination.py:65-68)."""
+    rng = np.random.RandomState(seed)
+    nsamples = int(nsamples)
+    equal = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != nsamples:
+            raise ValueError("one weight per sample")
+        positions = (rng.random_sample() + np.arange(nsamples)) / nsamples
+        cum = np.cumsum(w)
+        cum /= cum[-1]
+        equal = np.minimum(np.searchsorted(cum, positions, side="right"), nsamples - 1)
+    idx = np.empty((int(nlc), int(ninc_samples)), dtype=np.int64)
+    for n in range(int(nlc)):
+        for j in range(int(ninc_samples)):
+            idx[n, j] = rng.randint(nsamples)
+    return equal, idx
+
+
+def compute_inclination_pdf(t, flux, ferr, period, samples, inc=np.linspace(0, 90, 100), ninc_samples=10,
+                            weights=None, seed=None, ydeg=15, u=[0.0, 0.0], baseline_mean=0.0, baseline_log_var=0.0,
+                            apply_jac=True, normalized=True, upstream="device", device=None):
+    """Per-star inclination posteriors (calibrate/inclination.py:9-76, without dynesty): returns
+    dict(inc=inc, lp=(nlc, ninc_samples, ninc_pts)), lp[n, j, k] = get_log_prob(t, ferr=ferr, p=period, ...,
+    marginalize_over_inclination=False)(flux[n], *sample, inc[k]) for the sample drawn for (n, j).
+
+    t: (K,); flux: (nlc, K); ferr: scalar; period: scalar or (nlc,); samples: rows of (r, a, b, c, n[, m][, v]) --
+    m when baseline_mean is None, v (log10 of the baseline variance) when baseline_log_var is None, as get_log_prob
+    orders its free variables; weights: the samples' weights (resampled to equal weight first) or None.  The sample of
+    each (n, j) comes from inclination_sample_indices.  The moments of the drawn samples are formed once each and
+    every (light curve, draw, inclination) triple is ONE device call; log_jac is added when apply_jac is set and no
+    zmax guard applies, as in get_log_prob."""
+    from .defaults import defaults
+    from .engine import get_engine, make_stars
+    from .sp import StarryProcess, _neg_inf_if_nan
+    from .upstream import log_jac
+    from ._lib import SP_STAR_NO_BASIS
+
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    K = t.shape[0]
+    flux = np.atleast_2d(np.asarray(flux, dtype=np.float64))
+    nlc = flux.shape[0]
+    if flux.shape[1] != K:
+        raise ValueError("`flux` must be (nlc, K) like `t`")
+    inc = np.asarray(inc, dtype=np.float64).reshape(-1)
+    samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+    nfree = 5 + (baseline_mean is None) + (baseline_log_var is None)
+    if samples.shape[1] != nfree:
+        raise ValueError("samples must have %d columns: r, a, b, c, n%s%s" % (
+            nfree, ", m" if baseline_mean is None else "", ", v" if baseline_log_var is None else ""))
+    equal, idx = inclination_sample_indices(samples.shape[0], nlc, ninc_samples, weights, seed)
+    if equal is not None:
+        samples = samples[equal]
+    used, sel = np.unique(idx.reshape(-1), return_inverse=True)
+    sm = samples[used]
+    e = get_engine(ydeg, 2, device)
+    means, covs, jac = [], [], np.zeros(used.shape[0])
+    for b_, row in enumerate(sm):
+        r, a, b, c, n = (float(x) for x in row[:5])
+        if upstream == "device":
+            from .upstream_device import ylm_moments_device
+
+            mu, cov = ylm_moments_device(e, r=r, dr=defaults["dr"], a=a, b=b, c=c, n=n)
+        elif upstream == "reference":
+            from .upstream import ylm_moments
+
+            mu, cov = ylm_moments(r=r, dr=defaults["dr"], a=a, b=b, c=c, n=n, ydeg=ydeg)
+        else:
+            raise ValueError("upstream must be 'reference' or 'device'")
+        means.append(e.f64(mu).reshape(-1))
+        covs.append(e.f64(cov))
+        if apply_jac:
+            jac[b_] = float(log_jac(a, b, ydeg=ydeg))
+    import torch
+
+    mean_ylm, cov_ylm = torch.stack(means), torch.stack(covs)
+    # one system per (light curve, draw): its own baseline terms when they are free parameters
+    S = nlc * int(ninc_samples)
+    col = 5
+    bm = np.full(used.shape[0], 0.0 if baseline_mean is None else float(baseline_mean))
+    if baseline_mean is None:
+        bm, col = sm[:, col], col + 1
+    bv = 10.0 ** (sm[:, col] if baseline_log_var is None else np.full(used.shape[0], float(baseline_log_var)))
+    per = np.repeat(np.broadcast_to(np.asarray(period, dtype=np.float64), (nlc,)), int(ninc_samples))
+    stars = make_stars(S, period=per, baseline_mean=bm[sel], baseline_var=bv[sel], data_var=float(ferr) ** 2)
+    uu = np.asarray(u, dtype=np.float64).reshape(1, -1)
+    fl = np.repeat(flux, int(ninc_samples), axis=0)
+    out, status = e.lnlike_inclinations(np.broadcast_to(t, (S, K)), fl, stars, e.rTA1L(uu), mean_ylm, cov_ylm,
+                                        inc * (np.pi / 180), select=sel.reshape(S, 1), normalized=normalized,
+                                        zmax=np.inf)
+    lp = _neg_inf_if_nan(out[:, 0, :].cpu().numpy())
+    bad = np.nonzero(np.any(status[:, 0, :].cpu().numpy() & SP_STAR_NO_BASIS, axis=1))[0]
+    for s_ in bad:
+        b_ = int(sel[s_])
+        sp = StarryProcess(ydeg=ydeg, mean_ylm=means[b_].cpu().numpy(), cov_ylm=covs[b_].cpu().numpy(),
+                           normalized=normalized, marginalize_over_inclination=False, normalization_zmax=np.inf,
+                           device=device)
+        lp[s_] = np.asarray(sp.log_likelihood_inclinations(t, fl[s_], float(ferr) ** 2, inc=inc, p=per[s_], u=u,
+                                                           baseline_mean=bm[sel[s_]], baseline_var=bv[sel[s_]]))
+    lp = lp + jac[sel][:, None]
+    return dict(inc=inc, lp=lp.reshape(nlc, int(ninc_samples), inc.shape[0]))

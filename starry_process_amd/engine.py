@@ -672,6 +672,48 @@ class Engine(object):
                                       int(bool(unit_background)), self._p(out), self._stream()))
         return out
 
+    # -- conditional likelihoods on a grid of inclinations (sp_lnlike_inclinations) ---------------
+    def lnlike_inclinations(self, t, flux, stars, rta1, mean_ylm, cov_ylm, inc_rad, select=None, diag=None,
+                            normalized=True, norm_order=20, zmax=0.023):
+        """Conditional-branch log-likelihoods of S stars x J moment sets x P inclinations in one call:
+        t [S, K], flux [S, M, K] (or [S, K]), stars (host sp_star records; inc is not read), rta1 [ntab, N],
+        mean_ylm [B, N], cov_ylm [B, N, N], inc_rad [P], select [S, J] indices of the moment sets (None: J = B,
+        every set for every star), diag [S, K] per-cadence variances or None.
+        Returns (lnlike [S, J, P], status [S, J, P]); SP_STAR_NO_BASIS marks stars the basis cannot take."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        if flux.dim() == 2:
+            flux = flux[:, None, :].contiguous()
+        S, M, K = flux.shape
+        sd = self.stars_to_device(stars)
+        rta1 = self.f64(rta1).reshape(-1, self.N)
+        mean_ylm = self.f64(mean_ylm).reshape(-1, self.N)
+        cov_ylm = self.f64(cov_ylm).reshape(-1, self.N, self.N)
+        B, ntab = int(mean_ylm.shape[0]), int(rta1.shape[0])
+        if cov_ylm.shape[0] != B:
+            raise ValueError("mean_ylm and cov_ylm hold different numbers of moment sets")
+        inc = self.f64(np.asarray(inc_rad, dtype=np.float64).reshape(-1))
+        P = int(inc.shape[0])
+        if select is None:
+            J, sel = B, None
+        else:
+            select = np.array(np.broadcast_to(np.asarray(select, dtype=np.int32), (S, np.shape(select)[-1])))
+            if select.size and (select.min() < 0 or select.max() >= B):
+                raise ValueError("select holds an index outside the %d moment sets" % B)
+            J, sel = int(select.shape[1]), self.dev(select)
+        diag = None if diag is None else self.f64(diag)
+        out = self.empty(S, J, P)
+        status = torch.zeros(S, J, P, dtype=torch.int32, device=self.device)
+        if S == 0 or J == 0 or P == 0:
+            return out, status
+        nbytes = int(self._L.sp_lnlike_inclinations_workspace_bytes(self._h, S, M, ntab, B, P))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self._L.sp_lnlike_inclinations(
+            self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(rta1), ntab, B,
+            self._p(mean_ylm), self._p(cov_ylm), J, self._p(sel), P, self._p(inc), int(bool(normalized)),
+            int(norm_order), float(zmax), self._p(out), self._p(status), self._p(ws), self._stream()))
+        return out, status
+
     # -- fused likelihood ----------------------------------------------------------
     def workspace(self, S, K, M):
         torch = _torch()

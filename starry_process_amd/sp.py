@@ -744,6 +744,111 @@ class StarryProcess(object):
             norm_order=self._normN, zmax=self._normzmax)
         return Eager(_neg_inf_if_nan(out.cpu().numpy()))
 
+    # -- conditional likelihood on a grid of inclinations (calibrate/inclination.py:9-76) ------------------
+    # The conditional branch (sp.py:1052-1188 with marginalize_over_inclination=False) at P inclinations in one
+    # device call, whatever marginalize_over_inclination says (as ylm_conditional).  The flux covariance at one
+    # inclination has rank 2 ydeg + 1 (sp_lnlike_inclinations).  What that route cannot take -- a
+    # time-variable process, a full data covariance or baseline_var matrix, a variance <= 0, a star with fewer
+    # distinct phases than 2 ydeg + 1 -- takes the dense conditional path on one system per inclination.
+    def _check_inc(self, inc):
+        inc = np.atleast_1d(np.asarray(inc, dtype=np.float64)).reshape(-1)
+        if np.any(inc * np.pi / 180 < -1e-6) or np.any(inc * np.pi / 180 > 0.5 * np.pi + 1e-6):
+            raise ValueError("inc out of bounds")
+        return inc
+
+    def _incl_dense(self, t, F, data_cov, inc, p, u, baseline_mean, baseline_var, chunk=16):
+        """(P,) by the dense conditional path: sp_cov_conditional_batched on one system per inclination, then the
+        data and baseline terms and sp_cholesky_lnlike_batched (log_likelihood's general path)."""
+        e, f = self._engine, self._flux
+        f._bind()
+        K = t.shape[0]
+        rta1 = f._rta1(u)
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        bmean, bvar = np.asarray(baseline_mean, dtype=np.float64), np.asarray(baseline_var, dtype=np.float64)
+        Fd = e.f64(np.asarray(F, dtype=np.float64).reshape(-1, K))
+        out = np.empty(inc.shape[0])
+        for c0 in range(0, inc.shape[0], chunk):
+            ii = inc[c0:c0 + chunk]
+            n = ii.shape[0]
+            stars = make_stars(n, period=p, inc_deg=ii, tau=self._tau)
+            cov, mean, z = e.cov_conditional(np.broadcast_to(t, (n, K)), stars, rta1, temporal=self._temporal,
+                                             normalized=self._normalized, norm_order=self._normN)
+            if data_cov.ndim == 0:
+                cov.diagonal(dim1=1, dim2=2).add_(float(data_cov))
+            elif data_cov.ndim == 1:
+                cov.diagonal(dim1=1, dim2=2).add_(e.f64(data_cov))
+            else:
+                cov += e.f64(data_cov)
+            cov += e.f64(bvar) if bvar.ndim else float(bvar)
+            gp = 0.0 if self._normalized else mean[:, None, None]
+            resid = Fd[None, :, :] - (gp + (e.f64(bmean) if bmean.ndim else float(bmean)))
+            val, _ = e.cholesky_lnlike(cov, resid.contiguous())
+            val = val.cpu().numpy()
+            if self._normalized:
+                val = np.where(z.cpu().numpy() > self._normzmax, -np.inf, val)
+            out[c0:c0 + n] = _neg_inf_if_nan(val)
+        return out
+
+    def _incl_basis(self, t, F, stars, utab, diag, inc):
+        """(lnlike [S, P], status [S, P]) of the basis route for t [S, K], F [S, M, K]."""
+        e = self._engine
+        mu, cov = self._moments_dev()
+        out, status = e.lnlike_inclinations(t, F, stars, e.rTA1L(utab), mu, cov, inc * (np.pi / 180), diag=diag,
+                                            normalized=self._normalized, norm_order=self._normN, zmax=self._normzmax)
+        return out[:, 0, :].cpu().numpy(), status[:, 0, :].cpu().numpy()
+
+    def log_likelihood_inclinations(self, t, flux, data_cov, inc=np.linspace(0, 90, 100), p=defaults["p"],
+                                    u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                                    baseline_var=defaults["baseline_var"]):
+        """``log_likelihood(t, flux, data_cov, i, p, u, baseline_mean, baseline_var)`` of the conditional branch at
+        every inclination of ``inc`` (degrees): shape (P,).  ``flux`` is (K,) or (M, K) light curves of one star."""
+        from ._lib import SP_STAR_NO_BASIS
+
+        f = self._flux
+        inc = self._check_inc(inc)
+        t, _, p, u = f._ingest(t, 60.0, p, u)
+        K = t.shape[0]
+        F = np.asarray(flux, dtype=np.float64).reshape(-1, K)
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        bmean, bvar = np.asarray(baseline_mean, dtype=np.float64), np.asarray(baseline_var, dtype=np.float64)
+        fast = (not self._time_variable and data_cov.ndim <= 1 and bmean.ndim == 0 and bvar.ndim == 0
+                and np.all(data_cov > 0) and np.all(np.isfinite(data_cov)))
+        if fast:
+            stars = make_stars(1, period=p, baseline_var=float(bvar), baseline_mean=float(bmean),
+                               data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
+            diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (K,))[None, :]
+            val, status = self._incl_basis(t[None, :], F[None, :, :], stars, u[None, :], diag, inc)
+            if not np.any(status[0] & SP_STAR_NO_BASIS):
+                return Eager(_neg_inf_if_nan(val[0]))
+        return Eager(self._incl_dense(t, F, data_cov, inc, p, u, bmean, bvar))
+
+    def log_likelihood_inclinations_ensemble(self, t, flux, data_cov, inc=np.linspace(0, 90, 100), p=None, u=None,
+                                             baseline_mean=0.0, baseline_var=0.0):
+        """``log_likelihood_inclinations`` of S stars in one device call: shape (S, P).
+
+        t: (K,) or (S, K); flux: (S, K); data_cov: scalar, (S,) or (S, K); p: scalar or (S,);
+        u: (udeg,) shared or (S, udeg); baseline_mean, baseline_var: scalars or (S,)."""
+        from ._lib import SP_STAR_NO_BASIS
+
+        inc = self._check_inc(inc)
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, None, p, u, baseline_mean, baseline_var)
+        S, P = flux.shape[0], inc.shape[0]
+        var = diag if diag is not None else stars["data_var"][:, None]
+        dense = ~np.all((var > 0) & np.isfinite(var), axis=1)
+        out = np.empty((S, P))
+        if not self._time_variable:
+            val, status = self._incl_basis(t, flux[:, None, :], stars, utab, diag, inc)
+            out[:] = _neg_inf_if_nan(val)
+            dense |= np.any(status & SP_STAR_NO_BASIS, axis=1)
+        else:
+            dense[:] = True
+        for s_ in np.nonzero(dense)[0]:
+            dc = diag[s_] if diag is not None else stars["data_var"][s_]
+            out[s_] = self._incl_dense(t[s_], flux[s_][None, :], dc, inc, stars["period"][s_],
+                                       utab[stars["table"][s_]], stars["baseline_mean"][s_],
+                                       stars["baseline_var"][s_])
+        return Eager(out)
+
 
 class StarryProcessSum(StarryProcess):
     """Sum of independent processes (several spot populations on one star): the moments of
