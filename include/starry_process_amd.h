@@ -504,6 +504,31 @@ int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, lon
 int sp_pixel_render(sp_handle *h, int nmaps, int npix, const double *y_dev, const double *M_dev, long ldm,
                     int unit_background, double *out_dev, void *stream);
 
+/* ---- time-variable surface maps (sp.py:489-516 sample_ylm(t), sp.py:1237-1282 flux; ops/sample.py:24-33) --------
+ * Lt_dev [Nt, Nt] (row stride ldlt >= Nt) = cho_factor(k(t, t, tau)), the temporal kernel of temporal.py:8-16 with
+ * no jitter: t_dev [Nt] cadence times, temporal SP_TEMPORAL_MATERN32 or SP_TEMPORAL_EXPSQUARED (SP_ERR_INVALID
+ * otherwise).  The Gram matrix is formed in place and factored by sp_cho_factor: a matrix that is not positive
+ * definite (the exp-squared kernel on a dense cadence) gives an all-NaN factor and info_dev[0] = 1 (may be NULL). */
+int sp_temporal_gram(sp_handle *h, int Nt, const double *t_dev, double tau, int temporal, double *Lt_dev, long ldlt,
+                     int32_t *info_dev, void *stream);
+/* ns samples Y[n] = Lt U[n] Ly^T (SampleYlmTemporalOp): Lt_dev [Nt, Nt] (ldlt >= Nt), Ly_dev [N, N] (ldly >= N) lower
+ * factors -- only their lower triangles are read --, U_dev [ns, Nt, N] deviates, Y_dev [ns, Nt, N] (contiguous; written,
+ * never read).  Two triangular products on the matrix cores (csrc/sp_temporal.hip), the samples in
+ * chunks.  A non-finite diagonal entry of Lt or Ly (a factorisation that failed: on_error="nan", math.py:94) gives
+ * an all-NaN Y and status_dev[0] = 1 (may be NULL; 0 otherwise); the call still returns SP_OK.  Each sample is
+ * computed from its own deviates alone: the same bits in any batch.  ns <= 65535; ns = 0 is SP_OK and touches
+ * nothing.  workspace_dev: sp_ylm_temporal_workspace_bytes(h, ns, Nt) bytes (0 for ns = 0; at most about 128 MiB
+ * beyond the two padded factors).  All launches go to `stream`; nothing is synchronised.                      */
+size_t sp_ylm_temporal_workspace_bytes(sp_handle *h, int ns, int Nt);
+int sp_ylm_temporal(sp_handle *h, int ns, int Nt, const double *Lt_dev, long ldlt, const double *Ly_dev, long ldly,
+                    const double *U_dev, double *Y_dev, void *workspace_dev, int32_t *status_dev, void *stream);
+/* Light curves of time-variable maps, the diagonal of tensordot(A, y) (sp.py:1271-1276) without forming it:
+ *   out[r][k] = A[k, :] . y[r][k][:]       A_dev [Nt, N] (row stride lda >= N), y_dev [nrows, Nt, N], out_dev [nrows, Nt]
+ * normalized != 0 then maps each row to (1 + F) / mean(1 + F) - 1 (sp.py:1277-1280).  The sums run in a fixed order:
+ * a row's values do not depend on the other rows.  nrows = 0 is SP_OK and touches nothing.                    */
+int sp_flux_rows(sp_handle *h, int nrows, int Nt, const double *A_dev, long lda, const double *y_dev, int normalized,
+                 double *out_dev, void *stream);
+
 /* ---- conditional log-likelihoods on a grid of inclinations (calibrate/inclination.py:9-76) -------------------
  * lnlike[s][j][p] = sp_lnlike_ensemble(conditional = 1) of star s with the moment set select[s][j] (mu_y, Sigma_y)
  * at inclination inc[p], every (s, j, p) at once -- without a K x K matrix.  Row k of the design matrix is
@@ -607,7 +632,8 @@ int sp_profile_end(sp_handle *h, long *launches, double *total_ms, double *flops
  * profiling is on): 0 symmetric trailing updates (what sp_profile_end reports), 2 every panel
  * launch under its own pair of events (5: the same, kept apart so that both may be armed),
  * 4 the panel launches of a whole super-panel under ONE pair (cheap enough for a timed region).
- * Kinds 1 and 3 are not produced any more.  Scopes nest.  Stops the profile like sp_profile_end;
+ * 6 and 7 the two triangular products of sp_ylm_temporal (pass 1 Ly U^T, pass 2 Lt Wt^T), one pair
+ * per chunk of samples.  Kinds 1 and 3 are not produced any more.  Scopes nest.  Stops the profile like sp_profile_end;
  * may be called for several kinds in a row.                                                  */
 int sp_profile_kind(sp_handle *h, int kind, long *launches, double *total_ms, double *flops);
 /* The same with both flop counts (round 6): `flops` is the ALGORITHMIC count -- the K cadences' rows and the M residual

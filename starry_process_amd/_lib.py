@@ -106,6 +106,10 @@ PROTOTYPES = {
     "sp_incl_plan_data": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_lnlike_inclinations_planned": (_I, [_V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _I, _D, _V,
                                             _V, _V, _V]),
+    "sp_temporal_gram": (_I, [_V, _I, _V, _D, _I, _V, _L, _V, _V]),
+    "sp_ylm_temporal_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
+    "sp_ylm_temporal": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _V, _V, _V, _V]),
+    "sp_flux_rows": (_I, [_V, _I, _I, _V, _L, _V, _I, _V, _V]),
     "sp_alpha_beta": (_I, [_D, _I, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sp_set_marginal_constants": (_I, [_V, _V, _V]),
     "sp_set_ylm_moments": (_I, [_V, _V, _V]),

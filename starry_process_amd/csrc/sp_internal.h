@@ -98,7 +98,9 @@ struct sp_handle {
 // for a timed region: 2 pairs per K = 1000 factorisation); SP_PROF_CHAIN and SP_PROF_PANEL_LAUNCH:
 // every panel launch under its own pair (comparable with rocprofv3's durations)
 enum {
-  SP_PROF_SYRK = 0, SP_PROF_CHAIN = 2, SP_PROF_PANELS = 4, SP_PROF_PANEL_LAUNCH = 5, SP_PROF_NKINDS = 6
+  SP_PROF_SYRK = 0, SP_PROF_CHAIN = 2, SP_PROF_PANELS = 4, SP_PROF_PANEL_LAUNCH = 5,
+  SP_PROF_TRI1 = 6, SP_PROF_TRI2 = 7,   // the triangular products of sp_ylm_temporal (sp_temporal.hip)
+  SP_PROF_NKINDS = 8
 };
 
 // brackets the launches issued during its lifetime with a pair of events on `st`.  Scopes nest (the

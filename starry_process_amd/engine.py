@@ -304,7 +304,7 @@ class Engine(object):
         self._moments_owner = None
         check(self._L.sp_set_ylm_moments_dev(self._h, self._p(mean_ylm), self._p(cov_ylm), self._stream()))
 
-    PROF_KINDS = {"syrk": 0, "chain": 2, "panels": 4, "panel_launch": 5}
+    PROF_KINDS = {"syrk": 0, "chain": 2, "panels": 4, "panel_launch": 5, "tri1": 6, "tri2": 7}
 
     def profile_begin(self, max_launches, kinds=("syrk",)):
         """Bracket the factorisation's launches of the given kinds with HIP events on their stream
@@ -670,6 +670,51 @@ class Engine(object):
         out = self.empty(*(lead + (npix,)))
         check(self._L.sp_pixel_render(self._h, int(y2.shape[0]), npix, self._p(y2), self._p(M), N,
                                       int(bool(unit_background)), self._p(out), self._stream()))
+        return out
+
+    # -- time-variable surface maps (sp_temporal_gram, sp_ylm_temporal, sp_flux_rows; sp.py:489-516, 1237-1282) ------
+    def temporal_gram(self, t, tau, temporal):
+        """(Lt [Nt, Nt], info [1]): the lower Cholesky factor of the temporal kernel k(t, t, tau) with no jitter,
+        temporal "matern32" or "expsquared"; all NaN and info 1 if it is not positive definite."""
+        torch = _torch()
+        t = self.f64(t).reshape(-1)
+        Nt = int(t.shape[0])
+        if Nt < 1:
+            raise ValueError("t must hold at least one time")
+        Lt = self.empty(Nt, Nt)
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        check(self._L.sp_temporal_gram(self._h, Nt, self._p(t), float(tau), TEMPORAL[temporal], self._p(Lt), Nt,
+                                       self._p(info), self._stream()))
+        return Lt, info
+
+    def ylm_temporal(self, Lt, Ly, U, status=None):
+        """Y[n] = Lt U[n] Ly^T (sp_ylm_temporal): Lt [Nt, Nt], Ly [N, N] (lower triangles read), U [ns, Nt, N] ->
+        Y [ns, Nt, N]; all NaN if a factor's diagonal is not finite (then status [1], if given, gets 1)."""
+        torch = _torch()
+        Lt, Ly, U = self.f64(Lt), self.f64(Ly), self.f64(U)
+        if U.dim() != 3 or Lt.dim() != 2 or Lt.shape[0] != Lt.shape[1] or Lt.shape[0] != U.shape[1] or \
+                Ly.shape != (self.N, self.N) or U.shape[2] != self.N:
+            raise ValueError("need Lt [Nt, Nt], Ly [N, N] and U [ns, Nt, N] with N = %d" % self.N)
+        ns, Nt = int(U.shape[0]), int(U.shape[1])
+        Y = self.empty(ns, Nt, self.N)
+        ws = torch.empty(int(self._L.sp_ylm_temporal_workspace_bytes(self._h, ns, Nt)), dtype=torch.uint8,
+                         device=self.device)
+        check(self._L.sp_ylm_temporal(self._h, ns, Nt, self._p(Lt), Nt, self._p(Ly), self.N, self._p(U), self._p(Y),
+                                      self._p(ws), self._p(status), self._stream()))
+        return Y
+
+    def flux_rows(self, A, y, normalized=False):
+        """F[..., k] = A[k, :] . y[..., k, :] (sp_flux_rows): A [Nt, N], y [..., Nt, N] -> [..., Nt]; normalized maps
+        every row to (1 + F) / mean(1 + F) - 1."""
+        A, y = self.f64(A), self.f64(y)
+        if A.dim() != 2 or A.shape[1] != self.N or y.dim() < 2 or tuple(y.shape[-2:]) != tuple(A.shape):
+            raise ValueError("y must have shape (..., %d, %d)" % (int(A.shape[0]), self.N))
+        Nt = int(A.shape[0])
+        lead = tuple(y.shape[:-2])
+        y2 = y.reshape(-1, Nt, self.N)
+        out = self.empty(*(lead + (Nt,)))
+        check(self._L.sp_flux_rows(self._h, int(y2.shape[0]), Nt, self._p(A), self.N, self._p(y2),
+                                   int(bool(normalized)), self._p(out), self._stream()))
         return out
 
     # -- conditional likelihoods on a grid of inclinations (sp_lnlike_inclinations) ---------------

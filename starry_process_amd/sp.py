@@ -426,13 +426,34 @@ class StarryProcess(object):
         return Eager(img.cpu().numpy().reshape(tuple(img.shape[:-1]) + (self._my, self._mx)))
 
     def sample_ylm(self, t=None, nsamples=1, seed=None):
-        """Samples of the spherical-harmonic coefficients from the prior, shape
-        (nsamples, nylm) (sp.py:503-507).  The time-variable form (``t`` given) needs the
-        reference's SampleYlmTemporalOp, which is outside this package's scope."""
+        """Samples of the spherical-harmonic coefficients from the prior (sp.py:489-516): shape (nsamples, nylm),
+        or (nsamples, ntimes, nylm) when the times ``t`` are given to a time-variable process (``tau`` set).
+
+        The time-variable samples are Y[n] = Lt U[n] Ly^T with Lt the Cholesky factor of the temporal kernel
+        k(t, t, tau) (no jitter), Ly that of Sigma_y and U = RandomState(seed).normal(size=(nsamples, ntimes,
+        nylm)), ``seed`` defaulting to the constructor's.  As in the reference they have ZERO MEAN: mean_ylm is not
+        added.  If either factorisation fails (the exp-squared kernel on a dense cadence is numerically singular),
+        every value is NaN, as the reference's cho_factor(on_error="nan") gives; nothing is raised."""
         if t is not None:
-            raise NotImplementedError("time-variable Ylm samples are not implemented")
+            if not self._time_variable:
+                raise NotImplementedError("samples at times t need a time-variable process (tau=...)")
+            return Eager(self._sample_ylm_temporal(t, nsamples, seed).cpu().numpy())
         u = self._rng(seed).randn(self._nylm, int(nsamples))
         return Eager((self._mean_ylm[:, None] + np.array(self.cho_cov_ylm) @ u).T)
+
+    def _cho_ylm_dev(self):
+        """Lower Cholesky factor of Sigma_y on the device (all NaN if it does not factor), once per instance."""
+        L = self.__dict__.get("_cho_ylm")
+        if L is None:
+            L = self._cho_ylm = self._engine.cho_factor(self._moments_dev()[1])[0]
+        return L
+
+    def _sample_ylm_temporal(self, t, nsamples, seed):
+        e = self._engine
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        Lt, _ = e.temporal_gram(t, self._tau, self._temporal)
+        U = self._rng(seed).normal(size=(int(nsamples), t.shape[0], self._nylm))
+        return e.ylm_temporal(Lt, self._cho_ylm_dev(), U)
 
     def sample(self, t, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]],
                nsamples=1, eps=defaults["eps"], seed=None):
@@ -449,15 +470,32 @@ class StarryProcess(object):
         return Eager((np.array(self.mean(t, i, p, u))[:, None] + L @ U).T)
 
     def flux(self, y, t, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]]):
-        """Light curves of given spherical-harmonic vectors y (nsamples, nylm)
-        (sp.py:1237-1282), through the device design matrix."""
+        """Light curves of given spherical-harmonic vectors (sp.py:1237-1282), through the device design matrix A.
+        A process that is not time-variable takes y (nsamples, nylm) and returns (nsamples, ntimes).  A
+        time-variable one takes y (..., ntimes, nylm), one map per time (what ``sample_ylm(t)`` returns), and
+        returns F[..., k] = A[k] . y[..., k] with shape (..., ntimes); normalised, each row becomes
+        (1 + F) / mean(1 + F) - 1, and a 2-D y gives (1, ntimes) as in the reference."""
         if self._time_variable:
-            raise NotImplementedError("time-variable maps are not implemented")
+            return self._flux_temporal(y, t, i, p, u)
         y = np.atleast_2d(np.asarray(y, dtype=np.float64))
         A = np.array(self._flux.design_matrix(t, i, p, u))      # (ntimes, nylm)
         flux = (A @ y.T).T
         if self._normalized:
             flux = (1.0 + flux) / np.mean(1.0 + flux, axis=-1).reshape(-1, 1) - 1.0
+        return Eager(flux)
+
+    def _flux_temporal(self, y, t, i, p, u):
+        e, f = self._engine, self._flux
+        t, i, p, u = f._ingest(t, i, p, u)
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim < 2 or y.shape[-2:] != (t.shape[0], self._nylm):
+            raise ValueError("y must have shape (..., %d, %d) for a time-variable process: one map per time"
+                             % (t.shape[0], self._nylm))
+        f._bind()
+        A = e.design_matrix(t[None, :], make_stars(1, period=p, inc_deg=i), f._rta1(u))[0]
+        flux = e.flux_rows(A, y, normalized=self._normalized).cpu().numpy()
+        if self._normalized and y.ndim == 2:
+            flux = flux.reshape(1, -1)      # (the reference's mean reshaped to (-1, 1) broadcasts a 1-D flux to 2-D)
         return Eager(flux)
 
     # -- conditioning on data (sp.py:767-1002) ---------------------------------------------
