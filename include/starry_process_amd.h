@@ -529,6 +529,44 @@ int sp_ylm_temporal(sp_handle *h, int ns, int Nt, const double *Lt_dev, long ldl
 int sp_flux_rows(sp_handle *h, int nrows, int Nt, const double *A_dev, long lda, const double *y_dev, int normalized,
                  double *out_dev, void *stream);
 
+/* ---- synthetic spotted-star ensembles (calibrate/generate.py:10-190; csrc/sp_generate.hip) --------
+ * S stars painted on an nlat x nlon grid (pixel p = ilat nlon + ilon; npix = nlat nlon): lat_dev [nlat], lon_dev
+ * [nlon] in degrees, w_dev [nlat] the weights cos(lat); spots_dev [nspots, 4] rows (lon, lat, radius, contrast) in
+ * draw order, offsets_dev [S + 1] (star s owns rows offsets[s] .. offsets[s + 1] - 1).  A pixel is in a spot where the
+ * great-circle distance arccos(sin lat1 sin lat2 + cos lat1 cos lat2 cos(lon2 - lon1)) 180 / pi <= radius (NaN: not);
+ * linear != 0 subtracts each covering spot's contrast in turn, linear == 0 sets -contrast (the last spot wins).
+ * X_dev [S, npix] (may be NULL) receives the intensities; WX_dev [roundup(S, 128), ldwx] (ldwx >= roundup(npix, 32),
+ * even) receives w X with zeros everywhere else: the operand of sp_generate_project.  S = 0 is SP_OK.            */
+int sp_generate_paint(sp_handle *h, int S, int nlat, int nlon, const double *lat_dev, const double *lon_dev,
+                      const double *w_dev, const double *spots_dev, const int32_t *offsets_dev, int linear,
+                      double *X_dev, double *WX_dev, long ldwx, void *stream);
+/* The projection's shared factor, once per grid: P = M / pi (M [npix, N], row stride ldm: sp_pixel_transform at the
+ * grid's points), w_dev [npix].  Writes WPT_dev [roundup(N, 128), ldp] = (P^T W) zero-padded (ldp >= roundup(npix,
+ * 32), even) and L_dev [N, N] (row stride ldl) = cho_factor((W P)^T (W P) + eps I), info_dev[0] (may be NULL) 1 if
+ * that is not positive definite (L all NaN).  workspace_dev: sp_generate_gram_workspace_bytes(h) bytes.          */
+size_t sp_generate_gram_workspace_bytes(sp_handle *h);
+int sp_generate_gram(sp_handle *h, int npix, const double *M_dev, long ldm, const double *w_dev, double eps,
+                     double *WPT_dev, long ldp, double *L_dev, long ldl, int32_t *info_dev, void *workspace_dev,
+                     void *stream);
+/* y[s] = s_l . (L L^T)^-1 (W P)^T (W X[s]) for S <= 65535 stars, s_l = exp(-l (l + 1) smoothing^2 / 2) where
+ * smoothing > 0 (1 otherwise): WPT_dev / L_dev from sp_generate_gram, WX_dev from sp_generate_paint (same S, npix;
+ * ldwx, ldp >= roundup(npix, 32)); y_dev [S, N].  Both operands are padded so that every call runs the same product:
+ * a star's y does not depend on the others.  workspace_dev: sp_generate_project_workspace_bytes(h, S) bytes.     */
+size_t sp_generate_project_workspace_bytes(sp_handle *h, int S);
+int sp_generate_project(sp_handle *h, int S, int npix, const double *WPT_dev, long ldp, const double *L_dev, long ldl,
+                        const double *WX_dev, long ldwx, double smoothing, double *y_dev, void *workspace_dev,
+                        void *stream);
+/* Light curves of S maps y_dev [S, N] at K shared times t_dev [K]: flux0[s] = A_s y[s], A_s = sp_design_matrix of
+ * stars_dev[s] (period, inc in radians, table into rta1_dev), the design matrices formed a chunk of stars at a time
+ * (at most 256 MiB).  Then flux[s][k] = f + ferr noise[s][k] with f = flux0 (norm 0), or
+ * (1 + flux0) / (1 + m) - 1 with m the mean (norm 1) or the median (norm 2) of flux0[s].  noise_dev, flux0_dev,
+ * flux_dev: [S, K].  Every sum runs in a fixed order: a star's values do not depend on the batch.  S = 0 is SP_OK.
+ * workspace_dev: sp_generate_flux_workspace_bytes(h, S, K) bytes.                                                */
+size_t sp_generate_flux_workspace_bytes(sp_handle *h, int S, int K);
+int sp_generate_flux(sp_handle *h, int S, int K, const double *t_dev, const sp_star *stars_dev, const double *rta1_dev,
+                     const double *y_dev, const double *noise_dev, double ferr, int norm, double *flux0_dev,
+                     double *flux_dev, void *workspace_dev, void *stream);
+
 /* ---- conditional log-likelihoods on a grid of inclinations (calibrate/inclination.py:9-76) -------------------
  * lnlike[s][j][p] = sp_lnlike_ensemble(conditional = 1) of star s with the moment set select[s][j] (mu_y, Sigma_y)
  * at inclination inc[p], every (s, j, p) at once -- without a K x K matrix.  Row k of the design matrix is

@@ -110,6 +110,13 @@ PROTOTYPES = {
     "sp_ylm_temporal_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_temporal": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _V, _V, _V, _V]),
     "sp_flux_rows": (_I, [_V, _I, _I, _V, _L, _V, _I, _V, _V]),
+    "sp_generate_paint": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _L, _V]),
+    "sp_generate_gram_workspace_bytes": (ctypes.c_size_t, [_V]),
+    "sp_generate_gram": (_I, [_V, _I, _V, _L, _V, _D, _V, _L, _V, _L, _V, _V, _V]),
+    "sp_generate_project_workspace_bytes": (ctypes.c_size_t, [_V, _I]),
+    "sp_generate_project": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _L, _D, _V, _V, _V]),
+    "sp_generate_flux_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
+    "sp_generate_flux": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _D, _I, _V, _V, _V, _V]),
     "sp_alpha_beta": (_I, [_D, _I, c_double_p, c_double_p, c_double_p, c_double_p]),
     "sp_set_marginal_constants": (_I, [_V, _V, _V]),
     "sp_set_ylm_moments": (_I, [_V, _V, _V]),

@@ -28,10 +28,11 @@ upstream, and ``depth`` samples are kept in flight on separate streams.
 """
 import numpy as np
 
+from .calibrate_generate import draw_spots, generate
 from .sp import StarryProcess
 
 __all__ = ["get_log_prob", "get_log_prob_ensemble", "EnsembleLogProb", "SampleBatches", "MAX_STREAMS",
-           "compute_inclination_pdf"]
+           "compute_inclination_pdf", "generate", "draw_spots"]
 
 # Independent evaluations in flight on one GPU.  Four is where the throughput peaks; a fifth stream LOSES 10-25 %
 # (108k against 120k evaluations/s at cfg3's shape, bench.py; EnsembleLogProb 0.584 -> 0.818 ms per sample with

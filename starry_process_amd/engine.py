@@ -717,6 +717,98 @@ class Engine(object):
                                    int(bool(normalized)), self._p(out), self._stream()))
         return out
 
+    # -- synthetic ensembles (sp_generate_*; calibrate/generate.py) -------------------------------------------------
+    GEN_ROWS, GEN_DEPTH = 128, 32   # padding of the projection's operands (rows, pixels): sp_generate_paint
+
+    def generate_setup(self, nlon, eps=1e-12):
+        """(WPT, L) of the reference's nlon x nlon // 2 lat/lon grid: WPT [roundup(N, 128), ldp] = (P^T W) zero-padded,
+        P = M / pi the intensity design matrix, and L = cho_factor((W P)^T (W P) + eps I) [N, N] (sp_generate_gram).
+        Formed once per (nlon, eps) and kept on the engine (one grid at a time)."""
+        torch = _torch()
+        key = (int(nlon), float(eps))
+        cache = self.__dict__.get("_gen_setup")
+        if cache is not None and cache[0] == key:
+            return cache[1]
+        self._gen_setup = None
+        from .calibrate_generate import grid
+
+        lat, lon, w, xyz = grid(nlon)
+        npix = lat.size * lon.size
+        M = self.pixel_transform(xyz)
+        ldp = (npix + self.GEN_DEPTH - 1) // self.GEN_DEPTH * self.GEN_DEPTH
+        Np = (self.N + self.GEN_ROWS - 1) // self.GEN_ROWS * self.GEN_ROWS
+        WPT = torch.empty(Np, ldp, dtype=torch.float64, device=self.device)
+        L = self.empty(self.N, self.N)
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        ws = torch.empty(int(self._L.sp_generate_gram_workspace_bytes(self._h)), dtype=torch.uint8, device=self.device)
+        wd = self.f64(np.repeat(w, lon.size))   # (every uploaded operand stays referenced until the call returns)
+        check(self._L.sp_generate_gram(self._h, npix, self._p(M), self.N, self._p(wd), float(eps), self._p(WPT), ldp,
+                                       self._p(L), self.N, self._p(info), self._p(ws), self._stream()))
+        del M
+        if int(info.cpu()[0]):
+            raise SPError("the projection's Gram matrix is not positive definite (nlon %d, eps %g)" % key)
+        self._gen_setup = (key, (WPT, L))
+        return WPT, L
+
+    def generate_paint(self, nlon, spots, offsets, linear=True, intensities=False):
+        """(X [S, npix] or None, WX [roundup(S, 128), ldwx]): the stars of the spot table spots [nspots, 4] (lon, lat,
+        radius, contrast), star s owning rows offsets[s] .. offsets[s + 1] - 1, painted on the nlon grid
+        (sp_generate_paint).  WX = w X zero-padded is what generate_project reads."""
+        torch = _torch()
+        from .calibrate_generate import grid
+
+        lat, lon, w, _ = grid(nlon, xyz=False)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int32)
+        S = int(offsets.shape[0]) - 1
+        spots = np.ascontiguousarray(spots, dtype=np.float64).reshape(-1, 4)
+        if S < 0 or offsets[0] != 0 or offsets[-1] != spots.shape[0] or np.any(np.diff(offsets) < 0):
+            raise ValueError("offsets must rise from 0 to the number of spots")
+        npix = lat.size * lon.size
+        ldwx = (npix + self.GEN_DEPTH - 1) // self.GEN_DEPTH * self.GEN_DEPTH
+        rows = max(1, (S + self.GEN_ROWS - 1) // self.GEN_ROWS) * self.GEN_ROWS
+        X = self.empty(S, npix) if intensities else None
+        WX = torch.empty(rows, ldwx, dtype=torch.float64, device=self.device)
+        sp = self.f64(spots) if spots.size else None
+        latd, lond, wd, offd = self.f64(lat), self.f64(lon), self.f64(w), self.dev(offsets)
+        check(self._L.sp_generate_paint(self._h, S, lat.size, lon.size, self._p(latd), self._p(lond), self._p(wd),
+                                        self._p(sp), self._p(offd), int(bool(linear)), self._p(X), self._p(WX), ldwx,
+                                        self._stream()))
+        return X, WX
+
+    def generate_project(self, WPT, L, WX, S, smoothing):
+        """y [S, N] = s_l . G^-1 (W P)^T (W X[s]) (sp_generate_project), WPT / L from generate_setup, WX from
+        generate_paint."""
+        torch = _torch()
+        ldp, ldwx = int(WPT.shape[1]), int(WX.shape[1])
+        if int(WX.shape[0]) < max(1, (S + self.GEN_ROWS - 1) // self.GEN_ROWS) * self.GEN_ROWS or \
+                int(WPT.shape[0]) < (self.N + self.GEN_ROWS - 1) // self.GEN_ROWS * self.GEN_ROWS:
+            raise ValueError("WX must come from generate_paint of the same S stars, WPT from generate_setup")
+        y = self.empty(S, self.N)
+        ws = torch.empty(int(self._L.sp_generate_project_workspace_bytes(self._h, S)), dtype=torch.uint8,
+                         device=self.device)
+        check(self._L.sp_generate_project(self._h, int(S), ldp, self._p(WPT), ldp, self._p(L), self.N, self._p(WX),
+                                          ldwx, float(smoothing), self._p(y), self._p(ws), self._stream()))
+        return y
+
+    GEN_NORM = {None: 0, "mean": 1, "median": 2}
+
+    def generate_flux(self, t, stars, rta1, y, noise, ferr, normalization=None):
+        """(flux0, flux) [S, K] (sp_generate_flux): flux0[s] = A_s y[s] at the shared times t [K], A_s the design
+        matrix of stars[s]; flux = flux0 (normalization None) or its mean / median normalisation, plus ferr noise."""
+        torch = _torch()
+        t, y, noise = self.f64(t).reshape(-1), self.f64(y), self.f64(noise)
+        S, K = int(y.shape[0]), int(t.shape[0])
+        if y.shape != (S, self.N) or noise.shape != (S, K) or len(stars) != S:
+            raise ValueError("need y [S, %d], noise [S, K] and S stars" % self.N)
+        flux0, flux = self.empty(S, K), self.empty(S, K)
+        ws = torch.empty(int(self._L.sp_generate_flux_workspace_bytes(self._h, S, K)), dtype=torch.uint8,
+                         device=self.device)
+        sd, rta1 = self.stars_to_device(stars), self.f64(rta1)
+        check(self._L.sp_generate_flux(self._h, S, K, self._p(t), self._p(sd), self._p(rta1), self._p(y),
+                                       self._p(noise), float(ferr), self.GEN_NORM[normalization], self._p(flux0),
+                                       self._p(flux), self._p(ws), self._stream()))
+        return flux0, flux
+
     # -- conditional likelihoods on a grid of inclinations (sp_lnlike_inclinations) ---------------
     def lnlike_inclinations(self, t, flux, stars, rta1, mean_ylm, cov_ylm, inc_rad, select=None, diag=None,
                             normalized=True, norm_order=20, zmax=0.023):
