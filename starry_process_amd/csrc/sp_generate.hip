@@ -23,19 +23,12 @@
 
 #include "sp_internal.h"
 
-int sp_launch_tri_solve(const double *L, int K, long ldl, long strideL, double *B, long strideB, long rs, long cs,
-                        int nrhs, int batch, int mode, hipStream_t st);
-
 namespace {
 
 constexpr int GEN_ROWS = 128;                               // row padding of both projection operands
 constexpr int GEN_DEPTH = 32;                               // depth (pixel) padding
 constexpr size_t GEN_FLUX_CHUNK_BYTES = (size_t)256 << 20;  // design matrices of one chunk of stars
-
-unsigned grid_for(size_t total) {
-  const size_t b = (total + 255) / 256;
-  return (unsigned)(b < 16384 ? (b > 0 ? b : 1) : 16384);
-}
+constexpr size_t GEN_MAX_BLOCKS = 16384;                    // grid_for's cap on the grid-stride kernels
 
 // the reference's Star._angular_distance(lon, self.lon, lat, self.lat) <= radius, in its order of operations
 __device__ __forceinline__ bool in_spot(double lam1, double phi1, double r, double lam2, double sphi2, double cphi2) {
@@ -213,7 +206,7 @@ int sp_generate_paint(sp_handle *h, int S, int nlat, int nlon, const double *lat
   if (!lat_dev || !lon_dev || !w_dev || !offsets_dev || !WX_dev) return SP_ERR_INVALID;
   hipStream_t st = (hipStream_t)stream;
   const int rows = sp_roundup(S, GEN_ROWS);
-  hipLaunchKernelGGL(paint_kernel, dim3(grid_for((size_t)rows * ldwx)), dim3(256), 0, st, S, nlat, nlon, rows, ldwx,
+  hipLaunchKernelGGL(paint_kernel, dim3(grid_for((size_t)rows * ldwx, GEN_MAX_BLOCKS)), dim3(256), 0, st, S, nlat, nlon, rows, ldwx,
                      lat_dev, lon_dev, w_dev, spots_dev, offsets_dev, linear, X_dev, WX_dev);
   SP_LAUNCH_CHECK();
   return SP_OK;
@@ -273,7 +266,7 @@ int sp_generate_project(sp_handle *h, int S, int npix, const double *WPT_dev, lo
   if (rc) return rc;
   // star s is the column of stride Np (its N coefficients contiguous): G^-1 applied one workgroup per star
   if ((rc = sp_launch_tri_solve(L_dev, N, ldl, 0, C, 0, 1, Np, S, 1, 0, st))) return rc;
-  hipLaunchKernelGGL(smooth_kernel, dim3(grid_for((size_t)S * N)), dim3(256), 0, st, S, N, C, (long)Np, smoothing,
+  hipLaunchKernelGGL(smooth_kernel, dim3(grid_for((size_t)S * N, GEN_MAX_BLOCKS)), dim3(256), 0, st, S, N, C, (long)Np, smoothing,
                      y_dev);
   SP_LAUNCH_CHECK();
   return SP_OK;
@@ -296,7 +289,7 @@ int sp_generate_flux(sp_handle *h, int S, int K, const double *t_dev, const sp_s
   const int N = h->N;
   const FluxLayout L(N, S, K);
   double *tr = at<double>(workspace_dev, L.ot), *A = at<double>(workspace_dev, L.oA);
-  hipLaunchKernelGGL(replicate_kernel, dim3(grid_for((size_t)L.chunk * K)), dim3(256), 0, st, L.chunk, K, t_dev, tr);
+  hipLaunchKernelGGL(replicate_kernel, dim3(grid_for((size_t)L.chunk * K, GEN_MAX_BLOCKS)), dim3(256), 0, st, L.chunk, K, t_dev, tr);
   SP_LAUNCH_CHECK();
   for (int c0 = 0; c0 < S; c0 += L.chunk) {
     const int nb = S - c0 < L.chunk ? S - c0 : L.chunk;

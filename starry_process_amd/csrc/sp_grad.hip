@@ -4,7 +4,7 @@
 //   lnL_s = -1/2 r^T C^-1 r - 1/2 log det C - K/2 log 2 pi,      C = C(table_s, flux mean)      (sp.py:1129-1188)
 //   d lnL / dC = G = (alpha alpha^T - C^-1) / 2,  alpha = C^-1 r
 //
-// C^-1 comes from sp_spd_inverse_batched (the identity riding through the blocked factorisation, sp_api.hip).
+// C^-1 comes from sp_spd_inverse_batched (the identity riding through the blocked factorisation, sp_linalg.hip).
 // C depends on the hyperparameters only through the star's kernel TABLE yp[covpts + 4] (the second moment on the
 // lag grid, flux.py:310-320) and the scalar flux mean:  Sigma_ij = spline(|theta_i - theta_j|; yp) T_ij is LINEAR
 // in yp, and the normalisation (sp.py:705-727)
@@ -341,8 +341,6 @@ __global__ __launch_bounds__(256) void grad_bins_reduce_kernel(int np, int nwg, 
     ybar[(size_t)s * np + k] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-}  // namespace
-
 int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double *theta, const double *t,
                          const double *flux, const sp_star *stars, const void *coef, const double *qv,
                          const double *diag, const double *logdet, const int32_t *info, int covpts, int temporal,
@@ -350,7 +348,7 @@ int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double
                          double *partial, double *lnlike, double *ybar, double *meanbar, uint32_t *status,
                          hipStream_t st) {
   const int ntr = Kr / 64, np = covpts + 4;
-  // (part: the scatter's partial tables later -- [S][ntr][4][K] doubles of it here, sp_api.hip: grad_layout)
+  // (part: the scatter's partial tables later -- [S][ntr][4][K] doubles of it here, grad_layout)
   for (int v0 = 0; v0 < M + 3; v0 += 4) {
     hipLaunchKernelGGL(grad_matvec_kernel, dim3(ntr * (ntr + 1) / 2, S), dim3(256), 0, st, K, Kr, M, v0, Cinv, flux, stars,
                        (const SpCoef *)coef, qv, normalized, partial);
@@ -384,3 +382,96 @@ int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
+
+struct GradLayout {
+  size_t inv, cinv, vec, dots, hcoef, logdet, partial, total;
+};
+GradLayout grad_layout(sp_handle *h, int S, int K, int M, int covpts) {
+  const int Kr = sp_roundup(K, SP_NB);
+  GradLayout G;
+  SpCarve c;
+  const size_t d = sizeof(double);
+  G.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
+  G.cinv = c.take(d * (size_t)S * Kr * Kr);
+  G.vec = c.take(d * (size_t)S * (M + 3) * K);       // C^-1 [p, q, 1, r_0 .. r_{M-1}]
+  G.dots = c.take(d * (size_t)S * M * 2);
+  G.hcoef = c.take(d * S);
+  G.logdet = c.take(d * S);
+  {
+    // the scatter's bins per lower tile; before that, the row parts of the products with C^-1 ([S][ntr][4][K])
+    const size_t ntr = Kr / SP_NB, bins = ntr * (ntr + 1) / 2 * (covpts + 4), rows = ntr * 4 * (size_t)K;
+    G.partial = c.take(d * (size_t)S * (bins > rows ? bins : rows));
+  }
+  G.total = c.off;
+  return G;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sp_lnlike_grad_workspace_bytes_multi(sp_handle *h, int S, int K, int M, int covpts) {
+  if (!h || S < 0 || K < 2 || M < 1 || covpts < 1) return 0;
+  return grad_layout(h, S, K, M, covpts).total;
+}
+size_t sp_lnlike_grad_workspace_bytes(sp_handle *h, int S, int K, int covpts) {
+  return sp_lnlike_grad_workspace_bytes_multi(h, S, K, 1, covpts);
+}
+
+int sp_lnlike_grad_marginal(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                            const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                            const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                            void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                            uint32_t *status_dev, void *stream) {
+  return sp_lnlike_grad_marginal_multi(h, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
+                                       temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev,
+                                       meanbar_dev, status_dev, stream);
+}
+
+int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                                  const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                                  const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                                  void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                                  uint32_t *status_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !t_dev || !flux_dev || !stars_dev || !tab_dev || !meanvar_dev || !workspace_dev || !lnlike_dev ||
+      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || M < 1 || covpts < 1 || norm_order < 0 ||
+      norm_order > SP_NORM_MAXORDER)
+    return SP_ERR_INVALID;
+  if (h->xp_covpts != covpts) return SP_ERR_STATE;
+  if (S == 0) return SP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int Kr = sp_roundup(K, SP_NB);
+  const GradLayout G = grad_layout(h, S, K, M, covpts);
+  char *base = static_cast<char *>(workspace_dev);
+  void *ws = base + G.inv;
+  Layout L = make_layout(h, S, K, Kr, true, true);
+  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum), *qv = at<double>(ws, L.qv);
+  double *coef = at<double>(ws, L.coef), *sys = at<double>(ws, L.sys);
+  int32_t *info = at<int32_t>(ws, L.info);
+  double *Cinv = reinterpret_cast<double *>(base + G.cinv), *vec = reinterpret_cast<double *>(base + G.vec);
+  double *hcoef = reinterpret_cast<double *>(base + G.hcoef), *logdet = reinterpret_cast<double *>(base + G.logdet);
+  double *partial = reinterpret_cast<double *>(base + G.partial);
+  int rc;
+  // the covariance as the likelihood sees it, K x K (direct normalisation: sp.py:705-727, 1135-1151)
+  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
+  if (normalized)
+    if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, h->d_xp, temporal, nullptr,
+                               rowsum, st)))
+      return rc;
+  if ((rc = sp_launch_norm_coef(S, K, stars_dev, meanvar_dev, nullptr, normalized, norm_order, zmax, rowsum, qv, coef,
+                                nullptr, st)))
+    return rc;
+  // (straight into the corner of the system the inverse factors: leading dimension Kp)
+  // (the LOWER tiles of the Kr x Kr corner: the system form of the assembly with no rows below the matrix)
+  if ((rc = sp_launch_assemble(S, K, 0, Kr, 1, theta, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, h->d_xp, temporal,
+                               nullptr, normalized, qv, coef, diag_dev, 1, nullptr, sys, L.Kp, (long)L.Kp * L.Kp, st)))
+    return rc;
+  if ((rc = spd_inverse_in_place(h, S, K, L, ws, Cinv, logdet, st))) return rc;
+  return sp_launch_grad_sweep(S, K, Kr, M, Cinv, theta, t_dev, flux_dev, stars_dev, coef, qv, diag_dev, logdet, info,
+                              covpts, temporal, normalized, norm_order, zmax, vec,
+                              reinterpret_cast<double *>(base + G.dots), hcoef, partial, lnlike_dev, ybar_dev,
+                              meanbar_dev, status_dev, st);
+}
+
+}  // extern "C"

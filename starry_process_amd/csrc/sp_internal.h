@@ -334,19 +334,86 @@ void sp_build_flux_constants(int ydeg, int udeg, std::vector<double> &rT,
 void sp_host_rTA1L(const sp_handle *h, const double *u, double *out);
 void sp_host_rTA1L_rev(const sp_handle *h, const double *u, const double *bf, double *bu);
 
-// ---- kernel launchers (one per .hip file) -----------------------------------
+// ---- launchers and helpers by defining file (a function called from another file is declared here only, defaults too)
+// sp_wigner.hip
 int sp_launch_Rx(sp_handle *h, const double *cs_dev /* [n,2] cos,sin */, int n,
                  double *R, double *dR, hipStream_t st);
 int sp_launch_dotRx(sp_handle *h, const double *M, long strideM, long rs,
                     long cs, int rows, const double *R, long strideR,
                     double *out, int batch, hipStream_t st, int transposeR = 0);
-
 // ez, Ez (and the resident copies of mu, Sigma) from device pointers, one launch
 int sp_launch_polar_moments(sp_handle *h, const double *mu_src, const double *cov_src,
                             hipStream_t st);
-
-// C[b] (+)= alpha * A[b] . B[b]^T  on the matrix cores (sp_gemm.hip): A: Mrows x Kd (lda), B: Nrows x Kd
-// (ldb), C: Mrows x Nrows (ldc); beta is 0 or 1; lower_only: only tiles with tile_i >= tile_j.
+// sp_table.hip
+int sp_launch_kernel_table(sp_handle *h, const double *rta1_dev, int ntab,
+                           int covpts, const double *xp_dev, double *tab_dev,
+                           double *meanvar_dev, hipStream_t st, int nsets = 0, const double *ez_dev = nullptr,
+                           const double *Ez_dev = nullptr);
+// sp_assemble.hip
+int sp_launch_theta(int S, int K, const double *t, const sp_star *stars,
+                    double *theta, hipStream_t st, int32_t *info = nullptr,
+                    uint32_t *status = nullptr, const double *tab = nullptr, int covpts = 0,
+                    double *ptab = nullptr);
+int sp_launch_rowsum(int S, int K, const double *theta, const double *t,
+                     const sp_star *stars, int covpts, const double *tab,
+                     const double *meanvar, const double *xp, int temporal,
+                     const double *raw, double *rowsum, hipStream_t st);
+int sp_launch_norm_coef(int S, int K, const sp_star *stars, const double *meanvar,
+                        const double *condmean, int normalized, int order,
+                        double zmax, const double *rowsum, double *qv, void *coef,
+                        uint32_t *status, hipStream_t st);
+int sp_launch_assemble(int S, int K, int M, int Kp, int system,
+                       const double *theta, const double *t, const sp_star *stars,
+                       int covpts, const double *tab, const double *meanvar,
+                       const double *xp, int temporal, const double *raw,
+                       int normalized, const double *qv, const void *coef,
+                       const double *diag, int add_noise, const double *flux,
+                       double *out, long ldo, long strideo, hipStream_t st, double *part = nullptr,
+                       int lazy_nfull = 0);
+// LDS the hot form of the assembly needs (assemble_sums_kernel) and the most it may ask for
+#define SP_ASM_LDS_MAX (80 * 1024)
+size_t sp_assemble_sums_lds(int Kp, int covpts, int temporal);
+int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, const double *t,
+                            const sp_star *stars, int covpts, const double *ptab, const double *meanvar,
+                            int temporal, const double *flux, double *sys, hipStream_t st, double *part,
+                            int lazy_nfull, int *nflat);
+int sp_launch_defer_finish(int S, int K, int M, int Kp, const sp_star *stars, const double *meanvar,
+                           const double *condmean, int order, double zmax, const double *part,
+                           const double *diag, const double *flux, double *sys, void *coef, double *rscal,
+                           uint32_t *status, hipStream_t st, int nflat = 0);
+// sp_planasm.hip
+int sp_launch_assemble_planned(int S, int K, int M, int Kp, const PlanDev &plan, const double *t,
+                               const sp_star *stars, int covpts, const double *tab, const double *meanvar,
+                               int temporal, const double *flux, const double *diag, double *sys, int nfull,
+                               int ncolw, int order, double zmax, void *coef, double *rscal, double *ptab, int32_t *info,
+                               uint32_t *status, hipStream_t st, double *img, long lts, int fuse0, double *rid, int dfrom);
+// sp_cond.hip
+int sp_launch_cond_system(const double *B1, const double *A, int N, int Kr, int S, int K, int M, int Kp,
+                          const double *t, const sp_star *stars, int temporal, const void *coef,
+                          const double *diag, const double *flux, double *sys, double *part,
+                          hipStream_t st);
+// sp_small.hip
+bool sp_small_k_serves(int K, int M, int covpts, bool has_diag);
+int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const double *t, const sp_star *stars, int covpts,
+                           const double *tab, const double *meanvar, int temporal, const double *flux, const double *diag,
+                           int order, double zmax, double *lnlike, uint32_t *status_out, hipStream_t st);
+// sp_cholesky.hip
+int sp_launch_cholesky_systems(sp_handle *h, double *sys, int S, int K, int Kp,
+                               int32_t *info, double *invL, hipStream_t st);
+int sp_launch_cholesky_groups(sp_handle *h, int ngroups, const sp_chol_group *grp, int K,
+                              int Kp);
+int sp_launch_lnlike_reduce(const double *sys, int S, int K, int M, int Kp,
+                            const int32_t *info, double *lnlike, uint32_t *status,
+                            hipStream_t st, uint32_t *status_out = nullptr,
+                            const sp_star *stars = nullptr, const void *defer_coef = nullptr,
+                            const double *rscal = nullptr, int dvec = 0);
+int sp_launch_pad_in(const double *A, int K, long lda, long strideA, double *sys,
+                     int Kp, int M, const double *resid, int S, hipStream_t st, int ident = 0,
+                     int32_t *nonfinite = nullptr);
+int sp_launch_pad_out(const double *sys, int Kp, double *A, int K, long lda,
+                      long strideA, const int32_t *info, int S, hipStream_t st);
+int sp_launch_cho_solve(const double *L, int K, long ldl, long strideL, double *B,
+                        int nrhs, int batch, hipStream_t st);
 int sp_launch_tri_solve(const double *L, int K, long ldl, long strideL, double *B, long strideB,
                         long rs, long cs, int nrhs, int batch, int mode, hipStream_t st);
 int sp_launch_transpose(const double *in, long ldi, long stridei, double *out, int K, int batch,
@@ -354,6 +421,8 @@ int sp_launch_transpose(const double *in, long ldi, long stridei, double *out, i
 int sp_launch_tri_mask(double *A, int K, int batch, int upper, double dscale, hipStream_t st);
 int sp_launch_chol_rev_finish(const double *S, const double *L, long ldl, long strideL, double *out,
                               int K, int batch, hipStream_t st);
+// sp_gemm.hip: C[b] (+)= alpha * A[b] . B[b]^T  on the matrix cores: A: Mrows x Kd (lda), B: Nrows x Kd
+// (ldb), C: Mrows x Nrows (ldc); beta is 0 or 1; lower_only: only tiles with tile_i >= tile_j.
 int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B,
                       long ldb, long strideB, double *C, long ldc, long strideC,
                       int Mrows, int Nrows, int Kd, double alpha, int beta,
@@ -367,23 +436,30 @@ int sp_launch_panel2(int layout, const SpReduceArgs *red, double *sys, long ld, 
                      int next_nact, int last, int what, int ncu, double *img, long lts, int32_t *info,
                      hipStream_t st, const LazyCov *lazy);
 // symmetric trailing update C -= X X^T (lower 64 x 64 tiles, tile (0, 0) skipped) whose tile-(0, 0)
-// workgroup factors the pivot block described by `df` (sp_paneldiag.h)
+// workgroup factors the pivot block described by `df` (sp_paneldiag.h; sp_gemm.hip)
 int sp_launch_syrk_diag(const double *X, long ld, long stride, double *T, int n, int kd, int batch,
                         hipStream_t st, const LazyCov *lazy, const DiagFuse *df, int tj_limit = 0);
 
-// reverse sweep of the marginal-branch likelihood (sp_grad.hip): C^-1 (lower tiles in, full out) -> lnL, the table's
-// adjoint ybar [S, covpts + 4], the flux mean's adjoint [S]
-// LDS the hot form of the assembly needs (sp_assemble.hip, assemble_sums_kernel) and the most it may ask for
-#define SP_ASM_LDS_MAX (80 * 1024)
-size_t sp_assemble_sums_lds(int Kp, int covpts, int temporal);
-int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double *theta, const double *t,
-                         const double *flux, const sp_star *stars, const void *coef, const double *qv,
-                         const double *diag, const double *logdet, const int32_t *info, int covpts, int temporal,
-                         int normalized, int order, double zmax, double *vec, double *dots, double *hcoef,
-                         double *partial, double *lnlike, double *ybar, double *meanbar, uint32_t *status,
-                         hipStream_t st);
-
 // per-star scratch of the factorisation: three image slots + the chain words (sp_tile.h).  Doubles.
 static inline long sp_lt_stride(int) { return 2 * 4096L; }
+
+// sp_lnlike.hip: the workspace of the likelihood driver, also carved by the SPD inverse and the gradient
+struct Layout {
+  int S, K, M, Kp, N, NWIG;
+  int Kr;   // rows per star of the design-matrix buffers A, B1: roundup(K, 64), the rows beyond K zero
+  size_t theta, rowsum, qv, coef, rscal, info, status, condmean, cs, vrow, Rinc, invL, A,
+      B1, raw, part, sys, total;
+};
+Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool lean = false, int s0 = 0);
+
+// sp_linalg.hip: C^-1 (and log det C) of the matrices already in the top-left K x K corners of the systems of `ws`
+int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
+                         hipStream_t st);
+
+// grid of a grid-stride kernel: blocks of 256 threads covering `total` elements, at most `max_blocks` of them
+static inline unsigned grid_for(size_t total, size_t max_blocks = 8192) {
+  const size_t b = (total + 255) / 256;
+  return (unsigned)(b < max_blocks ? (b > 0 ? b : 1) : max_blocks);
+}
 
 #endif

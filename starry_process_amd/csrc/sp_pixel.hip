@@ -86,11 +86,6 @@ __global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__rest
   }
 }
 
-unsigned grid_for(size_t total) {
-  const size_t b = (total + 255) / 256;
-  return (unsigned)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
-
 size_t pT_ld(int N) { return (size_t)sp_roundup(N, 32); }
 
 // A1^T (leading N x N block of the degree ydeg + udeg change of basis), rows padded to Kp with zeros, on the

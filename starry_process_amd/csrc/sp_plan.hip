@@ -21,10 +21,6 @@
 #include "sp_internal.h"
 #include "sp_cov.h"
 
-int sp_launch_theta(int S, int K, const double *t, const sp_star *stars, double *theta, hipStream_t st,
-                    int32_t *info = nullptr, uint32_t *status = nullptr, const double *tab = nullptr,
-                    int covpts = 0, double *ptab = nullptr);
-
 namespace {
 
 // One workgroup per LOWER 64 x 64 tile of a star (the covariance is symmetric: tiles below the diagonal count

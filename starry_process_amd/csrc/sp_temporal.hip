@@ -29,11 +29,6 @@ constexpr int TT = 64;                         // tile edge of the triangular pr
 using TriCore = MM2<64, 64, 8, 6, 4>;
 constexpr size_t TEMPORAL_CHUNK_BYTES = (size_t)128 << 20;   // U and Wt images of one chunk of samples
 
-unsigned grid_for(size_t total) {
-  const size_t b = (total + 255) / 256;
-  return (unsigned)(b < 8192 ? (b > 0 ? b : 1) : 8192);
-}
-
 __global__ __launch_bounds__(256) void temporal_gram_kernel(int Nt, const double *__restrict__ t, double tau, int kind,
                                                             double *__restrict__ K, long ldk) {
   const size_t total = (size_t)Nt * Nt;

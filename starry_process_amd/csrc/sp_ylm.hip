@@ -19,6 +19,8 @@
 //   ylm_epilogue_kernel  W = G + Sigma_y^-1 - c g g^T mirrored to a full symmetric matrix, and rhs.
 // The "whitened" form (a full data covariance, C = L L^T: the caller passes L^-1 A and L^-1 r) is the same
 // with unit weights and c = 0.  DESIGN.md section 9 gives the reasons for this split.
+#include <algorithm>
+
 #include "sp_internal.h"
 
 namespace {
@@ -196,8 +198,6 @@ __global__ void ylm_status_kernel(int S, const uint32_t *__restrict__ flags, con
   status[s] = f;
 }
 
-}  // namespace
-
 int sp_launch_ylm_gram(int S, int K, int N, const double *A, const double *flux, const double *diag,
                        const sp_star *stars, int whitened, const double *sinv, const double *sinvmu, double *Bt,
                        double *G, double *gh, double *sq, uint32_t *flags, double *W, double *rhs, hipStream_t st) {
@@ -233,3 +233,98 @@ int sp_launch_ylm_status(int S, const uint32_t *flags, const int32_t *info1, con
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
+
+// Caller workspace: [A (design matrices; reused for G = A^T D^-1 A)] [Bt (reused for W)] [g, h] [s, q] [flags,
+// info of W, info of ycov].  The factorisations and solves of the N x N systems are the library's own entry points.
+struct YlmLayout {
+  size_t A, Bt, gh, sq, flags, info1, info2, total;
+};
+YlmLayout ylm_layout(int S, int K, int N) {
+  const size_t Kp = sp_roundup(K, 32), Np = sp_roundup(N, 64), s = (size_t)S;
+  const size_t r0 = std::max(s * K * N, s * Np * Np), r1 = std::max(s * Np * Kp, s * N * N);
+  YlmLayout L;
+  SpCarve c;
+  L.A = c.take(sizeof(double) * r0);
+  L.Bt = c.take(sizeof(double) * r1);
+  L.gh = c.take(sizeof(double) * s * 2 * N);
+  L.sq = c.take(sizeof(double) * s * 2);
+  L.flags = c.take(sizeof(uint32_t) * s);
+  L.info1 = c.take(sizeof(int32_t) * s);
+  L.info2 = c.take(sizeof(int32_t) * s);
+  L.total = c.off;
+  return L;
+}
+
+// from W, rhs in the workspace: ymu, ycov (and ycho), status
+int ylm_finish(sp_handle *h, int S, const YlmLayout &L, void *ws, double *ymu_dev, double *ycov_dev,
+               double *ycho_dev, uint32_t *status_dev, hipStream_t st) {
+  const int N = h->N;
+  double *W = at<double>(ws, L.Bt);
+  int32_t *info1 = at<int32_t>(ws, L.info1), *info2 = at<int32_t>(ws, L.info2);
+  int rc;
+  // W = L_W L_W^T (a W that is not positive definite comes back NaN, and so does every solve with it)
+  if ((rc = sp_cho_factor(h, W, N, N, (long)N * N, S, info1, st))) return rc;
+  if ((rc = sp_cho_solve(h, W, N, N, (long)N * N, ymu_dev, 1, S, st))) return rc;
+  // ycov = W^-1 = cho_solve(W, I), as the reference forms it
+  if ((rc = sp_launch_ylm_eye(S, N, ycov_dev, st))) return rc;
+  if ((rc = sp_cho_solve(h, W, N, N, (long)N * N, ycov_dev, N, S, st))) return rc;
+  if (ycho_dev) {
+    SP_HIP(hipMemcpyAsync(ycho_dev, ycov_dev, sizeof(double) * (size_t)S * N * N, hipMemcpyDeviceToDevice, st));
+    if ((rc = sp_cho_factor(h, ycho_dev, N, N, (long)N * N, S, info2, st))) return rc;
+  }
+  return sp_launch_ylm_status(S, at<uint32_t>(ws, L.flags), info1, ycho_dev ? info2 : nullptr, status_dev, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sp_ylm_conditional_workspace_bytes(sp_handle *h, int S, int K) {
+  if (!h || S < 0 || K < 1) return 0;
+  return ylm_layout(S, K, h->N).total;
+}
+
+int sp_ylm_conditional_batched(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                               const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev,
+                               const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev, double *ycov_dev,
+                               double *ycho_dev, uint32_t *status_dev, void *workspace_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || K < 1 || !t_dev || !flux_dev || !stars_dev || !rta1_dev || !sinv_dev || !sinvmu_dev ||
+      !ymu_dev || !ycov_dev || !workspace_dev)
+    return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const YlmLayout L = ylm_layout(S, K, h->N);
+  void *ws = workspace_dev;
+  double *A = at<double>(ws, L.A);
+  int rc;
+  if ((rc = sp_design_matrix(h, S, K, t_dev, stars_dev, rta1_dev, A, st))) return rc;
+  if ((rc = sp_launch_ylm_gram(S, K, h->N, A, flux_dev, diag_dev, stars_dev, 0, sinv_dev, sinvmu_dev,
+                               at<double>(ws, L.Bt), A, at<double>(ws, L.gh), at<double>(ws, L.sq),
+                               at<uint32_t>(ws, L.flags), at<double>(ws, L.Bt), ymu_dev, st)))
+    return rc;
+  return ylm_finish(h, S, L, ws, ymu_dev, ycov_dev, ycho_dev, status_dev, st);
+}
+
+int sp_ylm_conditional_whitened(sp_handle *h, int S, int K, const double *B_dev, const double *r_dev,
+                                const double *sinv_dev, const double *sinvmu_dev, double *ymu_dev,
+                                double *ycov_dev, double *ycho_dev, uint32_t *status_dev, void *workspace_dev,
+                                void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || K < 1 || !B_dev || !r_dev || !sinv_dev || !sinvmu_dev || !ymu_dev || !ycov_dev ||
+      !workspace_dev)
+    return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const YlmLayout L = ylm_layout(S, K, h->N);
+  void *ws = workspace_dev;
+  int rc;
+  if ((rc = sp_launch_ylm_gram(S, K, h->N, B_dev, r_dev, nullptr, nullptr, 1, sinv_dev, sinvmu_dev,
+                               at<double>(ws, L.Bt), at<double>(ws, L.A), at<double>(ws, L.gh),
+                               at<double>(ws, L.sq), at<uint32_t>(ws, L.flags), at<double>(ws, L.Bt), ymu_dev,
+                               st)))
+    return rc;
+  return ylm_finish(h, S, L, ws, ymu_dev, ycov_dev, ycho_dev, status_dev, st);
+}
+
+}  // extern "C"

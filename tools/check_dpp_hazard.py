@@ -5,7 +5,8 @@ that for the instructions it emits, but inline assembly is opaque to its hazard 
 instruction that PRODUCES a DPP operand directly in front of the asm statement (it did: the select that initialises a
 column of the pivot block's inverse, in front of that column's first step -- an inverse wrong in its tenth digit).  Every
 asm DPP instruction therefore has to bring its own idle states or sit provably behind another one; this script compiles
-the kernels that include sp_diag.h to assembly and looks at what is in front of each v_fmac_f64_dpp.
+every source of the library to assembly, each with its own flags (csrc/Makefile: `make -s print-flags`), and looks at
+what is in front of each v_fmac_f64_dpp.
 
     python tools/check_dpp_hazard.py [extra hipcc flags ...]        exit code 1 and the offending pairs if any"""
 import os
@@ -16,9 +17,12 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "starry_process_amd", "csrc")
-FILES = ["sp_panel.hip", "sp_small.hip"]
-FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-mllvm", "-amdgpu-mfma-vgpr-form=1",
-         "-Wno-unused-function", "--cuda-device-only", "-S"]
+
+
+def sources():
+    """[(file, [its compile flags])] of every source the library builds, from the Makefile"""
+    out = subprocess.run(["make", "-s", "-C", CSRC, "print-flags"], check=True, capture_output=True, text=True).stdout
+    return [(l.split()[0], l.split()[1:]) for l in out.splitlines() if l.strip()]
 
 
 def written(instr):
@@ -61,15 +65,16 @@ def scan(asm_path):
 def check(extra=()):
     out = {}
 
-    def one(f):
+    def one(src):
+        f, flags = src
         with tempfile.TemporaryDirectory() as d:
             s = os.path.join(d, f + ".s")
-            subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + list(extra) + ["-I", CSRC, os.path.join(CSRC, f), "-o", s],
-                           check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["--cuda-device-only", "-S"] + list(extra) +
+                           [os.path.join(CSRC, f), "-o", s], check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             return f, scan(s)
 
-    with ThreadPoolExecutor(len(FILES)) as ex:
-        for f, r in ex.map(one, FILES):
+    with ThreadPoolExecutor(8) as ex:
+        for f, r in ex.map(one, sources()):
             out[f] = r
     return out
 
