@@ -406,6 +406,25 @@ int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const doubl
                                   const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
                                   void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
                                   uint32_t *status_dev, void *stream);
+/* sp_lnlike_grad_marginal_multi, and additionally the derivatives with respect to each star's OWN parameters:
+ *   starbar_dev [S, SP_STARBAR]   d lnL_s / d (summed over the star's M light curves)
+ *     [0] period            sum_ij H_ij T_ij s'(x_ij) dx_ij/dp: x_ij = |theta_i - theta_j|, theta = 2 pi mod(t / p, 1),
+ *                           s' the derivative of the cubic inside its segment (the segment index is data, as the
+ *                           reference's floor is), H the pull-back of d lnL / dC through the normalisation
+ *     [1] tau               sum_ij H_ij s(x_ij) dT_ij/dtau; 0 when temporal == SP_TEMPORAL_NONE
+ *     [2] baseline_mean     sum_m alpha_m . 1
+ *     [3] baseline_var      <G, 1 1^T>,  G = d lnL / dC
+ *     [4] log of a common factor on the star's data variances (sp_star.data_var or its row of diag_dev): <G, D>
+ *     [5] reserved, 0
+ * A star the likelihood rejects (-inf) gets zeros, a ragged star NaN in every slot.  No atomic additions on the way:
+ * starbar is the same bits run after run.  starbar_dev == NULL: SP_ERR_INVALID; everything else (arguments, codes,
+ * workspace size, the other outputs) as sp_lnlike_grad_marginal_multi, whose launches this call repeats before its own. */
+#define SP_STARBAR 6
+int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                                  const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                                  const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                                  void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                                  uint32_t *status_dev, double *starbar_dev, void *stream);
 
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}

@@ -90,6 +90,8 @@ PROTOTYPES = {
     "sp_lnlike_grad_workspace_bytes_multi": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_lnlike_grad_marginal_multi": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                            _V, _V]),
+    "sp_lnlike_grad_marginal_stars": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
+                                           _V, _V, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_ylm_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_conditional_batched": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),

@@ -24,6 +24,19 @@ __device__ __forceinline__ double temporal_factor(int kind, double ti, double tj
   return exp(-(dt * dt) / (2.0 * tau));
 }
 
+// d temporal_factor / d tau, of the function as coded above: Matern-3/2 (1 + x) e^-x with x = sqrt(3) dt / tau has
+// dT/dx = -x e^-x and dx/dtau = -x / tau; the squared exponential exp(-dt^2 / (2 tau)) has dT/dtau = dt^2 / (2 tau^2) T
+__device__ __forceinline__ double temporal_dfactor_dtau(int kind, double ti, double tj,
+                                                        double tau) {
+  if (kind == SP_TEMPORAL_NONE) return 0.0;
+  const double dt = fabs(ti - tj);
+  if (kind == SP_TEMPORAL_MATERN32) {
+    const double x = 1.7320508075688772 * dt / tau;
+    return x * x / tau * exp(-x);
+  }
+  return (dt * dt) / (2.0 * tau * tau) * exp(-(dt * dt) / (2.0 * tau));
+}
+
 // sums over the 16 lanes of a DPP row, N values at once, result in every lane: four exchange-and-add steps on the
 // cross-lane data path (quad_perm xor 1, xor 2, row_half_mirror, row_mirror; two 32-bit moves per double).
 // __shfl_xor(double, k, 16) compiles to ds_bpermute_b32 pairs -- a round trip through the LDS crossbar per step

@@ -136,12 +136,20 @@ __global__ __launch_bounds__(256) void grad_matvec_reduce_kernel(int K, int ntr,
 // the alpha_m stay in vec[s][3 + m].  With M light curves on one covariance (sp.py:1162-1171)
 //   lnL = sum_m -1/2 r_m^T C^-1 r_m - M/2 log det C - M K/2 log 2 pi,      G = (sum_m alpha_m alpha_m^T - M C^-1) / 2:
 // every quadratic form in alpha below is summed over m, every term of C^-1 alone counts M times.
+// STARS (sp_lnlike_grad_marginal_stars): three of the per-star derivatives are contractions of G with matrices the sums
+// below already hold -- baseline_mean: r = flux - mean - baseline_mean, d lnL / dr = -alpha: sum_m alpha_m.1 (O1);
+// baseline_var: dC = 1 1^T, <G, 1 1^T> = (sum_m (alpha_m.1)^2 - M 1^T C^-1 1) / 2 (O2, mt[3]); the log of a common factor
+// on the data variances: dC = D, <G, D> = (sum_m alpha_m^T D alpha_m - M tr(C^-1 D)) / 2 (AD, mt[4]) -- D and b 1 1^T are
+// added behind the normalisation, so none of the three passes through it.  starbar[s][2..5]; slots 0 and 1 are
+// grad_stars_kernel's.
+template <bool STARS>
 __global__ __launch_bounds__(256) void grad_scalars_kernel(
     int K, int Kr, int M, const double *__restrict__ Cinv, const double *__restrict__ flux,
     const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef, const double *__restrict__ qv,
     const double *__restrict__ diag, const double *__restrict__ logdet, const int32_t *__restrict__ info,
     int normalized, int order, double zmax, double *__restrict__ vec, double *__restrict__ dots /* [S][M][2] */,
-    double *__restrict__ lnlike, double *__restrict__ meanbar, double *__restrict__ hcoef, uint32_t *__restrict__ status) {
+    double *__restrict__ lnlike, double *__restrict__ meanbar, double *__restrict__ hcoef, uint32_t *__restrict__ status,
+    double *__restrict__ starbar /* [S][SP_STARBAR], STARS only */) {
   __shared__ double red[5][4];
   const int s = blockIdx.x, tid = threadIdx.x, NV = M + 3;
   const sp_star st = stars[s];
@@ -258,6 +266,14 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
     hcoef[s] = dead ? 0.0 : c1;           // (0: the scatter adds nothing for a star the likelihood rejects)
     if (status) status[s] = ((info && info[s]) ? SP_STAR_NOT_PD : 0u) | ((normalized && c.z > zmax) ? SP_STAR_ZMAX : 0u) |
                             (((!(ll == ll) && !bad) || ragged) ? SP_STAR_NAN : 0u);
+    if (STARS) {
+      double *sb = starbar + (size_t)s * SP_STARBAR;
+      const double nanv = __builtin_nan("");
+      sb[2] = ragged ? nanv : (dead ? 0.0 : O1);
+      sb[3] = ragged ? nanv : (dead ? 0.0 : 0.5 * (O2 - Md * mt[3]));
+      sb[4] = ragged ? nanv : (dead ? 0.0 : 0.5 * (AD - Md * mt[4]));
+      sb[5] = ragged ? nanv : 0.0;
+    }
   }
 }
 
@@ -341,12 +357,127 @@ __global__ __launch_bounds__(256) void grad_bins_reduce_kernel(int np, int nwg, 
     ybar[(size_t)s * np + k] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
+// The per-star derivatives that need the K^2 entries (sp_lnlike_grad_marginal_stars): period and timescale.  Sigma_ij =
+// s(x_ij) T_ij with x_ij = |theta_i - theta_j|, theta_i = 2 pi mod(t_i / p, 1), so with the H of the scatter above
+//   d lnL / dp   = sum_ij H_ij T_ij s'(x_ij) dx_ij/dp,     dx_ij/dp = sign(theta_i - theta_j) (-2 pi / p^2) (t_i - t_j)
+//   d lnL / dtau = sum_ij H_ij s(x_ij) dT_ij/dtau          (temporal_dfactor_dtau, sp_cov.h)
+// s'(x) is the derivative of the cubic INSIDE its segment, (1 / dx) sum_m yp[idx + m] c'_m(x0): the segment index is data
+// (the reference differentiates through Theano's floor, whose gradient is zero; so does grad.log_likelihood_with_grad),
+// index and position taken exactly as the scatter takes them.  One workgroup per LOWER tile, as the scatter; the star's
+// table yp in LDS; the two sums in registers, then over the wavefront and over the four wavefronts in a fixed order: one
+// pair per tile into spart[s][tile][2] (no atomics: grad_stars_reduce_kernel adds the pairs in a fixed order, so the
+// result is the same bits run after run).  The factor -2 pi / p^2 is taken once per tile.
+template <int TK, bool ONE>
+__global__ __launch_bounds__(256) void grad_stars_kernel(
+    int K, int Kr, int Mrt, const double *__restrict__ Cinv, const double *__restrict__ theta, const double *__restrict__ t,
+    const sp_star *__restrict__ stars, int covpts, const double *__restrict__ tab, const double *__restrict__ vec,
+    const double *__restrict__ hcoef, double *__restrict__ spart) {
+  extern __shared__ __attribute__((aligned(16))) double yp[];   // covpts + 4
+  __shared__ double red[2][4];
+  const int M = ONE ? 1 : Mrt;
+  const int s = blockIdx.y, np = covpts + 4, tid = threadIdx.x;
+  const sp_star st = stars[s];
+  {
+    const double *src = tab + (size_t)st.table * 5 * np;         // (row 0 of the star's table block: yp)
+    for (int k = tid; k < np; k += 256) yp[k] = src[k];
+  }
+  __syncthreads();
+  const int tile = blockIdx.x;
+  int ta = (int)((sqrtf(8.0f * tile + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
+  while (ta * (ta + 1) / 2 > tile) --ta;
+  while ((ta + 1) * (ta + 2) / 2 <= tile) ++ta;
+  const int tb = tile - ta * (ta + 1) / 2;
+  const int i = tb * 64 + (tid & 63), rq = tid >> 6;
+  const double c1 = hcoef[s];
+  double accp = 0.0, acct = 0.0;
+  if (i < K && c1 != 0.0) {
+    const double *V = vec + (size_t)s * (M + 3) * K, *Al = V + 3 * (size_t)K;     // w in V[0], alpha_m in V[3 + m]
+    const double *Ci = Cinv + (size_t)s * Kr * Kr;
+    const double thi = theta[(size_t)s * K + i], ai = Al[i], wi = V[i], Md = (double)M;
+    const double ti = t[(size_t)s * K + i];
+    const double dx = 6.283185307179586 / covpts, inv_dx = 1.0 / dx;
+    const double mult = ta > tb ? 2.0 : 1.0;
+    const int jend = ta * 64 + 64 < K ? ta * 64 + 64 : K;
+    for (int j = ta * 64 + rq; j < jend; j += 4) {
+      double aa = ai * Al[j];
+      for (int m = 1; m < M; ++m) aa += Al[(size_t)m * K + i] * Al[(size_t)m * K + j];
+      const double H = mult * (c1 * 0.5 * (aa - Md * Ci[(size_t)j * Kr + i]) + wi + V[j]);
+      const double thj = theta[(size_t)s * K + j], tj = t[(size_t)s * K + j];
+      const double T = temporal_factor(TK, ti, tj, st.tau);
+      int idx;
+      double x;
+      {
+#pragma clang fp contract(off)
+        const double lag = fabs(thi - thj);
+        const double qd = lag * inv_dx;
+        idx = (int)qd;
+        x = qd - (double)idx;
+        if (fabs(x - 0.5) > 0.5 - 1.0e-9) {
+          idx = (int)floor(lag / dx);
+          x = qd - (double)idx;
+        }
+        idx = idx < 0 ? 0 : (idx > covpts ? covpts : idx);
+      }
+      const double y0 = yp[idx], y1 = yp[idx + 1], y2 = yp[idx + 2], y3 = yp[idx + 3];
+      const double x2 = x * x, x3 = x2 * x;
+      // the weights of the scatter and their derivatives with respect to x0
+      const double ds = (y0 * (-1.0 / 3.0 + x - 0.5 * x2) + y1 * (-0.5 - 2.0 * x + 1.5 * x2) + y2 * (1.0 + x - 1.5 * x2) +
+                         y3 * (-1.0 / 6.0 + 0.5 * x2)) * inv_dx;
+      const double dth = thi - thj, sgn = dth > 0.0 ? 1.0 : (dth < 0.0 ? -1.0 : 0.0);
+      accp += H * T * ds * (sgn * (ti - tj));
+      if (TK != SP_TEMPORAL_NONE) {
+        const double sv = y0 * (-x / 3.0 + 0.5 * x2 - x3 / 6.0) + y1 * (1.0 - 0.5 * x - x2 + 0.5 * x3) +
+                          y2 * (x + 0.5 * x2 - 0.5 * x3) + y3 * (-x / 6.0 + x3 / 6.0);
+        acct += H * sv * temporal_dfactor_dtau(TK, ti, tj, st.tau);
+      }
+    }
+  }
+  accp = wsum(accp);
+  acct = wsum(acct);
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = accp;
+    red[1][tid >> 6] = acct;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double *P = spart + ((size_t)s * gridDim.x + blockIdx.x) * 2;
+    P[0] = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) * (-6.283185307179586 / (st.period * st.period));
+    P[1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// starbar[s][0..1] = sum over the tiles' pairs in a fixed order: thread k adds the tiles k, k + 256, ..., then the
+// wavefront, then the four wavefronts in order.  A ragged star (whose value is NaN): NaN.  grid (S)
+__global__ __launch_bounds__(256) void grad_stars_reduce_kernel(int K, int nwg, const sp_star *__restrict__ stars,
+                                                                const double *__restrict__ spart,
+                                                                double *__restrict__ starbar) {
+  __shared__ double red[2][4];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  double a = 0.0, b = 0.0;
+  for (int w = tid; w < nwg; w += 256) {
+    a += spart[((size_t)s * nwg + w) * 2];
+    b += spart[((size_t)s * nwg + w) * 2 + 1];
+  }
+  a = wsum(a);
+  b = wsum(b);
+  if ((tid & 63) == 0) {
+    red[0][tid >> 6] = a;
+    red[1][tid >> 6] = b;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const bool ragged = stars[s].nobs > 0 && stars[s].nobs < K;
+    starbar[(size_t)s * SP_STARBAR] = ragged ? __builtin_nan("") : (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    starbar[(size_t)s * SP_STARBAR + 1] = ragged ? __builtin_nan("") : (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
 int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double *theta, const double *t,
                          const double *flux, const sp_star *stars, const void *coef, const double *qv,
                          const double *diag, const double *logdet, const int32_t *info, int covpts, int temporal,
                          int normalized, int order, double zmax, double *vec, double *dots, double *hcoef,
                          double *partial, double *lnlike, double *ybar, double *meanbar, uint32_t *status,
-                         hipStream_t st) {
+                         hipStream_t st, const double *tab = nullptr, double *starbar = nullptr) {
   const int ntr = Kr / 64, np = covpts + 4;
   // (part: the scatter's partial tables later -- [S][ntr][4][K] doubles of it here, grad_layout)
   for (int v0 = 0; v0 < M + 3; v0 += 4) {
@@ -357,8 +488,16 @@ int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double
                        vec);
     SP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(grad_scalars_kernel, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars, (const SpCoef *)coef,
-                     qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar, hcoef, status);
+  // (starbar: sp_lnlike_grad_marginal_stars -- the same launches, the scalars kernel also writes the per-star slots it
+  //  has in hand, and two more launches behind the table's adjoint)
+  if (starbar)
+    hipLaunchKernelGGL(grad_scalars_kernel<true>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
+                       hcoef, status, starbar);
+  else
+    hipLaunchKernelGGL(grad_scalars_kernel<false>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
+                       hcoef, status, starbar);
   SP_LAUNCH_CHECK();
   const size_t lds = sizeof(double) * np;
   if (lds > 60 * 1024) return SP_ERR_INVALID;
@@ -379,6 +518,25 @@ int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double
 #undef SP_SCATTER
   SP_LAUNCH_CHECK();
   hipLaunchKernelGGL(grad_bins_reduce_kernel, dim3((np + 63) / 64, S), dim3(256), 0, st, np, ntr * (ntr + 1) / 2, partial, ybar);
+  SP_LAUNCH_CHECK();
+  if (!starbar) return SP_OK;
+  // period and timescale: one more pass over the lower tiles (the bins are reduced: `partial` takes the tiles' pairs,
+  // 2 doubles per tile where the bins had covpts + 4)
+#define SP_STARS(TK)                                                                                                 \
+  do {                                                                                                               \
+    if (M == 1)                                                                                                      \
+      hipLaunchKernelGGL((grad_stars_kernel<TK, true>), grid, dim3(256), lds, st, K, Kr, M, Cinv, theta, t, stars,    \
+                         covpts, tab, vec, hcoef, partial);                                                          \
+    else                                                                                                             \
+      hipLaunchKernelGGL((grad_stars_kernel<TK, false>), grid, dim3(256), lds, st, K, Kr, M, Cinv, theta, t, stars,   \
+                         covpts, tab, vec, hcoef, partial);                                                          \
+  } while (0)
+  if (temporal == SP_TEMPORAL_NONE) SP_STARS(SP_TEMPORAL_NONE);
+  else if (temporal == SP_TEMPORAL_MATERN32) SP_STARS(SP_TEMPORAL_MATERN32);
+  else SP_STARS(SP_TEMPORAL_EXPSQUARED);
+#undef SP_STARS
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_stars_reduce_kernel, dim3(S), dim3(256), 0, st, K, ntr * (ntr + 1) / 2, stars, partial, starbar);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -406,35 +564,13 @@ GradLayout grad_layout(sp_handle *h, int S, int K, int M, int covpts) {
   return G;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t sp_lnlike_grad_workspace_bytes_multi(sp_handle *h, int S, int K, int M, int covpts) {
-  if (!h || S < 0 || K < 2 || M < 1 || covpts < 1) return 0;
-  return grad_layout(h, S, K, M, covpts).total;
-}
-size_t sp_lnlike_grad_workspace_bytes(sp_handle *h, int S, int K, int covpts) {
-  return sp_lnlike_grad_workspace_bytes_multi(h, S, K, 1, covpts);
-}
-
-int sp_lnlike_grad_marginal(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
-                            const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
-                            const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
-                            void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
-                            uint32_t *status_dev, void *stream) {
-  return sp_lnlike_grad_marginal_multi(h, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
-                                       temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev,
-                                       meanbar_dev, status_dev, stream);
-}
-
-int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
-                                  const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
-                                  const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
-                                  void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
-                                  uint32_t *status_dev, void *stream) {
+// the sweep behind the three entry points; starbar == nullptr: the launches of rounds 4-6, nothing else
+int grad_marginal(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev, const double *diag_dev,
+                  const sp_star *stars_dev, int covpts, const double *tab_dev, const double *meanvar_dev, int temporal,
+                  int normalized, int norm_order, double zmax, void *workspace_dev, double *lnlike_dev, double *ybar_dev,
+                  double *meanbar_dev, uint32_t *status_dev, double *starbar_dev, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !t_dev || !flux_dev || !stars_dev || !tab_dev || !meanvar_dev || !workspace_dev || !lnlike_dev ||
+  if (!h ||!t_dev || !flux_dev || !stars_dev || !tab_dev || !meanvar_dev || !workspace_dev || !lnlike_dev ||
       !ybar_dev || !meanbar_dev || S < 0 || K < 2 || M < 1 || covpts < 1 || norm_order < 0 ||
       norm_order > SP_NORM_MAXORDER)
     return SP_ERR_INVALID;
@@ -471,7 +607,51 @@ int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const doubl
   return sp_launch_grad_sweep(S, K, Kr, M, Cinv, theta, t_dev, flux_dev, stars_dev, coef, qv, diag_dev, logdet, info,
                               covpts, temporal, normalized, norm_order, zmax, vec,
                               reinterpret_cast<double *>(base + G.dots), hcoef, partial, lnlike_dev, ybar_dev,
-                              meanbar_dev, status_dev, st);
+                              meanbar_dev, status_dev, st, tab_dev, starbar_dev);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t sp_lnlike_grad_workspace_bytes_multi(sp_handle *h, int S, int K, int M, int covpts) {
+  if (!h || S < 0 || K < 2 || M < 1 || covpts < 1) return 0;
+  return grad_layout(h, S, K, M, covpts).total;
+}
+size_t sp_lnlike_grad_workspace_bytes(sp_handle *h, int S, int K, int covpts) {
+  return sp_lnlike_grad_workspace_bytes_multi(h, S, K, 1, covpts);
+}
+
+int sp_lnlike_grad_marginal(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                            const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                            const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                            void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                            uint32_t *status_dev, void *stream) {
+  return sp_lnlike_grad_marginal_multi(h, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
+                                       temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev,
+                                       meanbar_dev, status_dev, stream);
+}
+
+int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                                  const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                                  const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                                  void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                                  uint32_t *status_dev, void *stream) {
+  return grad_marginal(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
+                       normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, nullptr,
+                       stream);
+}
+
+int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                                  const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                                  const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                                  void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
+                                  uint32_t *status_dev, double *starbar_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!starbar_dev) return SP_ERR_INVALID;
+  return grad_marginal(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
+                       normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev,
+                       starbar_dev, stream);
 }
 
 }  // extern "C"

@@ -946,6 +946,28 @@ class Engine(object):
             self._p(out), self._p(ybar), self._p(mbar), self._p(status), self._stream()))
         return out, ybar, mbar, status
 
+    def lnlike_grad_marginal_stars(self, t, flux, stars_dev, tab, meanvar, diag=None, covpts=300, temporal=None,
+                                   normalized=True, norm_order=20, zmax=0.023, workspace=None):
+        """``lnlike_grad_marginal`` and, from the same sweep, the derivatives with respect to each star's own
+        parameters (sp_lnlike_grad_marginal_stars) -> (lnlike [S], ybar [S, covpts + 4], meanbar [S], starbar [S, 6],
+        status [S]); starbar[s] = d lnL_s / d (period, tau, baseline_mean, baseline_var, log of a common factor on the
+        star's data variances, reserved 0)."""
+        torch = _torch()
+        S, K = t.shape
+        flux = flux.reshape(S, -1, K)
+        M = flux.shape[1]
+        nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, M, int(covpts)))
+        ws = workspace
+        if ws is None or ws.numel() < nbytes:
+            ws = self._grad_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out, ybar, mbar, sbar = self.empty(S), self.empty(S, covpts + 4), self.empty(S), self.empty(S, 6)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        check(self._L.sp_lnlike_grad_marginal_stars(
+            self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), int(covpts), self._p(tab),
+            self._p(meanvar), TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(ws),
+            self._p(out), self._p(ybar), self._p(mbar), self._p(status), self._p(sbar), self._stream()))
+        return out, ybar, mbar, sbar, status
+
     def grad_workspace(self, S, K, covpts, M=1):
         torch = _torch()
         nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, int(M), int(covpts)))

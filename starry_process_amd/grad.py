@@ -323,6 +323,23 @@ def hyper_gradient(t, flux, data_var, r=defaults["r"], dr=defaults["dr"], a=defa
     return lnl, out
 
 
+# the per-star derivatives of EnsembleGradient(wrt=...), in the order of the device's row (SP_STARBAR slots 0-4)
+_WRT = ("p", "tau", "baseline_mean", "baseline_var", "log_var")
+
+
+def _check_wrt(wrt, has_tau):
+    """``wrt`` as a tuple of known names (None stays None); ValueError otherwise.  No device work."""
+    if wrt is None:
+        return None
+    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+    for name in wrt:
+        if name not in _WRT:
+            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT)))
+    if "tau" in wrt and not has_tau:
+        raise ValueError("wrt: 'tau' needs a timescale (EnsembleGradient(..., tau=...))")
+    return wrt
+
+
 class EnsembleGradient(object):
     """Log-likelihood of an ENSEMBLE of light curves and its gradient with respect to the spot hyperparameters
     (r, a, b, c, n[, dr]) in ONE device sweep per evaluation -- what ``theano.grad`` of the summed
@@ -405,9 +422,24 @@ class EnsembleGradient(object):
         tab, mv = eng.kernel_table(self._rta1, self._covpts)
         return tab[:, 0, :], mv[:, 0], (mu, Sig, tab, mv)
 
-    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None):
+    _WRT = _WRT
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
+                 wrt=None):
+        """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .[, "dr": .]}).
+
+        wrt: None, or a tuple of names out of ("p", "tau", "baseline_mean", "baseline_var", "log_var"): the dict then
+        also holds the derivatives with respect to the stars' OWN parameters, from the same device sweep
+        (sp_lnlike_grad_marginal_stars) and the same one transfer: "p", "baseline_mean", "baseline_var", "log_var" as
+        arrays [S] -- d lnL_s / d of star s's period, baseline mean, baseline variance and the log of a common factor
+        on its data variances (ferr^2, scalar or per cadence; with s_s^2 = exp(log_var) ferr_s^2) -- and "tau" as a
+        float, the sum over the stars (the constructor takes one timescale).  Where the ensemble shares a baseline (or a
+        noise factor), as in calibrate/log_prob.py:7-106, the derivative with respect to the shared value is the sum of
+        the array.  A star the likelihood rejects adds zeros.  d/dp is the derivative of the interpolant inside its
+        segments, as ``log_likelihood_with_grad``'s."""
         import torch
 
+        wrt = _check_wrt(wrt, self._temporal is not None)
         e = self._e
         x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
         hp0 = dict(x0, c=float(c), n=float(n))
@@ -418,9 +450,14 @@ class EnsembleGradient(object):
             yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
             at_point = torch.cuda.Event()
             at_point.record(self._stream)
-            lnl, ybar, mbar, status = e.lnlike_grad_marginal(
-                self._t, self._flux, self._stars, tab, mv, diag=self._diag, covpts=self._covpts,
-                temporal=self._temporal, normalized=self._normalized, workspace=self._ws)
+            sweep_kw = dict(diag=self._diag, covpts=self._covpts, temporal=self._temporal,
+                            normalized=self._normalized, workspace=self._ws)
+            sbar = None
+            if wrt is None:
+                lnl, ybar, mbar, status = e.lnlike_grad_marginal(self._t, self._flux, self._stars, tab, mv, **sweep_kw)
+            else:
+                lnl, ybar, mbar, sbar, status = e.lnlike_grad_marginal_stars(self._t, self._flux, self._stars, tab, mv,
+                                                                             **sweep_kw)
         # three more streams, meanwhile: the tables' derivatives
         bounds = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}
         dy, dm, events = {}, {}, []
@@ -533,19 +570,28 @@ class EnsembleGradient(object):
             if names:
                 DY, DM = torch.stack([dy[k] for k in names]), torch.stack([dm[k] for k in names])
                 parts.insert(0, (DY * Yb).sum(dim=(1, 2)) + (DM * Mb).sum(dim=1))
+            if sbar is not None:
+                parts.append(sbar.reshape(-1))
             host = torch.cat(parts).cpu().numpy()    # (on the main stream, which has waited for the others)
         ng = len(names)
         self.lnlike = host[ng:ng + self.S].copy()
-        self.status = host[ng + self.S:].astype(np.uint32)
+        self.status = host[ng + self.S:ng + 2 * self.S].astype(np.uint32)
         total = float(self.lnlike.sum())
         grad = {k: float(v) for k, v in zip(names, host[:ng])}
+        if sbar is not None:
+            sb = host[ng + 2 * self.S:].reshape(self.S, -1)
+            for k in wrt:
+                col = sb[:, self._WRT.index(k)]
+                grad[k] = float(col.sum()) if k == "tau" else col.copy()
         return total, grad
 
 
 def ensemble_gradient(t, flux, ferr=1.0e-3, p=1.0, r=defaults["r"], a=defaults["a"], b=defaults["b"],
-                      c=defaults["c"], n=defaults["n"], dr=None, **kwargs):
-    """One-shot form of ``EnsembleGradient``: (sum of log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .})."""
-    return EnsembleGradient(t, flux, ferr=ferr, p=p, **kwargs)(r=r, a=a, b=b, c=c, n=n, dr=dr)
+                      c=defaults["c"], n=defaults["n"], dr=None, wrt=None, **kwargs):
+    """One-shot form of ``EnsembleGradient``: (sum of log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .});
+    wrt: the per-star derivatives to return as well (``EnsembleGradient.__call__``)."""
+    wrt = _check_wrt(wrt, bool(kwargs.get("tau")))          # (before any data goes to the device)
+    return EnsembleGradient(t, flux, ferr=ferr, p=p, **kwargs)(r=r, a=a, b=b, c=c, n=n, dr=dr, wrt=wrt)
 
 
 def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], r=defaults["r"], a=defaults["a"],

@@ -1,0 +1,389 @@
+"""
+Per-star derivatives of the ensemble gradient (sp_lnlike_grad_marginal_stars, EnsembleGradient(wrt=...)): period,
+timescale, baseline mean, baseline variance and the log of a common factor on the data variances, for every star of
+the batch from the one device sweep.
+
+  * the outputs the new call shares with sp_lnlike_grad_marginal_multi are that call's;
+  * the raw process against the EXACT contractions <G, dC/d.> formed in NumPy from the oracle's pieces (no step size);
+  * normalised and raw against Richardson differences of the oracle's log-likelihood;
+  * period and timescale against the one-star autograd chain (grad.log_likelihood_with_grad), an independent device route;
+  * rejected and ragged stars, sizes off the tile grid, two limb-darkening tables, bad arguments, determinism.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+
+from conftest import golden
+from starry_process_amd.synthetic import synthetic_star
+
+pytestmark = pytest.mark.gpu
+
+YDEG = 15
+COVPTS = 300
+SLOTS = ("p", "tau", "baseline_mean", "baseline_var", "log_var")
+
+
+def _moments():
+    g = golden("moments_L15")
+    return g["default_mean_ylm"], g["default_cov_ylm"]
+
+
+def _case(S=3, K=96, M=1, normalized=True, tau=None, per_cadence=False, bvar=0.0, bmean=0.0, seed0=0, u=None,
+          tspan=4.0, kernel="matern32"):
+    sts = [synthetic_star(seed0 + s, K, tspan) for s in range(S)]
+    t = np.array([s["t"] for s in sts])
+    if M == 1:
+        flux = np.array([s["flux"] for s in sts])
+    else:
+        # M light curves of one star: the star's signal with independent noise
+        flux = np.array([[sts[s]["flux"] + 1e-3 * np.random.RandomState(500 + 10 * s + m).randn(K)
+                          for m in range(M)] for s in range(S)])
+    p = np.array([s["p"] for s in sts])
+    if per_cadence:
+        var = np.array([np.linspace(1e-6, 3e-6, K) * (1.0 + 0.25 * s) for s in range(S)])
+    else:
+        var = np.full(S, 1e-6)
+    return dict(S=S, K=K, M=M, t=t, flux=flux, p=p, var=var, normalized=normalized, tau=tau, kernel=kernel,
+                bvar=np.broadcast_to(np.asarray(bvar, dtype=float), (S,)).copy(),
+                bmean=np.broadcast_to(np.asarray(bmean, dtype=float), (S,)).copy(),
+                u=np.zeros((S, 2)) if u is None else np.asarray(u, dtype=float))
+
+
+def _device(case, stars_kw=None, new=True, old=True, mom=None, oracle_table=False):
+    """(old call's outputs, new call's outputs) as NumPy: lnlike, ybar, meanbar, [starbar,] status.
+    oracle_table: the kernel tables and flux means the sweep reads (tab_dev, meanvar_dev: inputs of the entry point) are
+    the ORACLE's, uploaded, instead of the device's own (which agree with them to a few 1e-14 of the table's scale)."""
+    from starry_process_amd.engine import get_engine, make_stars
+
+    e = get_engine(YDEG, 2)
+    if mom is None:
+        e.set_moments(*_moments())
+    else:
+        e.set_moments_dev(*mom)
+    utab, table = np.unique(case["u"], axis=0, return_inverse=True)
+    tab, mv = e.kernel_table(e.f64(e.rTA1L(utab)), COVPTS)
+    if oracle_table:
+        tnp, mnp = tab.cpu().numpy().copy(), mv.cpu().numpy().copy()
+        for k in range(utab.shape[0]):
+            op = _process(case, 0)
+            mean, _ = op.flux_mean_cov(case["t"][0], p=1.0, u=utab[k])
+            assert np.abs(tnp[k, 0] - op.tab["yp"]).max() < 1e-11 * np.abs(op.tab["yp"]).max()
+            tnp[k, 0] = op.tab["yp"]
+            for j, name in enumerate(("a0", "a1", "a2", "a3")):
+                tnp[k, 1 + j, :op.tab[name].shape[0]] = op.tab[name]
+            mnp[k] = (mean, op.var)
+        tab, mv = e.f64(tnp), e.f64(mnp)
+    S, K = case["S"], case["K"]
+    kw = dict(period=case["p"], tau=float(case["tau"]) if case["tau"] else 0.0, baseline_var=case["bvar"],
+              baseline_mean=case["bmean"], data_var=case["var"] if case["var"].ndim == 1 else 0.0,
+              table=table.astype(np.int32).reshape(-1))
+    kw.update(stars_kw or {})
+    stars = e.stars_to_device(make_stars(S, **kw))
+    diag = e.f64(np.ascontiguousarray(case["var"])) if case["var"].ndim == 2 else None
+    args = (e.f64(case["t"]), e.f64(np.ascontiguousarray(case["flux"])), stars, tab, mv)
+    okw = dict(diag=diag, covpts=COVPTS, temporal=case["kernel"] if case["tau"] else None,
+               normalized=case["normalized"])
+    a = [x.cpu().numpy() for x in e.lnlike_grad_marginal(*args, **okw)] if old else None
+    b = [x.cpu().numpy() for x in e.lnlike_grad_marginal_stars(*args, **okw)] if new else None
+    return a, b
+
+
+def _process(case, s, mom=None):
+    import oracle.sp_oracle as orc
+
+    mu, Sig = _moments() if mom is None else mom
+    tk = orc.Matern32Kernel if case["kernel"] == "matern32" else orc.ExpSquaredKernel
+    return orc.OracleProcess(mu, Sig, ydeg=YDEG, udeg=2, normalized=case["normalized"], tau=case["tau"],
+                             temporal_kernel=tk, covpts=COVPTS)
+
+
+def _oracle_lnlike(case, s, p=None, tau=None, bmean=None, bvar=None, logvar=0.0):
+    c = dict(case, tau=case["tau"] if tau is None else tau)
+    op = _process(c, s)
+    return op.log_likelihood(case["t"][s], case["flux"][s], case["var"][s] * np.exp(logvar),
+                             p=float(case["p"][s] if p is None else p), u=case["u"][s],
+                             baseline_mean=float(case["bmean"][s] if bmean is None else bmean),
+                             baseline_var=float(case["bvar"][s] if bvar is None else bvar))
+
+
+def exact_raw_starbar(case, s):
+    """(lnL, [d/dp, d/dtau, d/dbaseline_mean, d/dbaseline_var, d/dlog_var]) of star s of a RAW (un-normalised) case,
+    in NumPy from the oracle's pieces: G = (sum_m alpha_m alpha_m^T - M C^-1) / 2 contracted with dC/d. built entry by
+    entry; the period through the derivative of the cubic inside its segment (interpolate_cov's index and x0)."""
+    import oracle.sp_oracle as orc
+
+    assert not case["normalized"]
+    op = _process(case, s)
+    t, p, K = case["t"][s], float(case["p"][s]), case["K"]
+    mean, Sigma = op.flux_mean_cov(t, p=p, u=case["u"][s])
+    tab = op.tab
+    theta = orc.phase(t, p)
+    dth = theta[:, None] - theta[None, :]
+    x = np.abs(dth).reshape(-1)
+    inds = np.floor(x / tab["dx"]).astype("int64")
+    x0 = (x - tab["xp"][inds + 1]) / tab["dx"]
+    ds = ((tab["a1"][inds] + 2.0 * tab["a2"][inds] * x0 + 3.0 * tab["a3"][inds] * x0 ** 2) / tab["dx"]).reshape(K, K)
+    dxdp = np.sign(dth) * (-2.0 * np.pi / p ** 2) * (t[:, None] - t[None, :])
+    T, dT = np.ones((K, K)), np.zeros((K, K))
+    if case["tau"]:
+        tau = float(case["tau"])
+        T = op.temporal_kernel(t, t, tau)
+        dt = np.abs(t[:, None] - t[None, :])
+        if case["kernel"] == "matern32":
+            xx = np.sqrt(3.0) * dt / tau
+            dT = xx ** 2 / tau * np.exp(-xx)
+        else:
+            dT = dt ** 2 / (2.0 * tau ** 2) * T
+    D = np.diag(np.broadcast_to(case["var"][s], (K,)))
+    C = Sigma * T + D + case["bvar"][s]
+    L = orc.cho_factor(C)
+    r = case["flux"][s].reshape(-1, K).T - (mean + case["bmean"][s])
+    M = r.shape[1]
+    al = orc.cho_solve(L, r)
+    Cinv = orc.cho_solve(L, np.eye(K))
+    lnl = -0.5 * np.sum(r * al) - M * np.sum(np.log(np.diag(L))) - 0.5 * K * M * np.log(2 * np.pi)
+    G = 0.5 * (al @ al.T - M * Cinv)
+    return lnl, np.array([np.sum(G * ds * dxdp * T), np.sum(G * Sigma * dT), np.sum(al), np.sum(G), np.sum(G * D)])
+
+
+def _central(f, h):
+    d1 = (f(h) - f(-h)) / (2 * h)
+    d2 = (f(0.5 * h) - f(-0.5 * h)) / h
+    return (4.0 * d2 - d1) / 3.0
+
+
+def _bits(a, b):
+    return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
+
+
+# ---- 2. the outputs shared with the old call --------------------------------------------------------------------
+OLD_CASES = [dict(M=1, normalized=True, tau=None), dict(M=3, normalized=True, tau=0.7),
+             dict(M=1, normalized=False, tau=0.7), dict(M=3, normalized=False, tau=None),
+             dict(M=1, normalized=True, tau=None, K=1000, S=2)]
+
+
+@pytest.mark.parametrize("kw", OLD_CASES, ids=lambda k: "M%d-%s-tau%s-K%d" % (
+    k["M"], "norm" if k["normalized"] else "raw", k["tau"], k.get("K", 100)))
+def test_shared_outputs_are_the_old_calls(kw):
+    """lnlike, meanbar, status: bit-equal.  ybar passes through LDS atomic additions whose order of arrival is not
+    fixed by anything: where the OLD call repeats its own ybar bit for bit the new call must give those bits too,
+    otherwise the difference is bounded by ten times the old call's run-to-run difference.  (On the MI355X runs of
+    this pull request the old call did NOT repeat its ybar bit for bit in any of these cases -- run-to-run differences
+    of 2e-9 to 7e-8 absolute -- so the second bound is the one that held; the new call's ybar differed from the old
+    one's by 0.5 to 1.0 times that.)"""
+    case = _case(K=kw.get("K", 100), S=kw.get("S", 3), M=kw["M"], normalized=kw["normalized"], tau=kw["tau"],
+                 bvar=1e-5)
+    a1, b = _device(case)
+    a2, _ = _device(case, new=False)
+    assert _bits(a1[0], b[0]) and _bits(a1[2], b[2]) and np.array_equal(a1[3], b[4])
+    assert not b[4].any() and np.all(np.isfinite(b[3]))
+    own = np.abs(a1[1] - a2[1]).max()
+    print("old call's run-to-run difference of ybar: %.3g; new against old: %.3g" % (own, np.abs(b[1] - a1[1]).max()))
+    if _bits(a1[1], a2[1]):
+        assert _bits(a1[1], b[1])
+    else:
+        assert np.abs(b[1] - a1[1]).max() <= 10.0 * own
+
+
+def test_wrt_none_is_todays_call_and_wrt_adds_keys():
+    from starry_process_amd.grad import EnsembleGradient
+
+    case = _case(S=3, K=100, tau=1.5, bvar=1e-5)
+    eg = EnsembleGradient(case["t"], case["flux"], ferr=1e-3, p=case["p"], tau=1.5, baseline_var=1e-5)
+    hp = dict(r=18.0, a=0.45, b=0.3, c=0.12, n=6.0)
+    t0, g0 = eg(**hp)
+    l0 = eg.lnlike.copy()
+    t0b, g0b = eg(**hp)
+    t1, g1 = eg(wrt=("p",), **hp)
+    assert set(g0) == {"r", "a", "b", "c", "n"} and set(g1) == set(g0) | {"p"}
+    assert t1 == t0 and np.array_equal(eg.lnlike, l0) and not eg.status.any()
+    for k in g0:
+        own = abs(g0[k] - g0b[k])
+        assert g1[k] == g0[k] if own == 0.0 else abs(g1[k] - g0[k]) <= 10.0 * own, (k, g0[k], g0b[k], g1[k])
+    assert g1["p"].shape == (3,)
+    t2, g2 = eg(wrt=SLOTS, **hp)
+    assert isinstance(g2["tau"], float) and all(g2[k].shape == (3,) for k in SLOTS if k != "tau")
+    assert np.array_equal(g2["p"], g1["p"])
+    # the row of the device call at the object's own tables
+    from starry_process_amd.upstream_device import ylm_moments_device
+
+    e = eg._e
+    mu, Sig = ylm_moments_device(e, **hp)
+    e.set_moments_dev(mu, Sig)
+    tab, mv = e.kernel_table(eg._rta1, eg._covpts)
+    sb = e.lnlike_grad_marginal_stars(eg._t, eg._flux, eg._stars, tab, mv, covpts=eg._covpts, temporal=eg._temporal,
+                                      normalized=True)[3].cpu().numpy()
+    for k, name in enumerate(SLOTS):
+        ref = sb[:, k].sum() if name == "tau" else sb[:, k]
+        assert np.allclose(g2[name], ref, rtol=1e-12, atol=0.0), name
+    assert not sb[:, 5].any()
+    with pytest.raises(ValueError):
+        eg(wrt=("period",), **hp)
+    eg_notau = EnsembleGradient(case["t"], case["flux"], ferr=1e-3, p=case["p"])
+    with pytest.raises(ValueError):
+        eg_notau(wrt=("tau",), **hp)
+    _, g3 = eg_notau(wrt=("p", "log_var"), **hp)
+    assert set(g3) == set(g0) | {"p", "log_var"}
+
+
+# ---- 3. the raw process against the exact contractions -----------------------------------------------------------
+@pytest.mark.parametrize("kw", [dict(M=1, tau=None, K=96), dict(M=2, tau=0.7, K=100, per_cadence=True, bvar=1e-5),
+                                dict(M=1, tau=2.0, K=100, kernel="expsquared", bmean=1e-3),
+                                dict(M=1, tau=None, K=64)],
+                         ids=["M1-K96", "M2-matern-K100-diag-bvar", "expsquared-K100-bmean", "K64"])
+def test_raw_process_equals_the_exact_contractions(kw):
+    """Device and NumPy contract the SAME kernel table (the oracle's, uploaded: the table is an input of the entry
+    point).  d/dp reads the table through its first differences: with each side on its own table -- they agree to a few
+    1e-14 of the table's scale -- the two periods' derivatives differ by up to 8e-8 absolute (4e-9 of the value) on the
+    star whose period puts its lags on the knots, measured on the MI355X; long-double solves on the host move the NumPy
+    statement by 3e-10 at most, so that difference is the tables', not the sweep's."""
+    case = _case(normalized=False, **kw)
+    _, b = _device(case, old=False, oracle_table=True)
+    for s in range(case["S"]):
+        lnl, ref = exact_raw_starbar(case, s)
+        assert abs(b[0][s] - lnl) < 1e-9 * abs(lnl)
+        for k, name in enumerate(SLOTS):
+            err = abs(b[3][s, k] - ref[k])
+            print("star %d %-13s device %.12g exact %.12g (%.1e of the bound)" %
+                  (s, name, b[3][s, k], ref[k], err / (1e-9 * max(abs(ref[k]), 1e-3 * abs(lnl)))))
+            assert err < 1e-9 * max(abs(ref[k]), 1e-3 * abs(lnl)), (s, name, b[3][s, k], ref[k])
+        assert b[3][s, 5] == 0.0
+        if not case["tau"]:
+            assert b[3][s, 1] == 0.0
+
+
+# ---- 4. finite differences of the oracle ------------------------------------------------------------------------
+# steps of the differences; the period's was chosen on the host with the oracle alone, see the test's docstring
+FD_STEPS = dict(p=1e-6, tau=1e-3, baseline_mean=1e-5, baseline_var=1e-7, log_var=1e-3)
+FD_CASES = [dict(normalized=True, tau=None), dict(normalized=False, tau=None),
+            dict(normalized=True, tau=0.7), dict(normalized=False, tau=0.7)]
+
+
+@pytest.mark.parametrize("kw", FD_CASES, ids=lambda k: "%s-tau%s" % ("norm" if k["normalized"] else "raw", k["tau"]))
+def test_against_finite_differences_of_the_oracle(kw):
+    """Richardson differences of OracleProcess.log_likelihood at two step sizes (h and 2 h); their disagreement is the
+    differences' own uncertainty `unc`, which must stay below 1e-3 |fd|; the device's value within 2e-5 max(|fd|, 1)
+    + 2 unc.  Three stars, K = 96, two light curves per star, per-cadence variances, a baseline variance.
+
+    The likelihood is only piecewise smooth in the period (the interpolant is C0 at its knots and a step in p moves
+    K^2 lags across them), so the period's step was chosen with the oracle alone, on these inputs, over
+    h = 1e-7, 3e-7, 1e-6, 3e-6, 1e-5: every one of them meets the cap for every star of all four cases (the largest
+    unc / |fd| found: 2e-5, at h = 1e-5); h = 1e-6 gives unc / |fd| between 8e-9 and 2.6e-7, normalised and raw, with
+    and without the Matern kernel, and is used.  The other parameters are smooth: tau h = 1e-3, baseline_mean 1e-5,
+    baseline_var 1e-7, log_var 1e-3 give unc / |fd| <= 9e-9."""
+    case = _case(S=3, K=96, M=2, per_cadence=True, bvar=1e-5, seed0=7, **kw)
+    _, b = _device(case, old=False)
+    sb, S = b[3], case["S"]
+    for s in range(S):
+        ref = _oracle_lnlike(case, s)
+        assert abs(b[0][s] - ref) < 1e-9 * abs(ref)
+
+    def check(name, got, f, cap=1e-3):
+        h = FD_STEPS[name]
+        fd1, fd2 = _central(f, h), _central(f, 2.0 * h)
+        fd, unc = 0.5 * (fd1 + fd2), abs(fd1 - fd2)
+        print("%-14s device %.10g differences %.10g +- %.1g" % (name, got, fd, unc))
+        assert unc < cap * abs(fd), (name, fd1, fd2)
+        assert abs(got - fd) < 2e-5 * max(abs(fd), 1.0) + 2.0 * unc, (name, got, fd1, fd2)
+
+    for s in range(S):
+        check("p", sb[s, 0], lambda d: _oracle_lnlike(case, s, p=case["p"][s] + d))
+        check("baseline_mean", sb[s, 2], lambda d: _oracle_lnlike(case, s, bmean=case["bmean"][s] + d))
+        check("baseline_var", sb[s, 3], lambda d: _oracle_lnlike(case, s, bvar=case["bvar"][s] + d))
+        check("log_var", sb[s, 4], lambda d: _oracle_lnlike(case, s, logvar=d))
+    if case["tau"]:
+        check("tau", sb[:, 1].sum(), lambda d: sum(_oracle_lnlike(case, s, tau=case["tau"] + d) for s in range(S)))
+
+
+# ---- 5. the one-star autograd chain ----------------------------------------------------------------------------
+@pytest.mark.parametrize("normalized", [True, False], ids=["norm", "raw"])
+@pytest.mark.parametrize("S,K", [(3, 96), (2, 1000)])
+def test_period_and_timescale_equal_the_single_star_autograd_chain(S, K, normalized):
+    from starry_process_amd.grad import log_likelihood_with_grad
+
+    case = _case(S=S, K=K, normalized=normalized, tau=0.7, bvar=1e-5, seed0=11)
+    _, b = _device(case, old=False)
+    mu, Sig = _moments()
+    for s in range(S):
+        lnl, g = log_likelihood_with_grad(mu, Sig, case["t"][s], case["flux"][s], case["var"][s], p=float(case["p"][s]),
+                                          tau=0.7, normalized=normalized, baseline_var=1e-5, ydeg=YDEG)
+        assert abs(b[0][s] - lnl) < 1e-9 * abs(lnl)
+        for k, name in ((0, "p"), (1, "tau")):
+            print("star %d %-3s sweep %.12g autograd %.12g" % (s, name, b[3][s, k], g[name]))
+            assert abs(b[3][s, k] - g[name]) < 2e-6 * max(abs(g[name]), 1e-3 * abs(lnl)), (s, name, b[3][s, k], g[name])
+
+
+# ---- 6. edges --------------------------------------------------------------------------------------------------
+def test_rejected_and_ragged_stars():
+    K = 100
+    case = _case(S=3, K=K, tau=0.7)
+    _, good = _device(case, old=False)
+    # star 1 ragged: NaN in every slot, SP_STAR_NAN; its neighbours their own rows
+    _, b = _device(case, old=False, stars_kw=dict(nobs=[0, K - 1, K]))
+    assert np.isnan(b[0][1]) and np.all(np.isnan(b[3][1])) and (b[4][1] & 4)
+    assert _bits(b[3][[0, 2]], good[3][[0, 2]]) and _bits(b[0][[0, 2]], good[0][[0, 2]])
+    # a system that is not positive definite (a negative variance larger than the signal): -inf, zeros, SP_STAR_NOT_PD
+    bad = dict(case, var=np.array([1e-6, -1.0, 1e-6]))
+    _, b = _device(bad, old=False)
+    assert b[0][1] == -np.inf and not b[3][1].any() and (b[4][1] & 1)
+    assert _bits(b[3][[0, 2]], good[3][[0, 2]])
+    # z > zmax: the moments of a high-contrast process (as tests/test_gpu_grad.py rejects every star)
+    from starry_process_amd.engine import get_engine
+    from starry_process_amd.upstream_device import ylm_moments_device
+
+    _, b = _device(case, old=False, mom=ylm_moments_device(get_engine(YDEG, 2), r=20.0, a=0.4, b=0.27, c=0.9, n=20.0))
+    assert np.all(b[0] == -np.inf) and not b[3].any() and np.all(b[4] & 2)
+
+
+def test_two_limb_darkening_tables_in_one_batch():
+    """each star reads ITS table in the new pass: a batch with two tables equals the two batches with one each"""
+    u = np.array([[0.0, 0.0], [0.4, 0.2], [0.4, 0.2]])
+    case = _case(S=3, K=100, tau=0.7, u=u)
+    _, b = _device(case, old=False)
+    _, b0 = _device(dict(case, u=np.zeros((3, 2))), old=False)
+    _, b1 = _device(dict(case, u=np.tile(u[1], (3, 1))), old=False)
+    assert _bits(b[3][0], b0[3][0]) and _bits(b[3][1:], b1[3][1:])
+    assert not np.array_equal(b0[3][1], b1[3][1])
+
+
+def test_the_new_entry_point_refuses_bad_arguments():
+    import torch
+    from starry_process_amd import _lib
+    from starry_process_amd.engine import get_engine, make_stars
+
+    e = get_engine(YDEG, 2)
+    L = _lib.lib()
+    mu, Sig = _moments()
+    e.set_moments(mu, Sig)
+    tab, mv = e.kernel_table(e.f64(e.rTA1L([0.0, 0.0])), COVPTS)
+    K, S = 64, 1
+    st = synthetic_star(0, K)
+    t, f = e.f64(st["t"][None, :]), e.f64(np.stack([st["flux"], st["flux"][::-1]])[None])
+    stars = e.stars_to_device(make_stars(S, period=1.0, data_var=1e-6))
+    ws = e.grad_workspace(S, K, COVPTS, 2)
+    out, yb, mb, sb = e.empty(S), e.empty(S, COVPTS + 4), e.empty(S), e.empty(S, 6)
+
+    def sweep(S_=S, K_=K, M_=2, covpts=COVPTS, ws_p=e._p(ws), sb_p=e._p(sb)):
+        return L.sp_lnlike_grad_marginal_stars(e._h, S_, K_, M_, e._p(t), e._p(f), None, e._p(stars), covpts, e._p(tab),
+                                               e._p(mv), 0, 1, 20, ctypes.c_double(0.023), ws_p, e._p(out), e._p(yb),
+                                               e._p(mb), None, sb_p, e._stream())
+
+    assert sweep() == 0
+    assert sweep(sb_p=None) == -1
+    assert sweep(M_=0) == -1
+    assert sweep(K_=1) == -1
+    assert sweep(ws_p=None) == -1
+    assert sweep(covpts=123) == -4                     # the table was built for another lag grid: SP_ERR_STATE
+    assert sweep(S_=0) == 0
+    torch.cuda.synchronize()
+    assert np.all(np.isfinite(sb.cpu().numpy()))
+
+
+# ---- 7. determinism --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("S,K,M", [(3, 100, 2), (2, 1000, 1)])
+def test_starbar_is_bit_stable(S, K, M):
+    case = _case(S=S, K=K, M=M, tau=0.7, per_cadence=True, bvar=1e-5)
+    _, b1 = _device(case, old=False)
+    _, b2 = _device(case, old=False)
+    assert _bits(b1[3], b2[3]) and np.all(np.isfinite(b1[3]))

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Time of the ensemble gradient (grad.EnsembleGradient: one device sweep for the whole batch) at cfg3's shape,
-beside the forward step and round 3's one-star-per-call gradient:  python tools/grad_timing.py [S] [K]"""
+beside the forward step and round 3's one-star-per-call gradient:  python tools/grad_timing.py [S] [K] [N]
+(N: iterations of the timed loops of the gradient and of its device sweep, default 10 -- a 25 ms window at 64 x 1000;
+ give a few hundred for a figure that outlasts the clocks' ramp)"""
 import os
 import sys
 import time
@@ -23,7 +25,7 @@ eg = EnsembleGradient(t, flux, ferr=1e-3, p=p)
 for _ in range(3):
     total, g = eg()
 torch.cuda.synchronize()
-n = 10
+n = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 t0 = time.perf_counter()
 for k in range(n):
     total, g = eg(r=20.0 + 0.01 * k)
@@ -42,6 +44,15 @@ for _ in range(n):
     e.lnlike_grad_marginal(eg._t, eg._flux, eg._stars, tab, mv, workspace=eg._ws)
 torch.cuda.synchronize()
 ms_sweep = 1e3 * (time.perf_counter() - t0) / n
+# ... and with the per-star derivatives (period, timescale, baseline, noise: sp_lnlike_grad_marginal_stars)
+for _ in range(3):
+    e.lnlike_grad_marginal_stars(eg._t, eg._flux, eg._stars, tab, mv, workspace=eg._ws)
+torch.cuda.synchronize()
+t0 = time.perf_counter()
+for _ in range(n):
+    e.lnlike_grad_marginal_stars(eg._t, eg._flux, eg._stars, tab, mv, workspace=eg._ws)
+torch.cuda.synchronize()
+ms_stars = 1e3 * (time.perf_counter() - t0) / n
 # the forward step
 ws = e.workspace(S, K, 1)
 fl3 = eg._flux[:, None, :].contiguous()
@@ -65,6 +76,8 @@ print("forward step (moments -> table -> lnL of %d stars), one at a time:   %.3f
 print("ensemble gradient, device sweep alone (C, C^-1, adjoints):           %.3f ms  = %.2f x forward; "
       "%.1f TFLOP/s of the 3.5 K^3/3 flops of factor + triangular inverse + L^-T L^-1" %
       (ms_sweep, ms_sweep / ms_fwd, 3.5 * fl / (ms_sweep * 1e-3) / 1e12))
+print("   ... with every star's d/d(p, tau, baseline_mean, baseline_var, log_var) from the same sweep:          %.3f ms"
+      % ms_stars)
 print("ensemble gradient, whole call (moments with their exact tangents, 3 + 2 table evaluations on three more streams, "
       "sweep): %.3f ms = %.2f x forward" % (ms_grad, ms_grad / ms_fwd))
 eg_fd = EnsembleGradient(t, flux, ferr=1e-3, p=p, exact=False)
