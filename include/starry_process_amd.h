@@ -466,6 +466,43 @@ int sp_gp_condition(sp_handle *h, int K, int Ks, const double *Ktt_dev, const do
                     double *Kss_dev, const double *r_dev, double *mu_dev, int32_t *info_dev,
                     void *stream);
 
+/* ---- conditional light curves of S stars in one call (sp.py:767-1002 batched; csrc/sp_predict.hip) ----
+ * K observed and Ks sample times per star, common to all stars: t_dev [S, K], ts_dev [S, Ks] (NULL: predict at the
+ * observed times, Ks == K), flux_dev [S, K], diag_dev [S, K] per-cadence data variances or NULL (then
+ * stars[s].data_var), stars_dev [S] (period, inc, tau, table, baseline_mean, baseline_var, data_var; nobs is not
+ * read: ragged ensembles are not served).  conditional == 0: the marginal branch, tab_dev / meanvar_dev from
+ * sp_kernel_table at `covpts` (4 (covpts + 4) + 128 doubles must fit 64 KiB of LDS); conditional != 0: the design
+ * matrix of rta1_dev and the handle's moments (SP_ERR_STATE without them); covpts >= 1 in both (it sizes the
+ * workspace).  The process is the un-normalised one.
+ *
+ * sp_predict_assemble writes the padded systems the conditioning factors, sys_dev [S, Kp, Kp] with
+ * Kp = roundup(K + Ks + 1, 64) (16-byte aligned): the lower 64 x 64 tiles of K_tt + noise + baseline_var, the Ks rows
+ * K_st + baseline_var below, the row (flux - baseline_mean) - mean, identity padding -- tiles above the diagonal
+ * are not touched.  mean_dev [S] (may be NULL) receives the mean of the flux process.
+ *
+ * sp_predict_ensemble assembles, factors (sp_gp_condition's scheme: Y = K_st L^-T and w = L^-1 r ride along) and
+ * reduces: mu_dev [S, Ks] = mean + Y w always (the same bits in every mode), and by `mode`
+ *   SP_PREDICT_MEAN  nothing else;
+ *   SP_PREDICT_VAR   var_dev [S, Ks] = prior variance - |Y_j|^2 from the same pass over Y: nothing Ks x Ks is formed;
+ *   SP_PREDICT_COV   cov_dev [S, Ks, Ks] = K_ss - Y Y^T, exactly symmetric.
+ * info_dev [S] (may be NULL): != 0 for a star whose K_tt is not positive definite -- all its outputs are NaN, no
+ * other star is affected, the call returns SP_OK.  Each star's numbers depend on its own inputs alone.  The stars are
+ * processed in chunks of at most about 4 GiB of workspace: sp_predict_workspace_bytes(h, S, K, Ks, covpts) stops
+ * growing with S there (0 for S, K, Ks or covpts < 1).  All launches go to `stream`; nothing is synchronised.   */
+#define SP_PREDICT_MEAN 0
+#define SP_PREDICT_VAR 1
+#define SP_PREDICT_COV 2
+size_t sp_predict_workspace_bytes(sp_handle *h, int S, int K, int Ks, int covpts);
+int sp_predict_assemble(sp_handle *h, int S, int K, int Ks, const double *t_dev, const double *ts_dev,
+                        const double *flux_dev, const double *diag_dev, const sp_star *stars_dev, int conditional,
+                        int covpts, const double *tab_dev, const double *meanvar_dev, const double *rta1_dev,
+                        int temporal, double *sys_dev, double *mean_dev, void *workspace_dev, void *stream);
+int sp_predict_ensemble(sp_handle *h, int S, int K, int Ks, const double *t_dev, const double *ts_dev,
+                        const double *flux_dev, const double *diag_dev, const sp_star *stars_dev, int conditional,
+                        int covpts, const double *tab_dev, const double *meanvar_dev, const double *rta1_dev,
+                        int temporal, int mode, double *mu_dev, double *var_dev, double *cov_dev, int32_t *info_dev,
+                        void *workspace_dev, void *stream);
+
 /* ---- posterior of the spherical-harmonic map given a light curve (sp.py:518-641, sample_ylm_conditional) ----
  * For S stars with the conditional path's design matrices A_s = sp_design_matrix(t, stars, rta1) [K, N]:
  *   W   = Sigma_y^-1 + A^T C^-1 A,   C = diag(data var) + baseline_var 1 1^T     (sp.py:601-628)
@@ -767,6 +804,11 @@ int sp_debug_set_syrk_symdiag(int on);
  * (csrc/sp_small.hip; default on, environment SP_SMALL_K; 0 = the blocked path at every size, -1 = back to the
  * default): which kernels run, the same values to rounding.                                                        */
 int sp_debug_set_small_k(int on);
+/* (debug, process-wide) the workspace budget of one pass of stars of sp_predict_assemble / sp_predict_ensemble
+ * (default about 4 GiB; 0 = back to the default): a small budget forces several passes over a small ensemble.  It
+ * changes sp_predict_workspace_bytes too, so size the workspace after setting it.  Which stars share a pass changes,
+ * no star's bits do.                                                                                              */
+int sp_debug_set_predict_chunk_bytes(size_t bytes);
 /* (debug, host only) how the hot assembly kernel (csrc/sp_assemble.hip, assemble_sums_kernel) cuts a star's
  * ntr (ntr + 1) / 2 lower tiles (column-strip order) into nchunk chunks of equal COST: start_host[c] = first tile
  * of chunk c, c = 0 .. nchunk (start_host[nchunk] = the number of tiles).  A function of the shape alone.   */

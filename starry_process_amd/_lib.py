@@ -93,6 +93,10 @@ PROTOTYPES = {
     "sp_lnlike_grad_marginal_stars": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                            _V, _V, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_predict_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
+    "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),
+    "sp_predict_ensemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _V, _V, _V,
+                                 _V]),
     "sp_ylm_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_conditional_batched": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "sp_ylm_conditional_whitened": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
@@ -133,6 +137,7 @@ PROTOTYPES = {
     "sp_debug_asm_chunks": (_I, [_I, _I, _V]),
     "sp_debug_set_syrk128_from": (_I, [_I]),
     "sp_debug_set_small_k": (_I, [_I]),
+    "sp_debug_set_predict_chunk_bytes": (_I, [ctypes.c_size_t]),
     "sp_debug_set_syrk_symdiag": (_I, [_I]),
     "sp_debug_set_look_ahead": (_I, [_V, _I]),
     "sp_debug_set_panel_layout": (_I, [_V, _I, _I]),

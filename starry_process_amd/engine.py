@@ -580,6 +580,78 @@ class Engine(object):
                                       self._p(r), self._p(mu), self._p(info), self._stream()))
         return mu, Kpost, info
 
+    # -- conditional light curves of an ensemble (sp_predict_assemble, sp_predict_ensemble; sp.py:767-1002) ----------
+    @staticmethod
+    def _predict_mode(mode):
+        """True (full covariance), "diag" (variances) or False (means alone) -> SP_PREDICT_COV / VAR / MEAN."""
+        if mode is True:
+            return 2
+        if mode is False:
+            return 0
+        if isinstance(mode, str) and mode == "diag":
+            return 1
+        raise ValueError("mode must be True, False or \"diag\"")
+
+    def _predict_call(self, fn, t, ts, flux, stars, diag, conditional, covpts, tab, meanvar, rta1, temporal, extra):
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        if flux.dim() != 2 or t.shape != flux.shape:
+            raise ValueError("t and flux must both be (S, K)")
+        S, K = flux.shape
+        ts = None if ts is None else self.f64(ts)
+        if ts is not None and (ts.dim() != 2 or ts.shape[0] != S or ts.shape[1] < 1):
+            raise ValueError("ts must be (S, Ks)")
+        Ks = K if ts is None else int(ts.shape[1])
+        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        rta1 = None if rta1 is None else self.f64(rta1)
+        ws = torch.empty(int(self._L.sp_predict_workspace_bytes(self._h, S, K, Ks, int(covpts))), dtype=torch.uint8,
+                         device=self.device)
+        out = extra(S, K, Ks)
+        check(fn(self._h, S, K, Ks, self._p(t), self._p(ts), self._p(flux), self._p(diag), self._p(sd),
+                 int(bool(conditional)), int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
+                 TEMPORAL[temporal], *([x if isinstance(x, int) else self._p(x) for x in out] + [self._p(ws),
+                                                                                                 self._stream()])))
+        return out
+
+    def predict_assemble(self, t, ts, flux, stars, diag=None, conditional=False, covpts=300, tab=None, meanvar=None,
+                         rta1=None, temporal=None):
+        """The padded systems ``predict_ensemble`` factors (sp_predict_assemble): (sys [S, Kp, Kp], mean [S]) with
+        Kp = roundup(K + Ks + 1, 64).  Rows < K: the lower 64 x 64 tiles of K_tt + noise + baseline_var; rows K ..
+        K + Ks - 1: K_st + baseline_var; row K + Ks: (flux - baseline_mean) - mean; the tiles above the diagonal
+        are left zero.  Arguments as ``predict_ensemble``."""
+        torch = _torch()
+
+        def extra(S, K, Ks):
+            Kp = (K + Ks + 1 + 63) // 64 * 64
+            return [torch.zeros(S, Kp, Kp, dtype=torch.float64, device=self.device), self.empty(S)]
+
+        sys, mean = self._predict_call(self._L.sp_predict_assemble, t, ts, flux, stars, diag, conditional, covpts, tab,
+                                       meanvar, rta1, temporal, extra)
+        return sys, mean
+
+    def predict_ensemble(self, t, ts, flux, stars, diag=None, conditional=False, covpts=300, tab=None, meanvar=None,
+                         rta1=None, temporal=None, mode=True):
+        """Conditional light curves of S stars of an un-normalised process (sp_predict_ensemble): device tensors in,
+        device tensors out, nothing crosses to the host in between.
+
+        t, flux [S, K]; ts [S, Ks] or None (predict at t); stars: host sp_star records or their device copy
+        (period, inc, tau, table, baseline_mean, baseline_var, data_var); diag [S, K] per-cadence variances or
+        None.  Marginal branch: tab, meanvar from ``kernel_table(rta1, covpts)``; conditional branch: rta1 and the
+        moments set on this engine.  mode True: (mu [S, Ks], cov [S, Ks, Ks], info [S]); "diag": (mu,
+        var [S, Ks], info); False: (mu, None, info).  A star with info != 0 (K_tt not positive definite)
+        has NaN outputs."""
+        torch = _torch()
+        m = self._predict_mode(mode)
+
+        def extra(S, K, Ks):
+            return [m, self.empty(S, Ks), self.empty(S, Ks) if m == 1 else None,
+                    self.empty(S, Ks, Ks) if m == 2 else None, torch.zeros(S, dtype=torch.int32, device=self.device)]
+
+        _, mu, var, cov, info = self._predict_call(self._L.sp_predict_ensemble, t, ts, flux, stars, diag, conditional,
+                                                   covpts, tab, meanvar, rta1, temporal, extra)
+        return mu, (cov if m == 2 else var), info
+
     def ylm_precision(self, mean_ylm, cov_ylm):
         """(Sigma_y^-1, Sigma_y^-1 mu_y) the way the reference forms them (sp.py:267-271: cho_factor, then
         cho_solve against I and mu_y), on the device.  NaN if Sigma_y is not positive definite."""

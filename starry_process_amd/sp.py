@@ -569,6 +569,70 @@ class StarryProcess(object):
         z = np.random.RandomState(seed).randn(Kpost.shape[0], int(nsamples))
         return Eager(np.array(mu)[None, :] + (L @ z).T)
 
+    # -- conditioning on the data of an ensemble: S stars in one device call (sp_predict_ensemble) -----------
+    def _predict_ensemble_dev(self, t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var, mode):
+        """(mu, cov / var / None, info) as device tensors: the arguments of the ensemble calls through the engine."""
+        if self._normalized:
+            raise NotImplementedError("Method not implemented when the flux is normalized.")
+        e, f = self._engine, self._flux
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, i, p, u, baseline_mean, baseline_var)
+        S = flux.shape[0]
+        ts = None
+        if t_sample is not None:
+            ts = np.asarray(t_sample, dtype=np.float64)
+            if ts.ndim == 1 and ts.shape[0] >= 1:
+                ts = np.broadcast_to(ts, (S, ts.shape[0]))
+            elif ts.ndim != 2 or ts.shape[0] != S or ts.shape[1] < 1:
+                raise ValueError("`t_sample` must be (Ks,) or (S, Ks) with S = %d, not %s" % (S, ts.shape))
+            ts = np.ascontiguousarray(ts)
+        f._bind()
+        rta1 = e.f64(e.rTA1L(utab))
+        tab = mv = None
+        if self._marginalize_over_inclination:
+            tab, mv = e.kernel_table(rta1, self._covpts)
+        return e.predict_ensemble(t, ts, flux, stars, diag=diag, conditional=not self._marginalize_over_inclination,
+                                  covpts=self._covpts, tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal,
+                                  mode=mode)
+
+    def predict_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
+                         baseline_var=0.0, return_cov=True):
+        """``predict`` for S stars in one device call: the light curve distributions conditioned on the observed
+        fluxes, each star with its own period, inclination, limb darkening, baseline and noise.
+
+        t: (K,) or (S, K); flux: (S, K); data_cov: scalar, (S,) or (S, K); t_sample: None (predict at ``t``), (Ks,)
+        or (S, Ks); i, p, baseline_mean, baseline_var: scalars or (S,); u: (udeg,) shared or (S, udeg).
+        return_cov=True: (mu (S, Ks), cov (S, Ks, Ks)), each covariance exactly symmetric; "diag": (mu, var (S, Ks))
+        without forming any Ks x Ks matrix; False: mu alone.  A star whose covariance at the observed times does
+        not factor gets NaN in all its outputs (``predict``'s rule, per star).  Not implemented for normalized
+        processes, as in the reference."""
+        if not (return_cov is True or return_cov is False or (isinstance(return_cov, str) and return_cov == "diag")):
+            raise ValueError("`return_cov` must be True, False or \"diag\"")
+        mu, second, _ = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
+                                                  return_cov)
+        if return_cov is False:
+            return Eager(mu.cpu().numpy())
+        return Eager(mu.cpu().numpy()), Eager(second.cpu().numpy())
+
+    def sample_conditional_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
+                                    baseline_var=0.0, nsamples=1, eps=1e-12, seed=None):
+        """Samples from the conditional distributions of S stars, shape (S, nsamples, Ks): ``predict_ensemble``, then
+        mu_s + L_s z_s with L_s the Cholesky factor of the posterior covariance + eps I (one batched factorisation)
+        and z = RandomState(seed).randn(S, Ks, nsamples) -- the constructor's seed when ``seed`` is None; with one
+        star, the deviates ``sample_conditional`` draws.  The product runs on the device."""
+        e = self._engine
+        mu, cov, _ = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
+                                                True)
+        S, Ks = mu.shape
+        nsamples = int(nsamples)
+        cov.diagonal(dim1=1, dim2=2).add_(float(eps))
+        L, _ = e.cho_factor(cov)                                  # (all NaN for a star that does not factor)
+        z = self._rng(seed).randn(S, Ks, nsamples)
+        zt = e.f64(np.ascontiguousarray(np.swapaxes(z, 1, 2)))
+        smp = e.empty(S, nsamples, Ks)
+        e.gemm_nt_batched(zt, L.contiguous(), smp)                # (L_s z_s)^T
+        smp += mu[:, None, :]
+        return Eager(smp.cpu().numpy())
+
     # -- posterior of the surface map (sp.py:518-641) -------------------------------------
     # W = Sigma_y^-1 + A^T C^-1 A, ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)), ycov = W^-1,
     # with A the design matrix at (t, i, p, u) whatever marginalize_over_inclination says (sp.py:620), as in
