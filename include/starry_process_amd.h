@@ -426,6 +426,38 @@ int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const doubl
                                   void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
                                   uint32_t *status_dev, double *starbar_dev, void *stream);
 
+/* ---- the CONDITIONAL branch's ensemble gradient in one device sweep (each star at its own inclination, sp_star.inc;
+ * tests/test_lnlike.py:100-136 verifies the gradient on both branches) ----------------------------------------------
+ * One light curve per star (flux_dev [S, K]), every cadence valid; the handle's Ylm moments (sp_set_ylm_moments[_dev];
+ * SP_ERR_STATE without them, as sp_cov_conditional_batched).  With A_s the star's K x N design matrix (flux.py:278-281),
+ *   Sigma_flux = (A Sigma_y A^T) o T,  mean = (A mu_y)[0],  C and lnL as sp_lnlike_ensemble's conditional branch,
+ * for every star:
+ *   lnlike_dev [S]          the log-likelihood
+ *   mubar_dev [S, N]        d lnL_s / d mu_y  = meanbar_s A_s[0, :]
+ *   sigbar_dev [S, N, N]    d lnL_s / d Sigma_y = A_s^T (H o T) A_s, its N^2 entries taken as independent (it is
+ *                           symmetric); H the pull-back of d lnL / dC through the normalisation, as in the marginal sweep
+ *   starbar_dev [S, SP_STARBAR]
+ *     [0] period            through the phases theta = 2 pi mod(t / p, 1) of the design matrix (the integer part is data)
+ *     [1] inclination       per RADIAN (sp_star.inc is radians)
+ *     [2] baseline_mean  [3] baseline_var  [4] log of a common factor on the star's data variances  [5] 0
+ * The caller chains (mubar, sigbar), summed over the stars, to the hyperparameters (starry_process_amd/grad.py:
+ * EnsembleGradientConditional).  temporal: the kernel multiplies Sigma_flux in the value and in every adjoint above;
+ * the derivative with respect to tau is not computed on this branch.  norm_order, zmax, diag_dev, status_dev: as
+ * sp_lnlike_grad_marginal_stars, and so are the conventions: a star the likelihood rejects (not positive definite,
+ * z > zmax) gets -inf and zeros in every adjoint, a ragged star (0 < nobs < K) NaN everywhere and SP_STAR_NAN; S = 0 is
+ * SP_OK with nothing touched; a null required pointer or K < 2 SP_ERR_INVALID; a host-only handle SP_ERR_NO_DEVICE.
+ * Every star's numbers depend on its own inputs alone and are the same bits run after run (no atomic additions); all
+ * launches go to `stream`, nothing is synchronised.
+ * workspace_dev: sp_lnlike_grad_conditional_workspace_bytes(h, S, K) bytes (0 for a null handle, S < 1 or K < 2): the
+ * marginal sweep's system and inverse, five K x N matrices per star and the roundup(K, 64) / 64 partial copies of
+ * (H o T) A that the lower tiles of C^-1 leave -- 5.5 GB at 64 x 1000, degree 15.                                 */
+size_t sp_lnlike_grad_conditional_workspace_bytes(sp_handle *h, int S, int K);
+int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                               const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, int temporal,
+                               int normalized, int norm_order, double zmax, void *workspace_dev, double *lnlike_dev,
+                               double *mubar_dev, double *sigbar_dev, double *starbar_dev, uint32_t *status_dev,
+                               void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

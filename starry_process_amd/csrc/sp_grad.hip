@@ -480,25 +480,13 @@ int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double
                          hipStream_t st, const double *tab = nullptr, double *starbar = nullptr) {
   const int ntr = Kr / 64, np = covpts + 4;
   // (part: the scatter's partial tables later -- [S][ntr][4][K] doubles of it here, grad_layout)
-  for (int v0 = 0; v0 < M + 3; v0 += 4) {
-    hipLaunchKernelGGL(grad_matvec_kernel, dim3(ntr * (ntr + 1) / 2, S), dim3(256), 0, st, K, Kr, M, v0, Cinv, flux, stars,
-                       (const SpCoef *)coef, qv, normalized, partial);
-    SP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(grad_matvec_reduce_kernel, dim3((K + 255) / 256, S, 4), dim3(256), 0, st, K, ntr, M + 3, v0, partial,
-                       vec);
-    SP_LAUNCH_CHECK();
-  }
   // (starbar: sp_lnlike_grad_marginal_stars -- the same launches, the scalars kernel also writes the per-star slots it
   //  has in hand, and two more launches behind the table's adjoint)
-  if (starbar)
-    hipLaunchKernelGGL(grad_scalars_kernel<true>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
-                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
-                       hcoef, status, starbar);
-  else
-    hipLaunchKernelGGL(grad_scalars_kernel<false>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
-                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
-                       hcoef, status, starbar);
-  SP_LAUNCH_CHECK();
+  {
+    const int rc = sp_launch_grad_front(S, K, Kr, M, Cinv, flux, stars, coef, qv, diag, logdet, info, normalized, order,
+                                        zmax, vec, dots, hcoef, partial, lnlike, meanbar, status, starbar, st);
+    if (rc) return rc;
+  }
   const size_t lds = sizeof(double) * np;
   if (lds > 60 * 1024) return SP_ERR_INVALID;
   dim3 grid(ntr * (ntr + 1) / 2, S);
@@ -611,6 +599,35 @@ int grad_marginal(sp_handle *h, int S, int K, int M, const double *t_dev, const 
 }
 
 }  // namespace
+
+// The head of the sweep, shared by the two branches (the conditional one: sp_grad_cond.hip): the products of C^-1 with
+// p, q, 1 and the residuals, then the scalars -- lnL, the pull-back through the normalisation (hcoef, w, meanbar) and,
+// with starbar, the per-star slots 2-5.  `partial`: [S][Kr / 64][4][K] doubles.
+int sp_launch_grad_front(int S, int K, int Kr, int M, const double *Cinv, const double *flux, const sp_star *stars,
+                         const void *coef, const double *qv, const double *diag, const double *logdet,
+                         const int32_t *info, int normalized, int order, double zmax, double *vec, double *dots,
+                         double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
+                         double *starbar, hipStream_t st) {
+  const int ntr = Kr / 64;
+  for (int v0 = 0; v0 < M + 3; v0 += 4) {
+    hipLaunchKernelGGL(grad_matvec_kernel, dim3(ntr * (ntr + 1) / 2, S), dim3(256), 0, st, K, Kr, M, v0, Cinv, flux, stars,
+                       (const SpCoef *)coef, qv, normalized, partial);
+    SP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(grad_matvec_reduce_kernel, dim3((K + 255) / 256, S, 4), dim3(256), 0, st, K, ntr, M + 3, v0, partial,
+                       vec);
+    SP_LAUNCH_CHECK();
+  }
+  if (starbar)
+    hipLaunchKernelGGL(grad_scalars_kernel<true>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
+                       hcoef, status, starbar);
+  else
+    hipLaunchKernelGGL(grad_scalars_kernel<false>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+                       (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
+                       hcoef, status, starbar);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
 
 extern "C" {
 

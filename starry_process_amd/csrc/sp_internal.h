@@ -451,10 +451,22 @@ struct Layout {
       B1, raw, part, sys, total;
 };
 Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool lean = false, int s0 = 0);
+// the design matrices of L.S stars into A_out, Kr rows per star (L.theta filled; uses L.cs, L.vrow, L.Rinc), and
+// mean[s] = (A_s mu_y)[0] from matrices of `rows` rows per star
+int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars, const double *rta1, double *A_out,
+                     hipStream_t st, int Kr);
+int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st);
 
 // sp_linalg.hip: C^-1 (and log det C) of the matrices already in the top-left K x K corners of the systems of `ws`
 int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
                          hipStream_t st);
+
+// sp_grad.hip: the head of the gradient sweep (products with C^-1, scalars); partial: [S][Kr / 64][4][K] doubles
+int sp_launch_grad_front(int S, int K, int Kr, int M, const double *Cinv, const double *flux, const sp_star *stars,
+                         const void *coef, const double *qv, const double *diag, const double *logdet,
+                         const int32_t *info, int normalized, int order, double zmax, double *vec, double *dots,
+                         double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
+                         double *starbar, hipStream_t st);
 
 // grid of a grid-stride kernel: blocks of 256 threads covering `total` elements, at most `max_blocks` of them
 static inline unsigned grid_for(size_t total, size_t max_blocks = 8192) {

@@ -354,6 +354,17 @@ int lnlike_finish(const Layout &L, void *ws, int K, int M, double *lnlike_dev,
 
 }  // namespace
 
+// the two conditional-branch steps the gradient's driver shares with this one (sp_grad_cond.hip)
+int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars, const double *rta1, double *A_out,
+                     hipStream_t st, int Kr) {
+  return build_design(h, L, ws, stars, rta1, A_out, st, Kr);
+}
+int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st) {
+  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, rows, A, mu, mean);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
 extern "C" {
 
 // (debug, process-wide) the one-kernel path of short light curves on / off / back to the environment's setting

@@ -1040,6 +1040,36 @@ class Engine(object):
             self._p(out), self._p(ybar), self._p(mbar), self._p(status), self._p(sbar), self._stream()))
         return out, ybar, mbar, sbar, status
 
+    def lnlike_grad_conditional(self, t, flux, stars_dev, rta1, diag=None, temporal=None, normalized=True,
+                                norm_order=20, zmax=0.023, workspace=None):
+        """Device half of the CONDITIONAL branch's ensemble gradient (sp_lnlike_grad_conditional), at the engine's
+        current moments: t [S, K], flux [S, K], stars_dev (each star's inclination in sp_star.inc, radians), rta1
+        [ntab, N] -> (lnlike [S], mubar [S, N], sigbar [S, N, N], starbar [S, 6], status [S]); starbar[s] = d lnL_s / d
+        (period, inclination per radian, baseline_mean, baseline_var, log of a common factor on the star's data
+        variances, 0)."""
+        torch = _torch()
+        S, K = t.shape
+        assert tuple(flux.shape) == (S, K)
+        N = self.N
+        out, mubar, sigbar, sbar = self.empty(S), self.empty(S, N), self.empty(S, N, N), self.empty(S, 6)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S == 0:
+            return out, mubar, sigbar, sbar, status
+        nbytes = int(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
+        ws = workspace
+        if ws is None or ws.numel() < nbytes:
+            ws = self._grad_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self._L.sp_lnlike_grad_conditional(
+            self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(rta1),
+            TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(ws), self._p(out),
+            self._p(mubar), self._p(sigbar), self._p(sbar), self._p(status), self._stream()))
+        return out, mubar, sigbar, sbar, status
+
+    def grad_conditional_workspace(self, S, K):
+        torch = _torch()
+        nbytes = int(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+
     def grad_workspace(self, S, K, covpts, M=1):
         torch = _torch()
         nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, int(M), int(covpts)))

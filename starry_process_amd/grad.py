@@ -35,7 +35,8 @@ from .defaults import defaults
 from .engine import get_engine
 from .temporal import kernel_id
 
-__all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient"]
+__all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient",
+           "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional"]
 
 _cache = {}
 
@@ -604,7 +605,8 @@ def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], 
     ``log_likelihood_with_grad``: C = A Sigma_y A^T, the design matrix's adjoint through sp_dotRx / sp_tensordotRz_rev)
     are summed, then contracted with the moments' exact tangents (``ylm_moments_device_grad``) -- one upstream
     evaluation per gradient instead of one per star and parameter.  Star by star on the host (6.5 ms each at K = 1000):
-    an optimiser's aid, not a timed path; the marginal branch has the one-sweep device form (``EnsembleGradient``).
+    an optimiser's aid, not a timed path; the one-sweep device form of this branch is ``EnsembleGradientConditional``
+    (the marginal branch's: ``EnsembleGradient``).
     kwargs: as for ``log_likelihood_with_grad`` (u, tau, normalized, baseline_*, ydeg, ...)."""
     from .upstream_device import ylm_moments_device_grad
 
@@ -651,3 +653,139 @@ def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], 
         out["n"] = float(c) * gm + float(c) ** 2 * gS
     out["i"], out["p"] = gi, gp
     return float(lnl.sum()), out, lnl
+
+
+# the per-star derivatives of EnsembleGradientConditional(wrt=...), in the order of the device's row (SP_STARBAR slots 0-4)
+_WRT_COND = ("p", "i", "baseline_mean", "baseline_var", "log_var")
+
+
+def _check_wrt_conditional(wrt):
+    """``wrt`` as a tuple of names the conditional sweep serves (None stays None); ValueError otherwise.  No device
+    work."""
+    if wrt is None:
+        return None
+    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+    for name in wrt:
+        if name == "tau":
+            raise ValueError("wrt: 'tau' is not differentiated on the conditional branch (the sweep applies the temporal "
+                             "kernel but takes no derivative with respect to its timescale; the marginal branch does: "
+                             "EnsembleGradient)")
+        if name not in _WRT_COND:
+            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT_COND)))
+    return wrt
+
+
+class EnsembleGradientConditional(object):
+    """The CONDITIONAL branch (``marginalize_over_inclination=False``: star s at its own inclination i_s) of the ensemble
+    log-likelihood and its gradient in ONE device sweep per evaluation -- what ``ensemble_gradient_conditional`` computes
+    star by star through the autograd graph, for the whole batch at once (sp_lnlike_grad_conditional).
+
+        eg = EnsembleGradientConditional(t, flux, ferr=1e-3, p=periods, i=inclinations)     # data -> GPU, once
+        lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10., wrt=("i", "p"))   # lnl: sum over stars; grad: dict
+        eg.lnlike                                                         # per-star values of the last call
+
+    The sweep returns every star's d lnL_s / d(mu_y, Sigma_y); they are summed over the stars in a fixed order and
+    contracted with the moments' exact tangents (``ylm_moments_device_grad``) on the device -- c and n in closed form,
+    with the rule of ``ensemble_gradient_conditional`` on the boundary c = 0 or n = 0 -- and one small transfer leaves
+    the GPU per call.  One light curve per star; scalar or per-cadence ``ferr``; ``tau``: the temporal kernel
+    multiplies the covariance (no derivative with respect to it on this branch)."""
+
+    _WRT = _WRT_COND
+
+    def __init__(self, t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], u=None, ydeg=15, baseline_var=0.0,
+                 baseline_mean=0.0, normalized=True, tau=None, temporal_kernel="matern32", device=None,
+                 upstream_kwargs=None):
+        flux = np.asarray(flux, dtype=np.float64)
+        if flux.ndim != 2:
+            raise ValueError("flux must be (S, K)")
+        S, K = flux.shape
+        if K < 2:
+            raise ValueError("at least two cadences")
+        import torch
+
+        from .engine import make_stars
+
+        t = np.asarray(t, dtype=np.float64)
+        t = np.broadcast_to(t, (S, K)) if t.ndim == 1 else t
+        udeg = defaults["udeg"]
+        per = lambda x: np.broadcast_to(np.asarray(x, dtype=np.float64), (S,))          # noqa: E731
+        uu = np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
+        if uu.ndim == 1:
+            utab, table = uu[None, :udeg], np.zeros(S, dtype=np.int32)
+        else:
+            utab, table = np.unique(uu[:, :udeg], axis=0, return_inverse=True)
+            table = table.astype(np.int32).reshape(-1)
+        if np.any(per(p) < -1e-6):
+            raise ValueError("p out of bounds")
+        var = np.asarray(ferr, dtype=np.float64) ** 2
+        stars = make_stars(S, period=per(p), inc_deg=per(i), tau=float(tau) if tau else 0.0,
+                           baseline_var=per(baseline_var), baseline_mean=per(baseline_mean),
+                           data_var=per(var) if var.ndim < 2 else 0.0, table=table)
+        e = self._e = get_engine(ydeg, udeg, device)
+        self.S, self.K = S, K
+        self._t, self._flux = e.f64(np.ascontiguousarray(t)), e.f64(np.ascontiguousarray(flux))
+        self._diag = e.f64(np.ascontiguousarray(np.broadcast_to(var, (S, K)))) if var.ndim == 2 else None
+        self._stars = e.stars_to_device(stars)
+        self._rta1 = e.f64(e.rTA1L(utab))
+        self._temporal = (temporal_kernel if isinstance(temporal_kernel, str) else kernel_id(temporal_kernel)) if tau else None
+        self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
+        self._ws = e.grad_conditional_workspace(S, K)
+        self.lnlike = self.status = None
+        torch.cuda.synchronize(e.device)
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=None):
+        """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .}).
+
+        wrt: None, or a tuple of names out of ("i", "p", "baseline_mean", "baseline_var", "log_var"): the dict then also
+        holds arrays [S], d lnL_s / d of star s's inclination (per DEGREE, as ``log_likelihood_with_grad`` returns it),
+        period (the integer part of t / p is data), baseline mean, baseline variance and the log of a common factor on
+        its data variances -- from the same sweep and the same transfer.  A star the likelihood rejects adds zeros."""
+        import torch
+
+        from .upstream_device import ylm_moments_device, ylm_moments_device_grad
+
+        wrt = _check_wrt_conditional(wrt)
+        e = self._e
+        r, a, b, c, n = float(r), float(a), float(b), float(c), float(n)
+        mu, Sig, dmu, dSig = ylm_moments_device_grad(e, r=r, a=a, b=b, c=c, n=n, **self._ukw)
+        e.set_moments_dev(mu, Sig)
+        lnl, mubar, sigbar, sbar, status = e.lnlike_grad_conditional(
+            self._t, self._flux, self._stars, self._rta1, diag=self._diag, temporal=self._temporal,
+            normalized=self._normalized, workspace=self._ws)
+        # the stars' adjoints added up (a reduction over the leading axis: no atomics, the same order every call)
+        gmu, gSig = mubar.sum(dim=0), sigbar.sum(dim=0)
+        N = mu.shape[0]
+        eps = torch.full((N,), float(self._ukw.get("epsy", defaults["epsy"])), dtype=torch.float64, device=e.device)
+        eps[15 ** 2:] = float(self._ukw.get("epsy15", defaults["epsy15"]))
+        g_rab = dmu @ gmu + (dSig * gSig).sum(dim=(1, 2))
+        if c != 0 and n != 0:
+            # mu ~ c n, Sigma - eps ~ c^2 n (contrast.py:21-33)
+            gm, gS = torch.dot(gmu, mu), (gSig * (Sig - torch.diag(eps))).sum()
+            g_c, g_n = gm / c + 2.0 * gS / c, gm / n + gS / n
+        else:
+            # the boundary rule of ensemble_gradient_conditional: the moments at unit contrast and unit number of spots
+            m1, Sig1 = ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)
+            gm, gS = torch.dot(gmu, m1), (gSig * (Sig1 - torch.diag(eps))).sum()
+            g_c, g_n = n * gm + 2.0 * c * n * gS, c * gm + c * c * gS
+        # ONE transfer: [gradient | per-star values | per-star status | per-star derivatives]
+        host = torch.cat([g_rab, torch.stack([g_c, g_n]), lnl, status.to(torch.float64), sbar.reshape(-1)]).cpu().numpy()
+        S = self.S
+        self.lnlike = host[5:5 + S].copy()
+        self.status = host[5 + S:5 + 2 * S].astype(np.uint32)
+        grad = {k: float(v) for k, v in zip(("r", "a", "b", "c", "n"), host[:5])}
+        if wrt is not None:
+            sb = host[5 + 2 * S:].reshape(S, -1)
+            for k in wrt:
+                col = sb[:, _WRT_COND.index(k)]
+                grad[k] = col * (np.pi / 180.0) if k == "i" else col.copy()
+        return float(self.lnlike.sum()), grad
+
+
+def ensemble_gradient_conditional_device(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], r=defaults["r"], a=defaults["a"],
+                                         b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=("i", "p"), **kwargs):
+    """One-shot form of ``EnsembleGradientConditional`` with the return of ``ensemble_gradient_conditional``:
+    (sum_s lnL_s, {"r", "a", "b", "c", "n": floats, and the names of ``wrt``: arrays [S]}, lnL [S])."""
+    wrt = _check_wrt_conditional(wrt)          # (before any data goes to the device)
+    eg = EnsembleGradientConditional(t, flux, ferr=ferr, p=p, i=i, **kwargs)
+    total, grad = eg(r=r, a=a, b=b, c=c, n=n, wrt=wrt)
+    return total, grad, eg.lnlike
