@@ -50,9 +50,10 @@ typedef enum {
 #define SP_STAR_NAN 4u      /* NaN reached the final value (sp.py:1186-1188)  */
 #define SP_STAR_STALE_PLAN 8u /* sp_lnlike_ensemble_planned: the star's period, tau
                                or nobs differ from the planned ones; value = NaN   */
-#define SP_STAR_NO_BASIS 16u  /* sp_lnlike_inclinations: a variance <= 0 or G = T^T D^-1 T
-                               does not factor (fewer than 2 ydeg + 1 distinct phases);
-                               value = NaN: evaluate the star another way            */
+#define SP_STAR_NO_BASIS 16u  /* sp_lnlike_inclinations: a variance <= 0, or G = T^T D^-1 T
+                               does not factor (fewer than 2 ydeg + 1 distinct phases) or
+                               is too ill-conditioned (G00 trace(G^-1) > 3e8: partial phase
+                               coverage); value = NaN: evaluate the star another way  */
 
 /* temporal kernels (reference temporal.py:8-16) */
 #define SP_TEMPORAL_NONE 0

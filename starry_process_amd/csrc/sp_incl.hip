@@ -33,6 +33,9 @@ namespace {
 
 constexpr int IC_CH = 32;     // cadences per chunk of the data stage's Fourier sums
 constexpr int IC_PC = 8;      // inclinations per workgroup of the model stage
+// Largest G00 trace(G^-1) the basis route takes (the measured sweep over phase coverage)
+constexpr double IC_KAPPA_MAX = 3e8;
+static_assert(2 * IC_CH >= 2 * SP_MAX_YDEG + 1, "the conditioning estimate's n x n scratch reuses the cadence tables");
 
 __device__ __forceinline__ int ic_nobs(const sp_star &st, int K) { return st.nobs > 0 && st.nobs < K ? st.nobs : K; }
 
@@ -49,8 +52,9 @@ __device__ __forceinline__ double ic_phase(double t, double p) {
 }
 
 // One workgroup (256 threads) per star.  plan[s]: L_G [n][n] (zero above the diagonal), w [M][n], g0 [n], T0 [n],
-// then {sum_m rho_m, sum log d, nobs, flag}.  flag = 1: a variance <= 0 or not finite, or G does not factor
-// (fewer than n distinct phases): the star's values are NaN and its status carries SP_STAR_NO_BASIS.
+// then {sum_m rho_m, sum log d, nobs, flag}.  flag = 1: a variance <= 0 or not finite, G does not factor
+// (fewer than n distinct phases) or G00 trace(G^-1) > IC_KAPPA_MAX (the phases cover too little of the rotation):
+// the star's values are NaN and its status carries SP_STAR_NO_BASIS.
 __global__ __launch_bounds__(256) void incl_data_kernel(int L, int K, int M, const double *__restrict__ t,
                                                         const double *__restrict__ flux,
                                                         const double *__restrict__ diag,
@@ -141,7 +145,7 @@ __global__ __launch_bounds__(256) void incl_data_kernel(int L, int K, int M, con
   __syncthreads();
   // L_G: right-looking Cholesky in LDS.  A pivot below 1e-9 of G's largest diagonal entry (G00 = sum 1/d: no
   // diagonal entry exceeds it) means the phases do not determine the n Fourier coefficients
-  const double thresh = 1e-9 * sG[0];
+  const double g00 = sG[0], thresh = 1e-9 * g00;
   __syncthreads();
   for (int j = 0; j < n; ++j) {
     if (tid == 0) {
@@ -156,6 +160,30 @@ __global__ __launch_bounds__(256) void incl_data_kernel(int L, int K, int M, con
     for (int e = tid; e < (n - j - 1) * (n - j - 1); e += 256) {
       const int i = j + 1 + e / (n - j - 1), k = j + 1 + e % (n - j - 1);
       if (k <= i) sG[i * n + k] -= sG[i * n + j] * sG[k * n + j];
+    }
+    __syncthreads();
+  }
+  // Conditioning: kappa = G00 trace(G^-1) = G00 |L_G^-1|_F^2 (cond_2(G) <= kappa <= n^2 cond_2(G)).  G is formed
+  // explicitly, so the likelihood loses about eps kappa; beyond IC_KAPPA_MAX the star takes the dense path.  Thread c
+  // solves L_G x = e_c in the cadence tables' LDS, free by now (2 IC_CH n >= n^2 doubles: n <= 61).
+  {
+    double *sX = sTc;
+    for (int c = tid; c < n; c += 256) {
+      double *x = sX + c * n, ss = 0.0;
+      for (int a = c; a < n; ++a) {
+        double v = a == c ? 1.0 : 0.0;
+        for (int k = c; k < a; ++k) v -= sG[a * n + k] * x[k];
+        v /= sG[a * n + a];
+        x[a] = v;
+        ss += v * v;
+      }
+      sRed[c] = ss;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double tr = 0.0;
+      for (int c = 0; c < n; ++c) tr += sRed[c];
+      if (!(g00 * tr <= IC_KAPPA_MAX)) bad = 1;
     }
     __syncthreads();
   }

@@ -851,7 +851,8 @@ class StarryProcess(object):
     # device call, whatever marginalize_over_inclination says (as ylm_conditional).  The flux covariance at one
     # inclination has rank 2 ydeg + 1 (sp_lnlike_inclinations).  What that route cannot take -- a
     # time-variable process, a full data covariance or baseline_var matrix, a variance <= 0, a star with fewer
-    # distinct phases than 2 ydeg + 1 -- takes the dense conditional path on one system per inclination.
+    # distinct phases than 2 ydeg + 1 or with too little of the rotation covered (SP_STAR_NO_BASIS) -- takes the
+    # dense conditional path on one system per inclination.
     def _check_inc(self, inc):
         inc = np.atleast_1d(np.asarray(inc, dtype=np.float64)).reshape(-1)
         if np.any(inc * np.pi / 180 < -1e-6) or np.any(inc * np.pi / 180 > 0.5 * np.pi + 1e-6):
@@ -884,7 +885,8 @@ class StarryProcess(object):
             cov += e.f64(bvar) if bvar.ndim else float(bvar)
             gp = 0.0 if self._normalized else mean[:, None, None]
             resid = Fd[None, :, :] - (gp + (e.f64(bmean) if bmean.ndim else float(bmean)))
-            val, _ = e.cholesky_lnlike(cov, resid.contiguous())
+            # one residual per system: a normalised process subtracts no per-inclination mean, which leaves batch 1
+            val, _ = e.cholesky_lnlike(cov, resid.expand(n, -1, -1).contiguous())
             val = val.cpu().numpy()
             if self._normalized:
                 val = np.where(z.cpu().numpy() > self._normzmax, -np.inf, val)
