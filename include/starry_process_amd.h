@@ -179,6 +179,23 @@ int sp_kernel_table(sp_handle *h, const double *rta1_dev, int ntab, int covpts,
  *       samples_host [B][5]: r in RADIANS, alpha, beta (the Beta law's shape parameters, latitude.py:176-197), c, n.
  *       Needs sp_set_size_basis first (the spot profile's basis, size.py:9-47: theta [spts] = the colatitude grid,
  *       Bp [ydeg + 1][spts] = the smoothed pseudo-inverse of the Legendre basis, sfac = the sigmoid's steepness).
+ *   sp_polar_moments_samples_spread   the same for spots whose radii are drawn uniformly from [r - dr, r + dr]
+ *       (StarryProcess(dr=...); size.py:55-89, 109-125).  samples_host [B][6]: r, dr in RADIANS, alpha, beta, c, n; a
+ *       row with dr = 0 is the one-radius case and may sit in the same batch.  The first moment of the size integral
+ *       is e = Bp c, c = log((1 + chim) / (1 + chip)) / (2 dr sfac) (size.py:55-61); its second moment is Etilde = Bp C
+ *       Bp^T with C of size.py:71-84: nonzero on the first kmax grid points, kmax = the first index with theta / (r +
+ *       dr) > cutoff (0 when there is none, as argmax gives), off-diagonal and diagonal formulas of size.py:73-82 with
+ *       the + 1e-15 in the denominator.  The reference takes the eigen square root of Etilde and rotates its columns
+ *       (size.py:86-88, integrals.py:109-156); here none is taken: every vector v on the m = 0 entries has
+ *       (v Rx(phi) Rx(pi/2))[(l, m)] = v_l rho_phi(l, m), rho_phi the row formed with unit coefficients, so
+ *           sum_k w_k sum_j (col_j R_k)^T (col_j R_k) = Etilde[l, l'] (sum_k w_k rho_k rho_k^T)[(l, m), (l', m')]:
+ *       the matrix-core product of sp_polar_moments_samples on unit-coefficient rows, times a (ydeg + 1)^2 table per
+ *       sample at the finish (the longitude projection mixes entries of one (l, l') block only).  C is never stored:
+ *       a workgroup forms 128 of its rows entry by entry against Bp.  One upload of 6 B numbers, seven launches (six
+ *       when no row has dr > 0), no host arithmetic per sample, no atomics, nothing synchronised: the same bits run
+ *       after run, and B samples in one call give the bits of B calls with one sample each.  SP_ERR_INVALID for a
+ *       null pointer, B < 0, a non-finite entry, r or dr outside [0, pi/2], cutoff <= 0; SP_ERR_STATE without a size
+ *       basis.
  *   sp_kernel_table_samples    sp_kernel_table for B sets of polar moments: table b ntab + i (tab_dev
  *       [B ntab][5][covpts + 4], meanvar_dev [B ntab][2]) from sample b and flux operator i.
  * The likelihood of the (sample, star) pairs is then ONE sp_lnlike_ensemble_planned call on a replicated plan
@@ -186,6 +203,8 @@ int sp_kernel_table(sp_handle *h, const double *rta1_dev, int ntab, int covpts,
 int sp_set_size_basis(sp_handle *h, const double *theta_host, const double *Bp_host, int spts, double sfac);
 int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15,
                              double *ez_dev, double *Ez_dev, void *stream);
+int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
+                                    double epsy15, double *ez_dev, double *Ez_dev, void *stream);
 int sp_kernel_table_samples(sp_handle *h, int B, const double *ez_dev, const double *Ez_dev, const double *rta1_dev,
                             int ntab, int covpts, const double *xp_host, double *tab_dev, double *meanvar_dev,
                             void *stream);

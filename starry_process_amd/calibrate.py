@@ -71,15 +71,40 @@ class SampleBatches(object):
     polar moments (sp_polar_moments_samples), their kernel tables (sp_kernel_table_samples) and ONE planned likelihood
     call on a replicated data plan (sp_plan_replicate) whose stars carry the table of their sample.  A single light
     curve -- how the reference is called, sp.py:1052-1062 driven by calibrate/sample.py:95-107 -- then runs at the
-    rate of a 64-star ensemble instead of one latency-bound step per sample.  Marginal, normalised branch, one spot
-    radius (dr = None); consecutive groups go to the slots' streams in turn."""
+    rate of a 64-star ensemble instead of one latency-bound step per sample.  Marginal, normalised branch;
+    consecutive groups go to the slots' streams in turn.
+
+    ``dr``: None (one spot radius), a float (radii uniform in [r - dr, r + dr] degrees, the same for every sample:
+    StarryProcess(dr=...)) or "free" (a column of the samples); ``free``: which of ("baseline_mean",
+    "baseline_log_var") are columns of the samples instead of fields of ``stars`` (calibrate/log_prob.py:24-47).  The
+    columns are r[, dr], a, b, c, n[, m][, v]: the reference's order with dr where the constructor has it.  With free
+    baseline terms every group's star array goes up through the pinned staging ring into the slot's own device array
+    (the planned step reads the baseline terms of its stars on every call)."""
+
+    FREE = ("baseline_mean", "baseline_log_var")
 
     def __init__(self, slots, t_dev, flux_dev, stars, rta1_dev, covpts, diag_dev=None, temporal=None, group=None,
-                 norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None):
+                 norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None, dr=None, free=()):
         import torch
 
         from .engine import stars_for_samples
 
+        free = (free,) if isinstance(free, str) else tuple(free)
+        if len(set(free)) != len(free) or any(f not in self.FREE for f in free):
+            raise ValueError("free must be a subset of %r" % (self.FREE,))
+        if isinstance(dr, str):
+            if dr != "free":
+                raise ValueError("dr must be None, a number or 'free'")
+        elif dr is not None:
+            from .ops import CheckBoundsOp
+
+            dr = float(dr)
+            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
+        self._dr = dr
+        self._free = tuple(f for f in self.FREE if f in free)
+        self.columns = ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(
+            {"baseline_mean": "m", "baseline_log_var": "v"}[f] for f in self._free)
+        self._stars_host = np.ascontiguousarray(stars).copy()
         self._slots = slots
         e0 = slots[0][0]
         self.S, self.K = int(t_dev.shape[0]), int(t_dev.shape[1])
@@ -101,20 +126,37 @@ class SampleBatches(object):
                                   Ez=e.empty(self.group, e.N, e.N),
                                   tab=e.empty(self.group * self._ntab, 5, self._covpts + 4),
                                   mv=e.empty(self.group * self._ntab, 2)))
+            if self._free:          # (one star array per stream slot, rewritten by every group of the slot)
+                self._buf[-1]["stars"] = e.stars_to_device(stars_for_samples(stars, self.group, self._ntab))
             e.set_size_basis(**self._ukw)
         torch.cuda.synchronize(e0.device)
 
     def __call__(self, samples, out=None):
-        """samples (ns, 5) -> device tensor (ns, S); nothing is synchronised: the caller does, once."""
+        """samples (ns, len(self.columns)) -> device tensor (ns, S); nothing is synchronised: the caller does, once."""
         import torch
 
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+        if samples.ndim != 2 or samples.shape[1] != len(self.columns):
+            raise ValueError("samples must be (ns, %d): %s" % (len(self.columns), ", ".join(self.columns)))
         ns, g, S = samples.shape[0], self.group, self.S
         ngroups = -(-ns // g)
         e0 = self._slots[0][0]
         raw = e0.empty(ngroups, g * S)
         if ns < ngroups * g:          # (the last group is filled up with its own last sample; those values are dropped)
             samples = np.vstack([samples, np.repeat(samples[-1:], ngroups * g - ns, axis=0)])
+        new = self._dr is not None or bool(self._free)
+        if new:
+            from .engine import stars_for_samples
+
+            c0 = 2 if self._dr == "free" else 1
+            drv = samples[:, 1] if self._dr == "free" else self._dr
+            hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
+            col = c0 + 4
+            bm = bv = None
+            if "baseline_mean" in self._free:
+                bm, col = samples[:, col], col + 1
+            if "baseline_log_var" in self._free:
+                bv = 10.0 ** samples[:, col]
         cur = torch.cuda.current_stream(e0.device)
         start = torch.cuda.Event()
         start.record(cur)
@@ -137,12 +179,22 @@ class SampleBatches(object):
                     stream.wait_event(start)
                     if stagger is not None:
                         stream.wait_event(stagger)
-                e.polar_moments_samples(samples[gi * g:(gi + 1) * g], ez=b["ez"], Ez=b["Ez"], **self._ukw)
+                stars_d = self._stars
+                if not new:
+                    e.polar_moments_samples(samples[gi * g:(gi + 1) * g], ez=b["ez"], Ez=b["Ez"], **self._ukw)
+                else:
+                    sl = slice(gi * g, (gi + 1) * g)
+                    e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"],
+                                            dr=drv[sl] if self._dr == "free" else drv, **self._ukw)
+                    if self._free:
+                        stars_d = e.stars_staged(stars_for_samples(
+                            self._stars_host, g, self._ntab, baseline_mean=None if bm is None else bm[sl],
+                            baseline_var=None if bv is None else bv[sl]), b["stars"])
                 e.kernel_table_samples(b["ez"], b["Ez"], self._rta1, self._covpts, tab=b["tab"], meanvar=b["mv"])
                 if gi + 1 < min(ngroups, len(self._slots)):
                     stagger = torch.cuda.Event()
                     stagger.record(stream)
-                e.lnlike_ensemble_planned(self._plan, None, None, self._stars, b["tab"], b["mv"],
+                e.lnlike_ensemble_planned(self._plan, None, None, stars_d, b["tab"], b["mv"],
                                           norm_order=self._norm_order, zmax=self._zmax, out=raw[gi], workspace=b["ws"])
                 if ngroups > QUEUED * len(self._slots):
                     ev = torch.cuda.Event()
@@ -257,6 +309,11 @@ class EnsembleLogProb(object):
         lp = EnsembleLogProb(t, flux, ferr=1e-3, p=periods)          # data -> GPU, once
         values = lp(samples)                                          # samples (n, 5): r, a, b, c, n
 
+    ``baseline_mean=None`` / ``baseline_log_var=None`` make the baseline mean m / the log10 of the baseline variance v
+    trailing columns of the samples, as in ``get_log_prob`` (calibrate/log_prob.py:24-47, 93-103); ``dr``: None (one
+    spot radius), a float in degrees (StarryProcess(dr=...)) or "free" (a column behind r).  The columns are
+    r[, dr], a, b, c, n[, m][, v] (``lp.columns``).
+
     Per sample: moments by quadrature on the device (upstream_device.py) -> kernel table ->
     one batched likelihood call for this rank's stars; nothing is copied back or synchronised
     until every sample is enqueued, and sample k runs on stream k mod ``depth`` with its own
@@ -275,7 +332,7 @@ class EnsembleLogProb(object):
     def __init__(self, t, flux, ferr=1.0e-3, p=1.0, i=None, u=None, ydeg=15, baseline_log_var=0.0,
                  baseline_mean=0.0, apply_jac=True, normalized=True,
                  marginalize_over_inclination=True, covpts=None, device=None, depth=3, upstream_stream=True,
-                 batch_samples=True, out_of_bounds="raise"):
+                 batch_samples=True, out_of_bounds="raise", dr=None):
         import torch
         import torch.distributed as dist
 
@@ -283,6 +340,21 @@ class EnsembleLogProb(object):
         from .defaults import defaults
         from .engine import engine_slots, make_stars
 
+        self._free = tuple(name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var))
+                           if val is None)
+        if isinstance(dr, str):
+            if dr != "free":
+                raise ValueError("dr must be None, a number or 'free'")
+        elif dr is not None:
+            from .ops import CheckBoundsOp
+
+            dr = float(dr)
+            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
+        self._dr = dr
+        self.columns = ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(
+            {"baseline_mean": "m", "baseline_log_var": "v"}[f] for f in self._free)
+        baseline_mean = 0.0 if baseline_mean is None else baseline_mean            # (placeholders: overwritten per sample)
+        baseline_log_var = 0.0 if baseline_log_var is None else baseline_log_var
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim != 2:
             raise ValueError("flux must be (S, K); ragged ensembles: get_log_prob_ensemble")
@@ -319,6 +391,7 @@ class EnsembleLogProb(object):
         self._t = e0.f64(np.ascontiguousarray(t[lo:hi]))
         self._flux = e0.f64(np.ascontiguousarray(flux[lo:hi, None, :]))
         self._stars = e0.stars_to_device(stars)
+        self._stars_host = stars
         self._rta1 = e0.f64(e0.rTA1L(utab))
         self._ws = [e.workspace(max(hi - lo, 1), K, 1) for e, _ in self._slots]
         self._kw = dict(conditional=not marginalize_over_inclination, normalized=bool(normalized),
@@ -351,7 +424,7 @@ class EnsembleLogProb(object):
         if self._plan is not None and batch_samples:
             more = engine_slots(ydeg, udeg, device, 2) if len(self._slots) + 1 + 2 <= MAX_STREAMS_SAMPLES else []
             self._batch = SampleBatches(self._slots + [self._up] + more, self._t, self._flux, stars, self._rta1,
-                                        self._kw["covpts"], plan=self._plan, zmax=0.023)
+                                        self._kw["covpts"], plan=self._plan, zmax=0.023, dr=self._dr, free=self._free)
         torch.cuda.synchronize(e0.device)
 
     def __call__(self, samples):
@@ -362,12 +435,13 @@ class EnsembleLogProb(object):
         from .upstream_device import ylm_moments_device
 
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-        if samples.shape[1] != 5:
-            raise ValueError("samples must be (n, 5): r, a, b, c, n")
+        if samples.shape[1] != len(self.columns):
+            raise ValueError("samples must be (n, %d): %s" % (len(self.columns), ", ".join(self.columns)))
+        nh = 6 if self._dr == "free" else 5            # r[, dr], a, b, c, n: the columns with bounds
         if self._oob == "inf":
             from .engine import samples_in_bounds
 
-            ok = samples_in_bounds(samples)
+            ok = samples_in_bounds(samples[:, :nh], dr=self._dr == "free") & np.all(np.isfinite(samples), axis=1)
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
@@ -382,11 +456,23 @@ class EnsembleLogProb(object):
         elif nl:
             eu, su = self._up
             keep = []                                   # (the moments stay alive until the batch is done)
-            for k, (r, a, b, c, n) in enumerate(samples):
+            for k, row in enumerate(samples):
+                r, (a, b, c, n) = row[0], row[nh - 4:nh]
+                dr = row[1] if self._dr == "free" else self._dr
+                stars_d = self._stars
+                if self._free:
+                    st = self._stars_host.copy()
+                    col = nh
+                    if "baseline_mean" in self._free:
+                        st["baseline_mean"], col = row[col], col + 1
+                    if "baseline_log_var" in self._free:
+                        st["baseline_var"] = 10.0 ** row[col]
+                    stars_d = eu.stars_to_device(st)
+                    keep.append(stars_d)
                 e, stream = self._slots[k % len(self._slots)]
                 if self._upstream_stream:
                     with torch.cuda.stream(su):
-                        mean, cov = ylm_moments_device(eu, r=r, a=a, b=b, c=c, n=n)
+                        mean, cov = ylm_moments_device(eu, r=r, dr=dr, a=a, b=b, c=c, n=n)
                         ready = torch.cuda.Event()
                         ready.record(su)
                     keep.append((mean, cov, ready))
@@ -394,17 +480,17 @@ class EnsembleLogProb(object):
                     if self._upstream_stream:
                         stream.wait_event(ready)
                     else:
-                        mean, cov = ylm_moments_device(e, r=r, a=a, b=b, c=c, n=n)
+                        mean, cov = ylm_moments_device(e, r=r, dr=dr, a=a, b=b, c=c, n=n)
                         keep.append((mean, cov))
                     e.set_moments_dev(mean, cov)
                     tab = mv = None
                     if self._marg:
                         tab, mv = e.kernel_table(self._rta1, self._kw["covpts"])
                     if self._plan is not None:
-                        e.lnlike_ensemble_planned(self._plan, self._t, self._flux, self._stars, tab, mv, out=outs[k],
+                        e.lnlike_ensemble_planned(self._plan, self._t, self._flux, stars_d, tab, mv, out=outs[k],
                                                   workspace=self._ws[k % len(self._slots)])
                     else:
-                        e.lnlike_ensemble(self._t, self._flux, self._stars, tab=tab, meanvar=mv,
+                        e.lnlike_ensemble(self._t, self._flux, stars_d, tab=tab, meanvar=mv,
                                           rta1=self._rta1, out=outs[k], workspace=self._ws[k % len(self._slots)],
                                           **self._kw)
         torch.cuda.synchronize(e0.device)
@@ -418,7 +504,7 @@ class EnsembleLogProb(object):
         if self._apply_jac:
             from .upstream import log_jac_samples
 
-            total = total + log_jac_samples(samples[:, 1], samples[:, 2])
+            total = total + log_jac_samples(samples[:, nh - 4], samples[:, nh - 3])
         return total
 
 

@@ -33,6 +33,8 @@
 namespace {
 
 constexpr int SM_TK = 64;     // columns of a sample's row block T (its 2 (ydeg + 2) <= 64 rotations, zero padded)
+constexpr int SM_SJ = 128;    // sm_spread_kernel: rows of C0 per workgroup (one per thread)
+constexpr int SM_SK = 64;     // ... and columns of Bp per LDS tile
 
 __device__ __forceinline__ double sm_wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -43,20 +45,42 @@ __device__ __forceinline__ double sm_wave_sum(double v) {
 // nonzero), the Gauss-Jacobi rule of the latitude law and the scales of the rotations.  grid B.
 //   basis: Bp [nl][spts] (upstream._spot_basis), then the colatitude grid theta [spts]
 //   samp [B][5]: r [rad], alpha, beta, c, n
-__global__ __launch_bounds__(256) void sm_prepare_kernel(int ydeg, int spts, double sfac, const double *__restrict__ basis,
+// SPREAD (sp_polar_moments_samples_spread): samp [B][6]: r, dr [rad], alpha, beta, c, n.  A row with dr > 0 draws its
+// radii uniformly from [r - dr, r + dr]: the profile integrated over the radius (size.py:55-61) gives the FIRST moment's
+// coefficients, written to evec; svec is all ones (the rotation rows are formed with unit coefficients, the second
+// moment's coefficients enter at the finish) and scal[4 b + 3] = kmax, the first grid index with theta / (r + dr) >
+// cutoff (0 when there is none: argmax of all-false, size.py:71), or -1 for a row with dr = 0, whose evec is the
+// one-radius size vector.
+template <bool SPREAD>
+__global__ __launch_bounds__(256) void sm_prepare_kernel(int ydeg, int spts, double sfac, double cutoff,
+                                                         const double *__restrict__ basis,
                                                          const double *__restrict__ samp, double *__restrict__ svec,
-                                                         double *__restrict__ cs, double *__restrict__ sc,
-                                                         double *__restrict__ scal) {
+                                                         double *__restrict__ evec, double *__restrict__ cs,
+                                                         double *__restrict__ sc, double *__restrict__ scal) {
   extern __shared__ __attribute__((aligned(16))) double sm_lds[];
+  __shared__ int s_kmax;
   const int nl = ydeg + 1, nq = ydeg + 2, b = blockIdx.x, tid = threadIdx.x;
   double *s_b = sm_lds;          // [spts] the profile
   double *s_d = s_b + spts;      // [nq] diagonal of the Jacobi matrix
   double *s_e = s_d + nq;        // [nq] off-diagonal (e[k] couples k and k + 1)
   double *s_e2 = s_e + nq;       // [nq] its squares
   double *s_w = s_e2 + nq;       // [nq] weights before normalisation
-  const double r = samp[5 * b], alpha = samp[5 * b + 1], beta = samp[5 * b + 2], c = samp[5 * b + 3], n = samp[5 * b + 4];
+  constexpr int NS = SPREAD ? 6 : 5;
+  const double *sp = samp + (size_t)NS * b;
+  const double r = sp[0], dr = SPREAD ? sp[1] : 0.0, alpha = sp[NS - 4], beta = sp[NS - 3], c = sp[NS - 2], n = sp[NS - 1];
   const double *theta = basis + (size_t)nl * spts;
-  for (int j = tid; j < spts; j += 256) s_b[j] = 1.0 / (1.0 + exp(-sfac * (theta[j] - r))) - 1.0;
+  if (SPREAD && dr > 0.0) {
+    if (tid == 0) s_kmax = spts;
+    __syncthreads();
+    const double inv = 1.0 / (2.0 * dr * sfac);
+    for (int j = tid; j < spts; j += 256) {
+      const double chim = exp(sfac * (r - dr - theta[j])), chip = exp(sfac * (r + dr - theta[j]));
+      s_b[j] = inv * log((1.0 + chim) / (1.0 + chip));
+      if (theta[j] / (r + dr) > cutoff) atomicMin(&s_kmax, j);     // (a minimum: the same whatever the order)
+    }
+  } else {
+    for (int j = tid; j < spts; j += 256) s_b[j] = 1.0 / (1.0 + exp(-sfac * (theta[j] - r))) - 1.0;
+  }
   // weight (1 - t)^(beta - 1) (1 + t)^(alpha - 1): the recurrence coefficients of sp_gauss_jacobi (sp_host.cpp)
   if (tid < nq) {
     const double a = beta - 1.0, bb = alpha - 1.0, ab = a + bb;
@@ -83,7 +107,14 @@ __global__ __launch_bounds__(256) void sm_prepare_kernel(int ydeg, int spts, dou
       double acc = 0.0;
       for (int j = lane; j < spts; j += 64) acc += row[j] * s_b[j];
       acc = sm_wave_sum(acc);
-      if (lane == 0) svec[(size_t)b * nl + l] = acc;
+      if (lane == 0) {
+        if (SPREAD) {
+          evec[(size_t)b * nl + l] = acc;
+          svec[(size_t)b * nl + l] = 1.0;
+        } else {
+          svec[(size_t)b * nl + l] = acc;
+        }
+      }
     }
   }
   // node i: the i-th eigenvalue of the Jacobi matrix, bracketed on the Sturm count (all of them lie in (-1, 1)).  A
@@ -154,8 +185,89 @@ __global__ __launch_bounds__(256) void sm_prepare_kernel(int ydeg, int spts, dou
       scal[4 * b] = g;
       scal[4 * b + 1] = sqrt(n);
       scal[4 * b + 2] = n;
-      scal[4 * b + 3] = 0.0;
+      scal[4 * b + 3] = !SPREAD ? 0.0 : (dr > 0.0 ? (double)(s_kmax == spts ? 0 : s_kmax) : -1.0);
     }
+  }
+}
+
+// The second moment of the radius-averaged profile's Legendre coefficients (size.py:63-89), without its square root:
+//     Etilde = Bp[:, :kmax] C0 Bp[:, :kmax]^T,
+//     C0[j][k] = (x term_k - term_j) / (1 - x + 1e-15),  x = exp(sfac (theta_k - theta_j)),            j != k
+//     C0[j][j] = 1 / (1 + chip_j) + chim_j / (1 + chim_j) - term_j - 1,
+//     chim = exp(sfac (r - dr - theta)), chip = exp(sfac (r + dr - theta)), term = log(1 + chim) - log(1 + chip)
+// (the common factor 1 / (2 dr sfac) is applied by sm_first_kernel).  A workgroup takes SM_SJ rows j of C0, one per
+// thread: the thread forms its row entry by entry -- C0 is never stored -- against tiles of SM_SK columns of Bp held
+// transposed in LDS (every lane reads the same address: a broadcast), V[j][l'] = sum_k C0[j][k] Bp[l'][k] in NLP
+// registers; the workgroup then folds its rows, part[b][blk][l][l'] = sum_j Bp[l][j] V[j][l'], in the order of j.
+// No atomics: the partial sums of a sample's workgroups are added in the order of blk by sm_first_kernel.
+// grid (ceil(spts / SM_SJ), B); a workgroup whose rows lie at or beyond kmax (or whose sample has dr = 0) does nothing
+// and its slot of `part` is never read.
+template <int NLP>
+__global__ __launch_bounds__(SM_SJ) void sm_spread_kernel(int nl, int spts, double sfac, const double *__restrict__ basis,
+                                                          const double *__restrict__ samp,
+                                                          const double *__restrict__ scal, double *__restrict__ part) {
+  __shared__ double s_bt[SM_SK][NLP + 1];
+  __shared__ double s_tk[SM_SK], s_term[SM_SK];
+  __shared__ double s_v[SM_SJ][NLP + 1];
+  const int blk = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  const int kmax = (int)scal[4 * b + 3], j0 = blk * SM_SJ;
+  if (kmax <= j0) return;
+  const double r = samp[6 * (size_t)b], dr = samp[6 * (size_t)b + 1];
+  const double *theta = basis + (size_t)nl * spts;
+  const int j = j0 + tid;
+  const bool live = j < kmax;
+  double tj = 0.0, termj = 0.0, diagj = 0.0;
+  if (live) {
+    tj = theta[j];
+    const double chim = exp(sfac * (r - dr - tj)), chip = exp(sfac * (r + dr - tj));
+    termj = log(1.0 + chim) - log(1.0 + chip);
+    diagj = 1.0 / (1.0 + chip) + chim / (1.0 + chim) - termj - 1.0;
+  }
+  double acc[NLP];
+#pragma unroll
+  for (int l = 0; l < NLP; ++l) acc[l] = 0.0;
+  for (int k0 = 0; k0 < kmax; k0 += SM_SK) {
+    __syncthreads();
+    for (int idx = tid; idx < SM_SK * NLP; idx += SM_SJ) {
+      const int l = idx / SM_SK, kk = idx - l * SM_SK, k = k0 + kk;
+      s_bt[kk][l] = (l < nl && k < kmax) ? basis[(size_t)l * spts + k] : 0.0;
+    }
+    if (tid < SM_SK) {
+      const int k = k0 + tid;
+      double tk = 0.0, term = 0.0;
+      if (k < kmax) {
+        tk = theta[k];
+        const double chim = exp(sfac * (r - dr - tk)), chip = exp(sfac * (r + dr - tk));
+        term = log(1.0 + chim) - log(1.0 + chip);
+      }
+      s_tk[tid] = tk;
+      s_term[tid] = term;
+    }
+    __syncthreads();
+    if (live) {
+      const int kn = kmax - k0 < SM_SK ? kmax - k0 : SM_SK;
+      for (int kk = 0; kk < kn; ++kk) {
+        double c0 = diagj;
+        if (k0 + kk != j) {
+          const double x = exp(sfac * (s_tk[kk] - tj));
+          c0 = (x * s_term[kk] - termj) / (1.0 - x + 1.0e-15);
+        }
+#pragma unroll
+        for (int l = 0; l < NLP; ++l) acc[l] += c0 * s_bt[kk][l];
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < NLP; ++l) s_v[tid][l] = live ? acc[l] : 0.0;
+  __syncthreads();
+  const int nrow = kmax - j0 < SM_SJ ? kmax - j0 : SM_SJ;
+  double *out = part + ((size_t)b * gridDim.x + blk) * nl * nl;
+  for (int p = tid; p < nl * nl; p += SM_SJ) {
+    const int l = p / nl, lp = p - l * nl;
+    const double *row = basis + (size_t)l * spts + j0;
+    double sum = 0.0;
+    for (int jj = 0; jj < nrow; ++jj) sum += row[jj] * s_v[jj][lp];
+    out[p] = sum;
   }
 }
 
@@ -218,9 +330,16 @@ __global__ __launch_bounds__(256) void sm_rows_kernel(int ydeg, int N, int P, co
 }
 
 // e1[b][n] = sum_k sqrt(w_k) T[b][n][k] at the m = 0 entries, zero elsewhere.  grid B
+// SPREAD: the rows carry unit coefficients, so the entry of degree l takes the first moment's coefficient evec[b][l]
+// here; and the sample's Etilde [nl][nl] is finished: the partial sums of sm_spread_kernel's nblk workgroups in their
+// order, symmetrised, over 2 dr sfac (size.py:82-85) -- or evec evec^T for a row with one radius (scal[4 b + 3] < 0).
+template <bool SPREAD>
 __global__ __launch_bounds__(256) void sm_first_kernel(int N, int P, const int32_t *__restrict__ m_of,
                                                        const double *__restrict__ sc, const double *__restrict__ T,
-                                                       double *__restrict__ e1) {
+                                                       double *__restrict__ e1, int nl, const int32_t *__restrict__ l_of,
+                                                       const double *__restrict__ evec, const double *__restrict__ samp,
+                                                       const double *__restrict__ scal, double sfac, int nblk,
+                                                       const double *__restrict__ part, double *__restrict__ Et) {
   const int b = blockIdx.x;
   const double *sq = sc + (size_t)b * 2 * P + P;
   for (int n = threadIdx.x; n < N; n += 256) {
@@ -228,17 +347,42 @@ __global__ __launch_bounds__(256) void sm_first_kernel(int N, int P, const int32
     if (m_of[n] == 0) {
       const double *row = T + ((size_t)b * N + n) * SM_TK;
       for (int k = 0; k < P; ++k) acc += sq[k] * row[k];
+      if (SPREAD) acc *= evec[(size_t)b * nl + l_of[n]];
     }
     e1[(size_t)b * N + n] = acc;
+  }
+  if (SPREAD) {
+    const double kmaxf = scal[4 * b + 3], dr = samp[6 * (size_t)b + 1];
+    const int used = kmaxf > 0.0 ? ((int)kmaxf + SM_SJ - 1) / SM_SJ : 0;
+    const double *pb = part + (size_t)b * nblk * nl * nl, *eb = evec + (size_t)b * nl;
+    for (int p = threadIdx.x; p < nl * nl; p += 256) {
+      const int l = p / nl, lp = p - l * nl;
+      double v;
+      if (kmaxf < 0.0) {
+        v = eb[l < lp ? l : lp] * eb[l < lp ? lp : l];
+      } else {
+        double x = 0.0, y = 0.0;
+        for (int k = 0; k < used; ++k) {
+          x += pb[(size_t)k * nl * nl + l * nl + lp];
+          y += pb[(size_t)k * nl * nl + lp * nl + l];
+        }
+        v = 0.5 * (x + y) / (2.0 * dr * sfac);
+      }
+      Et[(size_t)b * nl * nl + p] = v;
+    }
   }
 }
 
 // Ez[b] = Proj(M[b]) + (n - 1) e1 e1^T + diag(eps), ez[b] = sqrt(n) e1.  grid (ceil(N^2 / 256), B)
+// SPREAD: M was formed from rows with unit coefficients; entry ((l, m), (l', m')) of its projection takes the factor
+// Etilde[l][l'] (the projection mixes entries of one (l, l') block only, so the factor commutes with it).
+template <bool SPREAD>
 __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__restrict__ m_of,
                                                         const int32_t *__restrict__ mirror, const double *__restrict__ M,
                                                         const double *__restrict__ e1, const double *__restrict__ scal,
                                                         double epsy, double epsy15, double *__restrict__ ez,
-                                                        double *__restrict__ Ez) {
+                                                        double *__restrict__ Ez, int nl, const int32_t *__restrict__ l_of,
+                                                        const double *__restrict__ Et) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (e >= (long)N * N) return;
@@ -251,6 +395,7 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__
     const int ii = mirror[i], jj = mirror[j];
     const double x = Mb[(size_t)i * N + j], y = Mb[(size_t)ii * N + jj];
     v = mi == mj ? 0.5 * (x + y) : 0.5 * (x - y);
+    if (SPREAD) v *= Et[(size_t)b * nl * nl + l_of[i] * nl + l_of[j]];
   }
   const int lo = i < j ? i : j, hi = i < j ? j : i;
   v += (scal[4 * b + 2] - 1.0) * (eb[lo] * eb[hi]);
@@ -311,8 +456,8 @@ int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, do
          *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE);
   const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);      // (+ 256 ints of flags)
   if (lds1 > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds1);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel<false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
   {
     // ONE staged upload: the samples (read by sm_prepare_kernel only)
     SpStage stage(h, 5 * (size_t)B);
@@ -320,20 +465,98 @@ int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, do
     memcpy(stage.host, samples_host, sizeof(double) * 5 * B);
     const double *samp = stage.upload(st);
     if (!samp) return SP_ERR_HIP;
-    hipLaunchKernelGGL(sm_prepare_kernel, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, h->d_size_basis, samp,
-                       svec, cs, sc, scal);
+    hipLaunchKernelGGL(sm_prepare_kernel<false>, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, 0.0,
+                       h->d_size_basis, samp, svec, (double *)nullptr, cs, sc, scal);
     SP_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
                      svec, cs, h->d_Rx90, sc, T);
   SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sm_first_kernel, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1);
+  hipLaunchKernelGGL(sm_first_kernel<false>, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1, nl,
+                     (const int32_t *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0.0,
+                     0, (const double *)nullptr, (double *)nullptr);
   SP_LAUNCH_CHECK();
   if ((rc = sp_launch_gemm_nt(T, SM_TK, (long)N * SM_TK, T, SM_TK, (long)N * SM_TK, M, N, (long)N * N, N, N, SM_TK, 1.0, 0,
                               0, B, st)))
     return rc;
-  hipLaunchKernelGGL(sm_finish_kernel, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N, h->d_m_of,
-                     h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev);
+  hipLaunchKernelGGL(sm_finish_kernel<false>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
+                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, (const int32_t *)nullptr,
+                     (const double *)nullptr);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
+                                    double epsy15, double *ez_dev, double *Ez_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !samples_host || !ez_dev || !Ez_dev || B < 0 || B > 65535 || !(cutoff > 0.0)) return SP_ERR_INVALID;
+  if (!h->d_size_basis) return SP_ERR_STATE;
+  if (B == 0) return SP_OK;
+  const int N = h->N, nl = h->ydeg + 1, nq = h->ydeg + 2, P = 2 * nq, spts = h->size_spts;
+  if (P > SM_TK) return SP_ERR_INVALID;
+  bool any_spread = false;
+  for (int b = 0; b < B; ++b) {
+    const double *s = samples_host + 6 * (size_t)b;
+    // r, dr in [0, pi/2] (size.py:103-122), then as sp_polar_moments_samples
+    if (!(s[0] >= 0.0 && s[0] <= 1.5707963267948966 + 1e-6) || !(s[1] >= 0.0 && s[1] <= 1.5707963267948966 + 1e-6) ||
+        !(s[2] > 0.0) || !(s[3] > 0.0) || !std::isfinite(s[2]) || !std::isfinite(s[3]) || !std::isfinite(s[4]) ||
+        !(s[5] >= 0.0) || !std::isfinite(s[5]))
+      return SP_ERR_INVALID;
+    any_spread = any_spread || s[1] > 0.0;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  SP_HIP(hipSetDevice(h->device));
+  // scratch: as sp_polar_moments_samples, then evec [B][nl] | Et [B][nl][nl] | part [B][nblk][nl][nl]
+  const int nblk = (spts + SM_SJ - 1) / SM_SJ;
+  const size_t d = sizeof(double);
+  SpCarve c;
+  const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
+               oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N),
+               oV = c.take(d * B * nl), oEt = c.take(d * B * nl * nl), oP = c.take(d * B * nblk * nl * nl);
+  void *ws = nullptr;
+  int rc = sp_ensure_scratch(h->big, c.off, &ws);
+  if (rc) return rc;
+  double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
+         *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE), *evec = at<double>(ws, oV),
+         *Et = at<double>(ws, oEt), *part = at<double>(ws, oP);
+  const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);
+  if (lds1 > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel<true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
+  {
+    // ONE staged upload: the samples (read until sm_first_kernel: the scope covers the launches up to it)
+    SpStage stage(h, 6 * (size_t)B);
+    if (stage.rc) return stage.rc;
+    memcpy(stage.host, samples_host, sizeof(double) * 6 * B);
+    const double *samp = stage.upload(st);
+    if (!samp) return SP_ERR_HIP;
+    hipLaunchKernelGGL(sm_prepare_kernel<true>, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, cutoff,
+                       h->d_size_basis, samp, svec, evec, cs, sc, scal);
+    SP_LAUNCH_CHECK();
+    if (any_spread) {
+      const dim3 grid(nblk, B), block(SM_SJ);
+      if (nl <= 8)
+        hipLaunchKernelGGL(sm_spread_kernel<8>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+      else if (nl <= 16)
+        hipLaunchKernelGGL(sm_spread_kernel<16>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+      else if (nl <= 24)
+        hipLaunchKernelGGL(sm_spread_kernel<24>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+      else
+        hipLaunchKernelGGL(sm_spread_kernel<32>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+      SP_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
+                       svec, cs, h->d_Rx90, sc, T);
+    SP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sm_first_kernel<true>, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1, nl, h->d_l_of, evec,
+                       samp, scal, h->size_sfac, nblk, part, Et);
+    SP_LAUNCH_CHECK();
+  }
+  if ((rc = sp_launch_gemm_nt(T, SM_TK, (long)N * SM_TK, T, SM_TK, (long)N * SM_TK, M, N, (long)N * N, N, N, SM_TK, 1.0, 0,
+                              0, B, st)))
+    return rc;
+  hipLaunchKernelGGL(sm_finish_kernel<true>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
+                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, h->d_l_of, Et);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

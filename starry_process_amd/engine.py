@@ -38,37 +38,64 @@ def make_stars(S, period=1.0, inc_deg=60.0, tau=0.0, baseline_var=0.0,
     return st
 
 
-def stars_for_samples(stars, B, ntab):
+def stars_for_samples(stars, B, ntab, baseline_mean=None, baseline_var=None):
     """The sp_star array of a batch of B hyperparameter samples x S stars (sample-major: system b S + s): the S stars
     repeated B times with table = b ntab + table_s, the kernel table of sample b for the star's flux operator
-    (sp_kernel_table_samples' numbering)."""
+    (sp_kernel_table_samples' numbering).  ``baseline_mean`` / ``baseline_var`` [B]: the baseline terms of sample b
+    when they are free parameters of the samples (calibrate/log_prob.py:24-47), for every star of that sample."""
     stars = np.ascontiguousarray(stars)
     assert stars.dtype == STAR_DTYPE
     out = np.tile(stars, int(B))
     out["table"] = (np.repeat(np.arange(int(B), dtype=np.int64), stars.shape[0]) * int(ntab) + out["table"]).astype(np.int32)
+    for field, val in (("baseline_mean", baseline_mean), ("baseline_var", baseline_var)):
+        if val is not None:
+            val = np.asarray(val, dtype=np.float64).reshape(-1)
+            if val.shape[0] != int(B):
+                raise ValueError("%s must have one entry per sample" % field)
+            out[field] = np.repeat(val, stars.shape[0])
     return out
 
 
-def samples_in_bounds(samples, tol=1e-6):
+def samples_in_bounds(samples, tol=1e-6, dr=False):
     """Boolean mask of the rows of samples [B, 5] = (r [degrees], a, b, c, n) inside the reference's bounds (r in [0, 90],
     a, b in [0, 1], n >= 0, everything finite; size.py:68, latitude.py:176-197, contrast.py:21-33 through CheckBoundsOp's
     tolerance): what ``sample_parameters`` raises ValueError for.  A sampler's walkers leave the box; the log-probability
-    callables can answer -inf for such rows instead of raising (``out_of_bounds="inf"``)."""
+    callables can answer -inf for such rows instead of raising (``out_of_bounds="inf"``).  ``dr=True``: rows of
+    (r, dr [degrees], a, b, c, n), dr in [0, 90] (size.py:120-122)."""
     sm = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
     ok = np.all(np.isfinite(sm), axis=1)
+    if dr:
+        d = sm[:, 1] * (np.pi / 180)
+        ok &= (d >= -tol) & (d <= 0.5 * np.pi + tol)
+        sm = np.delete(sm, 1, axis=1)
+    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
     ok &= (r >= -tol) & (r <= 0.5 * np.pi + tol) & (a >= -tol) & (a <= 1 + tol) & (b >= -tol) & (b <= 1 + tol) & (n >= -tol)
     return ok
 
 
-def sample_parameters(samples, **kw):
+def sample_parameters(samples, dr=False, **kw):
     """samples [B, 5] = (r [degrees], a, b, c, n) -> [B, 5] = (r [radians], alpha, beta, c, n), what
     sp_polar_moments_samples takes: the reference's bounds (size.py:68, latitude.py:176-197, contrast.py:21-33 through
     CheckBoundsOp: ValueError outside, tolerance 1e-6) and its (a, b) -> (alpha, beta) map, for the whole batch at once
-    (NumPy; one sample at a time ``upstream.ab_to_alphabeta`` does the same)."""
+    (NumPy; one sample at a time ``upstream.ab_to_alphabeta`` does the same).  ``dr=True``: samples [B, 6] = (r, dr
+    [degrees], a, b, c, n) -> [B, 6] = (r, dr [radians], alpha, beta, c, n), what sp_polar_moments_samples_spread takes
+    (dr in [0, 90] degrees, size.py:120-122)."""
     from .defaults import defaults
 
     sm = np.array(np.atleast_2d(np.asarray(samples, dtype=np.float64)), dtype=np.float64)
+    if dr:
+        if sm.ndim != 2 or sm.shape[1] != 6:
+            raise ValueError("samples must be (B, 6): r, dr, a, b, c, n")
+        from .ops import CheckBoundsOp
+
+        d = sm[:, 1] * (np.pi / 180)
+        CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(d)
+        if not np.all(np.isfinite(d)):
+            raise ValueError("samples must be finite")
+        out = np.empty_like(sm)
+        out[:, [0, 2, 3, 4, 5]] = sample_parameters(np.delete(sm, 1, axis=1), **kw)
+        out[:, 1] = np.clip(d, 0.0, None)
+        return np.ascontiguousarray(out)
     if sm.ndim != 2 or sm.shape[1] != 5:
         raise ValueError("samples must be (B, 5): r, a, b, c, n")
     r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
@@ -150,7 +177,7 @@ class Engine(object):
             t = t.to(dtype)
         return t.contiguous()
 
-    def _upload_small(self, a):
+    def _upload_small(self, a, out=None):
         """Small fp64 host array -> device through a ring of pinned staging buffers: the copy is
         enqueued on the current stream and the call returns (a pageable source makes the runtime
         stage and wait: 50 us per upload, four uploads per upstream evaluation).  A slot is reused
@@ -168,7 +195,8 @@ class Engine(object):
         n = a.size
         src = ring["buf"][k][:n]
         src.numpy()[...] = a.reshape(-1)
-        out = torch.empty(a.shape, dtype=torch.float64, device=self.device)
+        if out is None:
+            out = torch.empty(a.shape, dtype=torch.float64, device=self.device)
         out.view(-1).copy_(src, non_blocking=True)
         ev = ring["ev"][k]
         if ev is None:
@@ -189,6 +217,19 @@ class Engine(object):
         assert stars.dtype == STAR_DTYPE
         raw = torch.from_numpy(stars.view(np.uint8).reshape(-1).copy())
         return raw.to(self.device)
+
+    def stars_staged(self, stars, out):
+        """``stars`` (host sp_star array) into the device array ``out`` (of stars_to_device, same length) through the
+        pinned staging ring: one copy enqueued on the current stream, nothing synchronised -- for star arrays that
+        change from call to call (the free baseline terms of calibrate.SampleBatches)."""
+        stars = np.ascontiguousarray(stars)
+        assert stars.dtype == STAR_DTYPE and STAR_DTYPE.itemsize % 8 == 0
+        assert out.numel() == stars.nbytes
+        if stars.nbytes > _STAGE_BYTES:
+            out.copy_(_torch().from_numpy(stars.view(np.uint8).reshape(-1).copy()))
+            return out
+        self._upload_small(stars.view(np.float64).reshape(-1), out=out.view(_torch().float64))
+        return out
 
     @staticmethod
     def _p(t):
@@ -370,14 +411,25 @@ class Engine(object):
         check(self._L.sp_set_size_basis(self._h, hptr(theta), hptr(Bp), int(theta.shape[0]), sfac))
         self._size_basis_key = key
 
-    def polar_moments_samples(self, samples, ez=None, Ez=None, **kw):
+    def polar_moments_samples(self, samples, ez=None, Ez=None, dr=None, **kw):
         """samples [B, 5] = (r [degrees], a, b, c, n) per row, the argument order of the reference's log-probability
         (calibrate/log_prob.py:93-102) -> (ez [B, N], Ez [B, N, N]) device tensors: the polar-frame moments of B
         hyperparameter samples in one library call (sp_polar_moments_samples).  Bounds are the reference's
-        (ValueError before anything is launched)."""
+        (ValueError before anything is launched).  ``dr``: None (one spot radius), or the half-width of the uniform
+        law of the radii in degrees, a scalar or one value per sample (StarryProcess(dr=...), size.py:109-125): one
+        call of sp_polar_moments_samples_spread; a sample with dr = 0 is the one-radius case."""
         from .defaults import defaults
 
-        sm = sample_parameters(samples, **kw)
+        if dr is not None:
+            sm5 = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+            if sm5.ndim != 2 or sm5.shape[1] != 5:
+                raise ValueError("samples must be (B, 5): r, a, b, c, n")
+            d = np.asarray(dr, dtype=np.float64)
+            if d.ndim > 1 or (d.ndim == 1 and d.shape[0] != sm5.shape[0]):
+                raise ValueError("dr must be a scalar or one value per sample")
+            sm = sample_parameters(np.insert(sm5, 1, np.broadcast_to(d, (sm5.shape[0],)), axis=1), dr=True, **kw)
+        else:
+            sm = sample_parameters(samples, **kw)
         B = sm.shape[0]
         self.set_size_basis(**kw)
         if ez is None:
@@ -385,6 +437,11 @@ class Engine(object):
         if Ez is None:
             Ez = self.empty(B, self.N, self.N)
         assert tuple(ez.shape) == (B, self.N) and tuple(Ez.shape) == (B, self.N, self.N)
+        if dr is not None:
+            check(self._L.sp_polar_moments_samples_spread(
+                self._h, B, hptr(sm), float(kw.get("cutoff", 1.5)), float(kw.get("epsy", defaults["epsy"])),
+                float(kw.get("epsy15", defaults["epsy15"])), self._p(ez), self._p(Ez), self._stream()))
+            return ez, Ez
         check(self._L.sp_polar_moments_samples(
             self._h, B, hptr(sm), float(kw.get("epsy", defaults["epsy"])), float(kw.get("epsy15", defaults["epsy15"])),
             self._p(ez), self._p(Ez), self._stream()))

@@ -275,34 +275,48 @@ class StarryProcess(object):
         baseline_var=defaults["baseline_var"],
         depth=6,
         out_of_bounds="raise",
+        params=("r", "a", "b", "c", "n"),
     ):
         """``log_likelihood(t, flux, data_cov, ...)`` of THIS process's settings (degree, normalisation, lag grid,
-        temporal kernel) at many hyperparameter vectors: samples (ns, 5) = rows of (r, a, b, c, n) -> (ns,) values, each
-        what ``StarryProcess(r=r, a=a, b=b, c=c, n=n, <same settings>, upstream="device").log_likelihood(...)``
-        returns.  What a sampler does with the reference one call at a time (sp.py:1052-1062 driven by
-        calibrate/sample.py:95-107) is here ONE batched device step per 64 samples (calibrate.SampleBatches) --
-        marginalised, normalised processes with one spot radius and scalar or per-cadence data variance; anything
-        else is evaluated sample by sample.  ``out_of_bounds="inf"``: samples outside the reference's parameter bounds
-        (a ValueError there and, by default, here) get -inf and are not evaluated."""
+        temporal kernel, spot-size spread dr) at many hyperparameter vectors: samples (ns, 5) = rows of (r, a, b, c, n)
+        -> (ns,) values, each what ``StarryProcess(r=r, a=a, b=b, c=c, n=n, <same settings>,
+        upstream="device").log_likelihood(...)`` returns.  What a sampler does with the reference one call at a time
+        (sp.py:1052-1062 driven by calibrate/sample.py:95-107) is here ONE batched device step per 64 samples
+        (calibrate.SampleBatches) -- marginalised, normalised processes with scalar or per-cadence data variance;
+        anything else is evaluated sample by sample.  ``params`` names the columns of ``samples``: r, a, b, c, n and,
+        each at most once, "dr", "baseline_mean", "baseline_log_var" (log10 of the baseline variance); such a column
+        overrides the constructor's dr or the argument of the same name.  ``out_of_bounds="inf"``: samples outside the
+        reference's parameter bounds (a ValueError there and, by default, here) get -inf and are not evaluated."""
         from .calibrate import MAX_STREAMS_SAMPLES, SampleBatches, clamp_depth
         from .engine import engine_slots
 
         f = self._flux
         t, i, p, u = f._ingest(t, i, p, u)
         K = t.shape[0]
+        params = tuple(params)
+        allowed = ("r", "dr", "a", "b", "c", "n", "baseline_mean", "baseline_log_var")
+        if (len(set(params)) != len(params) or any(q not in allowed for q in params)
+                or any(q not in params for q in ("r", "a", "b", "c", "n"))):
+            raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var")
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-        if samples.shape[1] != 5:
-            raise ValueError("samples must be (ns, 5): r, a, b, c, n")
+        if samples.shape[1] != len(params):
+            raise ValueError("samples must be (ns, %d): %s" % (len(params), ", ".join(params)))
+        # the columns in SampleBatches' order: r[, dr], a, b, c, n[, m][, v]
+        dr_free = "dr" in params
+        free = tuple(q for q in ("baseline_mean", "baseline_log_var") if q in params)
+        order = ("r",) + (("dr",) if dr_free else ()) + ("a", "b", "c", "n") + free
+        samples = np.ascontiguousarray(samples[:, [params.index(q) for q in order]])
+        nh = 6 if dr_free else 5
         if out_of_bounds == "inf":
             from .engine import samples_in_bounds
 
-            ok = samples_in_bounds(samples)
+            ok = samples_in_bounds(samples[:, :nh], dr=dr_free) & np.all(np.isfinite(samples), axis=1)
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
                     out[ok] = np.asarray(self.log_likelihood_samples(t, flux, data_cov, samples[ok], i=i, p=p, u=u,
                                                                      baseline_mean=baseline_mean, baseline_var=baseline_var,
-                                                                     depth=depth))
+                                                                     depth=depth, params=order))
                 return Eager(out)
         elif out_of_bounds != "raise":
             raise ValueError("out_of_bounds must be 'raise' or 'inf'")
@@ -310,18 +324,32 @@ class StarryProcess(object):
         F = flux.reshape(1, K) if flux.ndim == 1 else flux.reshape(-1, K)
         data_cov = np.asarray(data_cov, dtype=np.float64)
         bmean, bvar = np.asarray(baseline_mean, dtype=np.float64), np.asarray(baseline_var, dtype=np.float64)
-        batched = (self._marginalize_over_inclination and self._normalized and self._dr is None and K >= 2
+        if "baseline_mean" in free:
+            bmean = np.float64(0.0)       # (a placeholder: the column overrides the argument)
+        if "baseline_log_var" in free:
+            bvar = np.float64(0.0)
+        batched = (self._marginalize_over_inclination and self._normalized and K >= 2
                    and data_cov.ndim <= 1 and bmean.ndim == 0 and bvar.ndim == 0)
         if not batched:
             kw = dict(self._kwargs)
-            kw.update(dr=self._dr, tau=self._tau if self._time_variable else None, temporal_kernel=self._temporal or "matern32",
+            kw.update(tau=self._tau if self._time_variable else None, temporal_kernel=self._temporal or "matern32",
                       marginalize_over_inclination=self._marginalize_over_inclination, normalized=self._normalized,
                       covpts=self._covpts, upstream="device")
-            return Eager(np.array([float(StarryProcess(r=r, a=a, b=b, c=c, n=n, **kw).log_likelihood(
-                t, flux, data_cov, i=i, p=p, u=u, baseline_mean=baseline_mean, baseline_var=baseline_var))
-                for r, a, b, c, n in samples]))
+            out = []
+            for row in samples:
+                r, (a, b, c, n) = row[0], row[nh - 4:nh]
+                col = nh
+                bm, bv = baseline_mean, baseline_var
+                if "baseline_mean" in free:
+                    bm, col = row[col], col + 1
+                if "baseline_log_var" in free:
+                    bv = 10.0 ** row[col]
+                out.append(float(StarryProcess(r=r, dr=row[1] if dr_free else self._dr, a=a, b=b, c=c, n=n, **kw).log_likelihood(
+                    t, flux, data_cov, i=i, p=p, u=u, baseline_mean=bm, baseline_var=bv)))
+            return Eager(np.array(out))
+        dr = "free" if dr_free else (None if self._dr is None else float(self._dr))
         key = (t.tobytes(), F.tobytes(), data_cov.tobytes(), float(p), tuple(np.asarray(u, dtype=float).reshape(-1)),
-               float(bmean), float(bvar), int(depth))
+               float(bmean), float(bvar), int(depth), dr, free)
         cache = self.__dict__.get("_sample_batches")
         if cache is None or cache[0] != key:
             # (the data set is planned once and kept: a sampler calls this with the same data every iteration)
@@ -330,12 +358,14 @@ class StarryProcess(object):
             e0 = slots[0][0]
             stars = make_stars(1, period=p, inc_deg=i, tau=self._tau, baseline_var=float(bvar), baseline_mean=float(bmean),
                                data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
-            ukw = {k: self._kwargs[k] for k in ("epsy", "epsy15", "spts", "eps4", "smoothing", "sfac", "abmin",
+            ukw = {k: self._kwargs[k] for k in ("epsy", "epsy15", "spts", "eps4", "smoothing", "sfac", "cutoff", "abmin",
                                                 "log_alpha_max", "log_beta_max") if k in self._kwargs}
+            extra = {} if dr is None and not free else dict(dr=dr, free=free)
             sb = SampleBatches(slots, e0.f64(t[None, :]), e0.f64(F[None, :, :]), stars,
                                e0.f64(e0.rTA1L(np.asarray(u, dtype=np.float64))), self._covpts,
                                diag_dev=e0.f64(data_cov.reshape(1, K)) if data_cov.ndim == 1 else None,
-                               temporal=self._temporal, norm_order=self._normN, zmax=self._normzmax, upstream_kwargs=ukw)
+                               temporal=self._temporal, norm_order=self._normN, zmax=self._normzmax, upstream_kwargs=ukw,
+                               **extra)
             cache = self._sample_batches = (key, sb)
         out = cache[1](samples)
         import torch

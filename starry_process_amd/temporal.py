@@ -32,6 +32,9 @@ def Matern32Kernel(t1, t2, tau):
 def kernel_id(kernel):
     if kernel is None:
         return None
+    if kernel in ("matern32", "expsquared"):
+        # (its own two ids: a process rebuilt from another's settings passes the id it holds)
+        return kernel
     if kernel is Matern32Kernel or getattr(kernel, "__name__", "") == "Matern32Kernel":
         return "matern32"
     if kernel is ExpSquaredKernel or getattr(kernel, "__name__", "") == "ExpSquaredKernel":
