@@ -208,6 +208,17 @@ int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_h
 int sp_kernel_table_samples(sp_handle *h, int B, const double *ez_dev, const double *Ez_dev, const double *rta1_dev,
                             int ntab, int covpts, const double *xp_host, double *tab_dev, double *meanvar_dev,
                             void *stream);
+/* sp_ylm_moments_samples: the Ylm-frame moments (mu_y, Sigma_y) of B samples in one call -- what the CONDITIONAL branch
+ * reads (flux.py:337-343), and what sp_ylm_moments_quadrature computes one sample at a time (0.3 ms each).  The same
+ * chain as above in the polar frame, finished as the polar-frame mean and covariance and rotated back by the handle's
+ * Rx(pi/2) blocks: mu = ez Rx(pi/2)^T, Sigma = Rx(pi/2) (Ez - ez ez^T) Rx(pi/2)^T, the difference formed term by term
+ * (never as a subtraction of the two large moments).  samples_host [B][5] as sp_polar_moments_samples (spread == 0,
+ * cutoff ignored) or [B][6] as sp_polar_moments_samples_spread (spread != 0).  Outputs mean_ylm_dev [B][N], cov_ylm_dev
+ * [B][N][N] (DEVICE).  One upload, eight launches (nine with a row of dr > 0), no host arithmetic per sample, nothing
+ * synchronised; B samples in one call give the bits of B calls with one sample each.  Status codes as the two above;
+ * B = 0 is SP_OK and touches nothing.                                                                              */
+int sp_ylm_moments_samples(sp_handle *h, int B, const double *samples_host, int spread, double cutoff, double epsy,
+                           double epsy15, double *mean_ylm_dev, double *cov_ylm_dev, void *stream);
 
 /* ---- per-star parameter block -------------------------------------------- */
 /* All batched entry points below take `S` stars with a common row length K.  A
@@ -329,6 +340,28 @@ int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
                        const double *rta1_dev, int temporal, int normalized,
                        int norm_order, double zmax, void *workspace_dev,
                        double *lnlike_dev, uint32_t *status_dev, void *stream);
+
+/* sp_lnlike_ensemble's CONDITIONAL branch with one moment set per system: system s is evaluated under
+ * (mean_ylm[select[s]], cov_ylm[select[s]]), one of B sets in DEVICE memory (sp_ylm_moments_samples writes them) --
+ * the (sample, star) pairs of a sampler on a process that does not marginalise over the inclination, whose stars
+ * carry their own period, inclination and timescale (sp_star).  Arguments, status codes, ragged handling, -inf / NaN
+ * rules, temporal kernels and the normalised / un-normalised forms are sp_lnlike_ensemble's (conditional = 1);
+ * mean_ylm_dev [B][N], cov_ylm_dev [B][N][N], select_dev [S] int32.  The handle's own moments are neither needed,
+ * read nor changed.  The launches are those of sp_lnlike_ensemble: the product A_s Sigma runs on the same tiles
+ * with its second operand chosen per system inside the kernel, and so does (A_s mu)[0].  Each value comes from its
+ * own system's inputs alone: the same bits in any batch and at any position, and the bits of sp_lnlike_ensemble
+ * (conditional = 1) after sp_set_ylm_moments_dev of that set.  SP_ERR_INVALID for a null required pointer or B < 1;
+ * select_dev lives in device memory and is not read by the host (that would synchronise the stream): an entry
+ * outside [0, B) never reads outside the sets and gives its system -inf with SP_STAR_NAN -- callers that hold the
+ * indices on the host check them there (Engine.lnlike_ensemble_sets raises).  S = 0 is SP_OK with nothing touched;
+ * a host-only handle SP_ERR_NO_DEVICE.  workspace_dev: sp_lnlike_ensemble_sets_workspace_bytes(h, S, K, M) bytes
+ * (= sp_lnlike_workspace_bytes).                                                                                  */
+long sp_lnlike_ensemble_sets_workspace_bytes(sp_handle *h, int S, int K, int M);
+int sp_lnlike_ensemble_sets(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                            const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, int B,
+                            const double *mean_ylm_dev, const double *cov_ylm_dev, const int32_t *select_dev,
+                            int temporal, int normalized, int norm_order, double zmax, void *workspace_dev,
+                            double *lnlike_dev, uint32_t *status_dev, void *stream);
 
 /* ---- the planned step (round 5): what depends on the DATA alone, taken out of the per-sample call -------------
  * A sampler evaluates the likelihood of ONE data set (t, flux, data variances, periods) at many hyperparameter

@@ -77,33 +77,39 @@ class SampleBatches(object):
     ``dr``: None (one spot radius), a float (radii uniform in [r - dr, r + dr] degrees, the same for every sample:
     StarryProcess(dr=...)) or "free" (a column of the samples); ``free``: which of ("baseline_mean",
     "baseline_log_var") are columns of the samples instead of fields of ``stars`` (calibrate/log_prob.py:24-47).  The
-    columns are r[, dr], a, b, c, n[, m][, v]: the reference's order with dr where the constructor has it.  With free
-    baseline terms every group's star array goes up through the pinned staging ring into the slot's own device array
-    (the planned step reads the baseline terms of its stars on every call)."""
+    columns are r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]: the reference's order (calibrate/log_prob.py:93-102: the
+    inclination behind the baseline terms) with dr where the constructor has it and the two parameters of its
+    time-variability tutorial last.  With free terms every group's star array goes up through the pinned staging ring
+    into the slot's own device array (the likelihood step reads its stars on every call).
 
-    FREE = ("baseline_mean", "baseline_log_var")
+    ``free`` may also name "i" (inclination in degrees; conditional only), "p" (period) and "tau" (timescale; needs a
+    temporal kernel), which become fields of sample b's stars.  Three routes:
+      * ``conditional=True`` (the process does not marginalise over the inclination; ``normalized`` either way): the
+        samples' Ylm-frame moments (sp_ylm_moments_samples), then ONE sp_lnlike_ensemble_sets call per group, system
+        b S + s under set b.  No plan, no tables: the data are tiled ``group`` times once, at construction.
+      * marginal with free "p" or "tau": the tables as below, then the unplanned sp_lnlike_ensemble on the tiled data
+        (the plan fixes period and timescale).
+      * marginal otherwise: the planned path described above, unchanged."""
+
+    FREE = ("baseline_mean", "baseline_log_var", "i", "p", "tau")
+    _NAMES = {"baseline_mean": "m", "baseline_log_var": "v", "i": "i", "p": "p", "tau": "tau"}
 
     def __init__(self, slots, t_dev, flux_dev, stars, rta1_dev, covpts, diag_dev=None, temporal=None, group=None,
-                 norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None, dr=None, free=()):
+                 norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None, dr=None, free=(), conditional=False,
+                 normalized=True):
         import torch
 
-        from .engine import stars_for_samples
-
-        free = (free,) if isinstance(free, str) else tuple(free)
-        if len(set(free)) != len(free) or any(f not in self.FREE for f in free):
-            raise ValueError("free must be a subset of %r" % (self.FREE,))
-        if isinstance(dr, str):
-            if dr != "free":
-                raise ValueError("dr must be None, a number or 'free'")
-        elif dr is not None:
-            from .ops import CheckBoundsOp
-
+        self.columns, self._free = self.column_names(dr=dr, free=free, conditional=conditional, temporal=temporal)
+        if dr is not None and not isinstance(dr, str):
             dr = float(dr)
-            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
         self._dr = dr
-        self._free = tuple(f for f in self.FREE if f in free)
-        self.columns = ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(
-            {"baseline_mean": "m", "baseline_log_var": "v"}[f] for f in self._free)
+        self._conditional, self._normalized, self._temporal = bool(conditional), bool(normalized), temporal
+        if not self._normalized and not self._conditional:
+            raise ValueError("the marginal branch is batched in its normalised form only")
+        # (the plan fixes every star's period and timescale: with either free, the unplanned call on tiled data)
+        self._planned = not self._conditional and not ("p" in self._free or "tau" in self._free)
+        if plan is not None and not self._planned:
+            raise ValueError("plan= belongs to the planned route: not with conditional=True or a free p / tau")
         self._stars_host = np.ascontiguousarray(stars).copy()
         self._slots = slots
         e0 = slots[0][0]
@@ -115,21 +121,60 @@ class SampleBatches(object):
         self._norm_order, self._zmax = int(norm_order), float(zmax)
         self._ukw = dict(upstream_kwargs or {})
         n = self.group * self.S
-        stars_d = e0.stars_to_device(stars)
-        self._base_plan = plan if plan is not None else e0.plan_data(t_dev, flux_dev, stars_d, diag=diag_dev,
-                                                                      covpts=self._covpts, temporal=temporal)
-        self._plan = e0.replicate_plan(self._base_plan, self.group)
-        self._stars = e0.stars_to_device(stars_for_samples(stars, self.group, self._ntab))
+        if self._planned:
+            stars_d = e0.stars_to_device(stars)
+            self._base_plan = plan if plan is not None else e0.plan_data(t_dev, flux_dev, stars_d, diag=diag_dev,
+                                                                          covpts=self._covpts, temporal=temporal)
+            self._plan = e0.replicate_plan(self._base_plan, self.group)
+        else:
+            # the data of the group's systems, sample-major like the stars: S stars, ``group`` times
+            self._t = t_dev.repeat(self.group, 1).contiguous()
+            self._flux = flux_dev.repeat(self.group, 1, 1).contiguous()
+            self._diag = None if diag_dev is None else diag_dev.repeat(self.group, 1).contiguous()
+            self._select = torch.arange(self.group, dtype=torch.int32, device=e0.device).repeat_interleave(
+                self.S).contiguous()
+        self._stars = e0.stars_to_device(self._group_stars())
         self._buf = []
         for e, _ in slots:
-            self._buf.append(dict(ws=e.workspace(n, self.K, self.M), ez=e.empty(self.group, e.N),
-                                  Ez=e.empty(self.group, e.N, e.N),
-                                  tab=e.empty(self.group * self._ntab, 5, self._covpts + 4),
-                                  mv=e.empty(self.group * self._ntab, 2)))
+            b = dict(ws=e.workspace(n, self.K, self.M))
+            if self._conditional:
+                b.update(mu=e.empty(self.group, e.N), cov=e.empty(self.group, e.N, e.N))
+            else:
+                b.update(ez=e.empty(self.group, e.N), Ez=e.empty(self.group, e.N, e.N),
+                         tab=e.empty(self.group * self._ntab, 5, self._covpts + 4),
+                         mv=e.empty(self.group * self._ntab, 2))
+            self._buf.append(b)
             if self._free:          # (one star array per stream slot, rewritten by every group of the slot)
-                self._buf[-1]["stars"] = e.stars_to_device(stars_for_samples(stars, self.group, self._ntab))
+                self._buf[-1]["stars"] = e.stars_to_device(self._group_stars())
             e.set_size_basis(**self._ukw)
         torch.cuda.synchronize(e0.device)
+
+    @classmethod
+    def column_names(cls, dr=None, free=(), conditional=False, temporal=None):
+        """(columns, free in column order) of the samples for these settings; ValueError for settings that name no batch
+        (needs no device)."""
+        free = (free,) if isinstance(free, str) else tuple(free)
+        if len(set(free)) != len(free) or any(f not in cls.FREE for f in free):
+            raise ValueError("free must be a subset of %r" % (cls.FREE,))
+        if isinstance(dr, str):
+            if dr != "free":
+                raise ValueError("dr must be None, a number or 'free'")
+        elif dr is not None:
+            from .ops import CheckBoundsOp
+
+            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(float(dr) * (np.pi / 180))
+        if "i" in free and not conditional:
+            raise ValueError("a free inclination needs conditional=True: the marginal branch integrates over it")
+        if "tau" in free and temporal is None:
+            raise ValueError("a free tau needs a temporal kernel")
+        free = tuple(f for f in cls.FREE if f in free)
+        return ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(cls._NAMES[f] for f in free), free
+
+    def _group_stars(self, **fields):
+        """The star array of one group; in the conditional branch ``table`` stays the star's flux operator."""
+        from .engine import stars_for_samples
+
+        return stars_for_samples(self._stars_host, self.group, self._ntab, own_tables=not self._conditional, **fields)
 
     def __call__(self, samples, out=None):
         """samples (ns, len(self.columns)) -> device tensor (ns, S); nothing is synchronised: the caller does, once."""
@@ -144,19 +189,18 @@ class SampleBatches(object):
         raw = e0.empty(ngroups, g * S)
         if ns < ngroups * g:          # (the last group is filled up with its own last sample; those values are dropped)
             samples = np.vstack([samples, np.repeat(samples[-1:], ngroups * g - ns, axis=0)])
-        new = self._dr is not None or bool(self._free)
+        new = self._dr is not None or bool(self._free) or not self._planned
         if new:
-            from .engine import stars_for_samples
-
             c0 = 2 if self._dr == "free" else 1
             drv = samples[:, 1] if self._dr == "free" else self._dr
             hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
             col = c0 + 4
-            bm = bv = None
-            if "baseline_mean" in self._free:
-                bm, col = samples[:, col], col + 1
-            if "baseline_log_var" in self._free:
-                bv = 10.0 ** samples[:, col]
+            cols = {}
+            for f, key in (("baseline_mean", "baseline_mean"), ("baseline_log_var", "baseline_var"), ("i", "inc_deg"),
+                           ("p", "period"), ("tau", "tau")):
+                if f in self._free:
+                    cols[key] = 10.0 ** samples[:, col] if f == "baseline_log_var" else samples[:, col]
+                    col += 1
         cur = torch.cuda.current_stream(e0.device)
         start = torch.cuda.Event()
         start.record(cur)
@@ -184,18 +228,30 @@ class SampleBatches(object):
                     e.polar_moments_samples(samples[gi * g:(gi + 1) * g], ez=b["ez"], Ez=b["Ez"], **self._ukw)
                 else:
                     sl = slice(gi * g, (gi + 1) * g)
-                    e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"],
-                                            dr=drv[sl] if self._dr == "free" else drv, **self._ukw)
+                    drs = drv[sl] if self._dr == "free" else drv
+                    if self._conditional:
+                        e.ylm_moments_samples(hyper[sl], mean=b["mu"], cov=b["cov"], dr=drs, **self._ukw)
+                    else:
+                        e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"], dr=drs, **self._ukw)
                     if self._free:
-                        stars_d = e.stars_staged(stars_for_samples(
-                            self._stars_host, g, self._ntab, baseline_mean=None if bm is None else bm[sl],
-                            baseline_var=None if bv is None else bv[sl]), b["stars"])
-                e.kernel_table_samples(b["ez"], b["Ez"], self._rta1, self._covpts, tab=b["tab"], meanvar=b["mv"])
+                        stars_d = e.stars_staged(self._group_stars(**{k: v[sl] for k, v in cols.items()}), b["stars"])
+                if not self._conditional:
+                    e.kernel_table_samples(b["ez"], b["Ez"], self._rta1, self._covpts, tab=b["tab"], meanvar=b["mv"])
                 if gi + 1 < min(ngroups, len(self._slots)):
                     stagger = torch.cuda.Event()
                     stagger.record(stream)
-                e.lnlike_ensemble_planned(self._plan, None, None, stars_d, b["tab"], b["mv"],
-                                          norm_order=self._norm_order, zmax=self._zmax, out=raw[gi], workspace=b["ws"])
+                if self._conditional:
+                    e.lnlike_ensemble_sets(self._t, self._flux, stars_d, self._rta1, b["mu"], b["cov"], self._select,
+                                           diag=self._diag, temporal=self._temporal, normalized=self._normalized,
+                                           norm_order=self._norm_order, zmax=self._zmax, out=raw[gi], workspace=b["ws"])
+                elif not self._planned:
+                    e.lnlike_ensemble(self._t, self._flux, stars_d, diag=self._diag, covpts=self._covpts, tab=b["tab"],
+                                      meanvar=b["mv"], temporal=self._temporal, norm_order=self._norm_order,
+                                      zmax=self._zmax, out=raw[gi], workspace=b["ws"])
+                else:
+                    e.lnlike_ensemble_planned(self._plan, None, None, stars_d, b["tab"], b["mv"],
+                                              norm_order=self._norm_order, zmax=self._zmax, out=raw[gi],
+                                              workspace=b["ws"])
                 if ngroups > QUEUED * len(self._slots):
                     ev = torch.cuda.Event()
                     ev.record(stream)

@@ -40,7 +40,7 @@ namespace {
 __global__ __launch_bounds__(256) void gemm_nt_kernel(
     const double *A, long lda, long strideA, const double *__restrict__ B, long ldb, long strideB,
     double *C, long ldc, long strideC, int Mrows, int Nrows, int Kd, double alpha, int beta,
-    int lower_only, int batch, int ntn, int ntiles) {
+    int lower_only, int batch, int ntn, int ntiles, const int32_t *__restrict__ bsel, int nsel) {
   constexpr int BK = 32, LDW = BK + 1;
   __shared__ __attribute__((aligned(16))) double smem[2 * GT * LDW];
   double *sA = smem, *sB = smem + GT * LDW;
@@ -58,7 +58,13 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(
   }
   const int row0 = ti * GT, col0 = tj * GT;
   const double *Ab = A + (size_t)mtx * strideA;
-  const double *Bb = B + (size_t)mtx * strideB;
+  // (bsel: matrix mtx takes the second operand bsel[mtx] of nsel -- an index outside them reads operand 0)
+  int bm = mtx;
+  if (bsel) {
+    bm = bsel[mtx];
+    if (bm < 0 || bm >= nsel) bm = 0;
+  }
+  const double *Bb = B + (size_t)bm * strideB;
   double *Cb = C + (size_t)mtx * strideC;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int fr = lane & 15, fk = lane >> 4;
@@ -128,11 +134,15 @@ __device__ long long sp_mm_dbg[8 * 4096];
 #ifndef SP_MM_SYRK_NS
 #define SP_MM_SYRK_NS 6
 #endif
-template <class Core, bool SGN>
+// SEL: the second operand of matrix mtx is B + bsel[mtx] strideB, one of nsel (the conditional covariance with a
+// moment set per system, sp_lnlike_ensemble_sets) -- only the operand's base address differs: staging, loop and
+// stores are those of the shared-operand product, so a tile's bits are those of a launch that was given that operand.
+template <class Core, bool SGN, bool SEL = false>
 __global__ __launch_bounds__(256, SP_MM_WAVES) void mm_nt_kernel(
     const double *__restrict__ A, long lda, long strideA, const double *__restrict__ B, long ldb,
     long strideB, double *__restrict__ C, long ldc, long strideC, int Kd, double alpha, int beta,
-    int lower_only, int batch, int ntn, int ntiles, int skip00, LazyCov lz, DiagFuse df) {
+    int lower_only, int batch, int ntn, int ntiles, int skip00, LazyCov lz, DiagFuse df,
+    const int32_t *__restrict__ bsel, int nsel) {
   constexpr int TM = Core::TM_, TN = Core::TN_;
   static_assert(Core::LDS_DOUBLES >= SP_DIAG_LDS_DOUBLES, "the tile-(0,0) workgroup factors a pivot block in this LDS");
   __shared__ __attribute__((aligned(16))) double lds[Core::LDS_DOUBLES];
@@ -176,7 +186,12 @@ __global__ __launch_bounds__(256, SP_MM_WAVES) void mm_nt_kernel(
     return;
   }
   const double *Ab = A + (size_t)mtx * strideA + (size_t)ti * TM * lda;
-  const double *Bb = B + (size_t)mtx * strideB + (size_t)tj * TN * ldb;
+  int bm = mtx;
+  if constexpr (SEL) {
+    bm = bsel[mtx];
+    if (bm < 0 || bm >= nsel) bm = 0;     // (never an address outside the operands)
+  }
+  const double *Bb = B + (size_t)bm * strideB + (size_t)tj * TN * ldb;
   double *Cb = C + (size_t)mtx * strideC + (size_t)ti * TM * ldc + (size_t)tj * TN;
   Core mm;
   mm.init(Ab, lda, Bb, ldb);
@@ -402,21 +417,26 @@ template <class Core>
 int mm_launch(const double *A, long lda, long strideA, const double *B, long ldb, long strideB,
               double *C, long ldc, long strideC, int Mrows, int Nrows, int Kd, double alpha, int beta,
               int lower_only, int batch, hipStream_t st, int skip00, const LazyCov *lazy = nullptr,
-              const DiagFuse *dfp = nullptr) {
+              const DiagFuse *dfp = nullptr, const int32_t *bsel = nullptr, int nsel = 0) {
   const LazyCov lz = lazy ? *lazy : LazyCov{};
   const DiagFuse df = dfp ? *dfp : DiagFuse{nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, -1, 0};
   const int ntm = Mrows / Core::TM_, ntn = Nrows / Core::TN_;
   const int ntiles = lower_only ? ntm * (ntm + 1) / 2 : ntm * ntn;
   const long nblk = sp_xcd_grid(batch, ntiles);
   if (nblk > 0x7fffffffL) return SP_ERR_INVALID;
-  if (alpha == 1.0 || alpha == -1.0)
+  if (bsel) {
+    if (alpha != 1.0 || lazy || dfp) return SP_ERR_INVALID;     // (a plain product only)
+    hipLaunchKernelGGL((mm_nt_kernel<Core, true, true>), dim3((unsigned)nblk), dim3(256), 0, st,
+                       A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Kd, alpha, beta, lower_only,
+                       batch, ntn, ntiles, skip00, lz, df, bsel, nsel);
+  } else if (alpha == 1.0 || alpha == -1.0)
     hipLaunchKernelGGL((mm_nt_kernel<Core, true>), dim3((unsigned)nblk), dim3(256), 0, st,
                        A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Kd, alpha, beta, lower_only,
-                       batch, ntn, ntiles, skip00, lz, df);
+                       batch, ntn, ntiles, skip00, lz, df, (const int32_t *)nullptr, 0);
   else
     hipLaunchKernelGGL((mm_nt_kernel<Core, false>), dim3((unsigned)nblk), dim3(256), 0, st,
                        A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Kd, alpha, beta, lower_only,
-                       batch, ntn, ntiles, skip00, lz, df);
+                       batch, ntn, ntiles, skip00, lz, df, (const int32_t *)nullptr, 0);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -431,7 +451,8 @@ extern "C" int sp_debug_mm_stamps(long long *out, int n) {
 static int launch_gemm(const double *A, long lda, long strideA, const double *B, long ldb,
                        long strideB, double *C, long ldc, long strideC, int Mrows, int Nrows,
                        int Kd, double alpha, int beta, int lower_only, int batch, hipStream_t st,
-                       int skip00 = 0, const LazyCov *lazy = nullptr) {
+                       int skip00 = 0, const LazyCov *lazy = nullptr, const int32_t *bsel = nullptr, int nsel = 0) {
+  if (bsel && (nsel < 1 || skip00 || (lazy && lazy->theta))) return SP_ERR_INVALID;
   if (Mrows <= 0 || Nrows <= 0 || batch <= 0) return SP_OK;
   if (Kd < 0) return SP_ERR_INVALID;
   const int ntm = (Mrows + GT - 1) / GT, ntn = (Nrows + GT - 1) / GT;
@@ -454,28 +475,29 @@ static int launch_gemm(const double *A, long lda, long strideA, const double *B,
 #ifdef SP_MM_TILE_PROBE
     // (tools/attic/mm_tile_bench.py: the engine's tile shapes against each other on one full product)
     static const int probe = getenv("SP_MM_TILE") ? atoi(getenv("SP_MM_TILE")) : 0;
-    if (!lower_only && probe == 1 && (Mrows % 128) == 0)
+    if (!bsel && !lower_only && probe == 1 && (Mrows % 128) == 0)
       return mm_launch<MM2<128, 64, 8, 4, 4>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha,
                                               beta, lower_only, batch, st, skip00);
-    if (!lower_only && probe == 2 && (Mrows % 128) == 0)
+    if (!bsel && !lower_only && probe == 2 && (Mrows % 128) == 0)
       return mm_launch<MM2<128, 64, 8, 5, 4>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha,
                                               beta, lower_only, batch, st, skip00);
-    if (!lower_only && probe == 3 && (Mrows % 128) == 0)
+    if (!bsel && !lower_only && probe == 3 && (Mrows % 128) == 0)
       return mm_launch<MM2<128, 64, 16, 3, 4>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha,
                                                beta, lower_only, batch, st, skip00);
-    if (!lower_only && probe == 4)
+    if (!bsel && !lower_only && probe == 4)
       return mm_launch<MM2<64, 64, 8, 6, 4>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha,
                                              beta, lower_only, batch, st, skip00);
 #endif
     if (!lower_only && (Mrows % 128) == 0 && (Nrows % 128) == 0)
       return mm_launch<MM2<128, 128, 8, 4, 2>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows,
-                                               Nrows, Kd, alpha, beta, lower_only, batch, st, skip00);
+                                               Nrows, Kd, alpha, beta, lower_only, batch, st, skip00, nullptr, nullptr,
+                                               bsel, nsel);
     return mm_launch<MM2<64, 64, 8, 6, 4>>(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows,
-                                           Kd, alpha, beta, lower_only, batch, st, skip00);
+                                           Kd, alpha, beta, lower_only, batch, st, skip00, nullptr, nullptr, bsel, nsel);
   }
   if (skip00) return SP_ERR_INVALID;   // (only the pipelined kernel leaves tiles out)
   hipLaunchKernelGGL(gemm_nt_kernel, dim3((unsigned)nblk), dim3(256), 0, st, A, lda, strideA, B, ldb,
-                     strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha, beta, lower_only, batch, ntn, ntiles);
+                     strideB, C, ldc, strideC, Mrows, Nrows, Kd, alpha, beta, lower_only, batch, ntn, ntiles, bsel, nsel);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -544,7 +566,7 @@ int sp_launch_syrk_diag(const double *X, long ld, long stride, double *T, int n,
 int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B, long ldb,
                       long strideB, double *C, long ldc, long strideC, int Mrows, int Nrows,
                       int Kd, double alpha, int beta, int lower_only, int batch,
-                      hipStream_t st, int skip_tile00, const LazyCov *lazy) {
+                      hipStream_t st, int skip_tile00, const LazyCov *lazy, const int32_t *bsel, int nsel) {
   return launch_gemm(A, lda, strideA, B, ldb, strideB, C, ldc, strideC, Mrows, Nrows, Kd,
-                     alpha, beta, lower_only, batch, st, skip_tile00, lazy);
+                     alpha, beta, lower_only, batch, st, skip_tile00, lazy, bsel, nsel);
 }

@@ -423,11 +423,14 @@ int sp_launch_chol_rev_finish(const double *S, const double *L, long ldl, long s
                               int K, int batch, hipStream_t st);
 // sp_gemm.hip: C[b] (+)= alpha * A[b] . B[b]^T  on the matrix cores: A: Mrows x Kd (lda), B: Nrows x Kd
 // (ldb), C: Mrows x Nrows (ldc); beta is 0 or 1; lower_only: only tiles with tile_i >= tile_j.
+// bsel [batch] (device, or null): matrix b takes the second operand B + bsel[b] strideB, one of nsel (an index outside
+// them reads operand 0) -- alpha = 1, nothing skipped or formed at first touch; the bits are those of the product with
+// that operand alone.
 int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B,
                       long ldb, long strideB, double *C, long ldc, long strideC,
                       int Mrows, int Nrows, int Kd, double alpha, int beta,
                       int lower_only, int batch, hipStream_t st, int skip_tile00 = 0,
-                      const LazyCov *lazy = nullptr);
+                      const LazyCov *lazy = nullptr, const int32_t *bsel = nullptr, int nsel = 0);
 
 // round-3 panel kernel (sp_panel.hip)
 struct DiagFuse;
@@ -455,7 +458,9 @@ Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool 
 // mean[s] = (A_s mu_y)[0] from matrices of `rows` rows per star
 int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars, const double *rta1, double *A_out,
                      hipStream_t st, int Kr);
-int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st);
+// (sel [S] (device, or null): star s takes mu + sel[s] N, one of nsets; an index outside them gives NaN)
+int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
+                        const int32_t *sel = nullptr, int nsets = 0);
 
 // sp_linalg.hip: C^-1 (and log det C) of the matrices already in the top-left K x K corners of the systems of `ws`
 int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,

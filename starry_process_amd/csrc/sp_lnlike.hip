@@ -178,14 +178,23 @@ __global__ __launch_bounds__(256) void cond_design_kernel(
   }
 }
 
-// mean[s] = (A mu_y)[0]   (flux.py:340)
+// mean[s] = (A mu_y)[0]   (flux.py:340); sel: with the mean vector sel[s] of nsets (NaN for an index outside them)
 __global__ __launch_bounds__(256) void cond_mean_kernel(int N, int K /* rows per star in A */,
                                                         const double *__restrict__ A,
                                                         const double *__restrict__ mu,
-                                                        double *__restrict__ mean) {
+                                                        double *__restrict__ mean,
+                                                        const int32_t *__restrict__ sel, int nsets) {
   __shared__ double red[4];
   const int s = blockIdx.x;
   const double *row = A + (size_t)s * K * N;
+  if (sel) {
+    const int b = sel[s];
+    if (b < 0 || b >= nsets) {
+      if (threadIdx.x == 0) mean[s] = __builtin_nan("");
+      return;
+    }
+    mu += (size_t)b * N;
+  }
   double part = 0.0;
   for (int n = threadIdx.x; n < N; n += 256) part += row[n] * mu[n];
   for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
@@ -237,17 +246,25 @@ int build_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars,
   return SP_OK;
 }
 
+// The moments of the conditional branch: the handle's one pair (sel == null), or nsets pairs mu [nsets][N], cov
+// [nsets][N][N] of which system s takes sel[s] (sp_lnlike_ensemble_sets) -- the product A_s Sigma then picks its
+// second operand per system inside the kernel (sp_gemm.hip), one launch either way.
+struct CondSets {
+  const double *mu, *cov;
+  const int32_t *sel;
+  int nsets;
+};
+
 // raw (un-normalised, no temporal factor) conditional covariance into L.raw
-int build_conditional_raw(sp_handle *h, const Layout &L, void *ws, hipStream_t st) {
+int build_conditional_raw(const CondSets &cs, const Layout &L, void *ws, hipStream_t st) {
   const int S = L.S, K = L.K, N = L.N;
   double *A = at<double>(ws, L.A), *B1 = at<double>(ws, L.B1);
   double *raw = at<double>(ws, L.raw), *cm = at<double>(ws, L.condmean);
-  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, K, A,
-                     h->d_mean_ylm, cm);
+  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, K, A, cs.mu, cm, cs.sel, cs.nsets);
   SP_LAUNCH_CHECK();
   // B1 = A Sigma_y  (Sigma_y symmetric: A . Sigma_y^T), then raw = B1 A^T
-  int rc = sp_launch_gemm_nt(A, N, (long)K * N, h->d_cov_ylm, N, 0, B1, N,
-                             (long)K * N, K, N, N, 1.0, 0, 0, S, st);
+  int rc = sp_launch_gemm_nt(A, N, (long)K * N, cs.cov, N, cs.sel ? (long)N * N : 0, B1, N,
+                             (long)K * N, K, N, N, 1.0, 0, 0, S, st, 0, nullptr, cs.sel, cs.nsets);
   if (rc) return rc;
   return sp_launch_gemm_nt(B1, N, (long)K * N, A, N, (long)K * N, raw, K,
                            (long)K * K, K, K, N, 1.0, 0, 0, S, st);
@@ -258,8 +275,10 @@ int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const
                     const double *flux_dev, const double *diag_dev, const sp_star *stars_dev,
                     int conditional, int covpts, const double *tab_dev,
                     const double *meanvar_dev, const double *rta1_dev, int temporal,
-                    int normalized, int norm_order, double zmax, hipStream_t st, int lazy_nfull = 0) {
+                    int normalized, int norm_order, double zmax, hipStream_t st, int lazy_nfull = 0,
+                    const CondSets *sets = nullptr) {
   const int S = L.S;
+  const CondSets cs = sets ? *sets : CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1};
   double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
   double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
   double *raw = at<double>(ws, L.raw), *cm = at<double>(ws, L.condmean);
@@ -282,10 +301,10 @@ int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const
     const int N = L.N, Kr = L.Kr;
     double *A = at<double>(ws, L.A), *B1 = at<double>(ws, L.B1);
     if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, A, st, Kr))) return rc;
-    hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, Kr, A, h->d_mean_ylm, cm);
+    hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, Kr, A, cs.mu, cm, cs.sel, cs.nsets);
     SP_LAUNCH_CHECK();
-    if ((rc = sp_launch_gemm_nt(A, N, (long)Kr * N, h->d_cov_ylm, N, 0, B1, N, (long)Kr * N, Kr, N, N, 1.0,
-                                0, 0, S, st)))
+    if ((rc = sp_launch_gemm_nt(A, N, (long)Kr * N, cs.cov, N, cs.sel ? (long)N * N : 0, B1, N, (long)Kr * N, Kr, N, N,
+                                1.0, 0, 0, S, st, 0, nullptr, cs.sel, cs.nsets)))
       return rc;
     if (normalized) {
       double *part = at<double>(ws, L.part);
@@ -304,7 +323,7 @@ int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const
   if (conditional) {
     if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, at<double>(ws, L.A), st, K)))
       return rc;
-    if ((rc = build_conditional_raw(h, L, ws, st))) return rc;
+    if ((rc = build_conditional_raw(cs, L, ws, st))) return rc;
     rawp = raw;
     condmean = cm;
   }
@@ -359,8 +378,9 @@ int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *sta
                      hipStream_t st, int Kr) {
   return build_design(h, L, ws, stars, rta1, A_out, st, Kr);
 }
-int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st) {
-  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, rows, A, mu, mean);
+int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
+                        const int32_t *sel, int nsets) {
+  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, rows, A, mu, mean, sel, nsets);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -453,7 +473,7 @@ int sp_cov_conditional_batched(sp_handle *h, int S, int K, const double *t_dev,
   if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
   if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, at<double>(ws, L.A), st, K)))
     return rc;
-  if ((rc = build_conditional_raw(h, L, ws, st))) return rc;
+  if ((rc = build_conditional_raw(CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1}, L, ws, st))) return rc;
   if (normalized)
     if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, 1, nullptr, nullptr,
                                nullptr, temporal, raw, rowsum, st)))
@@ -483,20 +503,26 @@ long sp_lnlike_workspace_bytes(sp_handle *h, int S, int K, int M) {
   return (long)make_layout(h, S, K, M, true).total;
 }
 
-int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
-                       const double *flux_dev, const double *diag_dev,
-                       const sp_star *stars_dev, int conditional, int covpts,
-                       const double *tab_dev, const double *meanvar_dev,
-                       const double *rta1_dev, int temporal, int normalized,
-                       int norm_order, double zmax, void *workspace_dev,
-                       double *lnlike_dev, uint32_t *status_dev, void *stream) {
+// sets != null: the conditional branch with a moment set per system (sp_lnlike_ensemble_sets); the handle's own
+// moments are then neither needed nor read
+static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const double *t_dev,
+                                  const double *flux_dev, const double *diag_dev,
+                                  const sp_star *stars_dev, int conditional, int covpts,
+                                  const double *tab_dev, const double *meanvar_dev,
+                                  const double *rta1_dev, int temporal, int normalized,
+                                  int norm_order, double zmax, void *workspace_dev,
+                                  double *lnlike_dev, uint32_t *status_dev, void *stream, const CondSets *sets) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !workspace_dev || !lnlike_dev ||
       S < 0 || K < 1 || M < 1 || norm_order < 0 || norm_order > SP_NORM_MAXORDER)
     return SP_ERR_INVALID;
   if (conditional) {
     if (!rta1_dev) return SP_ERR_INVALID;
-    if (!h->have_moments) return SP_ERR_STATE;
+    if (sets) {
+      if (!sets->mu || !sets->cov || !sets->sel || sets->nsets < 1) return SP_ERR_INVALID;
+    } else if (!h->have_moments) {
+      return SP_ERR_STATE;
+    }
   } else {
     if (!tab_dev || !meanvar_dev || covpts < 1) return SP_ERR_INVALID;
     if (h->xp_covpts != covpts) return SP_ERR_STATE;
@@ -560,11 +586,13 @@ int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
   }
   for (int g = 0; g < G; ++g) {
     const int s0 = first[g];
+    CondSets gs{};
+    if (sets) gs = CondSets{sets->mu, sets->cov, sets->sel + s0, sets->nsets};
     int rc = lnlike_assemble(h, LG[g], ws, K, M, t_dev + (size_t)s0 * K,
                              flux_dev + (size_t)s0 * M * K,
                              diag_dev ? diag_dev + (size_t)s0 * K : nullptr, stars_dev + s0,
                              conditional, covpts, tab_dev, meanvar_dev, rta1_dev, temporal,
-                             normalized, norm_order, zmax, CG[g].st, lazy_nfull);
+                             normalized, norm_order, zmax, CG[g].st, lazy_nfull, sets ? &gs : nullptr);
     if (rc) return rc;
   }
   {
@@ -584,6 +612,38 @@ int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
     }
   }
   return SP_OK;
+}
+
+int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
+                       const double *flux_dev, const double *diag_dev,
+                       const sp_star *stars_dev, int conditional, int covpts,
+                       const double *tab_dev, const double *meanvar_dev,
+                       const double *rta1_dev, int temporal, int normalized,
+                       int norm_order, double zmax, void *workspace_dev,
+                       double *lnlike_dev, uint32_t *status_dev, void *stream) {
+  return lnlike_ensemble_driver(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, conditional, covpts, tab_dev,
+                                meanvar_dev, rta1_dev, temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev,
+                                status_dev, stream, nullptr);
+}
+
+// sp_lnlike_ensemble's conditional branch with one moment set per system: system s takes (mean_ylm[select[s]],
+// cov_ylm[select[s]]) of the B sets -- the same launches, the operand of B1 = A_s Sigma and of (A_s mu)[0] chosen per
+// system inside the kernels.  The workspace is sp_lnlike_ensemble's.
+long sp_lnlike_ensemble_sets_workspace_bytes(sp_handle *h, int S, int K, int M) {
+  return sp_lnlike_workspace_bytes(h, S, K, M);
+}
+
+int sp_lnlike_ensemble_sets(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
+                            const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, int B,
+                            const double *mean_ylm_dev, const double *cov_ylm_dev, const int32_t *select_dev,
+                            int temporal, int normalized, int norm_order, double zmax, void *workspace_dev,
+                            double *lnlike_dev, uint32_t *status_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !mean_ylm_dev || !cov_ylm_dev || !select_dev || B < 1) return SP_ERR_INVALID;
+  const CondSets sets{mean_ylm_dev, cov_ylm_dev, select_dev, B};
+  return lnlike_ensemble_driver(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, 1, 1, nullptr, nullptr, rta1_dev,
+                                temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev, status_dev, stream,
+                                &sets);
 }
 
 // The per-sample call on planned data (sp_plan.hip): sp_lnlike_ensemble's marginal, normalised branch with the

@@ -376,13 +376,15 @@ __global__ __launch_bounds__(256) void sm_first_kernel(int N, int P, const int32
 // Ez[b] = Proj(M[b]) + (n - 1) e1 e1^T + diag(eps), ez[b] = sqrt(n) e1.  grid (ceil(N^2 / 256), B)
 // SPREAD: M was formed from rows with unit coefficients; entry ((l, m), (l', m')) of its projection takes the factor
 // Etilde[l][l'] (the projection mixes entries of one (l, l') block only, so the factor commutes with it).
+// central != 0 (sp_ylm_moments_samples): the polar-frame COVARIANCE Proj(M[b]) - e1 e1^T + diag(eps) instead of the
+// second moment -- formed here, not as Ez - ez ez^T afterwards, which would cancel n e1 e1^T against itself.
 template <bool SPREAD>
 __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__restrict__ m_of,
                                                         const int32_t *__restrict__ mirror, const double *__restrict__ M,
                                                         const double *__restrict__ e1, const double *__restrict__ scal,
                                                         double epsy, double epsy15, double *__restrict__ ez,
                                                         double *__restrict__ Ez, int nl, const int32_t *__restrict__ l_of,
-                                                        const double *__restrict__ Et) {
+                                                        const double *__restrict__ Et, int central) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   const int b = blockIdx.y;
   if (e >= (long)N * N) return;
@@ -398,7 +400,7 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__
     if (SPREAD) v *= Et[(size_t)b * nl * nl + l_of[i] * nl + l_of[j]];
   }
   const int lo = i < j ? i : j, hi = i < j ? j : i;
-  v += (scal[4 * b + 2] - 1.0) * (eb[lo] * eb[hi]);
+  v += (central ? -1.0 : scal[4 * b + 2] - 1.0) * (eb[lo] * eb[hi]);
   if (i == j) v += i >= 15 * 15 ? epsy15 : epsy;
   Ez[(size_t)b * N * N + e] = v;
   if (j == 0) ez[(size_t)b * N + i] = scal[4 * b + 1] * eb[i];
@@ -427,10 +429,15 @@ int sp_set_size_basis(sp_handle *h, const double *theta_host, const double *Bp_h
   return SP_OK;
 }
 
-int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15,
-                             double *ez_dev, double *Ez_dev, void *stream) {
+}  // extern "C"
+
+// The two entry points' bodies.  central: the polar-frame covariance instead of the second moment (sm_finish_kernel);
+// extra > 0: that many more bytes of the handle's scratch behind the call's own, handed back in *extra_ptr -- ez_dev and
+// Ez_dev may then be null and are placed there: ez [B][N] | Ez [B][N][N] | one more [B][N][N] (sp_ylm_moments_samples).
+static int polar_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15, double *ez_dev,
+                         double *Ez_dev, void *stream, int central, size_t extra, void **extra_ptr) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !samples_host || !ez_dev || !Ez_dev || B < 0 || B > 65535) return SP_ERR_INVALID;
+  if (!h || !samples_host || (!extra && (!ez_dev || !Ez_dev)) || B < 0 || B > 65535) return SP_ERR_INVALID;
   if (!h->d_size_basis) return SP_ERR_STATE;
   if (B == 0) return SP_OK;
   const int N = h->N, nl = h->ydeg + 1, nq = h->ydeg + 2, P = 2 * nq, spts = h->size_spts;
@@ -449,9 +456,15 @@ int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, do
   SpCarve c;
   const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
                oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N);
+  const size_t oX = c.take(extra);
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
+  if (extra) {
+    *extra_ptr = at<void>(ws, oX);
+    ez_dev = at<double>(ws, oX);
+    Ez_dev = ez_dev + sp_align_up(d * B * N) / d;
+  }
   double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
          *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE);
   const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);      // (+ 256 ints of flags)
@@ -481,15 +494,17 @@ int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, do
     return rc;
   hipLaunchKernelGGL(sm_finish_kernel<false>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
                      h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, (const int32_t *)nullptr,
-                     (const double *)nullptr);
+                     (const double *)nullptr, central);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
 
-int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
-                                    double epsy15, double *ez_dev, double *Ez_dev, void *stream) {
+static int polar_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
+                                double epsy15, double *ez_dev, double *Ez_dev, void *stream, int central, size_t extra,
+                                void **extra_ptr) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !samples_host || !ez_dev || !Ez_dev || B < 0 || B > 65535 || !(cutoff > 0.0)) return SP_ERR_INVALID;
+  if (!h || !samples_host || (!extra && (!ez_dev || !Ez_dev)) || B < 0 || B > 65535 || !(cutoff > 0.0))
+    return SP_ERR_INVALID;
   if (!h->d_size_basis) return SP_ERR_STATE;
   if (B == 0) return SP_OK;
   const int N = h->N, nl = h->ydeg + 1, nq = h->ydeg + 2, P = 2 * nq, spts = h->size_spts;
@@ -513,9 +528,15 @@ int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_h
   const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
                oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N),
                oV = c.take(d * B * nl), oEt = c.take(d * B * nl * nl), oP = c.take(d * B * nblk * nl * nl);
+  const size_t oX = c.take(extra);
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, c.off, &ws);
   if (rc) return rc;
+  if (extra) {
+    *extra_ptr = at<void>(ws, oX);
+    ez_dev = at<double>(ws, oX);
+    Ez_dev = ez_dev + sp_align_up(d * B * N) / d;
+  }
   double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
          *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE), *evec = at<double>(ws, oV),
          *Et = at<double>(ws, oEt), *part = at<double>(ws, oP);
@@ -556,9 +577,49 @@ int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_h
                               0, B, st)))
     return rc;
   hipLaunchKernelGGL(sm_finish_kernel<true>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
-                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, h->d_l_of, Et);
+                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, h->d_l_of, Et, central);
   SP_LAUNCH_CHECK();
   return SP_OK;
+}
+
+extern "C" {
+
+int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15,
+                             double *ez_dev, double *Ez_dev, void *stream) {
+  return polar_samples(h, B, samples_host, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
+}
+
+int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
+                                    double epsy15, double *ez_dev, double *Ez_dev, void *stream) {
+  return polar_samples_spread(h, B, samples_host, cutoff, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
+}
+
+// The Ylm-frame moments of B samples: the polar-frame mean and COVARIANCE of the chain above (sm_finish_kernel,
+// central), rotated back with the library's block rotations -- ez = mu Rx(pi/2), Ep = Rx(pi/2)^T Sigma Rx(pi/2)
+// (flux.py:54-62), so mu = ez Rx(pi/2)^T and Sigma = Rx(pi/2) Ep Rx(pi/2)^T: three launches of dotrx_kernel against the
+// transposed blocks of the handle's packed Rx(pi/2) (rows of Ep, then its columns).  diag(eps) is constant within a
+// degree's block and so passes through the rotation.  samples_host: [B][5], or [B][6] with spread != 0.
+int sp_ylm_moments_samples(sp_handle *h, int B, const double *samples_host, int spread, double cutoff, double epsy,
+                           double epsy15, double *mean_ylm_dev, double *cov_ylm_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !samples_host || !mean_ylm_dev || !cov_ylm_dev || B < 0 || B > 65535) return SP_ERR_INVALID;
+  if (!h->d_size_basis) return SP_ERR_STATE;
+  if (B == 0) return SP_OK;
+  const int N = h->N;
+  const size_t d = sizeof(double), nv = sp_align_up(d * B * N) / d, nm = sp_align_up(d * B * N * N) / d;
+  void *xp = nullptr;
+  int rc = spread ? polar_samples_spread(h, B, samples_host, cutoff, epsy, epsy15, nullptr, nullptr, stream, 1,
+                                         d * (nv + 2 * nm), &xp)
+                  : polar_samples(h, B, samples_host, epsy, epsy15, nullptr, nullptr, stream, 1, d * (nv + 2 * nm), &xp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const double *ez = static_cast<const double *>(xp), *Ep = ez + nv;
+  double *X = static_cast<double *>(xp) + nv + nm;
+  // mu[b][i] = sum_j ez[b][j] R[i][j]
+  if ((rc = sp_launch_dotRx(h, ez, N, N, 1, 1, h->d_Rx90, 0, mean_ylm_dev, B, st, 1))) return rc;
+  // X[b][r][n] = sum_j Ep[b][r][j] R[n][j];  Sigma[b][n][m] = sum_i X[b][i][n] R[m][i]  (the columns of X as rows)
+  if ((rc = sp_launch_dotRx(h, Ep, (long)N * N, N, 1, N, h->d_Rx90, 0, X, B, st, 1))) return rc;
+  return sp_launch_dotRx(h, X, (long)N * N, 1, N, N, h->d_Rx90, 0, cov_ylm_dev, B, st, 1);
 }
 
 }  // extern "C"

@@ -38,21 +38,28 @@ def make_stars(S, period=1.0, inc_deg=60.0, tau=0.0, baseline_var=0.0,
     return st
 
 
-def stars_for_samples(stars, B, ntab, baseline_mean=None, baseline_var=None):
+def stars_for_samples(stars, B, ntab, baseline_mean=None, baseline_var=None, period=None, inc_deg=None, tau=None,
+                      own_tables=True):
     """The sp_star array of a batch of B hyperparameter samples x S stars (sample-major: system b S + s): the S stars
     repeated B times with table = b ntab + table_s, the kernel table of sample b for the star's flux operator
     (sp_kernel_table_samples' numbering).  ``baseline_mean`` / ``baseline_var`` [B]: the baseline terms of sample b
-    when they are free parameters of the samples (calibrate/log_prob.py:24-47), for every star of that sample."""
+    when they are free parameters of the samples (calibrate/log_prob.py:24-47), for every star of that sample; ``period``,
+    ``inc_deg`` (degrees, stored in radians like make_stars) and ``tau`` [B] likewise: the rotation period, inclination
+    and timescale of sample b.  ``own_tables=False``: every sample keeps the stars' table indices (the conditional
+    branch, where ``table`` selects the flux operator and there are no per-sample tables)."""
     stars = np.ascontiguousarray(stars)
     assert stars.dtype == STAR_DTYPE
     out = np.tile(stars, int(B))
-    out["table"] = (np.repeat(np.arange(int(B), dtype=np.int64), stars.shape[0]) * int(ntab) + out["table"]).astype(np.int32)
-    for field, val in (("baseline_mean", baseline_mean), ("baseline_var", baseline_var)):
+    if own_tables:
+        out["table"] = (np.repeat(np.arange(int(B), dtype=np.int64), stars.shape[0]) * int(ntab)
+                        + out["table"]).astype(np.int32)
+    for field, val in (("baseline_mean", baseline_mean), ("baseline_var", baseline_var), ("period", period),
+                       ("inc", inc_deg), ("tau", tau)):
         if val is not None:
             val = np.asarray(val, dtype=np.float64).reshape(-1)
             if val.shape[0] != int(B):
                 raise ValueError("%s must have one entry per sample" % field)
-            out[field] = np.repeat(val, stars.shape[0])
+            out[field] = np.repeat(val * (np.pi / 180) if field == "inc" else val, stars.shape[0])
     return out
 
 
@@ -446,6 +453,36 @@ class Engine(object):
             self._h, B, hptr(sm), float(kw.get("epsy", defaults["epsy"])), float(kw.get("epsy15", defaults["epsy15"])),
             self._p(ez), self._p(Ez), self._stream()))
         return ez, Ez
+
+    def ylm_moments_samples(self, samples, mean=None, cov=None, dr=None, **kw):
+        """samples [B, 5] = (r [degrees], a, b, c, n) -> (mean_ylm [B, N], cov_ylm [B, N, N]) device tensors: the
+        Ylm-frame moments of B hyperparameter samples in one library call (sp_ylm_moments_samples) -- what
+        ``upstream_device.ylm_moments_device`` computes one sample at a time, and what the conditional branch reads.
+        Bounds, ``dr`` and the keywords are polar_moments_samples'."""
+        from .defaults import defaults
+
+        if dr is not None:
+            sm5 = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+            if sm5.ndim != 2 or sm5.shape[1] != 5:
+                raise ValueError("samples must be (B, 5): r, a, b, c, n")
+            d = np.asarray(dr, dtype=np.float64)
+            if d.ndim > 1 or (d.ndim == 1 and d.shape[0] != sm5.shape[0]):
+                raise ValueError("dr must be a scalar or one value per sample")
+            sm = sample_parameters(np.insert(sm5, 1, np.broadcast_to(d, (sm5.shape[0],)), axis=1), dr=True, **kw)
+        else:
+            sm = sample_parameters(samples, **kw)
+        B = sm.shape[0]
+        self.set_size_basis(**kw)
+        if mean is None:
+            mean = self.empty(B, self.N)
+        if cov is None:
+            cov = self.empty(B, self.N, self.N)
+        assert tuple(mean.shape) == (B, self.N) and tuple(cov.shape) == (B, self.N, self.N)
+        check(self._L.sp_ylm_moments_samples(
+            self._h, B, hptr(sm), int(dr is not None), float(kw.get("cutoff", 1.5)),
+            float(kw.get("epsy", defaults["epsy"])), float(kw.get("epsy15", defaults["epsy15"])), self._p(mean),
+            self._p(cov), self._stream()))
+        return mean, cov
 
     def kernel_table_samples(self, ez, Ez, rta1, covpts, tab=None, meanvar=None):
         """ez [B, N], Ez [B, N, N], rta1 [ntab, N] (device) -> tab [B ntab, 5, covpts + 4], meanvar [B ntab, 2]: table
@@ -1010,6 +1047,39 @@ class Engine(object):
             int(bool(conditional)), int(covpts), self._p(tab), self._p(meanvar),
             self._p(rta1), TEMPORAL[temporal], int(bool(normalized)), int(norm_order),
             float(zmax), self._p(ws), self._p(out), self._p(status), self._stream()))
+        return out, status
+
+    def lnlike_ensemble_sets(self, t, flux, stars_dev, rta1, mean_ylm, cov_ylm, select, diag=None, temporal=None,
+                             normalized=True, norm_order=20, zmax=0.023, out=None, status=None, workspace=None):
+        """The conditional branch of lnlike_ensemble with one moment set per system (sp_lnlike_ensemble_sets): system
+        s is evaluated under (mean_ylm[select[s]], cov_ylm[select[s]]).  t [S, K], flux [S, M, K], stars_dev, rta1
+        [ntab, N], mean_ylm [B, N], cov_ylm [B, N, N] on the device; ``select`` [S]: a host array of indices (checked
+        here: ValueError outside [0, B)) or an int32 device tensor (taken as it is).  The engine's own moments are not
+        touched.  Returns (lnlike, status)."""
+        torch = _torch()
+        S, K = t.shape
+        M = flux.shape[1]
+        B = int(mean_ylm.shape[0])
+        if tuple(mean_ylm.shape) != (B, self.N) or tuple(cov_ylm.shape) != (B, self.N, self.N):
+            raise ValueError("mean_ylm must be (B, N) and cov_ylm (B, N, N)")
+        if not isinstance(select, torch.Tensor):
+            sel = np.ascontiguousarray(np.asarray(select).reshape(-1), dtype=np.int32)
+            if sel.shape[0] != S:
+                raise ValueError("select must hold one index per system")
+            if sel.size and (sel.min() < 0 or sel.max() >= B):
+                raise ValueError("select holds an index outside the %d moment sets" % B)
+            select = torch.from_numpy(sel).to(self.device)
+        elif select.dtype != torch.int32 or select.numel() != S or not select.is_contiguous() or not select.is_cuda:
+            raise ValueError("a device select must be a contiguous int32 tensor with one index per system")
+        ws = workspace if workspace is not None else self.workspace(S, K, M)
+        if out is None:
+            out = self.empty(S)
+        if status is None:
+            status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        check(self._L.sp_lnlike_ensemble_sets(
+            self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(rta1), B,
+            self._p(mean_ylm), self._p(cov_ylm), self._p(select), TEMPORAL[temporal], int(bool(normalized)),
+            int(norm_order), float(zmax), self._p(ws), self._p(out), self._p(status), self._stream()))
         return out, status
 
     def plan_data(self, t, flux, stars_dev, diag=None, covpts=300, temporal=None, workspace=None):

@@ -39,6 +39,46 @@ def _neg_inf_if_nan(x):
     return np.where(np.isnan(x), -np.inf, x)
 
 
+def sample_columns(params, marginalize_over_inclination, time_variable):
+    """``log_likelihood_samples``' column names checked for a process of these settings: (params, the same names in the
+    batch's order r[, dr], a, b, c, n[, m][, v][, i][, p][, tau], whether dr is a column, the free terms in that order).
+    ValueError for an unknown or repeated name, a missing hyperparameter, "i" on a process that marginalises over the
+    inclination, "tau" on one built without a temporal kernel."""
+    params = tuple(params)
+    allowed = ("r", "dr", "a", "b", "c", "n", "baseline_mean", "baseline_log_var", "i", "p", "tau")
+    if (len(set(params)) != len(params) or any(q not in allowed for q in params)
+            or any(q not in params for q in ("r", "a", "b", "c", "n"))):
+        raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var, "
+                         "i, p, tau")
+    if "i" in params and marginalize_over_inclination:
+        raise ValueError("params names i, but this process marginalises over the inclination")
+    if "tau" in params and not time_variable:
+        raise ValueError("params names tau, but this process was built without a temporal kernel (tau=None)")
+    dr_free = "dr" in params
+    free = tuple(q for q in ("baseline_mean", "baseline_log_var", "i", "p", "tau") if q in params)
+    order = ("r",) + (("dr",) if dr_free else ()) + ("a", "b", "c", "n") + free
+    return params, order, dr_free, free
+
+
+def ipt_in_bounds(samples, order, tol=1e-6):
+    """Boolean mask of the rows whose "i", "p", "tau" columns (those that ``order`` names) lie inside the reference's
+    bounds: i in [0, 90] degrees and p >= 0 through CheckBoundsOp's tolerance (flux.py:233-254), tau > 0, all finite."""
+    samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+    ok = np.ones(samples.shape[0], dtype=bool)
+    for q in ("i", "p", "tau"):
+        if q in order:
+            v = samples[:, order.index(q)]
+            with np.errstate(invalid="ignore"):
+                if q == "i":
+                    inside = (v * (np.pi / 180) >= -tol) & (v * (np.pi / 180) <= 0.5 * np.pi + tol)
+                elif q == "p":
+                    inside = v >= -tol
+                else:
+                    inside = v > 0.0
+            ok &= np.isfinite(v) & inside
+    return ok
+
+
 class StarryProcess(object):
     def __init__(
         self,
@@ -282,35 +322,35 @@ class StarryProcess(object):
         -> (ns,) values, each what ``StarryProcess(r=r, a=a, b=b, c=c, n=n, <same settings>,
         upstream="device").log_likelihood(...)`` returns.  What a sampler does with the reference one call at a time
         (sp.py:1052-1062 driven by calibrate/sample.py:95-107) is here ONE batched device step per 64 samples
-        (calibrate.SampleBatches) -- marginalised, normalised processes with scalar or per-cadence data variance;
-        anything else is evaluated sample by sample.  ``params`` names the columns of ``samples``: r, a, b, c, n and,
-        each at most once, "dr", "baseline_mean", "baseline_log_var" (log10 of the baseline variance); such a column
-        overrides the constructor's dr or the argument of the same name.  ``out_of_bounds="inf"``: samples outside the
-        reference's parameter bounds (a ValueError there and, by default, here) get -inf and are not evaluated."""
+        (calibrate.SampleBatches) -- marginalised, normalised processes and conditional ones (normalised or not), with
+        or without a temporal kernel, with scalar or per-cadence data variance and scalar baseline terms; anything else
+        is evaluated sample by sample.  ``params`` names the columns of ``samples``: r, a, b, c, n and, each at most
+        once, "dr", "baseline_mean", "baseline_log_var" (log10 of the baseline variance), "i" (inclination in degrees; a
+        process that does not marginalise over it), "p" (period) and "tau" (timescale; a process built with one): the
+        free parameters of the reference's log-probability (calibrate/log_prob.py:24-47, 93-103) and of its
+        time-variability tutorial.  Such a column overrides the constructor's value or the argument of the same name.
+        Bounds of the three: i in [0, 90], p >= 0 (flux.py:233-254), tau > 0.  ``out_of_bounds="inf"``: samples outside
+        the reference's parameter bounds (a ValueError there and, by default, here) get -inf and are not evaluated."""
         from .calibrate import MAX_STREAMS_SAMPLES, SampleBatches, clamp_depth
         from .engine import engine_slots
 
         f = self._flux
         t, i, p, u = f._ingest(t, i, p, u)
         K = t.shape[0]
-        params = tuple(params)
-        allowed = ("r", "dr", "a", "b", "c", "n", "baseline_mean", "baseline_log_var")
-        if (len(set(params)) != len(params) or any(q not in allowed for q in params)
-                or any(q not in params for q in ("r", "a", "b", "c", "n"))):
-            raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var")
+        params, order, dr_free, free = sample_columns(params, self._marginalize_over_inclination, self._time_variable)
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
         if samples.shape[1] != len(params):
             raise ValueError("samples must be (ns, %d): %s" % (len(params), ", ".join(params)))
-        # the columns in SampleBatches' order: r[, dr], a, b, c, n[, m][, v]
-        dr_free = "dr" in params
-        free = tuple(q for q in ("baseline_mean", "baseline_log_var") if q in params)
-        order = ("r",) + (("dr",) if dr_free else ()) + ("a", "b", "c", "n") + free
+        # the columns in SampleBatches' order: r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]
         samples = np.ascontiguousarray(samples[:, [params.index(q) for q in order]])
         nh = 6 if dr_free else 5
+        ok3 = ipt_in_bounds(samples, order)
+        if out_of_bounds == "raise" and not ok3.all():
+            raise ValueError("samples out of bounds: i in [0, 90] degrees, p >= 0, tau > 0")
         if out_of_bounds == "inf":
             from .engine import samples_in_bounds
 
-            ok = samples_in_bounds(samples[:, :nh], dr=dr_free) & np.all(np.isfinite(samples), axis=1)
+            ok = samples_in_bounds(samples[:, :nh], dr=dr_free) & np.all(np.isfinite(samples), axis=1) & ok3
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
@@ -328,7 +368,7 @@ class StarryProcess(object):
             bmean = np.float64(0.0)       # (a placeholder: the column overrides the argument)
         if "baseline_log_var" in free:
             bvar = np.float64(0.0)
-        batched = (self._marginalize_over_inclination and self._normalized and K >= 2
+        batched = ((self._normalized or not self._marginalize_over_inclination) and K >= 2
                    and data_cov.ndim <= 1 and bmean.ndim == 0 and bvar.ndim == 0)
         if not batched:
             kw = dict(self._kwargs)
@@ -343,13 +383,20 @@ class StarryProcess(object):
                 if "baseline_mean" in free:
                     bm, col = row[col], col + 1
                 if "baseline_log_var" in free:
-                    bv = 10.0 ** row[col]
+                    bv, col = 10.0 ** row[col], col + 1
+                ii, pp = i, p
+                if "i" in free:
+                    ii, col = row[col], col + 1
+                if "p" in free:
+                    pp, col = row[col], col + 1
+                if "tau" in free:
+                    kw["tau"] = row[col]
                 out.append(float(StarryProcess(r=r, dr=row[1] if dr_free else self._dr, a=a, b=b, c=c, n=n, **kw).log_likelihood(
-                    t, flux, data_cov, i=i, p=p, u=u, baseline_mean=bm, baseline_var=bv)))
+                    t, flux, data_cov, i=ii, p=pp, u=u, baseline_mean=bm, baseline_var=bv)))
             return Eager(np.array(out))
         dr = "free" if dr_free else (None if self._dr is None else float(self._dr))
-        key = (t.tobytes(), F.tobytes(), data_cov.tobytes(), float(p), tuple(np.asarray(u, dtype=float).reshape(-1)),
-               float(bmean), float(bvar), int(depth), dr, free)
+        key = (t.tobytes(), F.tobytes(), data_cov.tobytes(), float(p), float(i),
+               tuple(np.asarray(u, dtype=float).reshape(-1)), float(bmean), float(bvar), int(depth), dr, free)
         cache = self.__dict__.get("_sample_batches")
         if cache is None or cache[0] != key:
             # (the data set is planned once and kept: a sampler calls this with the same data every iteration)
@@ -361,6 +408,8 @@ class StarryProcess(object):
             ukw = {k: self._kwargs[k] for k in ("epsy", "epsy15", "spts", "eps4", "smoothing", "sfac", "cutoff", "abmin",
                                                 "log_alpha_max", "log_beta_max") if k in self._kwargs}
             extra = {} if dr is None and not free else dict(dr=dr, free=free)
+            if not self._marginalize_over_inclination:
+                extra.update(conditional=True, normalized=self._normalized)
             sb = SampleBatches(slots, e0.f64(t[None, :]), e0.f64(F[None, :, :]), stars,
                                e0.f64(e0.rTA1L(np.asarray(u, dtype=np.float64))), self._covpts,
                                diag_dev=e0.f64(data_cov.reshape(1, K)) if data_cov.ndim == 1 else None,
