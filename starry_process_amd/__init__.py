@@ -16,7 +16,7 @@ def __getattr__(name):
 
         return getattr(upstream, name)
     if name in ("ops", "flux", "sp", "engine", "ensemble", "upstream", "upstream_device", "hostconst",
-                "calibrate", "math", "grad"):
+                "calibrate", "math", "grad", "stars"):
         import importlib
 
         return importlib.import_module("." + name, __name__)

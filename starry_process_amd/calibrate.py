@@ -394,21 +394,12 @@ class EnsembleLogProb(object):
 
         from . import ensemble
         from .defaults import defaults
-        from .engine import engine_slots, make_stars
+        from .engine import engine_slots
+        from .stars import check_period_inclination, ensemble_stars
 
-        self._free = tuple(name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var))
-                           if val is None)
-        if isinstance(dr, str):
-            if dr != "free":
-                raise ValueError("dr must be None, a number or 'free'")
-        elif dr is not None:
-            from .ops import CheckBoundsOp
-
-            dr = float(dr)
-            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
-        self._dr = dr
-        self.columns = ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(
-            {"baseline_mean": "m", "baseline_log_var": "v"}[f] for f in self._free)
+        self.columns, self._free = SampleBatches.column_names(dr=dr, free=[
+            name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var)) if val is None])
+        self._dr = dr if dr is None or isinstance(dr, str) else float(dr)
         baseline_mean = 0.0 if baseline_mean is None else baseline_mean            # (placeholders: overwritten per sample)
         baseline_log_var = 0.0 if baseline_log_var is None else baseline_log_var
         flux = np.asarray(flux, dtype=np.float64)
@@ -420,31 +411,22 @@ class EnsembleLogProb(object):
         lo, hi = ensemble.shard_bounds(S, rank, world)
         self.S, self.K, self._n_local = S, K, hi - lo
         udeg = defaults["udeg"]
-        t = np.asarray(t, dtype=np.float64)
-        t = np.broadcast_to(t, (S, K)) if t.ndim == 1 else t
-        per = lambda x, d: np.broadcast_to(np.asarray(d if x is None else x, dtype=np.float64), (S,))[lo:hi]
-        pp, ii = per(p, defaults["p"]), per(i, defaults["i"])
-        if np.any(pp < -1e-6):
-            raise ValueError("p out of bounds")
-        if np.any(ii * np.pi / 180 < -1e-6) or np.any(ii * np.pi / 180 > 0.5 * np.pi + 1e-6):
-            raise ValueError("i out of bounds")
-        uu = np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
-        if uu.ndim == 1:
-            utab, table = uu[None, :udeg], np.zeros(hi - lo, dtype=np.int32)
-        else:
-            utab, table = np.unique(uu[lo:hi, :udeg], axis=0, return_inverse=True)
-            table = table.astype(np.int32).reshape(-1)
-        stars = make_stars(hi - lo, period=pp, inc_deg=ii, tau=0.0,
-                           baseline_var=np.full(hi - lo, 10.0 ** baseline_log_var),
-                           baseline_mean=per(baseline_mean, 0.0),
-                           data_var=per(np.asarray(ferr, dtype=np.float64) ** 2, 1.0), table=table)
+        # this rank's stars: what is per star is cut to the shard [lo, hi) first, so that the limb-darkening sets (and
+        # with them rta1 and the kernel tables) are those of the shard alone
+        t, uu = np.asarray(t, dtype=np.float64), np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
+        shard = lambda x, d: np.broadcast_to(np.asarray(d if x is None else x, dtype=np.float64), (S,))[lo:hi]  # noqa: E731
+        pp, ii = shard(p, defaults["p"]), shard(i, defaults["i"])
+        check_period_inclination(pp, ii)
+        t, stars, utab, _ = ensemble_stars((hi - lo, K), t if t.ndim == 1 else t[lo:hi], pp, ii,
+                                           uu if uu.ndim == 1 else uu[lo:hi], udeg, shard(baseline_mean, 0.0),
+                                           10.0 ** baseline_log_var, shard(np.asarray(ferr, dtype=np.float64) ** 2, 1.0))
         # (depth likelihood streams + the upstream's own: never more than MAX_STREAMS concurrent streams)
         depth = clamp_depth(depth, 1)
         slots = engine_slots(ydeg, udeg, device, max(2, depth + 1))
         self._slots, self._up = slots[:-1], slots[-1]          # likelihood slots; the upstream's own engine + stream
         self._upstream_stream = bool(upstream_stream)          # False: a sample's moments on its likelihood stream
         e0 = self._slots[0][0]
-        self._t = e0.f64(np.ascontiguousarray(t[lo:hi]))
+        self._t = e0.f64(t)
         self._flux = e0.f64(np.ascontiguousarray(flux[lo:hi, None, :]))
         self._stars = e0.stars_to_device(stars)
         self._stars_host = stars

@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import hostconst
 from ._lib import STAR_DTYPE, TEMPORAL, SPError, c_void_p, check, hptr
+from .stars import make_stars, sample_parameters, samples_in_bounds, stars_for_samples  # noqa: F401
 
 __all__ = ["Engine", "DataPlan", "get_engine", "make_stars", "stars_for_samples", "sample_parameters", "samples_in_bounds"]
 
@@ -20,109 +21,6 @@ def _torch():
     import torch
 
     return torch
-
-
-def make_stars(S, period=1.0, inc_deg=60.0, tau=0.0, baseline_var=0.0,
-               baseline_mean=0.0, data_var=0.0, table=0, nobs=0):
-    """Structured host array of ``sp_star`` (inclination converted to radians,
-    flux.py:236-238).  ``nobs``: valid cadences per star for ragged ensembles (0 = all)."""
-    st = np.zeros(S, dtype=STAR_DTYPE)
-    st["period"] = period
-    st["inc"] = np.asarray(inc_deg, dtype=float) * (np.pi / 180)
-    st["tau"] = tau
-    st["baseline_var"] = baseline_var
-    st["baseline_mean"] = baseline_mean
-    st["data_var"] = data_var
-    st["table"] = table
-    st["nobs"] = nobs
-    return st
-
-
-def stars_for_samples(stars, B, ntab, baseline_mean=None, baseline_var=None, period=None, inc_deg=None, tau=None,
-                      own_tables=True):
-    """The sp_star array of a batch of B hyperparameter samples x S stars (sample-major: system b S + s): the S stars
-    repeated B times with table = b ntab + table_s, the kernel table of sample b for the star's flux operator
-    (sp_kernel_table_samples' numbering).  ``baseline_mean`` / ``baseline_var`` [B]: the baseline terms of sample b
-    when they are free parameters of the samples (calibrate/log_prob.py:24-47), for every star of that sample; ``period``,
-    ``inc_deg`` (degrees, stored in radians like make_stars) and ``tau`` [B] likewise: the rotation period, inclination
-    and timescale of sample b.  ``own_tables=False``: every sample keeps the stars' table indices (the conditional
-    branch, where ``table`` selects the flux operator and there are no per-sample tables)."""
-    stars = np.ascontiguousarray(stars)
-    assert stars.dtype == STAR_DTYPE
-    out = np.tile(stars, int(B))
-    if own_tables:
-        out["table"] = (np.repeat(np.arange(int(B), dtype=np.int64), stars.shape[0]) * int(ntab)
-                        + out["table"]).astype(np.int32)
-    for field, val in (("baseline_mean", baseline_mean), ("baseline_var", baseline_var), ("period", period),
-                       ("inc", inc_deg), ("tau", tau)):
-        if val is not None:
-            val = np.asarray(val, dtype=np.float64).reshape(-1)
-            if val.shape[0] != int(B):
-                raise ValueError("%s must have one entry per sample" % field)
-            out[field] = np.repeat(val * (np.pi / 180) if field == "inc" else val, stars.shape[0])
-    return out
-
-
-def samples_in_bounds(samples, tol=1e-6, dr=False):
-    """Boolean mask of the rows of samples [B, 5] = (r [degrees], a, b, c, n) inside the reference's bounds (r in [0, 90],
-    a, b in [0, 1], n >= 0, everything finite; size.py:68, latitude.py:176-197, contrast.py:21-33 through CheckBoundsOp's
-    tolerance): what ``sample_parameters`` raises ValueError for.  A sampler's walkers leave the box; the log-probability
-    callables can answer -inf for such rows instead of raising (``out_of_bounds="inf"``).  ``dr=True``: rows of
-    (r, dr [degrees], a, b, c, n), dr in [0, 90] (size.py:120-122)."""
-    sm = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-    ok = np.all(np.isfinite(sm), axis=1)
-    if dr:
-        d = sm[:, 1] * (np.pi / 180)
-        ok &= (d >= -tol) & (d <= 0.5 * np.pi + tol)
-        sm = np.delete(sm, 1, axis=1)
-    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
-    ok &= (r >= -tol) & (r <= 0.5 * np.pi + tol) & (a >= -tol) & (a <= 1 + tol) & (b >= -tol) & (b <= 1 + tol) & (n >= -tol)
-    return ok
-
-
-def sample_parameters(samples, dr=False, **kw):
-    """samples [B, 5] = (r [degrees], a, b, c, n) -> [B, 5] = (r [radians], alpha, beta, c, n), what
-    sp_polar_moments_samples takes: the reference's bounds (size.py:68, latitude.py:176-197, contrast.py:21-33 through
-    CheckBoundsOp: ValueError outside, tolerance 1e-6) and its (a, b) -> (alpha, beta) map, for the whole batch at once
-    (NumPy; one sample at a time ``upstream.ab_to_alphabeta`` does the same).  ``dr=True``: samples [B, 6] = (r, dr
-    [degrees], a, b, c, n) -> [B, 6] = (r, dr [radians], alpha, beta, c, n), what sp_polar_moments_samples_spread takes
-    (dr in [0, 90] degrees, size.py:120-122)."""
-    from .defaults import defaults
-
-    sm = np.array(np.atleast_2d(np.asarray(samples, dtype=np.float64)), dtype=np.float64)
-    if dr:
-        if sm.ndim != 2 or sm.shape[1] != 6:
-            raise ValueError("samples must be (B, 6): r, dr, a, b, c, n")
-        from .ops import CheckBoundsOp
-
-        d = sm[:, 1] * (np.pi / 180)
-        CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(d)
-        if not np.all(np.isfinite(d)):
-            raise ValueError("samples must be finite")
-        out = np.empty_like(sm)
-        out[:, [0, 2, 3, 4, 5]] = sample_parameters(np.delete(sm, 1, axis=1), **kw)
-        out[:, 1] = np.clip(d, 0.0, None)
-        return np.ascontiguousarray(out)
-    if sm.ndim != 2 or sm.shape[1] != 5:
-        raise ValueError("samples must be (B, 5): r, a, b, c, n")
-    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
-    from .ops import CheckBoundsOp
-
-    for name, v, lo, hi in (("r", r, 0.0, 0.5 * np.pi), ("a", a, 0.0, 1.0), ("b", b, 0.0, 1.0), ("n", n, 0.0, np.inf)):
-        CheckBoundsOp(name=name, lower=lo, upper=hi)(v)
-    if not np.all(np.isfinite(sm)):
-        raise ValueError("samples must be finite")
-    abmin = kw.get("abmin", defaults["abmin"])
-    lam = kw.get("log_alpha_max", defaults["log_alpha_max"])
-    lbm = kw.get("log_beta_max", defaults["log_beta_max"])
-    a, b = np.maximum(a, abmin), np.maximum(b, abmin)
-    out = np.empty_like(sm)
-    out[:, 0] = np.clip(r, 0.0, None)
-    out[:, 1] = np.exp(a * lam)
-    out[:, 2] = np.exp(np.log(0.5) + b * (lbm - np.log(0.5)))
-    out[:, 3] = sm[:, 3]
-    out[:, 4] = np.clip(n, 0.0, None)
-    return np.ascontiguousarray(out)
 
 
 _STAGE_BYTES, _STAGE_SLOTS = 1 << 16, 16   # pinned staging ring of Engine.dev (small uploads)
@@ -217,6 +115,26 @@ class Engine(object):
     def empty(self, *shape):
         torch = _torch()
         return torch.empty(*shape, dtype=torch.float64, device=self.device)
+
+    def _scratch(self, nbytes):
+        """``nbytes`` of device scratch for one library call (a ``*_workspace_bytes`` query's answer)."""
+        torch = _torch()
+        return torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+
+    def _grad_scratch(self, nbytes, workspace):
+        """The caller's ``workspace`` if it holds ``nbytes``, fresh scratch (kept on the engine) otherwise."""
+        if workspace is None or workspace.numel() < nbytes:
+            workspace = self._grad_ws = self._scratch(nbytes)
+        return workspace
+
+    def _out_status(self, S, out, status):
+        """(out, status) of a likelihood call over S systems: the caller's tensors, or fresh ones (status zeroed)."""
+        if out is None:
+            out = self.empty(S)
+        if status is None:
+            torch = _torch()
+            status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        return out, status
 
     def stars_to_device(self, stars):
         torch = _torch()
@@ -418,15 +336,10 @@ class Engine(object):
         check(self._L.sp_set_size_basis(self._h, hptr(theta), hptr(Bp), int(theta.shape[0]), sfac))
         self._size_basis_key = key
 
-    def polar_moments_samples(self, samples, ez=None, Ez=None, dr=None, **kw):
-        """samples [B, 5] = (r [degrees], a, b, c, n) per row, the argument order of the reference's log-probability
-        (calibrate/log_prob.py:93-102) -> (ez [B, N], Ez [B, N, N]) device tensors: the polar-frame moments of B
-        hyperparameter samples in one library call (sp_polar_moments_samples).  Bounds are the reference's
-        (ValueError before anything is launched).  ``dr``: None (one spot radius), or the half-width of the uniform
-        law of the radii in degrees, a scalar or one value per sample (StarryProcess(dr=...), size.py:109-125): one
-        call of sp_polar_moments_samples_spread; a sample with dr = 0 is the one-radius case."""
-        from .defaults import defaults
-
+    def _sample_rows(self, samples, dr, **kw):
+        """(rows [B, 5] or, with ``dr``, [B, 6] as the sample kernels take them, B): ``sample_parameters`` of samples
+        [B, 5] with ``dr`` (None, a scalar or one value per sample) as their second column; hands the spot profile's
+        basis to the library on the way (set_size_basis)."""
         if dr is not None:
             sm5 = np.atleast_2d(np.asarray(samples, dtype=np.float64))
             if sm5.ndim != 2 or sm5.shape[1] != 5:
@@ -437,8 +350,19 @@ class Engine(object):
             sm = sample_parameters(np.insert(sm5, 1, np.broadcast_to(d, (sm5.shape[0],)), axis=1), dr=True, **kw)
         else:
             sm = sample_parameters(samples, **kw)
-        B = sm.shape[0]
         self.set_size_basis(**kw)
+        return sm, sm.shape[0]
+
+    def polar_moments_samples(self, samples, ez=None, Ez=None, dr=None, **kw):
+        """samples [B, 5] = (r [degrees], a, b, c, n) per row, the argument order of the reference's log-probability
+        (calibrate/log_prob.py:93-102) -> (ez [B, N], Ez [B, N, N]) device tensors: the polar-frame moments of B
+        hyperparameter samples in one library call (sp_polar_moments_samples).  Bounds are the reference's
+        (ValueError before anything is launched).  ``dr``: None (one spot radius), or the half-width of the uniform
+        law of the radii in degrees, a scalar or one value per sample (StarryProcess(dr=...), size.py:109-125): one
+        call of sp_polar_moments_samples_spread; a sample with dr = 0 is the one-radius case."""
+        from .defaults import defaults
+
+        sm, B = self._sample_rows(samples, dr, **kw)
         if ez is None:
             ez = self.empty(B, self.N)
         if Ez is None:
@@ -461,18 +385,7 @@ class Engine(object):
         Bounds, ``dr`` and the keywords are polar_moments_samples'."""
         from .defaults import defaults
 
-        if dr is not None:
-            sm5 = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-            if sm5.ndim != 2 or sm5.shape[1] != 5:
-                raise ValueError("samples must be (B, 5): r, a, b, c, n")
-            d = np.asarray(dr, dtype=np.float64)
-            if d.ndim > 1 or (d.ndim == 1 and d.shape[0] != sm5.shape[0]):
-                raise ValueError("dr must be a scalar or one value per sample")
-            sm = sample_parameters(np.insert(sm5, 1, np.broadcast_to(d, (sm5.shape[0],)), axis=1), dr=True, **kw)
-        else:
-            sm = sample_parameters(samples, **kw)
-        B = sm.shape[0]
-        self.set_size_basis(**kw)
+        sm, B = self._sample_rows(samples, dr, **kw)
         if mean is None:
             mean = self.empty(B, self.N)
         if cov is None:
@@ -563,7 +476,7 @@ class Engine(object):
         nbytes = int(self._L.sp_spd_inverse_workspace_bytes(self._h, B, K))
         ws = workspace
         if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            ws = self._scratch(nbytes)
         out = torch.zeros(B, Kr, Kr, dtype=torch.float64, device=self.device)
         logdet = self.empty(B)
         info = torch.zeros(B, dtype=torch.int32, device=self.device)
@@ -699,8 +612,7 @@ class Engine(object):
         sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
         diag = None if diag is None else self.f64(diag)
         rta1 = None if rta1 is None else self.f64(rta1)
-        ws = torch.empty(int(self._L.sp_predict_workspace_bytes(self._h, S, K, Ks, int(covpts))), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_predict_workspace_bytes(self._h, S, K, Ks, int(covpts)))
         out = extra(S, K, Ks)
         check(fn(self._h, S, K, Ks, self._p(t), self._p(ts), self._p(flux), self._p(diag), self._p(sd),
                  int(bool(conditional)), int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
@@ -757,8 +669,7 @@ class Engine(object):
 
     def _ylm_buffers(self, S, K, with_cho):
         torch = _torch()
-        nbytes = int(self._L.sp_ylm_conditional_workspace_bytes(self._h, S, K))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._scratch(self._L.sp_ylm_conditional_workspace_bytes(self._h, S, K))
         ymu, ycov = self.empty(S, self.N), self.empty(S, self.N, self.N)
         ycho = self.empty(S, self.N, self.N) if with_cho else None
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
@@ -795,13 +706,11 @@ class Engine(object):
     def pixel_transform(self, xyz):
         """M [npts, N] = pi pT(x, y, z) A1, the Ylm -> intensity transform at the points xyz [3, npts] of the unit
         sphere (sp_pixel_transform; NaN rows where z is NaN)."""
-        torch = _torch()
         xyz = self.f64(xyz)
         if xyz.dim() != 2 or xyz.shape[0] != 3 or xyz.shape[1] < 1:
             raise ValueError("xyz must be (3, npts)")
         npts = int(xyz.shape[1])
-        ws = torch.empty(int(self._L.sp_pixel_transform_workspace_bytes(self._h, npts)), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_pixel_transform_workspace_bytes(self._h, npts))
         M = self.empty(npts, self.N)
         check(self._L.sp_pixel_transform(self._h, npts, self._p(xyz), self._p(M), self.N, self._p(ws),
                                          self._stream()))
@@ -810,7 +719,6 @@ class Engine(object):
     def pixel_cov(self, M, cov):
         """(M cov) M^T, exactly symmetric (sp_pixel_cov_batched): cov [N, N] -> [npts, npts], or a stack of S
         covariances [S, N, N] -> [S, npts, npts] in one call.  M [npts, N] from pixel_transform."""
-        torch = _torch()
         M, cov = self.f64(M), self.f64(cov)
         npts, N = M.shape
         assert N == self.N and cov.shape[-2:] == (N, N)
@@ -818,8 +726,7 @@ class Engine(object):
         cov = cov.reshape(-1, N, N).contiguous()
         S = int(cov.shape[0])
         out = self.empty(S, npts, npts)
-        ws = torch.empty(int(self._L.sp_pixel_cov_workspace_bytes(self._h, S, npts)), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_pixel_cov_workspace_bytes(self._h, S, npts))
         check(self._L.sp_pixel_cov_batched(self._h, S, npts, self._p(M), N, self._p(cov), N * N, self._p(out), npts,
                                            npts * npts, self._p(ws), self._stream()))
         return out[0] if single else out
@@ -856,15 +763,13 @@ class Engine(object):
     def ylm_temporal(self, Lt, Ly, U, status=None):
         """Y[n] = Lt U[n] Ly^T (sp_ylm_temporal): Lt [Nt, Nt], Ly [N, N] (lower triangles read), U [ns, Nt, N] ->
         Y [ns, Nt, N]; all NaN if a factor's diagonal is not finite (then status [1], if given, gets 1)."""
-        torch = _torch()
         Lt, Ly, U = self.f64(Lt), self.f64(Ly), self.f64(U)
         if U.dim() != 3 or Lt.dim() != 2 or Lt.shape[0] != Lt.shape[1] or Lt.shape[0] != U.shape[1] or \
                 Ly.shape != (self.N, self.N) or U.shape[2] != self.N:
             raise ValueError("need Lt [Nt, Nt], Ly [N, N] and U [ns, Nt, N] with N = %d" % self.N)
         ns, Nt = int(U.shape[0]), int(U.shape[1])
         Y = self.empty(ns, Nt, self.N)
-        ws = torch.empty(int(self._L.sp_ylm_temporal_workspace_bytes(self._h, ns, Nt)), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_ylm_temporal_workspace_bytes(self._h, ns, Nt))
         check(self._L.sp_ylm_temporal(self._h, ns, Nt, self._p(Lt), Nt, self._p(Ly), self.N, self._p(U), self._p(Y),
                                       self._p(ws), self._p(status), self._stream()))
         return Y
@@ -906,7 +811,7 @@ class Engine(object):
         WPT = torch.empty(Np, ldp, dtype=torch.float64, device=self.device)
         L = self.empty(self.N, self.N)
         info = torch.zeros(1, dtype=torch.int32, device=self.device)
-        ws = torch.empty(int(self._L.sp_generate_gram_workspace_bytes(self._h)), dtype=torch.uint8, device=self.device)
+        ws = self._scratch(self._L.sp_generate_gram_workspace_bytes(self._h))
         wd = self.f64(np.repeat(w, lon.size))   # (every uploaded operand stays referenced until the call returns)
         check(self._L.sp_generate_gram(self._h, npix, self._p(M), self.N, self._p(wd), float(eps), self._p(WPT), ldp,
                                        self._p(L), self.N, self._p(info), self._p(ws), self._stream()))
@@ -944,14 +849,12 @@ class Engine(object):
     def generate_project(self, WPT, L, WX, S, smoothing):
         """y [S, N] = s_l . G^-1 (W P)^T (W X[s]) (sp_generate_project), WPT / L from generate_setup, WX from
         generate_paint."""
-        torch = _torch()
         ldp, ldwx = int(WPT.shape[1]), int(WX.shape[1])
         if int(WX.shape[0]) < max(1, (S + self.GEN_ROWS - 1) // self.GEN_ROWS) * self.GEN_ROWS or \
                 int(WPT.shape[0]) < (self.N + self.GEN_ROWS - 1) // self.GEN_ROWS * self.GEN_ROWS:
             raise ValueError("WX must come from generate_paint of the same S stars, WPT from generate_setup")
         y = self.empty(S, self.N)
-        ws = torch.empty(int(self._L.sp_generate_project_workspace_bytes(self._h, S)), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_generate_project_workspace_bytes(self._h, S))
         check(self._L.sp_generate_project(self._h, int(S), ldp, self._p(WPT), ldp, self._p(L), self.N, self._p(WX),
                                           ldwx, float(smoothing), self._p(y), self._p(ws), self._stream()))
         return y
@@ -961,14 +864,12 @@ class Engine(object):
     def generate_flux(self, t, stars, rta1, y, noise, ferr, normalization=None):
         """(flux0, flux) [S, K] (sp_generate_flux): flux0[s] = A_s y[s] at the shared times t [K], A_s the design
         matrix of stars[s]; flux = flux0 (normalization None) or its mean / median normalisation, plus ferr noise."""
-        torch = _torch()
         t, y, noise = self.f64(t).reshape(-1), self.f64(y), self.f64(noise)
         S, K = int(y.shape[0]), int(t.shape[0])
         if y.shape != (S, self.N) or noise.shape != (S, K) or len(stars) != S:
             raise ValueError("need y [S, %d], noise [S, K] and S stars" % self.N)
         flux0, flux = self.empty(S, K), self.empty(S, K)
-        ws = torch.empty(int(self._L.sp_generate_flux_workspace_bytes(self._h, S, K)), dtype=torch.uint8,
-                         device=self.device)
+        ws = self._scratch(self._L.sp_generate_flux_workspace_bytes(self._h, S, K))
         sd, rta1 = self.stars_to_device(stars), self.f64(rta1)
         check(self._L.sp_generate_flux(self._h, S, K, self._p(t), self._p(sd), self._p(rta1), self._p(y),
                                        self._p(noise), float(ferr), self.GEN_NORM[normalization], self._p(flux0),
@@ -1009,8 +910,7 @@ class Engine(object):
         status = torch.zeros(S, J, P, dtype=torch.int32, device=self.device)
         if S == 0 or J == 0 or P == 0:
             return out, status
-        nbytes = int(self._L.sp_lnlike_inclinations_workspace_bytes(self._h, S, M, ntab, B, P))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._scratch(self._L.sp_lnlike_inclinations_workspace_bytes(self._h, S, M, ntab, B, P))
         check(self._L.sp_lnlike_inclinations(
             self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(rta1), ntab, B,
             self._p(mean_ylm), self._p(cov_ylm), J, self._p(sel), P, self._p(inc), int(bool(normalized)),
@@ -1019,13 +919,12 @@ class Engine(object):
 
     # -- fused likelihood ----------------------------------------------------------
     def workspace(self, S, K, M):
-        torch = _torch()
         nbytes = self._L.sp_lnlike_workspace_bytes(self._h, S, K, M)
         if nbytes < 0:
             check(int(nbytes))
         if self._ws is None or self._ws.numel() < nbytes:
             self._ws = None
-            self._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+            self._ws = self._scratch(nbytes)
         return self._ws
 
     def lnlike_ensemble(self, t, flux, stars_dev, diag=None, conditional=False,
@@ -1034,14 +933,10 @@ class Engine(object):
                         status=None, workspace=None):
         """All arguments already on the device (torch tensors); t [S,K],
         flux [S,M,K], stars_dev from stars_to_device().  Returns (lnlike, status)."""
-        torch = _torch()
         S, K = t.shape
         M = flux.shape[1]
         ws = workspace if workspace is not None else self.workspace(S, K, M)
-        if out is None:
-            out = self.empty(S)
-        if status is None:
-            status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        out, status = self._out_status(S, out, status)
         check(self._L.sp_lnlike_ensemble(
             self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev),
             int(bool(conditional)), int(covpts), self._p(tab), self._p(meanvar),
@@ -1072,10 +967,7 @@ class Engine(object):
         elif select.dtype != torch.int32 or select.numel() != S or not select.is_contiguous() or not select.is_cuda:
             raise ValueError("a device select must be a contiguous int32 tensor with one index per system")
         ws = workspace if workspace is not None else self.workspace(S, K, M)
-        if out is None:
-            out = self.empty(S)
-        if status is None:
-            status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        out, status = self._out_status(S, out, status)
         check(self._L.sp_lnlike_ensemble_sets(
             self._h, S, K, M, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(rta1), B,
             self._p(mean_ylm), self._p(cov_ylm), self._p(select), TEMPORAL[temporal], int(bool(normalized)),
@@ -1108,15 +1000,11 @@ class Engine(object):
                                 zmax=0.023, out=None, status=None, workspace=None):
         """``lnlike_ensemble(conditional=False, normalized=True)`` on planned data (sp_lnlike_ensemble_planned):
         the same values to rounding, without the per-sample pass over the covariance's entries."""
-        torch = _torch()
         S, K, M = plan.S, plan.K, plan.M
         # (t = flux = diag = None: the plan's own arrays -- a replica's copies, or the tensors of plan time)
         assert (t is None and flux is None and diag is None) or (tuple(t.shape) == (S, K) and tuple(flux.shape) == (S, M, K))
         ws = workspace if workspace is not None else self.workspace(S, K, M)
-        if out is None:
-            out = self.empty(S)
-        if status is None:
-            status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        out, status = self._out_status(S, out, status)
         check(self._L.sp_lnlike_ensemble_planned(
             self._h, plan.ptr, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(tab),
             self._p(meanvar), int(norm_order), float(zmax), self._p(ws), self._p(out), self._p(status),
@@ -1134,9 +1022,7 @@ class Engine(object):
         flux = flux.reshape(S, -1, K)
         M = flux.shape[1]
         nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, M, int(covpts)))
-        ws = workspace
-        if ws is None or ws.numel() < nbytes:
-            ws = self._grad_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._grad_scratch(nbytes, workspace)
         out, ybar, mbar = self.empty(S), self.empty(S, covpts + 4), self.empty(S)
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         check(self._L.sp_lnlike_grad_marginal_multi(
@@ -1156,9 +1042,7 @@ class Engine(object):
         flux = flux.reshape(S, -1, K)
         M = flux.shape[1]
         nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, M, int(covpts)))
-        ws = workspace
-        if ws is None or ws.numel() < nbytes:
-            ws = self._grad_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._grad_scratch(nbytes, workspace)
         out, ybar, mbar, sbar = self.empty(S), self.empty(S, covpts + 4), self.empty(S), self.empty(S, 6)
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         check(self._L.sp_lnlike_grad_marginal_stars(
@@ -1183,9 +1067,7 @@ class Engine(object):
         if S == 0:
             return out, mubar, sigbar, sbar, status
         nbytes = int(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
-        ws = workspace
-        if ws is None or ws.numel() < nbytes:
-            ws = self._grad_ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        ws = self._grad_scratch(nbytes, workspace)
         check(self._L.sp_lnlike_grad_conditional(
             self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(rta1),
             TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(ws), self._p(out),
@@ -1193,25 +1075,19 @@ class Engine(object):
         return out, mubar, sigbar, sbar, status
 
     def grad_conditional_workspace(self, S, K):
-        torch = _torch()
-        nbytes = int(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 
     def grad_workspace(self, S, K, covpts, M=1):
-        torch = _torch()
-        nbytes = int(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, int(M), int(covpts)))
-        return torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return self._scratch(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, int(M), int(covpts)))
 
     def cholesky_lnlike(self, cov, resid):
         """cov [S,K,K] (noise included), resid [S,M,K] -> (lnlike [S], status [S])."""
-        torch = _torch()
         cov = self.f64(cov)
         resid = self.f64(resid)
         S, K, _ = cov.shape
         M = resid.shape[1]
         ws = self.workspace(S, K, M)
-        out = self.empty(S)
-        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        out, status = self._out_status(S, None, None)
         check(self._L.sp_cholesky_lnlike_batched(self._h, S, K, M, self._p(cov), self._p(resid),
                                                  self._p(ws), self._p(out), self._p(status), self._stream()))
         return out, status

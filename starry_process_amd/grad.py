@@ -33,6 +33,7 @@ import numpy as np
 
 from .defaults import defaults
 from .engine import get_engine
+from .stars import check_period_inclination, ensemble_stars
 from .temporal import kernel_id
 
 __all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient",
@@ -152,6 +153,36 @@ def _alpha_beta(z, order):
         beta = beta + 2 * n * fac
         fac = fac * z * (2 * n + 3)
     return alpha, beta
+
+
+def _upstream_eps(N, ukw, like=None):
+    """[N] the jitter on the diagonal of Sigma_y (``epsy``, and ``epsy15`` from l = 15 on: upstream_kwargs ``ukw`` or the
+    defaults) -- the part of Sigma_y that does not scale with c and n.  NumPy, or a tensor on the device of ``like``."""
+    epsy = float(ukw.get("epsy", defaults["epsy"]))
+    if like is None:
+        eps = np.ones(N) * epsy
+    else:
+        eps = _torch().full((N,), epsy, dtype=_torch().float64, device=like.device)
+    eps[15 ** 2:] = float(ukw.get("epsy15", defaults["epsy15"]))
+    return eps
+
+
+def _cn_chain(gm, gS, c, n, unit=None):
+    """(d lnL / dc, d lnL / dn) through the moments mu_y = c n m, Sigma_y - eps = c^2 n S (contrast.py:21-33), from the
+    inner products gm = <gmu, mu_y> and gS = <gSig, Sigma_y - eps> of the moments' adjoints (floats or 0-d tensors).
+    On the boundary c = 0 or n = 0 the moments at the point hold nothing to divide by, but the derivative is not zero
+    there: ``unit()`` returns the same two products against the moments at unit contrast and unit number of spots (one
+    more upstream evaluation, made only there), and d/dc = n gm + 2 c n gS, d/dn = c gm + c^2 gS."""
+    if c != 0 and n != 0:
+        return gm / c + 2.0 * gS / c, gm / n + gS / n
+    gm, gS = unit()
+    return n * gm + 2.0 * c * n * gS, c * gm + c * c * gS
+
+
+def _temporal_id(temporal_kernel, tau):
+    """The device's kernel selector for ``temporal_kernel`` (a name or one of temporal.py's callables); None without a
+    timescale."""
+    return (temporal_kernel if isinstance(temporal_kernel, str) else kernel_id(temporal_kernel)) if tau else None
 
 
 def log_likelihood_with_grad(mean_ylm, cov_ylm, t, flux, data_var, i=defaults["i"], p=defaults["p"], u=None,
@@ -282,22 +313,17 @@ def hyper_gradient(t, flux, data_var, r=defaults["r"], dr=defaults["dr"], a=defa
     mu_at, Sig_at = (mu, Sig) if moments0 is None else (np.asarray(moments0[0]), np.asarray(moments0[1]))
     lnl, g = log_likelihood_with_grad(mu_at, Sig_at, t, flux, data_var, **kwargs)
     gmu, gSig = g["mean_ylm"], g["cov_ylm"]
-    N = mu.shape[0]
-    eps = np.ones(N) * float(ukw.get("epsy", defaults["epsy"]))
-    eps[15 ** 2:] = float(ukw.get("epsy15", defaults["epsy15"]))
-    S0 = Sig - np.diag(eps)                       # the part of Sigma_y that scales with c and n
+    eps = np.diag(_upstream_eps(mu.shape[0], ukw))        # Sigma_y - eps: the part that scales with c and n
+    inner = lambda m_, S_: (gmu @ m_, np.sum(gSig * (S_ - eps)))          # noqa: E731
     out = {k: v for k, v in g.items() if k not in ("mean_ylm", "cov_ylm")}
     if c != 0 and n != 0:
-        # mu ~ c n, Sigma ~ c^2 n (contrast.py:21-33)
-        out.update({"c": float(gmu @ mu / c + 2.0 * np.sum(gSig * S0) / c),
-                    "n": float(gmu @ mu / n + np.sum(gSig * S0) / n)})
+        gc, gn = _cn_chain(*inner(mu, Sig), c, n)
     else:
-        # at c = 0 (n = 0) the moments are linear (quadratic) in the vanishing parameter: take the
-        # derivative from the moments at unit value of it
-        m1, S1 = moments(r, dr, a, b, c_=c if c != 0 else 1.0, n_=n if n != 0 else 1.0)
-        S1 = S1 - np.diag(eps)
-        out.update({"c": float(gmu @ m1) if (c == 0 and n != 0) else 0.0,     # d mu / dc = mu(c = 1); d Sigma / dc = 0
-                    "n": float(gmu @ m1 + np.sum(gSig * S1)) if (n == 0 and c != 0) else 0.0})
+        # _cn_chain's boundary rule with the surviving factor left inside the moments (at c = 0: the moments at c = 1
+        # and the given n; at n = 0: at n = 1 and the given c) -- the same derivative, rounded in another order
+        gm, gS = inner(*moments(r, dr, a, b, c_=c if c != 0 else 1.0, n_=n if n != 0 else 1.0))
+        gc, gn = gm if (c == 0 and n != 0) else 0.0, gm + gS if (n == 0 and c != 0) else 0.0
+    out.update({"c": float(gc), "n": float(gn)})
     x0 = {"r": r, "dr": dr, "a": a, "b": b}
     bounds = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}
     if dr is None and exact:
@@ -341,7 +367,34 @@ def _check_wrt(wrt, has_tau):
     return wrt
 
 
-class EnsembleGradient(object):
+class _EnsembleSweep(object):
+    """What the two ensemble gradients share: their data and star records on the GPU."""
+
+    def _setup(self, t, flux, ferr, p, i, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel, device):
+        """Host work first (every ValueError before a device is touched), then ``self._open`` for the engine and the
+        uploads: t, flux, the per-cadence variances (or None), the star records, rTA1L of the distinct limb-darkening
+        sets and the temporal kernel's id; synchronised on return.  Returns the host records and sets."""
+        S, K = flux.shape[0], flux.shape[-1]
+        if K < 2:
+            raise ValueError("at least two cadences")
+        check_period_inclination(p)
+        udeg = defaults["udeg"]
+        var = np.asarray(ferr, dtype=np.float64) ** 2
+        t, stars, utab, diag = ensemble_stars((S, K), t, p, i, u, udeg, baseline_mean, baseline_var,
+                                              np.broadcast_to(var, (S, K)) if var.ndim == 2 else var,
+                                              tau=float(tau) if tau else 0.0)
+        e = self._e = self._open(ydeg, udeg, device)
+        self.S, self.K = S, K
+        self._t, self._flux = e.f64(t), e.f64(np.ascontiguousarray(flux))
+        self._diag = None if diag is None else e.f64(diag)
+        self._stars = e.stars_to_device(stars)
+        self._rta1 = e.f64(e.rTA1L(utab))
+        self._temporal = _temporal_id(temporal_kernel, tau)
+        _torch().cuda.synchronize(e.device)
+        return stars, utab
+
+
+class EnsembleGradient(_EnsembleSweep):
     """Log-likelihood of an ENSEMBLE of light curves and its gradient with respect to the spot hyperparameters
     (r, a, b, c, n[, dr]) in ONE device sweep per evaluation -- what ``theano.grad`` of the summed
     ``sp.log_likelihood`` is in the reference (tests/test_lnlike.py:100-136, calibrate/log_prob.py:53-91), for every
@@ -368,51 +421,31 @@ class EnsembleGradient(object):
     def __init__(self, t, flux, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, baseline_mean=0.0,
                  normalized=True, covpts=None, tau=None, temporal_kernel="matern32", device=None, h=1.0e-4,
                  upstream_kwargs=None, exact=True):
-        import torch
-
-        from .engine import engine_slots, make_stars
-
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim not in (2, 3):
             raise ValueError("flux must be (S, K) or (S, M, K)")
-        S, K = flux.shape[0], flux.shape[-1]
         M = flux.shape[1] if flux.ndim == 3 else 1
-        if K < 2:
-            raise ValueError("at least two cadences")
-        t = np.asarray(t, dtype=np.float64)
-        t = np.broadcast_to(t, (S, K)) if t.ndim == 1 else t
-        udeg = defaults["udeg"]
-        per = lambda x: np.broadcast_to(np.asarray(x, dtype=np.float64), (S,))
-        uu = np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
-        if uu.ndim == 1:
-            utab, table = uu[None, :udeg], np.zeros(S, dtype=np.int32)
-        else:
-            utab, table = np.unique(uu[:, :udeg], axis=0, return_inverse=True)
-            table = table.astype(np.int32).reshape(-1)
-        if np.any(per(p) < -1e-6):
-            raise ValueError("p out of bounds")
-        var = np.asarray(ferr, dtype=np.float64) ** 2
-        stars = make_stars(S, period=per(p), tau=float(tau) if tau else 0.0, baseline_var=per(baseline_var),
-                           baseline_mean=per(baseline_mean), data_var=per(var) if var.ndim < 2 else 0.0, table=table)
+        # (the star records carry no inclination on the marginal branch: make_stars' own default)
+        stars, utab = self._setup(t, flux, ferr, p, None, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel,
+                                  device)
+        e = self._e
+        self._ntab = utab.shape[0]
+        self._table = _torch().as_tensor(stars["table"].astype(np.int64), device=e.device)
+        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
+        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
+        self._exact = bool(exact)
+        self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
+        self.lnlike = None
+
+    def _open(self, ydeg, udeg, device):
+        from .engine import engine_slots
+
         # the sweep's handle + three more for the tables' finite differences: a table evaluation is a latency chain
         # of a dozen small kernels (0.3 ms); nine of them in a row on ONE stream outlast the sweep they should hide
         # behind (3.2 against 2.5 ms), three streams of three do not
         slots = engine_slots(ydeg, udeg, device, 4)
-        (self._e, self._stream), self._side = slots[0], slots[1:]
-        e = self._e
-        self.S, self.K, self._ntab = S, K, utab.shape[0]
-        self._t, self._flux = e.f64(np.ascontiguousarray(t)), e.f64(np.ascontiguousarray(flux))
-        self._diag = e.f64(np.ascontiguousarray(np.broadcast_to(var, (S, K)))) if var.ndim == 2 else None
-        self._stars = e.stars_to_device(stars)
-        self._rta1 = e.f64(e.rTA1L(utab))
-        self._table = torch.as_tensor(table.astype(np.int64), device=e.device)
-        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
-        self._temporal = (temporal_kernel if isinstance(temporal_kernel, str) else kernel_id(temporal_kernel)) if tau else None
-        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
-        self._exact = bool(exact)
-        self._ws = e.grad_workspace(S, K, self._covpts, M)
-        self.lnlike = None
-        torch.cuda.synchronize(e.device)
+        (e, self._stream), self._side = slots[0], slots[1:]
+        return e
 
     def _tables(self, eng, **hp):
         """(yp [ntab, np], mean [ntab]) of the kernel tables at the given hyperparameters, on eng's stream."""
@@ -521,9 +554,7 @@ class EnsembleGradient(object):
             # (the tables at the point are the main stream's: they are ready long before the sweep is)
             s3.wait_event(at_point)
             ypA, meanA, muA, SigA = yp0, mean0, mu, Sig
-            N = muA.shape[0]
-            eps = torch.full((N,), float(self._ukw.get("epsy", defaults["epsy"])), dtype=torch.float64, device=eu.device)
-            eps[15 ** 2:] = float(self._ukw.get("epsy15", defaults["epsy15"]))
+            eps = _upstream_eps(muA.shape[0], self._ukw, like=muA)
             zero_mu = torch.zeros_like(muA)
             eu.set_moments_dev(muA, torch.zeros_like(SigA))
             t_mm, _ = eu.kernel_table(self._rta1, self._covpts)             # f_mm part: yp = c^2 n^2 f_mm - mean^2
@@ -630,27 +661,13 @@ def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], 
         gmu += g["mean_ylm"]
         gSig += g["cov_ylm"]
         gi[s], gp[s] = g["i"], g["p"]
-    N = mu.shape[0]
-    eps = np.ones(N) * float(ukw.get("epsy", defaults["epsy"]))
-    eps[15 ** 2:] = float(ukw.get("epsy15", defaults["epsy15"]))
-    S0 = Sig - np.diag(eps)
-    out = {name: float(gmu @ dmu[k] + np.sum(gSig * dSig[k])) for k, name in enumerate(("r", "a", "b"))}
-    if c != 0 and n != 0:
-        # mu ~ c n, Sigma - eps ~ c^2 n (contrast.py:21-33)
-        out["c"] = float(gmu @ mu / c + 2.0 * np.sum(gSig * S0) / c)
-        out["n"] = float(gmu @ mu / n + np.sum(gSig * S0) / n)
-    else:
-        # On the boundary c = 0 or n = 0 the moments at the point hold nothing to divide by, but the derivative is not
-        # zero there: with the moments at unit contrast and unit number of spots, mu = c n m1 and Sigma - eps = c^2 n S1
-        # give d/dc = n gmu.m1 + 2 c n <gSig, S1> and d/dn = c gmu.m1 + c^2 <gSig, S1> -- what hyper_gradient and
-        # EnsembleGradient return there too (one more upstream evaluation).
-        from .upstream_device import ylm_moments_device
+    from .upstream_device import ylm_moments_device
 
-        m1, Sig1 = [x.cpu().numpy() for x in ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **ukw)]
-        S1 = Sig1 - np.diag(eps)
-        gm, gS = float(gmu @ m1), float(np.sum(gSig * S1))
-        out["c"] = float(n) * gm + 2.0 * float(c) * float(n) * gS
-        out["n"] = float(c) * gm + float(c) ** 2 * gS
+    eps = np.diag(_upstream_eps(mu.shape[0], ukw))
+    inner = lambda m_, S_: (float(gmu @ m_), float(np.sum(gSig * (S_ - eps))))          # noqa: E731
+    out = {name: float(gmu @ dmu[k] + np.sum(gSig * dSig[k])) for k, name in enumerate(("r", "a", "b"))}
+    out["c"], out["n"] = _cn_chain(*inner(mu, Sig), float(c), float(n), unit=lambda: inner(
+        *[x.cpu().numpy() for x in ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **ukw)]))
     out["i"], out["p"] = gi, gp
     return float(lnl.sum()), out, lnl
 
@@ -675,7 +692,7 @@ def _check_wrt_conditional(wrt):
     return wrt
 
 
-class EnsembleGradientConditional(object):
+class EnsembleGradientConditional(_EnsembleSweep):
     """The CONDITIONAL branch (``marginalize_over_inclination=False``: star s at its own inclination i_s) of the ensemble
     log-likelihood and its gradient in ONE device sweep per evaluation -- what ``ensemble_gradient_conditional`` computes
     star by star through the autograd graph, for the whole batch at once (sp_lnlike_grad_conditional).
@@ -698,40 +715,13 @@ class EnsembleGradientConditional(object):
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim != 2:
             raise ValueError("flux must be (S, K)")
-        S, K = flux.shape
-        if K < 2:
-            raise ValueError("at least two cadences")
-        import torch
-
-        from .engine import make_stars
-
-        t = np.asarray(t, dtype=np.float64)
-        t = np.broadcast_to(t, (S, K)) if t.ndim == 1 else t
-        udeg = defaults["udeg"]
-        per = lambda x: np.broadcast_to(np.asarray(x, dtype=np.float64), (S,))          # noqa: E731
-        uu = np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
-        if uu.ndim == 1:
-            utab, table = uu[None, :udeg], np.zeros(S, dtype=np.int32)
-        else:
-            utab, table = np.unique(uu[:, :udeg], axis=0, return_inverse=True)
-            table = table.astype(np.int32).reshape(-1)
-        if np.any(per(p) < -1e-6):
-            raise ValueError("p out of bounds")
-        var = np.asarray(ferr, dtype=np.float64) ** 2
-        stars = make_stars(S, period=per(p), inc_deg=per(i), tau=float(tau) if tau else 0.0,
-                           baseline_var=per(baseline_var), baseline_mean=per(baseline_mean),
-                           data_var=per(var) if var.ndim < 2 else 0.0, table=table)
-        e = self._e = get_engine(ydeg, udeg, device)
-        self.S, self.K = S, K
-        self._t, self._flux = e.f64(np.ascontiguousarray(t)), e.f64(np.ascontiguousarray(flux))
-        self._diag = e.f64(np.ascontiguousarray(np.broadcast_to(var, (S, K)))) if var.ndim == 2 else None
-        self._stars = e.stars_to_device(stars)
-        self._rta1 = e.f64(e.rTA1L(utab))
-        self._temporal = (temporal_kernel if isinstance(temporal_kernel, str) else kernel_id(temporal_kernel)) if tau else None
+        # (the inclinations' bounds are not checked on this branch)
+        self._setup(t, flux, ferr, p, i, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel, device)
         self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
-        self._ws = e.grad_conditional_workspace(S, K)
+        self._ws = self._e.grad_conditional_workspace(self.S, self.K)
         self.lnlike = self.status = None
-        torch.cuda.synchronize(e.device)
+
+    _open = staticmethod(get_engine)
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=None):
         """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .}).
@@ -754,19 +744,11 @@ class EnsembleGradientConditional(object):
             normalized=self._normalized, workspace=self._ws)
         # the stars' adjoints added up (a reduction over the leading axis: no atomics, the same order every call)
         gmu, gSig = mubar.sum(dim=0), sigbar.sum(dim=0)
-        N = mu.shape[0]
-        eps = torch.full((N,), float(self._ukw.get("epsy", defaults["epsy"])), dtype=torch.float64, device=e.device)
-        eps[15 ** 2:] = float(self._ukw.get("epsy15", defaults["epsy15"]))
+        eps = _upstream_eps(mu.shape[0], self._ukw, like=mu)
         g_rab = dmu @ gmu + (dSig * gSig).sum(dim=(1, 2))
-        if c != 0 and n != 0:
-            # mu ~ c n, Sigma - eps ~ c^2 n (contrast.py:21-33)
-            gm, gS = torch.dot(gmu, mu), (gSig * (Sig - torch.diag(eps))).sum()
-            g_c, g_n = gm / c + 2.0 * gS / c, gm / n + gS / n
-        else:
-            # the boundary rule of ensemble_gradient_conditional: the moments at unit contrast and unit number of spots
-            m1, Sig1 = ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)
-            gm, gS = torch.dot(gmu, m1), (gSig * (Sig1 - torch.diag(eps))).sum()
-            g_c, g_n = n * gm + 2.0 * c * n * gS, c * gm + c * c * gS
+        inner = lambda m_, S_: (torch.dot(gmu, m_), (gSig * (S_ - torch.diag(eps))).sum())          # noqa: E731
+        g_c, g_n = _cn_chain(*inner(mu, Sig), c, n, unit=lambda: inner(
+            *ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)))
         # ONE transfer: [gradient | per-star values | per-star status | per-star derivatives]
         host = torch.cat([g_rab, torch.stack([g_c, g_n]), lnl, status.to(torch.float64), sbar.reshape(-1)]).cpu().numpy()
         S = self.S

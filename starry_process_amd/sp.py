@@ -25,10 +25,11 @@ unimplemented (joss/paper.md:160-172).
 import numpy as np
 
 from .defaults import defaults
-from .engine import get_engine, make_stars
+from .engine import get_engine
 from .flux import FluxIntegral
 from .ops import AlphaBetaOp, CheckBoundsOp, Eager, _is_torch
 from .pixel import latlon_to_xyz, mollweide_grid
+from .stars import check_period_inclination, ensemble_stars, make_stars
 from .temporal import kernel_id
 
 __all__ = ["StarryProcess", "StarryProcessSum"]
@@ -799,40 +800,9 @@ class StarryProcess(object):
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim != 2:
             raise ValueError("`flux` must be (S, K)")
-        S, K = flux.shape
-        t = np.asarray(t, dtype=np.float64)
-        if t.shape not in ((K,), (S, K)):
-            raise ValueError("`t` must be (K,) or (S, K) like `flux` (%d, %d), not %s" % (S, K, t.shape))
-        t = np.ascontiguousarray(np.broadcast_to(t, (S, K)) if t.ndim == 1 else t)
-        p = np.broadcast_to(np.asarray(defaults["p"] if p is None else p, dtype=np.float64), (S,))
-        i = np.broadcast_to(np.asarray(defaults["i"] if i is None else i, dtype=np.float64), (S,))
-        if np.any(p < -1e-6):
-            raise ValueError("p out of bounds")
-        if np.any(i * np.pi / 180 < -1e-6) or np.any(i * np.pi / 180 > 0.5 * np.pi + 1e-6):
-            raise ValueError("i out of bounds")
-        u = np.asarray(defaults["u"][: self._udeg] if u is None else u, dtype=np.float64)
-        if u.ndim == 1:
-            utab, table = u[None, : self._udeg], np.zeros(S, dtype=np.int32)
-        elif u.ndim == 2 and u.shape[0] == S:
-            utab, table = np.unique(u[:, : self._udeg], axis=0, return_inverse=True)
-            table = table.astype(np.int32).reshape(-1)
-        else:
-            raise ValueError("`u` must be (udeg,) or (S, udeg)")
-        data_cov = np.asarray(data_cov, dtype=np.float64)
-        diag = None
-        dvar = 0.0
-        if data_cov.ndim == 2:
-            if data_cov.shape != (S, K):
-                raise ValueError("a 2-D `data_cov` must be (S, K) like `flux` (%d, %d), not %s" % (S, K, data_cov.shape))
-            diag = np.ascontiguousarray(data_cov)
-        elif data_cov.ndim <= 1 and data_cov.size in (1, S):
-            dvar = np.broadcast_to(data_cov.reshape(-1) if data_cov.ndim else data_cov, (S,))
-        else:
-            raise ValueError("`data_cov` must be a scalar, (S,) or (S, K)")
-        stars = make_stars(S, period=p, inc_deg=i, tau=self._tau,
-                           baseline_var=np.broadcast_to(np.asarray(baseline_var, float), (S,)),
-                           baseline_mean=np.broadcast_to(np.asarray(baseline_mean, float), (S,)),
-                           data_var=dvar, table=table, nobs=nobs)
+        check_period_inclination(p, i)
+        t, stars, utab, diag = ensemble_stars(flux.shape, t, p, i, u, self._udeg, baseline_mean, baseline_var, data_cov,
+                                              tau=self._tau, nobs=nobs)
         return t, flux, stars, utab, diag
 
     def ylm_conditional_ensemble(self, t, flux, data_cov, i=None, p=None, u=None, baseline_mean=0.0,

@@ -1,0 +1,167 @@
+"""
+Host side of the batched calls (NumPy only): the ``sp_star`` records of an ensemble of light curves and the parameter
+rows of a batch of hyperparameter samples.  Every batched front end -- ``StarryProcess``'s ensemble methods,
+``calibrate.EnsembleLogProb``, the two ensemble gradients of ``grad.py`` -- builds its records here; ``engine.py``
+re-exports the names.
+"""
+import numpy as np
+
+from ._lib import STAR_DTYPE
+from .defaults import defaults
+
+__all__ = ["make_stars", "ensemble_stars", "check_period_inclination", "stars_for_samples", "sample_parameters",
+           "samples_in_bounds"]
+
+
+def make_stars(S, period=1.0, inc_deg=60.0, tau=0.0, baseline_var=0.0,
+               baseline_mean=0.0, data_var=0.0, table=0, nobs=0):
+    """Structured host array of ``sp_star`` (inclination converted to radians,
+    flux.py:236-238).  ``nobs``: valid cadences per star for ragged ensembles (0 = all)."""
+    st = np.zeros(S, dtype=STAR_DTYPE)
+    st["period"] = period
+    st["inc"] = np.asarray(inc_deg, dtype=float) * (np.pi / 180)
+    st["tau"] = tau
+    st["baseline_var"] = baseline_var
+    st["baseline_mean"] = baseline_mean
+    st["data_var"] = data_var
+    st["table"] = table
+    st["nobs"] = nobs
+    return st
+
+
+def check_period_inclination(p, i=None):
+    """The reference's bounds on the periods and, where given, the inclinations [degrees] of an ensemble (CheckBoundsOp's
+    tolerance): ValueError outside.  ``None`` stands for the default, which is inside."""
+    if p is not None and np.any(np.asarray(p, dtype=np.float64) < -1e-6):
+        raise ValueError("p out of bounds")
+    if i is not None:
+        i = np.asarray(i, dtype=np.float64)
+        if np.any(i * np.pi / 180 < -1e-6) or np.any(i * np.pi / 180 > 0.5 * np.pi + 1e-6):
+            raise ValueError("i out of bounds")
+
+
+def ensemble_stars(flux_shape, t, p, i, u, udeg, baseline_mean, baseline_var, data_var, tau=0.0, nobs=0):
+    """Inputs of the ensemble calls, checked against flux's (S, K) shape: (t (S, K) contiguous, the star records, the
+    distinct limb-darkening sets utab, the per-cadence variances diag ((S, K) or None)).
+
+    t: (K,) or (S, K); p, i [degrees], baseline_mean, baseline_var: scalars or (S,), ``None`` for p or i being the
+    default; u: (udeg,) shared or (S, udeg), ``None`` the default -- the stars' ``table`` indexes the rows of utab;
+    data_var: a scalar or (S,) goes to the records, (S, K) comes back as diag with the records' variance 0.  No bounds
+    are checked here (``check_period_inclination``)."""
+    S, K = flux_shape
+    t = np.asarray(t, dtype=np.float64)
+    if t.shape not in ((K,), (S, K)):
+        raise ValueError("`t` must be (K,) or (S, K) like `flux` (%d, %d), not %s" % (S, K, t.shape))
+    t = np.ascontiguousarray(np.broadcast_to(t, (S, K)) if t.ndim == 1 else t)
+
+    def per(x):
+        return np.broadcast_to(np.asarray(x, dtype=np.float64), (S,))
+
+    u = np.asarray(defaults["u"][:udeg] if u is None else u, dtype=np.float64)
+    if u.ndim == 1:
+        utab, table = u[None, :udeg], np.zeros(S, dtype=np.int32)
+    elif u.ndim == 2 and u.shape[0] == S:
+        utab, table = np.unique(u[:, :udeg], axis=0, return_inverse=True)
+        table = table.astype(np.int32).reshape(-1)
+    else:
+        raise ValueError("`u` must be (udeg,) or (S, udeg)")
+    data_var = np.asarray(data_var, dtype=np.float64)
+    diag = None
+    dvar = 0.0
+    if data_var.ndim == 2:
+        if data_var.shape != (S, K):
+            raise ValueError("a 2-D `data_cov` must be (S, K) like `flux` (%d, %d), not %s" % (S, K, data_var.shape))
+        diag = np.ascontiguousarray(data_var)
+    elif data_var.ndim <= 1 and data_var.size in (1, S):
+        dvar = per(data_var.reshape(-1) if data_var.ndim else data_var)
+    else:
+        raise ValueError("`data_cov` must be a scalar, (S,) or (S, K)")
+    stars = make_stars(S, period=per(defaults["p"] if p is None else p), inc_deg=per(defaults["i"] if i is None else i),
+                       tau=tau, baseline_var=per(baseline_var), baseline_mean=per(baseline_mean), data_var=dvar,
+                       table=table, nobs=nobs)
+    return t, stars, utab, diag
+
+
+def stars_for_samples(stars, B, ntab, baseline_mean=None, baseline_var=None, period=None, inc_deg=None, tau=None,
+                      own_tables=True):
+    """The sp_star array of a batch of B hyperparameter samples x S stars (sample-major: system b S + s): the S stars
+    repeated B times with table = b ntab + table_s, the kernel table of sample b for the star's flux operator
+    (sp_kernel_table_samples' numbering).  ``baseline_mean`` / ``baseline_var`` [B]: the baseline terms of sample b
+    when they are free parameters of the samples (calibrate/log_prob.py:24-47), for every star of that sample; ``period``,
+    ``inc_deg`` (degrees, stored in radians like make_stars) and ``tau`` [B] likewise: the rotation period, inclination
+    and timescale of sample b.  ``own_tables=False``: every sample keeps the stars' table indices (the conditional
+    branch, where ``table`` selects the flux operator and there are no per-sample tables)."""
+    stars = np.ascontiguousarray(stars)
+    assert stars.dtype == STAR_DTYPE
+    out = np.tile(stars, int(B))
+    if own_tables:
+        out["table"] = (np.repeat(np.arange(int(B), dtype=np.int64), stars.shape[0]) * int(ntab)
+                        + out["table"]).astype(np.int32)
+    for field, val in (("baseline_mean", baseline_mean), ("baseline_var", baseline_var), ("period", period),
+                       ("inc", inc_deg), ("tau", tau)):
+        if val is not None:
+            val = np.asarray(val, dtype=np.float64).reshape(-1)
+            if val.shape[0] != int(B):
+                raise ValueError("%s must have one entry per sample" % field)
+            out[field] = np.repeat(val * (np.pi / 180) if field == "inc" else val, stars.shape[0])
+    return out
+
+
+def samples_in_bounds(samples, tol=1e-6, dr=False):
+    """Boolean mask of the rows of samples [B, 5] = (r [degrees], a, b, c, n) inside the reference's bounds (r in [0, 90],
+    a, b in [0, 1], n >= 0, everything finite; size.py:68, latitude.py:176-197, contrast.py:21-33 through CheckBoundsOp's
+    tolerance): what ``sample_parameters`` raises ValueError for.  A sampler's walkers leave the box; the log-probability
+    callables can answer -inf for such rows instead of raising (``out_of_bounds="inf"``).  ``dr=True``: rows of
+    (r, dr [degrees], a, b, c, n), dr in [0, 90] (size.py:120-122)."""
+    sm = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+    ok = np.all(np.isfinite(sm), axis=1)
+    if dr:
+        d = sm[:, 1] * (np.pi / 180)
+        ok &= (d >= -tol) & (d <= 0.5 * np.pi + tol)
+        sm = np.delete(sm, 1, axis=1)
+    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
+    ok &= (r >= -tol) & (r <= 0.5 * np.pi + tol) & (a >= -tol) & (a <= 1 + tol) & (b >= -tol) & (b <= 1 + tol) & (n >= -tol)
+    return ok
+
+
+def sample_parameters(samples, dr=False, **kw):
+    """samples [B, 5] = (r [degrees], a, b, c, n) -> [B, 5] = (r [radians], alpha, beta, c, n), what
+    sp_polar_moments_samples takes: the reference's bounds (size.py:68, latitude.py:176-197, contrast.py:21-33 through
+    CheckBoundsOp: ValueError outside, tolerance 1e-6) and its (a, b) -> (alpha, beta) map, for the whole batch at once
+    (NumPy; one sample at a time ``upstream.ab_to_alphabeta`` does the same).  ``dr=True``: samples [B, 6] = (r, dr
+    [degrees], a, b, c, n) -> [B, 6] = (r, dr [radians], alpha, beta, c, n), what sp_polar_moments_samples_spread takes
+    (dr in [0, 90] degrees, size.py:120-122)."""
+    sm = np.array(np.atleast_2d(np.asarray(samples, dtype=np.float64)), dtype=np.float64)
+    if dr:
+        if sm.ndim != 2 or sm.shape[1] != 6:
+            raise ValueError("samples must be (B, 6): r, dr, a, b, c, n")
+        from .ops import CheckBoundsOp
+
+        d = sm[:, 1] * (np.pi / 180)
+        CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(d)
+        if not np.all(np.isfinite(d)):
+            raise ValueError("samples must be finite")
+        out = np.empty_like(sm)
+        out[:, [0, 2, 3, 4, 5]] = sample_parameters(np.delete(sm, 1, axis=1), **kw)
+        out[:, 1] = np.clip(d, 0.0, None)
+        return np.ascontiguousarray(out)
+    if sm.ndim != 2 or sm.shape[1] != 5:
+        raise ValueError("samples must be (B, 5): r, a, b, c, n")
+    r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
+    from .ops import CheckBoundsOp
+
+    for name, v, lo, hi in (("r", r, 0.0, 0.5 * np.pi), ("a", a, 0.0, 1.0), ("b", b, 0.0, 1.0), ("n", n, 0.0, np.inf)):
+        CheckBoundsOp(name=name, lower=lo, upper=hi)(v)
+    if not np.all(np.isfinite(sm)):
+        raise ValueError("samples must be finite")
+    abmin = kw.get("abmin", defaults["abmin"])
+    lam = kw.get("log_alpha_max", defaults["log_alpha_max"])
+    lbm = kw.get("log_beta_max", defaults["log_beta_max"])
+    a, b = np.maximum(a, abmin), np.maximum(b, abmin)
+    out = np.empty_like(sm)
+    out[:, 0] = np.clip(r, 0.0, None)
+    out[:, 1] = np.exp(a * lam)
+    out[:, 2] = np.exp(np.log(0.5) + b * (lbm - np.log(0.5)))
+    out[:, 3] = sm[:, 3]
+    out[:, 4] = np.clip(n, 0.0, None)
+    return np.ascontiguousarray(out)
