@@ -30,6 +30,7 @@ import numpy as np
 
 from .calibrate_generate import draw_spots, generate
 from .sp import StarryProcess
+from .stars import SampleColumns
 
 __all__ = ["get_log_prob", "get_log_prob_ensemble", "EnsembleLogProb", "SampleBatches", "MAX_STREAMS",
            "compute_inclination_pdf", "generate", "draw_spots"]
@@ -77,10 +78,9 @@ class SampleBatches(object):
     ``dr``: None (one spot radius), a float (radii uniform in [r - dr, r + dr] degrees, the same for every sample:
     StarryProcess(dr=...)) or "free" (a column of the samples); ``free``: which of ("baseline_mean",
     "baseline_log_var") are columns of the samples instead of fields of ``stars`` (calibrate/log_prob.py:24-47).  The
-    columns are r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]: the reference's order (calibrate/log_prob.py:93-102: the
-    inclination behind the baseline terms) with dr where the constructor has it and the two parameters of its
-    time-variability tutorial last.  With free terms every group's star array goes up through the pinned staging ring
-    into the slot's own device array (the likelihood step reads its stars on every call).
+    columns are r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]: ``stars.SampleColumns`` holds that layout.  With free
+    terms every group's star array goes up through the pinned staging ring into the slot's own device array (the
+    likelihood step reads its stars on every call).
 
     ``free`` may also name "i" (inclination in degrees; conditional only), "p" (period) and "tau" (timescale; needs a
     temporal kernel), which become fields of sample b's stars.  Three routes:
@@ -91,18 +91,13 @@ class SampleBatches(object):
         (the plan fixes period and timescale).
       * marginal otherwise: the planned path described above, unchanged."""
 
-    FREE = ("baseline_mean", "baseline_log_var", "i", "p", "tau")
-    _NAMES = {"baseline_mean": "m", "baseline_log_var": "v", "i": "i", "p": "p", "tau": "tau"}
-
     def __init__(self, slots, t_dev, flux_dev, stars, rta1_dev, covpts, diag_dev=None, temporal=None, group=None,
                  norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None, dr=None, free=(), conditional=False,
                  normalized=True):
         import torch
 
-        self.columns, self._free = self.column_names(dr=dr, free=free, conditional=conditional, temporal=temporal)
-        if dr is not None and not isinstance(dr, str):
-            dr = float(dr)
-        self._dr = dr
+        self._cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal)
+        self.columns, self._free, self._dr = self._cols.columns, self._cols.free, self._cols.dr
         self._conditional, self._normalized, self._temporal = bool(conditional), bool(normalized), temporal
         if not self._normalized and not self._conditional:
             raise ValueError("the marginal branch is batched in its normalised form only")
@@ -153,22 +148,8 @@ class SampleBatches(object):
     def column_names(cls, dr=None, free=(), conditional=False, temporal=None):
         """(columns, free in column order) of the samples for these settings; ValueError for settings that name no batch
         (needs no device)."""
-        free = (free,) if isinstance(free, str) else tuple(free)
-        if len(set(free)) != len(free) or any(f not in cls.FREE for f in free):
-            raise ValueError("free must be a subset of %r" % (cls.FREE,))
-        if isinstance(dr, str):
-            if dr != "free":
-                raise ValueError("dr must be None, a number or 'free'")
-        elif dr is not None:
-            from .ops import CheckBoundsOp
-
-            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(float(dr) * (np.pi / 180))
-        if "i" in free and not conditional:
-            raise ValueError("a free inclination needs conditional=True: the marginal branch integrates over it")
-        if "tau" in free and temporal is None:
-            raise ValueError("a free tau needs a temporal kernel")
-        free = tuple(f for f in cls.FREE if f in free)
-        return ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + tuple(cls._NAMES[f] for f in free), free
+        cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal)
+        return cols.columns, cols.free
 
     def _group_stars(self, **fields):
         """The star array of one group; in the conditional branch ``table`` stays the star's flux operator."""
@@ -189,18 +170,7 @@ class SampleBatches(object):
         raw = e0.empty(ngroups, g * S)
         if ns < ngroups * g:          # (the last group is filled up with its own last sample; those values are dropped)
             samples = np.vstack([samples, np.repeat(samples[-1:], ngroups * g - ns, axis=0)])
-        new = self._dr is not None or bool(self._free) or not self._planned
-        if new:
-            c0 = 2 if self._dr == "free" else 1
-            drv = samples[:, 1] if self._dr == "free" else self._dr
-            hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
-            col = c0 + 4
-            cols = {}
-            for f, key in (("baseline_mean", "baseline_mean"), ("baseline_log_var", "baseline_var"), ("i", "inc_deg"),
-                           ("p", "period"), ("tau", "tau")):
-                if f in self._free:
-                    cols[key] = 10.0 ** samples[:, col] if f == "baseline_log_var" else samples[:, col]
-                    col += 1
+        hyper, dr, fields = self._cols.split(samples)
         cur = torch.cuda.current_stream(e0.device)
         start = torch.cuda.Event()
         start.record(cur)
@@ -224,17 +194,14 @@ class SampleBatches(object):
                     if stagger is not None:
                         stream.wait_event(stagger)
                 stars_d = self._stars
-                if not new:
-                    e.polar_moments_samples(samples[gi * g:(gi + 1) * g], ez=b["ez"], Ez=b["Ez"], **self._ukw)
+                sl = slice(gi * g, (gi + 1) * g)
+                drs = dr[sl] if self._cols.dr_free else dr
+                if self._conditional:
+                    e.ylm_moments_samples(hyper[sl], mean=b["mu"], cov=b["cov"], dr=drs, **self._ukw)
                 else:
-                    sl = slice(gi * g, (gi + 1) * g)
-                    drs = drv[sl] if self._dr == "free" else drv
-                    if self._conditional:
-                        e.ylm_moments_samples(hyper[sl], mean=b["mu"], cov=b["cov"], dr=drs, **self._ukw)
-                    else:
-                        e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"], dr=drs, **self._ukw)
-                    if self._free:
-                        stars_d = e.stars_staged(self._group_stars(**{k: v[sl] for k, v in cols.items()}), b["stars"])
+                    e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"], dr=drs, **self._ukw)
+                if self._free:
+                    stars_d = e.stars_staged(self._group_stars(**{k: v[sl] for k, v in fields.items()}), b["stars"])
                 if not self._conditional:
                     e.kernel_table_samples(b["ez"], b["Ez"], self._rta1, self._covpts, tab=b["tab"], meanvar=b["mv"])
                 if gi + 1 < min(ngroups, len(self._slots)):
@@ -397,9 +364,9 @@ class EnsembleLogProb(object):
         from .engine import engine_slots
         from .stars import check_period_inclination, ensemble_stars
 
-        self.columns, self._free = SampleBatches.column_names(dr=dr, free=[
+        self._cols = SampleColumns(dr=dr, free=[
             name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var)) if val is None])
-        self._dr = dr if dr is None or isinstance(dr, str) else float(dr)
+        self.columns, self._free, self._dr = self._cols.columns, self._cols.free, self._cols.dr
         baseline_mean = 0.0 if baseline_mean is None else baseline_mean            # (placeholders: overwritten per sample)
         baseline_log_var = 0.0 if baseline_log_var is None else baseline_log_var
         flux = np.asarray(flux, dtype=np.float64)
@@ -475,17 +442,15 @@ class EnsembleLogProb(object):
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
         if samples.shape[1] != len(self.columns):
             raise ValueError("samples must be (n, %d): %s" % (len(self.columns), ", ".join(self.columns)))
-        nh = 6 if self._dr == "free" else 5            # r[, dr], a, b, c, n: the columns with bounds
         if self._oob == "inf":
-            from .engine import samples_in_bounds
-
-            ok = samples_in_bounds(samples[:, :nh], dr=self._dr == "free") & np.all(np.isfinite(samples), axis=1)
+            ok = self._cols.in_bounds(samples)
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
                     out[ok] = self(samples[ok])
                 return out
         ns, nl = samples.shape[0], self._n_local
+        hyper, drs, fields = self._cols.split(samples)
         e0 = self._slots[0][0]
         outs = e0.empty(ns, max(nl, 1))
         torch.cuda.synchronize(e0.device)
@@ -494,17 +459,13 @@ class EnsembleLogProb(object):
         elif nl:
             eu, su = self._up
             keep = []                                   # (the moments stay alive until the batch is done)
-            for k, row in enumerate(samples):
-                r, (a, b, c, n) = row[0], row[nh - 4:nh]
-                dr = row[1] if self._dr == "free" else self._dr
+            for k, (r, a, b, c, n) in enumerate(hyper):
+                dr = drs[k] if self._cols.dr_free else drs
                 stars_d = self._stars
                 if self._free:
                     st = self._stars_host.copy()
-                    col = nh
-                    if "baseline_mean" in self._free:
-                        st["baseline_mean"], col = row[col], col + 1
-                    if "baseline_log_var" in self._free:
-                        st["baseline_var"] = 10.0 ** row[col]
+                    for field, v in fields.items():          # (baseline_mean, baseline_var: the fields' own names)
+                        st[field] = v[k]
                     stars_d = eu.stars_to_device(st)
                     keep.append(stars_d)
                 e, stream = self._slots[k % len(self._slots)]
@@ -542,7 +503,7 @@ class EnsembleLogProb(object):
         if self._apply_jac:
             from .upstream import log_jac_samples
 
-            total = total + log_jac_samples(samples[:, nh - 4], samples[:, nh - 3])
+            total = total + log_jac_samples(hyper[:, 1], hyper[:, 2])
         return total
 
 
@@ -597,19 +558,19 @@ def compute_inclination_pdf(t, flux, ferr, period, samples, inc=np.linspace(0, 9
         raise ValueError("`flux` must be (nlc, K) like `t`")
     inc = np.asarray(inc, dtype=np.float64).reshape(-1)
     samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-    nfree = 5 + (baseline_mean is None) + (baseline_log_var is None)
-    if samples.shape[1] != nfree:
-        raise ValueError("samples must have %d columns: r, a, b, c, n%s%s" % (
-            nfree, ", m" if baseline_mean is None else "", ", v" if baseline_log_var is None else ""))
+    cols = SampleColumns(free=[
+        name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var)) if val is None])
+    if samples.shape[1] != len(cols.columns):
+        raise ValueError("samples must have %d columns: %s" % (len(cols.columns), ", ".join(cols.columns)))
     equal, idx = inclination_sample_indices(samples.shape[0], nlc, ninc_samples, weights, seed)
     if equal is not None:
         samples = samples[equal]
     used, sel = np.unique(idx.reshape(-1), return_inverse=True)
-    sm = samples[used]
+    hyper, _, fields = cols.split(samples[used])
     e = get_engine(ydeg, 2, device)
     means, covs, jac = [], [], np.zeros(used.shape[0])
-    for b_, row in enumerate(sm):
-        r, a, b, c, n = (float(x) for x in row[:5])
+    for b_, row in enumerate(hyper):
+        r, a, b, c, n = (float(x) for x in row)
         if upstream == "device":
             from .upstream_device import ylm_moments_device
 
@@ -629,11 +590,11 @@ def compute_inclination_pdf(t, flux, ferr, period, samples, inc=np.linspace(0, 9
     mean_ylm, cov_ylm = torch.stack(means), torch.stack(covs)
     # one system per (light curve, draw): its own baseline terms when they are free parameters
     S = nlc * int(ninc_samples)
-    col = 5
-    bm = np.full(used.shape[0], 0.0 if baseline_mean is None else float(baseline_mean))
-    if baseline_mean is None:
-        bm, col = sm[:, col], col + 1
-    bv = 10.0 ** (sm[:, col] if baseline_log_var is None else np.full(used.shape[0], float(baseline_log_var)))
+    bm, bv = fields.get("baseline_mean"), fields.get("baseline_var")
+    if bm is None:
+        bm = np.full(used.shape[0], float(baseline_mean))
+    if bv is None:
+        bv = 10.0 ** np.full(used.shape[0], float(baseline_log_var))
     per = np.repeat(np.broadcast_to(np.asarray(period, dtype=np.float64), (nlc,)), int(ninc_samples))
     stars = make_stars(S, period=per, baseline_mean=bm[sel], baseline_var=bv[sel], data_var=float(ferr) ** 2)
     uu = np.asarray(u, dtype=np.float64).reshape(1, -1)

@@ -27,6 +27,7 @@
 // and 2e-11 in the weights over the reference's whole prior box (tests/test_gpu_samples.py).
 #include <cmath>
 #include <cstring>
+#include <optional>
 
 #include "sp_internal.h"
 
@@ -431,79 +432,16 @@ int sp_set_size_basis(sp_handle *h, const double *theta_host, const double *Bp_h
 
 }  // extern "C"
 
-// The two entry points' bodies.  central: the polar-frame covariance instead of the second moment (sm_finish_kernel);
-// extra > 0: that many more bytes of the handle's scratch behind the call's own, handed back in *extra_ptr -- ez_dev and
-// Ez_dev may then be null and are placed there: ez [B][N] | Ez [B][N][N] | one more [B][N][N] (sp_ylm_moments_samples).
-static int polar_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15, double *ez_dev,
-                         double *Ez_dev, void *stream, int central, size_t extra, void **extra_ptr) {
+// The three entry points' body.  SPREAD: rows of 6 (r, dr, alpha, beta, c, n) and the radius law's chain, else rows of 5;
+// central: the polar-frame covariance instead of the second moment (sm_finish_kernel); extra > 0: that many more bytes
+// of the handle's scratch behind the call's own, handed back in *extra_ptr -- ez_dev and Ez_dev may then be null and are
+// placed there: ez [B][N] | Ez [B][N][N] | one more [B][N][N] (sp_ylm_moments_samples).
+template <bool SPREAD>
+static int polar_samples(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy, double epsy15,
+                         double *ez_dev, double *Ez_dev, void *stream, int central, size_t extra, void **extra_ptr) {
+  constexpr int NS = SPREAD ? 6 : 5;
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !samples_host || (!extra && (!ez_dev || !Ez_dev)) || B < 0 || B > 65535) return SP_ERR_INVALID;
-  if (!h->d_size_basis) return SP_ERR_STATE;
-  if (B == 0) return SP_OK;
-  const int N = h->N, nl = h->ydeg + 1, nq = h->ydeg + 2, P = 2 * nq, spts = h->size_spts;
-  if (P > SM_TK) return SP_ERR_INVALID;
-  for (int b = 0; b < B; ++b) {
-    const double *s = samples_host + 5 * (size_t)b;
-    // r in [0, pi/2], alpha, beta > 0 (Beta law), c finite, n >= 0 (size.py:68, latitude.py:176-197, contrast.py:21-33)
-    if (!(s[0] >= 0.0 && s[0] <= 1.5707963267948966 + 1e-6) || !(s[1] > 0.0) || !(s[2] > 0.0) || !std::isfinite(s[1]) ||
-        !std::isfinite(s[2]) || !std::isfinite(s[3]) || !(s[4] >= 0.0) || !std::isfinite(s[4]))
-      return SP_ERR_INVALID;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  SP_HIP(hipSetDevice(h->device));
-  // scratch: svec [B][nl] | cs [B nq][2] | sc [B][2][P] | scal [B][4] | T [B][N][64] | M [B][N][N] | e1 [B][N]
-  const size_t d = sizeof(double);
-  SpCarve c;
-  const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
-               oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N);
-  const size_t oX = c.take(extra);
-  void *ws = nullptr;
-  int rc = sp_ensure_scratch(h->big, c.off, &ws);
-  if (rc) return rc;
-  if (extra) {
-    *extra_ptr = at<void>(ws, oX);
-    ez_dev = at<double>(ws, oX);
-    Ez_dev = ez_dev + sp_align_up(d * B * N) / d;
-  }
-  double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
-         *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE);
-  const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);      // (+ 256 ints of flags)
-  if (lds1 > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-  {
-    // ONE staged upload: the samples (read by sm_prepare_kernel only)
-    SpStage stage(h, 5 * (size_t)B);
-    if (stage.rc) return stage.rc;
-    memcpy(stage.host, samples_host, sizeof(double) * 5 * B);
-    const double *samp = stage.upload(st);
-    if (!samp) return SP_ERR_HIP;
-    hipLaunchKernelGGL(sm_prepare_kernel<false>, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, 0.0,
-                       h->d_size_basis, samp, svec, (double *)nullptr, cs, sc, scal);
-    SP_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
-                     svec, cs, h->d_Rx90, sc, T);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(sm_first_kernel<false>, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1, nl,
-                     (const int32_t *)nullptr, (const double *)nullptr, (const double *)nullptr, (const double *)nullptr, 0.0,
-                     0, (const double *)nullptr, (double *)nullptr);
-  SP_LAUNCH_CHECK();
-  if ((rc = sp_launch_gemm_nt(T, SM_TK, (long)N * SM_TK, T, SM_TK, (long)N * SM_TK, M, N, (long)N * N, N, N, SM_TK, 1.0, 0,
-                              0, B, st)))
-    return rc;
-  hipLaunchKernelGGL(sm_finish_kernel<false>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
-                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, (const int32_t *)nullptr,
-                     (const double *)nullptr, central);
-  SP_LAUNCH_CHECK();
-  return SP_OK;
-}
-
-static int polar_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
-                                double epsy15, double *ez_dev, double *Ez_dev, void *stream, int central, size_t extra,
-                                void **extra_ptr) {
-  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !samples_host || (!extra && (!ez_dev || !Ez_dev)) || B < 0 || B > 65535 || !(cutoff > 0.0))
+  if (!h || !samples_host || (!extra && (!ez_dev || !Ez_dev)) || B < 0 || B > 65535 || (SPREAD && !(cutoff > 0.0)))
     return SP_ERR_INVALID;
   if (!h->d_size_basis) return SP_ERR_STATE;
   if (B == 0) return SP_OK;
@@ -511,23 +449,27 @@ static int polar_samples_spread(sp_handle *h, int B, const double *samples_host,
   if (P > SM_TK) return SP_ERR_INVALID;
   bool any_spread = false;
   for (int b = 0; b < B; ++b) {
-    const double *s = samples_host + 6 * (size_t)b;
-    // r, dr in [0, pi/2] (size.py:103-122), then as sp_polar_moments_samples
-    if (!(s[0] >= 0.0 && s[0] <= 1.5707963267948966 + 1e-6) || !(s[1] >= 0.0 && s[1] <= 1.5707963267948966 + 1e-6) ||
-        !(s[2] > 0.0) || !(s[3] > 0.0) || !std::isfinite(s[2]) || !std::isfinite(s[3]) || !std::isfinite(s[4]) ||
-        !(s[5] >= 0.0) || !std::isfinite(s[5]))
+    const double *s = samples_host + NS * (size_t)b, *q = s + NS - 4;
+    // r in [0, pi/2], alpha, beta > 0 (Beta law), c finite, n >= 0 (size.py:68, latitude.py:176-197, contrast.py:21-33);
+    // dr in [0, pi/2] (size.py:103-122)
+    if (!(s[0] >= 0.0 && s[0] <= 1.5707963267948966 + 1e-6) ||
+        (SPREAD && !(s[1] >= 0.0 && s[1] <= 1.5707963267948966 + 1e-6)) || !(q[0] > 0.0) || !(q[1] > 0.0) ||
+        !std::isfinite(q[0]) || !std::isfinite(q[1]) || !std::isfinite(q[2]) || !(q[3] >= 0.0) || !std::isfinite(q[3]))
       return SP_ERR_INVALID;
-    any_spread = any_spread || s[1] > 0.0;
+    any_spread = any_spread || (SPREAD && s[1] > 0.0);
   }
   hipStream_t st = (hipStream_t)stream;
   SP_HIP(hipSetDevice(h->device));
-  // scratch: as sp_polar_moments_samples, then evec [B][nl] | Et [B][nl][nl] | part [B][nblk][nl][nl]
+  // scratch: svec [B][nl] | cs [B nq][2] | sc [B][2][P] | scal [B][4] | T [B][N][64] | M [B][N][N] | e1 [B][N], then with
+  // SPREAD (and only then: the one-radius call's scratch holds no more than its own seven regions)
+  // evec [B][nl] | Et [B][nl][nl] | part [B][nblk][nl][nl]
   const int nblk = (spts + SM_SJ - 1) / SM_SJ;
   const size_t d = sizeof(double);
   SpCarve c;
   const size_t oS = c.take(d * B * nl), oC = c.take(d * B * nq * 2), oSc = c.take(d * B * 2 * P), oSl = c.take(d * B * 4),
                oT = c.take(d * B * N * SM_TK), oM = c.take(d * B * N * N), oE = c.take(d * B * N),
-               oV = c.take(d * B * nl), oEt = c.take(d * B * nl * nl), oP = c.take(d * B * nblk * nl * nl);
+               oV = SPREAD ? c.take(d * B * nl) : 0, oEt = SPREAD ? c.take(d * B * nl * nl) : 0,
+               oP = SPREAD ? c.take(d * B * nblk * nl * nl) : 0;
   const size_t oX = c.take(extra);
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, c.off, &ws);
@@ -538,46 +480,50 @@ static int polar_samples_spread(sp_handle *h, int B, const double *samples_host,
     Ez_dev = ez_dev + sp_align_up(d * B * N) / d;
   }
   double *svec = at<double>(ws, oS), *cs = at<double>(ws, oC), *sc = at<double>(ws, oSc), *scal = at<double>(ws, oSl),
-         *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE), *evec = at<double>(ws, oV),
-         *Et = at<double>(ws, oEt), *part = at<double>(ws, oP);
-  const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);
+         *T = at<double>(ws, oT), *M = at<double>(ws, oM), *e1 = at<double>(ws, oE),
+         *evec = SPREAD ? at<double>(ws, oV) : nullptr, *Et = SPREAD ? at<double>(ws, oEt) : nullptr,
+         *part = SPREAD ? at<double>(ws, oP) : nullptr;
+  const int32_t *l_of = SPREAD ? h->d_l_of : nullptr;
+  const size_t lds1 = sizeof(double) * ((size_t)spts + 4 * nq + 128);      // (+ 256 ints of flags)
   if (lds1 > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel<true>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(sm_prepare_kernel<SPREAD>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-  {
-    // ONE staged upload: the samples (read until sm_first_kernel: the scope covers the launches up to it)
-    SpStage stage(h, 6 * (size_t)B);
-    if (stage.rc) return stage.rc;
-    memcpy(stage.host, samples_host, sizeof(double) * 6 * B);
-    const double *samp = stage.upload(st);
-    if (!samp) return SP_ERR_HIP;
-    hipLaunchKernelGGL(sm_prepare_kernel<true>, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac, cutoff,
-                       h->d_size_basis, samp, svec, evec, cs, sc, scal);
-    SP_LAUNCH_CHECK();
-    if (any_spread) {
-      const dim3 grid(nblk, B), block(SM_SJ);
-      if (nl <= 8)
-        hipLaunchKernelGGL(sm_spread_kernel<8>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
-      else if (nl <= 16)
-        hipLaunchKernelGGL(sm_spread_kernel<16>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
-      else if (nl <= 24)
-        hipLaunchKernelGGL(sm_spread_kernel<24>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
-      else
-        hipLaunchKernelGGL(sm_spread_kernel<32>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
-      SP_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
-                       svec, cs, h->d_Rx90, sc, T);
-    SP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sm_first_kernel<true>, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1, nl, h->d_l_of, evec,
-                       samp, scal, h->size_sfac, nblk, part, Et);
+  // ONE staged upload: the samples.  The slot is given back (its done-event recorded) behind the last kernel that reads
+  // them: sm_prepare_kernel with one radius, sm_first_kernel with SPREAD
+  std::optional<SpStage> stage(std::in_place, h, NS * (size_t)B);
+  if (stage->rc) return stage->rc;
+  memcpy(stage->host, samples_host, sizeof(double) * NS * B);
+  const double *samp = stage->upload(st);
+  if (!samp) return SP_ERR_HIP;
+  hipLaunchKernelGGL(sm_prepare_kernel<SPREAD>, dim3(B), dim3(256), lds1, st, h->ydeg, spts, h->size_sfac,
+                     SPREAD ? cutoff : 0.0, h->d_size_basis, samp, svec, evec, cs, sc, scal);
+  SP_LAUNCH_CHECK();
+  if (!SPREAD) stage.reset();
+  if constexpr (SPREAD) if (any_spread) {      // (constexpr: the one-radius driver instantiates no spread kernel)
+    const dim3 grid(nblk, B), block(SM_SJ);
+    if (nl <= 8)
+      hipLaunchKernelGGL(sm_spread_kernel<8>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+    else if (nl <= 16)
+      hipLaunchKernelGGL(sm_spread_kernel<16>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+    else if (nl <= 24)
+      hipLaunchKernelGGL(sm_spread_kernel<24>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
+    else
+      hipLaunchKernelGGL(sm_spread_kernel<32>, grid, block, 0, st, nl, spts, h->size_sfac, h->d_size_basis, samp, scal, part);
     SP_LAUNCH_CHECK();
   }
+  hipLaunchKernelGGL(sm_rows_kernel, dim3(SM_TK, B), dim3(256), sizeof(double) * N, st, h->ydeg, N, P, h->d_l_of, h->d_blk,
+                     svec, cs, h->d_Rx90, sc, T);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(sm_first_kernel<SPREAD>, dim3(B), dim3(256), 0, st, N, P, h->d_m_of, sc, T, e1, nl, l_of, evec,
+                     SPREAD ? samp : nullptr, SPREAD ? scal : nullptr, SPREAD ? h->size_sfac : 0.0, SPREAD ? nblk : 0,
+                     part, Et);
+  SP_LAUNCH_CHECK();
+  stage.reset();
   if ((rc = sp_launch_gemm_nt(T, SM_TK, (long)N * SM_TK, T, SM_TK, (long)N * SM_TK, M, N, (long)N * N, N, N, SM_TK, 1.0, 0,
                               0, B, st)))
     return rc;
-  hipLaunchKernelGGL(sm_finish_kernel<true>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
-                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, h->d_l_of, Et, central);
+  hipLaunchKernelGGL(sm_finish_kernel<SPREAD>, dim3((unsigned)(((long)N * N + 255) / 256), B), dim3(256), 0, st, N,
+                     h->d_m_of, h->d_mirror, M, e1, scal, epsy, epsy15, ez_dev, Ez_dev, nl, l_of, Et, central);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -586,12 +532,12 @@ extern "C" {
 
 int sp_polar_moments_samples(sp_handle *h, int B, const double *samples_host, double epsy, double epsy15,
                              double *ez_dev, double *Ez_dev, void *stream) {
-  return polar_samples(h, B, samples_host, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
+  return polar_samples<false>(h, B, samples_host, 0.0, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
 }
 
 int sp_polar_moments_samples_spread(sp_handle *h, int B, const double *samples_host, double cutoff, double epsy,
                                     double epsy15, double *ez_dev, double *Ez_dev, void *stream) {
-  return polar_samples_spread(h, B, samples_host, cutoff, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
+  return polar_samples<true>(h, B, samples_host, cutoff, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
 }
 
 // The Ylm-frame moments of B samples: the polar-frame mean and COVARIANCE of the chain above (sm_finish_kernel,
@@ -608,9 +554,8 @@ int sp_ylm_moments_samples(sp_handle *h, int B, const double *samples_host, int 
   const int N = h->N;
   const size_t d = sizeof(double), nv = sp_align_up(d * B * N) / d, nm = sp_align_up(d * B * N * N) / d;
   void *xp = nullptr;
-  int rc = spread ? polar_samples_spread(h, B, samples_host, cutoff, epsy, epsy15, nullptr, nullptr, stream, 1,
-                                         d * (nv + 2 * nm), &xp)
-                  : polar_samples(h, B, samples_host, epsy, epsy15, nullptr, nullptr, stream, 1, d * (nv + 2 * nm), &xp);
+  int rc = (spread ? polar_samples<true> : polar_samples<false>)(h, B, samples_host, cutoff, epsy, epsy15, nullptr, nullptr,
+                                                                 stream, 1, d * (nv + 2 * nm), &xp);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const double *ez = static_cast<const double *>(xp), *Ep = ez + nv;

@@ -337,9 +337,12 @@ class Engine(object):
         self._size_basis_key = key
 
     def _sample_rows(self, samples, dr, **kw):
-        """(rows [B, 5] or, with ``dr``, [B, 6] as the sample kernels take them, B): ``sample_parameters`` of samples
-        [B, 5] with ``dr`` (None, a scalar or one value per sample) as their second column; hands the spot profile's
-        basis to the library on the way (set_size_basis)."""
+        """(rows [B, 5] or, with ``dr``, [B, 6] as the sample kernels take them, B, cutoff, epsy, epsy15):
+        ``sample_parameters`` of samples [B, 5] with ``dr`` (None, a scalar or one value per sample) as their second
+        column, then the three scalars the sample entry points take from ``kw``; hands the spot profile's basis to the
+        library on the way (set_size_basis)."""
+        from .defaults import defaults
+
         if dr is not None:
             sm5 = np.atleast_2d(np.asarray(samples, dtype=np.float64))
             if sm5.ndim != 2 or sm5.shape[1] != 5:
@@ -351,7 +354,8 @@ class Engine(object):
         else:
             sm = sample_parameters(samples, **kw)
         self.set_size_basis(**kw)
-        return sm, sm.shape[0]
+        return (sm, sm.shape[0], float(kw.get("cutoff", 1.5)), float(kw.get("epsy", defaults["epsy"])),
+                float(kw.get("epsy15", defaults["epsy15"])))
 
     def polar_moments_samples(self, samples, ez=None, Ez=None, dr=None, **kw):
         """samples [B, 5] = (r [degrees], a, b, c, n) per row, the argument order of the reference's log-probability
@@ -360,22 +364,18 @@ class Engine(object):
         (ValueError before anything is launched).  ``dr``: None (one spot radius), or the half-width of the uniform
         law of the radii in degrees, a scalar or one value per sample (StarryProcess(dr=...), size.py:109-125): one
         call of sp_polar_moments_samples_spread; a sample with dr = 0 is the one-radius case."""
-        from .defaults import defaults
-
-        sm, B = self._sample_rows(samples, dr, **kw)
+        sm, B, cutoff, epsy, epsy15 = self._sample_rows(samples, dr, **kw)
         if ez is None:
             ez = self.empty(B, self.N)
         if Ez is None:
             Ez = self.empty(B, self.N, self.N)
         assert tuple(ez.shape) == (B, self.N) and tuple(Ez.shape) == (B, self.N, self.N)
         if dr is not None:
-            check(self._L.sp_polar_moments_samples_spread(
-                self._h, B, hptr(sm), float(kw.get("cutoff", 1.5)), float(kw.get("epsy", defaults["epsy"])),
-                float(kw.get("epsy15", defaults["epsy15"])), self._p(ez), self._p(Ez), self._stream()))
-            return ez, Ez
-        check(self._L.sp_polar_moments_samples(
-            self._h, B, hptr(sm), float(kw.get("epsy", defaults["epsy"])), float(kw.get("epsy15", defaults["epsy15"])),
-            self._p(ez), self._p(Ez), self._stream()))
+            check(self._L.sp_polar_moments_samples_spread(self._h, B, hptr(sm), cutoff, epsy, epsy15, self._p(ez),
+                                                          self._p(Ez), self._stream()))
+        else:
+            check(self._L.sp_polar_moments_samples(self._h, B, hptr(sm), epsy, epsy15, self._p(ez), self._p(Ez),
+                                                   self._stream()))
         return ez, Ez
 
     def ylm_moments_samples(self, samples, mean=None, cov=None, dr=None, **kw):
@@ -383,18 +383,14 @@ class Engine(object):
         Ylm-frame moments of B hyperparameter samples in one library call (sp_ylm_moments_samples) -- what
         ``upstream_device.ylm_moments_device`` computes one sample at a time, and what the conditional branch reads.
         Bounds, ``dr`` and the keywords are polar_moments_samples'."""
-        from .defaults import defaults
-
-        sm, B = self._sample_rows(samples, dr, **kw)
+        sm, B, cutoff, epsy, epsy15 = self._sample_rows(samples, dr, **kw)
         if mean is None:
             mean = self.empty(B, self.N)
         if cov is None:
             cov = self.empty(B, self.N, self.N)
         assert tuple(mean.shape) == (B, self.N) and tuple(cov.shape) == (B, self.N, self.N)
-        check(self._L.sp_ylm_moments_samples(
-            self._h, B, hptr(sm), int(dr is not None), float(kw.get("cutoff", 1.5)),
-            float(kw.get("epsy", defaults["epsy"])), float(kw.get("epsy15", defaults["epsy15"])), self._p(mean),
-            self._p(cov), self._stream()))
+        check(self._L.sp_ylm_moments_samples(self._h, B, hptr(sm), int(dr is not None), cutoff, epsy, epsy15,
+                                             self._p(mean), self._p(cov), self._stream()))
         return mean, cov
 
     def kernel_table_samples(self, ez, Ez, rta1, covpts, tab=None, meanvar=None):

@@ -29,7 +29,7 @@ from .engine import get_engine
 from .flux import FluxIntegral
 from .ops import AlphaBetaOp, CheckBoundsOp, Eager, _is_torch
 from .pixel import latlon_to_xyz, mollweide_grid
-from .stars import check_period_inclination, ensemble_stars, make_stars
+from .stars import SampleColumns, check_period_inclination, ensemble_stars, ipt_in_bounds, make_stars  # noqa: F401
 from .temporal import kernel_id
 
 __all__ = ["StarryProcess", "StarryProcessSum"]
@@ -41,43 +41,10 @@ def _neg_inf_if_nan(x):
 
 
 def sample_columns(params, marginalize_over_inclination, time_variable):
-    """``log_likelihood_samples``' column names checked for a process of these settings: (params, the same names in the
-    batch's order r[, dr], a, b, c, n[, m][, v][, i][, p][, tau], whether dr is a column, the free terms in that order).
-    ValueError for an unknown or repeated name, a missing hyperparameter, "i" on a process that marginalises over the
-    inclination, "tau" on one built without a temporal kernel."""
-    params = tuple(params)
-    allowed = ("r", "dr", "a", "b", "c", "n", "baseline_mean", "baseline_log_var", "i", "p", "tau")
-    if (len(set(params)) != len(params) or any(q not in allowed for q in params)
-            or any(q not in params for q in ("r", "a", "b", "c", "n"))):
-        raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var, "
-                         "i, p, tau")
-    if "i" in params and marginalize_over_inclination:
-        raise ValueError("params names i, but this process marginalises over the inclination")
-    if "tau" in params and not time_variable:
-        raise ValueError("params names tau, but this process was built without a temporal kernel (tau=None)")
-    dr_free = "dr" in params
-    free = tuple(q for q in ("baseline_mean", "baseline_log_var", "i", "p", "tau") if q in params)
-    order = ("r",) + (("dr",) if dr_free else ()) + ("a", "b", "c", "n") + free
-    return params, order, dr_free, free
-
-
-def ipt_in_bounds(samples, order, tol=1e-6):
-    """Boolean mask of the rows whose "i", "p", "tau" columns (those that ``order`` names) lie inside the reference's
-    bounds: i in [0, 90] degrees and p >= 0 through CheckBoundsOp's tolerance (flux.py:233-254), tau > 0, all finite."""
-    samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-    ok = np.ones(samples.shape[0], dtype=bool)
-    for q in ("i", "p", "tau"):
-        if q in order:
-            v = samples[:, order.index(q)]
-            with np.errstate(invalid="ignore"):
-                if q == "i":
-                    inside = (v * (np.pi / 180) >= -tol) & (v * (np.pi / 180) <= 0.5 * np.pi + tol)
-                elif q == "p":
-                    inside = v >= -tol
-                else:
-                    inside = v > 0.0
-            ok &= np.isfinite(v) & inside
-    return ok
+    """``stars.SampleColumns.from_params`` as a tuple: (params, the same names in the batch's order, whether dr is a
+    column, the free terms in that order)."""
+    cols = SampleColumns.from_params(params, marginalize_over_inclination, time_variable)
+    return cols.params, cols.names, cols.dr_free, cols.free
 
 
 class StarryProcess(object):
@@ -338,26 +305,23 @@ class StarryProcess(object):
         f = self._flux
         t, i, p, u = f._ingest(t, i, p, u)
         K = t.shape[0]
-        params, order, dr_free, free = sample_columns(params, self._marginalize_over_inclination, self._time_variable)
+        cols = SampleColumns.from_params(params, self._marginalize_over_inclination, self._time_variable, dr=self._dr)
+        free = cols.free
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-        if samples.shape[1] != len(params):
-            raise ValueError("samples must be (ns, %d): %s" % (len(params), ", ".join(params)))
-        # the columns in SampleBatches' order: r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]
-        samples = np.ascontiguousarray(samples[:, [params.index(q) for q in order]])
-        nh = 6 if dr_free else 5
-        ok3 = ipt_in_bounds(samples, order)
-        if out_of_bounds == "raise" and not ok3.all():
-            raise ValueError("samples out of bounds: i in [0, 90] degrees, p >= 0, tau > 0")
+        if samples.shape[1] != len(cols.params):
+            raise ValueError("samples must be (ns, %d): %s" % (len(cols.params), ", ".join(cols.params)))
+        # the columns in the layout's own order (stars.SampleColumns)
+        samples = np.ascontiguousarray(samples[:, cols.permutation])
+        if out_of_bounds == "raise":
+            cols.check_ipt(samples)
         if out_of_bounds == "inf":
-            from .engine import samples_in_bounds
-
-            ok = samples_in_bounds(samples[:, :nh], dr=dr_free) & np.all(np.isfinite(samples), axis=1) & ok3
+            ok = cols.in_bounds(samples)
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
                     out[ok] = np.asarray(self.log_likelihood_samples(t, flux, data_cov, samples[ok], i=i, p=p, u=u,
                                                                      baseline_mean=baseline_mean, baseline_var=baseline_var,
-                                                                     depth=depth, params=order))
+                                                                     depth=depth, params=cols.names))
                 return Eager(out)
         elif out_of_bounds != "raise":
             raise ValueError("out_of_bounds must be 'raise' or 'inf'")
@@ -377,25 +341,16 @@ class StarryProcess(object):
                       marginalize_over_inclination=self._marginalize_over_inclination, normalized=self._normalized,
                       covpts=self._covpts, upstream="device")
             out = []
-            for row in samples:
-                r, (a, b, c, n) = row[0], row[nh - 4:nh]
-                col = nh
-                bm, bv = baseline_mean, baseline_var
-                if "baseline_mean" in free:
-                    bm, col = row[col], col + 1
-                if "baseline_log_var" in free:
-                    bv, col = 10.0 ** row[col], col + 1
-                ii, pp = i, p
-                if "i" in free:
-                    ii, col = row[col], col + 1
-                if "p" in free:
-                    pp, col = row[col], col + 1
-                if "tau" in free:
-                    kw["tau"] = row[col]
-                out.append(float(StarryProcess(r=r, dr=row[1] if dr_free else self._dr, a=a, b=b, c=c, n=n, **kw).log_likelihood(
-                    t, flux, data_cov, i=ii, p=pp, u=u, baseline_mean=bm, baseline_var=bv)))
+            hyper, drs, fields = cols.split(samples)
+            for k, (r, a, b, c, n) in enumerate(hyper):
+                at = {key: v[k] for key, v in fields.items()}        # (this sample's free terms over the arguments)
+                if "tau" in at:
+                    kw["tau"] = at["tau"]
+                out.append(float(StarryProcess(r=r, dr=drs[k] if cols.dr_free else drs, a=a, b=b, c=c, n=n, **kw).log_likelihood(
+                    t, flux, data_cov, i=at.get("inc_deg", i), p=at.get("period", p), u=u,
+                    baseline_mean=at.get("baseline_mean", baseline_mean), baseline_var=at.get("baseline_var", baseline_var))))
             return Eager(np.array(out))
-        dr = "free" if dr_free else (None if self._dr is None else float(self._dr))
+        dr = cols.dr
         key = (t.tobytes(), F.tobytes(), data_cov.tobytes(), float(p), float(i),
                tuple(np.asarray(u, dtype=float).reshape(-1)), float(bmean), float(bvar), int(depth), dr, free)
         cache = self.__dict__.get("_sample_batches")
@@ -408,14 +363,12 @@ class StarryProcess(object):
                                data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
             ukw = {k: self._kwargs[k] for k in ("epsy", "epsy15", "spts", "eps4", "smoothing", "sfac", "cutoff", "abmin",
                                                 "log_alpha_max", "log_beta_max") if k in self._kwargs}
-            extra = {} if dr is None and not free else dict(dr=dr, free=free)
-            if not self._marginalize_over_inclination:
-                extra.update(conditional=True, normalized=self._normalized)
             sb = SampleBatches(slots, e0.f64(t[None, :]), e0.f64(F[None, :, :]), stars,
                                e0.f64(e0.rTA1L(np.asarray(u, dtype=np.float64))), self._covpts,
                                diag_dev=e0.f64(data_cov.reshape(1, K)) if data_cov.ndim == 1 else None,
                                temporal=self._temporal, norm_order=self._normN, zmax=self._normzmax, upstream_kwargs=ukw,
-                               **extra)
+                               dr=dr, free=free, conditional=not self._marginalize_over_inclination,
+                               normalized=self._normalized)
             cache = self._sample_batches = (key, sb)
         out = cache[1](samples)
         import torch

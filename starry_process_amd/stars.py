@@ -1,8 +1,8 @@
 """
 Host side of the batched calls (NumPy only): the ``sp_star`` records of an ensemble of light curves and the parameter
-rows of a batch of hyperparameter samples.  Every batched front end -- ``StarryProcess``'s ensemble methods,
-``calibrate.EnsembleLogProb``, the two ensemble gradients of ``grad.py`` -- builds its records here; ``engine.py``
-re-exports the names.
+rows of a batch of hyperparameter samples, whose column layout ``SampleColumns`` alone knows.  Every batched front end
+-- ``StarryProcess``'s ensemble methods, ``calibrate.EnsembleLogProb``, the two ensemble gradients of ``grad.py`` --
+builds its records here; ``engine.py`` re-exports the names.
 """
 import numpy as np
 
@@ -10,7 +10,7 @@ from ._lib import STAR_DTYPE
 from .defaults import defaults
 
 __all__ = ["make_stars", "ensemble_stars", "check_period_inclination", "stars_for_samples", "sample_parameters",
-           "samples_in_bounds"]
+           "samples_in_bounds", "ipt_in_bounds", "SampleColumns"]
 
 
 def make_stars(S, period=1.0, inc_deg=60.0, tau=0.0, baseline_var=0.0,
@@ -122,6 +122,109 @@ def samples_in_bounds(samples, tol=1e-6, dr=False):
     r, a, b, n = sm[:, 0] * (np.pi / 180), sm[:, 1], sm[:, 2], sm[:, 4]
     ok &= (r >= -tol) & (r <= 0.5 * np.pi + tol) & (a >= -tol) & (a <= 1 + tol) & (b >= -tol) & (b <= 1 + tol) & (n >= -tol)
     return ok
+
+
+def ipt_in_bounds(samples, order, tol=1e-6):
+    """Boolean mask of the rows whose "i", "p", "tau" columns (those that ``order`` names) lie inside the reference's
+    bounds: i in [0, 90] degrees and p >= 0 through CheckBoundsOp's tolerance (flux.py:233-254), tau > 0, all finite."""
+    samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+    ok = np.ones(samples.shape[0], dtype=bool)
+    for q in ("i", "p", "tau"):
+        if q in order:
+            v = samples[:, order.index(q)]
+            with np.errstate(invalid="ignore"):
+                if q == "i":
+                    inside = (v * (np.pi / 180) >= -tol) & (v * (np.pi / 180) <= 0.5 * np.pi + tol)
+                elif q == "p":
+                    inside = v >= -tol
+                else:
+                    inside = v > 0.0
+            ok &= np.isfinite(v) & inside
+    return ok
+
+
+class SampleColumns(object):
+    """The columns of a batch of hyperparameter samples, r[, dr], a, b, c, n[, m][, v][, i][, p][, tau]: the reference's
+    order (calibrate/log_prob.py:93-102: the inclination behind the baseline terms) with dr where the constructor has it
+    and the two parameters of its time-variability tutorial last.  r, dr and i are in degrees, v is the log10 of the
+    baseline variance.  The one place that knows which columns there are, what they are called, how a batch is taken
+    apart (``split``) and which rows lie inside the reference's bounds (``in_bounds``).
+
+    ``dr``: None (one spot radius), a number (the same spread for every sample) or "free" (a column); ``free``: which of
+    FREE are columns, in any order; ValueError for settings that name no batch.  Attributes: ``dr`` (None, the float or
+    "free"), ``dr_free``, ``free`` (in column order), ``names`` (the columns as ``log_likelihood_samples``' params spell
+    them) and ``columns`` (the short spelling: m, v for the baseline terms)."""
+
+    FREE = ("baseline_mean", "baseline_log_var", "i", "p", "tau")
+    SHORT = {"baseline_mean": "m", "baseline_log_var": "v"}
+    FIELDS = {"baseline_mean": "baseline_mean", "baseline_log_var": "baseline_var", "i": "inc_deg", "p": "period",
+              "tau": "tau"}          # stars_for_samples' keywords
+
+    def __init__(self, dr=None, free=(), conditional=False, temporal=None, params=None):
+        free = (free,) if isinstance(free, str) else tuple(free)
+        if len(set(free)) != len(free) or any(f not in self.FREE for f in free):
+            raise ValueError("free must be a subset of %r" % (self.FREE,))
+        if isinstance(dr, str):
+            if dr != "free":
+                raise ValueError("dr must be None, a number or 'free'")
+        elif dr is not None:
+            from .ops import CheckBoundsOp
+
+            dr = float(dr)
+            CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
+        if "i" in free and not conditional:
+            raise ValueError("a free inclination needs conditional=True: the marginal branch integrates over it")
+        if "tau" in free and temporal is None:
+            raise ValueError("a free tau needs a temporal kernel")
+        self.dr, self.dr_free = dr, isinstance(dr, str)
+        self.free = tuple(f for f in self.FREE if f in free)
+        self.names = ("r",) + (("dr",) if self.dr_free else ()) + ("a", "b", "c", "n") + self.free
+        self.columns = tuple(self.SHORT.get(q, q) for q in self.names)
+        # (a caller's own order of the same names: samples[:, permutation] has the columns in this layout's)
+        self.params = self.names if params is None else tuple(params)
+        self.permutation = [self.params.index(q) for q in self.names]
+
+    @classmethod
+    def from_params(cls, params, marginalize_over_inclination, time_variable, dr=None):
+        """The layout that ``log_likelihood_samples``' ``params`` name, in whatever order, on a process of these two
+        settings and this spot-size spread ``dr`` (None or a number: what holds where "dr" is no column); ``params`` keeps
+        the caller's order and ``samples[:, permutation]`` has the columns in this layout's.  ValueError for an unknown or
+        repeated name, a missing hyperparameter, "i" on a process that marginalises over the inclination, "tau" on one
+        built without a temporal kernel."""
+        params = tuple(params)
+        if (len(set(params)) != len(params) or any(q not in ("r", "dr", "a", "b", "c", "n") + cls.FREE for q in params)
+                or any(q not in params for q in ("r", "a", "b", "c", "n"))):
+            raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var, "
+                             "i, p, tau")
+        if "i" in params and marginalize_over_inclination:
+            raise ValueError("params names i, but this process marginalises over the inclination")
+        if "tau" in params and not time_variable:
+            raise ValueError("params names tau, but this process was built without a temporal kernel (tau=None)")
+        return cls("free" if "dr" in params else dr, [q for q in params if q in cls.FREE], params=params,
+                   conditional=not marginalize_over_inclination, temporal=time_variable or None)
+
+    def split(self, samples):
+        """samples [B, len(names)] (float64, in this layout's order) -> (the rows (r, a, b, c, n) [B, 5], contiguous;
+        dr: None, the constructor's number or the column [B]; the free terms as stars_for_samples takes them, [B] each:
+        baseline_mean, baseline_var = 10 ** v, inc_deg [degrees], period, tau)."""
+        c0 = 2 if self.dr_free else 1
+        hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
+        fields = {self.FIELDS[f]: 10.0 ** samples[:, k] if f == "baseline_log_var" else samples[:, k]
+                  for k, f in enumerate(self.free, c0 + 4)}
+        return hyper, samples[:, 1] if self.dr_free else self.dr, fields
+
+    def in_bounds(self, samples):
+        """Boolean mask of the rows of samples (in this layout's order) inside the reference's bounds: samples_in_bounds
+        of the hyperparameter columns, every column finite, ipt_in_bounds of i, p and tau."""
+        samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
+        return (samples_in_bounds(samples[:, :6 if self.dr_free else 5], dr=self.dr_free)
+                & np.all(np.isfinite(samples), axis=1) & ipt_in_bounds(samples, self.names))
+
+    def check_ipt(self, samples):
+        """ValueError unless every row's i, p and tau are inside their bounds: the three that sample_parameters, which
+        raises for the hyperparameters, does not see."""
+        if not ipt_in_bounds(samples, self.names).all():
+            raise ValueError("samples out of bounds: i in [0, 90] degrees, p >= 0, tau > 0")
 
 
 def sample_parameters(samples, dr=False, **kw):

@@ -2,8 +2,11 @@
 Host-side builder of the ensemble star records (no GPU needed): ``stars.ensemble_stars`` against ``make_stars`` calls
 written out by hand at the smallest shapes where each branch can go wrong, its shape errors and the two bounds errors
 with the text ``StarryProcess._ensemble_args`` has always raised, a two-rank shard cut the way ``EnsembleLogProb`` cuts
-it, and the two small formulas the gradients share (``grad._cn_chain``, ``grad._upstream_eps``).
+it, the column layout of a batch of hyperparameter samples (``stars.SampleColumns``: ``split`` and ``in_bounds``), and the
+two small formulas the gradients share (``grad._cn_chain``, ``grad._upstream_eps``).
 """
+import itertools
+
 import numpy as np
 import pytest
 
@@ -144,6 +147,104 @@ def test_two_rank_shard_groups_its_own_rows_only():
     # rank 1 holds the last star alone: one row, its own, where the whole ensemble has two
     assert bounds[1] == (2, 3)
     assert np.array_equal(ensemble_stars((1, K), T, P[2:], INC[2:], u[2:], UDEG, 0.0, 0.0, 1e-6)[2], U0[None, :])
+
+
+@pytest.mark.parametrize("dr", [None, 7.0, "free"])
+def test_sample_columns_split(dr):
+    """Every subset of the five free terms under every dr mode: the pieces of ``split`` against the columns looked up
+    by name in a batch whose cells are all different."""
+    from starry_process_amd.stars import SampleColumns
+
+    B = 4
+    for k in range(6):
+        for free in itertools.combinations(SampleColumns.FREE[::-1], k):         # (named in the reverse order)
+            cols = SampleColumns(dr=dr, free=free, conditional="i" in free, temporal="matern32" if "tau" in free else None)
+            assert cols.free == tuple(f for f in SampleColumns.FREE if f in free) and cols.dr_free == (dr == "free")
+            assert cols.names == ("r",) + (("dr",) if dr == "free" else ()) + ("a", "b", "c", "n") + cols.free
+            assert cols.columns == tuple({"baseline_mean": "m", "baseline_log_var": "v"}.get(q, q) for q in cols.names)
+            samples = 0.25 + 0.125 * np.arange(B * len(cols.names), dtype=np.float64).reshape(B, len(cols.names))
+            assert np.unique(samples).size == samples.size
+            col = {name: samples[:, j] for j, name in enumerate(cols.names)}
+            before = samples.copy()
+            hyper, d, fields = cols.split(samples)
+            assert np.array_equal(samples, before)
+            assert hyper.dtype == np.float64 and hyper.shape == (B, 5) and hyper.flags["C_CONTIGUOUS"]
+            assert np.array_equal(hyper, np.stack([col[q] for q in ("r", "a", "b", "c", "n")], axis=1))
+            if dr is None:
+                assert d is None
+            elif dr == "free":
+                assert d.shape == (B,) and d.dtype == np.float64 and np.array_equal(d, col["dr"])
+            else:
+                assert isinstance(d, float) and d == 7.0
+            expected = {"baseline_mean": "baseline_mean", "baseline_log_var": "baseline_var", "i": "inc_deg",
+                        "p": "period", "tau": "tau"}
+            assert list(fields) == [expected[f] for f in cols.free]          # stars_for_samples' keywords, in column order
+            for f in cols.free:
+                v = fields[expected[f]]
+                assert v.shape == (B,) and v.dtype == np.float64
+                # 10 ** v for the baseline variance and for nothing else; the inclination stays in degrees
+                assert np.array_equal(v, 10.0 ** col[f] if f == "baseline_log_var" else col[f]), f
+            # the batch builder takes the pieces as they are
+            st = stars.stars_for_samples(make_stars(2), B, 1, **fields)
+            if "i" in free:
+                assert np.array_equal(st["inc"], np.repeat(col["i"] * (np.pi / 180), 2))
+            if "baseline_log_var" in free:
+                assert np.array_equal(st["baseline_var"], np.repeat(10.0 ** col["baseline_log_var"], 2))
+
+
+def test_sample_columns_from_params_and_errors():
+    from starry_process_amd.stars import SampleColumns
+
+    cols = SampleColumns.from_params(("tau", "i", "r", "a", "b", "c", "n", "p"), False, True, dr=5.0)
+    assert cols.params == ("tau", "i", "r", "a", "b", "c", "n", "p") and cols.permutation == [2, 3, 4, 5, 6, 1, 7, 0]
+    assert cols.names == ("r", "a", "b", "c", "n", "i", "p", "tau") and cols.dr == 5.0 and not cols.dr_free
+    row = np.arange(8.0)[None, :]
+    hyper, d, fields = cols.split(row[:, cols.permutation])
+    assert hyper.tolist() == [[2.0, 3.0, 4.0, 5.0, 6.0]] and d == 5.0
+    assert {k: v.tolist() for k, v in fields.items()} == {"inc_deg": [1.0], "period": [7.0], "tau": [0.0]}
+    cols = SampleColumns.from_params(("r", "dr", "a", "b", "c", "n", "p", "baseline_mean"), True, False, dr=5.0)
+    assert cols.names == ("r", "dr", "a", "b", "c", "n", "baseline_mean", "p") and cols.dr == "free" and cols.dr_free
+    assert cols.columns == ("r", "dr", "a", "b", "c", "n", "m", "p")
+    with pytest.raises(ValueError, match="marginalises"):
+        SampleColumns.from_params(("r", "a", "b", "c", "n", "i"), True, True)
+    with pytest.raises(ValueError, match="tau"):
+        SampleColumns.from_params(("r", "a", "b", "c", "n", "tau"), False, False)
+    with pytest.raises(ValueError, match="conditional"):
+        SampleColumns(free=("i",))
+    with pytest.raises(ValueError, match="temporal"):
+        SampleColumns(free=("tau",), conditional=True)
+    for bad in (dict(free=("q",)), dict(free=("p", "p")), dict(dr="fixed"), dict(dr=91.0), dict(dr=-1.0)):
+        with pytest.raises(ValueError):
+            SampleColumns(**bad)
+
+
+def test_sample_columns_in_bounds():
+    from starry_process_amd.stars import SampleColumns
+
+    # the nine rows of test_params_validation (i, p, tau), then non-finite m / v and dr just outside [0, 90]
+    cols = SampleColumns(dr="free", free=SampleColumns.FREE, conditional=True, temporal="matern32")
+    j = {name: k for k, name in enumerate(cols.columns)}
+    rows = np.tile([20.0, 5.0, 0.4, 0.27, 0.1, 10.0, 0.5, -4.0, 60.0, 1.0, 2.0], (19, 1))
+    rows[1, j["i"]], rows[2, j["i"]], rows[3, j["i"]], rows[4, j["i"]] = 0.0, 90.0, 90.0 + 1e-3, -1e-3
+    rows[5, j["p"]], rows[6, j["p"]] = 0.0, -1e-3
+    rows[7, j["tau"]], rows[8, j["tau"]] = 0.0, np.nan
+    ipt = [True, True, True, False, False, True, False, False, False]
+    rows[9, j["m"]], rows[10, j["m"]], rows[11, j["v"]], rows[12, j["v"]] = np.nan, np.inf, np.nan, -np.inf
+    rows[13, j["dr"]], rows[14, j["dr"]], rows[15, j["dr"]], rows[16, j["dr"]] = 0.0, 90.0, 90.0 + 1e-3, -1e-3
+    rows[17, j["r"]], rows[18, j["a"]] = 90.0 + 1e-3, 1.0 + 1e-3          # (samples_in_bounds' own columns)
+    more = [False, False, False, False, True, True, False, False, False, False]
+    assert cols.in_bounds(rows).tolist() == ipt + more
+    assert np.array_equal(cols.in_bounds(rows), stars.samples_in_bounds(rows[:, :6], dr=True)
+                          & np.all(np.isfinite(rows), axis=1) & stars.ipt_in_bounds(rows, cols.names))
+    cols.check_ipt(rows[[0, 1, 2, 5] + list(range(9, 19))])          # (only i, p, tau are its business)
+    for k in (3, 4, 6, 7, 8):
+        with pytest.raises(ValueError, match=r"^samples out of bounds: i in \[0, 90\] degrees, p >= 0, tau > 0$"):
+            cols.check_ipt(rows[[0, k]])
+    # without dr and without the three: the hyperparameters' bounds and finiteness alone
+    plain = SampleColumns(free=("baseline_mean", "baseline_log_var"))
+    sub = rows[:, [j[q] for q in plain.columns]]
+    assert plain.in_bounds(sub).tolist() == [True] * 9 + [False] * 4 + [True] * 4 + [False, False]
+    plain.check_ipt(sub)
 
 
 def test_cn_chain_against_the_formulas():
