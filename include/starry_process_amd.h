@@ -898,6 +898,16 @@ int sp_debug_set_predict_chunk_bytes(size_t bytes);
  * ntr (ntr + 1) / 2 lower tiles (column-strip order) into nchunk chunks of equal COST: start_host[c] = first tile
  * of chunk c, c = 0 .. nchunk (start_host[nchunk] = the number of tiles).  A function of the shape alone.   */
 int sp_debug_asm_chunks(int ntr, int nchunk, int *start_host);
+/* (debug, host only: no handle, no device) what sp_lnlike_ensemble_planned would launch for a plan of a given shape
+ * under given switches (csrc/sp_tuning.cpp, sp_planned_shape).  in[0 .. 5] = ydeg, K, M, covpts, temporal, has_diag,
+ * then the value of every switch in the order of the table (sp_debug_tuning), a negative value = the
+ * switch's default.  out[0 .. 9] = lazy_nfull, ncolw, no_panels, riding, nrid, dlazy, dfrom, fuse0, use_ptab,
+ * small_k; out[10 .. 12] = the super-panel width, whether the reduction rides in the last panel launch's tail, and
+ * whether the first trailing update (ntr - width blocks) runs on the kernel that can form diagonal tiles.          */
+int sp_debug_planned_shape(const int32_t *in, int32_t *out);
+/* (debug, host only) the switches as they stand, in the table's order (17 values): the per-handle ones as an
+ * sp_create now would read them from the environment, the process-wide ones with their overrides.               */
+int sp_debug_tuning(int32_t *out);
 
 #ifdef __cplusplus
 }

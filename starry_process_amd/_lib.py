@@ -137,6 +137,8 @@ PROTOTYPES = {
     "sp_debug_panel2_trace": (_I, [_V]),
     "sp_debug_panel2_chain": (_I, [_V]),
     "sp_debug_asm_chunks": (_I, [_I, _I, _V]),
+    "sp_debug_planned_shape": (_I, [_V, _V]),
+    "sp_debug_tuning": (_I, [_V]),
     "sp_debug_set_syrk128_from": (_I, [_I]),
     "sp_debug_set_small_k": (_I, [_I]),
     "sp_debug_set_predict_chunk_bytes": (_I, [ctypes.c_size_t]),

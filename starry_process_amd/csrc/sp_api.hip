@@ -102,26 +102,10 @@ int sp_create(int ydeg, int udeg, int device, sp_handle **out) {
   SP_HIP(hipMemcpy(h->d_mirror, h->mirror.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice));
   SP_HIP(hipMemcpy(h->d_blk, h->blk.data(), sizeof(int32_t) * (ydeg + 2), hipMemcpyHostToDevice));
 
+  h->tune = sp_tuning_from_env();
   {
-    const char *e3 = getenv("SP_GROUPS");
-    h->groups = e3 ? atoi(e3) : 1;
-    const char *e10 = getenv("SP_DEFER_NORM");
-    h->defer_norm = e10 ? atoi(e10) : 1;
-    const char *e11 = getenv("SP_LAZY_COV");
-    h->lazy_cov = e11 ? atoi(e11) : 1;
-    {
-      hipDeviceProp_t prop;
-      h->ncu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
-    const char *e12 = getenv("SP_PANEL_LA");
-    h->look_ahead = e12 ? atoi(e12) : 1;
-    const char *e13 = getenv("SP_PANEL_LAYOUT");
-    h->panel_layout = e13 ? atoi(e13) : 1;
-    const char *e14 = getenv("SP_FUSE_REDUCE");
-    h->fuse_reduce = e14 ? atoi(e14) : 1;
-    const char *e2 = getenv("SP_SUPER");
-    h->superpanel = e2 ? atoi(e2) : 0;   // 0: chosen from K (sp_launch_cholesky_groups)
-    if (h->superpanel < 0) h->superpanel = 0;
+    hipDeviceProp_t prop;
+    h->ncu = hipGetDeviceProperties(&prop, device) == hipSuccess ? prop.multiProcessorCount : 256;
   }
   // Rx(pi/2): the polar-frame rotation every path uses (flux.py:56,61,62,103)
   const double th = 0.5 * M_PI;
@@ -390,29 +374,29 @@ int sp_profile_end(sp_handle *h, long *launches, double *total_ms, double *flops
 int sp_set_lazy_cov(sp_handle *h, int on) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h) return SP_ERR_INVALID;
-  h->lazy_cov = on ? 1 : 0;
+  h->tune.lazy_cov = on ? 1 : 0;
   return SP_OK;
 }
 
 int sp_set_defer_norm(sp_handle *h, int on) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || (on != 0 && on != 1)) return SP_ERR_INVALID;
-  h->defer_norm = on;
+  h->tune.defer_norm = on;
   return SP_OK;
 }
 
 // (debug) look-ahead items of the panel launches on / off (sp_cholesky.hip); results agree to rounding
 int sp_debug_set_look_ahead(sp_handle *h, int on) {
   if (!h) return SP_ERR_INVALID;
-  h->look_ahead = on ? 1 : 0;
+  h->tune.look_ahead = on ? 1 : 0;
   return SP_OK;
 }
 
 // (debug) the panel launches' layout by CU and the reduction in the last launch's tail, on / off: same bits
 int sp_debug_set_panel_layout(sp_handle *h, int layout, int fuse_reduce) {
   if (!h) return SP_ERR_INVALID;
-  h->panel_layout = layout ? 1 : 0;
-  h->fuse_reduce = fuse_reduce ? 1 : 0;
+  h->tune.panel_layout = layout ? 1 : 0;
+  h->tune.fuse_reduce = fuse_reduce ? 1 : 0;
   return SP_OK;
 }
 

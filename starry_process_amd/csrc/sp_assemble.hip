@@ -842,11 +842,6 @@ extern "C" int sp_debug_asm_chunks(int ntr, int nchunk, int *start_host) {
   return SP_OK;
 }
 
-// LDS of the hot form: the star's table, the column-sum partials, its phases (and times); two workgroups per CU
-size_t sp_assemble_sums_lds(int Kp, int covpts, int temporal) {
-  return sizeof(double) * (4 * (size_t)(covpts + 4) + 8 + (size_t)Kp * (temporal == SP_TEMPORAL_NONE ? 1 : 2));
-}
-
 int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, const double *t,
                             const sp_star *stars, int covpts, const double *ptab, const double *meanvar,
                             int temporal, const double *flux, double *sys, hipStream_t st, double *part,
@@ -856,11 +851,7 @@ int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, co
   const int ntr = Kp / 64, ntiles = ntr * (ntr + 1) / 2;
   // tiles per workgroup: a function of nothing but the build -- the column sums of a strip segment are added
   // in the segment's order, and a star's value must not depend on how many stars share its launch
-  static const int per = [] {
-    const char *e = getenv("SP_ASM_TILES");
-    const int v = e ? atoi(e) : 17;
-    return v < 1 ? 1 : v;
-  }();
+  const int per = sp_proc_tuning().asm_tiles;
   int nchunk = (ntiles + per - 1) / per;
   if (nchunk > SP_ASM_MAX_CHUNKS) nchunk = SP_ASM_MAX_CHUNKS;
   if (ntiles > 65535) return SP_ERR_INVALID;

@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void chol_rev_finish_kernel(const double *__re
 static int cholesky_panel2(sp_handle *h, int ngroups, const sp_chol_group *grp, int K, int Kp, int w) {
   const long ld = Kp, stride = (long)Kp * Kp, lts = sp_lt_stride(Kp);
   const int nsteps = (K + SP_NB - 1) / SP_NB, ntile_all = Kp / SP_NB;
-  const bool la_on = h->look_ahead != 0;
+  const bool la_on = h->tune.look_ahead != 0;
   // row tiles a launch of pivot block j has to take (all of them, unless an identity rides along: tri0)
   const int tri0 = grp[0].tri0;
   auto ntile_of = [&](int j) {
@@ -240,7 +240,7 @@ static int cholesky_panel2(sp_handle *h, int ngroups, const sp_chol_group *grp, 
     const int need = (tri0 + SP_NB * (j + 1) + SP_NB - 1) / SP_NB;
     return need < ntile_all ? need : ntile_all;
   };
-  const bool fuse_reduce = sp_panel_fuses_reduce(h, K, Kp);
+  const bool fuse_reduce = sp_panel_fuses_reduce(h->tune, K, Kp);
   auto nact_of = [&](int j) { return K - j * SP_NB < SP_NB ? K - j * SP_NB : SP_NB; };
   for (int s0 = 0; s0 < nsteps; s0 += w) {
     {
@@ -284,7 +284,7 @@ static int cholesky_panel2(sp_handle *h, int ngroups, const sp_chol_group *grp, 
           sp_scope.add(fl, nl, flp);
           int rc = SP_OK;
           if (d_alone && !G.block0_done)
-            rc = sp_launch_panel2(h->panel_layout | (tri0 >= 0 ? (2 | (tri0 << 8)) : 0), nullptr, G.sys, ld, stride, G.S, ntile, j, s0, nact_of(j), 0, last, SP_PANEL_D,
+            rc = sp_launch_panel2(h->tune.panel_layout | (tri0 >= 0 ? (2 | (tri0 << 8)) : 0), nullptr, G.sys, ld, stride, G.S, ntile, j, s0, nact_of(j), 0, last, SP_PANEL_D,
                                   h->ncu, G.invL, lts, G.info, G.st, nullptr);
           const int what = rows > 0 ? (SP_PANEL_T | (tail ? SP_PANEL_TAILD : 0) | (la ? SP_PANEL_LA : 0) |
                                        (first_la ? SP_PANEL_FIRSTLA : 0))
@@ -297,7 +297,7 @@ static int cholesky_panel2(sp_handle *h, int ngroups, const sp_chol_group *grp, 
           if (probe_skip_p == 3 || (probe_skip_p == 1 && s0 == 0) || (probe_skip_p == 2 && s0 > 0)) continue;
 #endif
           if (rc == SP_OK && what)
-            rc = sp_launch_panel2(h->panel_layout | (tri0 >= 0 ? (2 | (tri0 << 8)) : 0), red, G.sys, ld, stride, G.S, ntile, j, s0, nact_of(j), tail ? nact_of(j + 1) : 0,
+            rc = sp_launch_panel2(h->tune.panel_layout | (tri0 >= 0 ? (2 | (tri0 << 8)) : 0), red, G.sys, ld, stride, G.S, ntile, j, s0, nact_of(j), tail ? nact_of(j + 1) : 0,
                                   last, what, h->ncu, G.invL, lts, G.info, G.st, lzp);
           if (rc != SP_OK) return rc;
         }
@@ -336,30 +336,11 @@ static int cholesky_panel2(sp_handle *h, int ngroups, const sp_chol_group *grp, 
 // previous panels of the group, k = 64 q) by the launch that solves it; the big trailing matrix is
 // touched once per super-panel with a rank-64w update instead of w rank-64 updates (at k = 64 that
 // update is HBM-bound: 8 flop per byte of C traffic; k = 64 w divides the traffic by w).
-static int superpanel_of(const sp_handle *h, int K) {
-  const int nsteps = (K + SP_NB - 1) / SP_NB;
-  return h->superpanel > 0 ? h->superpanel : (nsteps >= 16 ? 8 : 4);
-}
-
-// The last pivot block is partial and its row tile holds the rows below the matrix (nsteps == ntile), and it is
-// factored in the tail of launch nsteps - 2 (it is not the first block of a super-panel).
-int sp_superpanel_width(const sp_handle *h, int K) { return superpanel_of(h, K); }
-
-bool sp_panel_fuses_reduce(const sp_handle *h, int K, int Kp) {
-  const int nsteps = (K + SP_NB - 1) / SP_NB, ntile = Kp / SP_NB;
-  return h->fuse_reduce && nsteps >= 2 && nsteps == ntile && (nsteps - 1) % superpanel_of(h, K) != 0;
-}
-
+// (w: sp_superpanel_width, sp_tuning.cpp)
 int sp_launch_cholesky_groups(sp_handle *h, int ngroups, const sp_chol_group *grp, int K,
                               int Kp) {
   if (!h) return SP_ERR_INVALID;
-  const int nsteps = (K + SP_NB - 1) / SP_NB;
-  // panels per super-panel: wider super-panels raise the arithmetic intensity of the trailing update
-  // at the price of more left-looking work per block column; measured (round 1):
-  // K = 1000 (16 panels) w = 2 / 4 / 6 / 8 / 12 / 16 -> 1.17 / 1.10 / 1.085 / 1.08 / 1.12 / 1.14 ms per
-  // step; K = 3000 (47 panels): 8 best as well
-  (void)nsteps;
-  return cholesky_panel2(h, ngroups, grp, K, Kp, superpanel_of(h, K));
+  return cholesky_panel2(h, ngroups, grp, K, Kp, sp_superpanel_width(h->tune, K));
 }
 
 int sp_launch_cholesky_systems(sp_handle *h, double *sys, int S, int K, int Kp,

@@ -25,7 +25,7 @@
 
 #include <hip/hip_runtime.h>
 
-#define BLD 66   // LDS row of the 64x64 block: even (16-B aligned rows), 132 dwords = 4 mod 64 banks
+#include "sp_internal.h"   // BLD: the LDS row of the 64 x 64 block
 #define SP_DIAG_LDS_DOUBLES (64 * BLD + 64 + 256)   // block, reciprocal diagonal, the current leaf's inverse
 
 typedef double d4 __attribute__((ext_vector_type(4)));

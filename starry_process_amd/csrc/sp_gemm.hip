@@ -502,38 +502,6 @@ static int launch_gemm(const double *A, long lda, long strideA, const double *B,
   return SP_OK;
 }
 
-// from how many 64-blocks on a remainder takes the 128 x 64 tiles (environment SP_SYRK128_FROM; 0 = never)
-static int g_syrk128_from = -1;
-static int syrk128_from() {
-  if (g_syrk128_from < 0) {
-    const char *e = getenv("SP_SYRK128_FROM");
-    g_syrk128_from = e ? atoi(e) : 17;
-    if (g_syrk128_from < 0) g_syrk128_from = 0;
-  }
-  return g_syrk128_from;
-}
-extern "C" int sp_debug_set_syrk128_from(int blocks) {
-  g_syrk128_from = blocks < 0 ? -1 : blocks;      // (-1: back to the environment / default)
-  return SP_OK;
-}
-
-static int g_syrk_symdiag = -1;
-static int syrk_symdiag() {
-  if (g_syrk_symdiag < 0) {
-    const char *e = getenv("SP_SYRK_SYMDIAG");
-    g_syrk_symdiag = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return g_syrk_symdiag;
-}
-int sp_syrk_can_form_diag(int nb) {
-  const int big_from = syrk128_from();
-  return (syrk_symdiag() && !(big_from > 0 && nb >= big_from)) ? 1 : 0;
-}
-extern "C" int sp_debug_set_syrk_symdiag(int on) {
-  g_syrk_symdiag = on < 0 ? -1 : (on ? 1 : 0);    // (-1: back to the environment / default)
-  return SP_OK;
-}
-
 // C -= X X^T on the lower 64 x 64 tiles of an n x n block, tile (0, 0) skipped -- its workgroup
 // factors the pivot block `df` describes instead (sp_cholesky.hip)
 int sp_launch_syrk_diag(const double *X, long ld, long stride, double *T, int n, int kd, int batch,
@@ -542,8 +510,8 @@ int sp_launch_syrk_diag(const double *X, long ld, long stride, double *T, int n,
   if ((n % GT) || (kd % 16) || kd <= 0 || (ld & 1) || (stride & 1) ||
       ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(T)) & 15))
     return SP_ERR_INVALID;
-  // large remainders without an identity riding along: 128 x 64 tiles (syrk128_kernel)
-  const int big_from = syrk128_from();
+  // large remainders without an identity riding along: 128 x 64 tiles (syrk128_kernel; from SP_SYRK128_FROM blocks on)
+  const int big_from = sp_proc_tuning().syrk128_from;
   const int nb = n / GT;
   if (big_from > 0 && nb >= big_from && tj_limit == 0 && (!df || df->tri0 < 0) && (kd % 16) == 0) {
     const int o = nb & 1, nrt = (nb - o) / 2, ntiles = nrt * nrt + nrt * (o + 1) + 1;
@@ -557,7 +525,7 @@ int sp_launch_syrk_diag(const double *X, long ld, long stride, double *T, int n,
   }
   // (SP_SYRK_SYMDIAG=0 / sp_debug_set_syrk_symdiag(0): the diagonal tiles on the plain loop, all sixteen blocks -- the
   //  same bits below the diagonal)
-  const int symdiag = syrk_symdiag() ? 4 : 0;
+  const int symdiag = sp_proc_tuning().syrk_symdiag ? 4 : 0;
   return mm_launch<MM2<64, 64, 8, SP_MM_SYRK_NS, 4>>(X, ld, stride, X, ld, stride, T, ld, stride, n, n, kd, -1.0, 1, 1,
                                          batch, st, 1 | symdiag | (tj_limit > 0 ? tj_limit << 8 : 0),
                                          (lazy && lazy->theta) ? lazy : nullptr, df);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/starry_process_amd.h"
+#include "sp_tuning.h"
 
 #define SP_WAVE 64
 #define SP_MAX_YDEG 30
@@ -17,6 +18,13 @@
 // Cholesky blocking: panels of SP_NB columns, systems padded to a multiple of
 // SP_NB rows (the right-hand sides ride along as extra rows).
 #define SP_NB 64
+// rows below the matrix that the deferred normalisation adds (L^-1 1 and, with per-cadence variances, L^-1 d;
+// sp_reduce.h -- rounds 2-4: p, q, 1)
+#define SP_DEFER_ROWS 2
+// LDS row of the 64 x 64 pivot block (sp_diag.h): even (16-B aligned rows), 132 dwords = 4 mod 64 banks
+#define BLD 66
+// riding rows the small-K kernel takes (sp_small.hip): M + 1 (scalar variance) or M + 2 (per-cadence variances)
+constexpr int SMK_MAXR = 4;
 
 // grow-only device buffer owned by a handle (sp_ensure_scratch)
 struct SpScratch {
@@ -71,17 +79,11 @@ struct sp_handle {
   };
   std::vector<CsSlot> cs_ring;  // (grows while every slot is still in flight, up to SP_STAGE_MAX)
   int cs_next = 0;
-  int superpanel = 0;           // panels per super-panel (SP_SUPER; 0 = chosen from K)
-  int groups = 1;               // concurrent star groups (SP_GROUPS, default 1)
+  SpTuning tune;                // the per-handle switches (sp_tuning.h): the environment's at sp_create, then the setters'
   int ncu = 256;                // compute units of the device
-  int look_ahead = 1;           // panel launches carry a look-ahead item (sp_cholesky.hip; SP_PANEL_LA, default 1)
-  int panel_layout = 1;         // panel launches laid out by CU (sp_panel.hip; SP_PANEL_LAYOUT, default 1)
-  int fuse_reduce = 1;          // the reduction rides in the last panel launch's tail where it can (SP_FUSE_REDUCE, default 1)
   std::vector<hipStream_t> gstream;
   std::vector<hipEvent_t> gdone;
   hipEvent_t gfork = nullptr;
-  int defer_norm = 1;           // likelihood path: deferred normalisation (SP_DEFER_NORM, default 1)
-  int lazy_cov = 1;             // ... with covariance tiles formed at first touch (SP_LAZY_COV, default 1)
   // optional per-launch timing of the factorisation's launches by kind (bench roofline)
   bool prof_on = false;
   unsigned prof_mask = 1u;           // kinds that are bracketed (bit k = kind k)
@@ -216,6 +218,8 @@ static inline int sp_nwig_of(int l) {
   return ((l + 1) * (2 * l + 1) * (2 * l + 3)) / 3;
 }
 static inline int sp_roundup(int x, int m) { return ((x + m - 1) / m) * m; }
+// rows of the padded system of a likelihood step: K cadences, M residual rows, the deferred normalisation's
+static inline int sp_system_rows(int K, int M) { return sp_roundup(K + M + SP_DEFER_ROWS, SP_NB); }
 
 // covariance tiles formed at first touch (sp_cov.h); theta == null: every tile comes from memory.
 // (the star's table is staged in the LDS of the kernel that forms a tile: 4 (covpts + 4) doubles must
@@ -248,10 +252,6 @@ struct LazyCov {
   const double *inorder;   // [S] (or null) 1.0: the star's cadences are in non-decreasing order (the data plan knows) -- the
                            // Matern-3/2 factor of a tile below the diagonal then separates into row and column factors
 };
-
-// does the symmetric trailing update of a remainder of nb 64-column blocks run on the 64 x 64 kernel whose diagonal
-// tiles can be formed at first touch (sp_gemm.hip: not the 128 x 64 tiles of large remainders, not with SP_SYRK_SYMDIAG=0)?
-int sp_syrk_can_form_diag(int nb);
 
 // Per-star normalisation coefficients: 8 doubles per star in the workspace (`coef`), written by
 // norm_coef_kernel (direct form) or defer_finish_kernel (deferred form) of sp_assemble.hip, read
@@ -320,11 +320,6 @@ struct sp_chol_group {
   bool block0_done = false;   // pivot block 0 is factored already (the planned step's assembly does it, sp_planasm.hip)
 };
 
-// does the factorisation of a (K, Kp) system by this handle end in a panel launch's tail (which can carry the reduction)?
-bool sp_panel_fuses_reduce(const sp_handle *h, int K, int Kp);
-// panels per super-panel of a K-cadence factorisation by this handle (sp_cholesky.hip)
-int sp_superpanel_width(const sp_handle *h, int K);
-
 // host-side constant builders (sp_host.cpp)
 void sp_build_index_tables(int ydeg, int32_t *l_of, int32_t *m_of,
                            int32_t *mirror, int32_t *m0, int32_t *blk);
@@ -370,9 +365,8 @@ int sp_launch_assemble(int S, int K, int M, int Kp, int system,
                        const double *diag, int add_noise, const double *flux,
                        double *out, long ldo, long strideo, hipStream_t st, double *part = nullptr,
                        int lazy_nfull = 0);
-// LDS the hot form of the assembly needs (assemble_sums_kernel) and the most it may ask for
+// the most LDS the hot form of the assembly (assemble_sums_kernel; sp_assemble_sums_lds, sp_tuning.h) may ask for
 #define SP_ASM_LDS_MAX (80 * 1024)
-size_t sp_assemble_sums_lds(int Kp, int covpts, int temporal);
 int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, const double *t,
                             const sp_star *stars, int covpts, const double *ptab, const double *meanvar,
                             int temporal, const double *flux, double *sys, hipStream_t st, double *part,
@@ -392,8 +386,7 @@ int sp_launch_cond_system(const double *B1, const double *A, int N, int Kr, int 
                           const double *t, const sp_star *stars, int temporal, const void *coef,
                           const double *diag, const double *flux, double *sys, double *part,
                           hipStream_t st);
-// sp_small.hip
-bool sp_small_k_serves(int K, int M, int covpts, bool has_diag);
+// sp_small.hip (a shape sp_small_k_serves, sp_tuning.h)
 int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const double *t, const sp_star *stars, int covpts,
                            const double *tab, const double *meanvar, int temporal, const double *flux, const double *diag,
                            int order, double zmax, double *lnlike, uint32_t *status_out, hipStream_t st);

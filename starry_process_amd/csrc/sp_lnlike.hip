@@ -2,20 +2,9 @@
 // workspace layout (make_layout, shared with sp_linalg.hip and sp_grad.hip), argument checks and the kernel sequence
 // on the caller's stream, with the small kernels only this driver launches.
 #include <cmath>
-#include <cstdlib>
 
 #include "sp_internal.h"
 
-static int g_small_k = -1;       // sp_debug_set_small_k: -1 = the environment's SP_SMALL_K (default on)
-static bool sp_small_k_on() {
-  if (g_small_k >= 0) return g_small_k != 0;
-  static const bool env = !(getenv("SP_SMALL_K") && atoi(getenv("SP_SMALL_K")) == 0);
-  return env;
-}
-
-// rows below the matrix that the deferred normalisation adds (L^-1 1 and, with per-cadence variances, L^-1 d;
-// sp_reduce.h -- rounds 2-4: p, q, 1)
-#define SP_DEFER_ROWS 2
 // lean: no design-matrix buffers and no raw covariance (the SPD inverse and the gradient's sweep touch neither: at cfg3's
 // shape they were 1.5 GB of the 3.5 GB those calls asked for -- ADVICE r04).
 // s0 > 0: the same layout seen by the stars s0, s0 + 1, ... only (a star group of sp_lnlike_ensemble; the caller sets S)
@@ -26,7 +15,7 @@ Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool 
   L.M = M;
   // (sized for the deferred normalisation whatever the handle's current setting: it is the superset,
   //  so a workspace sized before sp_set_defer_norm changes is never too small)
-  L.Kp = sp_roundup(K + M + (with_sys ? SP_DEFER_ROWS : 0), SP_NB);
+  L.Kp = with_sys ? sp_system_rows(K, M) : sp_roundup(K + M, SP_NB);
   L.N = h->N;
   L.NWIG = h->NWIG;
   L.Kr = sp_roundup(K, SP_NB);
@@ -293,7 +282,7 @@ int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const
     return rc;
   const double *rawp = nullptr;
   const double *condmean = nullptr;
-  if (conditional && (L.N % 64) == 0 && ((normalized && h->defer_norm) || !normalized)) {
+  if (conditional && (L.N % 64) == 0 && ((normalized && h->tune.defer_norm) || !normalized)) {
     // Conditional branch, fused (sp_cond.hip): B1 = A Sigma_y, then the LOWER tiles of B1 A^T land in
     // the system assembled -- no K x K raw matrix written and read back (round 2: 0.5 GB per 64-star
     // step), 40 % fewer flops in the second product.  The design-matrix buffers hold roundup(K, 64)
@@ -328,7 +317,7 @@ int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const
     condmean = cm;
   }
   const int cp = conditional ? 1 : covpts;
-  if (normalized && h->defer_norm) {
+  if (normalized && h->tune.defer_norm) {
     // deferred normalisation: ONE pass over the K^2 entries (raw tiles + their row / column sums),
     // then the normalisation's vectors as three more rows of the system (sp_assemble.hip)
     double *part = at<double>(ws, L.part);
@@ -386,12 +375,6 @@ int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *m
 }
 
 extern "C" {
-
-// (debug, process-wide) the one-kernel path of short light curves on / off / back to the environment's setting
-int sp_debug_set_small_k(int on) {
-  g_small_k = on < 0 ? -1 : (on ? 1 : 0);
-  return SP_OK;
-}
 
 int sp_cov_marginal_batched(sp_handle *h, int S, int K, const double *t_dev,
                             const sp_star *stars_dev, int covpts,
@@ -531,14 +514,10 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
   hipStream_t st = (hipStream_t)stream;
   Layout L = make_layout(h, S, K, M, true);
   void *ws = workspace_dev;
-  // Star groups on concurrent streams: the diagonal-block kernel
-  // is a latency-bound chain that occupies 1/4 of the CUs with one wavefront
-  // each; with G groups in flight one group's GEMMs fill the machine while
-  // another group sits in its chain.  No event traffic inside the loop: one fork
+  // Star groups on concurrent streams (sp_ensemble_shape).  No event traffic inside the loop: one fork
   // and one join per call.
-  int G = h->groups;
-  if (G > S / 8) G = S / 8;  // keep groups large enough to fill the matrix cores
-  if (G < 1) G = 1;
+  const EnsembleShape shape = sp_ensemble_shape(h->tune, h->ydeg, S, K, M, covpts, conditional, temporal, normalized);
+  const int G = shape.G, lazy_nfull = shape.lazy_nfull;
   if (G > 1) {
     while ((int)h->gstream.size() < G - 1) {
       hipStream_t s2;
@@ -551,7 +530,7 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
     if (!h->gfork) SP_HIP(hipEventCreateWithFlags(&h->gfork, hipEventDisableTiming));
     SP_HIP(hipEventRecord(h->gfork, st));
   }
-  const bool fused_reduce = sp_panel_fuses_reduce(h, K, L.Kp);
+  const bool fused_reduce = shape.fused_reduce != 0;
   std::vector<Layout> LG(G, L);
   std::vector<sp_chol_group> CG(G);
   std::vector<int> first(G);
@@ -568,22 +547,14 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
     if (fused_reduce)
       CG[g].red = SpReduceArgs{lnlike_dev + s0, at<uint32_t>(ws, LG[g].status),
                                status_dev ? status_dev + s0 : nullptr, stars_dev + s0,
-                               (normalized && h->defer_norm) ? (const void *)at<double>(ws, LG[g].coef) : nullptr,
+                               (normalized && h->tune.defer_norm) ? (const void *)at<double>(ws, LG[g].coef) : nullptr,
                                at<double>(ws, LG[g].rscal), diag_dev ? 1 : 0, K, M,
-                               K + M + ((normalized && h->defer_norm) ? (diag_dev ? 2 : 1) : 0)};
+                               K + M + ((normalized && h->tune.defer_norm) ? (diag_dev ? 2 : 1) : 0)};
   }
-  // Tiles formed at first touch (LazyCov, sp_cov.h): the marginal path under the deferred
-  // normalisation.
-  int lazy_nfull = 0;
-  // (not with a temporal kernel: its exp per entry, evaluated twice, costs more than the traffic
-  //  it saves -- cfg5 shape: -2.5 %)
-  if (h->lazy_cov && !conditional && temporal == SP_TEMPORAL_NONE && normalized && h->defer_norm && G == 1 &&
-      K / SP_NB >= 2 &&
-      (size_t)K * L.N >= 4 * (size_t)(covpts + 4) && 4 * (covpts + 4) + 64 <= SP_TILE_LDS_MIN) {   // (+ a tile's column phases)
-    lazy_nfull = K / SP_NB;
+  // tiles formed at first touch (LazyCov, sp_cov.h)
+  if (lazy_nfull)
     CG[0].lazy = LazyCov{at<double>(ws, L.theta), t_dev, stars_dev, at<double>(ws, L.A), K, covpts,
                          temporal, lazy_nfull, 0, 0};
-  }
   for (int g = 0; g < G; ++g) {
     const int s0 = first[g];
     CondSets gs{};
@@ -604,7 +575,7 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
     int rc = fused_reduce ? SP_OK
                           : lnlike_finish(LG[g], ws, K, M, lnlike_dev + s0,
                                           status_dev ? status_dev + s0 : nullptr, CG[g].st, stars_dev + s0,
-                                          normalized && h->defer_norm, diag_dev != nullptr);
+                                          normalized && h->tune.defer_norm, diag_dev != nullptr);
     if (rc) return rc;
     if (g > 0) {
       SP_HIP(hipEventRecord(h->gdone[g - 1], CG[g].st));
@@ -671,73 +642,32 @@ int sp_lnlike_ensemble_planned(sp_handle *h, const sp_plan *plan, const double *
   const int S = plan->S, K = plan->K, M = plan->M, covpts = plan->covpts, temporal = plan->temporal;
   if (h->xp_covpts != covpts) return SP_ERR_STATE;
   hipStream_t st = (hipStream_t)stream;
-  // Short light curves: the whole evaluation of a star in one workgroup's LDS (sp_small.hip) -- no system in memory, no
-  // panel launches.  SP_SMALL_K=0: the blocked path at every size.
-  if (sp_small_k_on() && sp_small_k_serves(K, M, covpts, diag_dev != nullptr))
+  // which kernels form which tiles: sp_planned_shape (sp_tuning.cpp)
+  const PlannedShape ps = sp_planned_shape(h->tune, sp_proc_tuning(), h->ydeg, K, M, covpts, temporal, diag_dev != nullptr);
+  if (ps.small_k)
     return sp_launch_small_lnlike(S, K, M, plan->dev, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal, flux_dev,
                                   diag_dev, norm_order, zmax, lnlike_dev, status_dev, st);
   Layout L = make_layout(h, S, K, M, true);
   void *ws = workspace_dev;
-  // (the stars' packed tables for the kernels that form tiles at first touch: the design-matrix region)
-  double *ptab = 4 * (size_t)(covpts + 4) > (size_t)L.Kr * L.N ? nullptr : at<double>(ws, L.A);
-  // Tiles formed at first touch.  Without a temporal kernel: everything below the diagonal (the panel launches form
-  // the first super-panel's block columns, the first trailing update the rest).  With one: the trailing update's
-  // tiles only -- an exponential per entry has no place in the panel kernel's register budget, so the assembly writes
-  // the first super-panel's block columns; every entry is still evaluated once.
-  int lazy_nfull = 0, ncolw = 0, no_panels = 0;
-  // (the row tiles that hold riding rows -- residuals, ones, variances -- are formed at first touch as well: every row
-  //  tile is formable, the assembly writes the diagonal tiles only; SP_PLAN_RIDING_LAZY=0: it writes those row tiles)
-  static const bool riding_env = !(getenv("SP_PLAN_RIDING_LAZY") && atoi(getenv("SP_PLAN_RIDING_LAZY")) == 0);
-  bool riding = false;
-  const int nrid = M + (diag_dev ? 2 : 1);
-  double *rid = at<double>(ws, L.B1);
-  if (h->lazy_cov && ptab && K / SP_NB >= 2 && 4 * (covpts + 4) + 64 <= SP_TILE_LDS_MIN) {
-    // (the riding rows as the assembly would write them, [S][nrid][K], in the second design-matrix buffer)
-    riding = riding_env && ((size_t)nrid + 1) * K <= (size_t)L.Kr * L.N;
-    lazy_nfull = riding ? L.Kp / SP_NB : K / SP_NB;
-    // (SP_PLAN_PANEL_LAZY=0: without a temporal kernel too, the panel launches load their tiles and only the first
-    //  trailing update forms its own -- measured, not the default: DESIGN.md 4.11)
-    static const bool panel_lazy = !(getenv("SP_PLAN_PANEL_LAZY") && atoi(getenv("SP_PLAN_PANEL_LAZY")) == 0);
-    if (temporal != SP_TEMPORAL_NONE || !panel_lazy) {
-      static const bool tl = !(getenv("SP_PLAN_TEMPORAL_LAZY") && atoi(getenv("SP_PLAN_TEMPORAL_LAZY")) == 0);
-      ncolw = sp_superpanel_width(h, K);
-      no_panels = 1;
-      if ((!tl && temporal != SP_TEMPORAL_NONE) || ncolw * SP_NB >= K) lazy_nfull = ncolw = no_panels = 0;   // (one super-panel: no trailing update)
-    }
-  }
-  // The diagonal tiles beyond the first super-panel's reach (those the eager updates of its launches do not touch) are
-  // formed by the first trailing update too (LazyCov.dlazy bit 1), when that update runs on the kernel that can
-  // (sp_syrk_can_form_diag) and everything else of their strips is left to its first touch; SP_PLAN_DIAG_LAZY=0: the
-  // assembly writes them.
-  static const bool dlazy_env = !(getenv("SP_PLAN_DIAG_LAZY") && atoi(getenv("SP_PLAN_DIAG_LAZY")) == 0);
-  const int ntr = L.Kp / SP_NB, wsp = sp_superpanel_width(h, K), nsteps = (K + SP_NB - 1) / SP_NB;
-  int dlazy = 0, dfrom = ntr;
-  if (dlazy_env && riding && lazy_nfull == ntr && wsp * SP_NB < K && sp_syrk_can_form_diag(ntr - wsp) &&
-      temporal == SP_TEMPORAL_NONE) {
-    const int last = wsp < nsteps - 1 ? wsp : nsteps - 1;     // (cholesky_panel2: row tiles i <= last keep their diagonal tile up to date)
-    dlazy = 2;
-    dfrom = last + 1;
-  }
-  // (pivot block 0 is factored by the assembly's workgroup of tile (0, 0): no launch of its own; SP_PLAN_FUSE0=0 for
-  //  the separate launch)
-  static const bool fuse0_env = !(getenv("SP_PLAN_FUSE0") && atoi(getenv("SP_PLAN_FUSE0")) == 0);
-  const int fuse0 = (fuse0_env && K >= SP_NB) ? 1 : 0;
+  // (the stars' packed tables for the kernels that form tiles at first touch in the design-matrix region, the riding
+  //  rows as the assembly would write them, [S][nrid][K], in the second design-matrix buffer)
+  double *ptab = ps.use_ptab ? at<double>(ws, L.A) : nullptr;
+  double *rid = ps.riding ? at<double>(ws, L.B1) : nullptr;
   int rc = sp_launch_assemble_planned(S, K, M, L.Kp, plan->dev, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
-                                      flux_dev, diag_dev, at<double>(ws, L.sys), lazy_nfull, ncolw, norm_order, zmax,
+                                      flux_dev, diag_dev, at<double>(ws, L.sys), ps.lazy_nfull, ps.ncolw, norm_order, zmax,
                                       at<double>(ws, L.coef), at<double>(ws, L.rscal), ptab, at<int32_t>(ws, L.info),
-                                      at<uint32_t>(ws, L.status), st, at<double>(ws, L.invL), sp_lt_stride(L.Kp), fuse0,
-                                      riding ? rid : nullptr, dfrom);
+                                      at<uint32_t>(ws, L.status), st, at<double>(ws, L.invL), sp_lt_stride(L.Kp), ps.fuse0,
+                                      rid, ps.dfrom);
   if (rc) return rc;
-  const bool fused_reduce = sp_panel_fuses_reduce(h, K, L.Kp);
+  const bool fused_reduce = sp_panel_fuses_reduce(h->tune, K, L.Kp);
   sp_chol_group G{at<double>(ws, L.sys), at<int32_t>(ws, L.info), at<double>(ws, L.invL), S, st, LazyCov{}, SpReduceArgs{}};
   if (fused_reduce)
     G.red = SpReduceArgs{lnlike_dev, at<uint32_t>(ws, L.status), status_dev, stars_dev, (const void *)at<double>(ws, L.coef),
                          at<double>(ws, L.rscal), diag_dev ? 1 : 0, K, M, K + M + (diag_dev ? 2 : 1)};
-  G.block0_done = fuse0 != 0;
-  (void)dlazy;
-  if (lazy_nfull)
-    G.lazy = LazyCov{plan->dev.theta, t_dev, stars_dev, ptab, K, covpts, temporal, lazy_nfull, 0, 0, no_panels ? 0 : 1,
-                     no_panels, riding ? rid : nullptr, riding ? nrid : 0, dlazy, plan->dev.inorder};
+  G.block0_done = ps.fuse0 != 0;
+  if (ps.lazy_nfull)
+    G.lazy = LazyCov{plan->dev.theta, t_dev, stars_dev, ptab, K, covpts, temporal, ps.lazy_nfull, 0, 0, ps.no_panels ? 0 : 1,
+                     ps.no_panels, rid, ps.riding ? ps.nrid : 0, ps.dlazy, plan->dev.inorder};
   if ((rc = sp_launch_cholesky_groups(h, 1, &G, K, L.Kp))) return rc;
   if (!fused_reduce) return lnlike_finish(L, ws, K, M, lnlike_dev, status_dev, st, stars_dev, true, diag_dev != nullptr);
   return SP_OK;

@@ -498,10 +498,7 @@ int sp_launch_assemble_planned(int S, int K, int M, int Kp, const PlanDev &plan,
   // 2 or 4), never more than 24 (cfg5's shape: 1 128 tiles per star, three
   // rounds -- a workgroup's prologue copies the star's phases and times, 48 KB there).  No sums are taken here: the
   // cut changes no bit of the result.  SP_PLAN_TILES overrides.
-  static const int per_env = [] {
-    const char *e = getenv("SP_PLAN_TILES");
-    return e ? atoi(e) : 0;
-  }();
+  const int per_env = sp_proc_tuning().plan_tiles;
   int per = per_env > 0 ? per_env : (int)(((long)nwritten * S + 511) / 512);
   if (per_env <= 0) per = per < 3 ? 3 : (per > 24 ? 24 : per);
   int nchunk = (nwritten + per - 1) / per;

@@ -29,11 +29,6 @@
 
 namespace {
 
-// stars of one pass share this many bytes of workspace at most (the size query stops growing there);
-// sp_debug_set_predict_chunk_bytes overrides it process-wide so that a test can force several passes
-constexpr size_t PREDICT_CHUNK_BYTES = (size_t)4 << 30;
-size_t g_chunk_bytes = PREDICT_CHUNK_BYTES;
-
 struct PredictAsm {
   int K, Ks, covpts;
   const double *th_t, *th_s;   // [S][K], [S][Ks] phases (marginal branch)
@@ -318,7 +313,9 @@ struct PredictLayout {
       return c.off;
     };
     const size_t per = carve(1);
-    const size_t fit = g_chunk_bytes / per;
+    // (stars of one pass share this many bytes of workspace at most -- the size query stops growing there;
+    //  sp_debug_set_predict_chunk_bytes overrides it process-wide so that a test can force several passes)
+    const size_t fit = sp_proc_tuning().predict_chunk_bytes / per;
     chunk = fit < 1 ? 1 : (fit < (size_t)S ? (int)fit : S);
     if (chunk > 65535) chunk = 65535;
     bytes = carve(chunk);
@@ -428,12 +425,6 @@ int check_in(const sp_handle *h, int S, const PredictIn &in) {
 }  // namespace
 
 extern "C" {
-
-// (debug, process-wide) the workspace budget of one pass of stars; 0: back to the default
-int sp_debug_set_predict_chunk_bytes(size_t bytes) {
-  g_chunk_bytes = bytes ? bytes : PREDICT_CHUNK_BYTES;
-  return SP_OK;
-}
 
 size_t sp_predict_workspace_bytes(sp_handle *h, int S, int K, int Ks, int covpts) {
   if (!h || S < 1 || K < 1 || Ks < 1 || covpts < 1) return 0;

@@ -61,7 +61,6 @@ extern "C" int sp_debug_small_diag(long long *out) {
 namespace {
 
 typedef SpCoef Coef;
-constexpr int SMK_MAXR = 4;          // riding rows: M + 1 (scalar variance) or M + 2 (per-cadence variances)
 
 struct SmallSrc {                    // lnlike_reduce_src's view of the factored star
   const double *dg;                  // [64 NB] L_ii
@@ -324,16 +323,6 @@ __global__ __launch_bounds__(256, NB == 2 ? 3 : 4) void small_lnlike_kernel(
 }
 
 }  // namespace
-
-// can the planned step of this shape run in the small-K kernel?  (sp_lnlike_ensemble_planned asks)
-bool sp_small_k_serves(int K, int M, int covpts, bool has_diag) {
-  const int nr = M + (has_diag ? 2 : 1);
-  if (K < 2 || K > 128 || nr > SMK_MAXR) return false;
-  const int np = covpts + 4;
-  // the table: in the pivot block's place (K <= 64) or in a region of its own, no larger (K > 64: 54 KB, three
-  // workgroups a CU, up to covpts = 390 with two riding rows)
-  return 4 * np <= 64 * BLD;
-}
 
 int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const double *t, const sp_star *stars, int covpts,
                            const double *tab, const double *meanvar, int temporal, const double *flux, const double *diag,

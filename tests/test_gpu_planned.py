@@ -10,9 +10,14 @@ the flux and of the variances -- were taken once.  What the reference fixes when
   * planned against the direct normalisation (sp_set_defer_norm(0): row sums, normalised matrix assembled and
     factored as such) and against the unplanned deferred form over the input variants of the path (1e-10);
   * awkward sizes, calibrate's covpts = K - 1, tiles formed at first touch or all assembled (same bits), a plan
-    shared by several handles with steps in flight, a stale plan, bad arguments.
+    shared by several handles with steps in flight, a stale plan, bad arguments;
+  * the process-wide tuning switches (csrc/sp_tuning.cpp) toggled one at a time: the same value to 1e-10.
 """
 import ctypes
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -336,6 +341,78 @@ def test_one_plan_many_handles_in_flight():
     assert torch.equal(alone[0], alone[3]) and len({float(a[0]) for a in alone}) == 3
     ref = golden("lnlike_full")["cfg3_L15_K1000"]
     assert np.max(np.abs(alone[0].cpu().numpy() / ref - 1)) < TOL
+
+
+def switch_values(cases):
+    """the planned (or, planned = 0, the unplanned deferred) values of 8 stars, one light curve each, ydeg 5, per case
+    (K, temporal kernel or None, planned) -- in this process, under whatever switches it runs with"""
+    from starry_process_amd.engine import make_stars
+
+    e = make_engine(5)
+    out = []
+    for K, temporal, planned in cases:
+        sts, t, flux = star_batch(K, range(8))
+        stars = make_stars(8, period=[st["p"] for st in sts], tau=2.5 if temporal else 0.0, data_var=1e-6)
+        v, st, _ = run(e, t, flux, stars, bool(planned), temporal=temporal)
+        assert not st.any() and np.all(np.isfinite(v)), (K, temporal, planned)
+        out.append(v.tolist())
+    return out
+
+
+def test_process_wide_switches_do_not_change_the_planned_value():
+    """Every process-wide switch off its default, one at a time, at the smallest sizes where the riding-row,
+    lazy-diagonal and fused-block-0 rules change what is launched (K = 129, 200, 700; tests/golden/planned_shape.json
+    lists the shapes): the planned value is the default setting's to 1e-10.  A switch that changes nothing there also
+    runs at the smallest K of that fixture's grid where it does: SP_SMALL_K at K = 2, SP_SYRK128_FROM = 0 at K = 2488,
+    SP_PLAN_TEMPORAL_LAZY (which acts under a temporal kernel only) with Matern-3/2 at K = 512.  SP_ASM_TILES cuts the
+    UNPLANNED assembly's chunks: that call's value against the planned one.  Switches with a setter are toggled here,
+    the others in a fresh child process each (they are read once), all children at the same time."""
+    from starry_process_amd import _lib
+
+    base = [(K, None, 1) for K in (129, 200, 700)]
+    tcases = [(K, "matern32", 1) for K in (129, 200, 512, 700)]
+    allc = [(2, None, 1)] + base + [(2488, None, 1)] + tcases
+    children = {
+        "SP_PLAN_RIDING_LAZY": ("0", base + tcases), "SP_PLAN_PANEL_LAZY": ("0", base), "SP_PLAN_DIAG_LAZY": ("0", base),
+        "SP_PLAN_FUSE0": ("0", base + tcases), "SP_PLAN_TEMPORAL_LAZY": ("0", tcases), "SP_PLAN_TILES": ("5", base + tcases),
+        "SP_ASM_TILES": ("5", [(K, None, 0) for K in (129, 200, 700)]),
+    }
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    code = ("import sys, json; sys.path[:0] = [%r, %r]; import test_gpu_planned as m; "
+            "print('VALUES ' + json.dumps(m.switch_values(json.loads(sys.argv[1]))))" % (root, os.path.dirname(__file__)))
+    procs = {name: subprocess.Popen([sys.executable, "-c", code, json.dumps(cases)], env=dict(os.environ, **{name: val}),
+                                    stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+             for name, (val, cases) in children.items()}
+    try:
+        ref = dict(zip([c[:2] for c in allc], switch_values(allc)))
+        L = _lib.lib()
+        got = {}
+        setters = {"SP_SMALL_K": (L.sp_debug_set_small_k, 0, [(2, None, 1)] + base),
+                   "SP_SYRK_SYMDIAG": (L.sp_debug_set_syrk_symdiag, 0, base + tcases),
+                   "SP_SYRK128_FROM": (L.sp_debug_set_syrk128_from, 0, base + [(2488, None, 1)])}
+        for name, (fn, val, cases) in setters.items():
+            try:
+                assert fn(val) == 0
+                got[name] = (cases, switch_values(cases))
+            finally:
+                fn(-1)
+        for name, p in procs.items():
+            out, err = p.communicate(timeout=300)
+            assert p.returncode == 0, (name, err[-2000:])
+            line = [ln for ln in out.splitlines() if ln.startswith("VALUES ")][-1]
+            got[name] = (children[name][1], json.loads(line[7:]))
+    finally:
+        for p in procs.values():
+            if p.poll() is None:
+                p.kill()
+    assert set(got) == set(children) | set(setters)
+    for name, (cases, vals) in got.items():
+        for c, v in zip(cases, vals):
+            a, b = np.array(ref[tuple(c[:2])]), np.array(v)
+            scale = np.maximum(np.abs(a), np.abs(a).max())
+            err = np.max(np.abs(a - b) / scale)
+            print("%-22s K %4d %-9s %s  %.2e" % (name, c[0], c[1], "planned" if c[2] else "unplanned", err))
+            assert err < 1e-10, (name, c, a, b)
 
 
 def test_planned_bad_arguments(engines):
