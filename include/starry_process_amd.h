@@ -219,6 +219,28 @@ int sp_kernel_table_samples(sp_handle *h, int B, const double *ez_dev, const dou
  * B = 0 is SP_OK and touches nothing.                                                                              */
 int sp_ylm_moments_samples(sp_handle *h, int B, const double *samples_host, int spread, double cutoff, double epsy,
                            double epsy15, double *mean_ylm_dev, double *cov_ylm_dev, void *stream);
+/* Sums of C independent spot populations on one star (StarryProcessSum, sp.py:1335-1400: the children's Ylm moments
+ * add), B samples per call.  samples_host [B][C][5], or [B][C][6] with spread != 0: row b C + c is population c of
+ * sample b, a row of sp_polar_moments_samples / sp_polar_moments_samples_spread (r and dr in RADIANS, alpha, beta, c, n;
+ * cutoff is read with spread != 0 only).  The chain of those entry points runs ONCE on the B C rows -- one staged
+ * upload, the same six or seven launches -- and one more kernel reduces over the populations:
+ *   sp_polar_moments_samples_sum   ez [B][N] = sum_c ez_c;  Ez [B][N][N] = sum_c Ez_c + sum_{c < d} (ez_c ez_d^T +
+ *       ez_d ez_c^T): the second moment of the sum, Rx(pi/2)^T (Sigma + mu mu^T) Rx(pi/2) at mu = sum mu_c, Sigma = sum
+ *       Sigma_c, without a subtraction anywhere (never covariance + (sum ez)(sum ez)^T - sum ez_c ez_c^T).  Ez is
+ *       symmetric to the bit.
+ *   sp_ylm_moments_samples_sum     (mu_y, Sigma_y) [B][N], [B][N][N] of the sum, what the conditional branch reads: the
+ *       children's polar-frame means and covariances add, and the sum is rotated back once -- the three rotation
+ *       launches of sp_ylm_moments_samples do not grow with C.
+ * With C = 1 both return the bits of the entry points above; B samples in one call give the bits of B calls with one
+ * sample each.  No atomics, nothing synchronised, no host arithmetic per sample.  The children's moments live in the
+ * handle's scratch, which grows by B C (N + N^2) doubles over the one-population call's (67 MB at B = 64, C = 2,
+ * ydeg 15), and by B (N + 2 N^2) more for sp_ylm_moments_samples_sum.  SP_ERR_INVALID for a null pointer, C < 1, B < 0,
+ * B C > 65535 or a row outside the bounds of the entry points above; SP_ERR_STATE without a size basis; B = 0 is SP_OK
+ * and touches nothing.                                                                                             */
+int sp_polar_moments_samples_sum(sp_handle *h, int B, int C, const double *samples_host, int spread, double cutoff,
+                                 double epsy, double epsy15, double *ez_dev, double *Ez_dev, void *stream);
+int sp_ylm_moments_samples_sum(sp_handle *h, int B, int C, const double *samples_host, int spread, double cutoff,
+                               double epsy, double epsy15, double *mean_ylm_dev, double *cov_ylm_dev, void *stream);
 
 /* ---- per-star parameter block -------------------------------------------- */
 /* All batched entry points below take `S` stars with a common row length K.  A

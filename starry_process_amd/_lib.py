@@ -177,6 +177,8 @@ PROTOTYPES = {
     "sp_polar_moments_samples_spread": (_I, [_V, _I, _V, _D, _D, _D, _V, _V, _V]),
     "sp_kernel_table_samples": (_I, [_V, _I, _V, _V, _V, _I, _I, _V, _V, _V, _V]),
     "sp_ylm_moments_samples": (_I, [_V, _I, _V, _I, _D, _D, _D, _V, _V, _V]),
+    "sp_polar_moments_samples_sum": (_I, [_V, _I, _I, _V, _I, _D, _D, _D, _V, _V, _V]),
+    "sp_ylm_moments_samples_sum": (_I, [_V, _I, _I, _V, _I, _D, _D, _D, _V, _V, _V]),
     "sp_lnlike_ensemble_sets_workspace_bytes": (_L, [_V, _I, _I, _I]),
     "sp_lnlike_ensemble_sets": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V,
                                      _V]),

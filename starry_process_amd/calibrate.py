@@ -63,6 +63,21 @@ def clamp_depth(depth, extra_streams=0, limit=None):
     return depth
 
 
+def log_jac_populations(hyper):
+    """The log-Jacobian of a batch of samples, hyper [B, 5] = rows of (r, a, b, c, n), or [B, C, 5] for C independent
+    populations: the latitude transform is per population, so the Jacobians multiply -- the sum over the populations
+    of ``upstream.log_jac_samples``.  -> [B]."""
+    from .upstream import log_jac_samples
+
+    hyper = np.asarray(hyper, dtype=np.float64)
+    if hyper.ndim == 2:
+        return log_jac_samples(hyper[:, 1], hyper[:, 2])
+    total = log_jac_samples(hyper[:, 0, 1], hyper[:, 0, 2])
+    for q in range(1, hyper.shape[1]):
+        total = total + log_jac_samples(hyper[:, q, 1], hyper[:, q, 2])
+    return total
+
+
 class SampleBatches(object):
     """log-likelihoods of MANY hyperparameter samples for ONE planned data set, ``group`` samples per library call:
 
@@ -89,14 +104,19 @@ class SampleBatches(object):
         b S + s under set b.  No plan, no tables: the data are tiled ``group`` times once, at construction.
       * marginal with free "p" or "tau": the tables as below, then the unplanned sp_lnlike_ensemble on the tiled data
         (the plan fixes period and timescale).
-      * marginal otherwise: the planned path described above, unchanged."""
+      * marginal otherwise: the planned path described above, unchanged.
+
+    ``populations`` = C > 1: the samples are those of a sum of C independent spot populations (StarryProcessSum), columns
+    r1[, dr1], a1, b1, c1, n1, r2, ... and then the free terms; ``dr`` is one setting for all populations or a sequence of
+    C.  All three routes then take their moments from sp_polar_moments_samples_sum / sp_ylm_moments_samples_sum;
+    everything behind the moments is the same."""
 
     def __init__(self, slots, t_dev, flux_dev, stars, rta1_dev, covpts, diag_dev=None, temporal=None, group=None,
                  norm_order=20, zmax=0.023, upstream_kwargs=None, plan=None, dr=None, free=(), conditional=False,
-                 normalized=True):
+                 normalized=True, populations=1):
         import torch
 
-        self._cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal)
+        self._cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal, populations=populations)
         self.columns, self._free, self._dr = self._cols.columns, self._cols.free, self._cols.dr
         self._conditional, self._normalized, self._temporal = bool(conditional), bool(normalized), temporal
         if not self._normalized and not self._conditional:
@@ -145,10 +165,10 @@ class SampleBatches(object):
         torch.cuda.synchronize(e0.device)
 
     @classmethod
-    def column_names(cls, dr=None, free=(), conditional=False, temporal=None):
+    def column_names(cls, dr=None, free=(), conditional=False, temporal=None, populations=1):
         """(columns, free in column order) of the samples for these settings; ValueError for settings that name no batch
         (needs no device)."""
-        cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal)
+        cols = SampleColumns(dr=dr, free=free, conditional=conditional, temporal=temporal, populations=populations)
         return cols.columns, cols.free
 
     def _group_stars(self, **fields):
@@ -195,8 +215,13 @@ class SampleBatches(object):
                         stream.wait_event(stagger)
                 stars_d = self._stars
                 sl = slice(gi * g, (gi + 1) * g)
-                drs = dr[sl] if self._cols.dr_free else dr
-                if self._conditional:
+                drs = self._cols.take_dr(dr, sl)
+                if self._cols.populations > 1:          # (a sum of populations: hyper [ns, C, 5], dr None or [ns, C])
+                    if self._conditional:
+                        e.ylm_moments_samples_sum(hyper[sl], mean=b["mu"], cov=b["cov"], dr=drs, **self._ukw)
+                    else:
+                        e.polar_moments_samples_sum(hyper[sl], ez=b["ez"], Ez=b["Ez"], dr=drs, **self._ukw)
+                elif self._conditional:
                     e.ylm_moments_samples(hyper[sl], mean=b["mu"], cov=b["cov"], dr=drs, **self._ukw)
                 else:
                     e.polar_moments_samples(hyper[sl], ez=b["ez"], Ez=b["Ez"], dr=drs, **self._ukw)
@@ -335,7 +360,9 @@ class EnsembleLogProb(object):
     ``baseline_mean=None`` / ``baseline_log_var=None`` make the baseline mean m / the log10 of the baseline variance v
     trailing columns of the samples, as in ``get_log_prob`` (calibrate/log_prob.py:24-47, 93-103); ``dr``: None (one
     spot radius), a float in degrees (StarryProcess(dr=...)) or "free" (a column behind r).  The columns are
-    r[, dr], a, b, c, n[, m][, v] (``lp.columns``).
+    r[, dr], a, b, c, n[, m][, v] (``lp.columns``).  ``populations`` = C > 1: every star carries C independent spot
+    populations (``sp1 + sp2``); the hyperparameter block repeats per population, r1[, dr1], a1, b1, c1, n1, r2, ..., ``dr``
+    is one setting for all of them or a sequence of C, and the latitude Jacobians of the populations multiply.
 
     Per sample: moments by quadrature on the device (upstream_device.py) -> kernel table ->
     one batched likelihood call for this rank's stars; nothing is copied back or synchronised
@@ -355,7 +382,7 @@ class EnsembleLogProb(object):
     def __init__(self, t, flux, ferr=1.0e-3, p=1.0, i=None, u=None, ydeg=15, baseline_log_var=0.0,
                  baseline_mean=0.0, apply_jac=True, normalized=True,
                  marginalize_over_inclination=True, covpts=None, device=None, depth=3, upstream_stream=True,
-                 batch_samples=True, out_of_bounds="raise", dr=None):
+                 batch_samples=True, out_of_bounds="raise", dr=None, populations=1):
         import torch
         import torch.distributed as dist
 
@@ -365,7 +392,8 @@ class EnsembleLogProb(object):
         from .stars import check_period_inclination, ensemble_stars
 
         self._cols = SampleColumns(dr=dr, free=[
-            name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var)) if val is None])
+            name for name, val in (("baseline_mean", baseline_mean), ("baseline_log_var", baseline_log_var)) if val is None],
+            populations=populations)
         self.columns, self._free, self._dr = self._cols.columns, self._cols.free, self._cols.dr
         baseline_mean = 0.0 if baseline_mean is None else baseline_mean            # (placeholders: overwritten per sample)
         baseline_log_var = 0.0 if baseline_log_var is None else baseline_log_var
@@ -429,7 +457,8 @@ class EnsembleLogProb(object):
         if self._plan is not None and batch_samples:
             more = engine_slots(ydeg, udeg, device, 2) if len(self._slots) + 1 + 2 <= MAX_STREAMS_SAMPLES else []
             self._batch = SampleBatches(self._slots + [self._up] + more, self._t, self._flux, stars, self._rta1,
-                                        self._kw["covpts"], plan=self._plan, zmax=0.023, dr=self._dr, free=self._free)
+                                        self._kw["covpts"], plan=self._plan, zmax=0.023, dr=self._dr, free=self._free,
+                                        populations=self._cols.populations)
         torch.cuda.synchronize(e0.device)
 
     def __call__(self, samples):
@@ -459,8 +488,21 @@ class EnsembleLogProb(object):
         elif nl:
             eu, su = self._up
             keep = []                                   # (the moments stay alive until the batch is done)
-            for k, (r, a, b, c, n) in enumerate(hyper):
-                dr = drs[k] if self._cols.dr_free else drs
+            C = self._cols.populations
+
+            def moments(eng, k):
+                """(mean, cov) of sample k: of its one population, or the sum over its C independent ones."""
+                if C == 1:
+                    r, a, b, c, n = hyper[k]
+                    return ylm_moments_device(eng, r=r, dr=self._cols.take_dr(drs, k), a=a, b=b, c=c, n=n)
+                mean = cov = None
+                for q, (r, a, b, c, n) in enumerate(hyper[k]):
+                    one = self._cols.dr[q] is None          # (a population without a spread keeps dr=None)
+                    m1, c1 = ylm_moments_device(eng, r=r, dr=None if one else drs[k, q], a=a, b=b, c=c, n=n)
+                    mean, cov = (m1, c1) if mean is None else (mean + m1, cov + c1)
+                return mean, cov
+
+            for k in range(ns):
                 stars_d = self._stars
                 if self._free:
                     st = self._stars_host.copy()
@@ -471,7 +513,7 @@ class EnsembleLogProb(object):
                 e, stream = self._slots[k % len(self._slots)]
                 if self._upstream_stream:
                     with torch.cuda.stream(su):
-                        mean, cov = ylm_moments_device(eu, r=r, dr=dr, a=a, b=b, c=c, n=n)
+                        mean, cov = moments(eu, k)
                         ready = torch.cuda.Event()
                         ready.record(su)
                     keep.append((mean, cov, ready))
@@ -479,7 +521,7 @@ class EnsembleLogProb(object):
                     if self._upstream_stream:
                         stream.wait_event(ready)
                     else:
-                        mean, cov = ylm_moments_device(e, r=r, dr=dr, a=a, b=b, c=c, n=n)
+                        mean, cov = moments(e, k)
                         keep.append((mean, cov))
                     e.set_moments_dev(mean, cov)
                     tab = mv = None
@@ -501,9 +543,7 @@ class EnsembleLogProb(object):
             dist.all_reduce(total, op=dist.ReduceOp.SUM)
         total = total.cpu().numpy()
         if self._apply_jac:
-            from .upstream import log_jac_samples
-
-            total = total + log_jac_samples(hyper[:, 1], hyper[:, 2])
+            total = total + log_jac_populations(hyper)
         return total
 
 

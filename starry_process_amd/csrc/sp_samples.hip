@@ -407,6 +407,112 @@ __global__ __launch_bounds__(256) void sm_finish_kernel(int N, const int32_t *__
   if (j == 0) ez[(size_t)b * N + i] = scal[4 * b + 1] * eb[i];
 }
 
+constexpr int SM_CU = 4;      // sm_combine_kernel: child slabs whose loads are issued together
+
+// Two neighbouring doubles at p, copied as 16 bytes with the alignment of a double.  A slab of N^2 doubles with N odd
+// starts on an odd multiple of 8 bytes for every second sample, and a child's slab and the sum's need not agree in that;
+// global memory takes a wide access on any multiple of 4 bytes, so no stream needs a scalar head or tail of its own.
+// How wide the access is, is the compiler's choice: hipcc of ROCm 7 emits global_load_dwordx4 / global_store_dwordx4
+// for every pair of the kernel's main path (16 loads, 2 stores per instantiation; its code holds no v_fma_f64).
+__device__ __forceinline__ double2 sm_load2(const double *p) {
+  double2 v;
+  __builtin_memcpy(&v, p, sizeof(v));
+  return v;
+}
+__device__ __forceinline__ void sm_store2(double *p, double2 v) { __builtin_memcpy(p, &v, sizeof(v)); }
+
+// The cross terms of entry e = i N + j of the second moment of a sum of C independent populations,
+//     sum_{c < d} (ez_c[lo] ez_d[hi] + ez_d[lo] ez_c[hi]),      lo = min(i, j), hi = max(i, j),
+// added to acc in the order of (c, d).  The operands go by the smaller index, as sm_finish_kernel's do, and nothing is
+// contracted: (i, j) and (j, i) carry the same bits, and so do an entry of a 16-byte pair and one taken alone.
+__device__ __forceinline__ double sm_cross(double acc, int N, int C, const double *__restrict__ ezc, int e) {
+#pragma clang fp contract(off)
+  const int i = e / N, j = e - i * N, lo = i < j ? i : j, hi = i < j ? j : i;
+  for (int c = 0; c + 1 < C; ++c) {
+    const double cl = ezc[(size_t)c * N + lo], ch = ezc[(size_t)c * N + hi];
+    for (int d = c + 1; d < C; ++d) {
+      const double t = cl * ezc[(size_t)d * N + hi], u = ezc[(size_t)d * N + lo] * ch;
+      acc += t + u;
+    }
+  }
+  return acc;
+}
+
+// The moments of a sum of C independent populations from those of its children (sp.py:1380-1382: the Ylm moments add):
+// children b C .. b C + C - 1 of ezc [B C][N], Ezc [B C][N][N] -> ez [B][N], Ez [B][N][N].
+//   CENTRAL (the children's polar-frame mean and COVARIANCE): both add.
+//   otherwise (mean and SECOND moment): ez adds; Ez = sum_c Ez_c + the cross terms of sm_cross.  Nothing is subtracted:
+//   Ez is never formed as covariance + (sum ez)(sum ez)^T - sum ez_c ez_c^T.
+// The sums run in the order of c and begin with the first child: with C = 1 the kernel is a copy, to the bit.
+// A streaming kernel: (C + 1) N^2 doubles per sample pass through once.  grid (ceil(N^2 / 1024), B): a workgroup takes
+// 1024 consecutive entries as two runs of 512, a thread one pair of each (a wavefront's pairs are 1 KiB contiguous), the
+// loads of up to SM_CU children in flight together; the last pair of an odd N^2 is one entry, taken alone.
+// Measured (B = 64, C = 2, ydeg 15, five other streams busy beside it): 25.9 us for 101 MB, 3.9 TB/s, 0.62 of the 6.3
+// TB/s achievable.  sm_cross divides once per entry and re-reads the children's vectors from cache; what that costs
+// has not been isolated.
+template <bool CENTRAL>
+__global__ __launch_bounds__(256) void sm_combine_kernel(int N, int C, const double *__restrict__ ezc,
+                                                         const double *__restrict__ Ezc, double *__restrict__ ez,
+                                                         double *__restrict__ Ez) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y, tid = threadIdx.x, NN = N * N;
+  const double *eb = ezc + (size_t)b * C * N, *Eb = Ezc + (size_t)b * C * NN;
+  double *out = Ez + (size_t)b * NN;
+  if (blockIdx.x == 0) {
+    for (int n = tid; n < N; n += 256) {
+      double acc = eb[n];
+      for (int c = 1; c < C; ++c) acc += eb[(size_t)c * N + n];
+      ez[(size_t)b * N + n] = acc;
+    }
+  }
+  const int e0 = blockIdx.x * 1024 + 2 * tid, e1 = e0 + 512;
+  if (e1 + 1 < NN) {
+    double2 a0 = make_double2(0.0, 0.0), a1 = a0;
+    for (int c0 = 0; c0 < C; c0 += SM_CU) {
+      double2 v0[SM_CU], v1[SM_CU];
+#pragma unroll
+      for (int u = 0; u < SM_CU; ++u) {
+        if (c0 + u < C) {
+          v0[u] = sm_load2(Eb + (size_t)(c0 + u) * NN + e0);
+          v1[u] = sm_load2(Eb + (size_t)(c0 + u) * NN + e1);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < SM_CU; ++u) {
+        if (c0 + u < C) {
+          if (c0 + u == 0) {
+            a0 = v0[u];
+            a1 = v1[u];
+          } else {
+            a0.x += v0[u].x;
+            a0.y += v0[u].y;
+            a1.x += v1[u].x;
+            a1.y += v1[u].y;
+          }
+        }
+      }
+    }
+    if (!CENTRAL && C > 1) {
+      a0.x = sm_cross(a0.x, N, C, eb, e0);
+      a0.y = sm_cross(a0.y, N, C, eb, e0 + 1);
+      a1.x = sm_cross(a1.x, N, C, eb, e1);
+      a1.y = sm_cross(a1.y, N, C, eb, e1 + 1);
+    }
+    sm_store2(out + e0, a0);
+    sm_store2(out + e1, a1);
+    return;
+  }
+  // the workgroup's last threads: entry by entry, those below N^2
+  for (int k = 0; k < 4; ++k) {
+    const int e = (k < 2 ? e0 : e1) + (k & 1);
+    if (e >= NN) continue;
+    double acc = Eb[e];
+    for (int c = 1; c < C; ++c) acc += Eb[(size_t)c * NN + e];
+    if (!CENTRAL && C > 1) acc = sm_cross(acc, N, C, eb, e);
+    out[e] = acc;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -563,6 +669,71 @@ int sp_ylm_moments_samples(sp_handle *h, int B, const double *samples_host, int 
   // mu[b][i] = sum_j ez[b][j] R[i][j]
   if ((rc = sp_launch_dotRx(h, ez, N, N, 1, 1, h->d_Rx90, 0, mean_ylm_dev, B, st, 1))) return rc;
   // X[b][r][n] = sum_j Ep[b][r][j] R[n][j];  Sigma[b][n][m] = sum_i X[b][i][n] R[m][i]  (the columns of X as rows)
+  if ((rc = sp_launch_dotRx(h, Ep, (long)N * N, N, 1, N, h->d_Rx90, 0, X, B, st, 1))) return rc;
+  return sp_launch_dotRx(h, X, (long)N * N, 1, N, N, h->d_Rx90, 0, cov_ylm_dev, B, st, 1);
+}
+
+}  // extern "C"
+
+// Sums of C independent spot populations (StarryProcessSum, sp.py:1335-1400), B samples per call.  The chain above runs
+// ONCE on the B C rows of samples_host [B][C][5 or 6] -- one staged upload, the same launches -- with the children's
+// moments in `extra` scratch (ez [B C][N] | Ez [B C][N][N], then `more` bytes for the caller, handed back in *more_ptr);
+// sm_combine_kernel then reduces over C into ez_dev, Ez_dev.  The arguments are checked by the callers and, row by row,
+// by polar_samples.
+static int sum_samples(sp_handle *h, int B, int C, const double *samples_host, int spread, double cutoff, double epsy,
+                       double epsy15, double *ez_dev, double *Ez_dev, void *stream, int central, size_t more,
+                       void **more_ptr) {
+  const int N = h->N, R = B * C;
+  const size_t d = sizeof(double), nv = sp_align_up(d * R * N) / d, nm = sp_align_up(d * R * N * N) / d;
+  void *xp = nullptr;
+  int rc = (spread ? polar_samples<true> : polar_samples<false>)(h, R, samples_host, cutoff, epsy, epsy15, nullptr, nullptr,
+                                                                 stream, central, d * (nv + nm) + more, &xp);
+  if (rc) return rc;
+  const double *ezc = static_cast<const double *>(xp), *Ezc = ezc + nv;
+  if (more) {
+    *more_ptr = static_cast<double *>(xp) + nv + nm;
+    ez_dev = static_cast<double *>(*more_ptr);
+    Ez_dev = ez_dev + sp_align_up(d * B * N) / d;
+  }
+  const dim3 grid((unsigned)(((long)N * N + 1023) / 1024), B);
+  if (central)
+    hipLaunchKernelGGL(sm_combine_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, N, C, ezc, Ezc, ez_dev, Ez_dev);
+  else
+    hipLaunchKernelGGL(sm_combine_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, N, C, ezc, Ezc, ez_dev, Ez_dev);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+extern "C" {
+
+int sp_polar_moments_samples_sum(sp_handle *h, int B, int C, const double *samples_host, int spread, double cutoff,
+                                 double epsy, double epsy15, double *ez_dev, double *Ez_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !samples_host || !ez_dev || !Ez_dev || C < 1 || B < 0 || (long)B * C > 65535) return SP_ERR_INVALID;
+  if (!h->d_size_basis) return SP_ERR_STATE;
+  if (B == 0) return SP_OK;
+  return sum_samples(h, B, C, samples_host, spread, cutoff, epsy, epsy15, ez_dev, Ez_dev, stream, 0, 0, nullptr);
+}
+
+// The children's polar-frame means and COVARIANCES add (sm_combine_kernel<true>); the sum is rotated back ONCE, by the
+// three launches of sp_ylm_moments_samples: they do not grow with the number of populations.
+int sp_ylm_moments_samples_sum(sp_handle *h, int B, int C, const double *samples_host, int spread, double cutoff,
+                               double epsy, double epsy15, double *mean_ylm_dev, double *cov_ylm_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !samples_host || !mean_ylm_dev || !cov_ylm_dev || C < 1 || B < 0 || (long)B * C > 65535)
+    return SP_ERR_INVALID;
+  if (!h->d_size_basis) return SP_ERR_STATE;
+  if (B == 0) return SP_OK;
+  const int N = h->N;
+  const size_t d = sizeof(double), nv = sp_align_up(d * B * N) / d, nm = sp_align_up(d * B * N * N) / d;
+  void *xp = nullptr;
+  int rc = sum_samples(h, B, C, samples_host, spread, cutoff, epsy, epsy15, nullptr, nullptr, stream, 1, d * (nv + 2 * nm),
+                       &xp);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const double *ez = static_cast<const double *>(xp), *Ep = ez + nv;
+  double *X = static_cast<double *>(xp) + nv + nm;
+  if ((rc = sp_launch_dotRx(h, ez, N, N, 1, 1, h->d_Rx90, 0, mean_ylm_dev, B, st, 1))) return rc;
   if ((rc = sp_launch_dotRx(h, Ep, (long)N * N, N, 1, N, h->d_Rx90, 0, X, B, st, 1))) return rc;
   return sp_launch_dotRx(h, X, (long)N * N, 1, N, N, h->d_Rx90, 0, cov_ylm_dev, B, st, 1);
 }

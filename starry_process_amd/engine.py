@@ -393,6 +393,51 @@ class Engine(object):
                                              self._p(mean), self._p(cov), self._stream()))
         return mean, cov
 
+    def _sample_rows_sum(self, samples, dr, **kw):
+        """_sample_rows for samples [B, C, 5] of C populations, ``dr`` None or anything that broadcasts to [B, C]: (rows
+        [B C, 5 or 6], B, C, cutoff, epsy, epsy15); the bounds are checked row by row."""
+        sm = np.asarray(samples, dtype=np.float64)
+        if sm.ndim != 3 or sm.shape[1] < 1 or sm.shape[2] != 5:
+            raise ValueError("samples must be (B, C, 5): r, a, b, c, n of each of the C populations")
+        B, C = sm.shape[:2]
+        if dr is not None:
+            try:
+                dr = np.ascontiguousarray(np.broadcast_to(np.asarray(dr, dtype=np.float64), (B, C))).reshape(-1)
+            except ValueError:
+                raise ValueError("dr must be a scalar, one value per population or one per sample and population")
+        rows, _, cutoff, epsy, epsy15 = self._sample_rows(sm.reshape(B * C, 5), dr, **kw)
+        return rows, B, C, cutoff, epsy, epsy15
+
+    def polar_moments_samples_sum(self, samples, ez=None, Ez=None, dr=None, **kw):
+        """samples [B, C, 5]: (r [degrees], a, b, c, n) of each of C independent spot populations on one star, B samples
+        -> (ez [B, N], Ez [B, N, N]) device tensors: the polar-frame moments of the SUM of the populations
+        (StarryProcessSum), in one library call (sp_polar_moments_samples_sum).  ``dr``: None, or the half-widths of the
+        radius laws in degrees, broadcast to [B, C] (0 where a population has one radius).  Bounds and keywords are
+        polar_moments_samples'; ValueError before anything is launched."""
+        sm, B, C, cutoff, epsy, epsy15 = self._sample_rows_sum(samples, dr, **kw)
+        if ez is None:
+            ez = self.empty(B, self.N)
+        if Ez is None:
+            Ez = self.empty(B, self.N, self.N)
+        assert tuple(ez.shape) == (B, self.N) and tuple(Ez.shape) == (B, self.N, self.N)
+        check(self._L.sp_polar_moments_samples_sum(self._h, B, C, hptr(sm), int(dr is not None), cutoff, epsy, epsy15,
+                                                   self._p(ez), self._p(Ez), self._stream()))
+        return ez, Ez
+
+    def ylm_moments_samples_sum(self, samples, mean=None, cov=None, dr=None, **kw):
+        """samples [B, C, 5] -> (mean_ylm [B, N], cov_ylm [B, N, N]) device tensors: the Ylm-frame moments of the sum of
+        C populations, B samples in one library call (sp_ylm_moments_samples_sum) -- what the conditional branch reads.
+        Arguments as polar_moments_samples_sum."""
+        sm, B, C, cutoff, epsy, epsy15 = self._sample_rows_sum(samples, dr, **kw)
+        if mean is None:
+            mean = self.empty(B, self.N)
+        if cov is None:
+            cov = self.empty(B, self.N, self.N)
+        assert tuple(mean.shape) == (B, self.N) and tuple(cov.shape) == (B, self.N, self.N)
+        check(self._L.sp_ylm_moments_samples_sum(self._h, B, C, hptr(sm), int(dr is not None), cutoff, epsy, epsy15,
+                                                 self._p(mean), self._p(cov), self._stream()))
+        return mean, cov
+
     def kernel_table_samples(self, ez, Ez, rta1, covpts, tab=None, meanvar=None):
         """ez [B, N], Ez [B, N, N], rta1 [ntab, N] (device) -> tab [B ntab, 5, covpts + 4], meanvar [B ntab, 2]: table
         b ntab + i belongs to sample b and flux operator i (sp_kernel_table_samples)."""

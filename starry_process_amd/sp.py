@@ -299,19 +299,31 @@ class StarryProcess(object):
         time-variability tutorial.  Such a column overrides the constructor's value or the argument of the same name.
         Bounds of the three: i in [0, 90], p >= 0 (flux.py:233-254), tau > 0.  ``out_of_bounds="inf"``: samples outside
         the reference's parameter bounds (a ValueError there and, by default, here) get -inf and are not evaluated."""
+        cols = SampleColumns.from_params(params, self._marginalize_over_inclination, self._time_variable, dr=self._dr)
+        return self._log_likelihood_samples(cols, t, flux, data_cov, samples, i, p, u, baseline_mean, baseline_var, depth,
+                                            out_of_bounds)
+
+    def _sample_process(self, cols, hyper, dr, kw):
+        """The process of one sample on the sample-by-sample route: ``hyper`` (r, a, b, c, n), ``dr`` its spread."""
+        r, a, b, c, n = hyper
+        return StarryProcess(r=r, dr=dr, a=a, b=b, c=c, n=n, **kw)
+
+    def _log_likelihood_samples(self, cols, t, flux, data_cov, samples, i, p, u, baseline_mean, baseline_var, depth,
+                                out_of_bounds, ordered=False):
+        """log_likelihood_samples on the column layout ``cols``; ``ordered``: the columns are in the layout's own order
+        already."""
         from .calibrate import MAX_STREAMS_SAMPLES, SampleBatches, clamp_depth
         from .engine import engine_slots
 
         f = self._flux
         t, i, p, u = f._ingest(t, i, p, u)
         K = t.shape[0]
-        cols = SampleColumns.from_params(params, self._marginalize_over_inclination, self._time_variable, dr=self._dr)
         free = cols.free
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
         if samples.shape[1] != len(cols.params):
             raise ValueError("samples must be (ns, %d): %s" % (len(cols.params), ", ".join(cols.params)))
         # the columns in the layout's own order (stars.SampleColumns)
-        samples = np.ascontiguousarray(samples[:, cols.permutation])
+        samples = np.ascontiguousarray(samples if ordered else samples[:, cols.permutation])
         if out_of_bounds == "raise":
             cols.check_ipt(samples)
         if out_of_bounds == "inf":
@@ -319,9 +331,9 @@ class StarryProcess(object):
             if not ok.all():
                 out = np.full(samples.shape[0], -np.inf)
                 if ok.any():
-                    out[ok] = np.asarray(self.log_likelihood_samples(t, flux, data_cov, samples[ok], i=i, p=p, u=u,
-                                                                     baseline_mean=baseline_mean, baseline_var=baseline_var,
-                                                                     depth=depth, params=cols.names))
+                    out[ok] = np.asarray(self._log_likelihood_samples(cols, t, flux, data_cov, samples[ok], i, p, u,
+                                                                      baseline_mean, baseline_var, depth, "raise",
+                                                                      ordered=True))
                 return Eager(out)
         elif out_of_bounds != "raise":
             raise ValueError("out_of_bounds must be 'raise' or 'inf'")
@@ -342,11 +354,11 @@ class StarryProcess(object):
                       covpts=self._covpts, upstream="device")
             out = []
             hyper, drs, fields = cols.split(samples)
-            for k, (r, a, b, c, n) in enumerate(hyper):
+            for k in range(hyper.shape[0]):
                 at = {key: v[k] for key, v in fields.items()}        # (this sample's free terms over the arguments)
                 if "tau" in at:
                     kw["tau"] = at["tau"]
-                out.append(float(StarryProcess(r=r, dr=drs[k] if cols.dr_free else drs, a=a, b=b, c=c, n=n, **kw).log_likelihood(
+                out.append(float(self._sample_process(cols, hyper[k], cols.take_dr(drs, k), kw).log_likelihood(
                     t, flux, data_cov, i=at.get("inc_deg", i), p=at.get("period", p), u=u,
                     baseline_mean=at.get("baseline_mean", baseline_mean), baseline_var=at.get("baseline_var", baseline_var))))
             return Eager(np.array(out))
@@ -368,7 +380,7 @@ class StarryProcess(object):
                                diag_dev=e0.f64(data_cov.reshape(1, K)) if data_cov.ndim == 1 else None,
                                temporal=self._temporal, norm_order=self._normN, zmax=self._normzmax, upstream_kwargs=ukw,
                                dr=dr, free=free, conditional=not self._marginalize_over_inclination,
-                               normalized=self._normalized)
+                               normalized=self._normalized, populations=cols.populations)
             cache = self._sample_batches = (key, sb)
         out = cache[1](samples)
         import torch
@@ -989,3 +1001,55 @@ class StarryProcessSum(StarryProcess):
 
     def log_jac(self):
         raise NotImplementedError("the latitude Jacobian is defined per child process")
+
+    UPSTREAM_KEYS = ("epsy", "epsy15", "spts", "eps4", "smoothing", "sfac", "cutoff", "abmin", "log_alpha_max",
+                     "log_beta_max")
+
+    def log_likelihood_samples(
+        self,
+        t,
+        flux,
+        data_cov,
+        samples,
+        i=defaults["i"],
+        p=defaults["p"],
+        u=defaults["u"][: defaults["udeg"]],
+        baseline_mean=defaults["baseline_mean"],
+        baseline_var=defaults["baseline_var"],
+        depth=6,
+        out_of_bounds="raise",
+        params=None,
+    ):
+        """``log_likelihood`` of a sum of C spot populations with THIS sum's settings at many hyperparameter vectors:
+        samples (ns, 5 C [+ extras]), a block (r, a, b, c, n) per child in the order of the sum, -> (ns,) values, each
+        what ``(StarryProcess(<row 1>, upstream="device") + StarryProcess(<row 2>, upstream="device") +
+        ...).log_likelihood(...)`` returns.  ``params`` names the columns: by default r1, a1, b1, c1, n1, r2, ..., and in
+        any order those and, each at most once, "dr1" ... "drC", "baseline_mean", "baseline_log_var", "i", "p"
+        (``stars.SampleColumns(populations=C)``).  Every child keeps the dr of its own constructor unless a drK column
+        overrides it.  Batched and sample-by-sample routes, ``depth`` and ``out_of_bounds`` as the base class's (the
+        batched step: sp_polar_moments_samples_sum / sp_ylm_moments_samples_sum).  ValueError for a batch with the wrong
+        number of columns, a child built from ``mean_ylm`` / ``cov_ylm`` (it has no hyperparameters to sample) and
+        children that disagree in the upstream keywords (``epsy``, ``spts``, ...)."""
+        C = len(self._children)
+        if not all(ch._from_hyper for ch in self._children):
+            raise ValueError("a child of this sum was built from mean_ylm / cov_ylm: it has no hyperparameters to sample")
+        first = self._children[0]._kwargs
+        for ch in self._children[1:]:
+            for key in self.UPSTREAM_KEYS:
+                if (key in first) != (key in ch._kwargs) or (key in first and first[key] != ch._kwargs[key]):
+                    raise ValueError("the children of this sum disagree in the upstream keyword `%s`" % key)
+        each = [ch._dr for ch in self._children]
+        if params is None:
+            params = SampleColumns(dr=each, populations=C).names
+        cols = SampleColumns.from_params(params, self._marginalize_over_inclination, False, dr=each, populations=C)
+        return self._log_likelihood_samples(cols, t, flux, data_cov, samples, i, p, u, baseline_mean, baseline_var, depth,
+                                            out_of_bounds)
+
+    def _sample_process(self, cols, hyper, dr, kw):
+        """The sum of one sample's C populations, each built on the device: ``hyper`` [C, 5], ``dr`` None or [C]."""
+        total = None
+        for q, (r, a, b, c, n) in enumerate(hyper):
+            one = dr is None or (cols.dr[q] is None)          # (a population without a spread keeps dr=None)
+            child = StarryProcess(r=r, dr=None if one else dr[q], a=a, b=b, c=c, n=n, **kw)
+            total = child if total is None else total + child
+        return total

@@ -153,17 +153,51 @@ class SampleColumns(object):
     ``dr``: None (one spot radius), a number (the same spread for every sample) or "free" (a column); ``free``: which of
     FREE are columns, in any order; ValueError for settings that name no batch.  Attributes: ``dr`` (None, the float or
     "free"), ``dr_free``, ``free`` (in column order), ``names`` (the columns as ``log_likelihood_samples``' params spell
-    them) and ``columns`` (the short spelling: m, v for the baseline terms)."""
+    them) and ``columns`` (the short spelling: m, v for the baseline terms).
+
+    ``populations`` = C > 1: a sum of C independent spot populations on one star (``StarryProcessSum``).  The
+    hyperparameter block repeats per population and its names carry the population's number, r1[, dr1], a1, b1, c1, n1,
+    r2, ..., followed by the free terms as above.  ``dr`` is then one setting for all populations or a sequence of C
+    settings, and the attributes ``dr`` and ``dr_free`` are tuples of C."""
 
     FREE = ("baseline_mean", "baseline_log_var", "i", "p", "tau")
     SHORT = {"baseline_mean": "m", "baseline_log_var": "v"}
     FIELDS = {"baseline_mean": "baseline_mean", "baseline_log_var": "baseline_var", "i": "inc_deg", "p": "period",
               "tau": "tau"}          # stars_for_samples' keywords
+    HYPER = ("r", "dr", "a", "b", "c", "n")
 
-    def __init__(self, dr=None, free=(), conditional=False, temporal=None, params=None):
+    def __init__(self, dr=None, free=(), conditional=False, temporal=None, params=None, populations=1):
         free = (free,) if isinstance(free, str) else tuple(free)
         if len(set(free)) != len(free) or any(f not in self.FREE for f in free):
             raise ValueError("free must be a subset of %r" % (self.FREE,))
+        C = int(populations)
+        if C < 1:
+            raise ValueError("populations must be at least 1")
+        if C > 1 and isinstance(dr, (list, tuple, np.ndarray)):
+            if len(dr) != C:
+                raise ValueError("dr must be one setting or one per population (%d)" % C)
+            settings = [self._dr_setting(d) for d in dr]
+        else:
+            settings = [self._dr_setting(dr)] * C
+        if "i" in free and not conditional:
+            raise ValueError("a free inclination needs conditional=True: the marginal branch integrates over it")
+        if "tau" in free and temporal is None:
+            raise ValueError("a free tau needs a temporal kernel")
+        self.populations = C
+        if C == 1:
+            self.dr, self.dr_free = settings[0], isinstance(settings[0], str)
+        else:
+            self.dr, self.dr_free = tuple(settings), tuple(isinstance(d, str) for d in settings)
+        self.free = tuple(f for f in self.FREE if f in free)
+        self.names = self.hyper_names(C, [isinstance(d, str) for d in settings]) + self.free
+        self.columns = tuple(self.SHORT.get(q, q) for q in self.names)
+        # (a caller's own order of the same names: samples[:, permutation] has the columns in this layout's)
+        self.params = self.names if params is None else tuple(params)
+        self.permutation = [self.params.index(q) for q in self.names]
+
+    @staticmethod
+    def _dr_setting(dr):
+        """One population's spread: None, "free" or a number of degrees inside [0, 90] (ValueError otherwise)."""
         if isinstance(dr, str):
             if dr != "free":
                 raise ValueError("dr must be None, a number or 'free'")
@@ -172,53 +206,94 @@ class SampleColumns(object):
 
             dr = float(dr)
             CheckBoundsOp(name="dr", lower=0.0, upper=0.5 * np.pi)(dr * (np.pi / 180))
-        if "i" in free and not conditional:
-            raise ValueError("a free inclination needs conditional=True: the marginal branch integrates over it")
-        if "tau" in free and temporal is None:
-            raise ValueError("a free tau needs a temporal kernel")
-        self.dr, self.dr_free = dr, isinstance(dr, str)
-        self.free = tuple(f for f in self.FREE if f in free)
-        self.names = ("r",) + (("dr",) if self.dr_free else ()) + ("a", "b", "c", "n") + self.free
-        self.columns = tuple(self.SHORT.get(q, q) for q in self.names)
-        # (a caller's own order of the same names: samples[:, permutation] has the columns in this layout's)
-        self.params = self.names if params is None else tuple(params)
-        self.permutation = [self.params.index(q) for q in self.names]
+        return dr
 
     @classmethod
-    def from_params(cls, params, marginalize_over_inclination, time_variable, dr=None):
+    def hyper_names(cls, populations=1, dr_free=(False,)):
+        """The hyperparameter columns: r[, dr], a, b, c, n, numbered per population when there are several."""
+        tag = [""] if populations == 1 else ["%d" % (k + 1) for k in range(populations)]
+        return tuple(q + tag[k] for k in range(populations) for q in cls.HYPER if q != "dr" or dr_free[k])
+
+    @classmethod
+    def from_params(cls, params, marginalize_over_inclination, time_variable, dr=None, populations=1):
         """The layout that ``log_likelihood_samples``' ``params`` name, in whatever order, on a process of these two
         settings and this spot-size spread ``dr`` (None or a number: what holds where "dr" is no column); ``params`` keeps
         the caller's order and ``samples[:, permutation]`` has the columns in this layout's.  ValueError for an unknown or
         repeated name, a missing hyperparameter, "i" on a process that marginalises over the inclination, "tau" on one
-        built without a temporal kernel."""
+        built without a temporal kernel.  ``populations`` = C > 1: the names are numbered (r1, dr1, a1, ..., r2, ...) and
+        ``dr`` may be a sequence of C, one per population."""
         params = tuple(params)
-        if (len(set(params)) != len(params) or any(q not in ("r", "dr", "a", "b", "c", "n") + cls.FREE for q in params)
-                or any(q not in params for q in ("r", "a", "b", "c", "n"))):
-            raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, baseline_log_var, "
-                             "i, p, tau")
+        C = int(populations)
+        every = cls.hyper_names(C, [True] * C)
+        if (len(set(params)) != len(params) or any(q not in every + cls.FREE for q in params)
+                or any(q not in params for q in cls.hyper_names(C, [False] * C))):
+            if C == 1:
+                raise ValueError("params must name r, a, b, c, n and, at most once each, dr, baseline_mean, "
+                                 "baseline_log_var, i, p, tau")
+            raise ValueError("params must name r, a, b, c, n of each of the %d populations (r1, a1, ..., n%d) and, at most "
+                             "once each, dr1 ... dr%d, baseline_mean, baseline_log_var, i, p, tau" % (C, C, C))
         if "i" in params and marginalize_over_inclination:
             raise ValueError("params names i, but this process marginalises over the inclination")
         if "tau" in params and not time_variable:
             raise ValueError("params names tau, but this process was built without a temporal kernel (tau=None)")
-        return cls("free" if "dr" in params else dr, [q for q in params if q in cls.FREE], params=params,
-                   conditional=not marginalize_over_inclination, temporal=time_variable or None)
+        if C == 1:
+            dr = "free" if "dr" in params else dr
+        else:
+            each = list(dr) if isinstance(dr, (list, tuple, np.ndarray)) else [dr] * C
+            if len(each) != C:
+                raise ValueError("dr must be one setting or one per population (%d)" % C)
+            dr = ["free" if "dr%d" % (k + 1) in params else each[k] for k in range(C)]
+        return cls(dr, [q for q in params if q in cls.FREE], params=params,
+                   conditional=not marginalize_over_inclination, temporal=time_variable or None, populations=C)
+
+    def _blocks(self):
+        """(first column, whether dr is a column) of every population's hyperparameter block, then the first free column."""
+        free, col, out = (self.dr_free,) if self.populations == 1 else self.dr_free, 0, []
+        for f in free:
+            out.append((col, f))
+            col += 6 if f else 5
+        return out, col
 
     def split(self, samples):
         """samples [B, len(names)] (float64, in this layout's order) -> (the rows (r, a, b, c, n) [B, 5], contiguous;
         dr: None, the constructor's number or the column [B]; the free terms as stars_for_samples takes them, [B] each:
-        baseline_mean, baseline_var = 10 ** v, inc_deg [degrees], period, tau)."""
-        c0 = 2 if self.dr_free else 1
-        hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
+        baseline_mean, baseline_var = 10 ** v, inc_deg [degrees], period, tau).  With C > 1 populations the rows are
+        [B, C, 5] and dr is None when no population has a spread, else [B, C] with 0 where a population has none."""
+        blocks, c1 = self._blocks()
         fields = {self.FIELDS[f]: 10.0 ** samples[:, k] if f == "baseline_log_var" else samples[:, k]
-                  for k, f in enumerate(self.free, c0 + 4)}
-        return hyper, samples[:, 1] if self.dr_free else self.dr, fields
+                  for k, f in enumerate(self.free, c1)}
+        if self.populations == 1:
+            c0 = 2 if self.dr_free else 1
+            hyper = np.ascontiguousarray(np.hstack([samples[:, :1], samples[:, c0:c0 + 4]]))
+            return hyper, samples[:, 1] if self.dr_free else self.dr, fields
+        B = samples.shape[0]
+        hyper = np.empty((B, self.populations, 5), dtype=np.float64)
+        dr = None if all(d is None for d in self.dr) else np.zeros((B, self.populations), dtype=np.float64)
+        for k, (col, f) in enumerate(blocks):
+            hyper[:, k, 0] = samples[:, col]
+            hyper[:, k, 1:] = samples[:, col + (2 if f else 1):col + (6 if f else 5)]
+            if f:
+                dr[:, k] = samples[:, col + 1]
+            elif self.dr[k] is not None:
+                dr[:, k] = self.dr[k]
+        return hyper, dr, fields
+
+    def take_dr(self, dr, index):
+        """``split``'s dr for the samples ``index`` (an int or a slice), as the moment calls and the constructors take it:
+        the constructor's setting (None or the number) where dr is no column of one population, else the rows -- [C] or
+        [n, C] for C > 1 populations, None when no population has a spread."""
+        if self.populations == 1:
+            return dr[index] if self.dr_free else dr
+        return None if dr is None else dr[index]
 
     def in_bounds(self, samples):
         """Boolean mask of the rows of samples (in this layout's order) inside the reference's bounds: samples_in_bounds
-        of the hyperparameter columns, every column finite, ipt_in_bounds of i, p and tau."""
+        of the hyperparameter columns (of every population), every column finite, ipt_in_bounds of i, p and tau."""
         samples = np.atleast_2d(np.asarray(samples, dtype=np.float64))
-        return (samples_in_bounds(samples[:, :6 if self.dr_free else 5], dr=self.dr_free)
-                & np.all(np.isfinite(samples), axis=1) & ipt_in_bounds(samples, self.names))
+        ok = np.all(np.isfinite(samples), axis=1) & ipt_in_bounds(samples, self.names)
+        for col, f in self._blocks()[0]:
+            ok &= samples_in_bounds(samples[:, col:col + (6 if f else 5)], dr=f)
+        return ok
 
     def check_ipt(self, samples):
         """ValueError unless every row's i, p and tau are inside their bounds: the three that sample_parameters, which
