@@ -692,6 +692,31 @@ int sp_ylm_temporal(sp_handle *h, int ns, int Nt, const double *Lt_dev, long ldl
 int sp_flux_rows(sp_handle *h, int nrows, int Nt, const double *A_dev, long lda, const double *y_dev, int normalized,
                  double *out_dev, void *stream);
 
+/* ---- posterior maps of a time-variable process (the case sp.py:602-605 leaves open; csrc/sp_ylm_temporal_cond.hip,
+ * DESIGN.md 16) ----
+ * The model of the conditional likelihood (sp.py:696-698, 1135-1157): y(t) = mu_y + d(t), cov(d(t), d(t')) =
+ * k(t, t', tau) Sigma_y, C = (A Sigma_y A^T) o k(t, t) + data_cov + baseline_var 1 1^T.  One star per call: K observed
+ * times t_dev [K], T frame times tmap_dev [T], R residual vectors.  With B = A Sigma_y and k_j = k(tmap_j, t, tau):
+ *   out_dev [R, T, N]   out[r][j] = B^T (k_j o z_r): the posterior mean of frame j less mu_y for z = C^-1 (flux -
+ *                       baseline_mean - A mu_y), or the data term of a pathwise sample (Matheron's rule)
+ *   ycov_dev [T, N, N]  ycov[j] = Sigma_y - B^T (C^-1 o k_j k_j^T) B, exactly symmetric; NULL: not formed, and nothing
+ *                       of size N x K or N x N per frame is
+ * A_dev [K, N] the design matrix (row stride lda >= N), Sigma_dev [N, N] (row stride lds >= N; symmetric: its rows are
+ * read as its columns), Cinv_dev [Kr, Kr] = C^-1, Kr = roundup(K, 64), FULL and symmetric, rows and columns >= K zero,
+ * Z_dev [R, K] = the rows z_r (row stride ldz >= K), temporal SP_TEMPORAL_MATERN32 or SP_TEMPORAL_EXPSQUARED
+ * (SP_ERR_INVALID otherwise).  info_dev (may be NULL): info_dev[0] != 0 -- C did not factor -- makes every output NaN.
+ * Per frame: G_j C^-1 and (G_j C^-1) G_j^T, G_j = B^T diag(k_j), on the matrix cores, batched over the frames of a
+ * pass; the passes keep the workspace below about 1 GiB (beyond one frame's needs).  Every sum runs in a fixed order
+ * and no product's shape depends on T: a frame has the same bits alone, in any batch and in any pass.  T = 0 or R = 0
+ * is SP_OK and touches nothing.  workspace_dev: sp_ylm_conditional_temporal_workspace_bytes(h, K, T, R, with_cov)
+ * bytes, with_cov = (ycov_dev != NULL).  All launches go to `stream`; nothing is synchronised.                    */
+size_t sp_ylm_conditional_temporal_workspace_bytes(sp_handle *h, int K, int T, int R, int with_cov);
+int sp_ylm_conditional_temporal(sp_handle *h, int K, int T, int R, const double *A_dev, long lda,
+                                const double *Sigma_dev, long lds, const double *Cinv_dev, const double *Z_dev, long ldz,
+                                const double *t_dev, const double *tmap_dev, double tau, int temporal,
+                                const int32_t *info_dev, double *out_dev, double *ycov_dev, void *workspace_dev,
+                                void *stream);
+
 /* ---- synthetic spotted-star ensembles (calibrate/generate.py:10-190; csrc/sp_generate.hip) --------
  * S stars painted on an nlat x nlon grid (pixel p = ilat nlon + ilon; npix = nlat nlon): lat_dev [nlat], lon_dev
  * [nlon] in degrees, w_dev [nlat] the weights cos(lat); spots_dev [nspots, 4] rows (lon, lat, radius, contrast) in
@@ -916,6 +941,11 @@ int sp_debug_set_small_k(int on);
  * changes sp_predict_workspace_bytes too, so size the workspace after setting it.  Which stars share a pass changes,
  * no star's bits do.                                                                                              */
 int sp_debug_set_predict_chunk_bytes(size_t bytes);
+/* (debug, process-wide) the workspace budget of one pass of frames of sp_ylm_conditional_temporal (default about
+ * 1 GiB; 0 = back to the default): a small budget forces several passes over a few frames.  It changes
+ * sp_ylm_conditional_temporal_workspace_bytes too, so size the workspace after setting it.  Which frames share a pass
+ * changes, no frame's bits do.                                                                                      */
+int sp_debug_set_ylm_temporal_chunk_bytes(size_t bytes);
 /* (debug, host only) how the hot assembly kernel (csrc/sp_assemble.hip, assemble_sums_kernel) cuts a star's
  * ntr (ntr + 1) / 2 lower tiles (column-strip order) into nchunk chunks of equal COST: start_host[c] = first tile
  * of chunk c, c = 0 .. nchunk (start_host[nchunk] = the number of tiles).  A function of the shape alone.   */

@@ -118,6 +118,8 @@ PROTOTYPES = {
     "sp_ylm_temporal_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_temporal": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _V, _V, _V, _V]),
     "sp_flux_rows": (_I, [_V, _I, _I, _V, _L, _V, _I, _V, _V]),
+    "sp_ylm_conditional_temporal_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
+    "sp_ylm_conditional_temporal": (_I, [_V, _I, _I, _I, _V, _L, _V, _L, _V, _V, _L, _V, _V, _D, _I, _V, _V, _V, _V, _V]),
     "sp_generate_paint": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _L, _V]),
     "sp_generate_gram_workspace_bytes": (ctypes.c_size_t, [_V]),
     "sp_generate_gram": (_I, [_V, _I, _V, _L, _V, _D, _V, _L, _V, _L, _V, _V, _V]),
@@ -142,6 +144,7 @@ PROTOTYPES = {
     "sp_debug_set_syrk128_from": (_I, [_I]),
     "sp_debug_set_small_k": (_I, [_I]),
     "sp_debug_set_predict_chunk_bytes": (_I, [ctypes.c_size_t]),
+    "sp_debug_set_ylm_temporal_chunk_bytes": (_I, [ctypes.c_size_t]),
     "sp_debug_set_syrk_symdiag": (_I, [_I]),
     "sp_debug_set_look_ahead": (_I, [_V, _I]),
     "sp_debug_set_panel_layout": (_I, [_V, _I, _I]),

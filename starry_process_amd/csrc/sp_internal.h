@@ -425,6 +425,19 @@ int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B,
                       int lower_only, int batch, hipStream_t st, int skip_tile00 = 0,
                       const LazyCov *lazy = nullptr, const int32_t *bsel = nullptr, int nsel = 0);
 
+// sp_pixel.hip: out[b][j][i] = out[b][i][j] for i > j on `batch` (<= 65535) n x n matrices; only entries on or below
+// the diagonal are read
+int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st);
+// sp_ylm_temporal_cond.hip: the C ABI's posterior maps of a time-variable process (include/starry_process_amd.h)
+extern "C" {
+size_t sp_ylm_conditional_temporal_workspace_bytes(sp_handle *h, int K, int T, int R, int with_cov);
+int sp_ylm_conditional_temporal(sp_handle *h, int K, int T, int R, const double *A_dev, long lda,
+                                const double *Sigma_dev, long lds, const double *Cinv_dev, const double *Z_dev, long ldz,
+                                const double *t_dev, const double *tmap_dev, double tau, int temporal,
+                                const int32_t *info_dev, double *out_dev, double *ycov_dev, void *workspace_dev,
+                                void *stream);
+}
+
 // round-3 panel kernel (sp_panel.hip)
 struct DiagFuse;
 enum { SP_PANEL_D = 1, SP_PANEL_T = 2, SP_PANEL_TAILD = 4, SP_PANEL_LA = 8, SP_PANEL_FIRSTLA = 16 };

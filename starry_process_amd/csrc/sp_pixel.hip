@@ -87,6 +87,19 @@ __global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__rest
 }
 
 size_t pT_ld(int N) { return (size_t)sp_roundup(N, 32); }
+}  // namespace
+
+// the upper triangles of `batch` n x n matrices from their lower ones (pixel_mirror_kernel): batch <= 65535
+int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st) {
+  if (n <= 0 || batch <= 0) return SP_OK;
+  const long nt = (n + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
+  if (ntiles > 0x7fffffffL || batch > 65535) return SP_ERR_INVALID;
+  hipLaunchKernelGGL(pixel_mirror_kernel, dim3((unsigned)ntiles, batch), dim3(256), 0, st, n, out, ldo, strideOut);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+namespace {
 
 // A1^T (leading N x N block of the degree ydeg + udeg change of basis), rows padded to Kp with zeros, on the
 // device: uploaded once per handle through the staging ring, kept in the handle's pixel scratch
@@ -161,11 +174,7 @@ int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, lon
   if ((rc = sp_launch_gemm_nt(T, Kp, strideT, M_dev, ldm, 0, out_dev, ldo, strideOut, npts, npts, N, 1.0, 0, 1, S,
                               st)))
     return rc;
-  const long nt = (npts + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
-  if (ntiles > 0x7fffffffL) return SP_ERR_INVALID;
-  hipLaunchKernelGGL(pixel_mirror_kernel, dim3((unsigned)ntiles, S), dim3(256), 0, st, npts, out_dev, ldo, strideOut);
-  SP_LAUNCH_CHECK();
-  return SP_OK;
+  return sp_launch_mirror_lower(out_dev, npts, ldo, strideOut, S, st);
 }
 
 int sp_pixel_render(sp_handle *h, int nmaps, int npix, const double *y_dev, const double *M_dev, long ldm,

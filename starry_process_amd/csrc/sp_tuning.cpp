@@ -57,6 +57,7 @@ void sp_tuning_read(char *(*get)(const char *), SpTuning *t, SpProcTuning *p) {
     if (s.scope == SP_PER_PROCESS && p) p->*(s.p) = v;
   }
   if (p) p->predict_chunk_bytes = SP_PREDICT_CHUNK_BYTES;
+  if (p) p->ylm_temporal_chunk_bytes = SP_YLM_TEMPORAL_CHUNK_BYTES;
 }
 void sp_tuning_defaults(SpTuning *t, SpProcTuning *p) { sp_tuning_read(nullptr, t, p); }
 
@@ -209,6 +210,10 @@ int sp_debug_set_syrk_symdiag(int on) {
 }
 int sp_debug_set_predict_chunk_bytes(size_t bytes) {
   proc_state().cur.predict_chunk_bytes = bytes ? bytes : SP_PREDICT_CHUNK_BYTES;
+  return SP_OK;
+}
+int sp_debug_set_ylm_temporal_chunk_bytes(size_t bytes) {
+  proc_state().cur.ylm_temporal_chunk_bytes = bytes ? bytes : SP_YLM_TEMPORAL_CHUNK_BYTES;
   return SP_OK;
 }
 

@@ -32,8 +32,12 @@ struct SpProcTuning {
       syrk128_from, asm_tiles, plan_tiles;
   // (no environment variable: sp_debug_set_predict_chunk_bytes; the workspace of one pass of stars of sp_predict_*)
   size_t predict_chunk_bytes;
+  // (no environment variable: sp_debug_set_ylm_temporal_chunk_bytes; the workspace of one pass of frames of
+  //  sp_ylm_conditional_temporal)
+  size_t ylm_temporal_chunk_bytes;
 };
 #define SP_PREDICT_CHUNK_BYTES ((size_t)4 << 30)
+#define SP_YLM_TEMPORAL_CHUNK_BYTES ((size_t)1 << 30)
 
 enum SpScope { SP_PER_HANDLE, SP_PER_PROCESS };
 struct SpSwitch {

@@ -829,6 +829,40 @@ class Engine(object):
                                    int(bool(normalized)), self._p(out), self._stream()))
         return out
 
+    # -- posterior maps of a time-variable process (sp_ylm_conditional_temporal) -------------------------
+    def ylm_conditional_temporal(self, A, cov_ylm, C, resid, t, t_map, tau, temporal, with_cov=True):
+        """Posterior maps of one star at the frame times ``t_map`` [T]: device tensors in, device tensors out, nothing
+        crosses to the host in between.  A [K, N] the design matrix at the observed times t [K]; cov_ylm [N, N];
+        C [K, K] = (A Sigma_y A^T) o k(t, t) + data covariance + baseline_var; resid [R, K] residual vectors.
+        Returns (out [R, T, N] = B^T (k_j o C^-1 resid_r) with B = A Sigma_y, ycov [T, N, N] = Sigma_y - B^T (C^-1 o
+        k_j k_j^T) B or None, info [1]): C^-1 by ``spd_inverse``, its products with the residuals by ``gemm_nt``, the
+        frames by sp_ylm_conditional_temporal.  info != 0 (C not positive definite): every output is NaN."""
+        torch = _torch()
+        A, Sig, C = self.f64(A), self.f64(cov_ylm), self.f64(C)
+        resid, t, t_map = self.f64(resid), self.f64(t).reshape(-1), self.f64(t_map).reshape(-1)
+        K, T, R = int(t.shape[0]), int(t_map.shape[0]), int(resid.shape[0])
+        if A.shape != (K, self.N) or Sig.shape != (self.N, self.N) or C.shape != (K, K) or resid.dim() != 2 or \
+                resid.shape[1] != K or K < 1:
+            raise ValueError("need A [K, N], cov_ylm [N, N], C [K, K] and resid [R, K] with N = %d, K = %d" % (self.N, K))
+        out = self.empty(R, T, self.N)
+        ycov = self.empty(T, self.N, self.N) if with_cov else None
+        info = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if T == 0 or R == 0:
+            return out, ycov, info
+        low, _, info = self.spd_inverse(C, full=False)          # [1, Kr, Kr]: the lower 64 x 64 tiles of C^-1
+        low = torch.tril(low[0])
+        Cinv = (low + torch.tril(low, -1).T).contiguous()       # full and exactly symmetric, zero beyond K
+        Kr = int(Cinv.shape[0])
+        Rp = torch.zeros(R, Kr, dtype=torch.float64, device=self.device)
+        Rp[:, :K] = resid
+        Z = self.gemm_nt(Rp, Cinv)                              # rows (C^-1 resid_r)^T, [R, Kr]
+        ws = self._scratch(self._L.sp_ylm_conditional_temporal_workspace_bytes(self._h, K, T, R, int(bool(with_cov))))
+        check(self._L.sp_ylm_conditional_temporal(
+            self._h, K, T, R, self._p(A), self.N, self._p(Sig), self.N, self._p(Cinv), self._p(Z), Kr, self._p(t),
+            self._p(t_map), float(tau), TEMPORAL[temporal], self._p(info), self._p(out), self._p(ycov), self._p(ws),
+            self._stream()))
+        return out, ycov, info
+
     # -- synthetic ensembles (sp_generate_*; calibrate/generate.py) -------------------------------------------------
     GEN_ROWS, GEN_DEPTH = 128, 32   # padding of the projection's operands (rows, pixels): sp_generate_paint
 

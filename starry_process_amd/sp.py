@@ -758,6 +758,129 @@ class StarryProcess(object):
         out += ymu[None, :]
         return Eager(out.cpu().numpy())
 
+    # -- posterior of the surface map of a time-variable process --------------------------------------
+    # y(t) = mu_y + d(t) with cov(d(t), d(t')) = k(t, t', tau) Sigma_y, the model of cov() / log_likelihood on the
+    # conditional branch (sp.py:696-698, 1135-1157): C = (A Sigma_y A^T) o k(t, t) + data_cov + baseline_var 1 1^T.
+    # With B = A Sigma_y, alpha = C^-1 (flux - baseline_mean - A mu_y) and k_j = k(t*_j, t, tau), frame t*_j has
+    # ymu_j = mu_y + B^T (k_j o alpha) and ycov_j = Sigma_y - B^T (C^-1 o k_j k_j^T) B (sp_ylm_conditional_temporal).
+    def _ylm_temporal_args(self, t, flux, data_cov, t_map, baseline_mean, baseline_var, matrix_ok):
+        """The checked host arguments (t [K], flux [K], data_cov, t_map [T], baseline_mean, baseline_var): every error
+        of the two methods below is raised here, before any device work."""
+        if self._normalized:
+            raise NotImplementedError("Method not implemented when the flux is normalized.")
+        if not self._time_variable:
+            raise NotImplementedError("Method implemented for time-variable maps only (tau=...): use `ylm_conditional` "
+                                      "for a static map.")
+        t = np.ascontiguousarray(np.asarray(t, dtype=np.float64).reshape(-1))
+        K = t.shape[0]
+        if K < 1:
+            raise ValueError("`t` must hold at least one time")
+        flux = np.asarray(flux, dtype=np.float64)
+        if flux.shape != (K,):
+            raise ValueError("`flux` must have one value per time: shape (%d,), not %s" % (K, flux.shape))
+        if t_map is None:
+            t_map = t
+        else:
+            t_map = np.asarray(t_map, dtype=np.float64)
+            if t_map.ndim != 1:
+                raise ValueError("`t_map` must be 1-D: one time per frame")
+            t_map = np.ascontiguousarray(t_map)
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        if data_cov.ndim == 2 and not matrix_ok:
+            raise ValueError("`data_cov` must be a scalar or (K,) here: the noise draw needs independent cadences")
+        if data_cov.ndim > 2 or (data_cov.ndim == 1 and data_cov.shape != (K,)) or \
+                (data_cov.ndim == 2 and data_cov.shape != (K, K)):
+            raise ValueError("`data_cov` must be a scalar, (K,) or (K, K) with K = %d, not %s" % (K, data_cov.shape))
+        bmean, bvar = np.asarray(baseline_mean, dtype=np.float64), np.asarray(baseline_var, dtype=np.float64)
+        if bmean.ndim != 0 or bvar.ndim != 0:
+            raise ValueError("`baseline_mean` and `baseline_var` must be scalars")
+        return t, flux, data_cov, t_map, float(bmean), float(bvar)
+
+    def _ylm_temporal_system(self, t, flux, data_cov, i, p, u, bmean, bvar):
+        """(A [K, N], C [K, K], r0 [K] = flux - baseline_mean - A mu_y, Sigma_y, mu_y) on the device."""
+        e, f = self._engine, self._flux
+        t, i, p, u = f._ingest(t, i, p, u)
+        f._bind()
+        rta1 = f._rta1(u)
+        mu, Sig = (e.f64(x) for x in self._moments_dev())
+        A = e.design_matrix(t[None, :], make_stars(1, period=p, inc_deg=i), rta1)[0]
+        C, _, _ = e.cov_conditional(t[None, :], make_stars(1, period=p, inc_deg=i, tau=self._tau), rta1,
+                                    temporal=self._temporal, normalized=False)
+        C = C[0]
+        if data_cov.ndim == 2:
+            C += e.f64(data_cov)
+        else:
+            C.diagonal().add_(e.f64(data_cov) if data_cov.ndim else float(data_cov))
+        C += bvar
+        r0 = e.f64(flux - bmean) - e.gemm_nt(mu.reshape(1, -1), A)[0]
+        return A, C, r0, Sig, mu
+
+    def ylm_conditional_temporal(self, t, flux, data_cov, t_map=None, i=defaults["i"], p=defaults["p"],
+                                 u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                                 baseline_var=defaults["baseline_var"], return_cov=True):
+        """Posterior of the surface map of a time-variable process at the frame times ``t_map`` (default: the observed
+        times ``t``), conditioned on the observed flux: (ymu (T, nylm), ycov (T, nylm, nylm)), frame by frame the
+        Gaussian of the spherical-harmonic coefficients at that time, each covariance exactly symmetric;
+        ``return_cov=False`` returns ymu alone and forms nothing nylm x nylm per frame.  The reference leaves this case
+        open (its sp.py:602-605); the model is that of its conditional likelihood: maps y(t) = mean_ylm + d(t) with
+        cov(d(t), d(t')) = k(t, t', tau) cov_ylm.  ``data_cov`` is a scalar, (K,) or (K, K); ``baseline_var`` a scalar.
+        Frames are independent marginals: for a coherent movie use ``sample_ylm_conditional_temporal``.  NaN everywhere
+        if the flux covariance is not positive definite; nothing is raised.  NotImplementedError for a normalized
+        process and for one without ``tau`` (use ``ylm_conditional``); ValueError for arguments of the wrong shape."""
+        t, flux, data_cov, t_map, bmean, bvar = self._ylm_temporal_args(t, flux, data_cov, t_map, baseline_mean,
+                                                                        baseline_var, True)
+        e = self._engine
+        A, C, r0, Sig, mu = self._ylm_temporal_system(t, flux, data_cov, i, p, u, bmean, bvar)
+        out, ycov, _ = e.ylm_conditional_temporal(A, Sig, C, r0[None, :], t, t_map, self._tau, self._temporal,
+                                                  with_cov=bool(return_cov))
+        ymu = out[0] + mu[None, :]
+        if not return_cov:
+            return Eager(ymu.cpu().numpy())
+        return Eager(ymu.cpu().numpy()), Eager(ycov.cpu().numpy())
+
+    def sample_ylm_conditional_temporal(self, t, flux, data_cov, t_map=None, i=defaults["i"], p=defaults["p"],
+                                        u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                                        baseline_var=defaults["baseline_var"], nsamples=1, seed=None):
+        """Surface movies conditioned on the observed flux, shape (nsamples, T, nylm): what ``flux(y, t_map)`` and
+        ``mollweide(y)`` take.  The frames of one sample are coherent in time (pathwise conditioning, Matheron's rule):
+        a prior movie y0 on the union of the observed and the frame times and a noise vector eps are drawn, and the
+        sample is y0(t*_j) + mean_ylm + B^T (k_j o C^-1 (flux - baseline_mean - A mean_ylm - f0 - eps)) with
+        f0_k = A_k . y0(t_k), in the notation of ``ylm_conditional_temporal``, whose Gaussian every frame follows.
+        ``data_cov`` is a scalar or (K,) (a matrix raises ValueError).
+
+        The deviates come from rng = RandomState(seed) -- the constructor's ``seed`` when ``seed`` is None -- in this
+        order: (1) U = rng.normal(size=(nsamples, Nu, nylm)), Nu the number of distinct values among ``t`` and
+        ``t_map``, for the prior movie Lt U Ly^T on those sorted distinct times, as ``sample_ylm(t)`` forms it (zero
+        mean); (2) rng.normal(size=(nsamples, K)), times sqrt(data_cov); (3) only when baseline_var > 0,
+        rng.normal(size=(nsamples,)), times sqrt(baseline_var).
+
+        If the temporal kernel's Gram matrix on the union times does not factor (the exp-squared kernel on a dense
+        cadence, times that differ by rounding only) every sample is NaN, as ``sample_ylm(t)``; nothing is raised."""
+        t, flux, data_cov, t_map, bmean, bvar = self._ylm_temporal_args(t, flux, data_cov, t_map, baseline_mean,
+                                                                        baseline_var, False)
+        import torch
+
+        e = self._engine
+        ns, K = int(nsamples), t.shape[0]
+        tu = np.unique(np.concatenate([t, t_map]))
+        rng = self._rng(seed)
+        U = rng.normal(size=(ns, tu.shape[0], self._nylm))
+        with np.errstate(invalid="ignore"):
+            eps = rng.normal(size=(ns, K)) * np.sqrt(data_cov)
+            if bvar > 0:
+                eps = eps + (rng.normal(size=(ns,)) * np.sqrt(bvar))[:, None]
+        A, C, r0, Sig, mu = self._ylm_temporal_system(t, flux, data_cov, i, p, u, bmean, bvar)
+        Lt, _ = e.temporal_gram(tu, self._tau, self._temporal)
+        y0 = e.ylm_temporal(Lt, self._cho_ylm_dev(), U)        # (ns, Nu, nylm); all NaN if a factorisation failed
+        at_t = torch.from_numpy(np.searchsorted(tu, t)).to(e.device)
+        at_map = torch.from_numpy(np.searchsorted(tu, t_map)).to(e.device)
+        f0 = e.flux_rows(A, y0[:, at_t, :].contiguous())
+        resid = r0[None, :] - f0 - e.f64(eps)
+        out, _, _ = e.ylm_conditional_temporal(A, Sig, C, resid, t, t_map, self._tau, self._temporal, with_cov=False)
+        out += y0[:, at_map, :]
+        out += mu[None, None, :]
+        return Eager(out.cpu().numpy())
+
     def _ensemble_args(self, t, flux, data_cov, i, p, u, baseline_mean, baseline_var, nobs=0):
         """Inputs of the ensemble calls, checked against flux's (S, K) shape: t (S, K) contiguous, the star records
         (period, inclination, baselines, scalar variances, limb-darkening table, nobs), the distinct limb-darkening
