@@ -533,6 +533,34 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
                                double *mubar_dev, double *sigbar_dev, double *starbar_dev, uint32_t *status_dev,
                                void *stream);
 
+/* ---- Fisher information of an ensemble about the spot hyperparameters, marginal branch, in one device sweep ------
+ * No flux data: for star s and P <= 6 parameters theta_i, with C_s the covariance sp_lnlike_grad_marginal assembles
+ * (normalised or not, temporal kernel, data variances, baseline variance) and m_s the mean of its flux GP (the flux
+ * mean for an unnormalised process, 0 for a normalised one: sp.py:669-672),
+ *   F_s[i, j] = 1/2 tr(C^-1 d_i C  C^-1 d_j C) + (d_i m)(d_j m) 1^T C^-1 1        -> fisher_dev [S, P, P].
+ * C depends on theta only through the star's kernel table and flux mean; the caller supplies their tangents,
+ *   dyp_dev [P, ntab, covpts + 4]   d yp / d theta_i, yp = tab_dev[table][0, :]
+ *   dmean_dev [P, ntab]             d (flux mean) / d theta_i
+ * (ntab: the tables of the handle's last sp_kernel_table, the call that made tab_dev; SP_ERR_STATE without one), and the
+ * sweep forms d_i C through the cubic interpolation (same segment index and position as the assembly; tau held fixed)
+ * and the normalisation (sp.py:705-727 differentiated by the product rule), G_i = C^-1 d_i C on the matrix cores and
+ * the pair traces 1/2 sum_ab G_i[a, b] G_j[b, a] by a two-stage reduction with one writer per partial: no
+ * floating-point atomics, the same bits run after run, F_s exactly symmetric.  dcov_dev (may be NULL): [S, P, K, K], the
+ * tangents d_i C themselves.  status_dev (may be NULL) [S].
+ *   star with z > zmax: zeros, SP_STAR_ZMAX (whether or not its covariance factors);  covariance that does not factor:
+ *   NaN, SP_STAR_NOT_PD;  ragged star (0 < nobs < K): NaN, SP_STAR_NAN (also set when a NaN reaches F_s otherwise).
+ * No star affects another.  The stars are worked through in groups of as many as workspace_bytes holds
+ * (sp_fisher_workspace_bytes(h, S', K, P, covpts) for S' stars resident at once: the inverse's workspace, the inverse and
+ * 2 P roundup(K, 64)^2 doubles per star); a star's bits do not depend on the grouping.  A workspace too small for one
+ * star, a null required pointer, K < 2 or P outside 1 .. 6: SP_ERR_INVALID, nothing launched.  S = 0: SP_OK, nothing
+ * touched.  All launches go to `stream`; nothing is synchronised.                                                     */
+size_t sp_fisher_workspace_bytes(sp_handle *h, int S, int K, int P, int covpts);
+int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, const double *diag_dev,
+                       const sp_star *stars_dev, int covpts, const double *tab_dev, const double *meanvar_dev,
+                       const double *dyp_dev, const double *dmean_dev, int temporal, int normalized, int norm_order,
+                       double zmax, double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

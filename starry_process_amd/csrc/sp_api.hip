@@ -442,8 +442,10 @@ int sp_kernel_table(sp_handle *h, const double *rta1_dev, int ntab, int covpts,
   if (ntab == 0) return SP_OK;
   int rc = sp_ensure_lag_grid(h, covpts, xp_host);
   if (rc) return rc;
-  return sp_launch_kernel_table(h, rta1_dev, ntab, covpts, h->d_xp, tab_dev,
-                                meanvar_dev, (hipStream_t)stream);
+  rc = sp_launch_kernel_table(h, rta1_dev, ntab, covpts, h->d_xp, tab_dev,
+                              meanvar_dev, (hipStream_t)stream);
+  if (rc == SP_OK) h->tab_ntab = ntab;
+  return rc;
 }
 
 // The kernel tables of B hyperparameter samples in one call (round 6): polar-frame moments ez [B][N], Ez [B][N][N]

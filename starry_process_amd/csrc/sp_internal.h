@@ -53,6 +53,7 @@ struct sp_handle {
   bool have_marginal = false;
   double *d_xp = nullptr;       // lag grid of the last kernel table
   int xp_covpts = -1;
+  int tab_ntab = 0;             // tables of the last sp_kernel_table (sp_fisher_marginal: the leading dimension of the tangents)
   std::vector<double> xp_host;  // its host copy (re-upload only on change)
   // device state: Ylm moments
   double *d_mean_ylm = nullptr, *d_cov_ylm = nullptr, *d_ez = nullptr, *d_Ez = nullptr, *d_tmpNN = nullptr;

@@ -1149,6 +1149,35 @@ class Engine(object):
             self._p(mubar), self._p(sigbar), self._p(sbar), self._p(status), self._stream()))
         return out, mubar, sigbar, sbar, status
 
+    def fisher_workspace(self, S, K, P, covpts):
+        """Device scratch that holds ``S`` stars of ``fisher_marginal`` at once (sp_fisher_workspace_bytes)."""
+        return self._scratch(self._L.sp_fisher_workspace_bytes(self._h, int(S), int(K), int(P), int(covpts)))
+
+    def fisher_marginal(self, t, stars_dev, tab, meanvar, dyp, dmean, diag=None, covpts=300, temporal=None,
+                        normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False):
+        """Device half of the ensemble's Fisher information (sp_fisher_marginal): t [S, K], the kernel tables of the
+        engine's last ``kernel_table`` (tab [ntab, 5, covpts + 4], meanvar [ntab, 2]) and the tangents of their first
+        rows and of the flux means with respect to P parameters (dyp [P, ntab, covpts + 4], dmean [P, ntab]) ->
+        (fisher [S, P, P], status [S]) and, with ``return_tangents``, dcov [S, P, K, K]: the tangents of the stars'
+        covariances.  workspace: a byte tensor (``fisher_workspace``); one that holds fewer than S stars makes the call
+        work through the stars in groups, with the same bits."""
+        torch = _torch()
+        S, K = t.shape
+        P = int(dyp.shape[0])
+        assert tuple(dyp.shape) == (P, tab.shape[0], covpts + 4) and tuple(dmean.shape) == (P, tab.shape[0])
+        fisher = self.empty(S, P, P)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        dcov = self.empty(S, P, K, K) if return_tangents else None
+        if S > 0:
+            if workspace is None:
+                workspace = self._grad_ws = self.fisher_workspace(S, K, P, covpts)
+            check(self._L.sp_fisher_marginal(
+                self._h, S, K, P, self._p(t), self._p(diag), self._p(stars_dev), int(covpts), self._p(tab),
+                self._p(meanvar), self._p(dyp.contiguous()), self._p(dmean.contiguous()), TEMPORAL[temporal],
+                int(bool(normalized)), int(norm_order), float(zmax), self._p(fisher), self._p(dcov), self._p(status),
+                self._p(workspace), int(workspace.numel()), self._stream()))
+        return (fisher, status, dcov) if return_tangents else (fisher, status)
+
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 

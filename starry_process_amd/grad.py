@@ -37,7 +37,7 @@ from .stars import check_period_inclination, ensemble_stars
 from .temporal import kernel_id
 
 __all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient",
-           "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional"]
+           "EnsembleFisher", "ensemble_fisher", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional"]
 
 _cache = {}
 
@@ -394,48 +394,9 @@ class _EnsembleSweep(object):
         return stars, utab
 
 
-class EnsembleGradient(_EnsembleSweep):
-    """Log-likelihood of an ENSEMBLE of light curves and its gradient with respect to the spot hyperparameters
-    (r, a, b, c, n[, dr]) in ONE device sweep per evaluation -- what ``theano.grad`` of the summed
-    ``sp.log_likelihood`` is in the reference (tests/test_lnlike.py:100-136, calibrate/log_prob.py:53-91), for every
-    star of the batch at once.  Marginal branch, scalar or per-cadence data variance; one light curve per star
-    (flux [S, K]) or M of them on the star's one covariance (flux [S, M, K]: the shared-covariance form of
-    sp.py:1162-1171 -- with S = 1 the gradient of what ``calibrate.get_log_prob`` evaluates).
-
-        eg = EnsembleGradient(t, flux, ferr=1e-3, p=periods)       # data -> GPU, once
-        lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10.)             # lnl: sum over stars; grad: dict
-        eg.lnlike                                                   # per-star values of the last call
-
-    How (DESIGN.md 8): d lnL / dC = (alpha alpha^T - C^-1) / 2 with C^-1 from the factorisation's own machinery
-    (sp_spd_inverse_batched: the identity rides through the blocked Cholesky), pulled back on the device through the
-    normalisation and the cubic interpolation to the adjoint of each star's kernel TABLE (304 numbers) and flux mean
-    (sp_lnlike_grad_marginal).  The chain from the hyperparameters to the table is short and cheap -- moments by the
-    device quadrature, then the table kernels -- and is differentiated there: exactly in c and n (the moments are
-    mu_y = c n m, Sigma_y = c^2 n S + eps, contrast.py:21-33, and the table is linear in Sigma_y + mu_y mu_y^T), and
-    since round 5 exactly in r, a, b too: the moments come with their tangents (ylm_moments_device_grad: the
-    quadrature rule differentiated with respect to its exponents -- the reference's analytic latitude derivatives,
-    ops/include/latitude.h:21-173), and one table evaluation per parameter turns a tangent of the moments into the
-    tangent of the table, on two more streams while the sweep runs.  With a spread of radii (dr) or exact=False:
-    central differences of the table (step h), as in round 4."""
-
-    def __init__(self, t, flux, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, baseline_mean=0.0,
-                 normalized=True, covpts=None, tau=None, temporal_kernel="matern32", device=None, h=1.0e-4,
-                 upstream_kwargs=None, exact=True):
-        flux = np.asarray(flux, dtype=np.float64)
-        if flux.ndim not in (2, 3):
-            raise ValueError("flux must be (S, K) or (S, M, K)")
-        M = flux.shape[1] if flux.ndim == 3 else 1
-        # (the star records carry no inclination on the marginal branch: make_stars' own default)
-        stars, utab = self._setup(t, flux, ferr, p, None, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel,
-                                  device)
-        e = self._e
-        self._ntab = utab.shape[0]
-        self._table = _torch().as_tensor(stars["table"].astype(np.int64), device=e.device)
-        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
-        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
-        self._exact = bool(exact)
-        self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
-        self.lnlike = None
+class _MarginalSweep(_EnsembleSweep):
+    """What the marginal branch's sweeps (gradient, Fisher information) share beyond their data: four engines on four
+    streams, the kernel tables at a point and the tables' tangents with respect to the hyperparameters."""
 
     def _open(self, ydeg, udeg, device):
         from .engine import engine_slots
@@ -456,43 +417,15 @@ class EnsembleGradient(_EnsembleSweep):
         tab, mv = eng.kernel_table(self._rta1, self._covpts)
         return tab[:, 0, :], mv[:, 0], (mu, Sig, tab, mv)
 
-    _WRT = _WRT
-
-    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
-                 wrt=None):
-        """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .[, "dr": .]}).
-
-        wrt: None, or a tuple of names out of ("p", "tau", "baseline_mean", "baseline_var", "log_var"): the dict then
-        also holds the derivatives with respect to the stars' OWN parameters, from the same device sweep
-        (sp_lnlike_grad_marginal_stars) and the same one transfer: "p", "baseline_mean", "baseline_var", "log_var" as
-        arrays [S] -- d lnL_s / d of star s's period, baseline mean, baseline variance and the log of a common factor
-        on its data variances (ferr^2, scalar or per cadence; with s_s^2 = exp(log_var) ferr_s^2) -- and "tau" as a
-        float, the sum over the stars (the constructor takes one timescale).  Where the ensemble shares a baseline (or a
-        noise factor), as in calibrate/log_prob.py:7-106, the derivative with respect to the shared value is the sum of
-        the array.  A star the likelihood rejects adds zeros.  d/dp is the derivative of the interpolant inside its
-        segments, as ``log_likelihood_with_grad``'s."""
+    def _table_tangents(self, x0, hp0, exact, at_point, yp0, mean0, mu, Sig):
+        """({name: d yp / d name [ntab, np]}, {name: d mean / d name [ntab]}, events) for r, a, b, c, n (and dr when
+        x0["dr"] is given), enqueued on the three side streams; the caller's stream waits for ``events`` before it reads
+        them.  x0: {"r", "dr", "a", "b"}, hp0: x0 with c and n; at_point: the event behind the tables at the point
+        (yp0, mean0, from the moments mu, Sig) on the main stream.  exact: the moments' exact tangents for r, a, b
+        (``ylm_moments_device_grad``), central differences of the table (step h) otherwise."""
         import torch
 
-        wrt = _check_wrt(wrt, self._temporal is not None)
-        e = self._e
-        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
-        hp0 = dict(x0, c=float(c), n=float(n))
-        torch.cuda.synchronize(e.device)
-        exact = self._exact and dr is None
-        # main stream: the tables at the point, then the sweep
-        with torch.cuda.stream(self._stream):
-            yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
-            at_point = torch.cuda.Event()
-            at_point.record(self._stream)
-            sweep_kw = dict(diag=self._diag, covpts=self._covpts, temporal=self._temporal,
-                            normalized=self._normalized, workspace=self._ws)
-            sbar = None
-            if wrt is None:
-                lnl, ybar, mbar, status = e.lnlike_grad_marginal(self._t, self._flux, self._stars, tab, mv, **sweep_kw)
-            else:
-                lnl, ybar, mbar, sbar, status = e.lnlike_grad_marginal_stars(self._t, self._flux, self._stars, tab, mv,
-                                                                             **sweep_kw)
-        # three more streams, meanwhile: the tables' derivatives
+        r, a, b, c, n = hp0["r"], hp0["a"], hp0["b"], hp0["c"], hp0["n"]
         bounds = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}
         dy, dm, events = {}, {}, []
 
@@ -525,8 +458,8 @@ class EnsembleGradient(_EnsembleSweep):
                 # the moments again, with their tangents, beside the main stream (which only waits for the value)
                 from .upstream_device import ylm_moments_device_grad
 
-                mu1, _, dmu, dSig = ylm_moments_device_grad(e1, r=float(r), a=float(a), b=float(b), c=float(c),
-                                                            n=float(n), **self._ukw)
+                mu1, _, dmu, dSig = ylm_moments_device_grad(e1, r=r, a=a, b=b, c=c,
+                                                            n=n, **self._ukw)
                 tang = (mu1, dmu, dSig)
                 have_tangents = torch.cuda.Event()
                 have_tangents.record(s1)
@@ -583,13 +516,97 @@ class EnsembleGradient(_EnsembleSweep):
                 eu.set_moments_dev(zero_mu, Sig1 - torch.diag(eps))
                 tS, _ = eu.kernel_table(self._rta1, self._covpts)
                 f_S1 = tS[:, 0, :]
-                cc, nn = float(c), float(n)
+                cc, nn = c, n
                 dy["c"] = 2.0 * cc * nn * f_S1 + 2.0 * cc * nn * nn * f_mm1 - 2.0 * cc * nn * nn * m1[:, None] ** 2
                 dm["c"] = nn * m1
                 dy["n"] = cc * cc * f_S1 + 2.0 * cc * cc * nn * f_mm1 - 2.0 * cc * cc * nn * m1[:, None] ** 2
                 dm["n"] = cc * m1
             events.append(torch.cuda.Event())
             events[-1].record(s3)
+        return dy, dm, events
+
+
+class EnsembleGradient(_MarginalSweep):
+    """Log-likelihood of an ENSEMBLE of light curves and its gradient with respect to the spot hyperparameters
+    (r, a, b, c, n[, dr]) in ONE device sweep per evaluation -- what ``theano.grad`` of the summed
+    ``sp.log_likelihood`` is in the reference (tests/test_lnlike.py:100-136, calibrate/log_prob.py:53-91), for every
+    star of the batch at once.  Marginal branch, scalar or per-cadence data variance; one light curve per star
+    (flux [S, K]) or M of them on the star's one covariance (flux [S, M, K]: the shared-covariance form of
+    sp.py:1162-1171 -- with S = 1 the gradient of what ``calibrate.get_log_prob`` evaluates).
+
+        eg = EnsembleGradient(t, flux, ferr=1e-3, p=periods)       # data -> GPU, once
+        lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10.)             # lnl: sum over stars; grad: dict
+        eg.lnlike                                                   # per-star values of the last call
+
+    How (DESIGN.md 8): d lnL / dC = (alpha alpha^T - C^-1) / 2 with C^-1 from the factorisation's own machinery
+    (sp_spd_inverse_batched: the identity rides through the blocked Cholesky), pulled back on the device through the
+    normalisation and the cubic interpolation to the adjoint of each star's kernel TABLE (304 numbers) and flux mean
+    (sp_lnlike_grad_marginal).  The chain from the hyperparameters to the table is short and cheap -- moments by the
+    device quadrature, then the table kernels -- and is differentiated there: exactly in c and n (the moments are
+    mu_y = c n m, Sigma_y = c^2 n S + eps, contrast.py:21-33, and the table is linear in Sigma_y + mu_y mu_y^T), and
+    since round 5 exactly in r, a, b too: the moments come with their tangents (ylm_moments_device_grad: the
+    quadrature rule differentiated with respect to its exponents -- the reference's analytic latitude derivatives,
+    ops/include/latitude.h:21-173), and one table evaluation per parameter turns a tangent of the moments into the
+    tangent of the table, on two more streams while the sweep runs.  With a spread of radii (dr) or exact=False:
+    central differences of the table (step h), as in round 4."""
+
+    def __init__(self, t, flux, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, baseline_mean=0.0,
+                 normalized=True, covpts=None, tau=None, temporal_kernel="matern32", device=None, h=1.0e-4,
+                 upstream_kwargs=None, exact=True):
+        flux = np.asarray(flux, dtype=np.float64)
+        if flux.ndim not in (2, 3):
+            raise ValueError("flux must be (S, K) or (S, M, K)")
+        M = flux.shape[1] if flux.ndim == 3 else 1
+        # (the star records carry no inclination on the marginal branch: make_stars' own default)
+        stars, utab = self._setup(t, flux, ferr, p, None, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel,
+                                  device)
+        e = self._e
+        self._ntab = utab.shape[0]
+        self._table = _torch().as_tensor(stars["table"].astype(np.int64), device=e.device)
+        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
+        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
+        self._exact = bool(exact)
+        self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
+        self.lnlike = None
+
+    _WRT = _WRT
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
+                 wrt=None):
+        """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .[, "dr": .]}).
+
+        wrt: None, or a tuple of names out of ("p", "tau", "baseline_mean", "baseline_var", "log_var"): the dict then
+        also holds the derivatives with respect to the stars' OWN parameters, from the same device sweep
+        (sp_lnlike_grad_marginal_stars) and the same one transfer: "p", "baseline_mean", "baseline_var", "log_var" as
+        arrays [S] -- d lnL_s / d of star s's period, baseline mean, baseline variance and the log of a common factor
+        on its data variances (ferr^2, scalar or per cadence; with s_s^2 = exp(log_var) ferr_s^2) -- and "tau" as a
+        float, the sum over the stars (the constructor takes one timescale).  Where the ensemble shares a baseline (or a
+        noise factor), as in calibrate/log_prob.py:7-106, the derivative with respect to the shared value is the sum of
+        the array.  A star the likelihood rejects adds zeros.  d/dp is the derivative of the interpolant inside its
+        segments, as ``log_likelihood_with_grad``'s."""
+        import torch
+
+        wrt = _check_wrt(wrt, self._temporal is not None)
+        e = self._e
+        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
+        hp0 = dict(x0, c=float(c), n=float(n))
+        torch.cuda.synchronize(e.device)
+        exact = self._exact and dr is None
+        # main stream: the tables at the point, then the sweep
+        with torch.cuda.stream(self._stream):
+            yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
+            at_point = torch.cuda.Event()
+            at_point.record(self._stream)
+            sweep_kw = dict(diag=self._diag, covpts=self._covpts, temporal=self._temporal,
+                            normalized=self._normalized, workspace=self._ws)
+            sbar = None
+            if wrt is None:
+                lnl, ybar, mbar, status = e.lnlike_grad_marginal(self._t, self._flux, self._stars, tab, mv, **sweep_kw)
+            else:
+                lnl, ybar, mbar, sbar, status = e.lnlike_grad_marginal_stars(self._t, self._flux, self._stars, tab, mv,
+                                                                             **sweep_kw)
+        # three more streams, meanwhile: the tables' derivatives
+        dy, dm, events = self._table_tangents(x0, hp0, exact, at_point, yp0, mean0, mu, Sig)
         with torch.cuda.stream(self._stream):
             for ev in events:
                 self._stream.wait_event(ev)
@@ -624,6 +641,132 @@ def ensemble_gradient(t, flux, ferr=1.0e-3, p=1.0, r=defaults["r"], a=defaults["
     wrt: the per-star derivatives to return as well (``EnsembleGradient.__call__``)."""
     wrt = _check_wrt(wrt, bool(kwargs.get("tau")))          # (before any data goes to the device)
     return EnsembleGradient(t, flux, ferr=ferr, p=p, **kwargs)(r=r, a=a, b=b, c=c, n=n, dr=dr, wrt=wrt)
+
+
+# the hyperparameters the Fisher information may be taken about, in the order of its default rows
+_FISHER_PARAMS = ("r", "a", "b", "c", "n", "dr")
+
+
+def _check_params(params, has_dr):
+    """``params`` as a tuple of distinct names out of (r, a, b, c, n, dr); ValueError otherwise, and for "dr" without a
+    spread of radii.  No device work."""
+    params = (params,) if isinstance(params, str) else tuple(params)
+    if not params:
+        raise ValueError("params: at least one name (out of %s)" % ", ".join(_FISHER_PARAMS))
+    for k, name in enumerate(params):
+        if name not in _FISHER_PARAMS:
+            raise ValueError("params: unknown name %r (one of %s)" % (name, ", ".join(_FISHER_PARAMS)))
+        if name in params[:k]:
+            raise ValueError("params: %r is named twice" % (name,))
+    if "dr" in params and not has_dr:
+        raise ValueError("params: 'dr' needs a spread of radii (dr=...)")
+    return params
+
+
+class EnsembleFisher(_MarginalSweep):
+    """Expected (Fisher) information of an ENSEMBLE of light curves about the spot hyperparameters, in one device sweep
+    and without any flux: how well S light curves with these cadences, periods and noise CAN constrain (r, a, b, c, n
+    [, dr]) -- the design question behind the reference's calibration runs, which it answers with a sampler over a
+    synthetic ensemble.  Marginal branch; per star, with C_s the covariance ``EnsembleGradient`` factors and m_s the
+    mean of its flux GP (the flux mean when not normalised, else 0: sp.py:669-672),
+
+        F_s[i, j] = 1/2 tr(C^-1 d_i C  C^-1 d_j C) + (d_i m)(d_j m) 1^T C^-1 1,        F = sum_s F_s
+
+        ef = EnsembleFisher(t, ferr=1e-3, p=periods)            # cadences and star records -> GPU, once
+        F = ef(r=20., a=.4, b=.27, c=.1, n=10.)                  # [5, 5]
+        ef.per_star, ef.status, ef.names                         # [S, 5, 5], [S], ("r", "a", "b", "c", "n")
+        cov, sigma = cramer_rao(F)                               # the Laplace / Cramer-Rao error bars
+
+    t: (K,) or (S, K); the number of stars is t's or p's.  The tangents of the kernel tables are ``EnsembleGradient``'s
+    (exact in r, a, b, c, n; central differences of step h with a spread of radii or exact=False); the device forms the
+    tangents of the covariances from them, C^-1 d_i C on the matrix cores and the pair traces (sp_fisher_marginal,
+    DESIGN.md 17).  max_workspace_bytes: a bound on the device scratch; the stars are then worked through in groups,
+    with the same bits."""
+
+    def __init__(self, t, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, normalized=True, covpts=None,
+                 tau=None, temporal_kernel="matern32", device=None, h=1.0e-4, upstream_kwargs=None, exact=True,
+                 max_workspace_bytes=None):
+        t = np.asarray(t, dtype=np.float64)
+        if t.ndim not in (1, 2):
+            raise ValueError("t must be (K,) or (S, K)")
+        S = t.shape[0] if t.ndim == 2 else (np.asarray(p).shape[0] if np.ndim(p) == 1 else 1)
+        stars, utab = self._setup(t, np.zeros((S, t.shape[-1])), ferr, p, None, u, ydeg, 0.0, baseline_var, tau,
+                                  temporal_kernel, device)
+        self._flux = None
+        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
+        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
+        self._exact = bool(exact)
+        self._max_ws = None if max_workspace_bytes is None else int(max_workspace_bytes)
+        self._ws = None
+        self.per_star = self.status = self.names = self.tangents = None
+
+    def _workspace(self, P):
+        """Scratch for P parameters: every star at once, or as many as ``max_workspace_bytes`` allows."""
+        e = self._e
+        need = int(e._L.sp_fisher_workspace_bytes(e._h, self.S, self.K, P, self._covpts))
+        nbytes = need if self._max_ws is None else min(need, self._max_ws)
+        if self._ws is None or self._ws.numel() != nbytes:
+            self._ws = e._scratch(nbytes)
+        return self._ws
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
+                 params=("r", "a", "b", "c", "n"), return_tangents=False):
+        """F [P, P] (NumPy), the sum of the stars' blocks in the order of ``params`` (names out of r, a, b, c, n and,
+        with a spread of radii ``dr``, "dr").  Afterwards ``per_star`` [S, P, P], ``status`` [S] (the library's per-star
+        flags: a star with z > zmax holds zeros, one whose covariance does not factor or whose light curve is ragged
+        NaN) and ``names``; F adds the stars of status 0 in index order.  return_tangents: ``tangents`` [S, P, K, K],
+        the d_i C the device formed."""
+        import torch
+
+        names = _check_params(params, dr is not None)
+        e = self._e
+        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
+        hp0 = dict(x0, c=float(c), n=float(n))
+        torch.cuda.synchronize(e.device)
+        exact = self._exact and dr is None
+        with torch.cuda.stream(self._stream):
+            yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
+            at_point = torch.cuda.Event()
+            at_point.record(self._stream)
+        dy, dm, events = self._table_tangents(x0, hp0, exact, at_point, yp0, mean0, mu, Sig)
+        with torch.cuda.stream(self._stream):
+            for ev in events:
+                self._stream.wait_event(ev)
+            DY, DM = torch.stack([dy[k] for k in names]), torch.stack([dm[k] for k in names])
+            out = e.fisher_marginal(self._t, self._stars, tab, mv, DY, DM, diag=self._diag, covpts=self._covpts,
+                                    temporal=self._temporal, normalized=self._normalized,
+                                    workspace=self._workspace(len(names)), return_tangents=return_tangents)
+            per_star, status = out[0].cpu().numpy(), out[1].cpu().numpy().astype(np.uint32)
+            self.tangents = out[2].cpu().numpy() if return_tangents else None
+        self.per_star, self.status, self.names = per_star, status, names
+        return per_star[status == 0].sum(axis=0)
+
+
+def ensemble_fisher(t, ferr=1.0e-3, p=1.0, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"],
+                    n=defaults["n"], dr=None, params=("r", "a", "b", "c", "n"), **kwargs):
+    """One-shot form of ``EnsembleFisher``: F [P, P]."""
+    params = _check_params(params, dr is not None)          # (before anything goes to the device)
+    return EnsembleFisher(t, ferr=ferr, p=p, **kwargs)(r=r, a=a, b=b, c=c, n=n, dr=dr, params=params)
+
+
+def cramer_rao(F):
+    """(cov, sigma) of a Fisher matrix F [P, P]: cov = F^-1 from a symmetric eigendecomposition, sigma = sqrt(diag(cov)):
+    the Cramer-Rao bound on the parameters' covariance, and the Laplace error bars at an optimum.  Everything NaN when
+    F holds a non-finite entry or is not positive definite (an eigenvalue <= 0 to rounding: some direction of parameter space the
+    data cannot constrain).  Host only."""
+    F = np.asarray(F, dtype=np.float64)
+    if F.ndim != 2 or F.shape[0] != F.shape[1]:
+        raise ValueError("F must be a square matrix")
+    P = F.shape[0]
+    bad = np.full((P, P), np.nan), np.full(P, np.nan)
+    if not np.all(np.isfinite(F)):
+        return bad
+    w, V = np.linalg.eigh(0.5 * (F + F.T))
+    if not w[0] > P * np.finfo(np.float64).eps * w[-1]:          # (singular to rounding counts as singular)
+        return bad
+    cov = (V / w) @ V.T
+    cov = 0.5 * (cov + cov.T)
+    return cov, np.sqrt(np.diag(cov))
 
 
 def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], r=defaults["r"], a=defaults["a"],
