@@ -6,8 +6,8 @@
 // with C_s = Sigma~_s + D_s + v_s 1 1^T as sp_lnlike_grad_marginal assembles it.  C depends on a hyperparameter only through
 // the star's kernel TABLE yp[covpts + 4] and the scalar flux mean, and the interpolant is linear in the table: the caller
 // hands in the tangents of both (dyp, dmean: grad.py), and the sweep is
-//   1. C assembled and inverted with the gradient sweep's own launches (sp_spd_inverse_batched's machinery), the inverse's
-//      upper tiles completed (fisher_mirror_kernel);
+//   1. C assembled and inverted by the gradient sweep's own opening (sp_launch_marginal_inverse, sp_grad.hip), the
+//      inverse's upper tiles completed (fisher_mirror_kernel);
 //   2. the row sums of the P raw tangents d_i Sigma (fisher_rowsum_kernel; no matrix stored) and the tangents of the
 //      normalisation's scalars and of q (fisher_coef_kernel) -- normalised only;
 //   3. d_i C for all P parameters from ONE evaluation of lag, segment index, cubic weights and temporal factor per entry
@@ -18,43 +18,25 @@
 // No floating-point atomics; every star's numbers depend on its own inputs alone.  The stars are worked through in groups
 // that fit the caller's workspace; a star's launches see only its own slices, so its bits do not depend on the grouping.
 //
-// Compiled with -ffp-contract=off: the segment index must be the assembly's (sp_cov.h), and the tangent's entries (a, b)
-// and (b, a) are the same sums of the same products only if no product is fused into a neighbour's addition.
+// Compiled with -ffp-contract=off: the segment index must be the assembly's (sp_lag_segment, sp_sweep.h), and the
+// tangent's entries (a, b) and (b, a) are the same sums of the same products only if no product is fused into a
+// neighbour's addition.
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_sweep.h"
 
 namespace {
 
 constexpr int FP_MAX = 6;      // parameters per call (r, a, b, c, n, dr)
 
-__device__ __forceinline__ double wsum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// the sum of one value per thread over the 256 threads, in a fixed order; every thread gets it.  `red`: 4 doubles of LDS
-__device__ __forceinline__ double block_sum(double v, double *red) {
-  v = wsum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// segment of a lag and the four cubic weights of the table entries yp[idx .. idx + 3] at the position inside it: the
-// index and x0 of SplineGen (sp_cov.h) and of the gradient's scatter (sp_grad.hip), value = sum_m yp[idx + m] w[m]
-// (a0 = y1, a1 = -y0/3 - y1/2 + y2 - y3/6, a2 = (y0 + y2)/2 - y1, a3 = ((y1 - y2) + (y3 - y0)/3)/2: flux.py:322-330)
+// segment of a lag (sp_lag_segment, sp_sweep.h: the index and x0 of SplineGen and of the gradient's scatter) and the four
+// cubic weights of the table entries yp[idx .. idx + 3] at the position inside it, value = sum_m yp[idx + m] w[m]
+// (a0 = y1, a1 = -y0/3 - y1/2 + y2 - y3/6, a2 = (y0 + y2)/2 - y1, a3 = ((y1 - y2) + (y3 - y0)/3)/2: flux.py:322-330).
+// The weights are this file's own, unfused: the scatter's sit in a file compiled with contraction.
 __device__ __forceinline__ int cubic_weights(double thi, double thj, double dx, double inv_dx, int covpts, double (&w)[4]) {
 #pragma clang fp contract(off)
-  const double lag = fabs(thi - thj);
-  const double qd = lag * inv_dx;
-  int idx = (int)qd;
-  double x = qd - (double)idx;
-  if (fabs(x - 0.5) > 0.5 - 1.0e-9) {
-    idx = (int)floor(lag / dx);
-    x = qd - (double)idx;
-  }
-  idx = idx < 0 ? 0 : (idx > covpts ? covpts : idx);
+  double x;
+  const int idx = sp_lag_segment(thi, thj, dx, inv_dx, covpts, x);
   const double x2 = x * x, x3 = x2 * x;
   w[0] = -x / 3.0 + 0.5 * x2 - x3 / 6.0;
   w[1] = 1.0 - 0.5 * x - x2 + 0.5 * x3;
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(256) void fisher_coef_kernel(
     double *row = drow + ((size_t)s * P + p) * K;
     double part = 0.0;
     for (int i = tid; i < K; i += 256) part += row[i];
-    const double dm = block_sum(part, red) / (Kd * Kd);
+    const double dm = sp_block_sum_256(part, red) / (Kd * Kd);
     const double dmu = dmean[(size_t)p * ntab + stars[s].table];
     const double dz = dm / (mu * mu) - 2.0 * m * dmu / (mu * mu * mu);
     const double da = dan * dz, db = dbn * dz;
@@ -246,12 +228,10 @@ __global__ __launch_bounds__(256) void fisher_tangent_kernel(
 // (ta, tb), ta > tb, goes transposed to (tb, ta) through LDS, both sides coalesced.  grid (ntr (ntr - 1) / 2, S)
 __global__ __launch_bounds__(256) void fisher_mirror_kernel(int Kr, double *__restrict__ Cinv) {
   __shared__ double tile[64][65];
-  const int c = threadIdx.x & 63, jq = threadIdx.x >> 6, t = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);     // strictly lower tiles: (ta + 1, tb), tb <= ta
-  while (ta * (ta + 1) / 2 > t) --ta;
-  while ((ta + 1) * (ta + 2) / 2 <= t) ++ta;
-  const int tb = t - ta * (ta + 1) / 2;
-  ta += 1;
+  const int c = threadIdx.x & 63, jq = threadIdx.x >> 6;
+  int ta, tb;
+  sp_lower_tile_decode(blockIdx.x, ta, tb);
+  ta += 1;                                // strictly lower tiles: (ta + 1, tb), tb <= ta
   double *M = Cinv + (size_t)blockIdx.y * Kr * Kr;
   const double *src = M + (size_t)(64 * ta) * Kr + 64 * tb;
 #pragma unroll
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(256) void fisher_ones_kernel(int K, int Kr, const d
     for (int cb = 0; cb < ntr; ++cb)
       if (64 * cb + c < K) a += M[(size_t)r * Kr + 64 * cb + c];
   }
-  a = block_sum(a, red);
+  a = sp_block_sum_256(a, red);
   if (threadIdx.x == 0) ones[(size_t)blockIdx.y * ntr + blockIdx.x] = a;
 }
 
@@ -314,7 +294,7 @@ __global__ __launch_bounds__(256) void fisher_trace_kernel(int Kr, int P, const 
     double a = 0.0;
 #pragma unroll
     for (int u = 0; u < 16; ++u) a += v[u] * tile[c][jq + 4 * u];
-    a = block_sum(a, red);
+    a = sp_block_sum_256(a, red);
     if (threadIdx.x == 0) part[((size_t)s * npairs + pair_index(i, j, P)) * nt2 + blockIdx.x] = a;
   }
 }
@@ -337,7 +317,7 @@ __global__ __launch_bounds__(256) void fisher_finish_kernel(
     const double *src = part + ((size_t)s * npairs + pr) * nt2;
     double a = 0.0;
     for (int w = tid; w < nt2; w += 256) a += src[w];
-    a = block_sum(a, red);
+    a = sp_block_sum_256(a, red);
     if (tid == 0) tr[pr] = a;
   }
   __syncthreads();
@@ -376,8 +356,7 @@ FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts) {
   FisherLayout F;
   SpCarve c;
   (void)covpts;
-  F.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
-  F.cinv = c.take(d * (size_t)S * kr2);
+  sp_sweep_head(c, h, S, K, F.inv, F.cinv);
   F.dC = c.take(d * (size_t)S * P * kr2);
   F.G = c.take(d * (size_t)S * P * kr2);
   F.drow = c.take(d * (size_t)S * P * K);
@@ -396,27 +375,17 @@ int fisher_group(sp_handle *h, int S, int K, int P, int ntab, const double *t, c
   const int Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB, np = covpts + 4;
   const FisherLayout F = fisher_layout(h, S, K, P, covpts);
   char *base = static_cast<char *>(workspace);
-  void *ws = base + F.inv;
-  Layout L = make_layout(h, S, K, Kr, true, true);
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum), *qv = at<double>(ws, L.qv);
-  double *coef = at<double>(ws, L.coef), *sys = at<double>(ws, L.sys);
-  int32_t *info = at<int32_t>(ws, L.info);
+  const SpSweepViews V = sp_sweep_views(h, S, K, base + F.inv);
+  double *theta = V.theta, *qv = V.qv, *coef = V.coef;
   double *Cinv = at<double>(base, F.cinv), *dC = at<double>(base, F.dC), *G = at<double>(base, F.G);
   double *drow = at<double>(base, F.drow), *dsc = at<double>(base, F.dsc), *part = at<double>(base, F.part);
   double *ones = at<double>(base, F.ones);
   const size_t kr2 = (size_t)Kr * Kr;
   int rc;
-  // C and its inverse: the launches of the gradient sweep (sp_grad.hip: grad_marginal)
-  if ((rc = sp_launch_theta(S, K, t, stars, theta, st))) return rc;
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal, nullptr, rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars, meanvar, nullptr, normalized, order, zmax, rowsum, qv, coef, nullptr, st)))
+  // C and its inverse: the gradient sweep's own opening (sp_grad.hip)
+  if ((rc = sp_launch_marginal_inverse(h, S, K, V, t, diag, stars, covpts, tab, meanvar, temporal, normalized, order, zmax,
+                                       Cinv, nullptr, st)))
     return rc;
-  if ((rc = sp_launch_assemble(S, K, 0, Kr, 1, theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal, nullptr,
-                               normalized, qv, coef, diag, 1, nullptr, sys, L.Kp, (long)L.Kp * L.Kp, st)))
-    return rc;
-  if ((rc = spd_inverse_in_place(h, S, K, L, ws, Cinv, nullptr, st))) return rc;
   if (ntr > 1) {
     hipLaunchKernelGGL(fisher_mirror_kernel, dim3(ntr * (ntr - 1) / 2, S), dim3(256), 0, st, Kr, Cinv);
     SP_LAUNCH_CHECK();
@@ -447,7 +416,7 @@ int fisher_group(sp_handle *h, int S, int K, int P, int ntab, const double *t, c
     hipLaunchKernelGGL(fisher_ones_kernel, dim3(ntr, S), dim3(256), 0, st, K, Kr, Cinv, ones);
     SP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, stars, (const SpCoef *)coef, info,
+  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, stars, (const SpCoef *)coef, V.info,
                      part, ones, dmean, normalized, zmax, fisher, status);
   SP_LAUNCH_CHECK();
   return SP_OK;

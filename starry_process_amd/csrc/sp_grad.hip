@@ -17,13 +17,9 @@
 // chain from (r, a, b, c, n) to the table is five numbers long and taken by the caller (grad.py).
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_sweep.h"
 
 namespace {
-
-__device__ __forceinline__ double wsum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // C^-1 [p, q, 1, r_0 .. r_{M-1}] per star from the LOWER tiles of C^-1 alone (the inverse comes out of the blocked
 // factorisation as its lower tiles, the diagonal ones complete; rounds 4-5 mirrored them into the upper ones first -- 8 MB
@@ -45,11 +41,8 @@ __global__ __launch_bounds__(256) void grad_matvec_kernel(
   __shared__ double tile[64][65];
   __shared__ double xs[2][4][64];         // [0]: entries 64 ta + ., [1]: entries 64 tb + .
   const int s = blockIdx.y, c = threadIdx.x & 63, jq = threadIdx.x >> 6, ntr = Kr / 64;
-  const int t = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * t + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
-  while (ta * (ta + 1) / 2 > t) --ta;
-  while ((ta + 1) * (ta + 2) / 2 <= t) ++ta;
-  const int tb = t - ta * (ta + 1) / 2;
+  int ta, tb;                             // row tile ta >= column tile tb
+  sp_lower_tile_decode(blockIdx.x, ta, tb);
   const double *T = Cinv + (size_t)s * Kr * Kr + (size_t)(64 * ta) * Kr + 64 * tb;
   double v[16];
 #pragma unroll
@@ -161,7 +154,7 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-      const double v = wsum(d[k]);
+      const double v = sp_wave_sum(d[k]);
       if ((tid & 63) == 0) red[k][tid >> 6] = v;
     }
     __syncthreads();
@@ -290,11 +283,8 @@ __global__ __launch_bounds__(256) void grad_scatter_kernel(
   const int s = blockIdx.y, np = covpts + 4, tid = threadIdx.x;
   for (int k = tid; k < np; k += 256) bins[k] = 0.0;
   __syncthreads();
-  const int tile = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * tile + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
-  while (ta * (ta + 1) / 2 > tile) --ta;
-  while ((ta + 1) * (ta + 2) / 2 <= tile) ++ta;
-  const int tb = tile - ta * (ta + 1) / 2;
+  int ta, tb;                             // row tile ta >= column tile tb
+  sp_lower_tile_decode(blockIdx.x, ta, tb);
   const int i = tb * 64 + (tid & 63), rq = tid >> 6;
   const double c1 = hcoef[s];
   const sp_star st = stars[s];
@@ -311,21 +301,9 @@ __global__ __launch_bounds__(256) void grad_scatter_kernel(
       for (int m = 1; m < M; ++m) aa += Al[(size_t)m * K + i] * Al[(size_t)m * K + j];
       const double H = mult * (c1 * 0.5 * (aa - Md * Ci[(size_t)j * Kr + i]) + wi + V[j]);
       const double T = temporal_factor(TK, ti, TK != SP_TEMPORAL_NONE ? t[(size_t)s * K + j] : 0.0, st.tau);
-      // the segment of the lag and the position inside it: SplineGen's index (flux.py:262-265)
-      int idx;
+      // the segment of the lag and the position inside it: SplineGen's index (sp_sweep.h)
       double x;
-      {
-#pragma clang fp contract(off)
-        const double lag = fabs(thi - theta[(size_t)s * K + j]);
-        const double qd = lag * inv_dx;
-        idx = (int)qd;
-        x = qd - (double)idx;
-        if (fabs(x - 0.5) > 0.5 - 1.0e-9) {
-          idx = (int)floor(lag / dx);
-          x = qd - (double)idx;
-        }
-        idx = idx < 0 ? 0 : (idx > covpts ? covpts : idx);
-      }
+      const int idx = sp_lag_segment(thi, theta[(size_t)s * K + j], dx, inv_dx, covpts, x);
       // value = sum_m yp[idx + m] c_m(x):  a0 = y1, a1 = -y0/3 - y1/2 + y2 - y3/6, a2 = (y0 + y2)/2 - y1,
       // a3 = ((y1 - y2) + (y3 - y0)/3)/2   (flux.py:322-330)
       const double x2 = x * x, x3 = x2 * x, HT = H * T;
@@ -382,11 +360,8 @@ __global__ __launch_bounds__(256) void grad_stars_kernel(
     for (int k = tid; k < np; k += 256) yp[k] = src[k];
   }
   __syncthreads();
-  const int tile = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * tile + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
-  while (ta * (ta + 1) / 2 > tile) --ta;
-  while ((ta + 1) * (ta + 2) / 2 <= tile) ++ta;
-  const int tb = tile - ta * (ta + 1) / 2;
+  int ta, tb;                             // row tile ta >= column tile tb
+  sp_lower_tile_decode(blockIdx.x, ta, tb);
   const int i = tb * 64 + (tid & 63), rq = tid >> 6;
   const double c1 = hcoef[s];
   double accp = 0.0, acct = 0.0;
@@ -404,20 +379,8 @@ __global__ __launch_bounds__(256) void grad_stars_kernel(
       const double H = mult * (c1 * 0.5 * (aa - Md * Ci[(size_t)j * Kr + i]) + wi + V[j]);
       const double thj = theta[(size_t)s * K + j], tj = t[(size_t)s * K + j];
       const double T = temporal_factor(TK, ti, tj, st.tau);
-      int idx;
       double x;
-      {
-#pragma clang fp contract(off)
-        const double lag = fabs(thi - thj);
-        const double qd = lag * inv_dx;
-        idx = (int)qd;
-        x = qd - (double)idx;
-        if (fabs(x - 0.5) > 0.5 - 1.0e-9) {
-          idx = (int)floor(lag / dx);
-          x = qd - (double)idx;
-        }
-        idx = idx < 0 ? 0 : (idx > covpts ? covpts : idx);
-      }
+      const int idx = sp_lag_segment(thi, thj, dx, inv_dx, covpts, x);
       const double y0 = yp[idx], y1 = yp[idx + 1], y2 = yp[idx + 2], y3 = yp[idx + 3];
       const double x2 = x * x, x3 = x2 * x;
       // the weights of the scatter and their derivatives with respect to x0
@@ -432,8 +395,8 @@ __global__ __launch_bounds__(256) void grad_stars_kernel(
       }
     }
   }
-  accp = wsum(accp);
-  acct = wsum(acct);
+  accp = sp_wave_sum(accp);
+  acct = sp_wave_sum(acct);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = accp;
     red[1][tid >> 6] = acct;
@@ -458,8 +421,8 @@ __global__ __launch_bounds__(256) void grad_stars_reduce_kernel(int K, int nwg, 
     a += spart[((size_t)s * nwg + w) * 2];
     b += spart[((size_t)s * nwg + w) * 2 + 1];
   }
-  a = wsum(a);
-  b = wsum(b);
+  a = sp_wave_sum(a);
+  b = sp_wave_sum(b);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = a;
     red[1][tid >> 6] = b;
@@ -537,8 +500,7 @@ GradLayout grad_layout(sp_handle *h, int S, int K, int M, int covpts) {
   GradLayout G;
   SpCarve c;
   const size_t d = sizeof(double);
-  G.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
-  G.cinv = c.take(d * (size_t)S * Kr * Kr);
+  sp_sweep_head(c, h, S, K, G.inv, G.cinv);
   G.vec = c.take(d * (size_t)S * (M + 3) * K);       // C^-1 [p, q, 1, r_0 .. r_{M-1}]
   G.dots = c.take(d * (size_t)S * M * 2);
   G.hcoef = c.take(d * S);
@@ -568,37 +530,40 @@ int grad_marginal(sp_handle *h, int S, int K, int M, const double *t_dev, const 
   const int Kr = sp_roundup(K, SP_NB);
   const GradLayout G = grad_layout(h, S, K, M, covpts);
   char *base = static_cast<char *>(workspace_dev);
-  void *ws = base + G.inv;
-  Layout L = make_layout(h, S, K, Kr, true, true);
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum), *qv = at<double>(ws, L.qv);
-  double *coef = at<double>(ws, L.coef), *sys = at<double>(ws, L.sys);
-  int32_t *info = at<int32_t>(ws, L.info);
-  double *Cinv = reinterpret_cast<double *>(base + G.cinv), *vec = reinterpret_cast<double *>(base + G.vec);
-  double *hcoef = reinterpret_cast<double *>(base + G.hcoef), *logdet = reinterpret_cast<double *>(base + G.logdet);
-  double *partial = reinterpret_cast<double *>(base + G.partial);
-  int rc;
-  // the covariance as the likelihood sees it, K x K (direct normalisation: sp.py:705-727, 1135-1151)
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, h->d_xp, temporal, nullptr,
-                               rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars_dev, meanvar_dev, nullptr, normalized, norm_order, zmax, rowsum, qv, coef,
-                                nullptr, st)))
+  const SpSweepViews V = sp_sweep_views(h, S, K, base + G.inv);
+  double *Cinv = at<double>(base, G.cinv), *logdet = at<double>(base, G.logdet);
+  if (const int rc = sp_launch_marginal_inverse(h, S, K, V, t_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
+                                                normalized, norm_order, zmax, Cinv, logdet, st))
     return rc;
-  // (straight into the corner of the system the inverse factors: leading dimension Kp)
-  // (the LOWER tiles of the Kr x Kr corner: the system form of the assembly with no rows below the matrix)
-  if ((rc = sp_launch_assemble(S, K, 0, Kr, 1, theta, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, h->d_xp, temporal,
-                               nullptr, normalized, qv, coef, diag_dev, 1, nullptr, sys, L.Kp, (long)L.Kp * L.Kp, st)))
-    return rc;
-  if ((rc = spd_inverse_in_place(h, S, K, L, ws, Cinv, logdet, st))) return rc;
-  return sp_launch_grad_sweep(S, K, Kr, M, Cinv, theta, t_dev, flux_dev, stars_dev, coef, qv, diag_dev, logdet, info,
-                              covpts, temporal, normalized, norm_order, zmax, vec,
-                              reinterpret_cast<double *>(base + G.dots), hcoef, partial, lnlike_dev, ybar_dev,
-                              meanbar_dev, status_dev, st, tab_dev, starbar_dev);
+  return sp_launch_grad_sweep(S, K, Kr, M, Cinv, V.theta, t_dev, flux_dev, stars_dev, V.coef, V.qv, diag_dev, logdet,
+                              V.info, covpts, temporal, normalized, norm_order, zmax, at<double>(base, G.vec),
+                              at<double>(base, G.dots), at<double>(base, G.hcoef), at<double>(base, G.partial),
+                              lnlike_dev, ybar_dev, meanbar_dev, status_dev, st, tab_dev, starbar_dev);
 }
 
 }  // namespace
+
+// The covariance as the likelihood sees it, K x K (direct normalisation: sp.py:705-727, 1135-1151), and its inverse: the
+// opening of the gradient sweep above and of the Fisher sweep (sp_fisher.hip), which must agree about C to the bit.
+int sp_launch_marginal_inverse(sp_handle *h, int S, int K, const SpSweepViews &V, const double *t, const double *diag,
+                               const sp_star *stars, int covpts, const double *tab, const double *meanvar, int temporal,
+                               int normalized, int order, double zmax, double *Cinv, double *logdet, hipStream_t st) {
+  const Layout &L = V.L;
+  int rc;
+  if ((rc = sp_launch_theta(S, K, t, stars, V.theta, st))) return rc;
+  if (normalized)
+    if ((rc = sp_launch_rowsum(S, K, V.theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal, nullptr, V.rowsum, st)))
+      return rc;
+  if ((rc = sp_launch_norm_coef(S, K, stars, meanvar, nullptr, normalized, order, zmax, V.rowsum, V.qv, V.coef, nullptr,
+                                st)))
+    return rc;
+  // (straight into the corner of the system the inverse factors: leading dimension Kp)
+  // (the LOWER tiles of the Kr x Kr corner: the system form of the assembly with no rows below the matrix)
+  if ((rc = sp_launch_assemble(S, K, 0, sp_roundup(K, SP_NB), 1, V.theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal,
+                               nullptr, normalized, V.qv, V.coef, diag, 1, nullptr, V.sys, L.Kp, (long)L.Kp * L.Kp, st)))
+    return rc;
+  return spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st);
+}
 
 // The head of the sweep, shared by the two branches (the conditional one: sp_grad_cond.hip): the products of C^-1 with
 // p, q, 1 and the residuals, then the scalars -- lnL, the pull-back through the normalisation (hcoef, w, meanbar) and,

@@ -18,14 +18,12 @@
 #include "sp_tile.h"
 #include "sp_cov.h"
 #include "sp_mm.h"
+#include "sp_sweep.h"
 
 namespace {
 
-__device__ __forceinline__ double gc_wsum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
+// sp_lower_tile_decode (sp_sweep.h) spelled through the references: the same numbers, but this file's kernels compile
+// to other instructions with the shared spelling (and sp_grad.hip's with this one), so the two stay apart
 __device__ __forceinline__ void gc_tile_decode(int tile, int &ta, int &tb) {
   ta = (int)((sqrtf(8.0f * tile + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
   while (ta * (ta + 1) / 2 > tile) --ta;
@@ -64,7 +62,7 @@ __global__ __launch_bounds__(256) void cond_raw_rows_kernel(int K, int Kr, int t
     row[j] = v;
     acc += v;
   }
-  acc = gc_wsum(acc);
+  acc = sp_wave_sum(acc);
   if (lane == 0) rowsum[(size_t)s * K + i] = acc;
 }
 
@@ -275,7 +273,7 @@ __global__ __launch_bounds__(256) void grad_cond_rot_kernel(
     bM[((size_t)s * Kr + k) * N + n] = tc + sf[nm] * (-sm);
     part += m * (sv[nm] * tc - sv[n] * ts);
   }
-  part = gc_wsum(part);
+  part = sp_wave_sum(part);
   if ((tid & 63) == 0) red[tid >> 6] = part;
   __syncthreads();
   if (tid == 0) thbar[(size_t)s * K + k] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -321,8 +319,8 @@ __global__ __launch_bounds__(256) void grad_cond_final_kernel(
     mubar[(size_t)s * N + n] = ragged ? nanv : meanbar[s] * A[(size_t)s * Kr * N + n];
   }
   for (int k = tid; k < K; k += 256) dp += thbar[(size_t)s * K + k] * t[(size_t)s * K + k];
-  di = gc_wsum(di);
-  dp = gc_wsum(dp);
+  di = sp_wave_sum(di);
+  dp = sp_wave_sum(dp);
   if ((tid & 63) == 0) {
     red[0][tid >> 6] = di;
     red[1][tid >> 6] = dp;
@@ -346,8 +344,7 @@ GradCondLayout grad_cond_layout(sp_handle *h, int S, int K) {
   GradCondLayout G;
   SpCarve c;
   const size_t d = sizeof(double), mat = d * (size_t)S * Kr * N;
-  G.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
-  G.cinv = c.take(d * (size_t)S * Kr * Kr);          // the raw lower tiles first, then C^-1
+  sp_sweep_head(c, h, S, K, G.inv, G.cinv);          // (cinv: the raw lower tiles first, then C^-1)
   G.vec = c.take(d * (size_t)S * 4 * K);             // C^-1 [p, q, 1, r]
   G.dots = c.take(d * (size_t)S * 2);
   G.hcoef = c.take(d * S);
@@ -394,12 +391,12 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   if ((long)S * ntri > 0x7ffffff0L) return SP_ERR_INVALID;
   const GradCondLayout G = grad_cond_layout(h, S, K);
   char *base = static_cast<char *>(workspace_dev);
-  void *ws = base + G.inv;
-  Layout L = make_layout(h, S, K, Kr, true, true);
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum), *qv = at<double>(ws, L.qv);
-  double *coef = at<double>(ws, L.coef), *sys = at<double>(ws, L.sys), *cm = at<double>(ws, L.condmean);
-  double *cs = at<double>(ws, L.cs), *vrow = at<double>(ws, L.vrow);
-  int32_t *info = at<int32_t>(ws, L.info);
+  const SpSweepViews V = sp_sweep_views(h, S, K, base + G.inv);
+  const Layout &L = V.L;
+  void *ws = V.ws;
+  double *theta = V.theta, *rowsum = V.rowsum, *qv = V.qv, *coef = V.coef, *sys = V.sys;
+  double *cm = at<double>(ws, L.condmean), *cs = at<double>(ws, L.cs), *vrow = at<double>(ws, L.vrow);
+  int32_t *info = V.info;
   double *Cinv = at<double>(base, G.cinv), *vec = at<double>(base, G.vec), *dots = at<double>(base, G.dots);
   double *hcoef = at<double>(base, G.hcoef), *logdet = at<double>(base, G.logdet), *meanbar = at<double>(base, G.meanbar);
   double *A = at<double>(base, G.A), *AT = at<double>(base, G.AT), *B = at<double>(base, G.B), *BT = at<double>(base, G.BT);

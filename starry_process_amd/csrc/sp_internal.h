@@ -427,8 +427,9 @@ int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B,
                       const LazyCov *lazy = nullptr, const int32_t *bsel = nullptr, int nsel = 0);
 
 // sp_pixel.hip: out[b][j][i] = out[b][i][j] for i > j on `batch` (<= 65535) n x n matrices; only entries on or below
-// the diagonal are read
-int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st);
+// the diagonal are read.  info [batch] (device, or null): a matrix with info[b] != 0 is filled with NaN instead
+int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st,
+                           const int32_t *info = nullptr);
 // sp_ylm_temporal_cond.hip: the C ABI's posterior maps of a time-variable process (include/starry_process_amd.h)
 extern "C" {
 size_t sp_ylm_conditional_temporal_workspace_bytes(sp_handle *h, int K, int T, int R, int with_cov);
@@ -473,6 +474,38 @@ int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *m
 int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
                          hipStream_t st);
 
+// What the gradient, conditional-gradient and Fisher sweeps share on the host.  Their workspaces begin alike: the SPD
+// inverse's own workspace (the lean layout with a system, K rows riding), then C^-1 [S][Kr][Kr], Kr = roundup(K, 64)
+static inline void sp_sweep_head(SpCarve &c, const sp_handle *h, int S, int K, size_t &inv, size_t &cinv) {
+  const int Kr = sp_roundup(K, SP_NB);
+  inv = c.take(make_layout(h, S, K, Kr, true, true).total);
+  cinv = c.take(sizeof(double) * (size_t)S * Kr * Kr);
+}
+// ... and the regions of the inverse's workspace `ws` (the sweep's workspace + inv) that they read and write
+struct SpSweepViews {
+  Layout L;
+  void *ws;
+  double *theta, *rowsum, *qv, *coef, *sys;
+  int32_t *info;
+};
+static inline SpSweepViews sp_sweep_views(const sp_handle *h, int S, int K, void *ws) {
+  SpSweepViews V;
+  V.L = make_layout(h, S, K, sp_roundup(K, SP_NB), true, true);
+  V.ws = ws;
+  V.theta = at<double>(ws, V.L.theta);
+  V.rowsum = at<double>(ws, V.L.rowsum);
+  V.qv = at<double>(ws, V.L.qv);
+  V.coef = at<double>(ws, V.L.coef);
+  V.sys = at<double>(ws, V.L.sys);
+  V.info = at<int32_t>(ws, V.L.info);
+  return V;
+}
+// sp_grad.hip: the covariance of the marginal branch as the likelihood sees it (phases, the normalisation's row sums and
+// coefficients, the assembly into the corner of the system) and its inverse into Cinv [S][Kr][Kr] (lower tiles); logdet
+// [S] or null.  Leaves V.theta, V.qv, V.coef and V.info for the sweep behind it.
+int sp_launch_marginal_inverse(sp_handle *h, int S, int K, const SpSweepViews &V, const double *t, const double *diag,
+                               const sp_star *stars, int covpts, const double *tab, const double *meanvar, int temporal,
+                               int normalized, int order, double zmax, double *Cinv, double *logdet, hipStream_t st);
 // sp_grad.hip: the head of the gradient sweep (products with C^-1, scalars); partial: [S][Kr / 64][4][K] doubles
 int sp_launch_grad_front(int S, int K, int Kr, int M, const double *Cinv, const double *flux, const sp_star *stars,
                          const void *coef, const double *qv, const double *diag, const double *logdet,

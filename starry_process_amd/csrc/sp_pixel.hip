@@ -65,8 +65,11 @@ constexpr int MT = 32;   // tile edge of the mirror
 
 // out[s][j][i] = out[s][i][j] for i > j: one workgroup per (32 x 32 tile on or below the diagonal, matrix).  The
 // tile is read along its rows into LDS and written transposed, again along rows; a diagonal tile writes only its
-// strict upper half.  Only entries on or below the diagonal are read.
-__global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__restrict__ out, long ldo, long strideOut) {
+// strict upper half.  Only entries on or below the diagonal are read.  INFO: a matrix with info[s] != 0 (sp_predict.hip: a
+// star whose K_tt did not factor) gets NaN everywhere.
+template <bool INFO>
+__global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__restrict__ out, long ldo, long strideOut,
+                                                           const int32_t *__restrict__ info) {
   __shared__ double T[MT][MT + 1];
   const int tile = blockIdx.x;
   int a = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
@@ -75,9 +78,20 @@ __global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__rest
   const int b = tile - a * (a + 1) / 2;   // tile row a >= tile column b
   const int r0 = a * MT, c0 = b * MT, tx = threadIdx.x & (MT - 1), ty = threadIdx.x / MT;
   double *o = out + (size_t)blockIdx.y * strideOut;
+  const bool bad = INFO && info[blockIdx.y] != 0;
   for (int y = ty; y < MT; y += 256 / MT) {
     const int i = r0 + y, j = c0 + tx;
-    T[y][tx] = (i < n && j < n && (a != b || j <= i)) ? o[(size_t)i * ldo + j] : 0.0;
+    if (!INFO) {     // (spelled apart from the other branch: this instantiation stays the kernel it was, to the instruction)
+      T[y][tx] = (i < n && j < n && (a != b || j <= i)) ? o[(size_t)i * ldo + j] : 0.0;
+    } else {
+      const bool in = i < n && j < n && (a != b || j <= i);
+      double v = in ? o[(size_t)i * ldo + j] : 0.0;
+      if (bad) {
+        v = __builtin_nan("");
+        if (in) o[(size_t)i * ldo + j] = v;
+      }
+      T[y][tx] = v;
+    }
   }
   __syncthreads();
   for (int y = ty; y < MT; y += 256 / MT) {
@@ -89,12 +103,15 @@ __global__ __launch_bounds__(256) void pixel_mirror_kernel(int n, double *__rest
 size_t pT_ld(int N) { return (size_t)sp_roundup(N, 32); }
 }  // namespace
 
-// the upper triangles of `batch` n x n matrices from their lower ones (pixel_mirror_kernel): batch <= 65535
-int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st) {
+// the upper triangles of `batch` n x n matrices from their lower ones (pixel_mirror_kernel): batch <= 65535.  info [batch]
+// (device, or null): a matrix with info[b] != 0 is filled with NaN instead
+int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st, const int32_t *info) {
   if (n <= 0 || batch <= 0) return SP_OK;
   const long nt = (n + MT - 1) / MT, ntiles = nt * (nt + 1) / 2;
   if (ntiles > 0x7fffffffL || batch > 65535) return SP_ERR_INVALID;
-  hipLaunchKernelGGL(pixel_mirror_kernel, dim3((unsigned)ntiles, batch), dim3(256), 0, st, n, out, ldo, strideOut);
+  const dim3 grid((unsigned)ntiles, batch);
+  if (info) hipLaunchKernelGGL(pixel_mirror_kernel<true>, grid, dim3(256), 0, st, n, out, ldo, strideOut, info);
+  else hipLaunchKernelGGL(pixel_mirror_kernel<false>, grid, dim3(256), 0, st, n, out, ldo, strideOut, info);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

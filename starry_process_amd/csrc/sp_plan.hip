@@ -20,6 +20,7 @@
 
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_sweep.h"
 
 namespace {
 
@@ -37,11 +38,8 @@ __global__ __launch_bounds__(256) void plan_wbar_kernel(
   const int s = blockIdx.y, np = covpts + 4, tid = threadIdx.x, wave = tid >> 6;
   for (int k = tid; k < 4 * np; k += 256) bins[k] = 0.0;
   __syncthreads();
-  const int tile = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * tile + 1.0f) - 1.0f) * 0.5f);     // row tile (ta >= tb)
-  while (ta * (ta + 1) / 2 > tile) --ta;
-  while ((ta + 1) * (ta + 2) / 2 <= tile) ++ta;
-  const int tb = tile - ta * (ta + 1) / 2;
+  int ta, tb;                             // row tile ta >= column tile tb
+  sp_lower_tile_decode(blockIdx.x, ta, tb);
   const int i = tb * 64 + (tid & 63);
   const sp_star st = stars[s];
   const int nobs = star_nobs(st, K);
@@ -54,20 +52,9 @@ __global__ __launch_bounds__(256) void plan_wbar_kernel(
     const int jend = ta * 64 + 64 < nobs ? ta * 64 + 64 : nobs;
     for (int j = ta * 64 + wave; j < jend; j += 4) {
       const double T = mult * temporal_factor(TK, ti, TK != SP_TEMPORAL_NONE ? t[(size_t)s * K + j] : 0.0, st.tau);
-      // the segment of the lag and the position inside it: SplineGen's index (sp_cov.h; flux.py:262-265)
-      int idx;
+      // the segment of the lag and the position inside it: SplineGen's index (sp_sweep.h)
       double x;
-      {
-        const double lag = fabs(thi - theta[(size_t)s * K + j]);
-        const double qd = lag * inv_dx;
-        idx = (int)qd;
-        x = qd - (double)idx;
-        if (fabs(x - 0.5) > 0.5 - 1.0e-9) {
-          idx = (int)floor(lag / dx);
-          x = qd - (double)idx;
-        }
-        idx = idx < 0 ? 0 : (idx > covpts ? covpts : idx);
-      }
+      const int idx = sp_lag_segment(thi, theta[(size_t)s * K + j], dx, inv_dx, covpts, x);
       // value = sum_k yp[idx + k] b_k(x):  a0 = y1, a1 = -y0/3 - y1/2 + y2 - y3/6, a2 = (y0 + y2)/2 - y1,
       // a3 = ((y1 - y2) + (y3 - y0)/3)/2   (flux.py:322-330)
       const double x2 = x * x, x3 = x2 * x;
@@ -108,20 +95,13 @@ __global__ __launch_bounds__(256) void plan_scalars_kernel(
   const int s = blockIdx.x, tid = threadIdx.x;
   const sp_star st = stars[s];
   const int nobs = star_nobs(st, K);
-  auto block_sum = [&](double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((tid & 63) == 0) red[tid >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-  };
   for (int m = 0; m <= M; ++m) {
     // (m == M: the variances)
     const double *src = m < M ? flux + ((size_t)s * M + m) * K : (diag ? diag + (size_t)s * K : nullptr);
     double a = 0.0;
     if (src)
       for (int i = tid; i < nobs; i += 256) a += src[i];
-    const double total = block_sum(a);
+    const double total = sp_block_sum_256(a, red);
     if (tid == 0) {
       if (m < M) sflux[(size_t)s * M + m] = total;
       else sdv[s] = total;

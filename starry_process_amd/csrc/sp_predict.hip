@@ -20,7 +20,8 @@
 // After the factorisation the Ks rows hold Y = K_st L^-T and the last row w = L^-1 r.  predict_reduce_kernel reads Y
 // once: mu_j = mean + Y_j . w and, when variances are asked for, var_j = kss_j - |Y_j|^2 from the same pass --
 // nothing Ks x Ks exists unless the full covariance is asked for (then K_ss is assembled by the kernel above,
-// K_ss -= Y Y^T runs on the matrix cores, lower tiles, and predict_mirror_kernel makes it exactly symmetric).
+// K_ss -= Y Y^T runs on the matrix cores, lower tiles, and sp_launch_mirror_lower, sp_pixel.hip, makes it exactly
+// symmetric).
 //
 // Compiled with -ffp-contract=off (Makefile: NOCONTRACT): the spline index and the entries must be the dense
 // assembly's, operation for operation.
@@ -252,37 +253,6 @@ __global__ __launch_bounds__(256) void predict_reduce_kernel(const double *__res
       const double prior = kss[kss_per_row ? (size_t)s * Ks + j : (size_t)s] + stars[s].baseline_var;
       var[(size_t)s * Ks + j] = bad ? __builtin_nan("") : prior - q;
     }
-  }
-}
-
-// out[s][j][i] = out[s][i][j] for i > j, 32 x 32 tiles on or below the diagonal (only those entries are read): the
-// posterior covariance exactly symmetric.  A star whose K_tt did not factor gets NaN everywhere.
-__global__ __launch_bounds__(256) void predict_mirror_kernel(int n, double *__restrict__ out, long ldo, long stride,
-                                                             const int32_t *__restrict__ info) {
-  constexpr int MT = 32;
-  __shared__ double T[MT][MT + 1];
-  const int tile = blockIdx.x;
-  int a = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
-  while ((long)a * (a + 1) / 2 > tile) --a;
-  while ((long)(a + 1) * (a + 2) / 2 <= tile) ++a;
-  const int b = tile - a * (a + 1) / 2;
-  const int r0 = a * MT, c0 = b * MT, tx = threadIdx.x & (MT - 1), ty = threadIdx.x / MT;
-  double *o = out + (size_t)blockIdx.y * stride;
-  const bool bad = info[blockIdx.y] != 0;
-  for (int y = ty; y < MT; y += 256 / MT) {
-    const int i = r0 + y, j = c0 + tx;
-    const bool in = i < n && j < n && (a != b || j <= i);
-    double v = in ? o[(size_t)i * ldo + j] : 0.0;
-    if (bad) {
-      v = __builtin_nan("");
-      if (in) o[(size_t)i * ldo + j] = v;
-    }
-    T[y][tx] = v;
-  }
-  __syncthreads();
-  for (int y = ty; y < MT; y += 256 / MT) {
-    const int i = c0 + y, j = r0 + tx;
-    if (i < n && j < n && (a != b || j > i)) o[(size_t)i * ldo + j] = T[tx][y];
   }
 }
 
@@ -522,11 +492,8 @@ int sp_predict_ensemble(sp_handle *h, int S, int K, int Ks, const double *t_dev,
       }
       const double *Y = sys + (size_t)K * Kp;
       if ((rc = sp_launch_gemm_nt(Y, ld, stride, Y, ld, stride, C, Ks, skk, Ks, Ks, K, -1.0, 1, 1, nb, st))) return rc;
-      const long nt = (Ks + 31) / 32, ntiles = nt * (nt + 1) / 2;
-      if (ntiles > 0x7fffffffL) return SP_ERR_INVALID;
-      hipLaunchKernelGGL(predict_mirror_kernel, dim3((unsigned)ntiles, nb), dim3(256), 0, st, Ks, C, (long)Ks, skk,
-                         info);
-      SP_LAUNCH_CHECK();
+      // (exactly symmetric; NaN everywhere for a star whose K_tt did not factor)
+      if ((rc = sp_launch_mirror_lower(C, Ks, (long)Ks, skk, nb, st, info))) return rc;
     }
     if (info_dev)
       SP_HIP(hipMemcpyAsync(info_dev + c0, info, sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, st));

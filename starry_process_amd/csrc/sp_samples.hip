@@ -30,17 +30,13 @@
 #include <optional>
 
 #include "sp_internal.h"
+#include "sp_sweep.h"
 
 namespace {
 
 constexpr int SM_TK = 64;     // columns of a sample's row block T (its 2 (ydeg + 2) <= 64 rotations, zero padded)
 constexpr int SM_SJ = 128;    // sm_spread_kernel: rows of C0 per workgroup (one per thread)
 constexpr int SM_SK = 64;     // ... and columns of Bp per LDS tile
-
-__device__ __forceinline__ double sm_wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // Per sample: the size vector (size.py:92-101: the sigmoid profile's Legendre coefficients, only the m = 0 entries are
 // nonzero), the Gauss-Jacobi rule of the latitude law and the scales of the rotations.  grid B.
@@ -107,7 +103,7 @@ __global__ __launch_bounds__(256) void sm_prepare_kernel(int ydeg, int spts, dou
       const double *row = basis + (size_t)l * spts;
       double acc = 0.0;
       for (int j = lane; j < spts; j += 64) acc += row[j] * s_b[j];
-      acc = sm_wave_sum(acc);
+      acc = sp_wave_sum(acc);
       if (lane == 0) {
         if (SPREAD) {
           evec[(size_t)b * nl + l] = acc;

@@ -12,17 +12,14 @@
 // with C_a, S_a sums of the N row-reductions r1, r2 of W o Ez -- O(N^2 + K' ydeg)
 // work.  One workgroup per table; everything but the N x N reads stays in LDS.
 #include "sp_internal.h"
+#include "sp_sweep.h"
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// sum over the 256 threads of the block; result valid in every thread
-__device__ __forceinline__ double block_sum(double v, double *red) {
-  v = wave_sum(v);
+// sum over the 256 threads of the block; result valid in every thread.  The wavefronts' sums are added LEFT TO RIGHT,
+// ((0 + 1) + 2) + 3: not sp_block_sum_256's pairs, and the table's bits depend on it
+__device__ __forceinline__ double table_sum_ltr(double v, double *red) {
+  v = sp_wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -57,11 +54,11 @@ __global__ __launch_bounds__(256) void table_rows_kernel(
     a += wv * En[j];
     b += wv * En[mirror[j]];
   }
-  a = wave_sum(a);
-  b = wave_sum(b);
+  a = sp_wave_sum(a);
+  b = sp_wave_sum(b);
   const int w = 2 * ln + 1;
   double m1 = lane < w ? rta1[ln * ln + lane] * wnp[blk[ln] + lane * w + (n - ln * ln)] : 0.0;   // (2 ydeg + 1 <= 64)
-  m1 = wave_sum(m1);
+  m1 = sp_wave_sum(m1);
   if (lane == 0) {
     double *rows = rows_all + ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * 3 * N;
     rows[n] = a;
@@ -102,12 +99,12 @@ __global__ __launch_bounds__(256) void table_finish_kernel(
   // first moment: w[l] = rTA1[l-block] . wnp[l];  mean = sum_l w[l] . ez[l-block]  (terms by table_rows_kernel)
   double part = 0.0;
   for (int n = tid; n < N; n += 256) part += rows[2 * N + n];
-  const double mean = block_sum(part, s_red);
+  const double mean = table_sum_ltr(part, s_red);
 
   // variance = <W, Ez> - mean^2 (flux.py:305-308)
   double pv = 0.0;
   for (int n = tid; n < N; n += 256) pv += s_r1[n];
-  const double wez = block_sum(pv, s_red);
+  const double wez = table_sum_ltr(pv, s_red);
   if (tid == 0) {
     meanvar_all[2 * it] = mean;
     meanvar_all[2 * it + 1] = wez - mean * mean;

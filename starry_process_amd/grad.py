@@ -40,6 +40,7 @@ __all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", 
            "EnsembleFisher", "ensemble_fisher", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional"]
 
 _cache = {}
+_BOUNDS = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}      # of the upstream integrals
 
 
 def _torch():
@@ -177,6 +178,12 @@ def _cn_chain(gm, gS, c, n, unit=None):
         return gm / c + 2.0 * gS / c, gm / n + gS / n
     gm, gS = unit()
     return n * gm + 2.0 * c * n * gS, c * gm + c * c * gS
+
+
+def _central_ends(name, x, h):
+    """(xl, xh) of the central difference about x, a step h max(|x|, 0.1) each way; one-sided within a step of a bound."""
+    step = h * max(abs(x), 0.1)
+    return max(x - step, _BOUNDS[name][0]), min(x + step, _BOUNDS[name][1])
 
 
 def _temporal_id(temporal_kernel, tau):
@@ -325,7 +332,6 @@ def hyper_gradient(t, flux, data_var, r=defaults["r"], dr=defaults["dr"], a=defa
         gc, gn = gm if (c == 0 and n != 0) else 0.0, gm + gS if (n == 0 and c != 0) else 0.0
     out.update({"c": float(gc), "n": float(gn)})
     x0 = {"r": r, "dr": dr, "a": a, "b": b}
-    bounds = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}
     if dr is None and exact:
         # one radius: the moments' exact tangents (upstream_device.ylm_moments_device_grad)
         from .upstream_device import ylm_moments_device_grad
@@ -339,13 +345,9 @@ def hyper_gradient(t, flux, data_var, r=defaults["r"], dr=defaults["dr"], a=defa
         if x0[name] is None:
             continue
         x = float(x0[name])
-        step = h * max(abs(x), 0.1)
-        lo_b, hi_b = bounds[name]
-        xl, xh = max(x - step, lo_b), min(x + step, hi_b)       # one-sided within a step of a bound
-        lo, hi = dict(x0), dict(x0)
-        lo[name], hi[name] = xl, xh
-        m0, S0_ = (mu, Sig) if xl == x else moments(lo["r"], lo["dr"], lo["a"], lo["b"])
-        m1, S1_ = (mu, Sig) if xh == x else moments(hi["r"], hi["dr"], hi["a"], hi["b"])
+        xl, xh = _central_ends(name, x, h)
+        m0, S0_ = (mu, Sig) if xl == x else moments(*[xl if k == name else x0[k] for k in x0])   # (x0: r, dr, a, b)
+        m1, S1_ = (mu, Sig) if xh == x else moments(*[xh if k == name else x0[k] for k in x0])
         out[name] = float(gmu @ ((m1 - m0) / (xh - xl)) + np.sum(gSig * ((S1_ - S0_) / (xh - xl))))
     return lnl, out
 
@@ -408,6 +410,24 @@ class _MarginalSweep(_EnsembleSweep):
         (e, self._stream), self._side = slots[0], slots[1:]
         return e
 
+    def _configure(self, covpts, normalized, h, upstream_kwargs, exact):
+        """The tail of the constructors: the numerical keywords the sweeps share."""
+        self._covpts, self._exact = int(defaults["covpts"] if covpts is None else covpts), bool(exact)
+        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
+
+    def _at_point(self, r, a, b, c, n, dr):
+        """(tab, mv, the arguments of ``_table_tangents``): the device drained, the tables at the point enqueued on the main
+        stream, the event behind them recorded.  Ends there: the caller's sweep is enqueued BEFORE the side streams' work."""
+        torch = _torch()
+        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
+        hp0 = dict(x0, c=float(c), n=float(n))
+        torch.cuda.synchronize(self._e.device)
+        with torch.cuda.stream(self._stream):
+            yp0, mean0, (mu, Sig, tab, mv) = self._tables(self._e, **hp0)
+            at_point = torch.cuda.Event()
+            at_point.record(self._stream)
+        return tab, mv, (x0, hp0, self._exact and dr is None, at_point, yp0, mean0, mu, Sig)
+
     def _tables(self, eng, **hp):
         """(yp [ntab, np], mean [ntab]) of the kernel tables at the given hyperparameters, on eng's stream."""
         from .upstream_device import ylm_moments_device
@@ -426,14 +446,10 @@ class _MarginalSweep(_EnsembleSweep):
         import torch
 
         r, a, b, c, n = hp0["r"], hp0["a"], hp0["b"], hp0["c"], hp0["n"]
-        bounds = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}
         dy, dm, events = {}, {}, []
 
         def central(eng, name):
-            x = float(x0[name])
-            step = self._h * max(abs(x), 0.1)
-            lo_b, hi_b = bounds[name]
-            xl, xh = max(x - step, lo_b), min(x + step, hi_b)        # one-sided within a step of a bound
+            xl, xh = _central_ends(name, float(x0[name]), self._h)
             yl, ml, _ = self._tables(eng, **dict(hp0, **{name: xl}))
             yh, mh, _ = self._tables(eng, **dict(hp0, **{name: xh}))
             dy[name], dm[name] = (yh - yl) / (xh - xl), (mh - ml) / (xh - xl)
@@ -563,9 +579,7 @@ class EnsembleGradient(_MarginalSweep):
         e = self._e
         self._ntab = utab.shape[0]
         self._table = _torch().as_tensor(stars["table"].astype(np.int64), device=e.device)
-        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
-        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
-        self._exact = bool(exact)
+        self._configure(covpts, normalized, h, upstream_kwargs, exact)
         self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
         self.lnlike = None
 
@@ -588,15 +602,9 @@ class EnsembleGradient(_MarginalSweep):
 
         wrt = _check_wrt(wrt, self._temporal is not None)
         e = self._e
-        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
-        hp0 = dict(x0, c=float(c), n=float(n))
-        torch.cuda.synchronize(e.device)
-        exact = self._exact and dr is None
         # main stream: the tables at the point, then the sweep
+        tab, mv, point = self._at_point(r, a, b, c, n, dr)
         with torch.cuda.stream(self._stream):
-            yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
-            at_point = torch.cuda.Event()
-            at_point.record(self._stream)
             sweep_kw = dict(diag=self._diag, covpts=self._covpts, temporal=self._temporal,
                             normalized=self._normalized, workspace=self._ws)
             sbar = None
@@ -606,7 +614,7 @@ class EnsembleGradient(_MarginalSweep):
                 lnl, ybar, mbar, sbar, status = e.lnlike_grad_marginal_stars(self._t, self._flux, self._stars, tab, mv,
                                                                              **sweep_kw)
         # three more streams, meanwhile: the tables' derivatives
-        dy, dm, events = self._table_tangents(x0, hp0, exact, at_point, yp0, mean0, mu, Sig)
+        dy, dm, events = self._table_tangents(*point)
         with torch.cuda.stream(self._stream):
             for ev in events:
                 self._stream.wait_event(ev)
@@ -693,9 +701,7 @@ class EnsembleFisher(_MarginalSweep):
         stars, utab = self._setup(t, np.zeros((S, t.shape[-1])), ferr, p, None, u, ydeg, 0.0, baseline_var, tau,
                                   temporal_kernel, device)
         self._flux = None
-        self._covpts = int(defaults["covpts"] if covpts is None else covpts)
-        self._normalized, self._h, self._ukw = bool(normalized), float(h), dict(upstream_kwargs or {})
-        self._exact = bool(exact)
+        self._configure(covpts, normalized, h, upstream_kwargs, exact)
         self._max_ws = None if max_workspace_bytes is None else int(max_workspace_bytes)
         self._ws = None
         self.per_star = self.status = self.names = self.tangents = None
@@ -720,15 +726,8 @@ class EnsembleFisher(_MarginalSweep):
 
         names = _check_params(params, dr is not None)
         e = self._e
-        x0 = {"r": float(r), "dr": dr, "a": float(a), "b": float(b)}
-        hp0 = dict(x0, c=float(c), n=float(n))
-        torch.cuda.synchronize(e.device)
-        exact = self._exact and dr is None
-        with torch.cuda.stream(self._stream):
-            yp0, mean0, (mu, Sig, tab, mv) = self._tables(e, **hp0)
-            at_point = torch.cuda.Event()
-            at_point.record(self._stream)
-        dy, dm, events = self._table_tangents(x0, hp0, exact, at_point, yp0, mean0, mu, Sig)
+        tab, mv, point = self._at_point(r, a, b, c, n, dr)
+        dy, dm, events = self._table_tangents(*point)
         with torch.cuda.stream(self._stream):
             for ev in events:
                 self._stream.wait_event(ev)
