@@ -704,11 +704,10 @@ static void allow_big_lds(F f) {
                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)attr_lds_limit);
 }
 
-int sp_launch_theta(int S, int K, const double *t, const sp_star *stars,
-                    double *theta, hipStream_t st, int32_t *info, uint32_t *status,
-                    const double *tab, int covpts, double *ptab) {
-  hipLaunchKernelGGL(theta_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K,
-                     t, stars, theta, info, status, tab, covpts + 4, ptab);
+// (the kernel reads the table and its length only to pack it into ptab: without one it is handed none)
+int sp_launch_theta(const SpProblem &P, double *theta, int32_t *info, uint32_t *status, double *ptab) {
+  hipLaunchKernelGGL(theta_kernel, dim3((P.K + 255) / 256, P.S), dim3(256), 0, P.st, P.K, P.t, P.stars, theta, info, status,
+                     ptab ? P.tab : nullptr, ptab ? P.covpts + 4 : 4, ptab);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -722,11 +721,8 @@ int sp_launch_spline_index(int K, const double *theta, double dx, long long *out
   return SP_OK;
 }
 
-int sp_launch_rowsum(int S, int K, const double *theta, const double *t,
-                     const sp_star *stars, int covpts, const double *tab,
-                     const double *meanvar, const double *xp, int temporal,
-                     const double *raw, double *rowsum, hipStream_t st) {
-  const int np = covpts + 4;
+int sp_launch_rowsum(const SpProblem &P, const double *theta, const double *raw, double *rowsum) {
+  const int K = P.K, np = P.covpts + 4;
   const size_t fixed = sizeof(double) * ((raw ? 0 : 4 * (size_t)np) + 256);
   if (fixed + sizeof(double) * 2 * 64 > attr_lds_limit) return SP_ERR_INVALID;
   // columns per LDS pass: all of them when they fit (K <= 4096 keeps every BASELINE
@@ -734,52 +730,43 @@ int sp_launch_rowsum(int S, int K, const double *theta, const double *t,
   const int chunk = K < 4096 ? K : 4096;
   const size_t lds = fixed + sizeof(double) * 2 * (size_t)chunk;
   if (lds > attr_lds_limit) return SP_ERR_INVALID;
-  dim3 grid((K + 63) / 64, S);
+  dim3 grid((K + 63) / 64, P.S);
   if (raw) {
     allow_big_lds(rowsum_kernel<true>);
-    hipLaunchKernelGGL(rowsum_kernel<true>, grid, dim3(256), lds, st, K, chunk, theta, t,
-                       stars, covpts, tab, meanvar, xp, temporal, raw, rowsum);
+    hipLaunchKernelGGL(rowsum_kernel<true>, grid, dim3(256), lds, P.st, K, chunk, theta, P.t, P.stars, P.covpts, P.tab,
+                       P.meanvar, P.xp, P.temporal, raw, rowsum);
   } else {
     allow_big_lds(rowsum_kernel<false>);
-    hipLaunchKernelGGL(rowsum_kernel<false>, grid, dim3(256), lds, st, K, chunk, theta,
-                       t, stars, covpts, tab, meanvar, xp, temporal, raw, rowsum);
+    hipLaunchKernelGGL(rowsum_kernel<false>, grid, dim3(256), lds, P.st, K, chunk, theta, P.t, P.stars, P.covpts, P.tab,
+                       P.meanvar, P.xp, P.temporal, raw, rowsum);
   }
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
 
-int sp_launch_norm_coef(int S, int K, const sp_star *stars, const double *meanvar,
-                        const double *condmean, int normalized, int order,
-                        double zmax, const double *rowsum, double *qv, void *coef,
-                        uint32_t *status, hipStream_t st) {
-  hipLaunchKernelGGL(norm_coef_kernel, dim3(S), dim3(256), 0, st, K, stars,
-                     meanvar, condmean, normalized, order, zmax, rowsum, qv,
-                     (Coef *)coef, status);
+int sp_launch_norm_coef(const SpProblem &P, const double *condmean, const double *rowsum, double *qv, void *coef,
+                        uint32_t *status) {
+  hipLaunchKernelGGL(norm_coef_kernel, dim3(P.S), dim3(256), 0, P.st, P.K, P.stars, P.meanvar, condmean, P.normalized,
+                     P.order, P.zmax, rowsum, qv, (Coef *)coef, status);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
 
-int sp_launch_assemble(int S, int K, int M, int Kp, int system,
-                       const double *theta, const double *t, const sp_star *stars,
-                       int covpts, const double *tab, const double *meanvar,
-                       const double *xp, int temporal, const double *raw,
-                       int normalized, const double *qv, const void *coef,
-                       const double *diag, int add_noise, const double *flux,
-                       double *out, long ldo, long strideo, hipStream_t st, double *part,
-                       int lazy_nfull) {
-  const int np = covpts + 4;
+int sp_launch_assemble(const SpProblem &P, const double *theta, const double *raw, const double *qv, const void *coef,
+                       const SpAsmOut &o, double *part, int lazy_nfull) {
+  const int np = P.covpts + 4, system = o.system;
   const size_t lds = sizeof(double) * ((raw ? 0 : 4 * (size_t)np) + 6 * 64 + (part ? 16 * 64 : 0));
   if (lds > attr_lds_limit) return SP_ERR_INVALID;
-  const int ntr = ((system ? Kp : K) + 63) / 64;
+  const int ntr = ((system ? o.Kp : P.K) + 63) / 64;
   const int ntiles = system ? ntr * (ntr + 1) / 2 : ntr * ntr;
-  dim3 grid(ntiles, S);
+  dim3 grid(ntiles, P.S);
 #define SP_ASM(FM, SY, ...)                                                                \
   do {                                                                                     \
     allow_big_lds(assemble_kernel<FM, SY, ##__VA_ARGS__>);                                 \
-    hipLaunchKernelGGL((assemble_kernel<FM, SY, ##__VA_ARGS__>), grid, dim3(256), lds, st, K, \
-                       M, Kp, theta, t, stars, covpts, tab, meanvar, xp,                   \
-                       temporal, raw, normalized, qv, (const Coef *)coef, diag,            \
-                       add_noise, flux, out, ldo, strideo, ntr, part, lazy_nfull);         \
+    hipLaunchKernelGGL((assemble_kernel<FM, SY, ##__VA_ARGS__>), grid, dim3(256), lds, P.st, P.K, \
+                       P.M, o.Kp, theta, P.t, P.stars, P.covpts, P.tab, P.meanvar, P.xp,   \
+                       P.temporal, raw, P.normalized, qv, (const Coef *)coef, P.diag,      \
+                       o.add_noise, P.flux, o.out, o.ldo, o.strideo, ntr, part, lazy_nfull); \
   } while (0)
   if (part && !system) return SP_ERR_INVALID;
   if (part && raw)
@@ -797,6 +784,14 @@ int sp_launch_assemble(int S, int K, int M, int Kp, int system,
 #undef SP_ASM
   SP_LAUNCH_CHECK();
   return SP_OK;
+}
+
+int sp_launch_direct_form(const SpProblem &P, const double *theta, const double *raw, const double *condmean,
+                          double *rowsum, double *qv, void *coef, uint32_t *status, const SpAsmOut &o) {
+  int rc;
+  if (P.normalized && (rc = sp_launch_rowsum(P, theta, raw, rowsum))) return rc;
+  if ((rc = sp_launch_norm_coef(P, condmean, rowsum, qv, coef, status))) return rc;
+  return sp_launch_assemble(P, theta, raw, qv, coef, o);
 }
 
 #ifdef SP_ASM_STAMPS
@@ -842,11 +837,10 @@ extern "C" int sp_debug_asm_chunks(int ntr, int nchunk, int *start_host) {
   return SP_OK;
 }
 
-int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, const double *t,
-                            const sp_star *stars, int covpts, const double *ptab, const double *meanvar,
-                            int temporal, const double *flux, double *sys, hipStream_t st, double *part,
+int sp_launch_assemble_sums(const SpProblem &P, int Kp, const double *theta, const double *ptab, double *sys, double *part,
                             int lazy_nfull, int *nflat) {
-  const size_t lds = sp_assemble_sums_lds(Kp, covpts, temporal);
+  const int K = P.K, temporal = P.temporal;
+  const size_t lds = sp_assemble_sums_lds(Kp, P.covpts, temporal);
   if (lds > SP_ASM_LDS_MAX || !ptab || !part) return SP_ERR_INVALID;
   const int ntr = Kp / 64, ntiles = ntr * (ntr + 1) / 2;
   // tiles per workgroup: a function of nothing but the build -- the column sums of a strip segment are added
@@ -856,7 +850,7 @@ int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, co
   if (nchunk > SP_ASM_MAX_CHUNKS) nchunk = SP_ASM_MAX_CHUNKS;
   if (ntiles > 65535) return SP_ERR_INVALID;
   const AsmChunks chunks = asm_chunks(ntr, nchunk);
-  dim3 grid(nchunk, S);
+  dim3 grid(nchunk, P.S);
   if ((size_t)nchunk > (size_t)ntr * K) return SP_ERR_INVALID;   // (part holds ntr K doubles per star)
   if (nflat) *nflat = nchunk;       // part[s][0 .. nchunk): one partial total per workgroup
 #ifdef SP_PROBE
@@ -867,8 +861,8 @@ int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, co
 #define SP_ASMS(TK)                                                                                     \
   do {                                                                                                  \
     allow_big_lds(assemble_sums_kernel<TK>);                                                            \
-    hipLaunchKernelGGL((assemble_sums_kernel<TK>), grid, dim3(256), lds, st, K, M, Kp, theta, t, stars, \
-                       covpts, ptab, meanvar, flux, sys, (long)Kp, (long)Kp * Kp, ntr, part, lazy_nfull, chunks); \
+    hipLaunchKernelGGL((assemble_sums_kernel<TK>), grid, dim3(256), lds, P.st, K, P.M, Kp, theta, P.t, P.stars, \
+                       P.covpts, ptab, P.meanvar, P.flux, sys, (long)Kp, (long)Kp * Kp, ntr, part, lazy_nfull, chunks); \
   } while (0)
   if (temporal == SP_TEMPORAL_NONE) SP_ASMS(SP_TEMPORAL_NONE);
   else if (temporal == SP_TEMPORAL_MATERN32) SP_ASMS(SP_TEMPORAL_MATERN32);
@@ -879,12 +873,10 @@ int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, co
   return SP_OK;
 }
 
-int sp_launch_defer_finish(int S, int K, int M, int Kp, const sp_star *stars, const double *meanvar,
-                           const double *condmean, int order, double zmax, const double *part,
-                           const double *diag, const double *flux, double *sys, void *coef, double *rscal,
-                           uint32_t *status, hipStream_t st, int nflat) {
-  hipLaunchKernelGGL(defer_finish_kernel, dim3(S), dim3(1024), 0, st, K, M, Kp, Kp / 64, nflat, stars, meanvar,
-                     condmean, order, zmax, part, diag, flux, sys, (Coef *)coef, rscal, status);
+int sp_launch_defer_finish(const SpProblem &P, int Kp, const double *condmean, const double *part, double *sys, void *coef,
+                           double *rscal, uint32_t *status, int nflat) {
+  hipLaunchKernelGGL(defer_finish_kernel, dim3(P.S), dim3(1024), 0, P.st, P.K, P.M, Kp, Kp / 64, nflat, P.stars, P.meanvar,
+                     condmean, P.order, P.zmax, part, P.diag, P.flux, sys, (Coef *)coef, rscal, status);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

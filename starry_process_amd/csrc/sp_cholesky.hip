@@ -349,14 +349,11 @@ int sp_launch_cholesky_systems(sp_handle *h, double *sys, int S, int K, int Kp,
   return sp_launch_cholesky_groups(h, 1, &g, K, Kp);
 }
 
-int sp_launch_lnlike_reduce(const double *sys, int S, int K, int M, int Kp,
-                            const int32_t *info, double *lnlike, uint32_t *status,
-                            hipStream_t st, uint32_t *status_out, const sp_star *stars,
-                            const void *defer_coef, const double *rscal, int dvec) {
-  if (defer_coef && !rscal) return SP_ERR_INVALID;
-  hipLaunchKernelGGL(lnlike_reduce_kernel, dim3(S), dim3(256), 0, st, sys,
-                     (long)Kp, (long)Kp * Kp, K, M, info, lnlike, status, status_out, stars,
-                     (const RedCoef *)defer_coef, rscal, dvec);
+int sp_launch_lnlike_reduce(const double *sys, int S, int Kp, const int32_t *info, const SpReduceArgs &red, hipStream_t st) {
+  if (red.coef && !red.rscal) return SP_ERR_INVALID;
+  hipLaunchKernelGGL(lnlike_reduce_kernel, dim3(S), dim3(256), 0, st, sys, (long)Kp, (long)Kp * Kp, red.K, red.M, info,
+                     red.lnlike, red.status, red.status_out, red.stars, (const RedCoef *)red.coef,
+                     red.coef ? red.rscal : nullptr, red.dvec);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

@@ -125,10 +125,9 @@ __global__ __launch_bounds__(256) void cond_system_kernel(
 }  // namespace
 
 // The lower tiles of B1 A^T into the padded systems, assembled (see the header).  defer: part != null.
-int sp_launch_cond_system(const double *B1, const double *A, int N, int Kr, int S, int K, int M, int Kp,
-                          const double *t, const sp_star *stars, int temporal, const void *coef,
-                          const double *diag, const double *flux, double *sys, double *part,
-                          hipStream_t st) {
+int sp_launch_cond_system(const SpProblem &P, const double *B1, const double *A, int N, int Kr, int Kp, const void *coef,
+                          double *sys, double *part) {
+  const int S = P.S, K = P.K, M = P.M;
   if (S <= 0) return SP_OK;
   if ((N % 16) || (Kr % 64) || Kr < K || (Kp % 64) || Kp < K + M) return SP_ERR_INVALID;
   if ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B1)) & 15) return SP_ERR_INVALID;
@@ -136,12 +135,12 @@ int sp_launch_cond_system(const double *B1, const double *A, int N, int Kr, int 
   const long nblk = sp_xcd_grid(S, (long)ntr * (ntr + 1) / 2);
   if (nblk > 0x7fffffffL) return SP_ERR_INVALID;
   if (part)
-    hipLaunchKernelGGL((cond_system_kernel<true>), dim3((unsigned)nblk), dim3(256), 0, st, B1, A, N,
-                       (long)Kr * N, K, M, Kp, t, stars, temporal, (const CondCoef *)coef, diag, flux, sys,
+    hipLaunchKernelGGL((cond_system_kernel<true>), dim3((unsigned)nblk), dim3(256), 0, P.st, B1, A, N,
+                       (long)Kr * N, K, M, Kp, P.t, P.stars, P.temporal, (const CondCoef *)coef, P.diag, P.flux, sys,
                        part, ntr, S);
   else
-    hipLaunchKernelGGL((cond_system_kernel<false>), dim3((unsigned)nblk), dim3(256), 0, st, B1, A, N,
-                       (long)Kr * N, K, M, Kp, t, stars, temporal, (const CondCoef *)coef, diag, flux, sys,
+    hipLaunchKernelGGL((cond_system_kernel<false>), dim3((unsigned)nblk), dim3(256), 0, P.st, B1, A, N,
+                       (long)Kr * N, K, M, Kp, P.t, P.stars, P.temporal, (const CondCoef *)coef, P.diag, P.flux, sys,
                        part, ntr, S);
   SP_LAUNCH_CHECK();
   return SP_OK;

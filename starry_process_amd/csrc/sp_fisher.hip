@@ -367,25 +367,26 @@ FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts) {
   return F;
 }
 
-// one group of stars (the slices of the per-star inputs and outputs already taken)
-int fisher_group(sp_handle *h, int S, int K, int P, int ntab, const double *t, const double *diag, const sp_star *stars,
-                 int covpts, const double *tab, const double *meanvar, const double *dyp, const double *dmean,
-                 int temporal, int normalized, int order, double zmax, double *fisher, double *dcov, uint32_t *status,
-                 void *workspace, hipStream_t st) {
+// one group of stars (Q: their problem; the slices of the per-star outputs already taken)
+int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double *dyp, const double *dmean, double *fisher,
+                 double *dcov, uint32_t *status, void *workspace) {
+  const int S = Q.S, K = Q.K, covpts = Q.covpts, temporal = Q.temporal, normalized = Q.normalized, order = Q.order;
+  const double *t = Q.t, *tab = Q.tab;
+  const double zmax = Q.zmax;
+  const sp_star *stars = Q.stars;
+  hipStream_t st = Q.st;
   const int Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB, np = covpts + 4;
   const FisherLayout F = fisher_layout(h, S, K, P, covpts);
   char *base = static_cast<char *>(workspace);
-  const SpSweepViews V = sp_sweep_views(h, S, K, base + F.inv);
-  double *theta = V.theta, *qv = V.qv, *coef = V.coef;
+  const SpViews V = sp_sweep_views(h, S, K, base + F.inv);
+  double *theta = V.theta(), *qv = V.qv(), *coef = V.coef();
   double *Cinv = at<double>(base, F.cinv), *dC = at<double>(base, F.dC), *G = at<double>(base, F.G);
   double *drow = at<double>(base, F.drow), *dsc = at<double>(base, F.dsc), *part = at<double>(base, F.part);
   double *ones = at<double>(base, F.ones);
   const size_t kr2 = (size_t)Kr * Kr;
   int rc;
   // C and its inverse: the gradient sweep's own opening (sp_grad.hip)
-  if ((rc = sp_launch_marginal_inverse(h, S, K, V, t, diag, stars, covpts, tab, meanvar, temporal, normalized, order, zmax,
-                                       Cinv, nullptr, st)))
-    return rc;
+  if ((rc = sp_launch_marginal_inverse(h, Q, V, Cinv, nullptr))) return rc;
   if (ntr > 1) {
     hipLaunchKernelGGL(fisher_mirror_kernel, dim3(ntr * (ntr - 1) / 2, S), dim3(256), 0, st, Kr, Cinv);
     SP_LAUNCH_CHECK();
@@ -416,7 +417,7 @@ int fisher_group(sp_handle *h, int S, int K, int P, int ntab, const double *t, c
     hipLaunchKernelGGL(fisher_ones_kernel, dim3(ntr, S), dim3(256), 0, st, K, Kr, Cinv, ones);
     SP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, stars, (const SpCoef *)coef, V.info,
+  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, stars, (const SpCoef *)coef, V.info(),
                      part, ones, dmean, normalized, zmax, fisher, status);
   SP_LAUNCH_CHECK();
   return SP_OK;
@@ -456,13 +457,15 @@ int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, c
     else hi = mid - 1;
   }
   const int group = lo;
+  SpProblem Q;   // (no data: M = 0, flux null)
+  Q.S = S, Q.K = K, Q.t = t_dev, Q.diag = diag_dev, Q.stars = stars_dev;
+  Q.covpts = covpts, Q.tab = tab_dev, Q.meanvar = meanvar_dev, Q.xp = h->d_xp;
+  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = (hipStream_t)stream;
   for (int s0 = 0; s0 < S; s0 += group) {
     const int n = S - s0 < group ? S - s0 : group;
-    const int rc = fisher_group(h, n, K, P, ntab, t_dev + (size_t)s0 * K, diag_dev ? diag_dev + (size_t)s0 * K : nullptr,
-                                stars_dev + s0, covpts, tab_dev, meanvar_dev, dyp_dev, dmean_dev, temporal, normalized,
-                                norm_order, zmax, fisher_dev + (size_t)s0 * P * P,
+    const int rc = fisher_group(h, Q.slice(s0, s0 + n), P, ntab, dyp_dev, dmean_dev, fisher_dev + (size_t)s0 * P * P,
                                 dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr,
-                                status_dev ? status_dev + s0 : nullptr, workspace_dev, (hipStream_t)stream);
+                                status_dev ? status_dev + s0 : nullptr, workspace_dev);
     if (rc) return rc;
   }
   return SP_OK;

@@ -435,19 +435,19 @@ __global__ __launch_bounds__(256) void grad_stars_reduce_kernel(int K, int nwg, 
   }
 }
 
-int sp_launch_grad_sweep(int S, int K, int Kr, int M, double *Cinv, const double *theta, const double *t,
-                         const double *flux, const sp_star *stars, const void *coef, const double *qv,
-                         const double *diag, const double *logdet, const int32_t *info, int covpts, int temporal,
-                         int normalized, int order, double zmax, double *vec, double *dots, double *hcoef,
-                         double *partial, double *lnlike, double *ybar, double *meanbar, uint32_t *status,
-                         hipStream_t st, const double *tab = nullptr, double *starbar = nullptr) {
+int sp_launch_grad_sweep(const SpProblem &P, const SpViews &V, double *Cinv, const double *logdet, double *vec,
+                         double *dots, double *hcoef, double *partial, double *lnlike, double *ybar, double *meanbar,
+                         uint32_t *status, double *starbar) {
+  const int S = P.S, K = P.K, M = P.M, Kr = sp_roundup(K, SP_NB), covpts = P.covpts, temporal = P.temporal;
+  const double *theta = V.theta(), *t = P.t, *tab = P.tab;
+  const sp_star *stars = P.stars;
+  hipStream_t st = P.st;
   const int ntr = Kr / 64, np = covpts + 4;
   // (part: the scatter's partial tables later -- [S][ntr][4][K] doubles of it here, grad_layout)
   // (starbar: sp_lnlike_grad_marginal_stars -- the same launches, the scalars kernel also writes the per-star slots it
   //  has in hand, and two more launches behind the table's adjoint)
   {
-    const int rc = sp_launch_grad_front(S, K, Kr, M, Cinv, flux, stars, coef, qv, diag, logdet, info, normalized, order,
-                                        zmax, vec, dots, hcoef, partial, lnlike, meanbar, status, starbar, st);
+    const int rc = sp_launch_grad_front(P, V, Cinv, logdet, vec, dots, hcoef, partial, lnlike, meanbar, status, starbar);
     if (rc) return rc;
   }
   const size_t lds = sizeof(double) * np;
@@ -514,65 +514,60 @@ GradLayout grad_layout(sp_handle *h, int S, int K, int M, int covpts) {
   return G;
 }
 
-// the sweep behind the three entry points; starbar == nullptr: the launches of rounds 4-6, nothing else
-int grad_marginal(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev, const double *diag_dev,
-                  const sp_star *stars_dev, int covpts, const double *tab_dev, const double *meanvar_dev, int temporal,
-                  int normalized, int norm_order, double zmax, void *workspace_dev, double *lnlike_dev, double *ybar_dev,
-                  double *meanbar_dev, uint32_t *status_dev, double *starbar_dev, void *stream) {
+// the sweep behind the three entry points (P as they filled it, before any check); starbar == nullptr: the launches of
+// rounds 4-6, nothing else
+int grad_marginal(sp_handle *h, const SpProblem &P, void *workspace_dev, double *lnlike_dev, double *ybar_dev,
+                  double *meanbar_dev, uint32_t *status_dev, double *starbar_dev) {
+  const int S = P.S, K = P.K, M = P.M;
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h ||!t_dev || !flux_dev || !stars_dev || !tab_dev || !meanvar_dev || !workspace_dev || !lnlike_dev ||
-      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || M < 1 || covpts < 1 || norm_order < 0 ||
-      norm_order > SP_NORM_MAXORDER)
+  if (!h || !P.t || !P.flux || !P.stars || !P.tab || !P.meanvar || !workspace_dev || !lnlike_dev ||
+      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || M < 1 || P.covpts < 1 || P.order < 0 ||
+      P.order > SP_NORM_MAXORDER)
     return SP_ERR_INVALID;
-  if (h->xp_covpts != covpts) return SP_ERR_STATE;
+  if (h->xp_covpts != P.covpts) return SP_ERR_STATE;
   if (S == 0) return SP_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int Kr = sp_roundup(K, SP_NB);
-  const GradLayout G = grad_layout(h, S, K, M, covpts);
+  const GradLayout G = grad_layout(h, S, K, M, P.covpts);
   char *base = static_cast<char *>(workspace_dev);
-  const SpSweepViews V = sp_sweep_views(h, S, K, base + G.inv);
+  const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
   double *Cinv = at<double>(base, G.cinv), *logdet = at<double>(base, G.logdet);
-  if (const int rc = sp_launch_marginal_inverse(h, S, K, V, t_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
-                                                normalized, norm_order, zmax, Cinv, logdet, st))
-    return rc;
-  return sp_launch_grad_sweep(S, K, Kr, M, Cinv, V.theta, t_dev, flux_dev, stars_dev, V.coef, V.qv, diag_dev, logdet,
-                              V.info, covpts, temporal, normalized, norm_order, zmax, at<double>(base, G.vec),
-                              at<double>(base, G.dots), at<double>(base, G.hcoef), at<double>(base, G.partial),
-                              lnlike_dev, ybar_dev, meanbar_dev, status_dev, st, tab_dev, starbar_dev);
+  if (const int rc = sp_launch_marginal_inverse(h, P, V, Cinv, logdet)) return rc;
+  return sp_launch_grad_sweep(P, V, Cinv, logdet, at<double>(base, G.vec), at<double>(base, G.dots),
+                              at<double>(base, G.hcoef), at<double>(base, G.partial), lnlike_dev, ybar_dev, meanbar_dev,
+                              status_dev, starbar_dev);
 }
 
 }  // namespace
 
 // The covariance as the likelihood sees it, K x K (direct normalisation: sp.py:705-727, 1135-1151), and its inverse: the
-// opening of the gradient sweep above and of the Fisher sweep (sp_fisher.hip), which must agree about C to the bit.
-int sp_launch_marginal_inverse(sp_handle *h, int S, int K, const SpSweepViews &V, const double *t, const double *diag,
-                               const sp_star *stars, int covpts, const double *tab, const double *meanvar, int temporal,
-                               int normalized, int order, double zmax, double *Cinv, double *logdet, hipStream_t st) {
+// opening of the gradient sweep above and of the Fisher sweep (sp_fisher.hip), which agree about C to the bit because
+// this is the likelihood's own chain (sp_launch_direct_form).
+int sp_launch_marginal_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, double *Cinv, double *logdet) {
   const Layout &L = V.L;
   int rc;
-  if ((rc = sp_launch_theta(S, K, t, stars, V.theta, st))) return rc;
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, V.theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal, nullptr, V.rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars, meanvar, nullptr, normalized, order, zmax, V.rowsum, V.qv, V.coef, nullptr,
-                                st)))
-    return rc;
+  if ((rc = sp_launch_theta(P, V.theta()))) return rc;
   // (straight into the corner of the system the inverse factors: leading dimension Kp)
   // (the LOWER tiles of the Kr x Kr corner: the system form of the assembly with no rows below the matrix)
-  if ((rc = sp_launch_assemble(S, K, 0, sp_roundup(K, SP_NB), 1, V.theta, t, stars, covpts, tab, meanvar, h->d_xp, temporal,
-                               nullptr, normalized, V.qv, V.coef, diag, 1, nullptr, V.sys, L.Kp, (long)L.Kp * L.Kp, st)))
+  SpProblem C = P;
+  C.M = 0;
+  C.flux = nullptr;
+  if ((rc = sp_launch_direct_form(C, V.theta(), nullptr, nullptr, V.rowsum(), V.qv(), V.coef(), nullptr,
+                                  SpAsmOut{V.sys(), L.Kp, (long)L.Kp * L.Kp, 1, sp_roundup(P.K, SP_NB), 1})))
     return rc;
-  return spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st);
+  return spd_inverse_in_place(h, P.S, P.K, L, V.ws, Cinv, logdet, P.st);
 }
 
 // The head of the sweep, shared by the two branches (the conditional one: sp_grad_cond.hip): the products of C^-1 with
 // p, q, 1 and the residuals, then the scalars -- lnL, the pull-back through the normalisation (hcoef, w, meanbar) and,
 // with starbar, the per-star slots 2-5.  `partial`: [S][Kr / 64][4][K] doubles.
-int sp_launch_grad_front(int S, int K, int Kr, int M, const double *Cinv, const double *flux, const sp_star *stars,
-                         const void *coef, const double *qv, const double *diag, const double *logdet,
-                         const int32_t *info, int normalized, int order, double zmax, double *vec, double *dots,
-                         double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
-                         double *starbar, hipStream_t st) {
+int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cinv, const double *logdet, double *vec,
+                         double *dots, double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
+                         double *starbar) {
+  const int S = P.S, K = P.K, M = P.M, Kr = sp_roundup(K, SP_NB), normalized = P.normalized, order = P.order;
+  const double *flux = P.flux, *diag = P.diag, *qv = V.qv(), *coef = V.coef();
+  const double zmax = P.zmax;
+  const sp_star *stars = P.stars;
+  const int32_t *info = V.info();
+  hipStream_t st = P.st;
   const int ntr = Kr / 64;
   for (int v0 = 0; v0 < M + 3; v0 += 4) {
     hipLaunchKernelGGL(grad_matvec_kernel, dim3(ntr * (ntr + 1) / 2, S), dim3(256), 0, st, K, Kr, M, v0, Cinv, flux, stars,
@@ -619,9 +614,11 @@ int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const doubl
                                   const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
                                   void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
                                   uint32_t *status_dev, void *stream) {
-  return grad_marginal(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
-                       normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, nullptr,
-                       stream);
+  SpProblem P;
+  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h ? h->d_xp : nullptr;
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  return grad_marginal(h, P, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, nullptr);
 }
 
 int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const double *t_dev, const double *flux_dev,
@@ -631,9 +628,11 @@ int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const doubl
                                   uint32_t *status_dev, double *starbar_dev, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!starbar_dev) return SP_ERR_INVALID;
-  return grad_marginal(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
-                       normalized, norm_order, zmax, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev,
-                       starbar_dev, stream);
+  SpProblem P;
+  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h ? h->d_xp : nullptr;
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  return grad_marginal(h, P, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, starbar_dev);
 }
 
 }  // extern "C"

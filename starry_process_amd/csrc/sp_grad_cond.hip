@@ -391,12 +391,14 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   if ((long)S * ntri > 0x7ffffff0L) return SP_ERR_INVALID;
   const GradCondLayout G = grad_cond_layout(h, S, K);
   char *base = static_cast<char *>(workspace_dev);
-  const SpSweepViews V = sp_sweep_views(h, S, K, base + G.inv);
+  const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
   const Layout &L = V.L;
-  void *ws = V.ws;
-  double *theta = V.theta, *rowsum = V.rowsum, *qv = V.qv, *coef = V.coef, *sys = V.sys;
-  double *cm = at<double>(ws, L.condmean), *cs = at<double>(ws, L.cs), *vrow = at<double>(ws, L.vrow);
-  int32_t *info = V.info;
+  double *theta = V.theta(), *rowsum = V.rowsum(), *qv = V.qv(), *coef = V.coef(), *sys = V.sys();
+  double *cm = V.condmean(), *cs = V.cs(), *vrow = V.vrow();
+  SpProblem P;
+  P.S = S, P.K = K, P.M = 1, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = st;
   double *Cinv = at<double>(base, G.cinv), *vec = at<double>(base, G.vec), *dots = at<double>(base, G.dots);
   double *hcoef = at<double>(base, G.hcoef), *logdet = at<double>(base, G.logdet), *meanbar = at<double>(base, G.meanbar);
   double *A = at<double>(base, G.A), *AT = at<double>(base, G.AT), *B = at<double>(base, G.B), *BT = at<double>(base, G.BT);
@@ -405,15 +407,18 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   const long sAB = (long)Kr * N;
   int rc;
   // ---- forward: C as the likelihood sees it, in the corner of the system the inverse factors
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
-  if ((rc = sp_launch_design(h, L, ws, stars_dev, rta1_dev, A, st, Kr))) return rc;
+  if ((rc = sp_launch_theta(P, theta))) return rc;
+  if ((rc = sp_launch_design(h, V, stars_dev, rta1_dev, A, st, Kr))) return rc;
   if ((rc = sp_launch_cond_mean(S, N, Kr, A, h->d_mean_ylm, cm, st))) return rc;
   if ((rc = sp_launch_gemm_nt(A, N, sAB, h->d_cov_ylm, N, 0, B, N, sAB, Kr, N, N, 1.0, 0, 0, S, st))) return rc;
   // (the raw covariance, temporal factor applied, where C^-1 will be: [S][Kr][Kr]; its row sums)
   if (N % 64 == 0) {
-    if ((rc = sp_launch_cond_system(B, A, N, Kr, S, K, 0, Kr, t_dev, stars_dev, temporal, nullptr, nullptr, nullptr, Cinv,
-                                    partial, st)))
-      return rc;
+    // (the Kr x Kr matrix alone, raw: no residual rows, no variances)
+    SpProblem R = P;
+    R.M = 0;
+    R.flux = nullptr;
+    R.diag = nullptr;
+    if ((rc = sp_launch_cond_system(R, B, A, N, Kr, Kr, nullptr, Cinv, partial))) return rc;
     if (normalized) {
       hipLaunchKernelGGL(cond_rowsum_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, ntr, partial, rowsum);
       SP_LAUNCH_CHECK();
@@ -424,16 +429,14 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
                        rowsum);
     SP_LAUNCH_CHECK();
   }
-  if ((rc = sp_launch_norm_coef(S, K, stars_dev, nullptr, cm, normalized, norm_order, zmax, rowsum, qv, coef, nullptr, st)))
-    return rc;
+  if ((rc = sp_launch_norm_coef(P, cm, rowsum, qv, coef, nullptr))) return rc;
   hipLaunchKernelGGL(cond_finish_kernel, dim3(ntri, S), dim3(256), 0, st, K, Kr, Cinv, stars_dev, (const SpCoef *)coef, qv,
                      diag_dev, normalized, sys, (long)L.Kp, (long)L.Kp * L.Kp);
   SP_LAUNCH_CHECK();
-  if ((rc = spd_inverse_in_place(h, S, K, L, ws, Cinv, logdet, st))) return rc;
+  if ((rc = spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st))) return rc;
   // ---- the head of the reverse sweep: lnL, hcoef = c1, w, alpha, meanbar and the slots 2-5 of starbar
-  if ((rc = sp_launch_grad_front(S, K, Kr, 1, Cinv, flux_dev, stars_dev, coef, qv, diag_dev, logdet, info, normalized,
-                                 norm_order, zmax, vec, dots, hcoef, partial, lnlike_dev, meanbar, status_dev, starbar_dev,
-                                 st)))
+  if ((rc = sp_launch_grad_front(P, V, Cinv, logdet, vec, dots, hcoef, partial, lnlike_dev, meanbar, status_dev,
+                                 starbar_dev)))
     return rc;
   // ---- B = (H o T) A
   const unsigned nblk = (unsigned)sp_xcd_grid(S, ntri);

@@ -290,6 +290,32 @@ struct sp_plan {
   int nrep;                // sp_plan_replicate: S = nrep x the source plan's stars (0: not a replica)
 };
 
+// The stars' data and the covariance model of one likelihood-type call: what every launcher of the family reads, filled
+// once by the C entry point behind its argument checks.  A site that deliberately passes something else copies the
+// problem and overwrites that field on a line of its own.
+struct SpProblem {
+  int S = 0, K = 0, M = 0;
+  const double *t = nullptr;          // [S][K] cadence times
+  const double *flux = nullptr;       // [S][M][K] light curves (null: no residual rows)
+  const double *diag = nullptr;       // [S][K] per-cadence variances, or null
+  const sp_star *stars = nullptr;
+  int covpts = 0;                     // (1 in the conditional branch; tab, meanvar and xp are then whatever the caller gave)
+  const double *tab = nullptr, *meanvar = nullptr, *xp = nullptr;   // the kernel tables, their moments, the lag grid
+  int temporal = 0, normalized = 0, order = 0;
+  double zmax = 0.0;
+  hipStream_t st = nullptr;
+  // the problem of the stars [s0, s1) (tab and meanvar are indexed through sp_star::table and do not move)
+  SpProblem slice(int s0, int s1) const {
+    SpProblem p = *this;
+    p.S = s1 - s0;
+    p.t = t + (size_t)s0 * K;
+    p.flux = flux ? flux + (size_t)s0 * M * K : nullptr;
+    p.diag = diag ? diag + (size_t)s0 * K : nullptr;
+    p.stars = stars + s0;
+    return p;
+  }
+};
+
 // What the workgroup that factors a group's LAST pivot block does behind it (sp_panel.hip): the
 // log-likelihood reduction of its star (sp_reduce.h), when the residual / normalisation rows live in
 // that block's row tile and the block is factored in a panel launch's tail (sp_panel_fuses_reduce).
@@ -346,61 +372,46 @@ int sp_launch_kernel_table(sp_handle *h, const double *rta1_dev, int ntab,
                            double *meanvar_dev, hipStream_t st, int nsets = 0, const double *ez_dev = nullptr,
                            const double *Ez_dev = nullptr);
 // sp_assemble.hip
-int sp_launch_theta(int S, int K, const double *t, const sp_star *stars,
-                    double *theta, hipStream_t st, int32_t *info = nullptr,
-                    uint32_t *status = nullptr, const double *tab = nullptr, int covpts = 0,
+struct SpViews;
+int sp_launch_theta(const SpProblem &P, double *theta, int32_t *info = nullptr, uint32_t *status = nullptr,
                     double *ptab = nullptr);
-int sp_launch_rowsum(int S, int K, const double *theta, const double *t,
-                     const sp_star *stars, int covpts, const double *tab,
-                     const double *meanvar, const double *xp, int temporal,
-                     const double *raw, double *rowsum, hipStream_t st);
-int sp_launch_norm_coef(int S, int K, const sp_star *stars, const double *meanvar,
-                        const double *condmean, int normalized, int order,
-                        double zmax, const double *rowsum, double *qv, void *coef,
-                        uint32_t *status, hipStream_t st);
-int sp_launch_assemble(int S, int K, int M, int Kp, int system,
-                       const double *theta, const double *t, const sp_star *stars,
-                       int covpts, const double *tab, const double *meanvar,
-                       const double *xp, int temporal, const double *raw,
-                       int normalized, const double *qv, const void *coef,
-                       const double *diag, int add_noise, const double *flux,
-                       double *out, long ldo, long strideo, hipStream_t st, double *part = nullptr,
-                       int lazy_nfull = 0);
+int sp_launch_rowsum(const SpProblem &P, const double *theta, const double *raw, double *rowsum);
+int sp_launch_norm_coef(const SpProblem &P, const double *condmean, const double *rowsum, double *qv, void *coef,
+                        uint32_t *status);
+// where the assembly writes: `system`: the lower tiles of padded systems of Kp rows (residual rows and identity padding
+// below the matrix); else the full K x K matrices.  add_noise: the data variances go on the diagonal
+struct SpAsmOut {
+  double *out;
+  long ldo, strideo;
+  int system, Kp, add_noise;
+};
+int sp_launch_assemble(const SpProblem &P, const double *theta, const double *raw, const double *qv, const void *coef,
+                       const SpAsmOut &o, double *part = nullptr, int lazy_nfull = 0);
+// The direct form of the normalisation behind the phases: row sums (when normalised), coefficients, assembly -- the
+// one chain behind sp_cov_*_batched, the likelihood without the deferred form, and the gradient and Fisher sweeps
+int sp_launch_direct_form(const SpProblem &P, const double *theta, const double *raw, const double *condmean,
+                          double *rowsum, double *qv, void *coef, uint32_t *status, const SpAsmOut &o);
 // the most LDS the hot form of the assembly (assemble_sums_kernel; sp_assemble_sums_lds, sp_tuning.h) may ask for
 #define SP_ASM_LDS_MAX (80 * 1024)
-int sp_launch_assemble_sums(int S, int K, int M, int Kp, const double *theta, const double *t,
-                            const sp_star *stars, int covpts, const double *ptab, const double *meanvar,
-                            int temporal, const double *flux, double *sys, hipStream_t st, double *part,
+int sp_launch_assemble_sums(const SpProblem &P, int Kp, const double *theta, const double *ptab, double *sys, double *part,
                             int lazy_nfull, int *nflat);
-int sp_launch_defer_finish(int S, int K, int M, int Kp, const sp_star *stars, const double *meanvar,
-                           const double *condmean, int order, double zmax, const double *part,
-                           const double *diag, const double *flux, double *sys, void *coef, double *rscal,
-                           uint32_t *status, hipStream_t st, int nflat = 0);
-// sp_planasm.hip
-int sp_launch_assemble_planned(int S, int K, int M, int Kp, const PlanDev &plan, const double *t,
-                               const sp_star *stars, int covpts, const double *tab, const double *meanvar,
-                               int temporal, const double *flux, const double *diag, double *sys, int nfull,
-                               int ncolw, int order, double zmax, void *coef, double *rscal, double *ptab, int32_t *info,
-                               uint32_t *status, hipStream_t st, double *img, long lts, int fuse0, double *rid, int dfrom);
+int sp_launch_defer_finish(const SpProblem &P, int Kp, const double *condmean, const double *part, double *sys, void *coef,
+                           double *rscal, uint32_t *status, int nflat = 0);
+// sp_planasm.hip (V: the likelihood's workspace -- sys, coef, rscal, info, status, invL)
+int sp_launch_assemble_planned(const SpProblem &P, const PlanDev &plan, const PlannedShape &ps, const SpViews &V,
+                               double *ptab, double *rid);
 // sp_cond.hip
-int sp_launch_cond_system(const double *B1, const double *A, int N, int Kr, int S, int K, int M, int Kp,
-                          const double *t, const sp_star *stars, int temporal, const void *coef,
-                          const double *diag, const double *flux, double *sys, double *part,
-                          hipStream_t st);
+int sp_launch_cond_system(const SpProblem &P, const double *B1, const double *A, int N, int Kr, int Kp, const void *coef,
+                          double *sys, double *part);
 // sp_small.hip (a shape sp_small_k_serves, sp_tuning.h)
-int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const double *t, const sp_star *stars, int covpts,
-                           const double *tab, const double *meanvar, int temporal, const double *flux, const double *diag,
-                           int order, double zmax, double *lnlike, uint32_t *status_out, hipStream_t st);
+int sp_launch_small_lnlike(const SpProblem &P, const PlanDev &plan, double *lnlike, uint32_t *status_out);
 // sp_cholesky.hip
 int sp_launch_cholesky_systems(sp_handle *h, double *sys, int S, int K, int Kp,
                                int32_t *info, double *invL, hipStream_t st);
 int sp_launch_cholesky_groups(sp_handle *h, int ngroups, const sp_chol_group *grp, int K,
                               int Kp);
-int sp_launch_lnlike_reduce(const double *sys, int S, int K, int M, int Kp,
-                            const int32_t *info, double *lnlike, uint32_t *status,
-                            hipStream_t st, uint32_t *status_out = nullptr,
-                            const sp_star *stars = nullptr, const void *defer_coef = nullptr,
-                            const double *rscal = nullptr, int dvec = 0);
+// (red.lnlike .. red.dvec as the panel kernel's fused reduction takes them; red.live_rows is not read here)
+int sp_launch_lnlike_reduce(const double *sys, int S, int Kp, const int32_t *info, const SpReduceArgs &red, hipStream_t st);
 int sp_launch_pad_in(const double *A, int K, long lda, long strideA, double *sys,
                      int Kp, int M, const double *resid, int S, hipStream_t st, int ident = 0,
                      int32_t *nonfinite = nullptr);
@@ -462,9 +473,32 @@ struct Layout {
       B1, raw, part, sys, total;
 };
 Layout make_layout(const sp_handle *h, int S, int K, int M, bool with_sys, bool lean = false, int s0 = 0);
-// the design matrices of L.S stars into A_out, Kr rows per star (L.theta filled; uses L.cs, L.vrow, L.Rinc), and
-// mean[s] = (A_s mu_y)[0] from matrices of `rows` rows per star
-int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars, const double *rta1, double *A_out,
+// a workspace carved by a Layout, by region (addresses only: a region the layout leaves empty is never touched)
+struct SpViews {
+  Layout L;
+  void *ws;
+  double *d(size_t off) const { return at<double>(ws, off); }
+  double *theta() const { return d(L.theta); }
+  double *rowsum() const { return d(L.rowsum); }
+  double *qv() const { return d(L.qv); }
+  double *coef() const { return d(L.coef); }
+  double *rscal() const { return d(L.rscal); }
+  double *condmean() const { return d(L.condmean); }
+  double *cs() const { return d(L.cs); }
+  double *vrow() const { return d(L.vrow); }
+  double *Rinc() const { return d(L.Rinc); }
+  double *invL() const { return d(L.invL); }
+  double *A() const { return d(L.A); }
+  double *B1() const { return d(L.B1); }
+  double *raw() const { return d(L.raw); }
+  double *part() const { return d(L.part); }
+  double *sys() const { return d(L.sys); }
+  int32_t *info() const { return at<int32_t>(ws, L.info); }
+  uint32_t *status() const { return at<uint32_t>(ws, L.status); }
+};
+// the design matrices of V.L.S stars into A_out, Kr rows per star (theta filled; uses cs, vrow, Rinc: Kr == K:
+// contiguous stars; Kr > K: the rows beyond K are zeroed), and mean[s] = (A_s mu_y)[0] from matrices of `rows` rows
+int sp_launch_design(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, double *A_out,
                      hipStream_t st, int Kr);
 // (sel [S] (device, or null): star s takes mu + sel[s] N, one of nsets; an index outside them gives NaN)
 int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
@@ -481,37 +515,19 @@ static inline void sp_sweep_head(SpCarve &c, const sp_handle *h, int S, int K, s
   inv = c.take(make_layout(h, S, K, Kr, true, true).total);
   cinv = c.take(sizeof(double) * (size_t)S * Kr * Kr);
 }
-// ... and the regions of the inverse's workspace `ws` (the sweep's workspace + inv) that they read and write
-struct SpSweepViews {
-  Layout L;
-  void *ws;
-  double *theta, *rowsum, *qv, *coef, *sys;
-  int32_t *info;
-};
-static inline SpSweepViews sp_sweep_views(const sp_handle *h, int S, int K, void *ws) {
-  SpSweepViews V;
-  V.L = make_layout(h, S, K, sp_roundup(K, SP_NB), true, true);
-  V.ws = ws;
-  V.theta = at<double>(ws, V.L.theta);
-  V.rowsum = at<double>(ws, V.L.rowsum);
-  V.qv = at<double>(ws, V.L.qv);
-  V.coef = at<double>(ws, V.L.coef);
-  V.sys = at<double>(ws, V.L.sys);
-  V.info = at<int32_t>(ws, V.L.info);
-  return V;
+// ... and the inverse's workspace `ws` (the sweep's workspace + inv)
+static inline SpViews sp_sweep_views(const sp_handle *h, int S, int K, void *ws) {
+  return SpViews{make_layout(h, S, K, sp_roundup(K, SP_NB), true, true), ws};
 }
-// sp_grad.hip: the covariance of the marginal branch as the likelihood sees it (phases, the normalisation's row sums and
-// coefficients, the assembly into the corner of the system) and its inverse into Cinv [S][Kr][Kr] (lower tiles); logdet
-// [S] or null.  Leaves V.theta, V.qv, V.coef and V.info for the sweep behind it.
-int sp_launch_marginal_inverse(sp_handle *h, int S, int K, const SpSweepViews &V, const double *t, const double *diag,
-                               const sp_star *stars, int covpts, const double *tab, const double *meanvar, int temporal,
-                               int normalized, int order, double zmax, double *Cinv, double *logdet, hipStream_t st);
-// sp_grad.hip: the head of the gradient sweep (products with C^-1, scalars); partial: [S][Kr / 64][4][K] doubles
-int sp_launch_grad_front(int S, int K, int Kr, int M, const double *Cinv, const double *flux, const sp_star *stars,
-                         const void *coef, const double *qv, const double *diag, const double *logdet,
-                         const int32_t *info, int normalized, int order, double zmax, double *vec, double *dots,
-                         double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
-                         double *starbar, hipStream_t st);
+// sp_grad.hip: the covariance of the marginal branch as the likelihood sees it (phases, then the direct form into the
+// corner of the system) and its inverse into Cinv [S][Kr][Kr] (lower tiles); logdet [S] or null.  Leaves theta, qv,
+// coef and info of V for the sweep behind it.
+int sp_launch_marginal_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, double *Cinv, double *logdet);
+// sp_grad.hip: the head of the gradient sweep (products with C^-1, scalars) on V's coef, qv and info; partial:
+// [S][Kr / 64][4][K] doubles, Kr = roundup(K, 64)
+int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cinv, const double *logdet, double *vec,
+                         double *dots, double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
+                         double *starbar);
 
 // grid of a grid-stride kernel: blocks of 256 threads covering `total` elements, at most `max_blocks` of them
 static inline unsigned grid_for(size_t total, size_t max_blocks = 8192) {

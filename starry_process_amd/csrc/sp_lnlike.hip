@@ -204,13 +204,14 @@ __global__ void get_gpmean_kernel(int S, const double *__restrict__ coef,
   if (s < S) out[s] = coef[8 * s + 6] - 1.0;  // mu - 1 = flux mean
 }
 
-// design matrix for S stars into A_out (uses L.theta already filled); Kr rows per star in A_out and
-// in the scratch L.B1 (Kr == K: contiguous stars; Kr > K: the rows beyond K are zeroed)
-int build_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars,
-                 const double *rta1, double *A_out, hipStream_t st, int Kr) {
-  const int S = L.S, K = L.K, N = L.N;
-  double *cs = at<double>(ws, L.cs), *vrow = at<double>(ws, L.vrow);
-  double *Rinc = at<double>(ws, L.Rinc), *theta = at<double>(ws, L.theta);
+}  // namespace
+
+// design matrix for S stars into A_out (theta already filled); Kr rows per star in A_out and
+// in the scratch B1 (Kr == K: contiguous stars; Kr > K: the rows beyond K are zeroed)
+int sp_launch_design(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, double *A_out,
+                     hipStream_t st, int Kr) {
+  const int S = V.L.S, K = V.L.K, N = V.L.N;
+  double *cs = V.cs(), *vrow = V.vrow(), *Rinc = V.Rinc(), *theta = V.theta();
   hipLaunchKernelGGL(inc_cs_kernel, dim3((S + 255) / 256), dim3(256), 0, st, S,
                      stars, cs);
   SP_LAUNCH_CHECK();
@@ -235,6 +236,15 @@ int build_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars,
   return SP_OK;
 }
 
+int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
+                        const int32_t *sel, int nsets) {
+  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, rows, A, mu, mean, sel, nsets);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+namespace {
+
 // The moments of the conditional branch: the handle's one pair (sel == null), or nsets pairs mu [nsets][N], cov
 // [nsets][N][N] of which system s takes sel[s] (sp_lnlike_ensemble_sets) -- the product A_s Sigma then picks its
 // second operand per system inside the kernel (sp_gemm.hip), one launch either way.
@@ -244,135 +254,89 @@ struct CondSets {
   int nsets;
 };
 
-// raw (un-normalised, no temporal factor) conditional covariance into L.raw
-int build_conditional_raw(const CondSets &cs, const Layout &L, void *ws, hipStream_t st) {
-  const int S = L.S, K = L.K, N = L.N;
-  double *A = at<double>(ws, L.A), *B1 = at<double>(ws, L.B1);
-  double *raw = at<double>(ws, L.raw), *cm = at<double>(ws, L.condmean);
-  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, K, A, cs.mu, cm, cs.sel, cs.nsets);
-  SP_LAUNCH_CHECK();
-  // B1 = A Sigma_y  (Sigma_y symmetric: A . Sigma_y^T), then raw = B1 A^T
-  int rc = sp_launch_gemm_nt(A, N, (long)K * N, cs.cov, N, cs.sel ? (long)N * N : 0, B1, N,
-                             (long)K * N, K, N, N, 1.0, 0, 0, S, st, 0, nullptr, cs.sel, cs.nsets);
+// raw (un-normalised, no temporal factor) conditional covariance into V's raw, its mean into condmean
+int build_conditional_raw(const CondSets &cs, const SpViews &V, hipStream_t st) {
+  const int S = V.L.S, K = V.L.K, N = V.L.N;
+  double *A = V.A(), *B1 = V.B1();
+  int rc = sp_launch_cond_mean(S, N, K, A, cs.mu, V.condmean(), st, cs.sel, cs.nsets);
   if (rc) return rc;
-  return sp_launch_gemm_nt(B1, N, (long)K * N, A, N, (long)K * N, raw, K,
+  // B1 = A Sigma_y  (Sigma_y symmetric: A . Sigma_y^T), then raw = B1 A^T
+  rc = sp_launch_gemm_nt(A, N, (long)K * N, cs.cov, N, cs.sel ? (long)N * N : 0, B1, N,
+                         (long)K * N, K, N, N, 1.0, 0, 0, S, st, 0, nullptr, cs.sel, cs.nsets);
+  if (rc) return rc;
+  return sp_launch_gemm_nt(B1, N, (long)K * N, A, N, (long)K * N, V.raw(), K,
                            (long)K * K, K, K, N, 1.0, 0, 0, S, st);
 }
 
-// stage A: everything up to the assembled systems, for one group on its stream
-int lnlike_assemble(sp_handle *h, const Layout &L, void *ws, int K, int M, const double *t_dev,
-                    const double *flux_dev, const double *diag_dev, const sp_star *stars_dev,
-                    int conditional, int covpts, const double *tab_dev,
-                    const double *meanvar_dev, const double *rta1_dev, int temporal,
-                    int normalized, int norm_order, double zmax, hipStream_t st, int lazy_nfull = 0,
-                    const CondSets *sets = nullptr) {
-  const int S = L.S;
-  const CondSets cs = sets ? *sets : CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1};
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
-  double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
-  double *raw = at<double>(ws, L.raw), *cm = at<double>(ws, L.condmean);
-  double *sys = at<double>(ws, L.sys);
-  int32_t *info = at<int32_t>(ws, L.info);
-  uint32_t *status = at<uint32_t>(ws, L.status);
+// where the likelihood's assembly writes: the padded systems of V
+SpAsmOut system_out(const SpViews &V) { return SpAsmOut{V.sys(), V.L.Kp, (long)V.L.Kp * V.L.Kp, 1, V.L.Kp, 1}; }
+
+// stage A: everything up to the assembled systems, for one group (P: its stars) on its stream
+int lnlike_assemble(sp_handle *h, const SpProblem &P, const SpViews &V, int conditional, const double *rta1_dev,
+                    int lazy_nfull, const CondSets &cs) {
+  const Layout &L = V.L;
+  const int S = P.S;
+  hipStream_t st = P.st;
+  const bool deferred = P.normalized && h->tune.defer_norm;
   int rc;
   // (the stars' tables packed for the spline gathers of the assembly and of the tiles formed at first
   //  touch, in the design-matrix region the marginal path does not use)
-  double *ptab = (conditional || 4 * (size_t)(covpts + 4) > (size_t)L.Kr * L.N) ? nullptr : at<double>(ws, L.A);
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st, info, status, tab_dev, covpts, ptab)))
-    return rc;
+  double *ptab = (conditional || 4 * (size_t)(P.covpts + 4) > (size_t)L.Kr * L.N) ? nullptr : V.A();
+  if ((rc = sp_launch_theta(P, V.theta(), V.info(), V.status(), ptab))) return rc;
   const double *rawp = nullptr;
   const double *condmean = nullptr;
-  if (conditional && (L.N % 64) == 0 && ((normalized && h->tune.defer_norm) || !normalized)) {
+  if (conditional && (L.N % 64) == 0 && (deferred || !P.normalized)) {
     // Conditional branch, fused (sp_cond.hip): B1 = A Sigma_y, then the LOWER tiles of B1 A^T land in
     // the system assembled -- no K x K raw matrix written and read back (round 2: 0.5 GB per 64-star
     // step), 40 % fewer flops in the second product.  The design-matrix buffers hold roundup(K, 64)
     // rows per star (zero beyond K) so that every tile of the products is a full one.
     const int N = L.N, Kr = L.Kr;
-    double *A = at<double>(ws, L.A), *B1 = at<double>(ws, L.B1);
-    if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, A, st, Kr))) return rc;
-    hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, Kr, A, cs.mu, cm, cs.sel, cs.nsets);
-    SP_LAUNCH_CHECK();
+    double *A = V.A(), *B1 = V.B1(), *cm = V.condmean();
+    if ((rc = sp_launch_design(h, V, P.stars, rta1_dev, A, st, Kr))) return rc;
+    if ((rc = sp_launch_cond_mean(S, N, Kr, A, cs.mu, cm, st, cs.sel, cs.nsets))) return rc;
     if ((rc = sp_launch_gemm_nt(A, N, (long)Kr * N, cs.cov, N, cs.sel ? (long)N * N : 0, B1, N, (long)Kr * N, Kr, N, N,
                                 1.0, 0, 0, S, st, 0, nullptr, cs.sel, cs.nsets)))
       return rc;
-    if (normalized) {
-      double *part = at<double>(ws, L.part);
-      if ((rc = sp_launch_cond_system(B1, A, N, Kr, S, K, M, L.Kp, t_dev, stars_dev, temporal, nullptr,
-                                      nullptr, flux_dev, sys, part, st)))
-        return rc;
-      return sp_launch_defer_finish(S, K, M, L.Kp, stars_dev, meanvar_dev, cm, norm_order, zmax, part,
-                                    diag_dev, flux_dev, sys, coef, at<double>(ws, L.rscal), status, st);
+    if (P.normalized) {
+      SpProblem raw = P;
+      raw.diag = nullptr;   // (the variances go in with the normalisation, behind the sums)
+      if ((rc = sp_launch_cond_system(raw, B1, A, N, Kr, L.Kp, nullptr, V.sys(), V.part()))) return rc;
+      return sp_launch_defer_finish(P, L.Kp, cm, V.part(), V.sys(), V.coef(), V.rscal(), V.status());
     }
-    if ((rc = sp_launch_norm_coef(S, K, stars_dev, meanvar_dev, cm, 0, norm_order, zmax, rowsum, qv, coef,
-                                  status, st)))
-      return rc;
-    return sp_launch_cond_system(B1, A, N, Kr, S, K, M, L.Kp, t_dev, stars_dev, temporal, coef, diag_dev,
-                                 flux_dev, sys, nullptr, st);
+    if ((rc = sp_launch_norm_coef(P, cm, V.rowsum(), V.qv(), V.coef(), V.status()))) return rc;
+    return sp_launch_cond_system(P, B1, A, N, Kr, L.Kp, V.coef(), V.sys(), nullptr);
   }
+  SpProblem C = P;
   if (conditional) {
-    if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, at<double>(ws, L.A), st, K)))
-      return rc;
-    if ((rc = build_conditional_raw(cs, L, ws, st))) return rc;
-    rawp = raw;
-    condmean = cm;
+    if ((rc = sp_launch_design(h, V, P.stars, rta1_dev, V.A(), st, P.K))) return rc;
+    if ((rc = build_conditional_raw(cs, V, st))) return rc;
+    rawp = V.raw();
+    condmean = V.condmean();
+    C.covpts = 1;   // (no table behind a raw covariance)
   }
-  const int cp = conditional ? 1 : covpts;
-  if (normalized && h->tune.defer_norm) {
+  if (deferred) {
+    C.normalized = 1;   // (whatever non-zero value the caller gave)
     // deferred normalisation: ONE pass over the K^2 entries (raw tiles + their row / column sums),
     // then the normalisation's vectors as three more rows of the system (sp_assemble.hip)
-    double *part = at<double>(ws, L.part);
     int nflat = 0;
-    if (!rawp && ptab && sp_assemble_sums_lds(L.Kp, cp, temporal) <= SP_ASM_LDS_MAX)
-      rc = sp_launch_assemble_sums(S, K, M, L.Kp, theta, t_dev, stars_dev, cp, ptab, meanvar_dev, temporal,
-                                   flux_dev, sys, st, part, lazy_nfull, &nflat);
+    if (!rawp && ptab && sp_assemble_sums_lds(L.Kp, C.covpts, C.temporal) <= SP_ASM_LDS_MAX)
+      rc = sp_launch_assemble_sums(C, L.Kp, V.theta(), ptab, V.sys(), V.part(), lazy_nfull, &nflat);
     else
-      rc = sp_launch_assemble(S, K, M, L.Kp, 1, theta, t_dev, stars_dev, cp, tab_dev, meanvar_dev,
-                              h->d_xp, temporal, rawp, 1, qv, coef, diag_dev, 1, flux_dev, sys,
-                              L.Kp, (long)L.Kp * L.Kp, st, part, lazy_nfull);
+      rc = sp_launch_assemble(C, V.theta(), rawp, V.qv(), V.coef(), system_out(V), V.part(), lazy_nfull);
     if (rc) return rc;
-    return sp_launch_defer_finish(S, K, M, L.Kp, stars_dev, meanvar_dev, condmean, norm_order, zmax,
-                                  part, diag_dev, flux_dev, sys, coef, at<double>(ws, L.rscal), status, st, nflat);
+    return sp_launch_defer_finish(C, L.Kp, condmean, V.part(), V.sys(), V.coef(), V.rscal(), V.status(), nflat);
   }
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, cp, tab_dev, meanvar_dev,
-                               h->d_xp, temporal, rawp, rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars_dev, meanvar_dev, condmean, normalized,
-                                norm_order, zmax, rowsum, qv, coef, status, st)))
-    return rc;
-  return sp_launch_assemble(S, K, M, L.Kp, 1, theta, t_dev, stars_dev, cp, tab_dev,
-                            meanvar_dev, h->d_xp, temporal, rawp, normalized, qv, coef,
-                            diag_dev, 1, flux_dev, sys, L.Kp, (long)L.Kp * L.Kp, st);
+  return sp_launch_direct_form(C, V.theta(), rawp, condmean, V.rowsum(), V.qv(), V.coef(), V.status(), system_out(V));
 }
 
-// stage C: reduction of one group's factored systems
-int lnlike_finish(const Layout &L, void *ws, int K, int M, double *lnlike_dev,
-                  uint32_t *status_dev, hipStream_t st, const sp_star *stars_dev, bool deferred, bool dvec) {
-  const int S = L.S;
-  int rc;
-  uint32_t *status = at<uint32_t>(ws, L.status);
-  if ((rc = sp_launch_lnlike_reduce(at<double>(ws, L.sys), S, K, M, L.Kp,
-                                    at<int32_t>(ws, L.info), lnlike_dev, status, st,
-                                    status_dev, stars_dev,
-                                    deferred ? at<double>(ws, L.coef) : nullptr,
-                                    deferred ? at<double>(ws, L.rscal) : nullptr, dvec ? 1 : 0)))
-    return rc;
-  return SP_OK;
+// the reduction of one group's factored systems: in the tail of the last panel launch (sp_chol_group::red) or by
+// sp_launch_lnlike_reduce.  deferred: the normalisation's rows ride below the residuals
+SpReduceArgs reduce_args(const SpProblem &P, const SpViews &V, bool deferred, double *lnlike, uint32_t *status_out) {
+  return SpReduceArgs{lnlike, V.status(), status_out, P.stars, deferred ? (const void *)V.coef() : nullptr, V.rscal(),
+                      P.diag ? 1 : 0, P.K, P.M, P.K + P.M + (deferred ? (P.diag ? 2 : 1) : 0)};
 }
 
 }  // namespace
-
-// the two conditional-branch steps the gradient's driver shares with this one (sp_grad_cond.hip)
-int sp_launch_design(sp_handle *h, const Layout &L, void *ws, const sp_star *stars, const double *rta1, double *A_out,
-                     hipStream_t st, int Kr) {
-  return build_design(h, L, ws, stars, rta1, A_out, st, Kr);
-}
-int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
-                        const int32_t *sel, int nsets) {
-  hipLaunchKernelGGL(cond_mean_kernel, dim3(S), dim3(256), 0, st, N, rows, A, mu, mean, sel, nsets);
-  SP_LAUNCH_CHECK();
-  return SP_OK;
-}
 
 extern "C" {
 
@@ -394,20 +358,16 @@ int sp_cov_marginal_batched(sp_handle *h, int S, int K, const double *t_dev,
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, L.condmean + 256, &ws);
   if (rc) return rc;
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
-  double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, covpts, tab_dev,
-                               meanvar_dev, h->d_xp, temporal, nullptr, rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars_dev, meanvar_dev, nullptr, normalized,
-                                norm_order, INFINITY, rowsum, qv, coef, nullptr, st)))
-    return rc;
-  if ((rc = sp_launch_assemble(S, K, 0, K, 0, theta, t_dev, stars_dev, covpts,
-                               tab_dev, meanvar_dev, h->d_xp, temporal, nullptr,
-                               normalized, qv, coef, nullptr, 0, nullptr, cov_dev,
-                               ldc, stridec, st)))
+  const SpViews V{L, ws};
+  SpProblem P;
+  P.S = S, P.K = K, P.t = t_dev, P.stars = stars_dev, P.st = st;
+  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h->d_xp;
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order;
+  P.zmax = INFINITY;   // (no star is rejected here)
+  double *coef = V.coef();
+  if ((rc = sp_launch_theta(P, V.theta()))) return rc;
+  if ((rc = sp_launch_direct_form(P, V.theta(), nullptr, nullptr, V.rowsum(), V.qv(), coef, nullptr,
+                                  SpAsmOut{cov_dev, ldc, stridec, 0, K, 0})))
     return rc;
   if (z_dev) {
     hipLaunchKernelGGL(get_z_kernel, dim3((S + 255) / 256), dim3(256), 0, st, S, coef,
@@ -429,9 +389,11 @@ int sp_design_matrix(sp_handle *h, int S, int K, const double *t_dev,
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, L.raw, &ws);  // up to and including B1
   if (rc) return rc;
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, at<double>(ws, L.theta), st)))
-    return rc;
-  return build_design(h, L, ws, stars_dev, rta1_dev, A_dev, st, K);
+  const SpViews V{L, ws};
+  SpProblem P;
+  P.S = S, P.K = K, P.t = t_dev, P.stars = stars_dev, P.st = st;
+  if ((rc = sp_launch_theta(P, V.theta()))) return rc;
+  return sp_launch_design(h, V, stars_dev, rta1_dev, A_dev, st, K);
 }
 
 int sp_cov_conditional_batched(sp_handle *h, int S, int K, const double *t_dev,
@@ -450,23 +412,18 @@ int sp_cov_conditional_batched(sp_handle *h, int S, int K, const double *t_dev,
   void *ws = nullptr;
   int rc = sp_ensure_scratch(h->big, L.total, &ws);
   if (rc) return rc;
-  double *theta = at<double>(ws, L.theta), *rowsum = at<double>(ws, L.rowsum);
-  double *qv = at<double>(ws, L.qv), *coef = at<double>(ws, L.coef);
-  double *raw = at<double>(ws, L.raw), *cm = at<double>(ws, L.condmean);
-  if ((rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st))) return rc;
-  if ((rc = build_design(h, L, ws, stars_dev, rta1_dev, at<double>(ws, L.A), st, K)))
-    return rc;
-  if ((rc = build_conditional_raw(CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1}, L, ws, st))) return rc;
-  if (normalized)
-    if ((rc = sp_launch_rowsum(S, K, theta, t_dev, stars_dev, 1, nullptr, nullptr,
-                               nullptr, temporal, raw, rowsum, st)))
-      return rc;
-  if ((rc = sp_launch_norm_coef(S, K, stars_dev, nullptr, cm, normalized, norm_order,
-                                INFINITY, rowsum, qv, coef, nullptr, st)))
-    return rc;
-  if ((rc = sp_launch_assemble(S, K, 0, K, 0, theta, t_dev, stars_dev, 1, nullptr,
-                               nullptr, nullptr, temporal, raw, normalized, qv, coef,
-                               nullptr, 0, nullptr, cov_dev, ldc, stridec, st)))
+  const SpViews V{L, ws};
+  SpProblem P;
+  P.S = S, P.K = K, P.t = t_dev, P.stars = stars_dev, P.st = st;
+  P.covpts = 1;        // (no table behind a raw covariance: tab, meanvar, xp stay null)
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order;
+  P.zmax = INFINITY;   // (no star is rejected here)
+  double *coef = V.coef();
+  if ((rc = sp_launch_theta(P, V.theta()))) return rc;
+  if ((rc = sp_launch_design(h, V, stars_dev, rta1_dev, V.A(), st, K))) return rc;
+  if ((rc = build_conditional_raw(CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1}, V, st))) return rc;
+  if ((rc = sp_launch_direct_form(P, V.theta(), V.raw(), V.condmean(), V.rowsum(), V.qv(), coef, nullptr,
+                                  SpAsmOut{cov_dev, ldc, stridec, 0, K, 0})))
     return rc;
   if (mean_dev) {
     hipLaunchKernelGGL(get_gpmean_kernel, dim3((S + 255) / 256), dim3(256), 0, st, S,
@@ -486,18 +443,14 @@ long sp_lnlike_workspace_bytes(sp_handle *h, int S, int K, int M) {
   return (long)make_layout(h, S, K, M, true).total;
 }
 
-// sets != null: the conditional branch with a moment set per system (sp_lnlike_ensemble_sets); the handle's own
-// moments are then neither needed nor read
-static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const double *t_dev,
-                                  const double *flux_dev, const double *diag_dev,
-                                  const sp_star *stars_dev, int conditional, int covpts,
-                                  const double *tab_dev, const double *meanvar_dev,
-                                  const double *rta1_dev, int temporal, int normalized,
-                                  int norm_order, double zmax, void *workspace_dev,
-                                  double *lnlike_dev, uint32_t *status_dev, void *stream, const CondSets *sets) {
+// P as the entry point filled it, before any check; sets != null: the conditional branch with a moment set per system
+// (sp_lnlike_ensemble_sets); the handle's own moments are then neither needed nor read
+static int lnlike_ensemble_driver(sp_handle *h, const SpProblem &P, int conditional, const double *rta1_dev,
+                                  void *workspace_dev, double *lnlike_dev, uint32_t *status_dev, const CondSets *sets) {
+  const int S = P.S, K = P.K, M = P.M;
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !t_dev || !flux_dev || !stars_dev || !workspace_dev || !lnlike_dev ||
-      S < 0 || K < 1 || M < 1 || norm_order < 0 || norm_order > SP_NORM_MAXORDER)
+  if (!h || !P.t || !P.flux || !P.stars || !workspace_dev || !lnlike_dev ||
+      S < 0 || K < 1 || M < 1 || P.order < 0 || P.order > SP_NORM_MAXORDER)
     return SP_ERR_INVALID;
   if (conditional) {
     if (!rta1_dev) return SP_ERR_INVALID;
@@ -507,16 +460,16 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
       return SP_ERR_STATE;
     }
   } else {
-    if (!tab_dev || !meanvar_dev || covpts < 1) return SP_ERR_INVALID;
-    if (h->xp_covpts != covpts) return SP_ERR_STATE;
+    if (!P.tab || !P.meanvar || P.covpts < 1) return SP_ERR_INVALID;
+    if (h->xp_covpts != P.covpts) return SP_ERR_STATE;
   }
   if (S == 0) return SP_OK;
-  hipStream_t st = (hipStream_t)stream;
-  Layout L = make_layout(h, S, K, M, true);
-  void *ws = workspace_dev;
+  hipStream_t st = P.st;
+  const SpViews V{make_layout(h, S, K, M, true), workspace_dev};
   // Star groups on concurrent streams (sp_ensemble_shape).  No event traffic inside the loop: one fork
   // and one join per call.
-  const EnsembleShape shape = sp_ensemble_shape(h->tune, h->ydeg, S, K, M, covpts, conditional, temporal, normalized);
+  const EnsembleShape shape =
+      sp_ensemble_shape(h->tune, h->ydeg, S, K, M, P.covpts, conditional, P.temporal, P.normalized);
   const int G = shape.G, lazy_nfull = shape.lazy_nfull;
   if (G > 1) {
     while ((int)h->gstream.size() < G - 1) {
@@ -530,55 +483,43 @@ static int lnlike_ensemble_driver(sp_handle *h, int S, int K, int M, const doubl
     if (!h->gfork) SP_HIP(hipEventCreateWithFlags(&h->gfork, hipEventDisableTiming));
     SP_HIP(hipEventRecord(h->gfork, st));
   }
-  const bool fused_reduce = shape.fused_reduce != 0;
-  std::vector<Layout> LG(G, L);
+  const bool fused_reduce = shape.fused_reduce != 0, deferred = P.normalized && h->tune.defer_norm;
+  // per group: its stars' problem on its stream, its view of the workspace, what the reduction takes
+  std::vector<SpProblem> PG(G);
+  std::vector<SpViews> VG(G);
+  std::vector<SpReduceArgs> RG(G);
   std::vector<sp_chol_group> CG(G);
-  std::vector<int> first(G);
   for (int g = 0; g < G; ++g) {
     const int s0 = (int)((long)S * g / G), s1 = (int)((long)S * (g + 1) / G);
-    first[g] = s0;
-    LG[g] = make_layout(h, S, K, M, true, false, s0);
-    LG[g].S = s1 - s0;
-    hipStream_t sg = g == 0 ? st : h->gstream[g - 1];
-    if (g > 0) SP_HIP(hipStreamWaitEvent(sg, h->gfork, 0));
-    CG[g] = sp_chol_group{at<double>(ws, LG[g].sys), at<int32_t>(ws, LG[g].info),
-                          at<double>(ws, LG[g].invL), s1 - s0, sg, LazyCov{}, SpReduceArgs{}};
+    PG[g] = P.slice(s0, s1);
+    PG[g].st = g == 0 ? st : h->gstream[g - 1];
+    VG[g] = SpViews{make_layout(h, S, K, M, true, false, s0), workspace_dev};
+    VG[g].L.S = s1 - s0;
+    if (g > 0) SP_HIP(hipStreamWaitEvent(PG[g].st, h->gfork, 0));
+    RG[g] = reduce_args(PG[g], VG[g], deferred, lnlike_dev + s0, status_dev ? status_dev + s0 : nullptr);
     // the reduction rides in the tail of the last panel launch when the system's shape allows
-    if (fused_reduce)
-      CG[g].red = SpReduceArgs{lnlike_dev + s0, at<uint32_t>(ws, LG[g].status),
-                               status_dev ? status_dev + s0 : nullptr, stars_dev + s0,
-                               (normalized && h->tune.defer_norm) ? (const void *)at<double>(ws, LG[g].coef) : nullptr,
-                               at<double>(ws, LG[g].rscal), diag_dev ? 1 : 0, K, M,
-                               K + M + ((normalized && h->tune.defer_norm) ? (diag_dev ? 2 : 1) : 0)};
+    CG[g] = sp_chol_group{VG[g].sys(), VG[g].info(), VG[g].invL(), s1 - s0, PG[g].st, LazyCov{},
+                          fused_reduce ? RG[g] : SpReduceArgs{}};
   }
   // tiles formed at first touch (LazyCov, sp_cov.h)
   if (lazy_nfull)
-    CG[0].lazy = LazyCov{at<double>(ws, L.theta), t_dev, stars_dev, at<double>(ws, L.A), K, covpts,
-                         temporal, lazy_nfull, 0, 0};
+    CG[0].lazy = LazyCov{V.theta(), P.t, P.stars, V.A(), K, P.covpts, P.temporal, lazy_nfull, 0, 0};
   for (int g = 0; g < G; ++g) {
-    const int s0 = first[g];
-    CondSets gs{};
-    if (sets) gs = CondSets{sets->mu, sets->cov, sets->sel + s0, sets->nsets};
-    int rc = lnlike_assemble(h, LG[g], ws, K, M, t_dev + (size_t)s0 * K,
-                             flux_dev + (size_t)s0 * M * K,
-                             diag_dev ? diag_dev + (size_t)s0 * K : nullptr, stars_dev + s0,
-                             conditional, covpts, tab_dev, meanvar_dev, rta1_dev, temporal,
-                             normalized, norm_order, zmax, CG[g].st, lazy_nfull, sets ? &gs : nullptr);
+    const int s0 = (int)((long)S * g / G);
+    const CondSets gs = sets ? CondSets{sets->mu, sets->cov, sets->sel + s0, sets->nsets}
+                             : CondSets{h->d_mean_ylm, h->d_cov_ylm, nullptr, 1};
+    int rc = lnlike_assemble(h, PG[g], VG[g], conditional, rta1_dev, lazy_nfull, gs);
     if (rc) return rc;
   }
   {
-    int rc = sp_launch_cholesky_groups(h, G, CG.data(), K, L.Kp);
+    int rc = sp_launch_cholesky_groups(h, G, CG.data(), K, V.L.Kp);
     if (rc) return rc;
   }
   for (int g = 0; g < G; ++g) {
-    const int s0 = first[g];
-    int rc = fused_reduce ? SP_OK
-                          : lnlike_finish(LG[g], ws, K, M, lnlike_dev + s0,
-                                          status_dev ? status_dev + s0 : nullptr, CG[g].st, stars_dev + s0,
-                                          normalized && h->tune.defer_norm, diag_dev != nullptr);
-    if (rc) return rc;
+    if (!fused_reduce)
+      if (int rc = sp_launch_lnlike_reduce(VG[g].sys(), PG[g].S, V.L.Kp, VG[g].info(), RG[g], PG[g].st)) return rc;
     if (g > 0) {
-      SP_HIP(hipEventRecord(h->gdone[g - 1], CG[g].st));
+      SP_HIP(hipEventRecord(h->gdone[g - 1], PG[g].st));
       SP_HIP(hipStreamWaitEvent(st, h->gdone[g - 1], 0));
     }
   }
@@ -592,9 +533,11 @@ int sp_lnlike_ensemble(sp_handle *h, int S, int K, int M, const double *t_dev,
                        const double *rta1_dev, int temporal, int normalized,
                        int norm_order, double zmax, void *workspace_dev,
                        double *lnlike_dev, uint32_t *status_dev, void *stream) {
-  return lnlike_ensemble_driver(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, conditional, covpts, tab_dev,
-                                meanvar_dev, rta1_dev, temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev,
-                                status_dev, stream, nullptr);
+  SpProblem P;
+  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h ? h->d_xp : nullptr;
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  return lnlike_ensemble_driver(h, P, conditional, rta1_dev, workspace_dev, lnlike_dev, status_dev, nullptr);
 }
 
 // sp_lnlike_ensemble's conditional branch with one moment set per system: system s takes (mean_ylm[select[s]],
@@ -612,9 +555,11 @@ int sp_lnlike_ensemble_sets(sp_handle *h, int S, int K, int M, const double *t_d
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !mean_ylm_dev || !cov_ylm_dev || !select_dev || B < 1) return SP_ERR_INVALID;
   const CondSets sets{mean_ylm_dev, cov_ylm_dev, select_dev, B};
-  return lnlike_ensemble_driver(h, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, 1, 1, nullptr, nullptr, rta1_dev,
-                                temporal, normalized, norm_order, zmax, workspace_dev, lnlike_dev, status_dev, stream,
-                                &sets);
+  SpProblem P;
+  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = 1, P.xp = h->d_xp;   // (the conditional branch: no table)
+  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  return lnlike_ensemble_driver(h, P, 1, rta1_dev, workspace_dev, lnlike_dev, status_dev, &sets);
 }
 
 // The per-sample call on planned data (sp_plan.hip): sp_lnlike_ensemble's marginal, normalised branch with the
@@ -639,38 +584,33 @@ int sp_lnlike_ensemble_planned(sp_handle *h, const sp_plan *plan, const double *
   } else if (t_dev != plan->t || flux_dev != plan->flux || diag_dev != plan->diag) {
     return SP_ERR_INVALID;
   }
-  const int S = plan->S, K = plan->K, M = plan->M, covpts = plan->covpts, temporal = plan->temporal;
-  if (h->xp_covpts != covpts) return SP_ERR_STATE;
-  hipStream_t st = (hipStream_t)stream;
+  if (h->xp_covpts != plan->covpts) return SP_ERR_STATE;
+  SpProblem P;
+  P.S = plan->S, P.K = plan->K, P.M = plan->M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
+  P.covpts = plan->covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h->d_xp;
+  P.temporal = plan->temporal, P.normalized = 1, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  const int K = P.K;
   // which kernels form which tiles: sp_planned_shape (sp_tuning.cpp)
-  const PlannedShape ps = sp_planned_shape(h->tune, sp_proc_tuning(), h->ydeg, K, M, covpts, temporal, diag_dev != nullptr);
-  if (ps.small_k)
-    return sp_launch_small_lnlike(S, K, M, plan->dev, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal, flux_dev,
-                                  diag_dev, norm_order, zmax, lnlike_dev, status_dev, st);
-  Layout L = make_layout(h, S, K, M, true);
-  void *ws = workspace_dev;
+  const PlannedShape ps =
+      sp_planned_shape(h->tune, sp_proc_tuning(), h->ydeg, K, P.M, P.covpts, P.temporal, diag_dev != nullptr);
+  if (ps.small_k) return sp_launch_small_lnlike(P, plan->dev, lnlike_dev, status_dev);
+  const SpViews V{make_layout(h, P.S, K, P.M, true), workspace_dev};
+  const int Kp = V.L.Kp;
   // (the stars' packed tables for the kernels that form tiles at first touch in the design-matrix region, the riding
   //  rows as the assembly would write them, [S][nrid][K], in the second design-matrix buffer)
-  double *ptab = ps.use_ptab ? at<double>(ws, L.A) : nullptr;
-  double *rid = ps.riding ? at<double>(ws, L.B1) : nullptr;
-  int rc = sp_launch_assemble_planned(S, K, M, L.Kp, plan->dev, t_dev, stars_dev, covpts, tab_dev, meanvar_dev, temporal,
-                                      flux_dev, diag_dev, at<double>(ws, L.sys), ps.lazy_nfull, ps.ncolw, norm_order, zmax,
-                                      at<double>(ws, L.coef), at<double>(ws, L.rscal), ptab, at<int32_t>(ws, L.info),
-                                      at<uint32_t>(ws, L.status), st, at<double>(ws, L.invL), sp_lt_stride(L.Kp), ps.fuse0,
-                                      rid, ps.dfrom);
+  double *ptab = ps.use_ptab ? V.A() : nullptr;
+  double *rid = ps.riding ? V.B1() : nullptr;
+  int rc = sp_launch_assemble_planned(P, plan->dev, ps, V, ptab, rid);
   if (rc) return rc;
-  const bool fused_reduce = sp_panel_fuses_reduce(h->tune, K, L.Kp);
-  sp_chol_group G{at<double>(ws, L.sys), at<int32_t>(ws, L.info), at<double>(ws, L.invL), S, st, LazyCov{}, SpReduceArgs{}};
-  if (fused_reduce)
-    G.red = SpReduceArgs{lnlike_dev, at<uint32_t>(ws, L.status), status_dev, stars_dev, (const void *)at<double>(ws, L.coef),
-                         at<double>(ws, L.rscal), diag_dev ? 1 : 0, K, M, K + M + (diag_dev ? 2 : 1)};
+  const bool fused_reduce = sp_panel_fuses_reduce(h->tune, K, Kp);
+  const SpReduceArgs red = reduce_args(P, V, true, lnlike_dev, status_dev);
+  sp_chol_group G{V.sys(), V.info(), V.invL(), P.S, P.st, LazyCov{}, fused_reduce ? red : SpReduceArgs{}};
   G.block0_done = ps.fuse0 != 0;
   if (ps.lazy_nfull)
-    G.lazy = LazyCov{plan->dev.theta, t_dev, stars_dev, ptab, K, covpts, temporal, ps.lazy_nfull, 0, 0, ps.no_panels ? 0 : 1,
-                     ps.no_panels, rid, ps.riding ? ps.nrid : 0, ps.dlazy, plan->dev.inorder};
-  if ((rc = sp_launch_cholesky_groups(h, 1, &G, K, L.Kp))) return rc;
-  if (!fused_reduce) return lnlike_finish(L, ws, K, M, lnlike_dev, status_dev, st, stars_dev, true, diag_dev != nullptr);
-  return SP_OK;
+    G.lazy = LazyCov{plan->dev.theta, t_dev, stars_dev, ptab, K, P.covpts, P.temporal, ps.lazy_nfull, 0, 0,
+                     ps.no_panels ? 0 : 1, ps.no_panels, rid, ps.riding ? ps.nrid : 0, ps.dlazy, plan->dev.inorder};
+  if ((rc = sp_launch_cholesky_groups(h, 1, &G, K, Kp))) return rc;
+  return fused_reduce ? SP_OK : sp_launch_lnlike_reduce(V.sys(), P.S, Kp, V.info(), red, P.st);
 }
 
 int sp_cholesky_lnlike_batched(sp_handle *h, int S, int K, int M,
@@ -694,7 +634,8 @@ int sp_cholesky_lnlike_batched(sp_handle *h, int S, int K, int M,
   if ((rc = sp_launch_pad_in(cov_dev, K, K, (long)K * K, sys, L.Kp, M, resid_dev, S, st)))
     return rc;
   if ((rc = sp_launch_cholesky_systems(h, sys, S, K, L.Kp, info, at<double>(ws, L.invL), st))) return rc;
-  if ((rc = sp_launch_lnlike_reduce(sys, S, K, M, L.Kp, info, lnlike_dev, status, st)))
+  if ((rc = sp_launch_lnlike_reduce(sys, S, L.Kp, info,
+                                    SpReduceArgs{lnlike_dev, status, nullptr, nullptr, nullptr, nullptr, 0, K, M, 0}, st)))
     return rc;
   if (status_dev)
     SP_HIP(hipMemcpyAsync(status_dev, status, sizeof(uint32_t) * S,

@@ -172,7 +172,9 @@ int sp_plan_data(sp_handle *h, int S, int K, int M, const double *t_dev, const d
     delete p;
     return rc;
   };
-  int rc = sp_launch_theta(S, K, t_dev, stars_dev, theta, st);
+  SpProblem P;
+  P.S = S, P.K = K, P.t = t_dev, P.stars = stars_dev, P.st = st;
+  int rc = sp_launch_theta(P, theta);
   if (rc) return fail(rc);
   hipLaunchKernelGGL(plan_scalars_kernel, dim3(S), dim3(256), 0, st, K, M, flux_dev, diag_dev, stars_dev, t_dev, sflux,
                      sdv, key, inorder);

@@ -476,11 +476,11 @@ static size_t assemble_planned_lds(int Kp, int covpts, int temporal, int lds_pha
   return sizeof(double) * ((fuse0 && own < SP_DIAG_LDS_DOUBLES) ? (size_t)SP_DIAG_LDS_DOUBLES : own);
 }
 
-int sp_launch_assemble_planned(int S, int K, int M, int Kp, const PlanDev &plan, const double *t,
-                               const sp_star *stars, int covpts, const double *tab, const double *meanvar,
-                               int temporal, const double *flux, const double *diag, double *sys, int nfull,
-                               int ncolw, int order, double zmax, void *coef, double *rscal, double *ptab, int32_t *info,
-                               uint32_t *status, hipStream_t st, double *img, long lts, int fuse0, double *rid, int dfrom) {
+int sp_launch_assemble_planned(const SpProblem &P, const PlanDev &plan, const PlannedShape &ps, const SpViews &V,
+                               double *ptab, double *rid) {
+  const int S = P.S, K = P.K, Kp = V.L.Kp, covpts = P.covpts, temporal = P.temporal;
+  const int nfull = ps.lazy_nfull, ncolw = ps.ncolw, fuse0 = ps.fuse0, dfrom = ps.dfrom;
+  double *coef = V.coef(), *rscal = V.rscal(), *img = V.invL();
   const int ntr = Kp / 64, ntiles = ntr * (ntr + 1) / 2;
   if (ntiles > 65535 || !coef || !rscal || (fuse0 && (!img || K < 64))) return SP_ERR_INVALID;
   int lds_phases = 1;
@@ -513,9 +513,10 @@ int sp_launch_assemble_planned(int S, int K, int M, int Kp, const PlanDev &plan,
 #define SP_ASMP(TK)                                                                                       \
   do {                                                                                                    \
     allow_big_lds(assemble_planned_kernel<TK>);                                                           \
-    hipLaunchKernelGGL((assemble_planned_kernel<TK>), grid, dim3(256), lds, st, K, M, Kp, plan, t, stars, \
-                       covpts, tab, meanvar, flux, diag, sys, (long)Kp, (long)Kp * Kp, ntr, nfull, ncolw, order, \
-                       zmax, (Coef *)coef, rscal, ptab, info, status, lds_phases, img, lts, fuse0, S, nchunk, rid, dfrom, chunks); \
+    hipLaunchKernelGGL((assemble_planned_kernel<TK>), grid, dim3(256), lds, P.st, K, P.M, Kp, plan, P.t, P.stars,  \
+                       covpts, P.tab, P.meanvar, P.flux, P.diag, V.sys(), (long)Kp, (long)Kp * Kp, ntr, nfull, ncolw, \
+                       P.order, P.zmax, (Coef *)coef, rscal, ptab, V.info(), V.status(), lds_phases, img,          \
+                       sp_lt_stride(Kp), fuse0, S, nchunk, rid, dfrom, chunks);                                   \
   } while (0)
   if (temporal == SP_TEMPORAL_NONE) SP_ASMP(SP_TEMPORAL_NONE);
   else if (temporal == SP_TEMPORAL_MATERN32) SP_ASMP(SP_TEMPORAL_MATERN32);

@@ -343,8 +343,13 @@ int assemble_chunk(sp_handle *h, const PredictLayout &L, void *ws, const Predict
   if (!in.conditional) {
     double *th_t = at<double>(ws, L.th_t), *th_s = same ? th_t : at<double>(ws, L.th_s);
     double *ptab = at<double>(ws, L.ptab);
-    if ((rc = sp_launch_theta(nb, K, t, stars, th_t, st, nullptr, nullptr, in.tab, in.covpts, ptab))) return rc;
-    if (!same && (rc = sp_launch_theta(nb, Ks, ts, stars, th_s, st))) return rc;
+    SpProblem P;   // the chunk's stars at the observed times, with their tables packed into ptab ...
+    P.S = nb, P.K = K, P.t = t, P.stars = stars, P.covpts = in.covpts, P.tab = in.tab, P.st = st;
+    if ((rc = sp_launch_theta(P, th_t, nullptr, nullptr, ptab))) return rc;
+    SpProblem Ps = P;   // ... and at the sample times
+    Ps.K = Ks;
+    Ps.t = ts;
+    if (!same && (rc = sp_launch_theta(Ps, th_s))) return rc;
     hipLaunchKernelGGL(predict_prior_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, nb, stars, in.meanvar, ptab,
                        L.np, mean, at<double>(ws, L.kss0));
     SP_LAUNCH_CHECK();

@@ -324,9 +324,9 @@ __global__ __launch_bounds__(256, NB == 2 ? 3 : 4) void small_lnlike_kernel(
 
 }  // namespace
 
-int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const double *t, const sp_star *stars, int covpts,
-                           const double *tab, const double *meanvar, int temporal, const double *flux, const double *diag,
-                           int order, double zmax, double *lnlike, uint32_t *status_out, hipStream_t st) {
+int sp_launch_small_lnlike(const SpProblem &P, const PlanDev &plan, double *lnlike, uint32_t *status_out) {
+  const int K = P.K, M = P.M, covpts = P.covpts, temporal = P.temporal;
+  const double *diag = P.diag;
   if (!sp_small_k_serves(K, M, covpts, diag != nullptr)) return SP_ERR_INVALID;
   const int NB = K > 64 ? 2 : 1, KC = 64 * NB, np = covpts + 4, nr = M + (diag ? 2 : 1);
   // (K <= 64: the table lies in the pivot block's place -- no region of its own)
@@ -337,8 +337,8 @@ int sp_launch_small_lnlike(int S, int K, int M, const PlanDev &plan, const doubl
   do {                                                                                                            \
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(small_lnlike_kernel<NBV, TKV>),                      \
                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);                            \
-    hipLaunchKernelGGL((small_lnlike_kernel<NBV, TKV>), dim3(S), dim3(256), lds, st, K, M, plan, t, stars, covpts, tab, \
-                       meanvar, flux, diag, order, zmax, lnlike, status_out, regionB);                            \
+    hipLaunchKernelGGL((small_lnlike_kernel<NBV, TKV>), dim3(P.S), dim3(256), lds, P.st, K, M, plan, P.t, P.stars, covpts, \
+                       P.tab, P.meanvar, P.flux, diag, P.order, P.zmax, lnlike, status_out, regionB);             \
   } while (0)
 #define SP_SMALL_TK(NBV)                                                                \
   do {                                                                                  \
