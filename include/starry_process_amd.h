@@ -561,6 +561,40 @@ int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, c
                        double zmax, double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
                        size_t workspace_bytes, void *stream);
 
+/* ---- Fisher information of an ensemble on the conditional branch, inclinations and periods included ------------
+ * No flux data: star s at its own inclination (sp_star.inc, radians), with C_s the covariance and mean
+ *   Sigma_flux = (A Sigma_y A^T) o T,  mean = (A mu_y)[0],  C = c1 Sigma_flux + s1 p p^T - s2 q q^T + D + b 1 1^T
+ * that sp_lnlike_grad_conditional factors, at the handle's current moments (SP_ERR_STATE without them), and m_s the
+ * mean of its flux GP (the flux mean for an unnormalised process, 0 for a normalised one),
+ *   F_s[i, j] = 1/2 tr(C^-1 d_i C  C^-1 d_j C) + (d_i m)(d_j m) 1^T C^-1 1        -> fisher_dev [S, P, P].
+ * The parameters of star s, in the order of F_s: Ph <= 5 shared hyperparameters (Ph may be 0), whose moment tangents
+ * the caller supplies,
+ *   dmu_dev [Ph, N]       d mu_y / d theta_k
+ *   dsig_dev [Ph, N, N]   d Sigma_y / d theta_k (symmetric)
+ * then the star's own inclination (star_mask bit 0; per RADIAN) and period (bit 1; the integer part of t / p is data,
+ * as in the gradient): P = Ph + the bits set, 1 .. 7.  D, b and the temporal factor T do not depend on any parameter
+ * (tau is held fixed).  The sweep forms the design-matrix tangents d A / d inc and d A / d p on the matrix cores, one
+ * Kr x Kr product per parameter ((A dSigma_k) A^T, or Z = dA (A Sigma_y)^T with d Sigma_flux = (Z + Z^T) o T), the
+ * normalisation by the product rule (sp.py:705-727), G_i = C^-1 d_i C and the pair traces as sp_fisher_marginal does: no
+ * floating-point atomics, the same bits run after run, F_s exactly symmetric.  dcov_dev (may be NULL): [S, P, K, K], the
+ * tangents d_i C themselves, exactly symmetric.  status_dev (may be NULL) [S].
+ *   star with z > zmax: zeros, SP_STAR_ZMAX (whether or not its covariance factors);  covariance that does not factor:
+ *   NaN, SP_STAR_NOT_PD;  ragged star (0 < nobs < K): NaN, SP_STAR_NAN (also set when a NaN reaches F_s otherwise).
+ * No star affects another.  The stars are worked through in groups of as many as workspace_bytes holds
+ * (sp_fisher_conditional_workspace_bytes(h, S', K, P) for S' stars resident at once: the inverse's workspace, the inverse,
+ * the raw covariance, three roundup(K, 64) x N matrices and 2 P roundup(K, 64)^2 doubles per star; 0 for a null handle,
+ * S' < 1, K < 2 or P outside 1 .. 7); a star's bits do not depend on the grouping.  A workspace too small for one star,
+ * a null required pointer (dmu_dev, dsig_dev: required when Ph > 0), K < 2, Ph outside 0 .. 5, a star_mask beyond its
+ * two bits, P = 0 or a bad `temporal`: SP_ERR_INVALID, nothing launched.  A host-only handle: SP_ERR_NO_DEVICE.  S = 0:
+ * SP_OK, nothing touched.  All launches go to `stream`; nothing is synchronised.                                     */
+size_t sp_fisher_conditional_workspace_bytes(sp_handle *h, int S, int K, int P);
+int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask /* bit 0: i, bit 1: p */,
+                          const double *t_dev, const double *diag_dev, const sp_star *stars_dev,
+                          const double *rta1_dev, const double *dmu_dev /* [Ph, N] */,
+                          const double *dsig_dev /* [Ph, N, N] */, int temporal, int normalized, int norm_order,
+                          double zmax, double *fisher_dev /* [S, P, P] */, double *dcov_dev /* NULL or [S, P, K, K] */,
+                          uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

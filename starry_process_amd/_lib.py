@@ -97,6 +97,9 @@ PROTOTYPES = {
     "sp_fisher_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_fisher_marginal": (_I, [_V, _I, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                 ctypes.c_size_t, _V]),
+    "sp_fisher_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I]),
+    "sp_fisher_conditional": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
+                                   ctypes.c_size_t, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_predict_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),

@@ -27,7 +27,8 @@
 
 namespace {
 
-constexpr int FP_MAX = 6;      // parameters per call (r, a, b, c, n, dr)
+constexpr int FP_MAX = 6;      // parameters per call (r, a, b, c, n, dr); the kernels shared with the conditional
+                               // branch's sweep (sp_fisher_cond.hip) hold up to SP_FISHER_PMAX
 
 // segment of a lag (sp_lag_segment, sp_sweep.h: the index and x0 of SplineGen and of the gradient's scatter) and the four
 // cubic weights of the table entries yp[idx .. idx + 3] at the position inside it, value = sum_m yp[idx + m] w[m]
@@ -105,9 +106,9 @@ __global__ __launch_bounds__(256) void fisher_rowsum_kernel(
 //   dmu = dmean,  dm = mean(dSigma),  dq = dSigma 1 / (K m) - q dm / m,  dz = dm / mu^2 - 2 m dmu / mu^3,
 //   dalpha = alpha'(z) dz,  dbeta = beta'(z) dz,
 //   dc1 = dalpha / mu^2 - 2 alpha dmu / mu^3,  ds1 = dz (alpha + beta) + z (dalpha + dbeta),  ds2 = dz alpha + z dalpha.
-enum { FS_DC1 = 0, FS_DS1 = 1, FS_DS2 = 2, FS_N = 4 };
+// dmean [P][ntab]: the tangent of the flux mean, of the star's table, or (per_star, ntab = S) of the star itself.
 __global__ __launch_bounds__(256) void fisher_coef_kernel(
-    int K, int P, int ntab, const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef,
+    int K, int P, int ntab, int per_star, const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef,
     const double *__restrict__ qv, const double *__restrict__ dmean, int order, double *__restrict__ drow,
     double *__restrict__ dsc) {
   __shared__ double red[4];
@@ -130,14 +131,14 @@ __global__ __launch_bounds__(256) void fisher_coef_kernel(
     double part = 0.0;
     for (int i = tid; i < K; i += 256) part += row[i];
     const double dm = sp_block_sum_256(part, red) / (Kd * Kd);
-    const double dmu = dmean[(size_t)p * ntab + stars[s].table];
+    const double dmu = dmean[(size_t)p * ntab + (per_star ? s : stars[s].table)];
     const double dz = dm / (mu * mu) - 2.0 * m * dmu / (mu * mu * mu);
     const double da = dan * dz, db = dbn * dz;
     if (tid == 0) {
-      double *o = dsc + ((size_t)s * P + p) * FS_N;
-      o[FS_DC1] = da / (mu * mu) - 2.0 * an * dmu / (mu * mu * mu);
-      o[FS_DS1] = dz * (an + bn) + z * (da + db);
-      o[FS_DS2] = dz * an + z * da;
+      double *o = dsc + ((size_t)s * P + p) * SP_FS_N;
+      o[SP_FS_DC1] = da / (mu * mu) - 2.0 * an * dmu / (mu * mu * mu);
+      o[SP_FS_DS1] = dz * (an + bn) + z * (da + db);
+      o[SP_FS_DS2] = dz * an + z * da;
       o[3] = 0.0;
     }
     // (each thread rewrites the entries it read above)
@@ -209,12 +210,12 @@ __global__ __launch_bounds__(256) void fisher_tangent_kernel(
         const double *y = s_tab + (size_t)(p + (normalized ? 1 : 0)) * np + idx;
         double v = (((y[0] * w[0] + y[1] * w[1]) + y[2] * w[2]) + y[3] * w[3]) * T;
         if (normalized) {
-          const double *d = dsc + ((size_t)s * P + p) * FS_N;
+          const double *d = dsc + ((size_t)s * P + p) * SP_FS_N;
           const double dqi = s_dqi[p * 64 + li], dqj = s_dqj[p * 64 + lj];
           // d(p p^T) = -(dq_a p_b + p_a dq_b),  d(q q^T) = dq_a q_b + q_a dq_b: each a sum of two products, the same
           // two for (a, b) and (b, a)
           const double dpp = -(dqi * (1.0 - qj) + (1.0 - qi) * dqj), dqq = dqi * qj + qi * dqj;
-          v = (d[FS_DC1] * sig + c.c1 * v) + ((d[FS_DS1] * pp + s1 * dpp) - (d[FS_DS2] * qq + s2 * dqq));
+          v = (d[SP_FS_DC1] * sig + c.c1 * v) + ((d[SP_FS_DS1] * pp + s1 * dpp) - (d[SP_FS_DS2] * qq + s2 * dqq));
         }
         if (!in) v = 0.0;
         ob[(size_t)p * kr2 + (size_t)i * Kr + j] = v;
@@ -306,10 +307,10 @@ __global__ __launch_bounds__(256) void fisher_trace_kernel(int Kr, int P, const 
 __global__ __launch_bounds__(256) void fisher_finish_kernel(
     int K, int Kr, int P, int ntab, const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef,
     const int32_t *__restrict__ info, const double *__restrict__ part, const double *__restrict__ ones,
-    const double *__restrict__ dmean, int normalized, double zmax, double *__restrict__ fisher,
+    const double *__restrict__ dmean, int per_star, int normalized, double zmax, double *__restrict__ fisher,
     uint32_t *__restrict__ status) {
   __shared__ double red[4];
-  __shared__ double tr[FP_MAX * (FP_MAX + 1) / 2];
+  __shared__ double tr[SP_FISHER_PMAX * (SP_FISHER_PMAX + 1) / 2];
   __shared__ int nonfinite;
   const int s = blockIdx.x, tid = threadIdx.x, ntr = Kr / 64, nt2 = ntr * ntr, npairs = P * (P + 1) / 2;
   if (tid == 0) nonfinite = 0;
@@ -332,7 +333,8 @@ __global__ __launch_bounds__(256) void fisher_finish_kernel(
     val = 0.5 * tr[pair_index(lo, hi, P)];
     if (!normalized) {
       // (the product of the two mean tangents in the order of the pair, so that F[i][j] and F[j][i] are the same bits)
-      const double dl = dmean[(size_t)lo * ntab + st.table], dh = dmean[(size_t)hi * ntab + st.table];
+      const int col = per_star ? s : st.table;
+      const double dl = dmean[(size_t)lo * ntab + col], dh = dmean[(size_t)hi * ntab + col];
       val += (dl * dh) * o11;
     }
     // (a rejected star holds zeros whether or not its covariance factors, as it adds zeros to the gradient)
@@ -360,7 +362,7 @@ FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts) {
   F.dC = c.take(d * (size_t)S * P * kr2);
   F.G = c.take(d * (size_t)S * P * kr2);
   F.drow = c.take(d * (size_t)S * P * K);
-  F.dsc = c.take(d * (size_t)S * P * FS_N);
+  F.dsc = c.take(d * (size_t)S * P * SP_FS_N);
   F.part = c.take(d * (size_t)S * (P * (P + 1) / 2) * ntr * ntr);
   F.ones = c.take(d * (size_t)S * ntr);
   F.total = c.off;
@@ -372,7 +374,6 @@ int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double
                  double *dcov, uint32_t *status, void *workspace) {
   const int S = Q.S, K = Q.K, covpts = Q.covpts, temporal = Q.temporal, normalized = Q.normalized, order = Q.order;
   const double *t = Q.t, *tab = Q.tab;
-  const double zmax = Q.zmax;
   const sp_star *stars = Q.stars;
   hipStream_t st = Q.st;
   const int Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB, np = covpts + 4;
@@ -383,22 +384,16 @@ int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double
   double *Cinv = at<double>(base, F.cinv), *dC = at<double>(base, F.dC), *G = at<double>(base, F.G);
   double *drow = at<double>(base, F.drow), *dsc = at<double>(base, F.dsc), *part = at<double>(base, F.part);
   double *ones = at<double>(base, F.ones);
-  const size_t kr2 = (size_t)Kr * Kr;
   int rc;
   // C and its inverse: the gradient sweep's own opening (sp_grad.hip)
   if ((rc = sp_launch_marginal_inverse(h, Q, V, Cinv, nullptr))) return rc;
-  if (ntr > 1) {
-    hipLaunchKernelGGL(fisher_mirror_kernel, dim3(ntr * (ntr - 1) / 2, S), dim3(256), 0, st, Kr, Cinv);
-    SP_LAUNCH_CHECK();
-  }
+  if ((rc = sp_launch_fisher_mirror(S, Kr, Cinv, st))) return rc;
   // the tangents
   if (normalized) {
     hipLaunchKernelGGL(fisher_rowsum_kernel, dim3(ntr, S), dim3(256), sizeof(double) * (size_t)P * np, st, K, P, ntab,
                        theta, t, stars, covpts, dyp, temporal, drow);
     SP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(fisher_coef_kernel, dim3(S), dim3(256), 0, st, K, P, ntab, stars, (const SpCoef *)coef, qv, dmean,
-                       order, drow, dsc);
-    SP_LAUNCH_CHECK();
+    if ((rc = sp_launch_fisher_coef(S, K, P, ntab, 0, stars, coef, qv, dmean, order, drow, dsc, st))) return rc;
   }
   {
     const size_t lds = sizeof(double) * ((size_t)(P + (normalized ? 1 : 0)) * np + 6 * 64 + 2 * FP_MAX * 64);
@@ -406,6 +401,36 @@ int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double
                        covpts, tab, dyp, temporal, normalized, qv, (const SpCoef *)coef, drow, dsc, dC, dcov);
     SP_LAUNCH_CHECK();
   }
+  return sp_launch_fisher_close(Q, V, P, ntab, 0, Cinv, dC, G, part, ones, dmean, fisher, status);
+}
+
+}  // namespace
+
+// ---- what the marginal sweep above and the conditional one (sp_fisher_cond.hip) both launch: one copy of the kernels
+int sp_launch_fisher_mirror(int S, int Kr, double *Cinv, hipStream_t st) {
+  const int ntr = Kr / SP_NB;
+  if (ntr > 1) {
+    hipLaunchKernelGGL(fisher_mirror_kernel, dim3(ntr * (ntr - 1) / 2, S), dim3(256), 0, st, Kr, Cinv);
+    SP_LAUNCH_CHECK();
+  }
+  return SP_OK;
+}
+
+int sp_launch_fisher_coef(int S, int K, int P, int ntab, int per_star, const sp_star *stars, const double *coef,
+                          const double *qv, const double *dmean, int order, double *drow, double *dsc, hipStream_t st) {
+  hipLaunchKernelGGL(fisher_coef_kernel, dim3(S), dim3(256), 0, st, K, P, ntab, per_star, stars, (const SpCoef *)coef, qv,
+                     dmean, order, drow, dsc);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+int sp_launch_fisher_close(const SpProblem &Q, const SpViews &V, int P, int ntab, int per_star, const double *Cinv,
+                           const double *dC, double *G, double *part, double *ones, const double *dmean, double *fisher,
+                           uint32_t *status) {
+  const int S = Q.S, K = Q.K, normalized = Q.normalized, Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB;
+  const size_t kr2 = (size_t)Kr * Kr;
+  hipStream_t st = Q.st;
+  int rc;
   // G_i = C^-1 d_i C (d_i C symmetric: A B^T with B = d_i C), the stars of the group as the batch
   for (int p = 0; p < P; ++p)
     if ((rc = sp_launch_gemm_nt(Cinv, Kr, (long)kr2, dC + (size_t)p * kr2, Kr, (long)(P * kr2), G + (size_t)p * kr2, Kr,
@@ -417,13 +442,11 @@ int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double
     hipLaunchKernelGGL(fisher_ones_kernel, dim3(ntr, S), dim3(256), 0, st, K, Kr, Cinv, ones);
     SP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, stars, (const SpCoef *)coef, V.info(),
-                     part, ones, dmean, normalized, zmax, fisher, status);
+  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, Q.stars, (const SpCoef *)V.coef(),
+                     V.info(), part, ones, dmean, per_star, normalized, Q.zmax, fisher, status);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

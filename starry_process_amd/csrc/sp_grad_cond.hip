@@ -367,6 +367,52 @@ GradCondLayout grad_cond_layout(sp_handle *h, int S, int K) {
 
 }  // namespace
 
+// The forward of the conditional branch's sweeps (this file's gradient, sp_fisher_cond.hip's Fisher information): C as the
+// likelihood sees it in the corner of the system the inverse factors, then C^-1 (lower tiles) into Cinv [S][Kr][Kr].
+//   A [S][Kr][N] the design matrices, B [S][Kr][N] = A Sigma_y, raw [S][Kr][Kr] the raw covariance (A Sigma_y A^T) o T
+//   (the lower tiles; every entry when N is no multiple of 64) -- raw == Cinv: the inverse takes its place;
+//   partial: [S][Kr / 64][K] doubles; logdet [S] or null.  Leaves theta, rowsum, qv, coef, condmean, cs, vrow, info of V.
+int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A, double *B,
+                           double *raw, double *Cinv, double *partial, double *logdet) {
+  const int S = P.S, K = P.K, temporal = P.temporal, normalized = P.normalized;
+  const double *t_dev = P.t, *diag_dev = P.diag;
+  const sp_star *stars_dev = P.stars;
+  hipStream_t st = P.st;
+  const int Kr = sp_roundup(K, SP_NB), N = h->N, ntr = Kr / SP_NB, ntri = ntr * (ntr + 1) / 2;
+  const Layout &L = V.L;
+  double *theta = V.theta(), *rowsum = V.rowsum(), *qv = V.qv(), *coef = V.coef(), *sys = V.sys();
+  double *cm = V.condmean();
+  const long sAB = (long)Kr * N;
+  int rc;
+  if ((rc = sp_launch_theta(P, theta))) return rc;
+  if ((rc = sp_launch_design(h, V, stars_dev, rta1_dev, A, st, Kr))) return rc;
+  if ((rc = sp_launch_cond_mean(S, N, Kr, A, h->d_mean_ylm, cm, st))) return rc;
+  if ((rc = sp_launch_gemm_nt(A, N, sAB, h->d_cov_ylm, N, 0, B, N, sAB, Kr, N, N, 1.0, 0, 0, S, st))) return rc;
+  // (the raw covariance, temporal factor applied: [S][Kr][Kr]; its row sums)
+  if (N % 64 == 0) {
+    // (the Kr x Kr matrix alone, raw: no residual rows, no variances)
+    SpProblem R = P;
+    R.M = 0;
+    R.flux = nullptr;
+    R.diag = nullptr;
+    if ((rc = sp_launch_cond_system(R, B, A, N, Kr, Kr, nullptr, raw, partial))) return rc;
+    if (normalized) {
+      hipLaunchKernelGGL(cond_rowsum_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, ntr, partial, rowsum);
+      SP_LAUNCH_CHECK();
+    }
+  } else {
+    if ((rc = sp_launch_gemm_nt(B, N, sAB, A, N, sAB, raw, Kr, (long)Kr * Kr, Kr, Kr, N, 1.0, 0, 0, S, st))) return rc;
+    hipLaunchKernelGGL(cond_raw_rows_kernel, dim3((K + 3) / 4, S), dim3(256), 0, st, K, Kr, temporal, t_dev, stars_dev, raw,
+                       rowsum);
+    SP_LAUNCH_CHECK();
+  }
+  if ((rc = sp_launch_norm_coef(P, cm, rowsum, qv, coef, nullptr))) return rc;
+  hipLaunchKernelGGL(cond_finish_kernel, dim3(ntri, S), dim3(256), 0, st, K, Kr, raw, stars_dev, (const SpCoef *)coef, qv,
+                     diag_dev, normalized, sys, (long)L.Kp, (long)L.Kp * L.Kp);
+  SP_LAUNCH_CHECK();
+  return spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st);
+}
+
 extern "C" {
 
 size_t sp_lnlike_grad_conditional_workspace_bytes(sp_handle *h, int S, int K) {
@@ -392,9 +438,7 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   const GradCondLayout G = grad_cond_layout(h, S, K);
   char *base = static_cast<char *>(workspace_dev);
   const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
-  const Layout &L = V.L;
-  double *theta = V.theta(), *rowsum = V.rowsum(), *qv = V.qv(), *coef = V.coef(), *sys = V.sys();
-  double *cm = V.condmean(), *cs = V.cs(), *vrow = V.vrow();
+  double *theta = V.theta(), *cs = V.cs(), *vrow = V.vrow();
   SpProblem P;
   P.S = S, P.K = K, P.M = 1, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
   P.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
@@ -406,34 +450,8 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   double *vbar = at<double>(base, G.vbar), *thbar = at<double>(base, G.thbar), *partial = at<double>(base, G.partial);
   const long sAB = (long)Kr * N;
   int rc;
-  // ---- forward: C as the likelihood sees it, in the corner of the system the inverse factors
-  if ((rc = sp_launch_theta(P, theta))) return rc;
-  if ((rc = sp_launch_design(h, V, stars_dev, rta1_dev, A, st, Kr))) return rc;
-  if ((rc = sp_launch_cond_mean(S, N, Kr, A, h->d_mean_ylm, cm, st))) return rc;
-  if ((rc = sp_launch_gemm_nt(A, N, sAB, h->d_cov_ylm, N, 0, B, N, sAB, Kr, N, N, 1.0, 0, 0, S, st))) return rc;
-  // (the raw covariance, temporal factor applied, where C^-1 will be: [S][Kr][Kr]; its row sums)
-  if (N % 64 == 0) {
-    // (the Kr x Kr matrix alone, raw: no residual rows, no variances)
-    SpProblem R = P;
-    R.M = 0;
-    R.flux = nullptr;
-    R.diag = nullptr;
-    if ((rc = sp_launch_cond_system(R, B, A, N, Kr, Kr, nullptr, Cinv, partial))) return rc;
-    if (normalized) {
-      hipLaunchKernelGGL(cond_rowsum_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, ntr, partial, rowsum);
-      SP_LAUNCH_CHECK();
-    }
-  } else {
-    if ((rc = sp_launch_gemm_nt(B, N, sAB, A, N, sAB, Cinv, Kr, (long)Kr * Kr, Kr, Kr, N, 1.0, 0, 0, S, st))) return rc;
-    hipLaunchKernelGGL(cond_raw_rows_kernel, dim3((K + 3) / 4, S), dim3(256), 0, st, K, Kr, temporal, t_dev, stars_dev, Cinv,
-                       rowsum);
-    SP_LAUNCH_CHECK();
-  }
-  if ((rc = sp_launch_norm_coef(P, cm, rowsum, qv, coef, nullptr))) return rc;
-  hipLaunchKernelGGL(cond_finish_kernel, dim3(ntri, S), dim3(256), 0, st, K, Kr, Cinv, stars_dev, (const SpCoef *)coef, qv,
-                     diag_dev, normalized, sys, (long)L.Kp, (long)L.Kp * L.Kp);
-  SP_LAUNCH_CHECK();
-  if ((rc = spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st))) return rc;
+  // ---- forward: C as the likelihood sees it, and its inverse
+  if ((rc = sp_launch_cond_inverse(h, P, V, rta1_dev, A, B, Cinv, Cinv, partial, logdet))) return rc;
   // ---- the head of the reverse sweep: lnL, hcoef = c1, w, alpha, meanbar and the slots 2-5 of starbar
   if ((rc = sp_launch_grad_front(P, V, Cinv, logdet, vec, dots, hcoef, partial, lnlike_dev, meanbar, status_dev,
                                  starbar_dev)))

@@ -529,6 +529,34 @@ int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cin
                          double *dots, double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
                          double *starbar);
 
+// sp_grad_cond.hip: the forward of the conditional branch's sweeps (gradient, Fisher information): the design matrices
+// A [S][Kr][N], B = A Sigma_y, the raw covariance (A Sigma_y A^T) o T into raw [S][Kr][Kr] (lower tiles; raw may be Cinv,
+// whose place the inverse then takes), the normalisation, C^-1 (lower tiles) into Cinv.  partial: [S][Kr / 64][K] doubles;
+// logdet [S] or null.  Leaves theta, rowsum, qv, coef, condmean, cs, vrow and info of V for the sweep behind it.
+int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A, double *B,
+                           double *raw, double *Cinv, double *partial, double *logdet);
+// sp_lnlike.hip: the tangents of the design matrices sp_launch_design left in place (V's cs, vrow, theta), Kr rows per
+// star: dA_inc = d A / d inc per radian (dR [S][NWIG], dv [S][N]: scratch), dA_per = d A / d period; either may be null
+int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,
+                              double *dR, double *dv, double *dA_inc, double *dA_per, hipStream_t st, int Kr);
+
+// sp_fisher.hip: the kernels the two Fisher sweeps (sp_fisher.hip, sp_fisher_cond.hip) share, behind host launchers.
+// Parameters per call the shared kernels hold (the conditional sweep: 5 hyperparameters, inclination, period)
+constexpr int SP_FISHER_PMAX = 7;
+// per-parameter scalars of a star's normalisation tangent: dsc [S][P][SP_FS_N] (fisher_coef_kernel)
+enum { SP_FS_DC1 = 0, SP_FS_DS1 = 1, SP_FS_DS2 = 2, SP_FS_N = 4 };
+// completes C^-1 [S][Kr][Kr]: the strictly lower 64 x 64 tiles transposed into the upper ones
+int sp_launch_fisher_mirror(int S, int Kr, double *Cinv, hipStream_t st);
+// from the row sums of the raw tangents (drow [S][P][K]; on return d q) and the tangents of the flux mean (dmean
+// [P][ntab], column = the star's table, or per_star: ntab = S, column = the star): dsc and d q of the normalisation
+int sp_launch_fisher_coef(int S, int K, int P, int ntab, int per_star, const sp_star *stars, const double *coef,
+                          const double *qv, const double *dmean, int order, double *drow, double *dsc, hipStream_t st);
+// G_i = C^-1 d_i C (dC, G [S][P][Kr][Kr]), the pair traces (part [S][P (P + 1) / 2][(Kr / 64)^2]), 1^T C^-1 1 (ones
+// [S][Kr / 64]; unnormalised), then F_s with the mean term, the failure semantics and the status word, on V's coef and info
+int sp_launch_fisher_close(const SpProblem &Q, const SpViews &V, int P, int ntab, int per_star, const double *Cinv,
+                           const double *dC, double *G, double *part, double *ones, const double *dmean, double *fisher,
+                           uint32_t *status);
+
 // grid of a grid-stride kernel: blocks of 256 threads covering `total` elements, at most `max_blocks` of them
 static inline unsigned grid_for(size_t total, size_t max_blocks = 8192) {
   const size_t b = (total + 255) / 256;

@@ -61,6 +61,8 @@ __global__ void inc_cs_kernel(int S, const sp_star *__restrict__ stars,
 
 // v[s] = rTA1[table_s] . blockdiag(R(-inc_s))   (all K rows of the tiled
 // operator are identical before the phase rotation, flux.py:280,97)
+// DERIV: Rinc holds Rx'(-inc_s) (sp_launch_Rx's dR) and the row is d v / d inc = -rTA1 . Rx'(-inc_s)
+template <bool DERIV>
 __global__ __launch_bounds__(256) void cond_prep_kernel(
     int N, int nwig, const int32_t *__restrict__ l_of, const int32_t *__restrict__ blk,
     const sp_star *__restrict__ stars, const double *__restrict__ rta1,
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void cond_prep_kernel(
   const double *B = Rinc + (size_t)s * nwig + blk[l] + (n - base);
   double acc = 0.0;
   for (int i = 0; i < w; ++i) acc += row[base + i] * B[i * w];
-  v[(size_t)s * N + n] = acc;
+  v[(size_t)s * N + n] = DERIV ? -acc : acc;
 }
 
 // The design matrix in ONE kernel, on the matrix cores (flux.py:278-281, 88-105; round 4): row k of star s is
@@ -86,11 +88,15 @@ __global__ __launch_bounds__(256) void cond_prep_kernel(
 // from the packed rotation in LDS (RLDS; from L2 for degrees whose NWIG doubles do not fit).  A first form on the
 // vector ALU (thread = output column, 8 rows per workgroup) spent 178 us on its LDS reads -- w x 9 of them for
 // 8 w multiply-adds; this one needs two per 64.  Rows K .. Kr - 1 are zero.
+// DTHETA: the tangent with respect to the star's period instead (sp_fisher_cond.hip): the A fragment is the
+// theta-derivative of the phase-rotated entry, m (-v[l, m] sin m theta + v[l, -m] cos m theta), and row k carries the
+// factor d theta_k / d p = -2 pi t_k / p^2, folded into the row's cos / sin table (t, stars: read only then).
 typedef double cd_d4 __attribute__((ext_vector_type(4)));
-template <bool RLDS>
+template <bool RLDS, bool DTHETA>
 __global__ __launch_bounds__(256) void cond_design_kernel(
     int ydeg, int N, int nwig, int K, int Kr, const double *__restrict__ v, const double *__restrict__ theta,
-    const double *__restrict__ Rpk, double *__restrict__ A) {
+    const double *__restrict__ Rpk, double *__restrict__ A, const double *__restrict__ t,
+    const sp_star *__restrict__ stars) {
   extern __shared__ __attribute__((aligned(16))) double cd_lds[];
   const int nc = ydeg + 1;
   double *sV = cd_lds;                       // N
@@ -130,6 +136,13 @@ __global__ __launch_bounds__(256) void cond_design_kernel(
         cn[n] = 2.0 * cn[n - 1] * c1 - cn[n - 2];
         sn[n] = 2.0 * sn[n - 1] * c1 - sn[n - 2];
       }
+      if (DTHETA) {
+        const double per = stars[s].period, sc = -6.283185307179586 * t[(size_t)s * K + r0 + tid] / (per * per);
+        for (int n = 0; n <= ydeg; ++n) {
+          cn[n] *= sc;
+          sn[n] *= sc;
+        }
+      }
     } else {
       for (int n = 0; n <= ydeg; ++n) cn[n] = sn[n] = 0.0;   // (a padding row: zeros)
     }
@@ -150,8 +163,12 @@ __global__ __launch_bounds__(256) void cond_design_kernel(
         if (k < w) {
           // entry n = base + k of the phase-rotated vector: m = k - l, its mirror is base + 2 l - k (wigner.h:289-339)
           const int m = k - l, am = m < 0 ? -m : m;
-          const double sm = m < 0 ? -srow[am] : srow[am];
-          a = sV[base + k] * crow[am] + sV[base + 2 * l - k] * sm;
+          if (DTHETA) {
+            a = sV[base + 2 * l - k] * ((double)m * crow[am]) - sV[base + k] * ((double)am * srow[am]);
+          } else {
+            const double sm = m < 0 ? -srow[am] : srow[am];
+            a = sV[base + k] * crow[am] + sV[base + 2 * l - k] * sm;
+          }
           if (col < w) b = Rsrc[boff + k * w + col];
         }
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
@@ -206,6 +223,29 @@ __global__ void get_gpmean_kernel(int S, const double *__restrict__ coef,
 
 }  // namespace
 
+namespace {
+// the design-matrix kernel (or its period tangent) on the row vectors `vrow` [S][N]
+template <bool DTHETA>
+int launch_design_rows(sp_handle *h, int S, int K, int Kr, const double *vrow, const double *theta, const double *t,
+                       const sp_star *stars, double *A_out, hipStream_t st) {
+  const int N = h->N;
+  const size_t small = sizeof(double) * ((size_t)N + 2 * 64 * (h->ydeg + 1));
+  const size_t withR = small + sizeof(double) * (size_t)h->NWIG;
+  dim3 grid((Kr + 63) / 64, S);
+  if (withR <= 150 * 1024) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cond_design_kernel<true, DTHETA>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipLaunchKernelGGL((cond_design_kernel<true, DTHETA>), grid, dim3(256), withR, st, h->ydeg, N, h->NWIG, K, Kr, vrow,
+                       theta, h->d_Rx90, A_out, t, stars);
+  } else {
+    hipLaunchKernelGGL((cond_design_kernel<false, DTHETA>), grid, dim3(256), small, st, h->ydeg, N, h->NWIG, K, Kr, vrow,
+                       theta, h->d_Rx90, A_out, t, stars);
+  }
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+}  // namespace
+
 // design matrix for S stars into A_out (theta already filled); Kr rows per star in A_out and
 // in the scratch B1 (Kr == K: contiguous stars; Kr > K: the rows beyond K are zeroed)
 int sp_launch_design(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, double *A_out,
@@ -217,22 +257,29 @@ int sp_launch_design(sp_handle *h, const SpViews &V, const sp_star *stars, const
   SP_LAUNCH_CHECK();
   int rc = sp_launch_Rx(h, cs, S, Rinc, nullptr, st);
   if (rc) return rc;
-  hipLaunchKernelGGL(cond_prep_kernel, dim3((N + 255) / 256, S), dim3(256), 0, st,
+  hipLaunchKernelGGL(cond_prep_kernel<false>, dim3((N + 255) / 256, S), dim3(256), 0, st,
                      N, h->NWIG, h->d_l_of, h->d_blk, stars, rta1, Rinc, vrow);
   SP_LAUNCH_CHECK();
-  const size_t small = sizeof(double) * ((size_t)N + 2 * 64 * (h->ydeg + 1));
-  const size_t withR = small + sizeof(double) * (size_t)h->NWIG;
-  dim3 grid((Kr + 63) / 64, S);
-  if (withR <= 150 * 1024) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cond_design_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipLaunchKernelGGL((cond_design_kernel<true>), grid, dim3(256), withR, st, h->ydeg, N, h->NWIG, K, Kr, vrow, theta,
-                       h->d_Rx90, A_out);
-  } else {
-    hipLaunchKernelGGL((cond_design_kernel<false>), grid, dim3(256), small, st, h->ydeg, N, h->NWIG, K, Kr, vrow, theta,
-                       h->d_Rx90, A_out);
+  return launch_design_rows<false>(h, S, K, Kr, vrow, theta, nullptr, nullptr, A_out, st);
+}
+
+// The tangents of the design matrices sp_launch_design left behind (V's cs, vrow, Rinc and theta as it filled them), Kr
+// rows per star, rows K .. Kr - 1 zero:
+//   dA_inc  d A / d inc (per radian): the design matrix of the row d v / d inc = -rTA1 Rx'(-inc)   (dR [S][NWIG], dv [S][N]: scratch)
+//   dA_per  d A / d p: the theta-derivative of the phase rotation, row k times d theta_k / d p = -2 pi t_k / p^2
+// either may be null.
+int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,
+                              double *dR, double *dv, double *dA_inc, double *dA_per, hipStream_t st, int Kr) {
+  const int S = V.L.S, K = V.L.K, N = V.L.N;
+  int rc;
+  if (dA_inc) {
+    if ((rc = sp_launch_Rx(h, V.cs(), S, V.Rinc(), dR, st))) return rc;     // (Rinc: the same numbers again)
+    hipLaunchKernelGGL(cond_prep_kernel<true>, dim3((N + 255) / 256, S), dim3(256), 0, st, N, h->NWIG, h->d_l_of, h->d_blk,
+                       stars, rta1, dR, dv);
+    SP_LAUNCH_CHECK();
+    if ((rc = launch_design_rows<false>(h, S, K, Kr, dv, V.theta(), nullptr, nullptr, dA_inc, st))) return rc;
   }
-  SP_LAUNCH_CHECK();
+  if (dA_per && (rc = launch_design_rows<true>(h, S, K, Kr, V.vrow(), V.theta(), t, stars, dA_per, st))) return rc;
   return SP_OK;
 }
 

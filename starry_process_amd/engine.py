@@ -1178,6 +1178,42 @@ class Engine(object):
                 self._p(workspace), int(workspace.numel()), self._stream()))
         return (fisher, status, dcov) if return_tangents else (fisher, status)
 
+    def fisher_conditional_workspace(self, S, K, P):
+        """Device scratch that holds ``S`` stars of ``fisher_conditional`` at once (sp_fisher_conditional_workspace_bytes)."""
+        return self._scratch(self._L.sp_fisher_conditional_workspace_bytes(self._h, int(S), int(K), int(P)))
+
+    def fisher_conditional(self, t, stars_dev, rta1, dmu, dsig, star_params=("i", "p"), diag=None, temporal=None,
+                           normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False):
+        """Device half of the conditional branch's Fisher information (sp_fisher_conditional), at the engine's current
+        moments: t [S, K], stars_dev (each star's inclination in sp_star.inc, radians), rta1 [ntab, N] and the moments'
+        tangents with respect to Ph shared hyperparameters (dmu [Ph, N], dsig [Ph, N, N]; None for Ph = 0) ->
+        (fisher [S, P, P], status [S]) and, with ``return_tangents``, dcov [S, P, K, K].  The rows of a star's block: the
+        Ph hyperparameters, then its inclination (per RADIAN) when "i" is in ``star_params``, then its period when "p"
+        is.  workspace: a byte tensor (``fisher_conditional_workspace``); one that holds fewer than S stars makes the
+        call work through the stars in groups, with the same bits."""
+        torch = _torch()
+        S, K = t.shape
+        N = self.N
+        Ph = 0 if dmu is None else int(dmu.shape[0])
+        mask = (1 if "i" in star_params else 0) | (2 if "p" in star_params else 0)
+        P = Ph + (mask & 1) + (mask >> 1)
+        if Ph:
+            assert tuple(dmu.shape) == (Ph, N) and tuple(dsig.shape) == (Ph, N, N)
+            dmu, dsig = dmu.contiguous(), dsig.contiguous()
+        else:
+            dmu = dsig = None
+        fisher = self.empty(S, P, P)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        dcov = self.empty(S, P, K, K) if return_tangents else None
+        if S > 0:
+            if workspace is None:
+                workspace = self._grad_ws = self.fisher_conditional_workspace(S, K, P)
+            check(self._L.sp_fisher_conditional(
+                self._h, S, K, Ph, mask, self._p(t), self._p(diag), self._p(stars_dev), self._p(rta1), self._p(dmu),
+                self._p(dsig), TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(fisher),
+                self._p(dcov), self._p(status), self._p(workspace), int(workspace.numel()), self._stream()))
+        return (fisher, status, dcov) if return_tangents else (fisher, status)
+
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 

@@ -37,7 +37,8 @@ from .stars import check_period_inclination, ensemble_stars
 from .temporal import kernel_id
 
 __all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient",
-           "EnsembleFisher", "ensemble_fisher", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional"]
+           "EnsembleFisher", "ensemble_fisher", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional",
+           "EnsembleFisherConditional", "ensemble_fisher_conditional", "cramer_rao_ensemble"]
 
 _cache = {}
 _BOUNDS = {"r": (0.0, 90.0), "dr": (0.0, 90.0), "a": (0.0, 1.0), "b": (0.0, 1.0)}      # of the upstream integrals
@@ -913,3 +914,189 @@ def ensemble_gradient_conditional_device(t, flux, ferr=1.0e-3, p=1.0, i=defaults
     eg = EnsembleGradientConditional(t, flux, ferr=ferr, p=p, i=i, **kwargs)
     total, grad = eg(r=r, a=a, b=b, c=c, n=n, wrt=wrt)
     return total, grad, eg.lnlike
+
+
+# what the conditional branch's Fisher information may be taken about: the shared hyperparameters (the moments' exact
+# tangents have no spread of radii) and each star's own parameters
+_FISHER_COND_PARAMS = ("r", "a", "b", "c", "n")
+_FISHER_STAR_PARAMS = ("i", "p")
+
+
+def _check_conditional_params(params, star_params):
+    """(params, star_params) as tuples of distinct names out of (r, a, b, c, n) and (i, p); ValueError otherwise, and
+    when both are empty.  No device work."""
+    out = []
+    for what, given, known in (("params", params, _FISHER_COND_PARAMS), ("star_params", star_params, _FISHER_STAR_PARAMS)):
+        given = (given,) if isinstance(given, str) else tuple(given)
+        for k, name in enumerate(given):
+            if name not in known:
+                raise ValueError("%s: unknown name %r (one of %s)" % (what, name, ", ".join(known)))
+            if name in given[:k]:
+                raise ValueError("%s: %r is named twice" % (what, name))
+        out.append(given)
+    if not out[0] and not out[1]:
+        raise ValueError("params and star_params: at least one name between them")
+    return out[0], out[1]
+
+
+class EnsembleFisherConditional(_EnsembleSweep):
+    """Expected (Fisher) information of an ENSEMBLE of light curves on the CONDITIONAL branch (star s at its own
+    inclination i_s), in one device sweep and without any flux: how well these cadences, periods and noise CAN constrain
+    the shared spot hyperparameters (r, a, b, c, n) AND every star's own inclination and period.  Per star, with C_s the
+    covariance ``EnsembleGradientConditional`` factors and m_s the mean of its flux GP (the flux mean when not normalised,
+    else 0),
+
+        F_s[i, j] = 1/2 tr(C^-1 d_i C  C^-1 d_j C) + (d_i m)(d_j m) 1^T C^-1 1
+
+    over the star's parameters: ``params``, then ``star_params``.
+
+        ef = EnsembleFisherConditional(t, ferr=1e-3, p=periods, i=inclinations)     # cadences, star records -> GPU, once
+        F_shared = ef(r=20., a=.4, b=.27, c=.1, n=10.)          # [5, 5]: the information at KNOWN inclinations and periods
+        ef.per_star, ef.status, ef.names, ef.star_names          # [S, 7, 7], [S], ("r", ..., "n"), ("i", "p")
+        cr = cramer_rao_ensemble(ef.per_star, 5, ef.status)      # bounds with the other block marginalised
+
+    t: (K,) or (S, K); the number of stars is t's, p's or i's.  The moments' tangents are ``ylm_moments_device_grad``'s for
+    r, a, b and closed forms for c and n; the device forms the design matrices' tangents with respect to i and p, the
+    tangents of the covariances, C^-1 d_i C on the matrix cores and the pair traces (sp_fisher_conditional, DESIGN.md
+    18).  Inclinations in degrees: the rows and columns of "i" are per degree.  max_workspace_bytes: a bound on the device
+    scratch; the stars are then worked through in groups, with the same bits."""
+
+    _open = staticmethod(get_engine)
+
+    def __init__(self, t, ferr=1.0e-3, p=1.0, i=defaults["i"], u=None, ydeg=15, baseline_var=0.0, normalized=True,
+                 tau=None, temporal_kernel="matern32", device=None, upstream_kwargs=None, max_workspace_bytes=None):
+        t = np.asarray(t, dtype=np.float64)
+        if t.ndim not in (1, 2):
+            raise ValueError("t must be (K,) or (S, K)")
+        S = t.shape[0] if t.ndim == 2 else max([np.asarray(x).shape[0] for x in (p, i) if np.ndim(x) == 1] or [1])
+        # (the inclinations' bounds are not checked on this branch)
+        self._setup(t, np.zeros((S, t.shape[-1])), ferr, p, i, u, ydeg, 0.0, baseline_var, tau, temporal_kernel, device)
+        self._flux = None
+        self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
+        self._max_ws = None if max_workspace_bytes is None else int(max_workspace_bytes)
+        self._ws = None
+        self.per_star = self.status = self.names = self.star_names = self.tangents = None
+
+    def _workspace(self, P):
+        """Scratch for P parameters: every star at once, or as many as ``max_workspace_bytes`` allows."""
+        e = self._e
+        need = int(e._L.sp_fisher_conditional_workspace_bytes(e._h, self.S, self.K, P))
+        nbytes = need if self._max_ws is None else min(need, self._max_ws)
+        if self._ws is None or self._ws.numel() != nbytes:
+            self._ws = e._scratch(nbytes)
+        return self._ws
+
+    def _moment_tangents(self, names, r, a, b, c, n):
+        """The engine's moments set at the point; (dmu [Ph, N], dSig [Ph, N, N]) in the order of ``names`` (None, None
+        without any): r, a, b from the quadrature's exact tangents, c and n in closed form -- mu_y = c n m, Sigma_y - eps =
+        c^2 n S (contrast.py:21-33) -- with the unit-contrast evaluation on the boundary c = 0 or n = 0 (``_cn_chain``)."""
+        import torch
+
+        from .upstream_device import ylm_moments_device, ylm_moments_device_grad
+
+        e = self._e
+        mu, Sig, dmu, dSig = ylm_moments_device_grad(e, r=r, a=a, b=b, c=c, n=n, **self._ukw)
+        e.set_moments_dev(mu, Sig)
+        if not names:
+            return None, None
+        tang = {name: (dmu[k], dSig[k]) for k, name in enumerate(("r", "a", "b"))}
+        if "c" in names or "n" in names:
+            eps = torch.diag(_upstream_eps(mu.shape[0], self._ukw, like=mu))
+            if c != 0 and n != 0:
+                tang["c"] = (mu / c, 2.0 * (Sig - eps) / c)
+                tang["n"] = (mu / n, (Sig - eps) / n)
+            else:
+                mu1, Sig1 = ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)
+                S1 = Sig1 - eps
+                tang["c"] = (n * mu1, 2.0 * c * n * S1)
+                tang["n"] = (c * mu1, c * c * S1)
+        return torch.stack([tang[k][0] for k in names]), torch.stack([tang[k][1] for k in names])
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
+                 params=("r", "a", "b", "c", "n"), star_params=("i", "p"), return_tangents=False):
+        """F_shared [P_h, P_h] (NumPy): the sum over the stars of the hyperparameter blocks, in the order of ``params`` --
+        the information about them at KNOWN inclinations and periods.  Afterwards ``per_star`` [S, P, P] over ``params``
+        + ``star_params`` (names out of r, a, b, c, n; out of i, p -- "i" per degree), ``status`` [S] (the library's
+        per-star flags: a star with z > zmax holds zeros, one whose covariance does not factor or whose light curve is
+        ragged NaN), ``names`` and ``star_names``; F_shared adds the stars of status 0 in index order.  return_tangents:
+        ``tangents`` [S, P, K, K], the d_i C the device formed."""
+        names, star_names = _check_conditional_params(params, star_params)
+        e = self._e
+        r, a, b, c, n = float(r), float(a), float(b), float(c), float(n)
+        dmu, dSig = self._moment_tangents(names, r, a, b, c, n)
+        Ph, P = len(names), len(names) + len(star_names)
+        out = e.fisher_conditional(self._t, self._stars, self._rta1, dmu, dSig, star_params=star_names, diag=self._diag,
+                                   temporal=self._temporal, normalized=self._normalized, workspace=self._workspace(P),
+                                   return_tangents=return_tangents)
+        per_star, status = out[0].cpu().numpy(), out[1].cpu().numpy().astype(np.uint32)
+        # the device's order (hyperparameters, i, p) -> params + star_params; "i" per degree
+        device_order = list(names) + [k for k in _FISHER_STAR_PARAMS if k in star_names]
+        perm = [device_order.index(k) for k in names + star_names]
+        scale = np.array([np.pi / 180.0 if k == "i" else 1.0 for k in names + star_names])
+        per_star = per_star[:, perm][:, :, perm] * scale[:, None] * scale[None, :]
+        self.tangents = None
+        if return_tangents:
+            self.tangents = out[2].cpu().numpy()[:, perm] * scale[None, :, None, None]
+        self.per_star, self.status, self.names, self.star_names = per_star, status, names, star_names
+        return per_star[status == 0][:, :Ph, :Ph].sum(axis=0)
+
+
+def ensemble_fisher_conditional(t, ferr=1.0e-3, p=1.0, i=defaults["i"], r=defaults["r"], a=defaults["a"],
+                                b=defaults["b"], c=defaults["c"], n=defaults["n"], params=("r", "a", "b", "c", "n"),
+                                star_params=("i", "p"), **kwargs):
+    """One-shot form of ``EnsembleFisherConditional``: (F_shared [P_h, P_h], per_star [S, P, P], status [S])."""
+    params, star_params = _check_conditional_params(params, star_params)          # (before anything goes to the device)
+    ef = EnsembleFisherConditional(t, ferr=ferr, p=p, i=i, **kwargs)
+    F = ef(r=r, a=a, b=b, c=c, n=n, params=params, star_params=star_params)
+    return F, ef.per_star, ef.status
+
+
+def cramer_rao_ensemble(per_star, n_shared, status=None):
+    """Cramer-Rao bounds of an ensemble whose stars share ``n_shared`` hyperparameters and have parameters of their own:
+    per_star [S, P, P] the stars' Fisher blocks (``EnsembleFisherConditional.per_star``), rows and columns ordered
+    hyperparameters (h) first, then the star's own (*).  The joint Fisher matrix is an ARROW: shared block sum_s F_s[h, h],
+    star blocks F_s[*, *], cross blocks F_s[h, *]; it is never formed.  Returns a dict:
+
+      cov_shared [P_h, P_h], sigma_shared [P_h]   the bound on the hyperparameters with every star's own parameters
+                                                  marginalised: the inverse of the Schur complement
+                                                  sum_s (F_hh - F_h* F_**^-1 F_*h)_s
+      sigma_star [S, P_star]                      each star's own parameters with the hyperparameters marginalised:
+                                                  F_**^-1 + F_**^-1 F_*h cov_shared F_h* F_**^-1
+      sigma_star_known [S, P_star]                the same with the hyperparameters known: F_**^-1
+
+    status [S] (or None): the stars with a nonzero entry are left out of the sums and hold NaN.  NaN as in
+    ``cramer_rao``: a singular or non-finite block makes what depends on it NaN (a star block: the shared bound and every
+    star's marginalised bound; the shared Schur complement -- the full set (r, a, b, c, n) of a normalised process, DESIGN.md
+    17 --: the shared bound and the marginalised star bounds, not the known-hyperparameter ones).  Host only."""
+    F = np.asarray(per_star, dtype=np.float64)
+    if F.ndim != 3 or F.shape[1] != F.shape[2]:
+        raise ValueError("per_star must be [S, P, P]")
+    S, P = F.shape[0], F.shape[1]
+    Ph = int(n_shared)
+    if not 0 <= Ph <= P:
+        raise ValueError("n_shared must lie in 0 .. P")
+    Ps = P - Ph
+    ok = np.ones(S, dtype=bool) if status is None else np.asarray(status).reshape(S) == 0
+    schur = np.zeros((Ph, Ph))
+    cov_ss = np.full((S, Ps, Ps), np.nan)
+    known = np.full((S, Ps), np.nan)
+    for s in np.flatnonzero(ok):
+        Fhh, Fhs, Fss = F[s, :Ph, :Ph], F[s, :Ph, Ph:], F[s, Ph:, Ph:]
+        if Ps:
+            cov_ss[s], known[s] = cramer_rao(Fss)
+            with np.errstate(invalid="ignore"):          # (a singular star block: NaN goes on)
+                schur = schur + (Fhh - Fhs @ cov_ss[s] @ Fhs.T)
+        else:
+            schur = schur + Fhh
+    if Ph:
+        cov_shared, sigma_shared = cramer_rao(schur)
+    else:
+        cov_shared, sigma_shared = np.zeros((0, 0)), np.zeros(0)
+    sigma_star = np.full((S, Ps), np.nan)
+    for s in np.flatnonzero(ok):
+        if not Ps:
+            continue
+        with np.errstate(invalid="ignore"):
+            X = cov_ss[s] @ F[s, :Ph, Ph:].T              # F_**^-1 F_*h
+            sigma_star[s] = np.sqrt(np.diag(cov_ss[s] + X @ cov_shared @ X.T))
+    return dict(cov_shared=cov_shared, sigma_shared=sigma_shared, sigma_star=sigma_star, sigma_star_known=known)
