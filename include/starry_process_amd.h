@@ -857,6 +857,50 @@ int sp_lnlike_inclinations_planned(sp_handle *h, int S, int M, const void *plan_
                                    const double *inc_rad_dev, int normalized, int norm_order, double zmax,
                                    double *lnlike_dev, uint32_t *status_dev, void *workspace_dev, void *stream);
 
+/* ---- surface-map posteriors with the inclination marginalised on a grid (csrc/sp_ylm_incl.hip) --------
+ * The posterior of the Ylm map of star s given its light curve, mixed over the P grid inclinations inc[j] with the
+ * weights pinc[s][j] = softmax_j(logprior[j] + lnL[s][j]), lnL the un-normalised sp_lnlike_inclinations value
+ * (normalized = 0) of that star at the one moment set (mean_ylm_dev [N], cov_ylm_dev [N,N], DEVICE):
+ *   ymu[s] = sum_j pinc_j ymu_j,   ycov[s] = sum_j pinc_j (ycov_j + (ymu_j - ymu)(ymu_j - ymu)^T),
+ * (ymu_j, ycov_j) the Gaussian of sp_ylm_conditional_batched at inc[j].  With A_j = T Q_j R every component is a
+ * rank-n downdate of the prior (n = 2 ydeg + 1): ycov_j = Sigma_y - U_j^T U_j, U_j = Z_j Q_j R Sigma_y [n, N], so no
+ * N x N system is solved and the mixture is one lower-triangular product per star on the matrix cores.  The baseline
+ * variance enters the data precision (1 = T e0); as in sp_lnlike_inclinations the likelihood's mean is the scalar
+ * flux mean while the map posterior subtracts A_j mu_y from the data.
+ * Inputs as sp_lnlike_inclinations with M = 1 (t_dev [S,K], flux_dev [S,K], diag_dev [S,K] or NULL, stars_dev [S]:
+ * period, table, baseline_mean, baseline_var, data_var, nobs; rta1_dev [ntab,N]; inc_rad_dev [P] RADIANS) and
+ * logprior_dev [P], the log of the prior weight of each grid point (-inf: weight 0).  A component whose
+ * logprior + lnL is not finite has weight 0.
+ * Outputs: pinc_dev [S,P]; ymu_dev [S,N]; ycov_dev [S,N,N] or NULL (exactly symmetric; NULL skips the product);
+ * ymu_inc_dev [S,P,N] or NULL (the component means); status_dev [S] or NULL.
+ *   star the plan rejects (as sp_lnlike_inclinations): NaN in every output, SP_STAR_NO_BASIS;
+ *   star with no finite logprior + lnL (a NaN in its light curve, say): NaN in every output, SP_STAR_NAN.
+ * A star's numbers depend on its own inputs alone: the same bits run after run and in any batch; no floating-point
+ * atomics.  S = 0: SP_OK, nothing touched.  A null required pointer, K < 2, P < 1, or S, P, ntab, ns beyond 65535:
+ * SP_ERR_INVALID; a host-only handle: SP_ERR_NO_DEVICE.  workspace_dev:
+ * sp_ylm_conditional_inclinations_workspace_bytes(h, S, ntab, P, with_cov, ns) bytes with with_cov = (ycov_dev != NULL)
+ * and ns the same value in both calls (0 for a null handle or bad arguments); with ycov it holds the stack
+ * [S, roundup(N, 64), roundup(P n, 32)].  All launches go to `stream`; nothing is synchronised.
+ *
+ * sp_ylm_inclination_samples draws from the mixture by pathwise conditioning, from the workspace the call above left
+ * (same S, ntab, P, stars_dev; at most its ns samples per star; not modified in between): sample r of star s takes
+ * component comp_dev [S,ns] (int32, chosen by the caller from pinc) and the standard normal deviates z_dev [S,ns,N],
+ * e_dev [S,ns,n]:
+ *   y0 = mu_y + L_y z (cho_ylm_dev [N,N]: the lower factor of Sigma_y),
+ *   y = y0 + U_j^T (Z_j (hhat - Q_j R y0) - L_H,j^-1 e)                                     -> y_dev [S,ns,N].
+ * A flagged star, a component outside the grid or one of weight 0 gives NaN.  ns = 0 or S = 0: SP_OK.               */
+size_t sp_ylm_conditional_inclinations_workspace_bytes(sp_handle *h, int S, int ntab, int P, int with_cov, int ns);
+int sp_ylm_conditional_inclinations(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                                    const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, int ntab,
+                                    const double *mean_ylm_dev, const double *cov_ylm_dev, int P,
+                                    const double *inc_rad_dev, const double *logprior_dev, double *pinc_dev,
+                                    double *ymu_dev, double *ycov_dev, double *ymu_inc_dev, uint32_t *status_dev,
+                                    int ns, void *workspace_dev, void *stream);
+int sp_ylm_inclination_samples(sp_handle *h, int S, int ntab, int P, int ns, const sp_star *stars_dev,
+                               const double *mean_ylm_dev, const double *cho_ylm_dev, const int32_t *comp_dev,
+                               const double *z_dev, const double *e_dev, double *y_dev, void *workspace_dev,
+                               void *stream);
+
 /* ---- upstream of the hot path, host only ---------------- */
 /* LatitudeIntegralOp values (ops/latitude/latitude.py, ops/include/latitude.h:
  * 21-173): q [N], Q [N x N] for Beta shape parameters alpha, beta.  The

@@ -120,6 +120,10 @@ PROTOTYPES = {
     "sp_incl_plan_data": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_lnlike_inclinations_planned": (_I, [_V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _I, _D, _V,
                                             _V, _V, _V]),
+    "sp_ylm_conditional_inclinations_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
+    "sp_ylm_conditional_inclinations": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V, _V, _V, _V,
+                                             _I, _V, _V]),
+    "sp_ylm_inclination_samples": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "sp_temporal_gram": (_I, [_V, _I, _V, _D, _I, _V, _L, _V, _V]),
     "sp_ylm_temporal_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_temporal": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _V, _V, _V, _V]),

@@ -528,6 +528,18 @@ void ic_lds_opt_in(const void *fn, size_t lds) {
 
 }  // namespace
 
+SpInclModel sp_incl_model_views(const sp_handle *h, int S, int M, int ntab, int B, int P, void *workspace_dev) {
+  const InclLayout Ly = incl_layout(h, S, M, ntab, B, P);
+  SpInclModel v;
+  v.plan = at<double>(workspace_dev, Ly.plan);
+  v.V = at<double>(workspace_dev, Ly.V);
+  v.Mm = at<double>(workspace_dev, Ly.Mm);
+  v.cm = at<double>(workspace_dev, Ly.cm);
+  v.SigRt = at<double>(workspace_dev, Ly.sig) + (size_t)B * h->N * h->N;
+  v.pstride = incl_pstride(2 * h->ydeg + 1, M);
+  return v;
+}
+
 extern "C" {
 
 size_t sp_incl_plan_bytes(sp_handle *h, int S, int M) {

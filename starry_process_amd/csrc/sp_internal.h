@@ -441,6 +441,14 @@ int sp_launch_gemm_nt(const double *A, long lda, long strideA, const double *B,
 // the diagonal are read.  info [batch] (device, or null): a matrix with info[b] != 0 is filled with NaN instead
 int sp_launch_mirror_lower(double *out, int n, long ldo, long strideOut, int batch, hipStream_t st,
                            const int32_t *info = nullptr);
+// sp_incl.hip: what the model stage of sp_lnlike_inclinations_planned leaves in its workspace (S, M, ntab, B, P as in
+// that call), for the map posterior on the same grid (sp_ylm_incl.hip): plan [S] (stride pstride doubles),
+// V [P][ntab][N] = rTA1 . Rx(-i), Mm [B][ntab][P][n][n], cm [B][ntab][P][n], SigRt [B][N][N] = Sigma_y R^T
+struct SpInclModel {
+  const double *plan, *V, *Mm, *cm, *SigRt;
+  long pstride;
+};
+SpInclModel sp_incl_model_views(const sp_handle *h, int S, int M, int ntab, int B, int P, void *workspace_dev);
 // sp_ylm_temporal_cond.hip: the C ABI's posterior maps of a time-variable process (include/starry_process_amd.h)
 extern "C" {
 size_t sp_ylm_conditional_temporal_workspace_bytes(sp_handle *h, int K, int T, int R, int with_cov);

@@ -992,6 +992,60 @@ class Engine(object):
             int(norm_order), float(zmax), self._p(out), self._p(status), self._p(ws), self._stream()))
         return out, status
 
+    # -- surface-map posteriors with the inclination marginalised (sp_ylm_conditional_inclinations) ------
+    def ylm_conditional_inclinations(self, t, flux, stars, rta1, mean_ylm, cov_ylm, inc_rad, logprior, diag=None,
+                                     with_cov=True, with_inc=False, nsamples=0):
+        """Mixture over P grid inclinations of the map posteriors of S stars, one device call: t, flux [S, K], stars
+        (host sp_star records; inc is not read), rta1 [ntab, N], mean_ylm [N], cov_ylm [N, N], inc_rad [P],
+        logprior [P] (log prior weight of each grid point; -inf: weight 0), diag [S, K] or None.
+        Returns (pinc [S, P], ymu [S, N], ycov [S, N, N] or None, ymu_inc [S, P, N] or None, status [S], state);
+        ``state`` is what ylm_inclination_samples needs for up to ``nsamples`` draws per star."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        S, K = flux.shape
+        sd = self.stars_to_device(stars)
+        rta1 = self.f64(rta1).reshape(-1, self.N)
+        ntab = int(rta1.shape[0])
+        mean_ylm = self.f64(mean_ylm).reshape(self.N)
+        cov_ylm = self.f64(cov_ylm).reshape(self.N, self.N)
+        inc = self.f64(np.asarray(inc_rad, dtype=np.float64).reshape(-1))
+        lp = self.f64(np.asarray(logprior, dtype=np.float64).reshape(-1))
+        P, ns = int(inc.shape[0]), int(nsamples)
+        if lp.shape[0] != P:
+            raise ValueError("logprior must hold one value per inclination")
+        diag = None if diag is None else self.f64(diag)
+        pinc, ymu = self.empty(S, P), self.empty(S, self.N)
+        ycov = self.empty(S, self.N, self.N) if with_cov else None
+        ymui = self.empty(S, P, self.N) if with_inc else None
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S == 0:
+            return pinc, ymu, ycov, ymui, status, None
+        nbytes = self._L.sp_ylm_conditional_inclinations_workspace_bytes(self._h, S, ntab, P, int(bool(with_cov)), ns)
+        ws = self._scratch(max(int(nbytes), 1))
+        check(self._L.sp_ylm_conditional_inclinations(
+            self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(rta1), ntab,
+            self._p(mean_ylm), self._p(cov_ylm), P, self._p(inc), self._p(lp), self._p(pinc), self._p(ymu),
+            self._p(ycov), self._p(ymui), self._p(status), ns, self._p(ws), self._stream()))
+        state = {"ws": ws, "S": S, "ntab": ntab, "P": P, "ns": ns, "stars": sd, "mean_ylm": mean_ylm}
+        return pinc, ymu, ycov, ymui, status, state
+
+    def ylm_inclination_samples(self, state, cho_ylm, comp, z, e):
+        """Samples of the mixture by pathwise conditioning (sp_ylm_inclination_samples): ``state`` from
+        ylm_conditional_inclinations, cho_ylm [N, N] the lower factor of Sigma_y, comp [S, ns] the component of each
+        sample, z [S, ns, N] and e [S, ns, 2 ydeg + 1] standard normal deviates.  Returns y [S, ns, N]."""
+        S, n = state["S"], 2 * self.ydeg + 1
+        comp = self.dev(np.ascontiguousarray(np.asarray(comp, dtype=np.int32).reshape(S, -1)))
+        ns = int(comp.shape[1])
+        if ns > state["ns"]:
+            raise ValueError("the posterior was computed for at most %d samples per star" % state["ns"])
+        z, e = self.f64(z).reshape(S, ns, self.N), self.f64(e).reshape(S, ns, n)
+        y = self.empty(S, ns, self.N)
+        check(self._L.sp_ylm_inclination_samples(
+            self._h, S, state["ntab"], state["P"], ns, self._p(state["stars"]), self._p(state["mean_ylm"]),
+            self._p(self.f64(cho_ylm)), self._p(comp), self._p(z), self._p(e), self._p(y), self._p(state["ws"]),
+            self._stream()))
+        return y
+
     # -- fused likelihood ----------------------------------------------------------
     def workspace(self, S, K, M):
         nbytes = self._L.sp_lnlike_workspace_bytes(self._h, S, K, M)

@@ -1090,6 +1090,242 @@ class StarryProcess(object):
                                        stars["baseline_var"][s_])
         return Eager(out)
 
+    # -- surface maps with the inclination marginalised on a grid ------------------------------------
+    # The posterior of the map when the inclination is unknown: the mixture of the conditional Gaussians of
+    # ylm_conditional over the grid `inc`, weighted by pinc_j ~ prior_j exp(lnL_j) with lnL_j the value
+    # log_likelihood_inclinations returns.  (As in the reference that likelihood subtracts the scalar flux mean, the
+    # map posterior A mu_y; the two are kept as they are.)  One device call forms every component as a rank-(2 ydeg + 1)
+    # downdate of the prior (sp_ylm_conditional_inclinations); a star that route cannot take (SP_STAR_NO_BASIS: a
+    # variance <= 0, too few distinct phases, too little of the rotation covered) takes the dense route below.
+    @staticmethod
+    def _inc_prior_weights(inc, inc_weights):
+        """Prior weight of each grid inclination (degrees): ``inc_weights`` if given (non-negative, (P,)), else
+        sin(i_j) times the trapezoid width of grid point j (half intervals at the ends; 1 for a single point), which
+        needs a strictly increasing grid."""
+        P = inc.shape[0]
+        if inc_weights is not None:
+            w = np.asarray(inc_weights, dtype=np.float64).reshape(-1)
+            if w.shape != (P,):
+                raise ValueError("`inc_weights` must hold one weight per inclination")
+            if not np.all(np.isfinite(w)) or np.any(w < 0) or not np.any(w > 0):
+                raise ValueError("`inc_weights` must be finite, non-negative and not all zero")
+            return w
+        if P == 1:
+            width = np.ones(1)
+        else:
+            d = np.diff(inc)
+            if not np.all(d > 0):
+                raise ValueError("the default prior sin(i) di needs a strictly increasing `inc`; pass `inc_weights`")
+            width = np.empty(P)
+            width[0], width[-1] = 0.5 * d[0], 0.5 * d[-1]
+            width[1:-1] = 0.5 * (d[:-1] + d[1:])
+        return np.maximum(np.sin(inc * np.pi / 180), 0.0) * width
+
+    @staticmethod
+    def _log_weights(w):
+        with np.errstate(divide="ignore"):
+            return np.log(w)
+
+    @staticmethod
+    def _mixture_components(pinc, u):
+        """Component of each sample, pinc (S, P) and u (S, ns): searchsorted(cumsum(pinc_s), u_s) clipped to P - 1."""
+        j = np.array([np.searchsorted(np.cumsum(w), x) for w, x in zip(pinc, u)]).reshape(u.shape)
+        return np.minimum(j, pinc.shape[-1] - 1).astype(np.int32)
+
+    def _marginal_deviates(self, S, nsamples, seed):
+        """(u, z, e) of the mixture's samples, drawn in this order from one RandomState."""
+        rs = self._rng(seed)
+        u = rs.rand(S, nsamples)
+        z = rs.normal(size=(S, nsamples, self._nylm))
+        e = rs.normal(size=(S, nsamples, 2 * self._ydeg + 1))
+        return u, z, e
+
+    def _ylm_marginal_dense(self, t, flux, data_cov, inc, logw, p, u, baseline_mean, baseline_var, return_cov=True,
+                            comp=None, z=None, chunk=16):
+        """The mixture for one star by the dense route: ylm_conditional on (star x inclination) pseudo-stars in chunks,
+        weights from the dense route of log_likelihood_inclinations, the mixture formed with torch on the device.
+        Returns device tensors (pinc (P,), ymu (N,), ycov (N, N) or None, ymu_inc (P, N)) and, with ``comp`` (ns,) and
+        ``z`` (ns, N), the samples ymu_j + cho(ycov_j) z (ns, N) as a fifth value."""
+        import torch
+
+        e = self._engine
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        K, P, N = t.shape[0], inc.shape[0], self._nylm
+        data_cov = np.asarray(data_cov, dtype=np.float64)
+        lnl = self._incl_dense(t, np.asarray(flux, dtype=np.float64)[None, :], data_cov, inc, p, u,
+                               np.asarray(baseline_mean, dtype=np.float64), np.asarray(baseline_var, dtype=np.float64))
+        lw = np.asarray(logw, dtype=np.float64) + lnl
+        ok = np.isfinite(lw)
+        pinc = np.zeros(P)
+        if ok.any():
+            pinc[ok] = np.exp(lw[ok] - lw[ok].max())
+            pinc /= pinc.sum()
+        else:
+            pinc[:] = np.nan
+        w = e.f64(pinc)
+        positive = bool(np.all(data_cov > 0))
+
+        def components(jj, with_cho):
+            n = len(jj)
+            if positive:
+                stars = make_stars(n, period=p, inc_deg=inc[jj], baseline_var=float(baseline_var),
+                                   baseline_mean=float(baseline_mean),
+                                   data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
+                stars["table"][:] = 0
+                diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (n, K))
+                sinv, sinvmu = self._ylm_precision()
+                m, c, l, _ = e.ylm_conditional(np.broadcast_to(t, (n, K)), np.broadcast_to(flux, (n, K)), stars,
+                                               self._flux._rta1(u), sinv, sinvmu, diag=diag, with_cho=with_cho)
+                return m, c, l
+            out = [self._ylm_posterior(t, flux, data_cov, inc[j], p, u, baseline_mean, baseline_var, with_cho, full=True)
+                   for j in jj]
+            return (torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out]),
+                    torch.stack([o[2] for o in out]) if with_cho else None)
+
+        ymui = e.empty(P, N)
+        cbar = torch.zeros(N, N, dtype=torch.float64, device=e.device) if return_cov else None
+        for c0 in range(0, P, chunk):
+            jj = np.arange(c0, min(P, c0 + chunk))
+            m, c, _ = components(jj, False)
+            ymui[c0:c0 + len(jj)] = m
+            if return_cov:
+                for k, j in enumerate(jj):
+                    if pinc[j] > 0:
+                        cbar += w[j] * c[k]
+        use = torch.nonzero(w > 0).reshape(-1)
+        ymu = (w[use, None] * ymui[use]).sum(0) if ok.any() else torch.full_like(ymui[0], float("nan"))
+        ycov = None
+        if return_cov:
+            d = ymui[use] - ymu[None, :]
+            ycov = cbar + (w[use, None] * d).T @ d
+            ycov = 0.5 * (ycov + ycov.T)
+            if not ok.any():
+                ycov = torch.full_like(ycov, float("nan"))
+        out = (w, ymu, ycov, ymui)
+        if comp is not None:
+            comp = np.asarray(comp).reshape(-1)
+            y = e.empty(comp.shape[0], N)
+            zd = e.f64(z).reshape(comp.shape[0], N)
+            for j in np.unique(comp):
+                m, _, l = components(np.array([j]), True)
+                rows = np.nonzero(comp == j)[0]
+                y[rows] = m[0][None, :] + zd[rows] @ l[0].T
+            out = out + (y,)
+        return out
+
+    def _ylm_marginal(self, t, flux, stars, utab, diag, inc, logw, return_cov, nsamples, seed, with_inc=False):
+        """The mixtures of S stars: the basis route in one device call, the stars it flags by the dense route.
+        Device tensors (pinc [S, P], ymu [S, N], ycov [S, N, N] or None, ymu_inc [S, P, N] or None), then the
+        samples y [S, ns, N] (device) and their inclinations (host, degrees), or None, None."""
+        from ._lib import SP_STAR_NO_BASIS
+
+        e = self._engine
+        S, P = flux.shape[0], inc.shape[0]
+        mu, cov = self._moments_dev()
+        pinc, ymu, ycov, ymui, status, state = e.ylm_conditional_inclinations(
+            t, flux, stars, e.rTA1L(utab), mu, cov, inc * (np.pi / 180), logw, diag=diag, with_cov=return_cov,
+            with_inc=with_inc, nsamples=nsamples)
+        dense = np.nonzero(status.cpu().numpy() & SP_STAR_NO_BASIS)[0] if S else []
+
+        def star_args(s_):
+            dc = diag[s_] if diag is not None else stars["data_var"][s_]
+            return (t[s_], flux[s_], dc, inc, logw, stars["period"][s_], utab[stars["table"][s_]],
+                    stars["baseline_mean"][s_], stars["baseline_var"][s_])
+
+        for s_ in dense:
+            w1, m1, c1, mi1 = self._ylm_marginal_dense(*star_args(s_), return_cov=return_cov)
+            pinc[s_], ymu[s_] = w1, m1
+            if return_cov:
+                ycov[s_] = c1
+            if with_inc:
+                ymui[s_] = mi1
+        if nsamples <= 0 or S == 0:
+            return pinc, ymu, ycov, ymui, None, None
+        u, z, dev = self._marginal_deviates(S, nsamples, seed)
+        ph = pinc.cpu().numpy()
+        comp = self._mixture_components(np.where(np.isfinite(ph), ph, 0.0), u)
+        y = e.ylm_inclination_samples(state, self._cho_ylm_dev(), comp, z, dev)
+        for s_ in dense:
+            y[s_] = self._ylm_marginal_dense(*star_args(s_), return_cov=False, comp=comp[s_], z=z[s_])[4]
+        return pinc, ymu, ycov, ymui, y, inc[comp]
+
+    def _ylm_marginal_single(self, t, flux, data_cov, inc, p, u, baseline_mean, baseline_var, inc_weights, return_cov,
+                             nsamples, seed):
+        self._ylm_check()
+        if np.ndim(data_cov) > 1 or np.ndim(baseline_var) > 0:
+            raise NotImplementedError("a full data covariance is not implemented for the marginal map posterior; "
+                                      "use ylm_conditional at each inclination")
+        inc = self._check_inc(inc)
+        logw = self._log_weights(self._inc_prior_weights(inc, inc_weights))
+        t, _, p, u = self._flux._ingest(t, 60.0, p, u)
+        flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
+        if flux.shape[1] != t.shape[0]:
+            raise ValueError("`flux` must have one value per time")
+        dc = np.asarray(data_cov, dtype=np.float64)
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, dc if dc.ndim == 0 else dc[None, :], None, p, u,
+                                                         baseline_mean, baseline_var)
+        return self._ylm_marginal(t, flux, stars, utab, diag, inc, logw, return_cov, int(nsamples), seed)
+
+    def ylm_conditional_marginal(self, t, flux, data_cov, inc=np.linspace(0, 90, 100), p=defaults["p"],
+                                 u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                                 baseline_var=defaults["baseline_var"], inc_weights=None, return_cov=True):
+        """The surface map's posterior with the inclination marginalised on the grid ``inc`` (degrees): mean (nylm,),
+        covariance (nylm, nylm) and ``pinc`` (P,), the posterior weight of each grid inclination (sums to 1); with
+        ``return_cov=False`` only (ymu, pinc).  The posterior is the mixture of ``ylm_conditional`` over the grid:
+        ymu = sum_j pinc_j ymu_j, ycov = sum_j pinc_j (ycov_j + (ymu_j - ymu)(ymu_j - ymu)^T), with
+        pinc_j ~ prior_j exp(log_likelihood_inclinations_j).  The prior weight of grid point j is ``inc_weights[j]``
+        (non-negative) or, by default, sin(i_j) times the trapezoid width of the point (an isotropic orientation; the
+        grid must then increase strictly).  ``data_cov`` is a scalar or a vector of variances; a full matrix raises
+        NotImplementedError (use ``ylm_conditional`` per inclination).  Not implemented for normalized or
+        time-variable processes."""
+        pinc, ymu, ycov, _, _, _ = self._ylm_marginal_single(t, flux, data_cov, inc, p, u, baseline_mean, baseline_var,
+                                                             inc_weights, return_cov, 0, None)
+        if return_cov:
+            return Eager(ymu[0].cpu().numpy()), Eager(ycov[0].cpu().numpy()), Eager(pinc[0].cpu().numpy())
+        return Eager(ymu[0].cpu().numpy()), Eager(pinc[0].cpu().numpy())
+
+    def sample_ylm_conditional_marginal(self, t, flux, data_cov, inc=np.linspace(0, 90, 100), p=defaults["p"],
+                                        u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                                        baseline_var=defaults["baseline_var"], inc_weights=None, nsamples=1, seed=None):
+        """Samples of the surface map given the light curve with the inclination marginalised: (y (nsamples, nylm),
+        inc_deg (nsamples,)), the map and the grid inclination it was drawn at.  The deviates come from one
+        ``RandomState(seed)`` (the constructor's ``seed`` when None) in this order: ``u = rand(nsamples)`` chooses the
+        components, j = searchsorted(cumsum(pinc), u) clipped to P - 1; ``z = normal(size=(nsamples, nylm))``;
+        ``e = normal(size=(nsamples, 2 ydeg + 1))``.  Each sample is y0 + U_j^T (Z_j (hhat - B_j y0) - L_H,j^-1 e)
+        with y0 = mean_ylm + cho_cov_ylm z (pathwise conditioning).  A light curve only the dense route
+        can take is sampled as ymu_j + cho(ycov_j) z."""
+        _, _, _, _, y, inc_s = self._ylm_marginal_single(t, flux, data_cov, inc, p, u, baseline_mean, baseline_var,
+                                                         inc_weights, False, int(nsamples), seed)
+        if y is None:
+            return Eager(np.empty((0, self._nylm))), Eager(np.empty(0))
+        return Eager(y[0].cpu().numpy()), Eager(inc_s[0])
+
+    def ylm_conditional_marginal_ensemble(self, t, flux, data_cov, inc=np.linspace(0, 90, 100), p=None, u=None,
+                                          baseline_mean=0.0, baseline_var=0.0, inc_weights=None, return_cov=True,
+                                          nsamples=0, seed=None):
+        """``ylm_conditional_marginal`` of S stars in one device call, one grid for all stars.
+
+        t: (K,) or (S, K); flux: (S, K); data_cov: scalar, (S,) or (S, K); p: scalar or (S,); u: (udeg,) shared or
+        (S, udeg); baseline_mean, baseline_var: scalars or (S,).
+        Returns (ymu (S, nylm), ycov (S, nylm, nylm), pinc (S, P)) -- (ymu, pinc) with ``return_cov=False`` -- and, with
+        nsamples > 0, also y (S, nsamples, nylm) and inc_deg (S, nsamples), drawn as sample_ylm_conditional_marginal
+        does with a leading S axis on every deviate: rand(S, nsamples), normal(size=(S, nsamples, nylm)),
+        normal(size=(S, nsamples, 2 ydeg + 1))."""
+        self._ylm_check()
+        if np.ndim(data_cov) > 2:
+            raise NotImplementedError("a full data covariance is not implemented for the marginal map posterior; "
+                                      "use ylm_conditional at each inclination")
+        inc = self._check_inc(inc)
+        logw = self._log_weights(self._inc_prior_weights(inc, inc_weights))
+        t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, None, p, u, baseline_mean, baseline_var)
+        pinc, ymu, ycov, _, y, inc_s = self._ylm_marginal(t, flux, stars, utab, diag, inc, logw, return_cov,
+                                                          int(nsamples), seed)
+        out = (Eager(ymu.cpu().numpy()),) + ((Eager(ycov.cpu().numpy()),) if return_cov else ())
+        out = out + (Eager(pinc.cpu().numpy()),)
+        if y is not None:
+            out = out + (Eager(y.cpu().numpy()), Eager(inc_s))
+        return out
+
 
 class StarryProcessSum(StarryProcess):
     """Sum of independent processes (several spot populations on one star): the moments of
