@@ -722,6 +722,19 @@ int sp_pixel_transform(sp_handle *h, int npts, const double *xyz_dev, double *M_
 size_t sp_pixel_cov_workspace_bytes(sp_handle *h, int S, int npts);
 int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, long ldm, const double *cov_dev,
                          long strideCov, double *out_dev, long ldo, long strideOut, void *workspace_dev, void *stream);
+/* S per-pixel variance maps out[s][p] = sum_ij M[p][i] cov[s][i][j] M[p][j], the diagonal of sp_pixel_cov_batched's
+ * out[s], without forming it or the product M cov[s] in memory: no workspace.  cov_dev [S, N, N] (row stride N,
+ * strideCov >= N N doubles apart; read as given, both triangles: the quadratic form of a matrix that is symmetric
+ * only to rounding is that of its symmetric part), out_dev [S, npts] (strideOut >= npts doubles apart), written
+ * once and never read.  A NaN row of M gives NaN in that pixel of every map and touches no other pixel; a NaN in
+ * cov[s] stays in out[s].  A pixel's bits do not depend on the other rows of M, on S or on s.  S = 0 is SP_OK and
+ * touches nothing.
+ * LIMIT: the kernel keeps a 32-row block of M in LDS, which holds it up to ydeg = SP_PIXEL_VAR_MAX_YDEG (N = 441).
+ * One kernel serves every N up to that and every npts; a handle of a higher degree is refused with
+ * SP_ERR_INVALID before anything else is looked at (sp_pixel_cov_batched serves those degrees).                 */
+#define SP_PIXEL_VAR_MAX_YDEG 20
+int sp_pixel_var_batched(sp_handle *h, int S, int npts, const double *M_dev, long ldm, const double *cov_dev,
+                         long strideCov, double *out_dev, long strideOut, void *stream);
 /* nmaps images out[i] = M y[i] (sp.py:1229-1231, tensordot(M, y^T)): y_dev [nmaps, N], out_dev [nmaps, npix]
  * (contiguous), M [npix, N] with row stride ldm.  unit_background != 0 adds 1 to y[i][0] first (sp.py:1225-1228),
  * i.e. M[:, 0] to the image: 1 on the grid and NaN off it.  out is written, never read.  The packed copy of y

@@ -112,6 +112,7 @@ PROTOTYPES = {
     "sp_pixel_transform": (_I, [_V, _I, _V, _V, _L, _V, _V]),
     "sp_pixel_cov_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_pixel_cov_batched": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _L, _L, _V, _V]),
+    "sp_pixel_var_batched": (_I, [_V, _I, _I, _V, _L, _V, _L, _V, _L, _V]),
     "sp_pixel_render": (_I, [_V, _I, _I, _V, _V, _L, _I, _V, _V]),
     "sp_lnlike_inclinations_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
     "sp_lnlike_inclinations": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _I, _V, _I, _V, _I, _I, _D,

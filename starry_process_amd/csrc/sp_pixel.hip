@@ -11,7 +11,9 @@
 //   sp_launch_gemm_nt   M = pi pT (A1^T)^T on the fp64 matrix cores (sp_mm.h / sp_gemm.hip)
 //   pixel_pack_kernel   Y [nmaps, Kp] with y_0 + 1 for a unit background, zero beyond N; then one product
 //   pixel_mirror_kernel the upper triangle of cov_pix from its lower one: exactly symmetric
+//   pixel_var_kernel    diag(M Sigma_b M^T) for a stack of covariances: M Sigma_b in accumulators only
 // DESIGN.md section 10 gives the reasons for this split.
+#include <atomic>
 #include <cmath>
 
 #include "sp_internal.h"
@@ -192,6 +194,201 @@ int sp_pixel_cov_batched(sp_handle *h, int S, int npts, const double *M_dev, lon
                               st)))
     return rc;
   return sp_launch_mirror_lower(out_dev, npts, ldo, strideOut, S, st);
+}
+
+// ---- per-pixel variances: out[b][p] = sum_ij M[p][i] cov_b[i][j] M[p][j] ------------------------------------------
+// The product T = M cov_b on the fp64 matrix cores with the row-wise dot against M as its epilogue: T lives in
+// accumulators only.  One workgroup (eight wavefronts, two per SIMD) per (PV_BM pixel rows, covariance):
+//   * the row block of M goes to LDS once, zero beyond npts and beyond N (columns up to a multiple of PV_JW), and is
+//     both the A operand of every product and the factor of the epilogue;
+//   * cov is walked in panels of PV_JW columns; wavefront w owns the 16 columns 16 (4 J + (w & 3)) of panel J for the
+//     16-row tile w >> 2 of the block: while one wavefront of a SIMD handles slice traffic, the other's MFMAs run.
+//     A panel is streamed in slices of PV_BK rows; a slice travels memory -> registers (loaded ahead of its use by
+//     plain loads) -> LDS (one slice ahead of the one being multiplied; two LDS buffers, one barrier per slice),
+//     zero beyond N.
+//     cov is read as it stands, both triangles: the symmetry is not used, because the posteriors this is made for
+//     (ycov = cho_solve(W, I) of sp_ylm_conditional_batched) are symmetric only to rounding, and the quadratic form
+//     of the matrix as given is what a caller can check;
+//   * at a panel's end the accumulator is multiplied elementwise with M's tile and added to four row sums per
+//     lane; after the last panel those are summed over the 16 lanes of a row (butterfly), then over the four
+//     wavefronts through LDS in a fixed order, and stored: one writer per output, nothing read back.
+// The order of every sum depends on N alone: a pixel's bits do not depend on its neighbours, its position in the
+// block (rows of an MFMA are independent), the covariance's place in a stack, or the run.
+namespace {
+
+constexpr int PV_BM = 32, PV_JW = 64, PV_BK = 32, PV_LDS = PV_JW + 16;   // (slice rows 80 doubles apart: the two
+                                                                         //  k rows of a 32-lane read on disjoint banks)
+constexpr int PV_SLICE = PV_BK * PV_LDS;
+// row stride of the M block: odd, so the 16 rows of a fragment read (which the compiler pairs into ds_read2_b64: groups
+// of 16 lanes on 32 banks) fall on 16 distinct bank pairs
+__host__ __device__ constexpr int pv_ldm(int N) { return ((N + PV_JW - 1) / PV_JW) * PV_JW + 1; }
+constexpr size_t pv_lds_bytes(int N) { return sizeof(double) * ((size_t)PV_BM * pv_ldm(N) + 2 * PV_SLICE); }
+// The whole row block of M sits in LDS, so the degree is bounded: ydeg 20 takes 32 x 449 + 2 x 2560 doubles = 155 904
+// bytes of the 160 KiB, ydeg 21 (N = 484) would take 172 288.  sp_pixel_var_batched refuses handles above the bound.
+constexpr int PV_MAX_N = (SP_PIXEL_VAR_MAX_YDEG + 1) * (SP_PIXEL_VAR_MAX_YDEG + 1);
+static_assert(pv_lds_bytes(PV_MAX_N) <= 160 * 1024, "the row block of M at the largest degree served must fit LDS");
+static_assert(pv_lds_bytes((SP_PIXEL_VAR_MAX_YDEG + 2) * (SP_PIXEL_VAR_MAX_YDEG + 2)) > 160 * 1024,
+              "SP_PIXEL_VAR_MAX_YDEG is the largest degree that fits");
+
+typedef double pv_d4 __attribute__((ext_vector_type(4)));
+
+// the slice (rows i0 .., columns j0 ..) of cov, this thread's four entries: column tid & 63, rows (tid >> 6) + 8 q.
+// Every load is unconditional (an entry beyond N reads cov[0]) and nothing is done with its value here: it stays in
+// flight until pv_store -- two slices later in the source; the compiler's wait, carried round the loop, also covers the
+// younger slice, so in effect one slice later -- puts it, or zero beyond N, into LDS.  (Hand-counted waits around
+// inline-assembly loads were measured: 1.5 % faster, not worth code that no tool checks.)
+// (entries Q0 .. Q1 - 1: a turn issues a slice in two halves; N N < 2^31)
+template <int Q0 = 0, int Q1 = 4>
+__device__ __forceinline__ void pv_load(const double *__restrict__ C, int N, int i0, int j0, double (&v)[4]) {
+  const int j = j0 + ((int)threadIdx.x & 63);
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    const int i = i0 + ((int)threadIdx.x >> 6) + 8 * q;
+    v[q] = C[(i < N && j < N) ? i * N + j : 0];
+  }
+}
+__device__ __forceinline__ void pv_store(double *S, int N, int i0, int j0, const double (&v)[4]) {
+  const int c = (int)threadIdx.x & 63, j = j0 + c;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = ((int)threadIdx.x >> 6) + 8 * q;
+    S[r * PV_LDS + c] = (i0 + r < N && j < N) ? v[q] : 0.0;
+  }
+}
+// the fragments of two MFMA k-steps (8 rows of a slice): a[ks] of M's row tile, b[ks] of the slice
+struct PvFrag {
+  double a[2], b[2];
+};
+__device__ __forceinline__ void pv_fetch(const double *Ma, int LDM, const double *Sb, int g, PvFrag &f) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) {
+    f.b[ks] = Sb[(8 * g + 4 * ks) * PV_LDS];
+    f.a[ks] = Ma[8 * g + 4 * ks];
+  }
+}
+__device__ __forceinline__ void pv_mma(const PvFrag &f, pv_d4 &acc) {
+#pragma unroll
+  for (int ks = 0; ks < 2; ++ks) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(f.a[ks], f.b[ks], acc, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(512) void pixel_var_kernel(int npts, int N, const double *__restrict__ M, long ldm,
+                                                        const double *__restrict__ cov, long strideCov,
+                                                        double *__restrict__ out, long strideOut) {
+  extern __shared__ double pv_lds[];
+  const int LDM = pv_ldm(N), Np = LDM - 1, KS = Np / PV_BK, total = (Np / PV_JW) * KS;   // (KS and total are even)
+  double *Ms = pv_lds, *Sl = pv_lds + PV_BM * LDM;
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int fr = lane & 15, fq = lane >> 4, wc = w & 3, wr = w >> 2;   // this wavefront's column and row tile
+  const long p0 = (long)blockIdx.x * PV_BM;
+  const double *C = cov + (size_t)blockIdx.y * strideCov;
+
+  // slice s of the walk is rows 32 (s mod KS) .. of panel s / KS.  Slices of odd s travel through v1, of even s
+  // through v0: a slice is loaded three turns before it is multiplied and stored to LDS one turn before.  Past the
+  // last slice the walk goes on into panels beyond N: every entry reads cov[0] and is stored as zero into a buffer
+  // nobody reads, so that each turn is the same straight line
+  double v0[4], v1[4];
+  pv_load(C, N, 0, 0, v0);
+  pv_load(C, N, PV_BK, 0, v1);
+  // the row block of M: four rows per wavefront, 256 columns at a time, the 16 loads in flight together.  A chunk of
+  // 64 columns past the padded width repeats the last one (the same values to the same place): every load is used, so
+  // none is left pending for the compiler to wait for inside the main loop
+  for (int c0 = 0; c0 < Np; c0 += 256) {
+    double t[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = (c0 + 64 * u < Np ? c0 + 64 * u : Np - 64) + lane;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const long p = p0 + w + 8 * q;
+        t[u][q] = M[(size_t)p0 * ldm + ((p < npts && c < N) ? (size_t)(p - p0) * ldm + c : 0)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int c = (c0 + 64 * u < Np ? c0 + 64 * u : Np - 64) + lane;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Ms[(w + 8 * q) * LDM + c] = (p0 + w + 8 * q < npts && c < N) ? t[u][q] : 0.0;
+    }
+  }
+  pv_store(Sl, N, 0, 0, v0);
+  pv_load(C, N, PV_BK * (2 % KS), PV_JW * (2 / KS), v0);
+  __syncthreads();
+
+  pv_d4 acc = pv_d4{0, 0, 0, 0};
+  double part[4] = {0.0, 0.0, 0.0, 0.0};
+  // one turn: slice s + 1 from its registers to the LDS buffer that slice s - 1 has left (the barrier that ended the
+  // previous turn), slice s + 3 on its way into those registers, slice s multiplied
+  auto turn = [&](int s, double (&v)[4]) {
+    const int J = s / KS, k = s - J * KS, ct = 4 * J + wc;
+    const int i3 = PV_BK * ((s + 3) % KS), j3 = PV_JW * ((s + 3) / KS);
+    const double *Ma = Ms + (16 * wr + fr) * LDM + PV_BK * k + fq;
+    const double *Sb = Sl + (s & 1) * PV_SLICE + fq * PV_LDS + 16 * wc + fr;
+    // acc += Mblock[16 wr .., slice rows] slice[.., 16 wc ..]: 8 k-steps, two at a time, the fragments of the next
+    // two read ahead of the MFMAs of the current two.  The slice traffic is written between the pairs of MFMAs; that
+    // is a hint, not a guarantee: the compiler is free to move the MFMAs across it, and does
+    PvFrag f0, f1;
+    pv_fetch(Ma, LDM, Sb, 0, f0);
+    pv_fetch(Ma, LDM, Sb, 1, f1);
+    pv_mma(f0, acc);
+    pv_store(Sl + ((s + 1) & 1) * PV_SLICE, N, PV_BK * ((s + 1) % KS), PV_JW * ((s + 1) / KS), v);
+    pv_fetch(Ma, LDM, Sb, 2, f0);
+    pv_mma(f1, acc);
+    pv_load<0, 2>(C, N, i3, j3, v);
+    pv_fetch(Ma, LDM, Sb, 3, f1);
+    pv_mma(f0, acc);
+    pv_load<2, 4>(C, N, i3, j3, v);
+    pv_mma(f1, acc);
+    if (k == KS - 1) {           // the panel's epilogue: (T . M) row sums
+#pragma unroll
+      for (int r = 0; r < 4; ++r) part[r] = part[r] + acc[r] * Ms[(16 * wr + fq + 4 * r) * LDM + 16 * ct + fr];
+      acc = pv_d4{0, 0, 0, 0};
+    }
+    __syncthreads();
+  };
+  for (int s = 0; s < total; s += 2) {
+    turn(s, v1);
+    turn(s + 1, v0);
+  }
+  // rows: over the 16 lanes that share fq, then over the four wavefronts of a row tile (every slice buffer is free:
+  // the barrier above)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double x = part[r];
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) x = x + __shfl_xor(x, off, 64);
+    if (fr == 0) Sl[wc * PV_BM + 16 * wr + fq + 4 * r] = x;
+  }
+  __syncthreads();
+  if (tid < PV_BM && p0 + tid < npts)
+    out[(size_t)blockIdx.y * strideOut + p0 + tid] =
+        ((Sl[tid] + Sl[PV_BM + tid]) + Sl[2 * PV_BM + tid]) + Sl[3 * PV_BM + tid];
+}
+
+}  // namespace
+
+int sp_pixel_var_batched(sp_handle *h, int S, int npts, const double *M_dev, long ldm, const double *cov_dev,
+                         long strideCov, double *out_dev, long strideOut, void *stream) {
+  // (a degree whose row block of M does not fit LDS is refused before anything else, host-only handles included)
+  if (h && h->ydeg > SP_PIXEL_VAR_MAX_YDEG) return SP_ERR_INVALID;
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || S > 65535 || npts < 1 || !M_dev || ldm < h->N || !cov_dev || !out_dev ||
+      (S > 1 && (strideCov < (long)h->N * h->N || strideOut < npts)))
+    return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  const size_t lds = pv_lds_bytes(h->N);
+  // more than 64 KiB of dynamic LDS needs an opt-in: once per device, for the largest degree served
+  static std::atomic<unsigned long long> opted{0};
+  const unsigned long long bit = 1ull << (h->device & 63);
+  if (!(opted.load(std::memory_order_relaxed) & bit)) {
+    SP_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pixel_var_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pv_lds_bytes(PV_MAX_N)));
+    opted.fetch_or(bit, std::memory_order_relaxed);
+  }
+  const dim3 grid((unsigned)((npts + PV_BM - 1) / PV_BM), S);
+  hipLaunchKernelGGL(pixel_var_kernel, grid, dim3(512), lds, (hipStream_t)stream, npts, h->N, M_dev, ldm, cov_dev,
+                     strideCov, out_dev, strideOut);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
 }
 
 int sp_pixel_render(sp_handle *h, int nmaps, int npix, const double *y_dev, const double *M_dev, long ldm,

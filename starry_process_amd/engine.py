@@ -772,6 +772,34 @@ class Engine(object):
                                            npts * npts, self._p(ws), self._stream()))
         return out[0] if single else out
 
+    PIXEL_VAR_BATCH = 65535    # covariances per sp_pixel_var_batched call (a grid dimension)
+    PIXEL_VAR_MAX_YDEG = 20    # SP_PIXEL_VAR_MAX_YDEG: the kernel keeps a row block of M in LDS
+
+    def pixel_var(self, M, cov):
+        """Per-pixel variances diag(M cov M^T) (sp_pixel_var_batched): cov [N, N] -> [npts], or a stack [..., N, N]
+        -> [..., npts] in one call, with neither M cov nor the npts x npts covariance formed in memory.  cov is read
+        as given (both triangles); a tensor on the device is used where it is.  M [npts, N] from pixel_transform.
+        An empty stack [0, N, N] gives an empty result.  ValueError for operands of the wrong shape and for an engine
+        of ydeg > 20 (PIXEL_VAR_MAX_YDEG): the kernel's row block of M does not fit LDS beyond that; the diagonal of
+        pixel_cov serves those degrees."""
+        if self.ydeg > self.PIXEL_VAR_MAX_YDEG:
+            raise ValueError("pixel_var serves ydeg <= %d (its row block of M must fit LDS); this engine has ydeg %d: "
+                             "take the diagonal of pixel_cov instead" % (self.PIXEL_VAR_MAX_YDEG, self.ydeg))
+        M, cov = self.f64(M), self.f64(cov)
+        N = self.N
+        if M.dim() != 2 or M.shape[1] != N or M.shape[0] < 1 or cov.dim() < 2 or tuple(cov.shape[-2:]) != (N, N):
+            raise ValueError("cov must be (..., %d, %d) and M (npts, %d) with npts >= 1" % (N, N, N))
+        npts = int(M.shape[0])
+        lead = tuple(cov.shape[:-2])
+        S = int(np.prod(lead, dtype=np.int64))
+        cov = cov.reshape(S, N, N).contiguous()
+        out = self.empty(S, npts)
+        for s0 in range(0, S, self.PIXEL_VAR_BATCH):
+            n = min(self.PIXEL_VAR_BATCH, S - s0)
+            check(self._L.sp_pixel_var_batched(self._h, n, npts, self._p(M), N, self._p(cov[s0:]), N * N,
+                                               self._p(out[s0:]), npts, self._stream()))
+        return out.reshape(lead + (npts,))
+
     def pixel_render(self, M, y, unit_background=True):
         """Images M y (sp_pixel_render): y [..., N] -> [..., npix]; unit_background adds 1 to y_0 first, i.e. the
         column M[:, 0] (1 on a grid, NaN off it).  M [npix, N] from pixel_transform."""

@@ -460,6 +460,30 @@ class StarryProcess(object):
         M = self._latlon_transform(latlon)
         return Eager(self._engine.pixel_cov(M, self._moments_dev()[1]).cpu().numpy())
 
+    def var_pix(self, latlon, ycov=None):
+        """The variance at lat/lon points in degrees, ``latlon`` of shape (..., 2) as in ``mean_pix``: the diagonal of
+        ``cov_pix(latlon)`` without the npts x npts matrix, shape (npts,).  ``ycov``, a covariance of the Ylm
+        coefficients or a stack of them of shape (..., nylm, nylm) (NumPy or a tensor on the device: what
+        ``ylm_conditional`` and its ensemble / temporal / marginal forms return), replaces the prior's: shape
+        (..., npts).  A posterior variance can round to a tiny negative number; it is returned as computed.
+        Served for ydeg <= 20 (``Engine.pixel_var``); ValueError above, where ``cov_pix`` remains."""
+        M = self._latlon_transform(latlon)
+        cov = self._moments_dev()[1] if ycov is None else ycov
+        return Eager(self._engine.pixel_var(M, cov).cpu().numpy())
+
+    def mollweide_var(self, ycov=None, std=False):
+        """The variance of the surface on the Mollweide grid of ``mollweide``: shape (my, mx) for the prior
+        (``ycov=None``), (..., my, mx) for a covariance or stack ``ycov`` of shape (..., nylm, nylm); NaN off the
+        ellipse.  ``std=True`` returns the standard deviation sqrt(max(var, 0)) instead.  Served for ydeg <= 20, as
+        ``var_pix``."""
+        e = self._engine
+        if self._M is None:
+            self._M = e.pixel_transform(mollweide_grid(self._my, self._mx))
+        var = e.pixel_var(self._M, self._moments_dev()[1] if ycov is None else ycov).cpu().numpy()
+        if std:
+            var = np.sqrt(np.maximum(var, 0.0))      # (NaN stays NaN)
+        return Eager(var.reshape(var.shape[:-1] + (self._my, self._mx)))
+
     def mollweide(self, y, unit_background=True):
         """Mollweide images of the Ylm vectors ``y`` (any shape (..., nylm)): shape (..., my, mx), NaN off the
         ellipse (sp.py:1199-1235).  ``unit_background`` adds 1 to y_0, so an unspotted surface is 1.  The image size
