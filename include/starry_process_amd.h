@@ -595,6 +595,38 @@ int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask /* b
                           double zmax, double *fisher_dev /* [S, P, P] */, double *dcov_dev /* NULL or [S, P, K, K] */,
                           uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- Leave-one-out predictive checks of an ensemble (Rasmussen & Williams 5.4.2), either branch -------------------
+ * For star s, with C_s the covariance the likelihood and the sweeps above factor (marginal branch: conditional == 0,
+ * the kernel tables of the handle's last sp_kernel_table; conditional branch: the star's own inclination, rta1_dev and
+ * the handle's current moments, SP_ERR_STATE without them; normalised or not, temporal kernel, data variances, baseline
+ * variance), r the likelihood's residual, alpha = C^-1 r and d = diag(C^-1):
+ *   loo_dev [S, 5, K]:  row 0  mu_loo[k]  = flux[k] - alpha[k] / d[k]     the mean of datum k predicted from the others
+ *                       row 1  var_loo[k] = 1 / d[k]                      its variance (the cadence's own noise included)
+ *                       row 2  z[k]       = alpha[k] / sqrt(d[k])         the standardised residual
+ *                       row 3  lpd[k]     = -1/2 log(2 pi var_loo[k]) - 1/2 z[k]^2
+ *                       row 4  white      = L^-1 r, C = L L^T
+ *   lnlike_dev [S]:     -1/2 |white|^2 - 1/2 log det C - K/2 log 2 pi
+ * No refit and no C^-1: the identity rides through the blocked factorisation (Y = L^-T) and two passes over the upper
+ * triangle of Y give white, d and alpha.  Reductions run in a fixed order without floating-point atomics: the same
+ * bits run after run.  status_dev (may be NULL) [S].
+ *   covariance that does not factor: NaN in the five rows and in lnlike, SP_STAR_NOT_PD;  ragged star (0 < nobs < K):
+ *   NaN, SP_STAR_NAN;  normalised star with z > zmax: lnlike = -inf, SP_STAR_ZMAX, the five rows still computed.
+ * No star affects another.  The stars are worked through in groups of as many as workspace_bytes holds
+ * (sp_loo_workspace_bytes(h, S', K, covpts, conditional) for S' stars resident at once: the SPD inverse's own workspace
+ * and one double per star -- no [S, Kr, Kr] inverse; the conditional branch adds what its forward writes: two
+ * roundup(K, 64) x N matrices and the raw covariance per star; 0 for a null handle, S' < 0 or K < 2); a star's bits do
+ * not depend on the grouping.  A workspace too small for one star, a null required pointer or K < 2: SP_ERR_INVALID.  A
+ * host-only handle: SP_ERR_NO_DEVICE, before everything else.  S = 0: SP_OK, nothing touched.  All launches go to
+ * `stream`; nothing is synchronised.                                                                               */
+size_t sp_loo_workspace_bytes(sp_handle *h, int S, int K, int covpts, int conditional);
+int sp_loo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev /* [S, K] */,
+                    const double *diag_dev, const sp_star *stars_dev, int conditional, int covpts,
+                    const double *tab_dev, const double *meanvar_dev, const double *rta1_dev, int temporal,
+                    int normalized, int norm_order, double zmax,
+                    double *loo_dev /* [S, 5, K]: mu_loo, var_loo, z, lpd, white */, double *lnlike_dev /* [S] */,
+                    uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
+                    void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /
@@ -1065,6 +1097,11 @@ int sp_debug_set_predict_chunk_bytes(size_t bytes);
  * sp_ylm_conditional_temporal_workspace_bytes too, so size the workspace after setting it.  Which frames share a pass
  * changes, no frame's bits do.                                                                                      */
 int sp_debug_set_ylm_temporal_chunk_bytes(size_t bytes);
+/* (debug, process-wide) the entries of the whitened residual the row pass of sp_loo_ensemble stages in LDS at a time
+ * (default 6144 = 48 KB; 0 = back to the default; rounded down to an even number, at least 2; above the default:
+ * SP_ERR_INVALID): a small tile makes a short light curve take the tiled path of a long one.  The values agree to
+ * rounding; the order of a row's sum changes with the tile.                                                         */
+int sp_debug_set_loo_tile_doubles(size_t doubles);
 /* (debug, host only) how the hot assembly kernel (csrc/sp_assemble.hip, assemble_sums_kernel) cuts a star's
  * ntr (ntr + 1) / 2 lower tiles (column-strip order) into nchunk chunks of equal COST: start_host[c] = first tile
  * of chunk c, c = 0 .. nchunk (start_host[nchunk] = the number of tiles).  A function of the shape alone.   */

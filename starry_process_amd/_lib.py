@@ -100,6 +100,9 @@ PROTOTYPES = {
     "sp_fisher_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I]),
     "sp_fisher_conditional": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                    ctypes.c_size_t, _V]),
+    "sp_loo_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
+    "sp_loo_ensemble": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
+                             ctypes.c_size_t, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_predict_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),
@@ -156,6 +159,7 @@ PROTOTYPES = {
     "sp_debug_set_small_k": (_I, [_I]),
     "sp_debug_set_predict_chunk_bytes": (_I, [ctypes.c_size_t]),
     "sp_debug_set_ylm_temporal_chunk_bytes": (_I, [ctypes.c_size_t]),
+    "sp_debug_set_loo_tile_doubles": (_I, [ctypes.c_size_t]),
     "sp_debug_set_syrk_symdiag": (_I, [_I]),
     "sp_debug_set_look_ahead": (_I, [_V, _I]),
     "sp_debug_set_panel_layout": (_I, [_V, _I, _I]),

@@ -272,16 +272,22 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
 
 // scatter of H_ij T_ij c_m(x0_ij) into the table's adjoint: one workgroup per LOWER 64 x 64 tile (C^-1 and H are
 // symmetric: the tiles below the diagonal count twice; the lower storage is read along its rows: coalesced), the
-// bins in LDS (ds_add_f64), one partial table per workgroup (grad_bins_reduce_kernel adds them in a fixed order)
+// bins in LDS (ds_add_f64), one partial table per workgroup (grad_bins_reduce_kernel adds them in a fixed order).
+// nb == 4: every wavefront adds into a copy of the bins of its own, and the copies are added as (0 + 1) + (2 + 3).  The
+// order in which additions of DIFFERENT wavefronts reach one bin is fixed by nothing (ybar then differs run to run in
+// its last bits); those of one wavefront are issued in program order and the lanes of one instruction that meet in a
+// bin are served in a fixed order, so with a copy per wavefront ybar is the same bits run after run.  nb == 1 (a table
+// whose four copies do not fit the LDS budget): one copy, as before.
 template <int TK, bool ONE>     // ONE: one light curve per star (M == 1: no loop over them per entry)
 __global__ __launch_bounds__(256) void grad_scatter_kernel(
     int K, int Kr, int Mrt, const double *__restrict__ Cinv, const double *__restrict__ theta, const double *__restrict__ t,
     const sp_star *__restrict__ stars, int covpts, const double *__restrict__ vec, const double *__restrict__ hcoef,
-    double *__restrict__ partial) {
-  extern __shared__ __attribute__((aligned(16))) double bins[];   // covpts + 4
+    double *__restrict__ partial, int nb) {
+  extern __shared__ __attribute__((aligned(16))) double allbins[];   // nb (covpts + 4)
   const int M = ONE ? 1 : Mrt;
   const int s = blockIdx.y, np = covpts + 4, tid = threadIdx.x;
-  for (int k = tid; k < np; k += 256) bins[k] = 0.0;
+  for (int k = tid; k < nb * np; k += 256) allbins[k] = 0.0;
+  double *bins = allbins + (nb == 4 ? (tid >> 6) * np : 0);
   __syncthreads();
   int ta, tb;                             // row tile ta >= column tile tb
   sp_lower_tile_decode(blockIdx.x, ta, tb);
@@ -315,7 +321,8 @@ __global__ __launch_bounds__(256) void grad_scatter_kernel(
   }
   __syncthreads();
   double *P = partial + ((size_t)s * gridDim.x + blockIdx.x) * np;
-  for (int k = tid; k < np; k += 256) P[k] = bins[k];
+  for (int k = tid; k < np; k += 256)
+    P[k] = nb == 4 ? (allbins[k] + allbins[np + k]) + (allbins[2 * np + k] + allbins[3 * np + k]) : allbins[k];
 }
 
 // ybar[s][k] = sum over the tiles' partial tables, in a fixed order: thread (k, g) adds the partials w = g, g + 4, ...,
@@ -453,14 +460,15 @@ int sp_launch_grad_sweep(const SpProblem &P, const SpViews &V, double *Cinv, con
   const size_t lds = sizeof(double) * np;
   if (lds > 60 * 1024) return SP_ERR_INVALID;
   dim3 grid(ntr * (ntr + 1) / 2, S);
+  const int nb = 4 * lds <= 60 * 1024 ? 4 : 1;   // (a copy of the bins per wavefront where four fit: the same bits every run)
 #define SP_SCATTER(TK)                                                                                               \
   do {                                                                                                               \
     if (M == 1)                                                                                                      \
-      hipLaunchKernelGGL((grad_scatter_kernel<TK, true>), grid, dim3(256), lds, st, K, Kr, M, Cinv, theta, t, stars,  \
-                         covpts, vec, hcoef, partial);                                                               \
+      hipLaunchKernelGGL((grad_scatter_kernel<TK, true>), grid, dim3(256), nb * lds, st, K, Kr, M, Cinv, theta, t,   \
+                         stars, covpts, vec, hcoef, partial, nb);                                                    \
     else                                                                                                             \
-      hipLaunchKernelGGL((grad_scatter_kernel<TK, false>), grid, dim3(256), lds, st, K, Kr, M, Cinv, theta, t, stars, \
-                         covpts, vec, hcoef, partial);                                                               \
+      hipLaunchKernelGGL((grad_scatter_kernel<TK, false>), grid, dim3(256), nb * lds, st, K, Kr, M, Cinv, theta, t,  \
+                         stars, covpts, vec, hcoef, partial, nb);                                                    \
   } while (0)
   if (temporal == SP_TEMPORAL_NONE) SP_SCATTER(SP_TEMPORAL_NONE);
   else if (temporal == SP_TEMPORAL_MATERN32) SP_SCATTER(SP_TEMPORAL_MATERN32);
@@ -542,6 +550,11 @@ int grad_marginal(sp_handle *h, const SpProblem &P, void *workspace_dev, double 
 // opening of the gradient sweep above and of the Fisher sweep (sp_fisher.hip), which agree about C to the bit because
 // this is the likelihood's own chain (sp_launch_direct_form).
 int sp_launch_marginal_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, double *Cinv, double *logdet) {
+  if (const int rc = sp_launch_marginal_system(P, V)) return rc;
+  return spd_inverse_in_place(h, P.S, P.K, V.L, V.ws, Cinv, logdet, P.st);
+}
+
+int sp_launch_marginal_system(const SpProblem &P, const SpViews &V) {
   const Layout &L = V.L;
   int rc;
   if ((rc = sp_launch_theta(P, V.theta()))) return rc;
@@ -550,10 +563,8 @@ int sp_launch_marginal_inverse(sp_handle *h, const SpProblem &P, const SpViews &
   SpProblem C = P;
   C.M = 0;
   C.flux = nullptr;
-  if ((rc = sp_launch_direct_form(C, V.theta(), nullptr, nullptr, V.rowsum(), V.qv(), V.coef(), nullptr,
-                                  SpAsmOut{V.sys(), L.Kp, (long)L.Kp * L.Kp, 1, sp_roundup(P.K, SP_NB), 1})))
-    return rc;
-  return spd_inverse_in_place(h, P.S, P.K, L, V.ws, Cinv, logdet, P.st);
+  return sp_launch_direct_form(C, V.theta(), nullptr, nullptr, V.rowsum(), V.qv(), V.coef(), nullptr,
+                               SpAsmOut{V.sys(), L.Kp, (long)L.Kp * L.Kp, 1, sp_roundup(P.K, SP_NB), 1});
 }
 
 // The head of the sweep, shared by the two branches (the conditional one: sp_grad_cond.hip): the products of C^-1 with

@@ -374,6 +374,12 @@ GradCondLayout grad_cond_layout(sp_handle *h, int S, int K) {
 //   partial: [S][Kr / 64][K] doubles; logdet [S] or null.  Leaves theta, rowsum, qv, coef, condmean, cs, vrow, info of V.
 int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A, double *B,
                            double *raw, double *Cinv, double *partial, double *logdet) {
+  if (const int rc = sp_launch_cond_covariance(h, P, V, rta1_dev, A, B, raw, partial)) return rc;
+  return spd_inverse_in_place(h, P.S, P.K, V.L, V.ws, Cinv, logdet, P.st);
+}
+
+int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A,
+                              double *B, double *raw, double *partial) {
   const int S = P.S, K = P.K, temporal = P.temporal, normalized = P.normalized;
   const double *t_dev = P.t, *diag_dev = P.diag;
   const sp_star *stars_dev = P.stars;
@@ -410,7 +416,7 @@ int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, c
   hipLaunchKernelGGL(cond_finish_kernel, dim3(ntri, S), dim3(256), 0, st, K, Kr, raw, stars_dev, (const SpCoef *)coef, qv,
                      diag_dev, normalized, sys, (long)L.Kp, (long)L.Kp * L.Kp);
   SP_LAUNCH_CHECK();
-  return spd_inverse_in_place(h, S, K, L, V.ws, Cinv, logdet, st);
+  return SP_OK;
 }
 
 extern "C" {

@@ -512,7 +512,13 @@ int sp_launch_design(sp_handle *h, const SpViews &V, const sp_star *stars, const
 int sp_launch_cond_mean(int S, int N, int rows, const double *A, const double *mu, double *mean, hipStream_t st,
                         const int32_t *sel = nullptr, int nsets = 0);
 
-// sp_linalg.hip: C^-1 (and log det C) of the matrices already in the top-left K x K corners of the systems of `ws`
+// sp_linalg.hip: C^-1 (and log det C) of the matrices already in the top-left K x K corners of the systems of `ws`,
+// in two halves.  spd_identity_factor: the identity rows below the matrices, the factorisation and log det C -- leaves
+// Y = L^-T (upper triangular) in the rows K .. 2 K - 1, columns < K, of every system (the columns K .. Kr - 1 of those rows
+// undefined) and the stars' info words.  spd_inverse_product: those columns zeroed, then C^-1 = Y Y^T (lower tiles) into
+// Cinv [S][Kr][Kr].  spd_inverse_in_place is one behind the other; the leave-one-out sweep (sp_loo.hip) stops after the first.
+int spd_identity_factor(sp_handle *h, int S, int K, const Layout &L, void *ws, double *logdet_dev, hipStream_t st);
+int spd_inverse_product(int S, int K, const Layout &L, void *ws, double *Cinv_dev, hipStream_t st);
 int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
                          hipStream_t st);
 
@@ -531,6 +537,8 @@ static inline SpViews sp_sweep_views(const sp_handle *h, int S, int K, void *ws)
 // corner of the system) and its inverse into Cinv [S][Kr][Kr] (lower tiles); logdet [S] or null.  Leaves theta, qv,
 // coef and info of V for the sweep behind it.
 int sp_launch_marginal_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, double *Cinv, double *logdet);
+// ... its first half alone: the phases and the direct form into the corner of the system (theta, qv, coef of V filled)
+int sp_launch_marginal_system(const SpProblem &P, const SpViews &V);
 // sp_grad.hip: the head of the gradient sweep (products with C^-1, scalars) on V's coef, qv and info; partial:
 // [S][Kr / 64][4][K] doubles, Kr = roundup(K, 64)
 int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cinv, const double *logdet, double *vec,
@@ -543,6 +551,9 @@ int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cin
 // logdet [S] or null.  Leaves theta, rowsum, qv, coef, condmean, cs, vrow and info of V for the sweep behind it.
 int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A, double *B,
                            double *raw, double *Cinv, double *partial, double *logdet);
+// ... its first half alone: everything up to C in the corner of the system (raw is then scratch of its own)
+int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A,
+                              double *B, double *raw, double *partial);
 // sp_lnlike.hip: the tangents of the design matrices sp_launch_design left in place (V's cs, vrow, theta), Kr rows per
 // star: dA_inc = d A / d inc per radian (dR [S][NWIG], dv [S][N]: scratch), dA_per = d A / d period; either may be null
 int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,

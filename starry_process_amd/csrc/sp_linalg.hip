@@ -59,9 +59,9 @@ __global__ __launch_bounds__(256) void zero_cols_kernel(double *__restrict__ sys
 // a launch of the factorisation only takes the identity's row tiles that hold something yet, the trailing updates
 // leave the columns without pivots alone, and the product of tile (ti, tj) starts at column 64 ti --
 // K^3 (1/3 + 1/2 + 1/3) flops, against K^3 (1/3 + 1 + 1) without the structure.
-// the inverse of the matrices ALREADY in the top-left K x K corners of the systems of `ws` (lower triangles)
-int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
-                         hipStream_t st) {
+// the inverse of the matrices ALREADY in the top-left K x K corners of the systems of `ws` (lower triangles), in two
+// halves (sp_internal.h): a caller that needs Y alone (sp_loo.hip) stops after the first
+int spd_identity_factor(sp_handle *h, int S, int K, const Layout &L, void *ws, double *logdet_dev, hipStream_t st) {
   const int Kr = sp_roundup(K, SP_NB);
   double *sys = at<double>(ws, L.sys);
   int32_t *info = at<int32_t>(ws, L.info);
@@ -76,6 +76,13 @@ int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, 
     hipLaunchKernelGGL(logdet_kernel, dim3(S), dim3(256), 0, st, sys, ld, stride, K, info, logdet_dev);
     SP_LAUNCH_CHECK();
   }
+  return SP_OK;
+}
+
+int spd_inverse_product(int S, int K, const Layout &L, void *ws, double *Cinv_dev, hipStream_t st) {
+  const int Kr = sp_roundup(K, SP_NB);
+  double *sys = at<double>(ws, L.sys);
+  const long ld = L.Kp, stride = (long)L.Kp * L.Kp;
   if (Kr > K) {
     const long n = (long)Kr * (Kr - K);
     hipLaunchKernelGGL(zero_cols_kernel, dim3((unsigned)((n + 255) / 256), S), dim3(256), 0, st, sys, ld, stride, K, Kr,
@@ -86,6 +93,12 @@ int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, 
   const double *Y = sys + (size_t)K * ld;
   return sp_launch_gemm_nt(Y, ld, stride, Y, ld, stride, Cinv_dev, Kr, (long)Kr * Kr, Kr, Kr, Kr, 1.0, 0, 1, S, st, 2,
                            nullptr);
+}
+
+int spd_inverse_in_place(sp_handle *h, int S, int K, const Layout &L, void *ws, double *Cinv_dev, double *logdet_dev,
+                         hipStream_t st) {
+  if (const int rc = spd_identity_factor(h, S, K, L, ws, logdet_dev, st)) return rc;
+  return spd_inverse_product(S, K, L, ws, Cinv_dev, st);
 }
 
 extern "C" {

@@ -58,6 +58,7 @@ void sp_tuning_read(char *(*get)(const char *), SpTuning *t, SpProcTuning *p) {
   }
   if (p) p->predict_chunk_bytes = SP_PREDICT_CHUNK_BYTES;
   if (p) p->ylm_temporal_chunk_bytes = SP_YLM_TEMPORAL_CHUNK_BYTES;
+  if (p) p->loo_tile_doubles = SP_LOO_TILE_DOUBLES;
 }
 void sp_tuning_defaults(SpTuning *t, SpProcTuning *p) { sp_tuning_read(nullptr, t, p); }
 
@@ -214,6 +215,12 @@ int sp_debug_set_predict_chunk_bytes(size_t bytes) {
 }
 int sp_debug_set_ylm_temporal_chunk_bytes(size_t bytes) {
   proc_state().cur.ylm_temporal_chunk_bytes = bytes ? bytes : SP_YLM_TEMPORAL_CHUNK_BYTES;
+  return SP_OK;
+}
+int sp_debug_set_loo_tile_doubles(size_t doubles) {
+  // (even, at least one pair, never above the default: the kernel's LDS request stays where it is measured)
+  if (doubles > SP_LOO_TILE_DOUBLES) return SP_ERR_INVALID;
+  proc_state().cur.loo_tile_doubles = doubles ? (doubles < 2 ? 2 : (doubles & ~(size_t)1)) : SP_LOO_TILE_DOUBLES;
   return SP_OK;
 }
 

@@ -35,7 +35,11 @@ struct SpProcTuning {
   // (no environment variable: sp_debug_set_ylm_temporal_chunk_bytes; the workspace of one pass of frames of
   //  sp_ylm_conditional_temporal)
   size_t ylm_temporal_chunk_bytes;
+  // (no environment variable: sp_debug_set_loo_tile_doubles; the entries of the whitened residual the row pass of
+  //  sp_loo_ensemble stages in LDS at a time; even)
+  size_t loo_tile_doubles;
 };
+#define SP_LOO_TILE_DOUBLES ((size_t)6144)
 #define SP_PREDICT_CHUNK_BYTES ((size_t)4 << 30)
 #define SP_YLM_TEMPORAL_CHUNK_BYTES ((size_t)1 << 30)
 

@@ -1296,6 +1296,53 @@ class Engine(object):
                 self._p(dcov), self._p(status), self._p(workspace), int(workspace.numel()), self._stream()))
         return (fisher, status, dcov) if return_tangents else (fisher, status)
 
+    def loo_workspace(self, S, K, covpts=300, conditional=False):
+        """Device scratch that holds ``S`` stars of ``loo_ensemble`` at once (sp_loo_workspace_bytes)."""
+        return self._scratch(self._L.sp_loo_workspace_bytes(self._h, int(S), int(K), int(covpts),
+                                                            int(bool(conditional))))
+
+    def loo_ensemble(self, t, flux, stars, diag=None, conditional=False, covpts=300, tab=None, meanvar=None, rta1=None,
+                     temporal=None, normalized=True, norm_order=20, zmax=0.023, workspace=None,
+                     max_workspace_bytes=None):
+        """Leave-one-out predictive checks of S light curves (sp_loo_ensemble): t, flux [S, K]; stars: host sp_star
+        records or their device copy; diag [S, K] per-cadence variances or None.  Marginal branch: tab, meanvar from
+        ``kernel_table(rta1, covpts)``; conditional branch: rta1 and the moments set on this engine.  Returns
+        (loo [S, 5, K], lnlike [S], status [S]) on the device; the rows of loo: mu_loo, var_loo, the standardised
+        residual z, the log predictive density, and the whitened residual L^-1 r.  A star whose covariance does not
+        factor, or a ragged one, holds NaN; a normalised star with z > zmax has lnlike = -inf and finite rows.
+        workspace: a byte tensor (``loo_workspace``); ``max_workspace_bytes`` caps the scratch allocated here
+        instead.  A workspace that holds fewer than S stars makes the call work through them in groups, with the
+        same bits."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        if flux.dim() != 2 or t.shape != flux.shape:
+            raise ValueError("t and flux must both be (S, K)")
+        S, K = flux.shape
+        if K < 2:
+            raise ValueError("leave-one-out needs at least two cadences")
+        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        rta1 = None if rta1 is None else self.f64(rta1)
+        conditional = int(bool(conditional))
+        loo, lnlike = self.empty(S, 5, K), self.empty(S)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S > 0:
+            if workspace is None:
+                need = int(self._L.sp_loo_workspace_bytes(self._h, S, K, int(covpts), conditional))
+                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
+                    one = int(self._L.sp_loo_workspace_bytes(self._h, 1, K, int(covpts), conditional))
+                    if int(max_workspace_bytes) < one:
+                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
+                                         % (int(max_workspace_bytes), one))
+                    need = int(max_workspace_bytes)
+                workspace = self._grad_ws = self._scratch(need)
+            check(self._L.sp_loo_ensemble(
+                self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), conditional, int(covpts),
+                self._p(tab), self._p(meanvar), self._p(rta1), TEMPORAL[temporal], int(bool(normalized)),
+                int(norm_order), float(zmax), self._p(loo), self._p(lnlike), self._p(status), self._p(workspace),
+                int(workspace.numel()), self._stream()))
+        return loo, lnlike, status
+
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 

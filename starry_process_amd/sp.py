@@ -702,6 +702,81 @@ class StarryProcess(object):
         smp += mu[:, None, :]
         return Eager(smp.cpu().numpy())
 
+    # -- model checking: leave-one-out predictive distributions (sp_loo_ensemble) ---------------------------
+    def loo_ensemble(self, t, flux, data_cov, i=None, p=None, u=None, baseline_mean=0.0, baseline_var=0.0,
+                     max_workspace_bytes=None):
+        """Leave-one-out predictive checks of S light curves in one device call (Rasmussen & Williams 5.4.2): what
+        the process, fitted to all the other cadences of a star, predicts for each cadence.  Nothing is refitted:
+        with C the covariance ``log_likelihood_ensemble`` factors, r its residual, alpha = C^-1 r, d = diag(C^-1),
+
+            mu[k] = flux[k] - alpha[k] / d[k]    var[k] = 1 / d[k]    z[k] = alpha[k] / sqrt(d[k])
+            lpd[k] = -1/2 log(2 pi var[k]) - 1/2 z[k]^2               white = L^-1 r  (C = L L^T)
+
+        Arguments as ``predict_ensemble``: t (K,) or (S, K); flux (S, K); data_cov: scalar, (S,) or (S, K); i, p,
+        baseline_mean, baseline_var: scalars or (S,); u: (udeg,) shared or (S, udeg).  The branch is the instance's
+        (``marginalize_over_inclination``, ``tau``, ``normalized``); unlike ``predict``, a normalised process is
+        served.  ``mu`` and ``var`` are predictive for the DATUM: they include ``baseline_mean`` and the cadence's
+        own noise variance (``predict`` at a held-out time gives mu - baseline_mean and var - data_var[k]).
+
+        Returns a dict of NumPy arrays: ``mu``, ``var``, ``z``, ``lpd``, ``white`` (S, K); ``elpd`` = lpd.sum(1),
+        ``lnlike`` (-inf where ``log_likelihood_ensemble`` gives -inf) and ``status`` (S,).  A star whose covariance
+        does not factor has NaN in its rows.  ``max_workspace_bytes`` caps the device scratch: the stars are then
+        worked through in groups, with the same bits.  A full-matrix ``data_cov``, a matrix ``baseline_var`` and
+        ragged input (lists of light curves of different lengths) are not served."""
+        e, f = self._engine, self._flux
+        try:
+            flux = np.asarray(flux, dtype=np.float64)
+            tt = np.asarray(t, dtype=np.float64)
+        except (ValueError, TypeError):
+            raise ValueError("loo_ensemble does not serve ragged input (lists of light curves of different lengths): "
+                             "pass `t` and `flux` as (S, K) arrays")
+        if flux.ndim != 2:
+            raise ValueError("`flux` must be (S, K)")
+        S, K = flux.shape
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
+            raise NotImplementedError("loo_ensemble does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
+                                      "(S, K) variances")
+        if np.ndim(baseline_var) >= 2:
+            raise NotImplementedError("loo_ensemble does not serve a matrix `baseline_var`: pass a scalar or (S,)")
+        if K < 2:
+            raise ValueError("leave-one-out needs at least two cadences")
+        t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
+        f._bind()
+        rta1 = e.f64(e.rTA1L(utab))
+        tab = mv = None
+        if self._marginalize_over_inclination:
+            tab, mv = e.kernel_table(rta1, self._covpts)
+        loo, lnlike, status = e.loo_ensemble(
+            t, flux, stars, diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
+            meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized, norm_order=self._normN,
+            zmax=self._normzmax, max_workspace_bytes=max_workspace_bytes)
+        loo = loo.cpu().numpy()
+        out = {name: np.ascontiguousarray(loo[:, k]) for k, name in enumerate(("mu", "var", "z", "lpd", "white"))}
+        out["elpd"] = out["lpd"].sum(axis=1)
+        out["lnlike"] = _neg_inf_if_nan(lnlike.cpu().numpy())
+        out["status"] = status.cpu().numpy()
+        return out
+
+    def loo(self, t, flux, data_cov, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]],
+            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"]):
+        """``loo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances.  The same dict
+        without the leading axis."""
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim >= 2:
+            raise NotImplementedError("loo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
+        if np.ndim(baseline_var) >= 1:
+            raise NotImplementedError("loo does not serve a matrix `baseline_var`: pass a scalar")
+        try:
+            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
+        except (ValueError, TypeError):
+            raise ValueError("`flux` must be one light curve of K cadences")
+        if dc.ndim == 1:
+            dc = dc.reshape(1, -1)
+        out = self.loo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, i=i, p=p, u=u,
+                                baseline_mean=baseline_mean, baseline_var=baseline_var)
+        return {k: v[0] for k, v in out.items()}
+
     # -- posterior of the surface map (sp.py:518-641) -------------------------------------
     # W = Sigma_y^-1 + A^T C^-1 A, ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)), ycov = W^-1,
     # with A the design matrix at (t, i, p, u) whatever marginalize_over_inclination says (sp.py:620), as in
