@@ -627,6 +627,42 @@ int sp_loo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
                     uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
                     void *stream);
 
+/* ---- Leave-block-out predictive checks of an ensemble (h-block cross-validation), either branch --------------------
+ * What the process, fitted to the cadences of star s OUTSIDE a block B of b consecutive ones, predicts for the block.
+ * C_s, r and the branches are sp_loo_ensemble's; with alpha = C^-1 r and G = (C^-1)_BB = L_G L_G^T:
+ *   rows_dev [S, 4, K]:  row 0  mu    = flux_B - G^-1 alpha_B     the predictive mean of the block's data
+ *                        row 1  var   = diag(G^-1)                their variances (the cadences' own noise included)
+ *                        row 2  u     = L_G^-1 alpha_B            the block's whitened residual: N(0, I) when the model holds
+ *                        row 3  white = L^-1 r, C = L L^T
+ *   lpd_dev [S, nblocks]:  -1/2 u^T u + sum log (L_G)_ii - b/2 log 2 pi, the log density of the held-out block
+ *   cov_dev (may be NULL) [S, nblocks, bmax, bmax], bmax = the widest block: G^-1 in the corner of the block's slot,
+ *                        exactly symmetric, its diagonal the bits of row 1; the rest of the slot NaN
+ *   lnlike_dev [S], status_dev (may be NULL) [S]: as sp_loo_ensemble
+ * edges_dev [nblocks + 1] (int32, device) is a partition of the cadence indices common to all stars:
+ * 0 = e_0 < e_1 < ... < e_nblocks = K with every width between 1 and 64 (one workgroup holds a block's 64 x 64 matrix G
+ * and its factor in LDS; wider blocks are not served).  It is copied to the host and checked, so the call synchronises
+ * `stream` once before its launches; anything else than such a partition: SP_ERR_INVALID.
+ * The opening is sp_loo_ensemble's own (the same C and Y = L^-T to the bit); one more pass over the upper triangle of Y
+ * gives G (the Gram matrix of the block's rows of Y, on the fp64 matrix cores) and alpha_B for every block; no K x K
+ * system is factored again and no C^-1 is formed.  Sums run in a fixed order without atomics: the same bits run after
+ * run, alone or among other stars, in any grouping (results of DIFFERENT partitions agree to rounding only).
+ *   covariance that does not factor: NaN in rows, lpd, cov and lnlike, SP_STAR_NOT_PD;  ragged star (0 < nobs < K): NaN,
+ *   SP_STAR_NAN;  normalised star with z > zmax: lnlike = -inf, SP_STAR_ZMAX, everything else still computed;  a block
+ *   whose G has a pivot that is not positive: NaN in that block's mu, var, u, lpd and cov, SP_STAR_NAN on the star, its
+ *   other blocks untouched.
+ * sp_lbo_workspace_bytes(h, S', K, covpts, conditional, nblocks): sp_loo_workspace_bytes plus 4 (nblocks + 1) +
+ * 4 S' nblocks bytes (0 for a null handle, S' < 0, K < 2, nblocks < 1 or nblocks > K).  Groups, a workspace too small
+ * for one star, null pointers, a host-only handle and S = 0 as sp_loo_ensemble.                                      */
+size_t sp_lbo_workspace_bytes(sp_handle *h, int S, int K, int covpts, int conditional, int nblocks);
+int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev /* [S, K] */,
+                    const double *diag_dev, const sp_star *stars_dev, int conditional, int covpts,
+                    const double *tab_dev, const double *meanvar_dev, const double *rta1_dev, int temporal,
+                    int normalized, int norm_order, double zmax, int nblocks,
+                    const int32_t *edges_dev /* [nblocks + 1] */, double *rows_dev /* [S, 4, K]: mu, var, u, white */,
+                    double *lpd_dev /* [S, nblocks] */, double *cov_dev /* NULL or [S, nblocks, bmax, bmax] */,
+                    double *lnlike_dev /* [S] */, uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev,
+                    size_t workspace_bytes, void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

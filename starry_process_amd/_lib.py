@@ -103,6 +103,9 @@ PROTOTYPES = {
     "sp_loo_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_loo_ensemble": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                              ctypes.c_size_t, _V]),
+    "sp_lbo_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
+    "sp_lbo_ensemble": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _I, _V, _V, _V, _V, _V, _V,
+                             _V, ctypes.c_size_t, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_predict_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),

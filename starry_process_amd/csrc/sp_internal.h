@@ -554,6 +554,21 @@ int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, c
 // ... its first half alone: everything up to C in the corner of the system (raw is then scratch of its own)
 int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A,
                               double *B, double *raw, double *partial);
+// sp_loo.hip: the opening the leave-one-out and the leave-block-out sweeps (sp_lbo.hip) share.  sp_loo_layout_bytes: the
+// workspace of S resident stars (sp_loo_workspace_bytes without its argument checks).  sp_loo_open: C into the corner of
+// the system (sp_launch_marginal_system / sp_launch_cond_covariance), spd_identity_factor, then the column pass: white =
+// L^-1 r of star s into white[s * wstride .. + K) (NaN for a star that did not factor or is ragged).  `out`: where Y =
+// L^-T lies (row m of star s at sys + s * stride + (K + m) * ld) and the per-star arrays behind it.
+struct SpLooSystem {
+  const double *sys;
+  long ld, stride;
+  const SpCoef *coef;
+  const int32_t *info;
+  const double *logdet;
+};
+size_t sp_loo_layout_bytes(const sp_handle *h, int S, int K, int conditional);
+int sp_loo_open(sp_handle *h, const SpProblem &Q, int conditional, const double *rta1, void *workspace, double *white,
+                long wstride, SpLooSystem *out);
 // sp_lnlike.hip: the tangents of the design matrices sp_launch_design left in place (V's cs, vrow, theta), Kr rows per
 // star: dA_inc = d A / d inc per radian (dR [S][NWIG], dv [S][N]: scratch), dA_per = d A / d period; either may be null
 int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,

@@ -17,22 +17,10 @@
 
 namespace {
 
-typedef double loo_v2 __attribute__((ext_vector_type(2)));
 constexpr int LOO_RB = 64;      // rows of Y per workgroup of the column pass (16 per wavefront, all loads in flight)
 constexpr int LOO_CB = 128;     // its columns: 64 lanes x 16 bytes
 constexpr int LOO_ROWS = 16;    // rows of Y per workgroup of the row pass (4 per wavefront)
 // (`white` is staged in LDS SP_LOO_TILE_DOUBLES entries at a time, sp_tuning.h: 48 KB, three workgroups per CU; even)
-
-// Y[m][j], Y[m][j + 1] of row m (j even: the pair is 16-byte aligned, ld and the row's offset being even).  Entries
-// left of the diagonal are exact zeros and those beyond column K - 1 undefined: neither is loaded.
-__device__ __forceinline__ loo_v2 loo_pair(const double *__restrict__ row, int m, int j, int K) {
-  loo_v2 y = {0.0, 0.0};
-  if (j + 1 < m || j >= K) return y;
-  if (j + 1 < K) y = *reinterpret_cast<const loo_v2 *>(row + j);
-  else y.x = row[j];
-  if (j < m) y.x = 0.0;
-  return y;
-}
 
 // The column pass, one workgroup per block of LOO_RB rows x LOO_CB columns that reaches the upper triangle
 // (64 tm <= 128 tc + 127; the others leave at once): part[s][tm][j] = sum over the block's rows m <= j of Y[m][j] r[m],
@@ -81,11 +69,13 @@ __device__ __forceinline__ bool loo_star_nan(const sp_star &st, int K, const int
   return info[s] != 0 || (st.nobs > 0 && st.nobs < K);
 }
 
-// white[j] = the blocks' parts tm = 0 .. min(nrb - 1, 2 (j / 128) + 1) in that order, into row 4 of the star's output.
+// white[j] = the blocks' parts tm = 0 .. min(nrb - 1, 2 (j / 128) + 1) in that order, into the star's row of `white`
+// (wstride doubles from one star's row to the next: row 4 of the leave-one-out output, row 3 of the leave-block-out one).
 // grid (ceil(K / 256), S)
 __global__ __launch_bounds__(256) void loo_white_kernel(int K, int nrb, const double *__restrict__ part,
                                                         const sp_star *__restrict__ stars,
-                                                        const int32_t *__restrict__ info, double *__restrict__ loo) {
+                                                        const int32_t *__restrict__ info, double *__restrict__ white,
+                                                        long wstride) {
   const int s = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
   if (j >= K) return;
   double a = 0.0;
@@ -97,7 +87,7 @@ __global__ __launch_bounds__(256) void loo_white_kernel(int K, int nrb, const do
 #pragma unroll 4
     for (int tm = 0; tm <= last; ++tm) a += P[(size_t)tm * K];
   }
-  loo[((size_t)s * 5 + 4) * K + j] = a;
+  white[(size_t)s * wstride + j] = a;
 }
 
 // The row pass: a workgroup takes LOO_ROWS rows of a star's Y, a wavefront four of them, 16 bytes per lane and load,
@@ -199,9 +189,16 @@ LooLayout loo_layout(const sp_handle *h, int S, int K, int conditional) {
   return G;
 }
 
-// one group of stars (Q: their problem; the slices of the outputs already taken)
-int loo_group(sp_handle *h, const SpProblem &Q, int conditional, const double *rta1, double *loo, double *lnlike,
-              uint32_t *status, void *workspace) {
+}  // namespace
+
+size_t sp_loo_layout_bytes(const sp_handle *h, int S, int K, int conditional) {
+  return loo_layout(h, S, K, conditional).total;
+}
+
+// The opening the leave-one-out and the leave-block-out sweeps share (sp_internal.h): C into the corner of the system,
+// the identity through the factorisation, the column pass for `white`.
+int sp_loo_open(sp_handle *h, const SpProblem &Q, int conditional, const double *rta1, void *workspace, double *white,
+                long wstride, SpLooSystem *out) {
   const int S = Q.S, K = Q.K, Kr = sp_roundup(K, SP_NB), nrb = Kr / LOO_RB;
   hipStream_t st = Q.st;
   const LooLayout G = loo_layout(h, S, K, conditional);
@@ -220,14 +217,29 @@ int loo_group(sp_handle *h, const SpProblem &Q, int conditional, const double *r
   hipLaunchKernelGGL(loo_white_part_kernel, dim3((K + LOO_CB - 1) / LOO_CB, nrb, S), dim3(256), 0, st, K, ld, stride,
                      V.sys(), Q.flux, Q.stars, (const SpCoef *)V.coef(), part);
   SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loo_white_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, nrb, part, Q.stars, V.info(), loo);
+  hipLaunchKernelGGL(loo_white_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, nrb, part, Q.stars, V.info(), white,
+                     wstride);
   SP_LAUNCH_CHECK();
+  out->sys = V.sys(), out->ld = ld, out->stride = stride, out->coef = (const SpCoef *)V.coef(), out->info = V.info();
+  out->logdet = logdet;
+  return SP_OK;
+}
+
+namespace {
+
+// one group of stars (Q: their problem; the slices of the outputs already taken)
+int loo_group(sp_handle *h, const SpProblem &Q, int conditional, const double *rta1, double *loo, double *lnlike,
+              uint32_t *status, void *workspace) {
+  const int S = Q.S, K = Q.K;
+  hipStream_t st = Q.st;
+  SpLooSystem Y;
+  const int rc = sp_loo_open(h, Q, conditional, rta1, workspace, loo + 4 * (size_t)K, 5 * (long)K, &Y);
+  if (rc) return rc;
   // (the tile of `white`: all of a short light curve, else SP_LOO_TILE_DOUBLES; sp_debug_set_loo_tile_doubles lowers it)
   const int tile = (int)sp_proc_tuning().loo_tile_doubles;
   const int wt = K + 1 < tile ? ((K + 1) & ~1) : tile;
-  hipLaunchKernelGGL(loo_rows_kernel, dim3((K + LOO_ROWS - 1) / LOO_ROWS, S), dim3(256), sizeof(double) * wt, st, K, ld,
-                     stride, wt, V.sys(), Q.flux, Q.stars, (const SpCoef *)V.coef(), V.info(), logdet, Q.normalized, Q.zmax,
-                     loo, lnlike, status);
+  hipLaunchKernelGGL(loo_rows_kernel, dim3((K + LOO_ROWS - 1) / LOO_ROWS, S), dim3(256), sizeof(double) * wt, st, K, Y.ld,
+                     Y.stride, wt, Y.sys, Q.flux, Q.stars, Y.coef, Y.info, Y.logdet, Q.normalized, Q.zmax, loo, lnlike, status);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

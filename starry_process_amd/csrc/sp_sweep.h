@@ -50,4 +50,17 @@ __device__ __forceinline__ double sp_block_sum_256(double v, double *red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// (sp_loo.hip, sp_lbo.hip) the rows of Y = L^-T, upper triangular, as spd_identity_factor leaves them:
+typedef double loo_v2 __attribute__((ext_vector_type(2)));
+// Y[m][j], Y[m][j + 1] of row m (j even: the pair is 16-byte aligned, ld and the row's offset being even).  Entries
+// left of the diagonal are exact zeros and those beyond column K - 1 undefined: neither is loaded.
+__device__ __forceinline__ loo_v2 loo_pair(const double *__restrict__ row, int m, int j, int K) {
+  loo_v2 y = {0.0, 0.0};
+  if (j + 1 < m || j >= K) return y;
+  if (j + 1 < K) y = *reinterpret_cast<const loo_v2 *>(row + j);
+  else y.x = row[j];
+  if (j < m) y.x = 0.0;
+  return y;
+}
+
 #endif

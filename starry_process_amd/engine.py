@@ -25,6 +25,40 @@ def _torch():
 
 _STAGE_BYTES, _STAGE_SLOTS = 1 << 16, 16   # pinned staging ring of Engine.dev (small uploads)
 
+LBO_MAX_BLOCK = 64   # the widest block of lbo_ensemble: one workgroup holds a block's 64 x 64 matrix in LDS
+
+
+def block_edges(block, K):
+    """The partition of K cadences ``lbo_ensemble`` is given, as int32 edges 0 = e_0 < ... < e_nb = K: ``block`` an int
+    b, 1 <= b <= 64 (blocks of b cadences, the last one shorter), or a 1-D integer array of edges.  Pure host code:
+    ValueError for a width outside 1 .. 64, edges that do not increase strictly, do not start at 0 or do not end at K."""
+    K = int(K)
+    if K < 2:
+        raise ValueError("leave-block-out needs at least two cadences")
+    if np.ndim(block) == 0:
+        if isinstance(block, (bool, np.bool_)) or int(block) != block:
+            raise ValueError("`block` must be an integer width or a 1-D array of edges")
+        b = int(block)
+        if not 1 <= b <= LBO_MAX_BLOCK:
+            raise ValueError("`block` = %d: a block holds 1 to %d cadences (wider blocks are not served)"
+                             % (b, LBO_MAX_BLOCK))
+        e = np.append(np.arange(0, K, b), K)
+    else:
+        raw = np.asarray(block)
+        if raw.ndim != 1 or raw.size < 2 or not (np.issubdtype(raw.dtype, np.integer) or
+                                                  np.all(raw == np.round(raw))):
+            raise ValueError("`block` must be an integer width or a 1-D integer array of at least two edges")
+        e = raw.astype(np.int64)
+        if e[0] != 0 or e[-1] != K:
+            raise ValueError("the block edges must start at 0 and end at K = %d" % K)
+        w = np.diff(e)
+        if np.any(w < 1):
+            raise ValueError("the block edges must increase strictly")
+        if np.any(w > LBO_MAX_BLOCK):
+            raise ValueError("a block of %d cadences: a block holds 1 to %d (wider blocks are not served)"
+                             % (int(w.max()), LBO_MAX_BLOCK))
+    return np.ascontiguousarray(e, dtype=np.int32)
+
 
 class Engine(object):
     def __init__(self, ydeg=15, udeg=2, device=0):
@@ -1342,6 +1376,65 @@ class Engine(object):
                 int(norm_order), float(zmax), self._p(loo), self._p(lnlike), self._p(status), self._p(workspace),
                 int(workspace.numel()), self._stream()))
         return loo, lnlike, status
+
+    def lbo_workspace(self, S, K, covpts=300, conditional=False, nblocks=1):
+        """Device scratch that holds ``S`` stars of ``lbo_ensemble`` at once (sp_lbo_workspace_bytes)."""
+        return self._scratch(self._L.sp_lbo_workspace_bytes(self._h, int(S), int(K), int(covpts),
+                                                            int(bool(conditional)), int(nblocks)))
+
+    def lbo_ensemble(self, t, flux, stars, edges, diag=None, conditional=False, covpts=300, tab=None, meanvar=None,
+                     rta1=None, temporal=None, normalized=True, norm_order=20, zmax=0.023, return_cov=False,
+                     workspace=None, max_workspace_bytes=None):
+        """Leave-block-out predictive checks of S light curves (sp_lbo_ensemble): t, flux [S, K]; stars: host sp_star
+        records or their device copy; edges [nblocks + 1]: a partition of the cadence indices into blocks of 1 to 64
+        (``block_edges``), an int32 device tensor or anything ``block_edges`` takes; the other arguments as
+        ``loo_ensemble``.  Returns (rows [S, 4, K], lpd [S, nblocks], cov [S, nblocks, bmax, bmax] or None, lnlike [S],
+        status [S]) on the device; the rows: the blocks' predictive means, variances and whitened residuals u, and
+        the whitened residual L^-1 r of the whole light curve.  A star whose covariance does not factor, or a ragged
+        one, holds NaN; a normalised star with z > zmax has lnlike = -inf and finite rows.  workspace: a byte tensor
+        (``lbo_workspace``); ``max_workspace_bytes`` caps the scratch allocated here instead.  A workspace that holds
+        fewer than S stars makes the call work through them in groups, with the same bits."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        if flux.dim() != 2 or t.shape != flux.shape:
+            raise ValueError("t and flux must both be (S, K)")
+        S, K = flux.shape
+        if K < 2:
+            raise ValueError("leave-block-out needs at least two cadences")
+        if isinstance(edges, torch.Tensor):
+            # (a device tensor is the caller's word: sp_lbo_ensemble checks it; its widest block sizes `cov`)
+            ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
+            if ed.dim() != 1 or ed.numel() < 2:
+                raise ValueError("`edges` must be a 1-D array of at least two block edges")
+            bmax = int((ed[1:] - ed[:-1]).max()) if return_cov else 0
+        else:
+            eh = block_edges(edges, K)
+            bmax = int(np.diff(eh).max())
+            ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
+        nb = int(ed.numel()) - 1
+        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        rta1 = None if rta1 is None else self.f64(rta1)
+        conditional = int(bool(conditional))
+        rows, lpd, lnlike = self.empty(S, 4, K), self.empty(S, nb), self.empty(S)
+        cov = self.empty(S, nb, bmax, bmax) if return_cov else None
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S > 0:
+            if workspace is None:
+                need = int(self._L.sp_lbo_workspace_bytes(self._h, S, K, int(covpts), conditional, nb))
+                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
+                    one = int(self._L.sp_lbo_workspace_bytes(self._h, 1, K, int(covpts), conditional, nb))
+                    if int(max_workspace_bytes) < one:
+                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
+                                         % (int(max_workspace_bytes), one))
+                    need = int(max_workspace_bytes)
+                workspace = self._grad_ws = self._scratch(need)
+            check(self._L.sp_lbo_ensemble(
+                self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), conditional, int(covpts),
+                self._p(tab), self._p(meanvar), self._p(rta1), TEMPORAL[temporal], int(bool(normalized)),
+                int(norm_order), float(zmax), nb, self._p(ed), self._p(rows), self._p(lpd), self._p(cov),
+                self._p(lnlike), self._p(status), self._p(workspace), int(workspace.numel()), self._stream()))
+        return rows, lpd, cov, lnlike, status
 
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))

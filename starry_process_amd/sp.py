@@ -25,7 +25,7 @@ unimplemented (joss/paper.md:160-172).
 import numpy as np
 
 from .defaults import defaults
-from .engine import get_engine
+from .engine import block_edges, get_engine
 from .flux import FluxIntegral
 from .ops import AlphaBetaOp, CheckBoundsOp, Eager, _is_torch
 from .pixel import latlon_to_xyz, mollweide_grid
@@ -776,6 +776,87 @@ class StarryProcess(object):
         out = self.loo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, i=i, p=p, u=u,
                                 baseline_mean=baseline_mean, baseline_var=baseline_var)
         return {k: v[0] for k, v in out.items()}
+
+    # -- model checking: leave-block-out predictive distributions (sp_lbo_ensemble) -------------------------
+    def lbo_ensemble(self, t, flux, data_cov, block, i=None, p=None, u=None, baseline_mean=0.0, baseline_var=0.0,
+                     return_cov=False, max_workspace_bytes=None):
+        """Leave-block-out predictive checks of S light curves in one device call (h-block cross-validation): what
+        the process, fitted to the cadences OUTSIDE a block B of consecutive ones, predicts for the whole block.
+        Nothing is refitted: with C the covariance ``log_likelihood_ensemble`` factors, r its residual, alpha = C^-1 r
+        and G = (C^-1)_BB = L_G L_G^T,
+
+            cov_B = G^-1    mu_B = flux_B - G^-1 alpha_B    u_B = L_G^-1 alpha_B    (N(0, I) when the model holds)
+            lpd_B = -1/2 u_B^T u_B + sum log (L_G)_ii - b/2 log 2 pi                (log density of the held-out block)
+
+        ``block``: an int b, 1 <= b <= 64 -- blocks of b cadences, the last one shorter -- or a 1-D integer array of
+        edges 0 = e_0 < e_1 < ... < e_nb = K with every width between 1 and 64; the partition is common to all stars.
+        Wider blocks are not served.  The other arguments, the branches and the refusals are ``loo_ensemble``'s.
+        ``mu``, ``var`` and ``cov`` are predictive for the DATA: they include ``baseline_mean`` and the cadences' own
+        noise variance.
+
+        Returns a dict of NumPy arrays: ``mu``, ``var``, ``u``, ``white`` (S, K); ``lpd`` (S, nb); ``elpd`` =
+        lpd.sum(1); ``edges`` (nb + 1,); ``lnlike`` (-inf where ``log_likelihood_ensemble`` gives -inf) and ``status``
+        (S,); with ``return_cov`` also ``cov`` (S, nb, bmax, bmax), bmax the widest block: the block's covariance in the
+        corner of its slot, the rest NaN.  A star whose covariance does not factor has NaN in its rows.
+        ``max_workspace_bytes`` caps the device scratch: the stars are then worked through in groups, with the same
+        bits."""
+        e, f = self._engine, self._flux
+        try:
+            flux = np.asarray(flux, dtype=np.float64)
+            tt = np.asarray(t, dtype=np.float64)
+        except (ValueError, TypeError):
+            raise ValueError("lbo_ensemble does not serve ragged input (lists of light curves of different lengths): "
+                             "pass `t` and `flux` as (S, K) arrays")
+        if flux.ndim != 2:
+            raise ValueError("`flux` must be (S, K)")
+        S, K = flux.shape
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
+            raise NotImplementedError("lbo_ensemble does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
+                                      "(S, K) variances")
+        if np.ndim(baseline_var) >= 2:
+            raise NotImplementedError("lbo_ensemble does not serve a matrix `baseline_var`: pass a scalar or (S,)")
+        edges = block_edges(block, K)
+        t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
+        f._bind()
+        rta1 = e.f64(e.rTA1L(utab))
+        tab = mv = None
+        if self._marginalize_over_inclination:
+            tab, mv = e.kernel_table(rta1, self._covpts)
+        rows, lpd, cov, lnlike, status = e.lbo_ensemble(
+            t, flux, stars, edges, diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts,
+            tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
+            norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
+            max_workspace_bytes=max_workspace_bytes)
+        rows = rows.cpu().numpy()
+        out = {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(("mu", "var", "u", "white"))}
+        out["lpd"] = lpd.cpu().numpy()
+        out["elpd"] = out["lpd"].sum(axis=1)
+        out["edges"] = edges
+        if return_cov:
+            out["cov"] = cov.cpu().numpy()
+        out["lnlike"] = _neg_inf_if_nan(lnlike.cpu().numpy())
+        out["status"] = status.cpu().numpy()
+        return out
+
+    def lbo(self, t, flux, data_cov, block, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]],
+            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"], return_cov=False):
+        """``lbo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances.  The same dict
+        without the leading axis (``edges`` as it is)."""
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim >= 2:
+            raise NotImplementedError("lbo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
+        if np.ndim(baseline_var) >= 1:
+            raise NotImplementedError("lbo does not serve a matrix `baseline_var`: pass a scalar")
+        try:
+            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
+        except (ValueError, TypeError):
+            raise ValueError("`flux` must be one light curve of K cadences")
+        if dc.ndim == 1:
+            dc = dc.reshape(1, -1)
+        out = self.lbo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, block, i=i, p=p, u=u,
+                                baseline_mean=baseline_mean, baseline_var=baseline_var, return_cov=return_cov)
+        return {k: (v if k == "edges" else v[0]) for k, v in out.items()}
 
     # -- posterior of the surface map (sp.py:518-641) -------------------------------------
     # W = Sigma_y^-1 + A^T C^-1 A, ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)), ycov = W^-1,
