@@ -447,8 +447,9 @@ class EnsembleLogProb(object):
             try:
                 self._plan = e0.plan_data(self._t, self._flux, self._stars, covpts=self._kw["covpts"], workspace=self._ws[0])
             except SPError:
-                # (a shape the planned step does not serve -- e.g. a lag grid beyond its LDS budget, covpts > ~4 700:
-                #  the unplanned call has the fallbacks)
+                # (a shape the planned step does not serve -- a lag grid beyond its LDS budget, covpts > 4794, or one
+                #  whose partial tables do not fit the systems' region, covpts > 4092 at K < 64: the unplanned call
+                #  takes it, its assembly reading a table that no LDS holds from memory)
                 self._plan = None
         # Samples go through SampleBatches: packed ceil(64 / S) to a library call when there are fewer than 64 stars (one
         # light curve above all) -- the GPU sees 64 systems per step whatever S is --, one sample per call otherwise; either

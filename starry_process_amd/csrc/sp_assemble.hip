@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void norm_coef_kernel(
 //                   normalisation's vectors, which then ride through the factorisation as three
 //                   more rows (sp.py:705-727 is  c1 Sigma + rank 2;  lnlike_reduce_kernel applies
 //                   the rank-2 (+ baseline) part by the matrix determinant / Woodbury identities).
-template <bool FROM_MATRIX, bool SYSTEM, bool DEFER = false>
+// TABLE_MEM: the table stays in memory (SplineGenMem): a lag grid whose 4 (covpts + 4) coefficients no LDS holds.
+template <bool FROM_MATRIX, bool SYSTEM, bool DEFER = false, bool TABLE_MEM = false>
 __global__ __launch_bounds__(256) void assemble_kernel(
     int K, int M, int Kp, const double *__restrict__ theta,
     const double *__restrict__ t, const sp_star *__restrict__ stars, int covpts,
@@ -221,11 +222,11 @@ __global__ __launch_bounds__(256) void assemble_kernel(
   }
   const int i0 = ti * 64, j0 = tj * 64;
   double *s_tab = lds;                                  // 4 np
-  double *s_thi = lds + (FROM_MATRIX ? 0 : 4 * np);     // 64 each below
+  double *s_thi = lds + ((FROM_MATRIX || TABLE_MEM) ? 0 : 4 * np);     // 64 each below
   double *s_thj = s_thi + 64, *s_ti = s_thj + 64, *s_tj = s_ti + 64;
   double *s_qi = s_tj + 64, *s_qj = s_qi + 64;
   double *s_col = s_qj + 64;   // DEFER: [16][64] column-sum partials
-  if (!FROM_MATRIX) load_tables(tab + (size_t)st.table * 5 * np, np, xp, s_tab);
+  if (!FROM_MATRIX && !TABLE_MEM) load_tables(tab + (size_t)st.table * 5 * np, np, xp, s_tab);
   if (threadIdx.x < 64) {
     const int i = i0 + threadIdx.x;
     const bool ok = i < K;
@@ -242,6 +243,9 @@ __global__ __launch_bounds__(256) void assemble_kernel(
   __syncthreads();
   SplineGen g{s_tab, 2 * np, 6.283185307179586 / covpts,
               1.0 / (6.283185307179586 / covpts), covpts};
+  // (TABLE_MEM: rows a0 .. a3 of the star's table, behind its row yp)
+  SplineGenMem gm{(TABLE_MEM && !FROM_MATRIX) ? tab + (size_t)st.table * 5 * np + np : nullptr, np,
+                  6.283185307179586 / covpts, 1.0 / (6.283185307179586 / covpts), covpts};
   const int nobs = star_nobs(st, K);
   const double var1 = (!FROM_MATRIX && nobs == 1) ? meanvar[2 * st.table + 1] : 0.0;
   double *ob = out + (size_t)s * strideo;
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(256) void assemble_kernel(
         else if (nobs == 1)
           rawv = var1;
         else
-          rawv = g(s_thi[li], s_thj[lj]);
+          rawv = TABLE_MEM ? gm(s_thi[li], s_thj[lj]) : g(s_thi[li], s_thj[lj]);
         rawv *= temporal_factor(temporal, s_ti[li], s_tj[lj], st.tau);
         if (DEFER) {
           val = rawv;
@@ -755,7 +759,13 @@ int sp_launch_norm_coef(const SpProblem &P, const double *condmean, const double
 int sp_launch_assemble(const SpProblem &P, const double *theta, const double *raw, const double *qv, const void *coef,
                        const SpAsmOut &o, double *part, int lazy_nfull) {
   const int np = P.covpts + 4, system = o.system;
-  const size_t lds = sizeof(double) * ((raw ? 0 : 4 * (size_t)np) + 6 * 64 + (part ? 16 * 64 : 0));
+  const size_t fixed = sizeof(double) * (6 * 64 + (part ? 16 * 64 : 0));
+  size_t lds = fixed + sizeof(double) * (raw ? 0 : 4 * (size_t)np);
+  // A table no LDS holds (covpts > 4444): the deferred form reads its coefficients from memory -- what a caller falls
+  // back to when sp_plan_data refuses the grid (covpts > 4796; calibrate.EnsembleLogProb).  The direct normalisation's
+  // row sums have no such form: that route refuses (sp_launch_rowsum).
+  const bool table_mem = lds > attr_lds_limit && part && !raw && system && P.tab;
+  if (table_mem) lds = fixed;
   if (lds > attr_lds_limit) return SP_ERR_INVALID;
   const int ntr = ((system ? o.Kp : P.K) + 63) / 64;
   const int ntiles = system ? ntr * (ntr + 1) / 2 : ntr * ntr;
@@ -771,6 +781,8 @@ int sp_launch_assemble(const SpProblem &P, const double *theta, const double *ra
   if (part && !system) return SP_ERR_INVALID;
   if (part && raw)
     SP_ASM(true, true, true);
+  else if (table_mem)
+    SP_ASM(false, true, true, true);
   else if (part)
     SP_ASM(false, true, true);
   else if (raw && system)

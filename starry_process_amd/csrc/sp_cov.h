@@ -155,6 +155,30 @@ struct SplineGen {
 };
 
 
+// The same lookup with the coefficients read from the kernel table in MEMORY (its rows a0 .. a3 of np entries each, as
+// sp_kernel_table wrote them): for lag grids whose table no LDS holds (the general assembly beyond covpts = 4444).  The
+// index and the Horner chain are SplineGen::operator()'s, operation for operation: the same bits.
+struct SplineGenMem {
+  const double *a;     // a0 at a, a1 at a + np, a2 at a + 2 np, a3 at a + 3 np; segments 0 .. covpts hold coefficients
+  int np;
+  double dx, inv_dx;
+  int covpts;
+  __device__ __forceinline__ double operator()(double thi, double thj) const {
+#pragma clang fp contract(off)
+    const double x = fabs(thi - thj);
+    const double q = x * inv_dx;
+    int idx = (int)q;
+    double x0 = q - (double)idx;
+    if (fabs(x0 - 0.5) > 0.5 - 1.0e-9) {
+      idx = (int)floor(x / dx);
+      x0 = q - (double)idx;
+    }
+    idx = idx > covpts ? covpts : (idx < 0 ? 0 : idx);      // (a load from memory: clamped on both sides)
+    const double c0 = a[idx], c1 = a[np + idx], c2 = a[2 * np + idx], c3 = a[3 * np + idx];
+    return __builtin_fma(x0, __builtin_fma(x0, __builtin_fma(x0, c3, c2), c1), c0);
+  }
+};
+
 // the star's packed table (theta_kernel: [np][2] = {a0, a1}, then [np][2] = {a2, a3}) into LDS, all 256 threads:
 // every load is issued before the first store (a plain copy loop waits out one memory round trip per
 // iteration -- the compiler keeps load, wait, store together)

@@ -141,7 +141,9 @@ int sp_plan_data(sp_handle *h, int S, int K, int M, const double *t_dev, const d
   const size_t Kp = (size_t)sp_roundup(K + M, SP_NB);
   if (ws_bytes < 0 || (size_t)ntl * np > Kp * Kp) return SP_ERR_INVALID;
   const size_t lds = sizeof(double) * 4 * (size_t)np;
-  if (lds > 150 * 1024) return SP_ERR_INVALID;
+  // (the planned assembly keeps 8 doubles of reduction scratch beside the same table, sp_launch_assemble_planned: a
+  //  grid it could not take -- covpts 4795 and 4796 fit here alone -- is refused now, while the caller can still fall back)
+  if (lds + sizeof(double) * 8 > 150 * 1024) return SP_ERR_INVALID;
   // (the systems are the last region of the workspace: S Kp'^2 doubles with Kp' >= Kp)
   double *partial = reinterpret_cast<double *>(static_cast<char *>(workspace_dev) + (size_t)ws_bytes) - (size_t)S * Kp * Kp;
 

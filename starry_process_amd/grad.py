@@ -37,7 +37,7 @@ from .stars import check_period_inclination, ensemble_stars
 from .temporal import kernel_id
 
 __all__ = ["EnsembleGradient", "ensemble_gradient", "log_likelihood_with_grad", "hyper_gradient",
-           "EnsembleFisher", "ensemble_fisher", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional",
+           "EnsembleFisher", "ensemble_fisher", "fisher_max_covpts", "cramer_rao", "EnsembleGradientConditional", "ensemble_gradient_conditional_device", "ensemble_gradient_conditional",
            "EnsembleFisherConditional", "ensemble_fisher_conditional", "cramer_rao_ensemble"]
 
 _cache = {}
@@ -672,6 +672,13 @@ def _check_params(params, has_dr):
     return params
 
 
+def fisher_max_covpts(P):
+    """The largest lag grid ``covpts`` the Fisher sweep serves for P parameters: its tangent kernel keeps P + 1 tables
+    of covpts + 4 doubles beside 1152 doubles of tile vectors in 60 KB of LDS (sp_fisher_marginal refuses beyond) --
+    1084 for P = 5, 928 for P = 6 (r, a, b, c, n and dr)."""
+    return (60 * 1024 // 8 - 1152) // (int(P) + 1) - 4
+
+
 class EnsembleFisher(_MarginalSweep):
     """Expected (Fisher) information of an ENSEMBLE of light curves about the spot hyperparameters, in one device sweep
     and without any flux: how well S light curves with these cadences, periods and noise CAN constrain (r, a, b, c, n
@@ -726,6 +733,11 @@ class EnsembleFisher(_MarginalSweep):
         import torch
 
         names = _check_params(params, dr is not None)
+        if self._covpts > fisher_max_covpts(len(names)):        # (before anything goes to the device)
+            raise ValueError("EnsembleFisher: covpts = %d is beyond the Fisher sweep's limit for %d parameters, "
+                             "covpts <= %d (P + 1 tables of covpts + 4 doubles in 60 KB of LDS); name fewer ``params`` "
+                             "or build the object with a smaller covpts" %
+                             (self._covpts, len(names), fisher_max_covpts(len(names))))
         e = self._e
         tab, mv, point = self._at_point(r, a, b, c, n, dr)
         dy, dm, events = self._table_tangents(*point)

@@ -35,7 +35,8 @@ U = np.array([[0.3, 0.2], [0.5, 0.1], [0.3, 0.2]])   # two limb-darkening tables
 H = 1.0e-4
 # The yardstick's own uncertainty: max over CASES (and the spread-of-radii case), stars and entries of
 # |F(H) - F(H / 2)| / sqrt(F_ii F_jj), both from the oracle on the CPU; printed by ``python tests/test_gpu_fisher.py``
-# (per case 1.7e-8 .. 3.2e-7, the spread-of-radii case 5.05e-7; the tangents themselves differ by 1e-9 of their scale).
+# (per case 1.7e-8 .. 3.2e-7 -- the two cases on larger lag grids, covpts 999 and 1084: 6.8e-8 and 2.8e-8 --, the
+# spread-of-radii case 5.05e-7; the tangents themselves differ by 1e-9 of their scale).
 DELTA_YARDSTICK = 5.05e-7
 TOL = 10.0 * DELTA_YARDSTICK
 
@@ -48,6 +49,11 @@ CASES = [
     dict(id="norm-tau3-K63", K=63, normalized=True, tau=3.0),
     dict(id="norm-tau3-K130", K=130, normalized=True, tau=3.0),
     dict(id="norm-var-baseline-K65", K=65, normalized=True, percadence=True, baseline_var=2.0e-5),
+    # the lag grid (a case without "covpts" runs at the default 300): 999 is calibrate's covpts = K - 1 at the reference's
+    # npts = 1000; 1084 is the largest grid the sweep serves for five parameters (grad.fisher_max_covpts: the tangent
+    # kernel's six tables of covpts + 4 doubles and 1152 doubles of tile vectors fill its 60 KB of LDS to 6528 + 1152)
+    dict(id="norm-K130-covpts999", K=130, normalized=True, covpts=999),
+    dict(id="norm-K65-covpts1084", K=65, normalized=True, covpts=1084),
 ]
 DR_CASE = dict(id="norm-dr-K65", K=65, normalized=True, dr=5.0)
 
@@ -90,7 +96,7 @@ def _oracle_C(case, hp, s):
 
     mu, Sig = _oracle_moments(hp)
     op = orc.OracleProcess(mu, Sig, ydeg=YDEG, udeg=2, normalized=case["normalized"], tau=case.get("tau"),
-                           temporal_kernel=orc.Matern32Kernel)
+                           temporal_kernel=orc.Matern32Kernel, covpts=case.get("covpts", 300))
     t = _times(case["K"])[s]
     C = op.cov(t, p=PERIODS[s], u=U[s])
     var = np.broadcast_to(np.asarray(_ferr(case)) ** 2, (3, case["K"]))[s]
@@ -167,7 +173,7 @@ def _fisher(case, stars=slice(None), **kw):
     t, ferr = _times(case["K"])[stars], _ferr(case)
     ferr = ferr[stars] if np.ndim(ferr) == 2 else ferr
     return EnsembleFisher(t, ferr=ferr, p=PERIODS[stars], u=U[stars], ydeg=YDEG, normalized=case["normalized"],
-                          tau=case.get("tau"), baseline_var=case.get("baseline_var", 0.0), **kw)
+                          tau=case.get("tau"), baseline_var=case.get("baseline_var", 0.0), covpts=case.get("covpts"), **kw)
 
 
 def _hp(case):
@@ -196,7 +202,7 @@ def test_tangents_and_fisher_match_the_oracle(case):
         assert w[0] >= -TOL * w[-1], (s, w)
 
 
-@pytest.mark.parametrize("case", [CASES[1], CASES[4], CASES[6], CASES[7]], ids=lambda c: c["id"])
+@pytest.mark.parametrize("case", [CASES[1], CASES[4], CASES[6], CASES[7], CASES[8], CASES[9]], ids=lambda c: c["id"])
 def test_bits(case):
     ef = _fisher(case)
     F = ef(**HP)
@@ -217,9 +223,10 @@ def test_bits(case):
     from starry_process_amd.engine import get_engine
 
     e = get_engine(YDEG, 2)
+    covpts = case.get("covpts", 300)
     for fit in (2, 1):
-        nbytes = int(e._L.sp_fisher_workspace_bytes(e._h, fit, case["K"], 5, 300))
-        assert nbytes < int(e._L.sp_fisher_workspace_bytes(e._h, 3, case["K"], 5, 300))
+        nbytes = int(e._L.sp_fisher_workspace_bytes(e._h, fit, case["K"], 5, covpts))
+        assert nbytes < int(e._L.sp_fisher_workspace_bytes(e._h, 3, case["K"], 5, covpts))
         eg = _fisher(case, max_workspace_bytes=nbytes)
         assert np.array_equal(eg(**HP), F) and np.array_equal(eg.per_star, per_star), fit
     # a subset of the parameters: that sub-block
@@ -249,6 +256,49 @@ def test_spread_of_radii():
     assert np.all(err < TOL), err
     with pytest.raises(ValueError):
         ef(params=names, **HP)              # "dr" named without a spread
+
+
+def test_lag_grids_beyond_the_sweeps_limit_are_refused_before_any_device_work():
+    """The tangent kernel keeps P + 1 tables of covpts + 4 doubles and 1152 doubles of tile vectors in 60 KB of LDS
+    (sp_fisher.hip, sp_fisher_marginal): covpts <= 1084 for P = 5, <= 928 for P = 6 -- so ``dr`` free is refused at
+    calibrate's covpts = 999.  The refusal is a ValueError that names the limit, raised before the tables are
+    evaluated; results of an earlier call stay as they were, and the same object serves the next call that fits."""
+    from starry_process_amd.grad import fisher_max_covpts
+
+    lds = 60 * 1024 // 8
+    for P, limit in ((5, 1084), (6, 928)):
+        assert fisher_max_covpts(P) == limit
+        assert (P + 1) * (limit + 4) + 1152 <= lds < (P + 1) * (limit + 1 + 4) + 1152
+    base = dict(K=65, normalized=True)
+    # covpts = 1085 at P = 5
+    ef = _fisher(dict(base, covpts=1085))
+    sub = ef(params=("a", "b"), **HP)                       # (two parameters fit: three tables)
+    per_star, status = ef.per_star.copy(), ef.status.copy()
+    assert not status.any() and np.all(np.isfinite(sub))
+    ef._tables = ef._at_point = None                        # (the refusal must come before either is called)
+    with pytest.raises(ValueError, match=r"covpts = 1085 .* 5 parameters, covpts <= 1084"):
+        ef(**HP)
+    del ef._tables, ef._at_point
+    assert np.array_equal(ef.per_star, per_star) and np.array_equal(ef.status, status) and ef.names == ("a", "b")
+    assert np.array_equal(ef(params=("a", "b"), **HP), sub)
+    # the raw entry point's own answer, should a caller get past the facade: SP_ERR_INVALID, nothing launched
+    import torch
+
+    e = ef._e
+    with torch.cuda.stream(ef._stream):
+        tab, mv = e.kernel_table(ef._rta1, 1085)
+        z = e.empty(5, tab.shape[0], 1089).zero_()
+        with pytest.raises(Exception, match="libsp_hip"):
+            e.fisher_marginal(ef._t, ef._stars, tab, mv, z, e.empty(5, tab.shape[0]).zero_(), covpts=1085)
+    torch.cuda.synchronize()
+    assert np.array_equal(ef(params=("a", "b"), **HP), sub)
+    # covpts = 999 with dr free (P = 6); the five parameters without it are served (CASES: norm-K130-covpts999)
+    ef = _fisher(dict(base, covpts=999), h=2.0e-5)
+    with pytest.raises(ValueError, match=r"covpts = 999 .* 6 parameters, covpts <= 928"):
+        ef(params=NAMES + ("dr",), **dict(HP, dr=5.0))
+    assert ef.status is None and ef.per_star is None
+    F = ef(**HP)
+    assert F.shape == (5, 5) and not ef.status.any() and np.all(np.isfinite(F))
 
 
 def _device_inputs(case, hp=HP):

@@ -4,7 +4,10 @@ timescale, baseline mean, baseline variance and the log of a common factor on th
 the batch from the one device sweep.
 
   * the outputs the new call shares with sp_lnlike_grad_marginal_multi are that call's;
-  * the raw process against the EXACT contractions <G, dC/d.> formed in NumPy from the oracle's pieces (no step size);
+  * the raw process against the EXACT contractions <G, dC/d.> formed in NumPy from the oracle's pieces (no step size),
+    the table's adjoint ybar among them, also over the lag grid: covpts 999 (calibrate's), 1916 and 1917 (the last grid
+    with a copy of the scatter's bins per wavefront, the first with a single copy); a grid beyond the sweep's LDS is
+    refused;
   * normalised and raw against Richardson differences of the oracle's log-likelihood;
   * period and timescale against the one-star autograd chain (grad.log_likelihood_with_grad), an independent device route;
   * rejected and ragged stars, sizes off the tile grid, two limb-darkening tables, bad arguments, determinism.
@@ -30,7 +33,7 @@ def _moments():
 
 
 def _case(S=3, K=96, M=1, normalized=True, tau=None, per_cadence=False, bvar=0.0, bmean=0.0, seed0=0, u=None,
-          tspan=4.0, kernel="matern32"):
+          tspan=4.0, kernel="matern32", covpts=COVPTS):
     sts = [synthetic_star(seed0 + s, K, tspan) for s in range(S)]
     t = np.array([s["t"] for s in sts])
     if M == 1:
@@ -44,7 +47,7 @@ def _case(S=3, K=96, M=1, normalized=True, tau=None, per_cadence=False, bvar=0.0
         var = np.array([np.linspace(1e-6, 3e-6, K) * (1.0 + 0.25 * s) for s in range(S)])
     else:
         var = np.full(S, 1e-6)
-    return dict(S=S, K=K, M=M, t=t, flux=flux, p=p, var=var, normalized=normalized, tau=tau, kernel=kernel,
+    return dict(S=S, K=K, M=M, t=t, flux=flux, p=p, var=var, normalized=normalized, tau=tau, kernel=kernel, covpts=covpts,
                 bvar=np.broadcast_to(np.asarray(bvar, dtype=float), (S,)).copy(),
                 bmean=np.broadcast_to(np.asarray(bmean, dtype=float), (S,)).copy(),
                 u=np.zeros((S, 2)) if u is None else np.asarray(u, dtype=float))
@@ -62,7 +65,8 @@ def _device(case, stars_kw=None, new=True, old=True, mom=None, oracle_table=Fals
     else:
         e.set_moments_dev(*mom)
     utab, table = np.unique(case["u"], axis=0, return_inverse=True)
-    tab, mv = e.kernel_table(e.f64(e.rTA1L(utab)), COVPTS)
+    covpts = case.get("covpts", COVPTS)
+    tab, mv = e.kernel_table(e.f64(e.rTA1L(utab)), covpts)
     if oracle_table:
         tnp, mnp = tab.cpu().numpy().copy(), mv.cpu().numpy().copy()
         for k in range(utab.shape[0]):
@@ -82,7 +86,7 @@ def _device(case, stars_kw=None, new=True, old=True, mom=None, oracle_table=Fals
     stars = e.stars_to_device(make_stars(S, **kw))
     diag = e.f64(np.ascontiguousarray(case["var"])) if case["var"].ndim == 2 else None
     args = (e.f64(case["t"]), e.f64(np.ascontiguousarray(case["flux"])), stars, tab, mv)
-    okw = dict(diag=diag, covpts=COVPTS, temporal=case["kernel"] if case["tau"] else None,
+    okw = dict(diag=diag, covpts=covpts, temporal=case["kernel"] if case["tau"] else None,
                normalized=case["normalized"])
     a = [x.cpu().numpy() for x in e.lnlike_grad_marginal(*args, **okw)] if old else None
     b = [x.cpu().numpy() for x in e.lnlike_grad_marginal_stars(*args, **okw)] if new else None
@@ -95,7 +99,7 @@ def _process(case, s, mom=None):
     mu, Sig = _moments() if mom is None else mom
     tk = orc.Matern32Kernel if case["kernel"] == "matern32" else orc.ExpSquaredKernel
     return orc.OracleProcess(mu, Sig, ydeg=YDEG, udeg=2, normalized=case["normalized"], tau=case["tau"],
-                             temporal_kernel=tk, covpts=COVPTS)
+                             temporal_kernel=tk, covpts=case.get("covpts", COVPTS))
 
 
 def _oracle_lnlike(case, s, p=None, tau=None, bmean=None, bvar=None, logvar=0.0):
@@ -107,13 +111,43 @@ def _oracle_lnlike(case, s, p=None, tau=None, bmean=None, bvar=None, logvar=0.0)
                              baseline_var=float(case["bvar"][s] if bvar is None else bvar))
 
 
-def exact_raw_starbar(case, s):
-    """(lnL, [d/dp, d/dtau, d/dbaseline_mean, d/dbaseline_var, d/dlog_var]) of star s of a RAW (un-normalised) case,
-    in NumPy from the oracle's pieces: G = (sum_m alpha_m alpha_m^T - M C^-1) / 2 contracted with dC/d. built entry by
-    entry; the period through the derivative of the cubic inside its segment (interpolate_cov's index and x0)."""
+def _chol_in(C):
+    """Lower Cholesky factor in the array's own precision (np.linalg has no long double)."""
+    K = C.shape[0]
+    L = np.zeros_like(C)
+    for j in range(K):
+        L[j, j] = np.sqrt(C[j, j] - np.dot(L[j, :j], L[j, :j]))
+        L[j + 1:, j] = (C[j + 1:, j] - np.dot(L[j + 1:, :j], L[j, :j])) / L[j, j]
+    return L
+
+
+def _chol_solve_in(L, B):
+    """(L L^T)^-1 B by substitution in the arrays' own precision."""
+    K = L.shape[0]
+    Y = np.zeros_like(B)
+    for i in range(K):
+        Y[i] = (B[i] - np.dot(L[i, :i], Y[:i])) / L[i, i]
+    X = np.zeros_like(B)
+    for i in range(K - 1, -1, -1):
+        X[i] = (Y[i] - np.dot(L[i + 1:, i], X[i + 1:])) / L[i, i]
+    return X
+
+
+def exact_raw(case, s, dtype=np.float64):
+    """(lnL, [d/dp, d/dtau, d/dbaseline_mean, d/dbaseline_var, d/dlog_var], ybar [covpts + 4]) of star s of a RAW
+    (un-normalised) case, in NumPy from the oracle's pieces: G = (sum_m alpha_m alpha_m^T - M C^-1) / 2 contracted with
+    dC/d. built entry by entry; the period through the derivative of the cubic inside its segment (interpolate_cov's
+    index and x0); the table's adjoint ybar[k] = sum_ij G_ij T_ij b_{k - idx_ij}(x0_ij), b the cubic's weights of the
+    four table entries around a lag (those of test_gpu_planned.numpy_wbar).
+
+    dtype = np.float64: the oracle's own arithmetic (its cho_factor / cho_solve).  dtype = np.longdouble: the table, the
+    times and the segment indices are the same fp64 numbers, everything after them -- the interpolation, the temporal
+    factor, C, its factorisation, the solves, G and the contractions -- in long double (the yardstick of
+    YBAR_YARDSTICK)."""
     import oracle.sp_oracle as orc
 
     assert not case["normalized"]
+    ld = dtype != np.float64
     op = _process(case, s)
     t, p, K = case["t"][s], float(case["p"][s]), case["K"]
     mean, Sigma = op.flux_mean_cov(t, p=p, u=case["u"][s])
@@ -122,29 +156,55 @@ def exact_raw_starbar(case, s):
     dth = theta[:, None] - theta[None, :]
     x = np.abs(dth).reshape(-1)
     inds = np.floor(x / tab["dx"]).astype("int64")
-    x0 = (x - tab["xp"][inds + 1]) / tab["dx"]
-    ds = ((tab["a1"][inds] + 2.0 * tab["a2"][inds] * x0 + 3.0 * tab["a3"][inds] * x0 ** 2) / tab["dx"]).reshape(K, K)
-    dxdp = np.sign(dth) * (-2.0 * np.pi / p ** 2) * (t[:, None] - t[None, :])
-    T, dT = np.ones((K, K)), np.zeros((K, K))
+    if ld:
+        dx = 2 * np.pi / dtype(op.covpts)              # (2 pi / covpts as fp64 rounds it, then exact)
+        a = [tab[k].astype(dtype) for k in ("a0", "a1", "a2", "a3")]
+        x0 = x.astype(dtype) / dx - inds                # (xp[k] = (k - 1) dx, flux.py:312-314)
+        Sigma = (a[0][inds] + x0 * (a[1][inds] + x0 * (a[2][inds] + x0 * a[3][inds]))).reshape(K, K)
+        t = t.astype(dtype)
+        mean = dtype(mean)
+    else:
+        dx = tab["dx"]
+        a = [tab[k] for k in ("a0", "a1", "a2", "a3")]
+        x0 = (x - tab["xp"][inds + 1]) / dx
+    ds = ((a[1][inds] + 2.0 * a[2][inds] * x0 + 3.0 * a[3][inds] * x0 ** 2) / dx).reshape(K, K)
+    dxdp = np.sign(dth) * (-2.0 * np.pi / dtype(p) ** 2) * (t[:, None] - t[None, :])
+    T, dT = np.ones((K, K), dtype), np.zeros((K, K), dtype)
     if case["tau"]:
-        tau = float(case["tau"])
-        T = op.temporal_kernel(t, t, tau)
+        tau = dtype(case["tau"])
         dt = np.abs(t[:, None] - t[None, :])
         if case["kernel"] == "matern32":
-            xx = np.sqrt(3.0) * dt / tau
+            xx = np.sqrt(dtype(3.0)) * dt / tau
+            T = (1.0 + xx) * np.exp(-xx) if ld else op.temporal_kernel(t, t, float(tau))
             dT = xx ** 2 / tau * np.exp(-xx)
         else:
+            T = np.exp(-dt ** 2 / (2.0 * tau)) if ld else op.temporal_kernel(t, t, float(tau))
             dT = dt ** 2 / (2.0 * tau ** 2) * T
-    D = np.diag(np.broadcast_to(case["var"][s], (K,)))
-    C = Sigma * T + D + case["bvar"][s]
-    L = orc.cho_factor(C)
-    r = case["flux"][s].reshape(-1, K).T - (mean + case["bmean"][s])
+    D = np.diag(np.broadcast_to(case["var"][s], (K,))).astype(dtype)
+    C = Sigma * T + D + dtype(case["bvar"][s])
+    r = (case["flux"][s].reshape(-1, K).T.astype(dtype) - (mean + dtype(case["bmean"][s])))
     M = r.shape[1]
-    al = orc.cho_solve(L, r)
-    Cinv = orc.cho_solve(L, np.eye(K))
-    lnl = -0.5 * np.sum(r * al) - M * np.sum(np.log(np.diag(L))) - 0.5 * K * M * np.log(2 * np.pi)
+    if ld:
+        L = _chol_in(C)
+        al, Cinv = _chol_solve_in(L, r), _chol_solve_in(L, np.eye(K, dtype=dtype))
+    else:
+        L = orc.cho_factor(C)
+        al, Cinv = orc.cho_solve(L, r), orc.cho_solve(L, np.eye(K))
+    lnl = -0.5 * np.sum(r * al) - M * np.sum(np.log(np.diag(L))) - 0.5 * K * M * np.log(2 * dtype(np.pi))
     G = 0.5 * (al @ al.T - M * Cinv)
-    return lnl, np.array([np.sum(G * ds * dxdp * T), np.sum(G * Sigma * dT), np.sum(al), np.sum(G), np.sum(G * D)])
+    x2, x3 = x0 * x0, x0 ** 3
+    b = [-x0 / 3 + x2 / 2 - x3 / 6, 1 - x0 / 2 - x2 + x3 / 2, x0 + x2 / 2 - x3 / 2, -x0 / 6 + x3 / 6]
+    gt = (G * T).reshape(-1)
+    ybar = np.zeros(op.covpts + 4, dtype)
+    for k in range(4):
+        np.add.at(ybar, inds + k, b[k] * gt)
+    sbar = np.array([np.sum(G * ds * dxdp * T), np.sum(G * Sigma * dT), np.sum(al), np.sum(G), np.sum(G * D)])
+    return lnl, sbar, ybar
+
+
+def exact_raw_starbar(case, s):
+    """(lnL, the five per-star derivatives) of ``exact_raw`` in fp64."""
+    return exact_raw(case, s)[:2]
 
 
 def _central(f, h):
@@ -228,20 +288,60 @@ def test_wrt_none_is_todays_call_and_wrt_adds_keys():
 
 
 # ---- 3. the raw process against the exact contractions -----------------------------------------------------------
-@pytest.mark.parametrize("kw", [dict(M=1, tau=None, K=96), dict(M=2, tau=0.7, K=100, per_cadence=True, bvar=1e-5),
-                                dict(M=1, tau=2.0, K=100, kernel="expsquared", bmean=1e-3),
-                                dict(M=1, tau=None, K=64)],
-                         ids=["M1-K96", "M2-matern-K100-diag-bvar", "expsquared-K100-bmean", "K64"])
+_RAW_BASE = {"M1-K96": dict(M=1, tau=None, K=96), "M2-matern-K100-diag-bvar": dict(M=2, tau=0.7, K=100, per_cadence=True, bvar=1e-5),
+             "expsquared-K100-bmean": dict(M=1, tau=2.0, K=100, kernel="expsquared", bmean=1e-3), "K64": dict(M=1, tau=None, K=64)}
+# The sweep over the lag grid: 999 is the reference's calibration grid (calibrate/log_prob.py:46 at npts = 1000); the
+# scatter keeps one copy of its covpts + 4 bins per wavefront while four fit 60 KB of LDS, covpts <= 1916, and a single
+# copy from 1917 on (sp_grad.hip, sp_launch_grad_sweep); grad_stars_kernel stages yp[covpts + 4] whatever its size.
+RAW_CASES = dict(_RAW_BASE)
+for _name in ("M1-K96", "M2-matern-K100-diag-bvar"):
+    for _covpts in (999, 1916, 1917):
+        RAW_CASES["%s-covpts%d" % (_name, _covpts)] = dict(_RAW_BASE[_name], covpts=_covpts)
+# The fp64 reference's own error in ybar: the largest |ybar(fp64) - ybar(long double)| / max |ybar| over RAW_CASES and
+# their stars, both from ``exact_raw`` on the CPU; printed by ``python tests/test_gpu_grad_stars.py`` (per case in
+# _measure_ybar_yardstick's docstring).  The test allows ten times that: device and NumPy solve the same ill-conditioned
+# system in fp64 in different orders of operation, and the device's LDS additions arrive in no fixed order
+# (test_shared_outputs_are_the_old_calls measured run-to-run differences of 2e-9 to 7e-8 absolute).
+YBAR_YARDSTICK = 4.21e-12
+
+
+def _measure_ybar_yardstick():
+    """Measured: M1-K96 2.3e-12 .. 4.2e-12 (at covpts 999, 1916, 1917: 2.2e-12 .. 4.0e-12), M2-matern-K100-diag-bvar
+    1.5e-13 .. 3.2e-13 (at the larger grids 5e-14 .. 1.3e-12), expsquared-K100-bmean 7.8e-13 .. 2.4e-12, K64 9.7e-13 ..
+    2.2e-12, max |ybar| between 3e6 and 1.7e7; lnL and the five per-star slots move by 5e-14 and 1.2e-11 of their
+    scales at most."""
+    worst = 0.0
+    for name, kw in RAW_CASES.items():
+        case = _case(normalized=False, **kw)
+        errs = []
+        for s in range(case["S"]):
+            l64, s64, y64 = exact_raw(case, s)
+            lld, sld, yld = exact_raw(case, s, np.longdouble)
+            errs.append(float(np.abs(y64 - yld).max() / np.abs(yld).max()))
+            print("%-36s star %d  ybar: %.3g of max |ybar| = %.3g   lnL: %.3g   starbar: %s" % (
+                name, s, errs[-1], float(np.abs(yld).max()), float(abs(l64 / lld - 1)),
+                " ".join("%.2g" % float(abs(a - b) / max(abs(b), 1e-3 * abs(lld))) for a, b in zip(s64, sld))))
+        worst = max(worst, max(errs))
+    print("YBAR_YARDSTICK = %.3g" % worst)
+
+
+@pytest.mark.parametrize("kw", list(RAW_CASES.values()), ids=list(RAW_CASES))
 def test_raw_process_equals_the_exact_contractions(kw):
     """Device and NumPy contract the SAME kernel table (the oracle's, uploaded: the table is an input of the entry
     point).  d/dp reads the table through its first differences: with each side on its own table -- they agree to a few
     1e-14 of the table's scale -- the two periods' derivatives differ by up to 8e-8 absolute (4e-9 of the value) on the
     star whose period puts its lags on the knots, measured on the MI355X; long-double solves on the host move the NumPy
-    statement by 3e-10 at most, so that difference is the tables', not the sweep's."""
+    statement by 3e-10 at most, so that difference is the tables', not the sweep's.
+
+    ybar, the table's adjoint (grad_scatter_kernel: the only check of it against something other than itself),
+    against the same G: within 10 YBAR_YARDSTICK of max |ybar|.  Measured on the MI355X: between 9e-14 and
+    1.0e-11 of max |ybar| (0.00 to 0.24 of the bound; the largest on M1-K96 at covpts 1916, star 0), at 300 as on the
+    larger grids, four copies of the bins or one."""
     case = _case(normalized=False, **kw)
     _, b = _device(case, old=False, oracle_table=True)
+    assert b[1].shape == (case["S"], case["covpts"] + 4)
     for s in range(case["S"]):
-        lnl, ref = exact_raw_starbar(case, s)
+        lnl, ref, yref = exact_raw(case, s)
         assert abs(b[0][s] - lnl) < 1e-9 * abs(lnl)
         for k, name in enumerate(SLOTS):
             err = abs(b[3][s, k] - ref[k])
@@ -251,6 +351,10 @@ def test_raw_process_equals_the_exact_contractions(kw):
         assert b[3][s, 5] == 0.0
         if not case["tau"]:
             assert b[3][s, 1] == 0.0
+        yerr = np.abs(b[1][s] - yref).max() / np.abs(yref).max()
+        print("star %d ybar off by %.3g of max |ybar| = %.3g (%.2f of the bound)" % (
+            s, yerr, np.abs(yref).max(), yerr / (10.0 * YBAR_YARDSTICK)))
+        assert yerr <= 10.0 * YBAR_YARDSTICK, (s, yerr)
 
 
 # ---- 4. finite differences of the oracle ------------------------------------------------------------------------
@@ -380,6 +484,46 @@ def test_the_new_entry_point_refuses_bad_arguments():
     assert np.all(np.isfinite(sb.cpu().numpy()))
 
 
+def test_a_lag_grid_beyond_the_sweeps_lds_is_refused():
+    """covpts = 7677: the scatter's covpts + 4 bins are 61 448 bytes, above its 60 KB of LDS (7676 is the last that
+    fits) -- SP_ERR_INVALID from the raw ABI with the table built for that grid (so not SP_ERR_STATE), no fault, and the
+    handle serves the next call.  (The first refusal the call meets at this size is the assembly's, whose table of
+    4 (covpts + 4) doubles exceeds its 150 KB of LDS: only the phases' kernel has been launched by then.)"""
+    import torch
+    from starry_process_amd import _lib
+    from starry_process_amd.engine import get_engine, make_stars
+
+    e = get_engine(YDEG, 2)
+    L = _lib.lib()
+    e.set_moments(*_moments())
+    big = 7677
+    assert 8 * (big + 4) > 60 * 1024 >= 8 * (big - 1 + 4)
+    K, S, M = 64, 1, 2
+    st = synthetic_star(0, K)
+    t, f = e.f64(st["t"][None, :]), e.f64(np.stack([st["flux"], st["flux"][::-1]])[None])
+    stars = e.stars_to_device(make_stars(S, period=1.0, data_var=1e-6))
+    out, mb, sb = e.empty(S), e.empty(S), e.empty(S, 6)
+
+    def sweep(covpts, tab, mv):
+        ws = e.grad_workspace(S, K, covpts, M)
+        yb = e.empty(S, covpts + 4)
+        rc = L.sp_lnlike_grad_marginal_stars(e._h, S, K, M, e._p(t), e._p(f), None, e._p(stars), covpts, e._p(tab),
+                                             e._p(mv), 0, 1, 20, ctypes.c_double(0.023), e._p(ws), e._p(out), e._p(yb),
+                                             e._p(mb), None, e._p(sb), e._stream())
+        torch.cuda.synchronize()
+        return rc
+
+    tab, mv = e.kernel_table(e.f64(e.rTA1L([0.0, 0.0])), COVPTS)
+    assert sweep(COVPTS, tab, mv) == 0
+    good = (out.cpu().numpy().copy(), sb.cpu().numpy().copy())
+    tab_big, mv_big = e.kernel_table(e.f64(e.rTA1L([0.0, 0.0])), big)
+    assert sweep(big, tab_big, mv_big) == -1                 # SP_ERR_INVALID
+    assert sweep(COVPTS, tab, mv) == -4                      # (the handle's grid is still the refused call's)
+    tab, mv = e.kernel_table(e.f64(e.rTA1L([0.0, 0.0])), COVPTS)
+    assert sweep(COVPTS, tab, mv) == 0
+    assert _bits(out.cpu().numpy(), good[0]) and _bits(sb.cpu().numpy(), good[1]) and np.all(np.isfinite(good[1]))
+
+
 # ---- 7. determinism --------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("S,K,M", [(3, 100, 2), (2, 1000, 1)])
 def test_starbar_is_bit_stable(S, K, M):
@@ -387,3 +531,7 @@ def test_starbar_is_bit_stable(S, K, M):
     _, b1 = _device(case, old=False)
     _, b2 = _device(case, old=False)
     assert _bits(b1[3], b2[3]) and np.all(np.isfinite(b1[3]))
+
+
+if __name__ == "__main__":
+    _measure_ybar_yardstick()

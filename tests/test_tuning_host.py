@@ -96,6 +96,61 @@ def test_planned_shape_reproduces_the_recorded_decisions():
     assert L.sp_debug_planned_shape(None, _lib.hptr(o)) == -1 and L.sp_debug_planned_shape(_lib.hptr(bad), _lib.hptr(o)) == -1
 
 
+SHAPE_OUT = ("lazy_nfull", "ncolw", "no_panels", "riding", "nrid", "dlazy", "dfrom", "fuse0", "use_ptab", "small_k",
+             "superpanel", "fuses_reduce", "can_form_diag")
+
+
+def planned_shape(ydeg, K, covpts, M=1, temporal=0, has_diag=0, **switches):
+    """sp_debug_planned_shape's outputs by name, every switch at the library's default unless given"""
+    assert set(switches) <= {n for n, _, _ in SWITCHES}
+    a = np.array([ydeg, K, M, covpts, temporal, has_diag] + [switches.get(n, -1) for n, _, _ in SWITCHES], np.int32)
+    o = np.full(len(SHAPE_OUT), -7, np.int32)
+    assert _lib.lib().sp_debug_planned_shape(_lib.hptr(a), _lib.hptr(o)) == 0
+    return dict(zip(SHAPE_OUT, o.tolist()))
+
+
+def test_planned_shape_over_the_lag_grid_size():
+    """The three decisions of sp_planned_shape that depend on covpts, each on either side of its threshold.  The
+    thresholds are derived here from the documented budgets, in doubles, of a table of 4 (covpts + 4) coefficients:
+      * the one-workgroup kernel keeps it in a region of 64 * BLD doubles, BLD = 66 the padded row of a 64 x 64 block
+        (csrc/sp_internal.h, sp_small_k_serves);
+      * the kernels that form tiles at first touch stage it, with a tile's 64 column phases behind it, in the smallest
+        of their scratch areas, SP_TILE_LDS_MIN = 4544 doubles (csrc/sp_internal.h);
+      * the stars' packed tables live in the design-matrix region, Kr * N doubles per star, Kr = K rounded up to 64
+        and N = (ydeg + 1)^2."""
+    nb, bld, tile_lds_min = 64, 66, 4544
+    # small_k (K = 100 <= 128): 4 (covpts + 4) <= 64 BLD
+    last = (64 * bld) // 4 - 4
+    assert last == 1052
+    for K in (100, 60):
+        assert planned_shape(5, K, last)["small_k"] == 1 and planned_shape(5, K, last + 1)["small_k"] == 0
+        assert planned_shape(5, K, last, SP_SMALL_K=0)["small_k"] == 0
+    # tiles at first touch (K = 330, ydeg 5): 4 (covpts + 4) + 64 <= SP_TILE_LDS_MIN; the packed tables fit either way
+    last = (tile_lds_min - 64) // 4 - 4
+    assert last == 1116 and 4 * (last + 4) + 64 == tile_lds_min      # (full to the last double)
+    K, N = 330, 36
+    Kr, Kp = -(-K // nb) * nb, -(-(K + 1 + 2) // nb) * nb           # (the system: K cadences, one residual row, two of the normalisation)
+    assert 4 * (last + 1 + 4) <= Kr * N
+    a, b = planned_shape(5, K, last), planned_shape(5, K, last + 1)
+    assert a["use_ptab"] == 1 and b["use_ptab"] == 1
+    assert a["riding"] == 1 and a["lazy_nfull"] == Kp // nb == 6    # (every row tile, those of the riding rows included)
+    assert b["riding"] == 0 and b["lazy_nfull"] == 0 and b["dlazy"] == 0
+    assert planned_shape(5, K, 300)["lazy_nfull"] == 6 and planned_shape(5, K, last, SP_LAZY_COV=0)["lazy_nfull"] == 0
+    # (with a temporal kernel the assembly writes the first super-panel of four block columns, the rest is formed)
+    at = planned_shape(5, K, last, temporal=1)
+    assert at["lazy_nfull"] == 6 and at["ncolw"] == 4 and at["no_panels"] == 1
+    assert planned_shape(5, K, last + 1, temporal=1)["lazy_nfull"] == 0
+    # packed tables (ydeg 5, K = 130): 4 (covpts + 4) <= Kr N
+    K = 130
+    Kr = -(-K // nb) * nb
+    assert Kr * N == 6912
+    last = (Kr * N) // 4 - 4
+    assert last == 1724
+    assert planned_shape(5, K, last)["use_ptab"] == 1 and planned_shape(5, K, last + 1)["use_ptab"] == 0
+    # (ydeg 15 has room for both)
+    assert planned_shape(15, K, last + 1)["use_ptab"] == 1
+
+
 @pytest.mark.parametrize("k", range(len(STRINGS)))
 def test_parse_rules(k):
     s = STRINGS[k]
