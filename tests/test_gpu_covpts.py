@@ -49,6 +49,7 @@ import pytest
 from conftest import golden
 from starry_process_amd.synthetic import synthetic_star
 from test_gpu_planned import make_engine, numpy_wbar, run, star_batch
+from test_time_axes_host import ORACLE_KERNEL
 from test_tuning_host import planned_shape
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +59,7 @@ AXIS = [300, 390, 520, 999, 1116, 1117]
 K_AXIS, S_AXIS = 330, 6    # five full blocks: more than one super-panel of four, so the trailing update forms tiles too
 ORACLE_STARS = (0, 2, 4)
 NB, TILE_LDS_MIN, ASM_LDS_MAX_DOUBLES = 64, 4544, 80 * 1024 // 8
-TEMPORAL_CODE = {None: 0, "matern32": 1}
+TEMPORAL_CODE = {None: 0, "matern32": 1, "expsquared": 2}
 
 
 # ---- NumPy: lags, staged tails, the oracle -----------------------------------------------------------------------------
@@ -103,14 +104,16 @@ def assert_lags_reach_the_tails(covpts, t, p):
 _oracle_values = {}
 
 
-def oracle_lnl(L, covpts, t, flux, p, tau=None):
+def oracle_lnl(L, covpts, t, flux, p, tau=None, kernel="matern32"):
+    """The oracle's value, kept per input; `kernel` names the temporal kernel that a tau is for."""
     from oracle import sp_oracle as orc
 
-    key = (L, covpts, tau, float(p), t.tobytes(), np.asarray(flux).tobytes())
+    tau = None if not tau else float(tau)
+    key = (L, covpts, tau, kernel if tau else None, float(p), t.tobytes(), np.asarray(flux).tobytes())
     if key not in _oracle_values:
         mom = golden("moments_L%d" % L)
         op = orc.OracleProcess(mom["default_mean_ylm"], mom["default_cov_ylm"], ydeg=L, covpts=covpts, tau=tau,
-                               temporal_kernel=orc.Matern32Kernel)
+                               temporal_kernel=getattr(orc, ORACLE_KERNEL[kernel]))
         _oracle_values[key] = op.log_likelihood(t, flux, 1e-6, p=float(p))
     return _oracle_values[key]
 
@@ -164,14 +167,17 @@ def all_routes(L, t, flux, stars, covpts, temporal):
     return out
 
 
-def check_routes(L, covpts, t, flux, per, tau, oracle_stars, nobs=None, tails=True):
+def check_routes(L, covpts, t, flux, per, tau, oracle_stars, nobs=None, tails=True, kernel="matern32"):
+    """tau: None (no temporal kernel), one timescale or one per star, of the temporal kernel named `kernel`.  Returns
+    the routes' values."""
     from starry_process_amd.engine import make_stars
 
     S, K = t.shape
-    temporal = "matern32" if tau else None
+    temporal = kernel if tau is not None and np.all(tau) else None
+    taus = np.broadcast_to(np.asarray(tau if temporal else 0.0, dtype=float), (S,))
     for lazy in (1, 0):
         expect_planned_shape(L, K, covpts, temporal, lazy)
-    stars = make_stars(S, period=per, tau=tau or 0.0, data_var=1e-6, nobs=nobs if nobs is not None else 0)
+    stars = make_stars(S, period=per, tau=taus, data_var=1e-6, nobs=nobs if nobs is not None else 0)
     v = all_routes(L, t, flux, stars, covpts, temporal)
     for name, w in v.items():
         print("covpts %4d %-20s against planned: %.2e" % (covpts, name, rel(w, v["planned"])))
@@ -191,15 +197,16 @@ def check_routes(L, covpts, t, flux, per, tau, oracle_stars, nobs=None, tails=Tr
         ts, fs = t[s, :n].copy(), flux[s, 0, :n].copy()
         if tails and n == K:
             assert_lags_reach_the_tails(covpts, ts, per[s])
-        ref = oracle_lnl(L, covpts, ts, fs, per[s], tau)
+        ref = oracle_lnl(L, covpts, ts, fs, per[s], taus[s], kernel)
         print("covpts %4d star %d planned %.12g oracle %.12g (%.2e)" % (covpts, s, v["planned"][s], ref,
                                                                         abs(v["planned"][s] / ref - 1)))
         if covpts >= 999:
-            other = oracle_lnl(L, 300, ts, fs, per[s], tau)
+            other = oracle_lnl(L, 300, ts, fs, per[s], taus[s], kernel)
             print("            the oracle at 300: %.12g (%.2e from its value at %d)" % (other, abs(other / ref - 1), covpts))
             assert abs(other / ref - 1) > 3e-8, (covpts, s, ref, other)
         for name, w in v.items():
             assert abs(w[s] / ref - 1) < TOL_ORACLE, (covpts, name, s, w[s], ref)
+    return v
 
 
 def axis_batch(tau=None):

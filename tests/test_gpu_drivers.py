@@ -321,10 +321,13 @@ def test_deferred_normalisation_matches_direct():
         "temporal_out_of_order": dict(tau=2.5, temporal="matern32", swap=True),
         "temporal_short_tau": dict(tau=1.0e-3, temporal="matern32"),
         "temporal_ragged": dict(tau=2.5, temporal="matern32", nobs=[K, K - 1, 200, 65, 64, 63, 2]),
+        "temporal_expsquared": dict(tau=2.0, temporal="expsquared"),
+        "temporal_expsquared_ragged": dict(tau=2.0, temporal="expsquared", nobs=[K, K - 1, 200, 65, 64, 63, 2]),
         "ragged": dict(nobs=[K, K - 1, 200, 65, 64, 63, 2]),
         "multi": dict(M=4),
         "vector_variance": dict(diag=1e-6 * (1.0 + rng.rand(S, K))),
         "conditional": dict(conditional=True),
+        "conditional_expsquared": dict(conditional=True, tau=2.0, temporal="expsquared"),
         "not_pd": dict(data_var=[1e-6, -1.0, 1e-6, 1e-6, 1e-6, 1e-6, 1e-6]),
     }
     for name, kw in cases.items():

@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 from test_fisher_host import fisher_numpy
+from test_time_axes_host import ORACLE_KERNEL
 
 pytestmark = pytest.mark.gpu
 
@@ -54,6 +55,10 @@ CASES = [
     # kernel's six tables of covpts + 4 doubles and 1152 doubles of tile vectors fill its 60 KB of LDS to 6528 + 1152)
     dict(id="norm-K130-covpts999", K=130, normalized=True, covpts=999),
     dict(id="norm-K65-covpts1084", K=65, normalized=True, covpts=1084),
+    # ExpSquaredKernel (exp(-dt^2 / (2 tau)), temporal.py:14-16): the sweeps' other temporal instantiation (the
+    # yardstick's own uncertainty for the two: 4.7e-8 and 5.0e-8, within DELTA_YARDSTICK)
+    dict(id="norm-expsq2-K63", K=63, normalized=True, tau=2.0, temporal="expsquared"),
+    dict(id="raw-expsq2-K130", K=130, normalized=False, tau=2.0, temporal="expsquared"),
 ]
 DR_CASE = dict(id="norm-dr-K65", K=65, normalized=True, dr=5.0)
 
@@ -96,7 +101,8 @@ def _oracle_C(case, hp, s):
 
     mu, Sig = _oracle_moments(hp)
     op = orc.OracleProcess(mu, Sig, ydeg=YDEG, udeg=2, normalized=case["normalized"], tau=case.get("tau"),
-                           temporal_kernel=orc.Matern32Kernel, covpts=case.get("covpts", 300))
+                           temporal_kernel=getattr(orc, ORACLE_KERNEL[case.get("temporal", "matern32")]),
+                           covpts=case.get("covpts", 300))
     t = _times(case["K"])[s]
     C = op.cov(t, p=PERIODS[s], u=U[s])
     var = np.broadcast_to(np.asarray(_ferr(case)) ** 2, (3, case["K"]))[s]
@@ -173,7 +179,8 @@ def _fisher(case, stars=slice(None), **kw):
     t, ferr = _times(case["K"])[stars], _ferr(case)
     ferr = ferr[stars] if np.ndim(ferr) == 2 else ferr
     return EnsembleFisher(t, ferr=ferr, p=PERIODS[stars], u=U[stars], ydeg=YDEG, normalized=case["normalized"],
-                          tau=case.get("tau"), baseline_var=case.get("baseline_var", 0.0), covpts=case.get("covpts"), **kw)
+                          tau=case.get("tau"), temporal_kernel=case.get("temporal", "matern32"),
+                          baseline_var=case.get("baseline_var", 0.0), covpts=case.get("covpts"), **kw)
 
 
 def _hp(case):

@@ -33,11 +33,16 @@ entry.  Per case, delta(F) and the tangents' own disagreement delta(dC):
     norm-tau3-K63            delta(F) = 3.11e-09   delta(dC) = 1.08e-10
     norm-var-baseline-K65    delta(F) = 8.71e-10   delta(dC) = 1.4e-10
     norm-ydeg7-K65           delta(F) = 2.46e-09   delta(dC) = 1.78e-10
+    norm-expsq2-K63          delta(F) = 4.20e-09   delta(dC) = 1.32e-10
+
+DELTA_YARDSTICK is the largest delta(F) of the first eight.  The last case (ExpSquaredKernel) is held to the bound of
+the others, 7.4 times its own uncertainty: the bound of the earlier cases does not move.
 """
 import numpy as np
 import pytest
 
 from test_fisher_host import fisher_numpy
+from test_time_axes_host import ORACLE_KERNEL
 
 pytestmark = pytest.mark.gpu
 
@@ -52,8 +57,11 @@ U = np.array([[0.3, 0.2], [0.5, 0.1], [0.3, 0.2]])   # two limb-darkening tables
 # relative step of the oracle's central differences (x the parameter's scale max(|x|, 0.1)), for the hyperparameters,
 # the inclination [degrees] and the period alike
 H = 1.0e-4
-# The yardstick's own uncertainty: max over CASES, stars and entries of |F(H) - F(H / 2)| / sqrt(F_ii F_jj), both from the
-# oracle on the CPU; printed by ``python tests/test_gpu_fisher_conditional.py`` (per case: the docstring's table)
+# The yardstick's own uncertainty: max over the first N_YARDSTICK = 8 of CASES, stars and entries of
+# |F(H) - F(H / 2)| / sqrt(F_ii F_jj), both from the oracle on the CPU; printed by
+# ``python tests/test_gpu_fisher_conditional.py`` (per case: the docstring's table).  A case added behind those eight (the
+# ExpSquared one, 4.2e-9) is held to the same bound and does not widen it.
+N_YARDSTICK = 8
 DELTA_YARDSTICK = 3.11e-9
 TOL = 10.0 * DELTA_YARDSTICK
 
@@ -66,6 +74,7 @@ CASES = [
     dict(id="norm-tau3-K63", K=63, normalized=True, tau=3.0),
     dict(id="norm-var-baseline-K65", K=65, normalized=True, percadence=True, baseline_var=2.0e-5),
     dict(id="norm-ydeg7-K65", K=65, normalized=True, ydeg=7),      # N = 64: the forward's tile product
+    dict(id="norm-expsq2-K63", K=63, normalized=True, tau=2.0, temporal="expsquared"),
 ]
 BY_ID = {c["id"]: c for c in CASES}
 
@@ -112,7 +121,8 @@ def _oracle_C(case, x, s):
 
     mu, Sig = _oracle_moments({k: x[k] for k in NAMES}, _ydeg(case))
     op = orc.OracleProcess(mu, Sig, ydeg=_ydeg(case), udeg=2, marginalize_over_inclination=False,
-                           normalized=case["normalized"], tau=case.get("tau"), temporal_kernel=orc.Matern32Kernel)
+                           normalized=case["normalized"], tau=case.get("tau"),
+                           temporal_kernel=getattr(orc, ORACLE_KERNEL[case.get("temporal", "matern32")]))
     t = _times(case["K"])[s]
     C = op.cov(t, i=x["i"], p=x["p"], u=U[s])
     var = np.broadcast_to(np.asarray(_ferr(case)) ** 2, (3, case["K"]))[s]
@@ -175,8 +185,9 @@ def _measure_delta():
         print("%-24s delta(F) = %.3g   delta(dC) = %.3g   min eig / max eig = %.3g" % (
             case["id"], delta, dd, min(np.linalg.eigvalsh(a["F"][s])[0] / np.linalg.eigvalsh(a["F"][s])[-1]
                                        for s in range(3))))
-        worst = max(worst, delta)
-    print("DELTA_YARDSTICK = %.3g" % worst)
+        if case in CASES[:N_YARDSTICK]:
+            worst = max(worst, delta)
+    print("DELTA_YARDSTICK = %.3g (the first %d cases)" % (worst, N_YARDSTICK))
 
 
 # ---- the device's side -------------------------------------------------------------------------------------------------
@@ -187,7 +198,7 @@ def _fisher(case, stars=slice(None), **kw):
     ferr = ferr[stars] if np.ndim(ferr) == 2 else ferr
     return EnsembleFisherConditional(t, ferr=ferr, p=PERIODS[stars], i=INCS[stars], u=U[stars], ydeg=_ydeg(case),
                                      normalized=case["normalized"], tau=case.get("tau"),
-                                     baseline_var=case.get("baseline_var", 0.0), **kw)
+                                     temporal_kernel=case.get("temporal", "matern32"), baseline_var=case.get("baseline_var", 0.0), **kw)
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c["id"])

@@ -53,7 +53,7 @@ def _moments(ydeg):
     return mu.cpu().numpy(), Sig.cpu().numpy()
 
 
-def _sweep(ydeg, t, flux, p, inc, normalized=True, tau=None, var=1e-6, nobs=0, bvar=0.0, bmean=0.0):
+def _sweep(ydeg, t, flux, p, inc, normalized=True, tau=None, var=1e-6, nobs=0, bvar=0.0, bmean=0.0, kernel="matern32"):
     """The entry point's outputs as NumPy: lnlike [S], mubar [S, N], sigbar [S, N, N], starbar [S, 6], status [S]."""
     from starry_process_amd.engine import get_engine, make_stars
 
@@ -64,21 +64,21 @@ def _sweep(ydeg, t, flux, p, inc, normalized=True, tau=None, var=1e-6, nobs=0, b
                                          nobs=nobs, baseline_var=bvar, baseline_mean=bmean))
     rta1 = e.f64(e.rTA1L(np.zeros((1, 2))))
     out = e.lnlike_grad_conditional(e.f64(np.ascontiguousarray(t)), e.f64(np.ascontiguousarray(flux)), stars, rta1,
-                                    temporal="matern32" if tau else None, normalized=normalized)
+                                    temporal=kernel if tau else None, normalized=normalized)
     return [x.cpu().numpy() for x in out]
 
 
 @functools.lru_cache(maxsize=None)
-def _case(ydeg, K, S, normalized, tau=None):
+def _case(ydeg, K, S, normalized, tau=None, kernel="matern32"):
     """(inputs, the sweep's outputs, the per-star autograd reference), computed once and shared."""
     from starry_process_amd.grad import log_likelihood_with_grad
 
     t, flux, p, _ = _ensemble(S, K, seed0=3)
     inc = _inc(S)
-    got = _sweep(ydeg, t, flux, p, inc, normalized=normalized, tau=tau)
+    got = _sweep(ydeg, t, flux, p, inc, normalized=normalized, tau=tau, kernel=kernel)
     mu, Sig = _moments(ydeg)
     ref = [log_likelihood_with_grad(mu, Sig, t[s], flux[s], 1e-6, i=float(inc[s]), p=float(p[s]), tau=tau,
-                                    marginalize_over_inclination=False, normalized=normalized, ydeg=ydeg)
+                                    temporal_kernel=kernel, marginalize_over_inclination=False, normalized=normalized, ydeg=ydeg)
            for s in range(S)]
     return (t, flux, p, inc), got, ref
 
@@ -92,12 +92,24 @@ def _bits(a, b):
 # (15, 130): three row tiles (one off-diagonal tile away from the diagonal), N = 256; S = 9 > the eight XCDs
 SHAPES = [(5, 64), (5, 70), (15, 130)]
 CASES = [(y, K, S, nrm, None) for (y, K) in SHAPES for S in (3, 9) for nrm in (False, True)] + [(15, 130, 3, True, 0.7)]
+# ExpSquaredKernel: grad_cond_hta_kernel's other temporal instantiation, at the smallest K of this list with two row tiles
+EXPSQUARED_CASES = [(5, 70, 3, True, 2.0), (15, 130, 3, False, 0.7)]
 
 
 @pytest.mark.parametrize("ydeg,K,S,normalized,tau", CASES,
                          ids=lambda v: str(v))
 def test_per_star_adjoints_equal_the_single_star_graph(ydeg, K, S, normalized, tau):
-    _, got, ref = _case(ydeg, K, S, normalized, tau)
+    _check_against_the_graph(ydeg, K, S, normalized, tau, "matern32")
+
+
+@pytest.mark.parametrize("ydeg,K,S,normalized,tau", EXPSQUARED_CASES, ids=lambda v: str(v))
+def test_per_star_adjoints_equal_the_single_star_graph_expsquared(ydeg, K, S, normalized, tau):
+    _check_against_the_graph(ydeg, K, S, normalized, tau, "expsquared")
+
+
+def _check_against_the_graph(ydeg, K, S, normalized, tau, kernel):
+    # (the default kernel left out: the key under which the later tests find the shared case)
+    _, got, ref = _case(ydeg, K, S, normalized, tau, *(() if kernel == "matern32" else (kernel,)))
     lnl, mubar, sigbar, sbar, status = got
     assert not status.any()
     dev = {}
@@ -117,7 +129,7 @@ def test_per_star_adjoints_equal_the_single_star_graph(ydeg, K, S, normalized, t
     dev["i"] = np.abs(sbar[:, 1] * (np.pi / 180.0) - gi).max() / np.abs(gi).max()
     dev["p"] = np.abs(sbar[:, 0] - gp).max() / np.abs(gp).max()
     dev["lnl"] = max(abs(lnl[s] - ref[s][0]) / abs(ref[s][0]) for s in range(S))
-    print("DEVIATION ydeg %d K %d S %d norm %d tau %s: " % (ydeg, K, S, normalized, tau) +
+    print("DEVIATION ydeg %d K %d S %d norm %d tau %s %s: " % (ydeg, K, S, normalized, tau, kernel if tau else "") +
           " ".join("%s %.3g" % kv for kv in sorted(dev.items())))
     assert np.all(sbar[:, 5] == 0.0)
     for k in ("mu", "Sigma", "i", "p"):

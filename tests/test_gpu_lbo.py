@@ -154,11 +154,15 @@ EDGE_CASES = [(K, dict(marginalize_over_inclination=marg, normalized=False))
               for K in (2, 3, 63, 64, 65, 127, 129, 200) for marg in (True, False)]
 EDGE_CASES += [(129, dict(marginalize_over_inclination=True, normalized=False, tau=2.0)),
                (129, dict(marginalize_over_inclination=True, normalized=True))]
+# ExpSquaredKernel on both branches (the sweeps' other temporal instantiation)
+EDGE_CASES += [(129, dict(marginalize_over_inclination=True, normalized=False, tau=2.0, temporal_kernel="expsquared")),
+               (65, dict(marginalize_over_inclination=False, normalized=False, tau=2.0, temporal_kernel="expsquared"))]
 
 
 @pytest.mark.parametrize("K,ckw", EDGE_CASES, ids=lambda v: str(v) if isinstance(v, int) else
                          "-".join(["marg" if v["marginalize_over_inclination"] else "cond"] +
-                                  (["norm"] if v["normalized"] else []) + (["tau"] if "tau" in v else [])))
+                                  (["norm"] if v["normalized"] else []) + (["tau"] if "tau" in v else []) +
+                                  (["expsq"] if "temporal_kernel" in v else [])))
 def test_shape_edges(K, ckw):
     """K at and around the 64-row band, the 32-column tile of the Gram pass, the 128-column tile of the column pass,
     the odd-K pair load and the last partial tile; blocks of 1, 2, 7, 16, 63 and 64 (clipped to K) and one irregular

@@ -109,11 +109,15 @@ EDGE_CASES = [(K, dict(marginalize_over_inclination=marg, normalized=False))
 EDGE_CASES += [(129, dict(marginalize_over_inclination=True, normalized=False, tau=2.0)),
                (129, dict(marginalize_over_inclination=True, normalized=True)),
                (65, dict(marginalize_over_inclination=False, normalized=True))]
+# ExpSquaredKernel on both branches (the sweeps' other temporal instantiation)
+EDGE_CASES += [(129, dict(marginalize_over_inclination=True, normalized=False, tau=2.0, temporal_kernel="expsquared")),
+               (65, dict(marginalize_over_inclination=False, normalized=False, tau=2.0, temporal_kernel="expsquared"))]
 
 
 @pytest.mark.parametrize("K,ckw", EDGE_CASES, ids=lambda v: str(v) if isinstance(v, int) else
                          "-".join(["marg" if v["marginalize_over_inclination"] else "cond"] +
-                                  (["norm"] if v["normalized"] else []) + (["tau"] if "tau" in v else [])))
+                                  (["norm"] if v["normalized"] else []) + (["tau"] if "tau" in v else []) +
+                                  (["expsq"] if "temporal_kernel" in v else [])))
 def test_shape_edges(K, ckw):
     """K at and around the 64- and 128-wide blocks of the two passes, S = 3, ydeg 5, both branches, a temporal and
     two normalised processes (for which no reference predict exists): NumPy's closed form on the package's own C."""

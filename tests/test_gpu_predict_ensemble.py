@@ -114,7 +114,12 @@ def test_realistic_size_against_predict(tau):
         assert np.array_equal(Kp[s], Kp[s].T)
 
 
-@pytest.mark.parametrize("ckw", [dict(), dict(marginalize_over_inclination=False), dict(tau=2.0)])
+# (ExpSquaredKernel: predict_assemble_kernel's other temporal instantiation, on both branches)
+EXPSQ = [dict(tau=2.0, temporal_kernel="expsquared"),
+         dict(tau=2.0, temporal_kernel="expsquared", marginalize_over_inclination=False)]
+
+
+@pytest.mark.parametrize("ckw", [dict(), dict(marginalize_over_inclination=False), dict(tau=2.0)] + EXPSQ)
 def test_modes_agree(ckw):
     """"diag" is the diagonal of the full result, False gives mu alone; mu is the same bits in all three modes."""
     sp = SP(**ckw)
@@ -281,7 +286,7 @@ def test_refusals():
 
 
 @pytest.mark.parametrize("K,Ks", [(128, 64), (64, 63)])
-@pytest.mark.parametrize("ckw", [dict(), dict(marginalize_over_inclination=False), dict(tau=2.0)])
+@pytest.mark.parametrize("ckw", [dict(), dict(marginalize_over_inclination=False), dict(tau=2.0)] + EXPSQ)
 def test_tile_edges_against_predict(K, Ks, ckw):
     """K = 128, Ks = 64: every product of the conditional branch and K_ss -= Y Y^T take the pipelined 64 x 64 tile
     kernel at ldc = Kp; K = 64, Ks = 63: K + Ks + 1 lands exactly on a tile edge (no padding row).  Every star
