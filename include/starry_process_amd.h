@@ -938,6 +938,33 @@ int sp_lnlike_inclinations_planned(sp_handle *h, int S, int M, const void *plan_
                                    const double *inc_rad_dev, int normalized, int norm_order, double zmax,
                                    double *lnlike_dev, uint32_t *status_dev, void *workspace_dev, void *stream);
 
+/* ---- the grid of inclinations with derivatives, and its mixture (csrc/sp_incl_grad.hip) --------------
+ * sp_lnlike_inclinations_planned's value for one moment set and one light curve per star (a plan of
+ * sp_incl_plan_data with M = 1), together with its directional derivatives along Pd directions of the moments and,
+ * with logw_dev, the mixture of each star's grid against the log prior weights: the inclination-marginal likelihood
+ *   lnmix[s] = log sum_j exp(logw[j] + lnlike[s][j]),  pinc[s][j] = softmax_j,  dlnmix[s][k] = sum_j pinc[s][j] dlnlike[s][j][k].
+ * Inputs (DEVICE): plan_dev, stars_dev [S], rta1_dev [ntab,N], mean_ylm_dev [N], cov_ylm_dev [N,N], the directions
+ * dmean_dev [Pd,N] and dcov_dev [Pd,N,N] (each SYMMETRIC; 1 <= Pd <= SP_INCL_GRAD_MAXDIR), inc_rad_dev [P] in radians,
+ * logw_dev [P] or NULL (then lnmix_dev, dlnmix_dev, pinc_dev are not written and may be NULL; -inf: weight 0).
+ * Outputs: lnlike_dev [S,P] (the bits of sp_lnlike_inclinations_planned), dlnlike_dev [S,P,Pd] with
+ * dlnlike[s][j][k] = d/d eps lnlike[s][j](mean + eps dmean_k, cov + eps dcov_k), lnmix_dev [S], dlnmix_dev [S,Pd],
+ * pinc_dev [S,P], status_dev [S,P] (may be NULL).  z > zmax and NaN -> -inf with the flag and ZERO derivatives; such an
+ * entry has weight 0 in the mixture, and a star whose whole grid is -inf gets lnmix = -inf, pinc = 0, dlnmix = 0.  A
+ * star the plan rejected gets NaN in every output and SP_STAR_NO_BASIS in its status row.  Each (star, inclination) is
+ * computed from its own inputs alone and every sum has a fixed order: the same bits in any batch, run after run; the
+ * derivative along direction k does not depend on the other directions.  ydeg <= 30; P and ntab at most 65535.
+ * workspace_dev: sp_lnlike_inclinations_grad_workspace_bytes(h, S, ntab, P, Pd) bytes.  All launches go to `stream`;
+ * nothing is synchronised; every buffer is the caller's. */
+#define SP_INCL_GRAD_MAXDIR 8
+size_t sp_lnlike_inclinations_grad_workspace_bytes(sp_handle *h, int S, int ntab, int P, int Pd);
+int sp_lnlike_inclinations_grad(sp_handle *h, int S, const void *plan_dev, const sp_star *stars_dev,
+                                const double *rta1_dev, int ntab, const double *mean_ylm_dev, const double *cov_ylm_dev,
+                                int Pd, const double *dmean_dev, const double *dcov_dev, int P,
+                                const double *inc_rad_dev, const double *logw_dev, int normalized, int norm_order,
+                                double zmax, double *lnlike_dev, double *dlnlike_dev, double *lnmix_dev,
+                                double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev, void *workspace_dev,
+                                void *stream);
+
 /* ---- surface-map posteriors with the inclination marginalised on a grid (csrc/sp_ylm_incl.hip) --------
  * The posterior of the Ylm map of star s given its light curve, mixed over the P grid inclinations inc[j] with the
  * weights pinc[s][j] = softmax_j(logprior[j] + lnL[s][j]), lnL the un-normalised sp_lnlike_inclinations value

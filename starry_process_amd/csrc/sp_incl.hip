@@ -27,6 +27,7 @@
 // in the batch, so a value does not depend on its neighbours.
 #include <cfloat>
 
+#include "sp_incl_triple.h"
 #include "sp_internal.h"
 
 namespace {
@@ -378,88 +379,9 @@ __global__ __launch_bounds__(64) void incl_triple_kernel(int L, int M, int J, in
   }
   const size_t mo = ((size_t)b * ntab + st.table) * P + p;
   const double *Mp = Mm + mo * n * n, *cp = cm + mo * n;
-  for (int e = tid; e < n * n; e += 64) {
-    sL[e] = Pl[e];
-    sA[e] = Mp[e];
-  }
-  if (tid == 0) notpd = 0;
-  __syncthreads();
   const double nobs = Ps[2];
-  if (tid == 0) {
-    double fm = 0.0;
-    for (int a = 0; a < n; ++a) fm += Pt[a] * cp[a];
-    sc[0] = fm;
-    sc[1] = normalized ? 0.0 : fm;
-  }
-  double z = 0.0;
-  if (normalized) {
-    for (int a = tid; a < n; a += 64) {
-      double x = 0.0;
-      for (int k = 0; k < n; ++k) x += sA[a * n + k] * Pg[k];
-      sv[a] = x;
-    }
-    __syncthreads();
-    double m = 0.0;
-    for (int a = 0; a < n; ++a) m += Pg[a] * sv[a];
-    m /= nobs * nobs;
-    const double mu = 1.0 + sc[0];
-    z = m / (mu * mu);
-    double fac = 1.0, alpha = 0.0, beta = 0.0;
-    for (int k = 0; k <= order; ++k) {
-      alpha += fac;
-      beta += 2 * k * fac;
-      fac *= z * (2 * k + 3);
-    }
-    const double c0 = alpha / (mu * mu), gam = z * (alpha + beta), za = z * alpha, km = nobs * m;
-    __syncthreads();
-    for (int a = tid; a < n; a += 64) sv[a] /= km;
-    __syncthreads();
-    for (int e = tid; e < n * n; e += 64) {
-      const int a = e / n, c = e - a * n;
-      const double pa = (a == 0 ? 1.0 : 0.0) - sv[a], pc = (c == 0 ? 1.0 : 0.0) - sv[c];
-      sA[e] = c0 * sA[e] + gam * pa * pc - za * sv[a] * sv[c];
-    }
-  }
-  __syncthreads();
-  if (tid == 0) sA[0] += st.baseline_var;
-  __syncthreads();
-  // Y = M~ L_G (L_G lower: rows k >= c of column c)
-  for (int e = tid; e < n * n; e += 64) {
-    const int a = e / n, c = e - a * n;
-    double x = 0.0;
-    for (int k = c; k < n; ++k) x += sA[a * n + k] * sL[k * n + c];
-    sY[e] = x;
-  }
-  __syncthreads();
-  // H = I + L_G^T Y, lower triangle
-  for (int e = tid; e < n * n; e += 64) {
-    const int a = e / n, c = e - a * n;
-    if (c > a) continue;
-    double x = a == c ? 1.0 : 0.0;
-    for (int k = a; k < n; ++k) x += sL[k * n + a] * sY[k * n + c];
-    sA[e] = x;
-  }
-  __syncthreads();
-  // H = L_H L_H^T in place (lane i owns row i: n <= 61 < 64)
-  for (int c = 0; c < n; ++c) {
-    if (tid == 0) {
-      const double piv = sA[c * n + c];
-      if (!(piv > 0.0)) notpd = 1;
-      sA[c * n + c] = sqrt(piv);
-    }
-    __syncthreads();
-    const int i = tid;
-    if (i > c && i < n) {
-      const double lic = sA[i * n + c] / sA[c * n + c];
-      sA[i * n + c] = lic;
-    }
-    __syncthreads();
-    if (i > c && i < n) {
-      const double lic = sA[i * n + c];
-      for (int k = c + 1; k <= i; ++k) sA[i * n + k] -= lic * sA[k * n + c];
-    }
-    __syncthreads();
-  }
+  const double z = ic_triple_factor(n, tid, Pl, Pg, Pt, nobs, Mp, cp, normalized, order, st.baseline_var, sL, sA, sY, sv,
+                                    sc, &notpd).z;
   if (tid == 0) {
     double logdet = 0.0;
     for (int a = 0; a < n; ++a) logdet += log(sA[a * n + a]);
@@ -517,15 +439,6 @@ size_t incl_data_lds(int L, int M) {
   return sizeof(double) * (Q + n * n + 2 * IC_CH * J2 + IC_CH + (size_t)M * IC_CH + (size_t)M * n + 256);
 }
 
-constexpr size_t IC_LDS_MAX = 150 * 1024;   // (as the other kernels that opt in: 160 KiB less the static LDS is refused)
-
-// opts a kernel in to more than 64 KiB of dynamic LDS when a launch needs it (a refusal must not be left behind as
-// the thread's last error: SP_LAUNCH_CHECK would report it against the launch)
-void ic_lds_opt_in(const void *fn, size_t lds) {
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IC_LDS_MAX) != hipSuccess)
-    (void)hipGetLastError();
-}
-
 }  // namespace
 
 SpInclModel sp_incl_model_views(const sp_handle *h, int S, int M, int ntab, int B, int P, void *workspace_dev) {
@@ -538,6 +451,40 @@ SpInclModel sp_incl_model_views(const sp_handle *h, int S, int M, int ntab, int 
   v.SigRt = at<double>(workspace_dev, Ly.sig) + (size_t)B * h->N * h->N;
   v.pstride = incl_pstride(2 * h->ydeg + 1, M);
   return v;
+}
+
+int sp_incl_model_stage(sp_handle *h, int S, int M, int ntab, int P, const double *rta1_dev, const double *inc_rad_dev,
+                        int B0, const double *mean0_dev, const double *cov0_dev, int B1, const double *mean1_dev,
+                        const double *cov1_dev, void *workspace_dev, hipStream_t st) {
+  const int N = h->N, B = B0 + B1;
+  const InclLayout Ly = incl_layout(h, S, M, ntab, B, P);
+  void *ws = workspace_dev;
+  double *sig = at<double>(ws, Ly.sig), *mu = at<double>(ws, Ly.mu), *cs = at<double>(ws, Ly.cs);
+  double *rinc = at<double>(ws, Ly.rinc), *V = at<double>(ws, Ly.V), *Mm = at<double>(ws, Ly.Mm);
+  double *cm = at<double>(ws, Ly.cm);
+  int rc;
+  // Sigma' = R Sigma R^T: Y = Sigma R^T, then Y^T R^T (a transposed view of Y); mu' = R mu = (mu^T R^T)^T
+  double *Y = sig + (size_t)B * N * N;
+  const size_t NN = (size_t)N * N;
+  if ((rc = sp_launch_dotRx(h, cov0_dev, (long)N * N, N, 1, N, h->d_Rx90, 0, Y, B0, st, 1))) return rc;
+  if ((rc = sp_launch_dotRx(h, Y, (long)N * N, 1, N, N, h->d_Rx90, 0, sig, B0, st, 1))) return rc;
+  if ((rc = sp_launch_dotRx(h, mean0_dev, N, N, 1, 1, h->d_Rx90, 0, mu, B0, st, 1))) return rc;
+  if (B1 > 0) {
+    if ((rc = sp_launch_dotRx(h, cov1_dev, (long)N * N, N, 1, N, h->d_Rx90, 0, Y + B0 * NN, B1, st, 1))) return rc;
+    if ((rc = sp_launch_dotRx(h, Y + B0 * NN, (long)N * N, 1, N, N, h->d_Rx90, 0, sig + B0 * NN, B1, st, 1))) return rc;
+    if ((rc = sp_launch_dotRx(h, mean1_dev, N, N, 1, 1, h->d_Rx90, 0, mu + (size_t)B0 * N, B1, st, 1))) return rc;
+  }
+  // v = rTA1 . Rx(-i) for every (inclination, flux operator): V [P][ntab][N]
+  hipLaunchKernelGGL(incl_cs_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, inc_rad_dev, cs);
+  SP_LAUNCH_CHECK();
+  if ((rc = sp_launch_Rx(h, cs, P, rinc, nullptr, st))) return rc;
+  if ((rc = sp_launch_dotRx(h, rta1_dev, 0, N, 1, ntab, rinc, h->NWIG, V, P, st, 0))) return rc;
+  const size_t mlds = sizeof(double) * IC_PC * N;
+  ic_lds_opt_in(reinterpret_cast<const void *>(incl_model_kernel), mlds);
+  hipLaunchKernelGGL(incl_model_kernel, dim3((P + IC_PC - 1) / IC_PC, ntab, B), dim3(256), mlds, st, h->ydeg, N,
+                     ntab, P, V, sig, mu, Mm, cm);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
 }
 
 extern "C" {
@@ -581,28 +528,12 @@ int sp_lnlike_inclinations_planned(sp_handle *h, int S, int M, const void *plan_
     return SP_ERR_INVALID;
   if (S == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int N = h->N, n = 2 * h->ydeg + 1;
+  const int n = 2 * h->ydeg + 1;
   const InclLayout Ly = incl_layout(h, S, M, ntab, B, P);
-  void *ws = workspace_dev;
-  double *sig = at<double>(ws, Ly.sig), *mu = at<double>(ws, Ly.mu), *cs = at<double>(ws, Ly.cs);
-  double *rinc = at<double>(ws, Ly.rinc), *V = at<double>(ws, Ly.V), *Mm = at<double>(ws, Ly.Mm);
-  double *cm = at<double>(ws, Ly.cm);
-  int rc;
-  // Sigma' = R Sigma R^T: Y = Sigma R^T, then Y^T R^T (a transposed view of Y); mu' = R mu = (mu^T R^T)^T
-  double *Y = sig + (size_t)B * N * N;
-  if ((rc = sp_launch_dotRx(h, cov_ylm_dev, (long)N * N, N, 1, N, h->d_Rx90, 0, Y, B, st, 1))) return rc;
-  if ((rc = sp_launch_dotRx(h, Y, (long)N * N, 1, N, N, h->d_Rx90, 0, sig, B, st, 1))) return rc;
-  if ((rc = sp_launch_dotRx(h, mean_ylm_dev, N, N, 1, 1, h->d_Rx90, 0, mu, B, st, 1))) return rc;
-  // v = rTA1 . Rx(-i) for every (inclination, flux operator): V [P][ntab][N]
-  hipLaunchKernelGGL(incl_cs_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, inc_rad_dev, cs);
-  SP_LAUNCH_CHECK();
-  if ((rc = sp_launch_Rx(h, cs, P, rinc, nullptr, st))) return rc;
-  if ((rc = sp_launch_dotRx(h, rta1_dev, 0, N, 1, ntab, rinc, h->NWIG, V, P, st, 0))) return rc;
-  const size_t mlds = sizeof(double) * IC_PC * N;
-  ic_lds_opt_in(reinterpret_cast<const void *>(incl_model_kernel), mlds);
-  hipLaunchKernelGGL(incl_model_kernel, dim3((P + IC_PC - 1) / IC_PC, ntab, B), dim3(256), mlds, st, h->ydeg, N,
-                     ntab, P, V, sig, mu, Mm, cm);
-  SP_LAUNCH_CHECK();
+  const double *Mm = at<double>(workspace_dev, Ly.Mm), *cm = at<double>(workspace_dev, Ly.cm);
+  int rc = sp_incl_model_stage(h, S, M, ntab, P, rta1_dev, inc_rad_dev, B, mean_ylm_dev, cov_ylm_dev, 0, nullptr, nullptr,
+                               workspace_dev, st);
+  if (rc) return rc;
   const long ntri = (long)S * J * P;
   if (ntri > 0x7fffffffL) return SP_ERR_INVALID;
   const size_t tlds = sizeof(double) * (3 * (size_t)n * n + 2 * n);

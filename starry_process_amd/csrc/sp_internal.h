@@ -449,6 +449,12 @@ struct SpInclModel {
   long pstride;
 };
 SpInclModel sp_incl_model_views(const sp_handle *h, int S, int M, int ntab, int B, int P, void *workspace_dev);
+// The model stage alone, into the workspace of sp_lnlike_inclinations_workspace_bytes(h, S, M, ntab, B0 + B1, P): the
+// moment sets are mean0 [B0, N], cov0 [B0, N, N] followed by mean1 [B1, N], cov1 [B1, N, N] (B1 = 0: none), set b of
+// either group by the same launches whatever the other holds.  The views above address its results.
+int sp_incl_model_stage(sp_handle *h, int S, int M, int ntab, int P, const double *rta1_dev, const double *inc_rad_dev,
+                        int B0, const double *mean0_dev, const double *cov0_dev, int B1, const double *mean1_dev,
+                        const double *cov1_dev, void *workspace_dev, hipStream_t st);
 // sp_ylm_temporal_cond.hip: the C ABI's posterior maps of a time-variable process (include/starry_process_amd.h)
 extern "C" {
 size_t sp_ylm_conditional_temporal_workspace_bytes(sp_handle *h, int K, int T, int R, int with_cov);

@@ -1054,6 +1054,66 @@ class Engine(object):
             int(norm_order), float(zmax), self._p(out), self._p(status), self._p(ws), self._stream()))
         return out, status
 
+    # -- the grid with derivatives and its mixture (sp_lnlike_inclinations_grad) ---------------
+    def incl_plan_data(self, t, flux, stars_dev, diag=None):
+        """The per-star plan of the inclination grid for one light curve per star (sp_incl_plan_data): t, flux
+        [S, K], stars_dev (device records), diag [S, K] or None -> (plan, status [S]: SP_STAR_NO_BASIS or 0)."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        S, K = flux.shape
+        diag = None if diag is None else self.f64(diag)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        plan = self._scratch(max(int(self._L.sp_incl_plan_bytes(self._h, S, 1)), 1))
+        if S == 0:
+            return plan, status
+        check(self._L.sp_incl_plan_data(self._h, S, K, 1, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev),
+                                        self._p(plan), self._p(status), self._stream()))
+        return plan, status
+
+    def lnlike_inclinations_grad(self, plan, stars, rta1, mean_ylm, cov_ylm, dmu, dsig, inc_rad, logw=None,
+                                 normalized=True, norm_order=20, zmax=0.023):
+        """The grid of ``lnlike_inclinations`` for one moment set with its derivatives along Pd directions of the
+        moments, and its mixture over the grid: plan (``incl_plan_data``), stars (host sp_star records or their device copy), rta1
+        [ntab, N], mean_ylm [N], cov_ylm [N, N], dmu [Pd, N], dsig [Pd, N, N] (symmetric, 1 <= Pd <= 8), inc_rad [P],
+        logw [P] log prior weights or None.  Returns (lnlike [S, P], dlnlike [S, P, Pd], lnmix [S], dlnmix [S, Pd],
+        pinc [S, P], status [S, P]); lnmix, dlnmix and pinc are None without logw."""
+        torch = _torch()
+        N = self.N
+        if isinstance(stars, np.ndarray):
+            stars = self.stars_to_device(stars)
+        S = int(stars.numel()) // STAR_DTYPE.itemsize
+        rta1 = self.f64(rta1).reshape(-1, N)
+        ntab = int(rta1.shape[0])
+        mean_ylm, cov_ylm = self.f64(mean_ylm).reshape(N), self.f64(cov_ylm).reshape(N, N)
+        dmu = self.f64(dmu).reshape(-1, N)
+        Pd = int(dmu.shape[0])
+        dsig = self.f64(dsig)
+        if not 1 <= Pd <= 8 or tuple(dsig.shape) != (Pd, N, N):
+            raise ValueError("need dmu [Pd, %d] and dsig [Pd, %d, %d] with 1 <= Pd <= 8" % (N, N, N))
+        vec = lambda x: self.f64(x if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)).reshape(-1)  # noqa: E731
+        inc = vec(inc_rad)
+        P = int(inc.shape[0])
+        if P < 1:
+            raise ValueError("at least one inclination")
+        lw = None
+        if logw is not None:
+            lw = vec(logw)
+            if lw.shape[0] != P:
+                raise ValueError("logw must hold one value per inclination")
+        lnl, dlnl = self.empty(S, P), self.empty(S, P, Pd)
+        status = torch.zeros(S, P, dtype=torch.int32, device=self.device)
+        mix = (self.empty(S), self.empty(S, Pd), self.empty(S, P)) if lw is not None else (None, None, None)
+        if S > 0:
+            if int(plan.numel()) < int(self._L.sp_incl_plan_bytes(self._h, S, 1)):
+                raise ValueError("the plan does not hold %d stars" % S)
+            ws = self._scratch(self._L.sp_lnlike_inclinations_grad_workspace_bytes(self._h, S, ntab, P, Pd))
+            check(self._L.sp_lnlike_inclinations_grad(
+                self._h, S, self._p(plan), self._p(stars), self._p(rta1), ntab, self._p(mean_ylm), self._p(cov_ylm), Pd,
+                self._p(dmu), self._p(dsig), P, self._p(inc), self._p(lw), int(bool(normalized)), int(norm_order),
+                float(zmax), self._p(lnl), self._p(dlnl), self._p(mix[0]), self._p(mix[1]), self._p(mix[2]),
+                self._p(status), self._p(ws), self._stream()))
+        return (lnl, dlnl) + mix + (status,)
+
     # -- surface-map posteriors with the inclination marginalised (sp_ylm_conditional_inclinations; DESIGN.md 19) ------
     def ylm_conditional_inclinations(self, t, flux, stars, rta1, mean_ylm, cov_ylm, inc_rad, logprior, diag=None,
                                      with_cov=True, with_inc=False, nsamples=0):

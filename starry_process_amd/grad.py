@@ -31,6 +31,7 @@ aid (``mci.optimize()``-style callers), not part of the timed hot path.
 """
 import numpy as np
 
+from ._lib import SP_STAR_NO_BASIS
 from .defaults import defaults
 from .engine import get_engine
 from .stars import check_period_inclination, ensemble_stars
@@ -951,6 +952,33 @@ def _check_conditional_params(params, star_params):
     return out[0], out[1]
 
 
+def _moment_tangents(e, ukw, names, r, a, b, c, n):
+    """The engine's moments set at the point; (mu, Sig, dmu [Ph, N], dSig [Ph, N, N]) on the device, the tangents in the
+    order of ``names`` (None, None without any): r, a, b from the quadrature's exact tangents, c and n in closed form --
+    mu_y = c n m, Sigma_y - eps = c^2 n S (contrast.py:21-33) -- with the unit-contrast evaluation on the boundary c = 0 or
+    n = 0 (``_cn_chain``).  A name's tangent does not depend on which other names are asked for."""
+    import torch
+
+    from .upstream_device import ylm_moments_device, ylm_moments_device_grad
+
+    mu, Sig, dmu, dSig = ylm_moments_device_grad(e, r=r, a=a, b=b, c=c, n=n, **ukw)
+    e.set_moments_dev(mu, Sig)
+    if not names:
+        return mu, Sig, None, None
+    tang = {name: (dmu[k], dSig[k]) for k, name in enumerate(("r", "a", "b"))}
+    if "c" in names or "n" in names:
+        eps = torch.diag(_upstream_eps(mu.shape[0], ukw, like=mu))
+        if c != 0 and n != 0:
+            tang["c"] = (mu / c, 2.0 * (Sig - eps) / c)
+            tang["n"] = (mu / n, (Sig - eps) / n)
+        else:
+            mu1, Sig1 = ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **ukw)
+            S1 = Sig1 - eps
+            tang["c"] = (n * mu1, 2.0 * c * n * S1)
+            tang["n"] = (c * mu1, c * c * S1)
+    return mu, Sig, torch.stack([tang[k][0] for k in names]), torch.stack([tang[k][1] for k in names])
+
+
 class EnsembleFisherConditional(_EnsembleSweep):
     """Expected (Fisher) information of an ENSEMBLE of light curves on the CONDITIONAL branch (star s at its own
     inclination i_s), in one device sweep and without any flux: how well these cadences, periods and noise CAN constrain
@@ -999,30 +1027,8 @@ class EnsembleFisherConditional(_EnsembleSweep):
         return self._ws
 
     def _moment_tangents(self, names, r, a, b, c, n):
-        """The engine's moments set at the point; (dmu [Ph, N], dSig [Ph, N, N]) in the order of ``names`` (None, None
-        without any): r, a, b from the quadrature's exact tangents, c and n in closed form -- mu_y = c n m, Sigma_y - eps =
-        c^2 n S (contrast.py:21-33) -- with the unit-contrast evaluation on the boundary c = 0 or n = 0 (``_cn_chain``)."""
-        import torch
-
-        from .upstream_device import ylm_moments_device, ylm_moments_device_grad
-
-        e = self._e
-        mu, Sig, dmu, dSig = ylm_moments_device_grad(e, r=r, a=a, b=b, c=c, n=n, **self._ukw)
-        e.set_moments_dev(mu, Sig)
-        if not names:
-            return None, None
-        tang = {name: (dmu[k], dSig[k]) for k, name in enumerate(("r", "a", "b"))}
-        if "c" in names or "n" in names:
-            eps = torch.diag(_upstream_eps(mu.shape[0], self._ukw, like=mu))
-            if c != 0 and n != 0:
-                tang["c"] = (mu / c, 2.0 * (Sig - eps) / c)
-                tang["n"] = (mu / n, (Sig - eps) / n)
-            else:
-                mu1, Sig1 = ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)
-                S1 = Sig1 - eps
-                tang["c"] = (n * mu1, 2.0 * c * n * S1)
-                tang["n"] = (c * mu1, c * c * S1)
-        return torch.stack([tang[k][0] for k in names]), torch.stack([tang[k][1] for k in names])
+        """The engine's moments set at the point; (dmu [Ph, N], dSig [Ph, N, N]) in the order of ``names``."""
+        return _moment_tangents(self._e, self._ukw, names, r, a, b, c, n)[2:]
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
                  params=("r", "a", "b", "c", "n"), star_params=("i", "p"), return_tangents=False):
@@ -1112,3 +1118,151 @@ def cramer_rao_ensemble(per_star, n_shared, status=None):
             X = cov_ss[s] @ F[s, :Ph, Ph:].T              # F_**^-1 F_*h
             sigma_star[s] = np.sqrt(np.diag(cov_ss[s] + X @ cov_shared @ X.T))
     return dict(cov_shared=cov_shared, sigma_shared=sigma_shared, sigma_star=sigma_star, sigma_star_known=known)
+
+
+# the largest degree the inclination grid's kernels serve (2 ydeg + 1 <= 61 rows, one per lane of a wavefront)
+_INCL_GRAD_MAX_YDEG = 30
+
+
+def _or_flags(status):
+    """Bitwise or of the library's per-star flags over the last axis of a device tensor."""
+    out = 0
+    for bit in (1, 2, 4, 8, 16):
+        out = out + ((status & bit) != 0).any(dim=-1).to(status.dtype) * bit
+    return out
+
+
+class EnsembleGradientInclinations(_EnsembleSweep):
+    """The ensemble log-likelihood with every star's inclination marginalised EXACTLY on a grid, and its gradient:
+
+        lnL_s = log sum_j w_j exp(lnL_s(i_j)),      lnL_s(i_j) the conditional branch at grid inclination i_j
+
+    with w_j the prior weights ``StarryProcess._inc_prior_weights(inc, inc_weights)`` (sin i di by default) -- the
+    quantity the marginal branch (``EnsembleGradient``) approximates to second moments and ``ylm_conditional_marginal``
+    uses as ``pinc``.  The grid runs through the rank-(2 ydeg + 1) Fourier basis (sp_lnlike_inclinations_grad, DESIGN.md
+    22): no K x K matrix, cost linear in K.
+
+        eg = EnsembleGradientInclinations(t, flux, ferr=1e-3, p=periods, inc=np.linspace(0, 90, 100))   # data -> GPU, once
+        lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10., params=("r", "a", "b", "c", "n"))
+        eg.lnlike (S,), eg.per_star (S, Pd), eg.pinc (S, P), eg.lnlike_grid (S, P), eg.status (S,), eg.names
+
+    t: (K,) or (S, K); flux (S, K); ferr: a scalar, (S,) or (S, K); p, baseline_mean, baseline_var: scalars or (S,); u:
+    (udeg,) or (S, udeg); inc in degrees.  The constructor uploads the data and plans it once (sp_incl_plan_data).  A
+    star the basis cannot take (SP_STAR_NO_BASIS in ``status``: partial phase coverage, fewer distinct phases than
+    2 ydeg + 1, a variance <= 0) goes through the dense conditional sweep instead, replicated over the grid
+    inclinations, and enters the same mixture.  ydeg <= 30.
+
+    Not served: a time-variable process (``tau``), a full ``data_cov`` matrix or a matrix ``baseline_var`` (refused here;
+    ``EnsembleGradientConditional`` takes ``tau`` at known inclinations); derivatives with respect to per-star parameters
+    (p, baselines, noise) or the spread of radii dr; more than one light curve per star; a multi-stream form."""
+
+    _open = staticmethod(get_engine)
+
+    def __init__(self, t, flux, ferr=1.0e-3, p=1.0, inc=np.linspace(0, 90, 100), inc_weights=None, u=None, ydeg=15,
+                 baseline_mean=0.0, baseline_var=0.0, normalized=True, tau=None, data_cov=None, device=None,
+                 upstream_kwargs=None):
+        from .sp import StarryProcess
+
+        flux = np.asarray(flux, dtype=np.float64)
+        if flux.ndim != 2:
+            raise ValueError("flux must be (S, K)")
+        if tau:
+            raise NotImplementedError("a time-variable process (tau) has no rank-(2 ydeg + 1) basis: use "
+                                      "EnsembleGradientConditional at known inclinations")
+        if data_cov is not None:
+            raise NotImplementedError("data_cov: the inclination grid takes per-cadence variances only, through ferr "
+                                      "(scalar, (S,) or (S, K)); a full covariance matrix needs the dense route, "
+                                      "EnsembleGradientConditional")
+        if np.ndim(baseline_var) > 1:
+            raise NotImplementedError("a matrix baseline_var needs the dense route, EnsembleGradientConditional")
+        if int(ydeg) > _INCL_GRAD_MAX_YDEG:
+            raise ValueError("ydeg = %d: the inclination grid serves ydeg <= %d" % (int(ydeg), _INCL_GRAD_MAX_YDEG))
+        inc = np.atleast_1d(np.asarray(inc, dtype=np.float64)).reshape(-1)
+        check_period_inclination(None, inc)
+        if inc.size < 1:
+            raise ValueError("at least one inclination")
+        self._inc = inc
+        self._logw = StarryProcess._log_weights(StarryProcess._inc_prior_weights(inc, inc_weights))
+        stars, _ = self._setup(t, flux, ferr, p, defaults["i"], u, ydeg, baseline_mean, baseline_var, None, "matern32",
+                               device)
+        e = self._e
+        self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
+        self._inc_rad, self._logw_dev = e.f64(inc * (np.pi / 180)), e.f64(self._logw)
+        self._plan, pstat = e.incl_plan_data(self._t, self._flux, self._stars, self._diag)
+        self._dense = np.flatnonzero(pstat.cpu().numpy().astype(np.uint32) & SP_STAR_NO_BASIS)
+        # a star of the dense route: its record once per grid inclination
+        self._dense_stars = []
+        for s in self._dense:
+            rep = np.repeat(stars[s:s + 1], inc.size)
+            rep["inc"] = inc * (np.pi / 180)
+            self._dense_stars.append(e.stars_to_device(rep))
+        self.lnlike = self.per_star = self.pinc = self.lnlike_grid = self.status = self.names = None
+
+    def _dense_star(self, k, dmu, dSig):
+        """(lnlike_grid [P], lnmix, dlnmix [Pd], pinc [P], status) of the k-th star of the dense route, on the device:
+        the conditional sweep at the engine's moments on the star replicated over the grid, then the same mixture."""
+        import torch
+
+        e, s, P = self._e, int(self._dense[k]), self._inc.size
+        rows = lambda x: None if x is None else x[s:s + 1].expand(P, -1).contiguous()          # noqa: E731
+        lnl, mubar, sigbar, _, status = e.lnlike_grad_conditional(
+            rows(self._t), rows(self._flux), self._dense_stars[k], self._rta1, diag=rows(self._diag),
+            temporal=self._temporal, normalized=self._normalized)
+        ninf = torch.full_like(lnl, -np.inf)
+        lnl = torch.where(torch.isnan(lnl), ninf, lnl)
+        a = self._logw_dev + lnl
+        live = a > -np.inf
+        if not bool(live.any()):
+            zero = torch.zeros_like(lnl)
+            return lnl, ninf[0], torch.zeros(dmu.shape[0], dtype=lnl.dtype, device=lnl.device), zero, status
+        lnmix = torch.logsumexp(a, dim=0)
+        pinc = torch.where(live, torch.exp(a - lnmix), torch.zeros_like(a))
+        z1, z2 = torch.zeros_like(mubar), torch.zeros_like(sigbar)
+        gmu = (pinc[:, None] * torch.where(live[:, None], mubar, z1)).sum(dim=0)
+        gSig = (pinc[:, None, None] * torch.where(live[:, None, None], sigbar, z2)).sum(dim=0)
+        return lnl, lnmix, dmu @ gmu + (dSig * gSig).sum(dim=(1, 2)), pinc, status
+
+    def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
+                 params=("r", "a", "b", "c", "n")):
+        """(sum over the stars of finite value of lnL_s, in index order; {name: d / d name} over ``params``, any subset
+        of r, a, b, c, n -- a sub-block has the bits of the matching columns of the full call).  Afterwards ``lnlike``
+        [S], ``per_star`` [S, Pd] (d lnL_s / d params), ``pinc`` [S, P] (each star's inclination posterior on the grid),
+        ``lnlike_grid`` [S, P], ``status`` [S] (the flags of the star's grid points or-ed; SP_STAR_NO_BASIS: the star took
+        the dense route) and ``names``."""
+        import torch
+
+        names, _ = _check_conditional_params(params, ())
+        e = self._e
+        r, a, b, c, n = float(r), float(a), float(b), float(c), float(n)
+        mu, Sig, dmu, dSig = _moment_tangents(e, self._ukw, names, r, a, b, c, n)
+        S, P, Pd = self.S, self._inc.size, len(names)
+        grid, _, lnmix, dlnmix, pinc, status = e.lnlike_inclinations_grad(
+            self._plan, self._stars, self._rta1, mu, Sig, dmu, dSig, self._inc_rad, logw=self._logw_dev,
+            normalized=self._normalized)
+        stat = _or_flags(status)
+        for k, s in enumerate(self._dense):
+            grid[s], lnmix[s], dlnmix[s], pinc[s], st = self._dense_star(k, dmu, dSig)
+            stat[s] = _or_flags(st) | SP_STAR_NO_BASIS
+        # ONE transfer: [per-star values | per-star gradients | grid | posteriors | status]
+        host = torch.cat([lnmix, dlnmix.reshape(-1), grid.reshape(-1), pinc.reshape(-1),
+                          stat.to(torch.float64)]).cpu().numpy()
+        o = np.cumsum([0, S, S * Pd, S * P, S * P, S])
+        self.lnlike, self.per_star = host[o[0]:o[1]].copy(), host[o[1]:o[2]].reshape(S, Pd).copy()
+        self.lnlike_grid, self.pinc = host[o[2]:o[3]].reshape(S, P).copy(), host[o[3]:o[4]].reshape(S, P).copy()
+        self.status, self.names = host[o[4]:o[5]].astype(np.uint32), names
+        total, g = 0.0, np.zeros(Pd)
+        for s in range(S):          # (index order)
+            if np.isfinite(self.lnlike[s]):
+                total += self.lnlike[s]
+                g += self.per_star[s]
+        return float(total), {k: float(v) for k, v in zip(names, g)}
+
+
+def ensemble_gradient_inclinations(t, flux, ferr=1.0e-3, p=1.0, inc=np.linspace(0, 90, 100), r=defaults["r"],
+                                   a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
+                                   params=("r", "a", "b", "c", "n"), **kwargs):
+    """One-shot form of ``EnsembleGradientInclinations``: (sum_s lnL_s, {name: float}, lnL [S])."""
+    _check_conditional_params(params, ())          # (before anything goes to the device)
+    eg = EnsembleGradientInclinations(t, flux, ferr=ferr, p=p, inc=inc, **kwargs)
+    total, grad = eg(r=r, a=a, b=b, c=c, n=n, params=params)
+    return total, grad, eg.lnlike
