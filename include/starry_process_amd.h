@@ -965,6 +965,32 @@ int sp_lnlike_inclinations_grad(sp_handle *h, int S, const void *plan_dev, const
                                 double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev, void *workspace_dev,
                                 void *stream);
 
+/* The same with each star's own derivatives: slots 0-3 = d lnlike / d of the star's period (the integer
+ * part of t / p is data), baseline_mean, baseline_var and the log of a common factor on its data variances (not on
+ * baseline_var).  star_mask: bit k = slot k, 1 <= star_mask <= 15; ptan_dev: the plan's tangent along the period
+ * (sp_incl_plan_tangent; may be NULL when bit 0 is clear).  Outputs: dstar_dev [S,P,4] and, with logw_dev,
+ * dstarmix_dev [S,4] = sum_j pinc[s][j] dstar[s][j][.] in the mixture's summation order; a slot that was not asked for
+ * is NOT written.  -inf entries get zeros, a star the plan rejected NaN.  Everything said of
+ * sp_lnlike_inclinations_grad holds (stream, no synchronisation, no atomics, fixed orders, the same bits in any batch,
+ * ydeg <= 30, refusals, status), and lnlike, dlnlike, lnmix, dlnmix and pinc have its bits; a slot's bits do not depend
+ * on the other slots asked for.  Same workspace.
+ * sp_incl_plan_tangent: once per data set, beside sp_incl_plan_data (M = 1) and from the same t_dev, flux_dev, diag_dev,
+ * stars_dev: per star Ldot [n,n], wdot [n], g0dot [n], T0dot [n], rhodot (n = 2 ydeg + 1; the plan's layout and
+ * stride), then W = L_G^-1 Ldot [n,n], the factor the evaluation contracts, into ptan_dev,
+ * sp_incl_plan_tangent_bytes(h, S) bytes; NaN for a star the plan flagged. */
+size_t sp_incl_plan_tangent_bytes(sp_handle *h, int S);
+int sp_incl_plan_tangent(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                         const double *diag_dev, const sp_star *stars_dev, const void *plan_dev, void *ptan_dev,
+                         void *stream);
+int sp_lnlike_inclinations_grad_stars(sp_handle *h, int S, const void *plan_dev, const sp_star *stars_dev,
+                                      const double *rta1_dev, int ntab, const double *mean_ylm_dev,
+                                      const double *cov_ylm_dev, int Pd, const double *dmean_dev, const double *dcov_dev,
+                                      int P, const double *inc_rad_dev, const double *logw_dev, int normalized,
+                                      int norm_order, double zmax, double *lnlike_dev, double *dlnlike_dev,
+                                      double *lnmix_dev, double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev,
+                                      const void *ptan_dev, int star_mask, double *dstar_dev, double *dstarmix_dev,
+                                      void *workspace_dev, void *stream);
+
 /* ---- surface-map posteriors with the inclination marginalised on a grid (csrc/sp_ylm_incl.hip) --------
  * The posterior of the Ylm map of star s given its light curve, mixed over the P grid inclinations inc[j] with the
  * weights pinc[s][j] = softmax_j(logprior[j] + lnL[s][j]), lnL the un-normalised sp_lnlike_inclinations value

@@ -130,6 +130,10 @@ PROTOTYPES = {
     "sp_lnlike_inclinations_grad_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_lnlike_inclinations_grad": (_I, [_V, _I, _V, _V, _V, _I, _V, _V, _I, _V, _V, _I, _V, _V, _I, _I, _D, _V, _V, _V,
                                          _V, _V, _V, _V, _V]),
+    "sp_incl_plan_tangent_bytes": (ctypes.c_size_t, [_V, _I]),
+    "sp_incl_plan_tangent": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "sp_lnlike_inclinations_grad_stars": (_I, [_V, _I, _V, _V, _V, _I, _V, _V, _I, _V, _V, _I, _V, _V, _I, _I, _D, _V, _V,
+                                               _V, _V, _V, _V, _V, _I, _V, _V, _V, _V]),
     "sp_ylm_conditional_inclinations_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
     "sp_ylm_conditional_inclinations": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _I, _V, _V, _V, _V, _V, _V, _V,
                                              _I, _V, _V]),

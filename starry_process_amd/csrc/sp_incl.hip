@@ -32,25 +32,10 @@
 
 namespace {
 
-constexpr int IC_CH = 32;     // cadences per chunk of the data stage's Fourier sums
 constexpr int IC_PC = 8;      // inclinations per workgroup of the model stage
 // Largest G00 trace(G^-1) the basis route takes (the measured sweep over phase coverage)
 constexpr double IC_KAPPA_MAX = 3e8;
 static_assert(2 * IC_CH >= 2 * SP_MAX_YDEG + 1, "the conditioning estimate's n x n scratch reuses the cadence tables");
-
-__device__ __forceinline__ int ic_nobs(const sp_star &st, int K) { return st.nobs > 0 && st.nobs < K ? st.nobs : K; }
-
-// T_a at one cadence from the tables of cos / sin(j theta), j = 0 .. L
-__device__ __forceinline__ double ic_T(const double *tc, const double *ts, int a) {
-  return a == 0 ? 1.0 : ((a & 1) ? tc[(a + 1) >> 1] : ts[a >> 1]);
-}
-
-__device__ __forceinline__ double ic_phase(double t, double p) {
-  // (the likelihood path's phase, sp_assemble.hip theta_kernel)
-  double m = fmod(t / p, 1.0);
-  if (m != 0.0 && m < 0.0) m += 1.0;
-  return 6.283185307179586 * m;
-}
 
 // One workgroup (256 threads) per star.  plan[s]: L_G [n][n] (zero above the diagonal), w [M][n], g0 [n], T0 [n],
 // then {sum_m rho_m, sum log d, nobs, flag}.  flag = 1: a variance <= 0 or not finite, G does not factor

@@ -19,6 +19,20 @@
 //   dm = g0^T dM g0 / K^2, dmu = T0 . dc, dz = dm / mu^2 - 2 z dmu / mu, dalpha = alpha'(z) dz, dbeta = beta'(z) dz,
 //   dv = dM g0 / (K m) - v dm / m,
 //   <A, dM~> = dc0 <A, M> + c0 <A, dM> + dgam p^T A p - 2 gam p^T A dv - dza v^T A v - 2 za v^T A dv.
+//
+// Each star's own derivatives (sp_lnlike_inclinations_grad_stars; slots p, baseline_mean, baseline_var, log_var), with
+// B = x x^T - H^-1, Y = M~ L_G and rho the plan's residual:
+//   baseline_var   A00                                   (dM~ = e0 e0^T)
+//   baseline_mean  (L_G)00 x0                            (1 = T e0: dw = -L_G^T e0, rho unchanged)
+//   log_var        1/2 (rho + tr B + n - K)              (d -> e^lambda d: L_G, w -> e^(-lambda/2), rho -> e^-lambda rho)
+//   p              <Y B, Ldot> + <A, dM~> - x^T dw' - 1/2 rhodot,   dw' = wdot - dgp L_G^T e0 - gp Ldot^T e0
+// where Ldot, wdot, g0dot, T0dot, rhodot are the plan's tangent along the period (incl_tangent_kernel, once per data
+// set; the integer part of t / p is data, so d theta_k / dp = -2 pi t_k / p^2).  The model does not depend on p: dM = 0,
+// dm = 2 g0dot^T M g0 / K^2, dmu = T0dot . c, dv = M g0dot / (K m) - v dm / m in the formulas above (normalised), or
+// gp = T0 . c, dgp = T0dot . c (not normalised).  Y is overwritten by the time B exists, and is not needed: with
+// Ldot = L_G W (W = Phi(L_G^-1 Gdot L_G^-T), which the tangent holds beside Ldot), L_G^T Y = H - I and H x = w',
+//   <Y B, Ldot> = <B, (H - I) W> = w'^T W x - tr W - <B, W> = sum_{c <= a} W_ac (w'_a x_c - B_ac - [a = c]),
+// one pass over the triangle at the moment sA holds B: no fourth n x n array and no n^3 product.
 #include <cfloat>
 
 #include "sp_incl_triple.h"
@@ -27,6 +41,9 @@ namespace {
 
 // lnlike / status [S][P], dlnlike [S][P][Pd].  Mm [1 + Pd][ntab][P][n][n], cm [1 + Pd][ntab][P][n]: set 0 the moments,
 // set 1 + k direction k.
+// STAR: also dstar [S][P][4], the slots of `mask` (bit k = slot k of p, baseline_mean, baseline_var, log_var); ptan
+// [S][tstride]: the plan's tangent along the period (read with bit 0 only).  Without STAR the four are not touched.
+template <bool STAR>
 __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int ntab, int Pd,
                                                               const sp_star *__restrict__ stars,
                                                               const double *__restrict__ plan, long pstride,
@@ -34,7 +51,9 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
                                                               const double *__restrict__ cm, int normalized, int order,
                                                               double zmax, double *__restrict__ lnlike,
                                                               double *__restrict__ dlnlike,
-                                                              uint32_t *__restrict__ status) {
+                                                              uint32_t *__restrict__ status,
+                                                              const double *__restrict__ ptan, long tstride,
+                                                              int mask, double *__restrict__ dstar) {
   extern __shared__ __attribute__((aligned(16))) double ig_lds[];
   const int n = 2 * L + 1, tid = threadIdx.x;
   const long tri = blockIdx.x;
@@ -49,12 +68,14 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
   double *sq = sp + n;          // n      A v
   double *s1 = sq + n;          // n      a direction's row sums of A o dM
   double *s2 = s1 + n;          // n      dM g0
+  double *sred = s2 + n;        // 64     (STAR) the lanes' partial sums of <Y B, Ldot>
   __shared__ double sc[4];      // fm (flux mean), gp (GP mean subtracted from r), <A, M>
   __shared__ int notpd, dead;
   const sp_star st = stars[s];
   const double *Pl = plan + (size_t)s * pstride;
   const double *Pw = Pl + (size_t)n * n, *Pg = Pw + n, *Pt = Pg + n, *Ps = Pt + n;
   double *dout = dlnlike + (size_t)tri * Pd;
+  double *sout = STAR ? dstar + (size_t)tri * 4 : nullptr;
   const bool stale = st.table < 0 || st.table >= ntab;
   if (stale || Ps[3] != 0.0) {
     if (tid == 0) {
@@ -62,6 +83,7 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
       if (status) status[tri] = stale ? SP_STAR_NAN : SP_STAR_NO_BASIS;
     }
     if (tid < Pd) dout[tid] = __builtin_nan("");
+    if (STAR && tid < 4 && ((mask >> tid) & 1)) sout[tid] = __builtin_nan("");
     return;
   }
   const size_t mo = (size_t)st.table * P + p, bstride = (size_t)ntab * P;
@@ -104,6 +126,7 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
   __syncthreads();
   if (dead) {   // (-inf has no slope: zeros, as the likelihood's other paths give)
     if (tid < Pd) dout[tid] = 0.0;
+    if (STAR && tid < 4 && ((mask >> tid) & 1)) sout[tid] = 0.0;
     return;
   }
   // L_H^-1 into sY: lane c solves L_H y = e_c down its own column
@@ -128,6 +151,24 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
     sA[e] = sx[a] * sx[c] - h;
   }
   __syncthreads();
+  double trB = 0.0;
+  if constexpr (STAR) {
+    if (tid == 0)
+      for (int a = 0; a < n; ++a) trB += sA[a * n + a];
+    if (mask & 1) {
+      // <Y B, Ldot> = sum over W's triangle of W_ac (w'_a x_c - B_ac - [a = c]), a partial sum per lane
+      const double *W = ptan + (size_t)s * tstride + pstride;
+      const double shift = sc[1] * sL[0];
+      double part = 0.0;
+      for (int e = tid; e < n * n; e += 64) {
+        const int a = e / n, c = e - a * n;
+        if (c > a) continue;
+        const double wa = a == 0 ? Pw[0] - shift : Pw[a];
+        part += W[e] * (wa * sx[c] - sA[e] - (a == c ? 1.0 : 0.0));
+      }
+      sred[tid] = part;
+    }
+  }
   // sY = (x x^T - H^-1) L_G^T
   for (int e = tid; e < n * n; e += 64) {
     const int a = e / n, c = e - a * n;
@@ -222,6 +263,51 @@ __global__ __launch_bounds__(64) void incl_grad_triple_kernel(int L, int P, int 
     }
     __syncthreads();
   }
+  if constexpr (STAR) {
+    const double *Td = ptan + (size_t)s * tstride;   // (Ldot, wdot, g0dot, T0dot, rhodot laid out as the plan; then W)
+    const double *wd = Td + (size_t)n * n, *gd = wd + n, *td = gd + n;
+    const bool per = mask & 1;
+    if (per && normalized && tid < n) {
+      const int a = tid;
+      double r2 = 0.0;
+      for (int c = 0; c < n; ++c) r2 += Mp[c * n + a] * gd[c];   // M g0dot (M symmetric)
+      s2[a] = r2;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      if (mask & 2) sout[1] = sL[0] * sx[0];
+      if (mask & 4) sout[2] = sA[0];
+      if (mask & 8) sout[3] = 0.5 * (Ps[0] + trB + (double)n - nobs);
+      if (per) {
+        double ybl = 0.0, xw = 0.0, dfm = 0.0;
+        for (int l = 0; l < 64; ++l) ybl += sred[l];
+        for (int a = 0; a < n; ++a) {
+          xw += sx[a] * wd[a];
+          dfm += td[a] * cp[a];
+        }
+        double out = ybl - 0.5 * td[n];
+        if (!normalized) {
+          out -= xw - (dfm * sL[0] + sc[1] * Td[0]) * sx[0];
+        } else {
+          double dm = 0.0, pAd = 0.0, vAd = 0.0;
+          for (int a = 0; a < n; ++a) {
+            dm += gd[a] * sv[a];
+            pAd += sp[a] * s2[a];
+            vAd += sq[a] * s2[a];
+          }
+          dm *= 2.0 * nm.km / (nobs * nobs);   // (M g0 = K m v)
+          const double mu = nm.mu, dz = dm / (mu * mu) - 2.0 * nm.z * dfm / mu;
+          const double dalpha = alpha1 * dz, dbeta = beta1 * dz;
+          const double dc0 = dalpha / (mu * mu) - 2.0 * nm.c0 * dfm / mu;
+          const double dgam = dz * (nm.alpha + nm.beta) + nm.z * (dalpha + dbeta);
+          const double dza = dz * nm.alpha + nm.z * dalpha;
+          const double pAdv = pAd / nm.km - pAv * dm / nm.m, vAdv = vAd / nm.km - vAv * dm / nm.m;
+          out += dc0 * AM + dgam * pAp - 2.0 * nm.gam * pAdv - dza * vAv - 2.0 * nm.za * vAdv - xw;
+        }
+        sout[0] = out;
+      }
+    }
+  }
 }
 
 // One wavefront per star: lane l takes the grid points l, l + 64, ...; the 64 partial sums are added in lane order.
@@ -283,7 +369,287 @@ __global__ __launch_bounds__(64) void incl_mix_kernel(int P, int Pd, const doubl
   }
 }
 
-size_t ig_triple_lds(int n) { return sizeof(double) * (3 * (size_t)n * n + 7 * (size_t)n); }
+// The mixture of the per-star slots, after incl_mix_kernel: dstarmix[s][k] = sum_j pinc[s][j] dstar[s][j][k] for the slots
+// of `mask`, in incl_mix_kernel's order (lane l: the grid points l, l + 64, ...; the 64 partial sums in lane order).
+__global__ __launch_bounds__(64) void incl_mix_star_kernel(int P, int mask, const double *__restrict__ pinc,
+                                                           const double *__restrict__ dstar,
+                                                           double *__restrict__ dstarmix) {
+  __shared__ double red[64];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const double *pi = pinc + (size_t)s * P, *dl = dstar + (size_t)s * P * 4;
+  if (isnan(pi[0])) {   // (the plan's flag: incl_mix_kernel left NaN in the whole row)
+    if (tid < 4 && ((mask >> tid) & 1)) dstarmix[(size_t)s * 4 + tid] = __builtin_nan("");
+    return;
+  }
+  for (int d = 0; d < 4; ++d) {
+    if (!((mask >> d) & 1)) continue;
+    double part = 0.0;
+    for (int j = tid; j < P; j += 64) {
+      const double w = pi[j];
+      if (w > 0.0) part += w * dl[(size_t)j * 4 + d];
+    }
+    red[tid] = part;
+    __syncthreads();
+    if (tid == 0) {
+      double g = 0.0;
+      for (int l = 0; l < 64; ++l) g += red[l];
+      dstarmix[(size_t)s * 4 + d] = g;
+    }
+    __syncthreads();
+  }
+}
+
+// d T_a / d theta at one cadence from the tables of cos / sin(j theta)
+__device__ __forceinline__ double ic_dT(const double *tc, const double *ts, int a) {
+  const int j = (a + 1) >> 1;
+  return a == 0 ? 0.0 : ((a & 1) ? -(double)j * ts[j] : (double)j * tc[j]);
+}
+
+// The plan's derivative with respect to each star's period, one workgroup (256 threads) per star, in the style of
+// incl_data_kernel.  With tau_k = d theta_k / dp = -2 pi t_k / p^2 and T' = diag(tau) dT / d theta:
+//   Gdot = T'^T D^-1 T + T^T D^-1 T'   from the (tau / d)-weighted sums of cos / sin(j theta), j <= 2L (the derivative of
+//                                      incl_data_kernel's product-to-sum entries: d cos = -j sin, d sin = j cos),
+//   Ldot = L_G Phi(L_G^-1 Gdot L_G^-T) (Phi: the lower triangle, its diagonal halved),
+//   wdot = L_G^-1 (T'^T D^-1 r - Ldot w),  g0dot = T'^T 1,  T0dot = T'[0],
+//   rhodot = -2 (r - T beta)^T D^-1 T' beta,  beta = L_G^-T w   (beta minimises rho: no term through beta).
+// tan[s]: Ldot [n][n] (zero above the diagonal), wdot [n], g0dot [n], T0dot [n], rhodot -- the plan's layout, pstride
+// doubles -- then W = Phi(.) = L_G^-1 Ldot [n][n] (zero above the diagonal), which the triple stage contracts instead of
+// Ldot; NaN for a star the plan flagged.
+__global__ __launch_bounds__(256) void incl_tangent_kernel(int L, int K, const double *__restrict__ t,
+                                                           const double *__restrict__ flux,
+                                                           const double *__restrict__ diag,
+                                                           const sp_star *__restrict__ stars, long pstride,
+                                                           const double *__restrict__ plan, long tstride,
+                                                           double *__restrict__ tan) {
+  extern __shared__ __attribute__((aligned(16))) double ic_lds[];
+  const int n = 2 * L + 1, J2 = 2 * L + 1;
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const sp_star st = stars[s];
+  const int nobs = ic_nobs(st, K);
+  // quantities: Fc'[0..2L], Fs'[0..2L] (weights tau / d), g0dot [n] (weights tau), b' [n] (weights tau r / d)
+  const int qG = 2 * J2, qB = qG + n, Q = qB + n;
+  double *sQ = ic_lds;                    // Q
+  double *sL = sQ + Q;                    // n x n  L_G
+  double *sX = sL + n * n;                // n x n  Gdot, then L_G^-1 Gdot L_G^-T
+  double *sTc = sX + n * n;               // IC_CH x J2
+  double *sTs = sTc + IC_CH * J2;         // IC_CH x J2
+  double *sW = sTs + IC_CH * J2;          // IC_CH  tau / d
+  double *sU = sW + IC_CH;                // IC_CH  tau
+  double *sR = sU + IC_CH;                // IC_CH  r
+  double *sw = sR + IC_CH;                // n      w
+  double *sBeta = sw + n;                 // n      beta
+  double *su = sBeta + n;                 // n      Phi(X) w, then b' - L_G Phi(X) w
+  double *sRed = su + n;                  // 256
+  const double *Pl = plan + (size_t)s * pstride;
+  const double *Pw = Pl + (size_t)n * n, *Ps = Pw + 3 * (size_t)n;
+  double *To = tan + (size_t)s * tstride;
+  double *Tw = To + (size_t)n * n, *Tg = Tw + n, *Tt = Tg + n, *TW = To + pstride;
+  if (Ps[3] != 0.0) {
+    for (long e = tid; e < tstride; e += 256) To[e] = __builtin_nan("");
+    return;
+  }
+  const double *ts_ = t + (size_t)s * K;
+  const double *fl = flux + (size_t)s * K;
+  const double dth = -6.283185307179586 / (st.period * st.period);
+  for (int e = tid; e < n * n; e += 256) sL[e] = Pl[e];
+  for (int a = tid; a < n; a += 256) sw[a] = Pw[a];
+  __syncthreads();
+  if (tid == 0) {   // beta = L_G^-T w
+    for (int a = n - 1; a >= 0; --a) {
+      double x = sw[a];
+      for (int k = a + 1; k < n; ++k) x -= sL[k * n + a] * sBeta[k];
+      sBeta[a] = x / sL[a * n + a];
+    }
+  }
+  for (int q0 = 0; q0 < Q; q0 += 256) {
+    const int q = q0 + tid;
+    double acc = 0.0;
+    for (int c0 = 0; c0 < nobs; c0 += IC_CH) {
+      const int nc = nobs - c0 < IC_CH ? nobs - c0 : IC_CH;
+      __syncthreads();
+      for (int e = tid; e < nc * J2; e += 256) {
+        const int k = e / J2, j = e - k * J2;
+        double sn, cn;
+        sincos((double)j * ic_phase(ts_[c0 + k], st.period), &sn, &cn);
+        sTc[k * J2 + j] = cn;
+        sTs[k * J2 + j] = sn;
+      }
+      for (int k = tid; k < nc; k += 256) {
+        const double d = diag ? diag[(size_t)s * K + c0 + k] : st.data_var;
+        const double tau = dth * ts_[c0 + k];
+        sU[k] = tau;
+        sW[k] = tau / d;
+        sR[k] = fl[c0 + k] - st.baseline_mean;
+      }
+      __syncthreads();
+      if (q < Q) {
+        if (q < qG) {
+          const bool sn = q >= J2;
+          const int j = sn ? q - J2 : q;
+          const double *tab = sn ? sTs : sTc;
+          for (int k = 0; k < nc; ++k) acc += sW[k] * tab[k * J2 + j];
+        } else if (q < qB) {
+          for (int k = 0; k < nc; ++k) acc += sU[k] * ic_dT(sTc + k * J2, sTs + k * J2, q - qG);
+        } else {
+          for (int k = 0; k < nc; ++k) acc += sW[k] * sR[k] * ic_dT(sTc + k * J2, sTs + k * J2, q - qB);
+        }
+      }
+    }
+    if (q < Q) sQ[q] = acc;
+  }
+  __syncthreads();
+  // Gdot: incl_data_kernel's entries differentiated term by term
+  for (int e = tid; e < n * n; e += 256) {
+    const int a = e / n, b = e - a * n;
+    const int ja = (a + 1) >> 1, jb = (b + 1) >> 1;
+    const bool sa = a > 0 && !(a & 1), sb = b > 0 && !(b & 1);
+    const int dm = ja > jb ? ja - jb : jb - ja, dp = ja + jb;
+    const double *Fc = sQ, *Fs = sQ + J2;
+    double g;
+    if (!sa && !sb) {
+      g = -0.5 * (dm * Fs[dm] + dp * Fs[dp]);
+    } else if (sa && sb) {
+      g = 0.5 * (dp * Fs[dp] - dm * Fs[dm]);
+    } else {
+      const int js = sa ? ja : jb, jc = sa ? jb : ja;   // sin(js) cos(jc) = (sin(js+jc) + sin(js-jc)) / 2
+      g = 0.5 * (dp * Fc[dp] + (js - jc) * Fc[dm]);
+    }
+    sX[e] = g;
+  }
+  __syncthreads();
+  // X = L_G^-1 Gdot L_G^-T in place: thread c solves down column c, then thread a along row a
+  for (int c = tid; c < n; c += 256)
+    for (int a = 0; a < n; ++a) {
+      double x = sX[a * n + c];
+      for (int k = 0; k < a; ++k) x -= sL[a * n + k] * sX[k * n + c];
+      sX[a * n + c] = x / sL[a * n + a];
+    }
+  __syncthreads();
+  for (int a = tid; a < n; a += 256)
+    for (int c = 0; c < n; ++c) {
+      double x = sX[a * n + c];
+      for (int k = 0; k < c; ++k) x -= sL[c * n + k] * sX[a * n + k];
+      sX[a * n + c] = x / sL[c * n + c];
+    }
+  __syncthreads();
+  // Phi in place (the upper triangle is not read again)
+  for (int a = tid; a < n; a += 256) sX[a * n + a] *= 0.5;
+  __syncthreads();
+  // Ldot = L_G Phi(X); u = Phi(X) w
+  for (int e = tid; e < n * n; e += 256) {
+    const int a = e / n, c = e - a * n;
+    double x = 0.0;
+    for (int k = c; k <= a; ++k) x += sL[a * n + k] * sX[k * n + c];
+    To[e] = x;   // (c > a: the empty sum)
+    TW[e] = c <= a ? sX[e] : 0.0;
+  }
+  for (int a = tid; a < n; a += 256) {
+    double x = 0.0;
+    for (int c = 0; c <= a; ++c) x += sX[a * n + c] * sw[c];
+    su[a] = x;
+  }
+  __syncthreads();
+  // wdot = L_G^-1 (b' - L_G u)
+  double lu = 0.0;
+  if (tid < n)
+    for (int k = 0; k <= tid; ++k) lu += sL[tid * n + k] * su[k];
+  __syncthreads();
+  if (tid < n) su[tid] = sQ[qB + tid] - lu;
+  __syncthreads();
+  if (tid == 0) {
+    for (int a = 0; a < n; ++a) {
+      double x = su[a];
+      for (int k = 0; k < a; ++k) x -= sL[a * n + k] * su[k];
+      su[a] = x / sL[a * n + a];
+    }
+  }
+  // rhodot, one cadence per thread, fixed-order reduction
+  double rd = 0.0;
+  for (int k = tid; k < nobs; k += 256) {
+    const double th = ic_phase(ts_[k], st.period);
+    const double d = diag ? diag[(size_t)s * K + k] : st.data_var;
+    double f = sBeta[0], fp = 0.0;
+    for (int j = 1; j <= L; ++j) {
+      double sn, cn;
+      sincos((double)j * th, &sn, &cn);
+      f += sBeta[2 * j - 1] * cn + sBeta[2 * j] * sn;
+      fp += (double)j * (sBeta[2 * j] * cn - sBeta[2 * j - 1] * sn);
+    }
+    rd -= 2.0 * ((fl[k] - st.baseline_mean) - f) * (dth * ts_[k]) * fp / d;
+  }
+  sRed[tid] = rd;
+  __syncthreads();
+  for (int a = tid; a < n; a += 256) {
+    Tw[a] = su[a];
+    Tg[a] = sQ[qG + a];
+    const int j = (a + 1) >> 1;
+    double sn, cn;
+    sincos((double)j * ic_phase(ts_[0], st.period), &sn, &cn);
+    Tt[a] = a == 0 ? 0.0 : (dth * ts_[0]) * ((a & 1) ? -(double)j * sn : (double)j * cn);
+  }
+  if (tid == 0) {
+    double r = 0.0;
+    for (int i = 0; i < 256; ++i) r += sRed[i];
+    Tt[n] = r;
+  }
+}
+
+// dynamic LDS of the triple kernel: the three n x n arrays and seven vectors; with the per-star slots the lanes' partial sums
+size_t ig_triple_lds(int n, int mask) { return sizeof(double) * (3 * (size_t)n * n + 7 * (size_t)n + (mask ? 64 : 0)); }
+
+long ig_pstride(int n) { return (long)n * n + 3L * n + 4; }   // (the stride of a plan with one light curve)
+long ig_tstride(int n) { return ig_pstride(n) + (long)n * n; }
+
+size_t ig_tangent_lds(int L) {
+  const size_t n = 2 * L + 1;
+  return sizeof(double) * (4 * n + 2 * n * n + 2 * IC_CH * n + 3 * IC_CH + 3 * n + 256);
+}
+
+// Both entry points: star_mask = 0 is sp_lnlike_inclinations_grad (the variant of the triple kernel without the
+// per-star slots: its code and bits do not depend on the other variant).
+int ig_run(sp_handle *h, int S, const void *plan_dev, const sp_star *stars_dev, const double *rta1_dev, int ntab,
+           const double *mean_ylm_dev, const double *cov_ylm_dev, int Pd, const double *dmean_dev,
+           const double *dcov_dev, int P, const double *inc_rad_dev, const double *logw_dev, int normalized,
+           int norm_order, double zmax, double *lnlike_dev, double *dlnlike_dev, double *lnmix_dev,
+           double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev, const void *ptan_dev, int star_mask,
+           double *dstar_dev, double *dstarmix_dev, void *workspace_dev, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || S < 0 || !plan_dev || !stars_dev || !rta1_dev || ntab < 1 || ntab > 65535 || !mean_ylm_dev ||
+      !cov_ylm_dev || Pd < 1 || Pd > SP_INCL_GRAD_MAXDIR || !dmean_dev || !dcov_dev || P < 1 || P > 65535 ||
+      !inc_rad_dev || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !lnlike_dev || !dlnlike_dev ||
+      !workspace_dev || h->ydeg > SP_MAX_YDEG || (logw_dev && (!lnmix_dev || !dlnmix_dev || !pinc_dev)))
+    return SP_ERR_INVALID;
+  if (star_mask && (!dstar_dev || (logw_dev && !dstarmix_dev) || ((star_mask & 1) && !ptan_dev))) return SP_ERR_INVALID;
+  const int n = 2 * h->ydeg + 1;
+  const size_t tlds = ig_triple_lds(n, star_mask);
+  if (tlds > IC_LDS_MAX) return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  const long ntri = (long)S * P;
+  if (ntri > 0x7fffffffL) return SP_ERR_INVALID;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = sp_incl_model_stage(h, S, 1, ntab, P, rta1_dev, inc_rad_dev, 1, mean_ylm_dev, cov_ylm_dev, Pd, dmean_dev,
+                               dcov_dev, workspace_dev, st);
+  if (rc) return rc;
+  const SpInclModel mv = sp_incl_model_views(h, S, 1, ntab, 1 + Pd, P, workspace_dev);
+  auto *kern = star_mask ? incl_grad_triple_kernel<true> : incl_grad_triple_kernel<false>;
+  ic_lds_opt_in(reinterpret_cast<const void *>(kern), tlds);
+  hipLaunchKernelGGL(kern, dim3((unsigned)ntri), dim3(64), tlds, st, h->ydeg, P, ntab, Pd, stars_dev,
+                     static_cast<const double *>(plan_dev), mv.pstride, mv.Mm, mv.cm, normalized, norm_order, zmax,
+                     lnlike_dev, dlnlike_dev, status_dev, static_cast<const double *>(ptan_dev), ig_tstride(n), star_mask,
+                     dstar_dev);
+  SP_LAUNCH_CHECK();
+  if (logw_dev) {
+    hipLaunchKernelGGL(incl_mix_kernel, dim3(S), dim3(64), 0, st, P, Pd, logw_dev, lnlike_dev, dlnlike_dev, status_dev,
+                       lnmix_dev, dlnmix_dev, pinc_dev);
+    SP_LAUNCH_CHECK();
+    if (star_mask) {
+      hipLaunchKernelGGL(incl_mix_star_kernel, dim3(S), dim3(64), 0, st, P, star_mask, pinc_dev, dstar_dev,
+                         dstarmix_dev);
+      SP_LAUNCH_CHECK();
+    }
+  }
+  return SP_OK;
+}
 
 }  // namespace
 
@@ -301,33 +667,45 @@ int sp_lnlike_inclinations_grad(sp_handle *h, int S, const void *plan_dev, const
                                 double zmax, double *lnlike_dev, double *dlnlike_dev, double *lnmix_dev,
                                 double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev, void *workspace_dev,
                                 void *stream) {
+  return ig_run(h, S, plan_dev, stars_dev, rta1_dev, ntab, mean_ylm_dev, cov_ylm_dev, Pd, dmean_dev, dcov_dev, P,
+                inc_rad_dev, logw_dev, normalized, norm_order, zmax, lnlike_dev, dlnlike_dev, lnmix_dev, dlnmix_dev,
+                pinc_dev, status_dev, nullptr, 0, nullptr, nullptr, workspace_dev, stream);
+}
+
+int sp_lnlike_inclinations_grad_stars(sp_handle *h, int S, const void *plan_dev, const sp_star *stars_dev,
+                                      const double *rta1_dev, int ntab, const double *mean_ylm_dev,
+                                      const double *cov_ylm_dev, int Pd, const double *dmean_dev, const double *dcov_dev,
+                                      int P, const double *inc_rad_dev, const double *logw_dev, int normalized,
+                                      int norm_order, double zmax, double *lnlike_dev, double *dlnlike_dev,
+                                      double *lnmix_dev, double *dlnmix_dev, double *pinc_dev, uint32_t *status_dev,
+                                      const void *ptan_dev, int star_mask, double *dstar_dev, double *dstarmix_dev,
+                                      void *workspace_dev, void *stream) {
+  // (the mask and its tangent are refused before the device is asked for: a caller's mistake whatever the handle)
+  if (star_mask < 1 || star_mask > 15 || ((star_mask & 1) && !ptan_dev)) return SP_ERR_INVALID;
+  return ig_run(h, S, plan_dev, stars_dev, rta1_dev, ntab, mean_ylm_dev, cov_ylm_dev, Pd, dmean_dev, dcov_dev, P,
+                inc_rad_dev, logw_dev, normalized, norm_order, zmax, lnlike_dev, dlnlike_dev, lnmix_dev, dlnmix_dev,
+                pinc_dev, status_dev, ptan_dev, star_mask, dstar_dev, dstarmix_dev, workspace_dev, stream);
+}
+
+size_t sp_incl_plan_tangent_bytes(sp_handle *h, int S) {
+  if (!h || S < 1) return 0;
+  return sizeof(double) * (size_t)S * ig_tstride(2 * h->ydeg + 1);
+}
+
+int sp_incl_plan_tangent(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
+                         const double *diag_dev, const sp_star *stars_dev, const void *plan_dev, void *ptan_dev,
+                         void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || S < 0 || !plan_dev || !stars_dev || !rta1_dev || ntab < 1 || ntab > 65535 || !mean_ylm_dev ||
-      !cov_ylm_dev || Pd < 1 || Pd > SP_INCL_GRAD_MAXDIR || !dmean_dev || !dcov_dev || P < 1 || P > 65535 ||
-      !inc_rad_dev || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !lnlike_dev || !dlnlike_dev ||
-      !workspace_dev || h->ydeg > SP_MAX_YDEG || (logw_dev && (!lnmix_dev || !dlnmix_dev || !pinc_dev)))
+  if (!h || S < 0 || K < 1 || !t_dev || !flux_dev || !stars_dev || !plan_dev || !ptan_dev || h->ydeg > SP_MAX_YDEG)
     return SP_ERR_INVALID;
-  const int n = 2 * h->ydeg + 1;
-  const size_t tlds = ig_triple_lds(n);
-  if (tlds > IC_LDS_MAX) return SP_ERR_INVALID;
   if (S == 0) return SP_OK;
-  const long ntri = (long)S * P;
-  if (ntri > 0x7fffffffL) return SP_ERR_INVALID;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = sp_incl_model_stage(h, S, 1, ntab, P, rta1_dev, inc_rad_dev, 1, mean_ylm_dev, cov_ylm_dev, Pd, dmean_dev,
-                               dcov_dev, workspace_dev, st);
-  if (rc) return rc;
-  const SpInclModel mv = sp_incl_model_views(h, S, 1, ntab, 1 + Pd, P, workspace_dev);
-  ic_lds_opt_in(reinterpret_cast<const void *>(incl_grad_triple_kernel), tlds);
-  hipLaunchKernelGGL(incl_grad_triple_kernel, dim3((unsigned)ntri), dim3(64), tlds, st, h->ydeg, P, ntab, Pd,
-                     stars_dev, static_cast<const double *>(plan_dev), mv.pstride, mv.Mm, mv.cm, normalized,
-                     norm_order, zmax, lnlike_dev, dlnlike_dev, status_dev);
+  const size_t lds = ig_tangent_lds(h->ydeg);
+  if (lds > IC_LDS_MAX) return SP_ERR_INVALID;
+  ic_lds_opt_in(reinterpret_cast<const void *>(incl_tangent_kernel), lds);
+  hipLaunchKernelGGL(incl_tangent_kernel, dim3(S), dim3(256), lds, (hipStream_t)stream, h->ydeg, K, t_dev, flux_dev,
+                     diag_dev, stars_dev, ig_pstride(2 * h->ydeg + 1), static_cast<const double *>(plan_dev),
+                     ig_tstride(2 * h->ydeg + 1), static_cast<double *>(ptan_dev));
   SP_LAUNCH_CHECK();
-  if (logw_dev) {
-    hipLaunchKernelGGL(incl_mix_kernel, dim3(S), dim3(64), 0, st, P, Pd, logw_dev, lnlike_dev, dlnlike_dev, status_dev,
-                       lnmix_dev, dlnmix_dev, pinc_dev);
-    SP_LAUNCH_CHECK();
-  }
   return SP_OK;
 }
 

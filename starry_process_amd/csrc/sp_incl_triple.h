@@ -1,6 +1,7 @@
 // The front of a triple of the inclination grid (sp_incl.hip, sp_incl_grad.hip; DESIGN.md sections 11 and 22): one
 // wavefront loads L_G and M, assembles the normalised M~, forms H = I + L_G^T M~ L_G and factors it in LDS.  The value
-// kernel and the gradient kernel both call this, so a value has the same bits from either.
+// kernel and the gradient kernel both call this, so a value has the same bits from either.  Also the small helpers the
+// per-star data stages share (the plan of sp_incl.hip and its tangent along the period in sp_incl_grad.hip).
 #pragma once
 
 #include "sp_internal.h"
@@ -12,6 +13,22 @@ constexpr size_t IC_LDS_MAX = 150 * 1024;   // (as the other kernels that opt in
 static inline void ic_lds_opt_in(const void *fn, size_t lds) {
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)IC_LDS_MAX) != hipSuccess)
     (void)hipGetLastError();
+}
+
+constexpr int IC_CH = 32;     // cadences per chunk of the data stages' Fourier sums (sp_incl.hip, sp_incl_grad.hip)
+
+__device__ __forceinline__ int ic_nobs(const sp_star &st, int K) { return st.nobs > 0 && st.nobs < K ? st.nobs : K; }
+
+// T_a at one cadence from the tables of cos / sin(j theta), j = 0 .. L
+__device__ __forceinline__ double ic_T(const double *tc, const double *ts, int a) {
+  return a == 0 ? 1.0 : ((a & 1) ? tc[(a + 1) >> 1] : ts[a >> 1]);
+}
+
+__device__ __forceinline__ double ic_phase(double t, double p) {
+  // (the likelihood path's phase, sp_assemble.hip theta_kernel)
+  double m = fmod(t / p, 1.0);
+  if (m != 0.0 && m < 0.0) m += 1.0;
+  return 6.283185307179586 * m;
 }
 
 // what the normalisation of one triple computed (all zero when not normalised, c0 = 1)

@@ -1070,13 +1070,34 @@ class Engine(object):
                                         self._p(plan), self._p(status), self._stream()))
         return plan, status
 
+    def incl_plan_tangent(self, t, flux, stars_dev, plan, diag=None):
+        """The plan's derivative with respect to each star's period (sp_incl_plan_tangent), from the inputs of
+        ``incl_plan_data`` and its plan: per star Ldot [n, n], wdot, g0dot, T0dot [n], rhodot and W = L_G^-1 Ldot [n, n];
+        NaN for a star the plan flagged.  Once per data set; ``lnlike_inclinations_grad(star_tangent=...)`` reads it."""
+        t, flux = self.f64(t), self.f64(flux)
+        S, K = flux.shape
+        diag = None if diag is None else self.f64(diag)
+        ptan = self._scratch(max(int(self._L.sp_incl_plan_tangent_bytes(self._h, S)), 1))
+        if S == 0:
+            return ptan
+        if int(plan.numel()) < int(self._L.sp_incl_plan_bytes(self._h, S, 1)):
+            raise ValueError("the plan does not hold %d stars" % S)
+        check(self._L.sp_incl_plan_tangent(self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev),
+                                           self._p(plan), self._p(ptan), self._stream()))
+        return ptan
+
     def lnlike_inclinations_grad(self, plan, stars, rta1, mean_ylm, cov_ylm, dmu, dsig, inc_rad, logw=None,
-                                 normalized=True, norm_order=20, zmax=0.023):
+                                 normalized=True, norm_order=20, zmax=0.023, star_tangent=None, star_mask=0):
         """The grid of ``lnlike_inclinations`` for one moment set with its derivatives along Pd directions of the
         moments, and its mixture over the grid: plan (``incl_plan_data``), stars (host sp_star records or their device copy), rta1
         [ntab, N], mean_ylm [N], cov_ylm [N, N], dmu [Pd, N], dsig [Pd, N, N] (symmetric, 1 <= Pd <= 8), inc_rad [P],
         logw [P] log prior weights or None.  Returns (lnlike [S, P], dlnlike [S, P, Pd], lnmix [S], dlnmix [S, Pd],
-        pinc [S, P], status [S, P]); lnmix, dlnmix and pinc are None without logw."""
+        pinc [S, P], status [S, P]); lnmix, dlnmix and pinc are None without logw.
+
+        star_mask: bit k asks for slot k of each star's own derivatives (period, baseline_mean, baseline_var, log_var;
+        sp_lnlike_inclinations_grad_stars); star_tangent: the plan's ``incl_plan_tangent``, needed with bit 0.  The return
+        then ends with (dstar [S, P, 4], dstarmix [S, 4] or None without logw); a slot that was not asked for holds NaN.
+        The other outputs have the bits of the call without."""
         torch = _torch()
         N = self.N
         if isinstance(stars, np.ndarray):
@@ -1103,9 +1124,30 @@ class Engine(object):
         lnl, dlnl = self.empty(S, P), self.empty(S, P, Pd)
         status = torch.zeros(S, P, dtype=torch.int32, device=self.device)
         mix = (self.empty(S), self.empty(S, Pd), self.empty(S, P)) if lw is not None else (None, None, None)
+        star_mask = int(star_mask)
+        if not 0 <= star_mask <= 15:
+            raise ValueError("star_mask: bits 0-3 (period, baseline_mean, baseline_var, log_var)")
+        if star_mask & 1:
+            if star_tangent is None:
+                raise ValueError("star_mask asks for the period: star_tangent (incl_plan_tangent) is needed")
+            if S > 0 and int(star_tangent.numel()) < int(self._L.sp_incl_plan_tangent_bytes(self._h, S)):
+                raise ValueError("star_tangent does not hold %d stars" % S)
+        if S > 0 and int(plan.numel()) < int(self._L.sp_incl_plan_bytes(self._h, S, 1)):
+            raise ValueError("the plan does not hold %d stars" % S)
+        if star_mask:
+            nan = float("nan")
+            dstar = torch.full((S, P, 4), nan, dtype=torch.float64, device=self.device)
+            dstarmix = torch.full((S, 4), nan, dtype=torch.float64, device=self.device) if lw is not None else None
+            if S > 0:
+                ws = self._scratch(self._L.sp_lnlike_inclinations_grad_workspace_bytes(self._h, S, ntab, P, Pd))
+                check(self._L.sp_lnlike_inclinations_grad_stars(
+                    self._h, S, self._p(plan), self._p(stars), self._p(rta1), ntab, self._p(mean_ylm), self._p(cov_ylm),
+                    Pd, self._p(dmu), self._p(dsig), P, self._p(inc), self._p(lw), int(bool(normalized)),
+                    int(norm_order), float(zmax), self._p(lnl), self._p(dlnl), self._p(mix[0]), self._p(mix[1]),
+                    self._p(mix[2]), self._p(status), self._p(star_tangent), star_mask, self._p(dstar),
+                    self._p(dstarmix), self._p(ws), self._stream()))
+            return (lnl, dlnl) + mix + (status, dstar, dstarmix)
         if S > 0:
-            if int(plan.numel()) < int(self._L.sp_incl_plan_bytes(self._h, S, 1)):
-                raise ValueError("the plan does not hold %d stars" % S)
             ws = self._scratch(self._L.sp_lnlike_inclinations_grad_workspace_bytes(self._h, S, ntab, P, Pd))
             check(self._L.sp_lnlike_inclinations_grad(
                 self._h, S, self._p(plan), self._p(stars), self._p(rta1), ntab, self._p(mean_ylm), self._p(cov_ylm), Pd,

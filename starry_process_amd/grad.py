@@ -1132,6 +1132,29 @@ def _or_flags(status):
     return out
 
 
+# the per-star derivatives of EnsembleGradientInclinations(wrt=...), in the order of the device's row (slots 0-3 of
+# sp_lnlike_inclinations_grad_stars) and of ``star_grad``
+_WRT_INCL = ("p", "baseline_mean", "baseline_var", "log_var")
+
+
+def _check_wrt_inclinations(wrt):
+    """``wrt`` as a tuple of names the inclination grid serves (None stays None); ValueError otherwise.  No device
+    work."""
+    if wrt is None:
+        return None
+    wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+    for name in wrt:
+        if name == "i":
+            raise ValueError("wrt: 'i' is marginalised on the grid (its posterior is ``pinc``); "
+                             "EnsembleGradientConditional differentiates at known inclinations")
+        if name == "tau":
+            raise ValueError("wrt: 'tau': a time-variable process has no rank-(2 ydeg + 1) basis (EnsembleGradient "
+                             "differentiates the marginal branch with respect to it)")
+        if name not in _WRT_INCL:
+            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT_INCL)))
+    return wrt
+
+
 class EnsembleGradientInclinations(_EnsembleSweep):
     """The ensemble log-likelihood with every star's inclination marginalised EXACTLY on a grid, and its gradient:
 
@@ -1145,16 +1168,19 @@ class EnsembleGradientInclinations(_EnsembleSweep):
         eg = EnsembleGradientInclinations(t, flux, ferr=1e-3, p=periods, inc=np.linspace(0, 90, 100))   # data -> GPU, once
         lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10., params=("r", "a", "b", "c", "n"))
         eg.lnlike (S,), eg.per_star (S, Pd), eg.pinc (S, P), eg.lnlike_grid (S, P), eg.status (S,), eg.names
+        lnl, grad = eg(r=20., a=.4, b=.27, c=.1, n=10., wrt=("p", "baseline_mean", "baseline_var", "log_var"))
+        grad["p"] (S,), ..., eg.star_grad (S, 4)       # d lnL_s / d of star s's own period, baselines, noise factor
 
     t: (K,) or (S, K); flux (S, K); ferr: a scalar, (S,) or (S, K); p, baseline_mean, baseline_var: scalars or (S,); u:
-    (udeg,) or (S, udeg); inc in degrees.  The constructor uploads the data and plans it once (sp_incl_plan_data).  A
+    (udeg,) or (S, udeg); inc in degrees.  The constructor uploads the data and plans it once (sp_incl_plan_data, and
+    the plan's tangent along each star's period, sp_incl_plan_tangent).  A
     star the basis cannot take (SP_STAR_NO_BASIS in ``status``: partial phase coverage, fewer distinct phases than
     2 ydeg + 1, a variance <= 0) goes through the dense conditional sweep instead, replicated over the grid
     inclinations, and enters the same mixture.  ydeg <= 30.
 
     Not served: a time-variable process (``tau``), a full ``data_cov`` matrix or a matrix ``baseline_var`` (refused here;
-    ``EnsembleGradientConditional`` takes ``tau`` at known inclinations); derivatives with respect to per-star parameters
-    (p, baselines, noise) or the spread of radii dr; more than one light curve per star; a multi-stream form."""
+    ``EnsembleGradientConditional`` takes ``tau`` at known inclinations); derivatives with respect to the spread of radii
+    dr or to a star's limb darkening; more than one light curve per star; a multi-stream form."""
 
     _open = staticmethod(get_engine)
 
@@ -1189,6 +1215,7 @@ class EnsembleGradientInclinations(_EnsembleSweep):
         self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
         self._inc_rad, self._logw_dev = e.f64(inc * (np.pi / 180)), e.f64(self._logw)
         self._plan, pstat = e.incl_plan_data(self._t, self._flux, self._stars, self._diag)
+        self._ptan = e.incl_plan_tangent(self._t, self._flux, self._stars, self._plan, self._diag)
         self._dense = np.flatnonzero(pstat.cpu().numpy().astype(np.uint32) & SP_STAR_NO_BASIS)
         # a star of the dense route: its record once per grid inclination
         self._dense_stars = []
@@ -1196,16 +1223,18 @@ class EnsembleGradientInclinations(_EnsembleSweep):
             rep = np.repeat(stars[s:s + 1], inc.size)
             rep["inc"] = inc * (np.pi / 180)
             self._dense_stars.append(e.stars_to_device(rep))
-        self.lnlike = self.per_star = self.pinc = self.lnlike_grid = self.status = self.names = None
+        self.lnlike = self.per_star = self.pinc = self.lnlike_grid = self.status = self.names = self.star_grad = None
 
-    def _dense_star(self, k, dmu, dSig):
+    def _dense_star(self, k, dmu, dSig, star=False):
         """(lnlike_grid [P], lnmix, dlnmix [Pd], pinc [P], status) of the k-th star of the dense route, on the device:
-        the conditional sweep at the engine's moments on the star replicated over the grid, then the same mixture."""
+        the conditional sweep at the engine's moments on the star replicated over the grid, then the same mixture.
+        star: a sixth entry, the sweep's per-star row (p, i, baseline_mean, baseline_var, log_var) mixed with pinc, the
+        inclination's slot dropped: [4] in the order of ``_WRT_INCL``."""
         import torch
 
         e, s, P = self._e, int(self._dense[k]), self._inc.size
         rows = lambda x: None if x is None else x[s:s + 1].expand(P, -1).contiguous()          # noqa: E731
-        lnl, mubar, sigbar, _, status = e.lnlike_grad_conditional(
+        lnl, mubar, sigbar, sbar, status = e.lnlike_grad_conditional(
             rows(self._t), rows(self._flux), self._dense_stars[k], self._rta1, diag=rows(self._diag),
             temporal=self._temporal, normalized=self._normalized)
         ninf = torch.full_like(lnl, -np.inf)
@@ -1214,55 +1243,80 @@ class EnsembleGradientInclinations(_EnsembleSweep):
         live = a > -np.inf
         if not bool(live.any()):
             zero = torch.zeros_like(lnl)
-            return lnl, ninf[0], torch.zeros(dmu.shape[0], dtype=lnl.dtype, device=lnl.device), zero, status
+            out = (lnl, ninf[0], torch.zeros(dmu.shape[0], dtype=lnl.dtype, device=lnl.device), zero, status)
+            return out + (torch.zeros(4, dtype=lnl.dtype, device=lnl.device),) if star else out
         lnmix = torch.logsumexp(a, dim=0)
         pinc = torch.where(live, torch.exp(a - lnmix), torch.zeros_like(a))
         z1, z2 = torch.zeros_like(mubar), torch.zeros_like(sigbar)
         gmu = (pinc[:, None] * torch.where(live[:, None], mubar, z1)).sum(dim=0)
         gSig = (pinc[:, None, None] * torch.where(live[:, None, None], sigbar, z2)).sum(dim=0)
-        return lnl, lnmix, dmu @ gmu + (dSig * gSig).sum(dim=(1, 2)), pinc, status
+        out = (lnl, lnmix, dmu @ gmu + (dSig * gSig).sum(dim=(1, 2)), pinc, status)
+        if star:
+            sb = sbar[:, [0, 2, 3, 4]]
+            out += ((pinc[:, None] * torch.where(live[:, None], sb, torch.zeros_like(sb))).sum(dim=0),)
+        return out
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
-                 params=("r", "a", "b", "c", "n")):
+                 params=("r", "a", "b", "c", "n"), wrt=None):
         """(sum over the stars of finite value of lnL_s, in index order; {name: d / d name} over ``params``, any subset
         of r, a, b, c, n -- a sub-block has the bits of the matching columns of the full call).  Afterwards ``lnlike``
         [S], ``per_star`` [S, Pd] (d lnL_s / d params), ``pinc`` [S, P] (each star's inclination posterior on the grid),
         ``lnlike_grid`` [S, P], ``status`` [S] (the flags of the star's grid points or-ed; SP_STAR_NO_BASIS: the star took
-        the dense route) and ``names``."""
+        the dense route) and ``names``.
+
+        wrt: None, a name or a tuple of names out of ("p", "baseline_mean", "baseline_var", "log_var"): the dict then also
+        holds arrays [S], d lnL_s / d of star s's own period (the integer part of t / p is data), baseline mean, baseline
+        variance and the log of a common factor on its data variances (not on baseline_var) -- the mixture over the grid
+        of the conditional derivatives, sum_j pinc_sj d lnL_s(i_j) / d theta_s, from the same sweep and the same transfer.
+        ``star_grad`` [S, 4] then holds them in that fixed order, NaN in a slot that was not asked for (None after a call
+        without ``wrt``).  A grid entry at -inf contributes zero; a star whose whole grid is -inf gets zeros."""
         import torch
 
         names, _ = _check_conditional_params(params, ())
+        wrt = _check_wrt_inclinations(wrt)
+        mask = 0
+        for k in wrt or ():
+            mask |= 1 << _WRT_INCL.index(k)
         e = self._e
         r, a, b, c, n = float(r), float(a), float(b), float(c), float(n)
         mu, Sig, dmu, dSig = _moment_tangents(e, self._ukw, names, r, a, b, c, n)
         S, P, Pd = self.S, self._inc.size, len(names)
-        grid, _, lnmix, dlnmix, pinc, status = e.lnlike_inclinations_grad(
+        grid, _, lnmix, dlnmix, pinc, status, *star = e.lnlike_inclinations_grad(
             self._plan, self._stars, self._rta1, mu, Sig, dmu, dSig, self._inc_rad, logw=self._logw_dev,
-            normalized=self._normalized)
+            normalized=self._normalized, star_tangent=self._ptan if mask & 1 else None, star_mask=mask)
         stat = _or_flags(status)
         for k, s in enumerate(self._dense):
-            grid[s], lnmix[s], dlnmix[s], pinc[s], st = self._dense_star(k, dmu, dSig)
+            grid[s], lnmix[s], dlnmix[s], pinc[s], st, *sb = self._dense_star(k, dmu, dSig, star=bool(mask))
             stat[s] = _or_flags(st) | SP_STAR_NO_BASIS
-        # ONE transfer: [per-star values | per-star gradients | grid | posteriors | status]
+            if mask:
+                asked = torch.tensor([bool(mask >> q & 1) for q in range(4)], device=sb[0].device)
+                star[1][s] = torch.where(asked, sb[0], torch.full_like(sb[0], np.nan))
+        # ONE transfer: [per-star values | per-star gradients | grid | posteriors | status | per-star derivatives]
         host = torch.cat([lnmix, dlnmix.reshape(-1), grid.reshape(-1), pinc.reshape(-1),
-                          stat.to(torch.float64)]).cpu().numpy()
-        o = np.cumsum([0, S, S * Pd, S * P, S * P, S])
+                          stat.to(torch.float64)] + ([star[1].reshape(-1)] if mask else [])).cpu().numpy()
+        o = np.cumsum([0, S, S * Pd, S * P, S * P, S, 4 * S if mask else 0])
         self.lnlike, self.per_star = host[o[0]:o[1]].copy(), host[o[1]:o[2]].reshape(S, Pd).copy()
         self.lnlike_grid, self.pinc = host[o[2]:o[3]].reshape(S, P).copy(), host[o[3]:o[4]].reshape(S, P).copy()
         self.status, self.names = host[o[4]:o[5]].astype(np.uint32), names
+        self.star_grad = host[o[5]:o[6]].reshape(S, 4).copy() if mask else None
         total, g = 0.0, np.zeros(Pd)
         for s in range(S):          # (index order)
             if np.isfinite(self.lnlike[s]):
                 total += self.lnlike[s]
                 g += self.per_star[s]
-        return float(total), {k: float(v) for k, v in zip(names, g)}
+        grad = {k: float(v) for k, v in zip(names, g)}
+        for k in wrt or ():
+            grad[k] = self.star_grad[:, _WRT_INCL.index(k)].copy()
+        return float(total), grad
 
 
 def ensemble_gradient_inclinations(t, flux, ferr=1.0e-3, p=1.0, inc=np.linspace(0, 90, 100), r=defaults["r"],
                                    a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"],
-                                   params=("r", "a", "b", "c", "n"), **kwargs):
-    """One-shot form of ``EnsembleGradientInclinations``: (sum_s lnL_s, {name: float}, lnL [S])."""
+                                   params=("r", "a", "b", "c", "n"), wrt=None, **kwargs):
+    """One-shot form of ``EnsembleGradientInclinations``: (sum_s lnL_s, {name: float, and the names of ``wrt``: arrays
+    [S]}, lnL [S])."""
     _check_conditional_params(params, ())          # (before anything goes to the device)
+    wrt = _check_wrt_inclinations(wrt)
     eg = EnsembleGradientInclinations(t, flux, ferr=ferr, p=p, inc=inc, **kwargs)
-    total, grad = eg(r=r, a=a, b=b, c=c, n=n, params=params)
+    total, grad = eg(r=r, a=a, b=b, c=c, n=n, params=params, wrt=wrt)
     return total, grad, eg.lnlike

@@ -10,11 +10,19 @@ inputs:
              (star, inclination) it is compared with grad / P
 
 at 64 stars, K = 1000, ydeg 15 and K = 3000, ydeg 20, P = 100 inclinations, Pd = 5 directions (r, a, b, c, n), a
-normalised process.  Every shape runs in a child process of its own under its own time limit.  Per shape one JSON line:
+normalised process.  With --wrt (names out of p, baseline_mean, baseline_var, log_var, separated by commas) three more:
+
+  grad_stars    the same call with the per-star slots of --wrt (sp_lnlike_inclinations_grad_stars): what each star's own
+                derivatives cost over the shared gradient
+  facade_stars  EnsembleGradientInclinations.__call__(wrt=...)
+  tangent       Engine.incl_plan_tangent, the plan's derivative along the periods: once per data set, not per call
+
+and the lines go to profiles/incl_grad_stars.txt.  Every shape runs in a child process of its own under its own time limit.  Per shape one JSON line:
 milliseconds of each route (3 warm-up calls, then ROUNDS interleaved rounds of REPS timed calls; the median of the
 rounds' medians and their lowest and highest) and the ratios.  The lines go to --out (profiles/incl_grad.txt).
 
     python tools/bench_incl_grad.py [--reps 10] [--rounds 5] [--timeout 300] [--out profiles/incl_grad.txt]
+                                    [--wrt p,baseline_mean,baseline_var,log_var]
 """
 import argparse
 import json
@@ -46,7 +54,7 @@ def timed(fn, reps):
     return float(np.median(ms))
 
 
-def shape(ydeg, S, K, P, reps, rounds):
+def shape(ydeg, S, K, P, reps, rounds, wrt=()):
     import torch
 
     from starry_process_amd._lib import check
@@ -86,6 +94,23 @@ def shape(ydeg, S, K, P, reps, rounds):
         return egc(**HP)
 
     routes = dict(grad=grad, value=value, facade=facade, dense=dense)
+    if wrt:
+        from starry_process_amd.grad import _WRT_INCL
+
+        mask = sum(1 << _WRT_INCL.index(k) for k in set(wrt))
+
+        def grad_stars():
+            return e.lnlike_inclinations_grad(eg._plan, eg._stars, eg._rta1, mu, Sig, dmu, dSig, eg._inc_rad,
+                                              logw=eg._logw_dev, star_tangent=eg._ptan if mask & 1 else None,
+                                              star_mask=mask)
+
+        def facade_stars():
+            return eg(wrt=wrt, **HP)
+
+        def tangent():
+            return e.incl_plan_tangent(eg._t, eg._flux, eg._stars, eg._plan, eg._diag)
+
+        routes.update(grad_stars=grad_stars, facade_stars=facade_stars, tangent=tangent)
     for _ in range(3):
         for fn in routes.values():
             fn()
@@ -100,6 +125,12 @@ def shape(ydeg, S, K, P, reps, rounds):
         return dict(median=round(float(np.median(x)), 3), low=round(min(x), 3), high=round(max(x), 3))
 
     med = {k: float(np.median(v)) for k, v in got.items()}
+    extra = {}
+    if wrt:
+        extra = dict(wrt=list(wrt), grad_stars_ms=stats(got["grad_stars"]), facade_stars_ms=stats(got["facade_stars"]),
+                     tangent_ms=stats(got["tangent"]), grad_stars_over_grad=round(med["grad_stars"] / med["grad"], 2),
+                     facade_stars_over_facade=round(med["facade_stars"] / med["facade"], 2),
+                     grad_stars_us_per_star_inclination=round(1e3 * med["grad_stars"] / (S * P), 3))
     print(json.dumps(dict(
         what="incl_grad", ydeg=ydeg, n=n, S=S, K=K, P=P, Pd=len(names), reps=reps, rounds=rounds,
         grad_ms=stats(got["grad"]), value_ms=stats(got["value"]), facade_ms=stats(got["facade"]),
@@ -107,7 +138,7 @@ def shape(ydeg, S, K, P, reps, rounds):
         grad_us_per_star_inclination=round(1e3 * med["grad"] / (S * P), 3),
         dense_us_per_star_inclination=round(1e3 * med["dense"] / S, 3),
         dense_over_grad_per_star_inclination=round((med["dense"] / S) / (med["grad"] / (S * P)), 1),
-        max_abs_value_difference=diff)), flush=True)
+        max_abs_value_difference=diff, **extra)), flush=True)
 
 
 def main():
@@ -115,25 +146,32 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per shape")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "incl_grad.txt"))
+    ap.add_argument("--out", default=None, help="profiles/incl_grad.txt, or profiles/incl_grad_stars.txt with --wrt")
+    ap.add_argument("--wrt", default="", help="per-star names, separated by commas: also time the call with them")
     ap.add_argument("--shape", type=int, default=None, help="(internal) run this one shape in this process")
     a = ap.parse_args()
+    wrt = tuple(k for k in a.wrt.split(",") if k)
+    if wrt:
+        from starry_process_amd.grad import _check_wrt_inclinations
+
+        _check_wrt_inclinations(wrt)
+    out = a.out or os.path.join(ROOT, "profiles", "incl_grad_stars.txt" if wrt else "incl_grad.txt")
     if a.shape is not None:
         ydeg, S, K, P = SHAPES[a.shape]
-        shape(ydeg, S, K, P, a.reps, a.rounds)
+        shape(ydeg, S, K, P, a.reps, a.rounds, wrt)
         return 0
     lines = []
     for k in range(len(SHAPES)):
         # a fresh child per shape under its own time limit; nothing more is started after one that fails
         cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--shape", str(k),
-               "--reps", str(a.reps), "--rounds", str(a.rounds)]
+               "--reps", str(a.reps), "--rounds", str(a.rounds)] + (["--wrt", ",".join(wrt)] if wrt else [])
         r = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
         sys.stdout.write(r.stdout)
         if r.returncode != 0:
             print("shape %d: exit status %d; stopping" % (k, r.returncode), file=sys.stderr)
             return r.returncode
         lines += [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
-    with open(a.out, "w") as fh:
+    with open(out, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return 0
 
