@@ -663,6 +663,42 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
                     double *lnlike_dev /* [S] */, uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev,
                     size_t workspace_bytes, void *stream);
 
+/* ---- Linear regressors marginalised out of the likelihood of an ensemble, either branch -----------------------------
+ * flux_s = process + U_s w + noise with w ~ N(0, diag lambda_s): segment offsets, instrumental trends, systematics
+ * vectors (Luger et al. 2017, Eq. 4; the reference's matrix baseline_var = U Lambda U^T, never formed here).  C_s, r and
+ * the branches are sp_loo_ensemble's; basis_dev [S, q, K]: regressor j of star s along row j (no mean is subtracted
+ * from it); basis_var_dev [S, q]: the prior variances lambda >= 0, finite (0 switches a regressor off exactly; a
+ * negative one gives the star NaN).  With C = L L^T, y = L^-1 r, W = L^-1 U and D = diag(sqrt(lambda)):
+ *   G = I + D W^T W D = L_G L_G^T,   v = L_G^-1 D W^T y
+ *   lnlike_dev  [S]:       -1/2 (y^T y - v^T v) - sum log L_ii - sum log (L_G)_jj - K/2 log 2 pi
+ *   lnlike0_dev [S]:       -1/2 y^T y - sum log L_ii - K/2 log 2 pi, the same star without regressors
+ *   wmean_dev   [S, q]:    D L_G^-T v, the posterior mean of the weights
+ *   wcov_dev    [S, q, q]: D G^-1 D, their posterior covariance, exactly symmetric (may be NULL: not computed, the
+ *                          other outputs keep their bits)
+ * r and the regressors ride through the blocked factorisation as 1 + q rows below C; one pass along those rows gives
+ * their Gram matrix (from K = 1000 on a star's columns are split over workgroups of 512 columns, the parts added in
+ * their order) and one wavefront per star finishes the q x q system.  Sums run in a fixed order without atomics: the
+ * same bits run after run, alone or among other stars, at any position, in any grouping.  status_dev (may be NULL) [S].
+ *   covariance that does not factor: NaN in every output, SP_STAR_NOT_PD;  ragged star (0 < nobs < K): NaN,
+ *   SP_STAR_NAN;  normalised star with z > zmax: lnlike = lnlike0 = -inf, SP_STAR_ZMAX, the weights still computed;
+ *   a NaN reaching G, v or a likelihood: NaN in every output, SP_STAR_NAN.
+ * No star affects another.  The stars are worked through in groups of as many as workspace_bytes holds
+ * (sp_lnlike_linear_workspace_bytes(h, S', K, q, covpts, conditional) for S' stars resident at once: the likelihood's
+ * workspace with a system of roundup(K + q + 3, 64) rows and (q + 1)(q + 2) / 2 + 1 doubles per 512 columns and star;
+ * the conditional branch adds two roundup(K, 64) x N matrices and the raw covariance per star; 0 for a null handle,
+ * S' < 0, K < 2 or q outside 1 .. 32).  One light curve per star.  A workspace too small for one star, a null required
+ * pointer, K < 2 or q outside 1 .. 32: SP_ERR_INVALID, nothing launched.  A host-only handle: SP_ERR_NO_DEVICE, before
+ * everything else.  S = 0: SP_OK, nothing touched.  All launches go to `stream`; nothing is synchronised.            */
+size_t sp_lnlike_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts, int conditional);
+int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const double *flux_dev /* [S, K] */,
+                     const double *diag_dev, const sp_star *stars_dev, const double *basis_dev /* [S, q, K] */,
+                     const double *basis_var_dev /* [S, q] */, int conditional, int covpts, const double *tab_dev,
+                     const double *meanvar_dev, const double *rta1_dev, int temporal, int normalized, int norm_order,
+                     double zmax, double *lnlike_dev /* [S] */, double *lnlike0_dev /* [S] */,
+                     double *wmean_dev /* [S, q] */, double *wcov_dev /* NULL or [S, q, q] */,
+                     uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
+                     void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

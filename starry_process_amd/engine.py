@@ -1538,6 +1538,64 @@ class Engine(object):
                 self._p(lnlike), self._p(status), self._p(workspace), int(workspace.numel()), self._stream()))
         return rows, lpd, cov, lnlike, status
 
+    def lnlike_linear_workspace(self, S, K, q, covpts=300, conditional=False):
+        """Device scratch that holds ``S`` stars of ``lnlike_linear`` at once (sp_lnlike_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_lnlike_linear_workspace_bytes(self._h, int(S), int(K), int(q), int(covpts),
+                                                                      int(bool(conditional))))
+
+    def lnlike_linear(self, t, flux, stars, basis, basis_var, diag=None, conditional=False, covpts=300, tab=None,
+                      meanvar=None, rta1=None, temporal=None, normalized=True, norm_order=20, zmax=0.023,
+                      return_cov=True, workspace=None, max_workspace_bytes=None):
+        """The likelihood of S light curves with q linear regressors per star marginalised out (sp_lnlike_linear):
+        t, flux [S, K]; stars: host sp_star records or their device copy; basis [S, q, K]: regressor j of star s along
+        row j; basis_var [S, q]: the prior variances of the weights, >= 0; diag [S, K] per-cadence variances or None.
+        Marginal branch: tab, meanvar from ``kernel_table(rta1, covpts)``; conditional branch: rta1 and the moments
+        set on this engine.  Returns (lnlike [S], lnlike0 [S], w_mean [S, q], w_cov [S, q, q] or None, status [S]) on
+        the device: the likelihood with and without the regressors and the posterior of their weights.  A star whose
+        covariance does not factor, or a ragged one, holds NaN; a normalised star with z > zmax has lnlike = lnlike0 =
+        -inf and finite weights.  workspace: a byte tensor (``lnlike_linear_workspace``); ``max_workspace_bytes``
+        caps the scratch allocated here instead.  A workspace that holds fewer than S stars makes the call work
+        through them in groups, with the same bits."""
+        torch = _torch()
+        t, flux, basis, basis_var = self.f64(t), self.f64(flux), self.f64(basis), self.f64(basis_var)
+        if flux.dim() != 2 or t.shape != flux.shape:
+            raise ValueError("t and flux must both be (S, K)")
+        S, K = flux.shape
+        if K < 2:
+            raise ValueError("the likelihood with regressors needs at least two cadences")
+        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
+            raise ValueError("`basis` must be (S, q, K)")
+        q = int(basis.shape[1])
+        if not 1 <= q <= 32:
+            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
+        if tuple(basis_var.shape) != (S, q):
+            raise ValueError("`basis_var` must be (S, q)")
+        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        rta1 = None if rta1 is None else self.f64(rta1)
+        conditional = int(bool(conditional))
+        lnlike, lnlike0, wmean = self.empty(S), self.empty(S), self.empty(S, q)
+        wcov = self.empty(S, q, q) if return_cov else None
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S > 0:
+            if workspace is None:
+                need = int(self._L.sp_lnlike_linear_workspace_bytes(self._h, S, K, q, int(covpts), conditional))
+                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
+                    one = int(self._L.sp_lnlike_linear_workspace_bytes(self._h, 1, K, q, int(covpts), conditional))
+                    if int(max_workspace_bytes) < one:
+                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
+                                         % (int(max_workspace_bytes), one))
+                    need = int(max_workspace_bytes)
+                workspace = self._grad_ws = self._scratch(need)
+            check(self._L.sp_lnlike_linear(
+                self._h, S, K, q, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(basis),
+                self._p(basis_var), conditional, int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
+                TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(lnlike),
+                self._p(lnlike0), self._p(wmean), self._p(wcov), self._p(status), self._p(workspace),
+                int(workspace.numel()), self._stream()))
+        return lnlike, lnlike0, wmean, wcov, status
+
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 

@@ -1,0 +1,68 @@
+"""Host builders of regressor matrices for ``StarryProcess.log_likelihood_linear`` and
+``log_likelihood_linear_ensemble``: per-segment offsets (Kepler quarters, TESS sectors) and slow per-segment trends.
+Each returns a ``(K, q)`` float64 array, one regressor per column; ``stack_bases`` puts them side by side."""
+import numpy as np
+
+__all__ = ["offset_basis", "polynomial_basis", "stack_bases"]
+
+
+def _segment_edges(edges, K):
+    """``edges`` as an int64 array 0 = e_0 < e_1 < ... < e_n = K (None: one segment)."""
+    if edges is None:
+        return np.array([0, K], dtype=np.int64)
+    raw = np.asarray(edges)
+    if raw.ndim != 1 or raw.size < 2 or not np.all(np.isfinite(raw)) or not np.all(raw == np.floor(raw)):
+        raise ValueError("`edges` must be a 1-D array of at least two integer segment edges")
+    ed = raw.astype(np.int64)
+    if ed[0] != 0 or ed[-1] != K or np.any(np.diff(ed) < 1):
+        raise ValueError("`edges` must run 0 = e_0 < e_1 < ... < e_n = K = %d, not %s" % (K, ed.tolist()))
+    return ed
+
+
+def offset_basis(K, edges):
+    """One indicator column per segment: column j is 1 on the cadences edges[j] .. edges[j + 1] - 1 and 0 elsewhere.
+    ``edges``: 0 = e_0 < e_1 < ... < e_n = K.  Returns (K, n)."""
+    K = int(K)
+    if K < 1:
+        raise ValueError("`K` must be at least 1")
+    ed = _segment_edges(edges, K)
+    U = np.zeros((K, ed.size - 1))
+    for j in range(ed.size - 1):
+        U[ed[j]:ed[j + 1], j] = 1.0
+    return U
+
+
+def polynomial_basis(t, degree, edges=None):
+    """Legendre columns P_1 .. P_degree in each segment's own time, rescaled to [-1, 1] over the segment
+    (x = 2 (t - t_first) / (t_last - t_first) - 1), zero outside the segment.  No constant column: the offsets are
+    ``offset_basis``'s.  A segment of one cadence, or of constant time, gets zero columns.  ``edges`` as
+    ``offset_basis`` (None: one segment).  Returns (K, n degree), the columns of segment 0 first."""
+    t = np.asarray(t, dtype=np.float64)
+    degree = int(degree)
+    if t.ndim != 1 or t.size < 1 or not np.all(np.isfinite(t)):
+        raise ValueError("`t` must be a finite 1-D array")
+    if degree < 1:
+        raise ValueError("`degree` must be at least 1")
+    K = t.size
+    ed = _segment_edges(edges, K)
+    n = ed.size - 1
+    U = np.zeros((K, n * degree))
+    for j in range(n):
+        ts = t[ed[j]:ed[j + 1]]
+        span = ts.max() - ts.min()
+        if not span > 0:
+            continue
+        x = 2.0 * (ts - ts.min()) / span - 1.0
+        V = np.polynomial.legendre.legvander(x, degree)
+        U[ed[j]:ed[j + 1], j * degree:(j + 1) * degree] = V[:, 1:]
+    return U
+
+
+def stack_bases(*bases):
+    """The given (K, q_i) bases side by side: (K, sum q_i)."""
+    if not bases:
+        raise ValueError("at least one basis is needed")
+    mats = [np.asarray(b, dtype=np.float64) for b in bases]
+    if any(m.ndim != 2 for m in mats) or len({m.shape[0] for m in mats}) != 1:
+        raise ValueError("every basis must be (K, q_i) with the same K")
+    return np.ascontiguousarray(np.concatenate(mats, axis=1))

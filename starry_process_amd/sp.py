@@ -858,6 +858,120 @@ class StarryProcess(object):
                                 baseline_mean=baseline_mean, baseline_var=baseline_var, return_cov=return_cov)
         return {k: (v if k == "edges" else v[0]) for k, v in out.items()}
 
+    # -- linear regressors marginalised out of the likelihood (sp_lnlike_linear) ------------------------------
+    def log_likelihood_linear_ensemble(self, t, flux, data_cov, basis, basis_var, i=None, p=None, u=None,
+                                       baseline_mean=0.0, baseline_var=0.0, return_cov=True,
+                                       max_workspace_bytes=None):
+        """The log likelihood of S light curves with linear regressors marginalised out, in one device call:
+        flux = process + U w + noise with w ~ N(0, diag(basis_var)) -- segment offsets, instrumental trends,
+        systematics vectors (``starry_process_amd.linear`` builds the usual ones).  It is the reference's
+        ``log_likelihood(..., baseline_var=b + U diag(basis_var) U^T)`` (Luger et al. 2017, Eq. 4) without the K x K
+        matrix, and it returns the posterior of the weights as well: the detrending itself.  With C = L L^T the
+        covariance ``log_likelihood_ensemble`` factors, r its residual, y = L^-1 r, W = L^-1 U, D = diag(sqrt(basis_var)):
+
+            G = I + D W^T W D = L_G L_G^T        v = L_G^-1 D W^T y
+            lnlike = -1/2 (y^T y - v^T v) - sum log L_ii - sum log (L_G)_jj - K/2 log 2 pi
+            w_mean = D L_G^-T v                  w_cov = D G^-1 D
+
+        basis: (K, q) shared or (S, K, q), 1 <= q <= 32, finite; basis_var: scalar, (q,) or (S, q), finite and >= 0
+        (0 switches a regressor off exactly).  The other arguments, the branch of the instance and the refusals are
+        ``loo_ensemble``'s.
+
+        Returns a dict of NumPy arrays: ``lnlike`` and ``lnlike0``, the likelihood with and without the regressors
+        (S,) (-inf where ``log_likelihood_ensemble`` gives -inf); ``w_mean`` (S, q); ``w_cov`` (S, q, q), exactly
+        symmetric (absent with ``return_cov=False``); ``trend`` (S, K) = U w_mean; ``status`` (S,).  A star whose
+        covariance does not factor has NaN in its outputs.  ``max_workspace_bytes`` caps the device scratch: the stars
+        are then worked through in groups, with the same bits."""
+        try:
+            flux = np.asarray(flux, dtype=np.float64)
+            tt = np.asarray(t, dtype=np.float64)
+        except (ValueError, TypeError):
+            raise ValueError("log_likelihood_linear_ensemble does not serve ragged input (lists of light curves of "
+                             "different lengths): pass `t` and `flux` as (S, K) arrays")
+        if flux.ndim != 2:
+            raise ValueError("`flux` must be (S, K)")
+        S, K = flux.shape
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
+            raise NotImplementedError("log_likelihood_linear_ensemble does not serve a full-matrix `data_cov`: pass a "
+                                      "scalar, (S,) or (S, K) variances")
+        if np.ndim(baseline_var) >= 2:
+            raise NotImplementedError("log_likelihood_linear_ensemble does not serve a matrix `baseline_var`: pass a "
+                                      "scalar or (S,), and the structured part as `basis`, `basis_var`")
+        if K < 2:
+            raise ValueError("the likelihood with regressors needs at least two cadences")
+        U = np.asarray(basis, dtype=np.float64)
+        if U.ndim == 2 and U.shape[0] == K:
+            U = np.broadcast_to(U, (S,) + U.shape)
+        if U.ndim != 3 or U.shape[0] != S or U.shape[1] != K:
+            raise ValueError("`basis` must be (K, q) or (S, K, q) with S = %d, K = %d, not %s"
+                             % (S, K, np.shape(basis)))
+        q = U.shape[2]
+        if not 1 <= q <= 32:
+            raise ValueError("1 to 32 regressors are served, not %d" % q)
+        if not np.all(np.isfinite(U)):
+            raise ValueError("`basis` must be finite")
+        lam = np.asarray(basis_var, dtype=np.float64)
+        if lam.ndim == 0 or lam.shape == (q,) or lam.shape == (S, q):
+            lam = np.ascontiguousarray(np.broadcast_to(lam, (S, q)))
+        else:
+            raise ValueError("`basis_var` must be a scalar, (q,) or (S, q) with S = %d, q = %d, not %s"
+                             % (S, q, lam.shape))
+        if not np.all(np.isfinite(lam)) or np.any(lam < 0):
+            raise ValueError("`basis_var` must be finite and >= 0")
+        Ut = np.ascontiguousarray(np.swapaxes(U, 1, 2))          # [S, q, K]: a regressor along a row
+        e, f = self._engine, self._flux
+        t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
+        f._bind()
+        rta1 = e.f64(e.rTA1L(utab))
+        tab = mv = None
+        if self._marginalize_over_inclination:
+            tab, mv = e.kernel_table(rta1, self._covpts)
+        Ud = e.f64(Ut)
+        lnlike, lnlike0, wmean, wcov, status = e.lnlike_linear(
+            t, flux, stars, Ud, lam, diag=diag, conditional=not self._marginalize_over_inclination,
+            covpts=self._covpts, tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
+            norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
+            max_workspace_bytes=max_workspace_bytes)
+        # (U w_mean on the device; a weight switched off contributes an exact zero)
+        trend = (Ud * wmean[:, :, None]).sum(dim=1)
+        out = {"lnlike": _neg_inf_if_nan(lnlike.cpu().numpy()), "lnlike0": _neg_inf_if_nan(lnlike0.cpu().numpy()),
+               "w_mean": wmean.cpu().numpy()}
+        if return_cov:
+            out["w_cov"] = wcov.cpu().numpy()
+        out["trend"] = trend.cpu().numpy()
+        out["status"] = status.cpu().numpy()
+        return out
+
+    def log_likelihood_linear(self, t, flux, data_cov, basis, basis_var, i=defaults["i"], p=defaults["p"],
+                              u=defaults["u"][: defaults["udeg"]], baseline_mean=defaults["baseline_mean"],
+                              baseline_var=defaults["baseline_var"], return_cov=True):
+        """``log_likelihood_linear_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances;
+        basis (K, q); basis_var a scalar or (q,).  The same dict without the leading axis."""
+        dc = np.asarray(data_cov, dtype=np.float64)
+        if dc.ndim >= 2:
+            raise NotImplementedError("log_likelihood_linear does not serve a full-matrix `data_cov`: pass a scalar "
+                                      "or (K,) variances")
+        if np.ndim(baseline_var) >= 1:
+            raise NotImplementedError("log_likelihood_linear does not serve a matrix `baseline_var`: pass a scalar, "
+                                      "and the structured part as `basis`, `basis_var`")
+        try:
+            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
+        except (ValueError, TypeError):
+            raise ValueError("`flux` must be one light curve of K cadences")
+        if dc.ndim == 1:
+            dc = dc.reshape(1, -1)
+        U = np.asarray(basis, dtype=np.float64)
+        if U.ndim != 2:
+            raise ValueError("`basis` must be (K, q)")
+        lam = np.asarray(basis_var, dtype=np.float64)
+        if lam.ndim > 1:
+            raise ValueError("`basis_var` must be a scalar or (q,)")
+        out = self.log_likelihood_linear_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, U[None], lam,
+                                                  i=i, p=p, u=u, baseline_mean=baseline_mean,
+                                                  baseline_var=baseline_var, return_cov=return_cov)
+        return {k: v[0] for k, v in out.items()}
+
     # -- posterior of the surface map (sp.py:518-641) -------------------------------------
     # W = Sigma_y^-1 + A^T C^-1 A, ymu = W^-1 (Sigma_y^-1 mu_y + A^T C^-1 (flux - baseline_mean)), ycov = W^-1,
     # with A the design matrix at (t, i, p, u) whatever marginalize_over_inclination says (sp.py:620), as in
