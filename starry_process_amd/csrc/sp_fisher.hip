@@ -461,37 +461,26 @@ int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, c
                        double zmax, double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
                        size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !t_dev || !stars_dev || !tab_dev || !meanvar_dev || !dyp_dev || !dmean_dev || !fisher_dev || !workspace_dev ||
-      S < 0 || K < 2 || P < 1 || P > FP_MAX || covpts < 1 || norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+  if (!h || !t_dev || !stars_dev || !dyp_dev || !dmean_dev || !fisher_dev || !workspace_dev || S < 0 || K < 2 || P < 1 ||
+      P > FP_MAX || covpts < 1 || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
   // (the tangent kernel's LDS: P + 1 tables and the tile's vectors)
   if (sizeof(double) * ((size_t)(P + 1) * (covpts + 4) + 6 * 64 + 2 * FP_MAX * 64) > 60 * 1024) return SP_ERR_INVALID;
   // (tab_dev is the handle's last kernel table: its lag grid and its number of tables, which is dyp's and dmean's too)
-  if (h->xp_covpts != covpts || h->tab_ntab < 1) return SP_ERR_STATE;
+  if (const int rc = sp_branch_check(h, 0, nullptr, tab_dev, meanvar_dev, covpts)) return rc;
+  if (h->tab_ntab < 1) return SP_ERR_STATE;
   const int ntab = h->tab_ntab;
   if (S == 0) return SP_OK;
-  // the largest group the workspace holds (the layout grows with the number of stars)
-  if (fisher_layout(h, 1, K, P, covpts).total > workspace_bytes) return SP_ERR_INVALID;
-  int lo = 1, hi = S < 65535 ? S : 65535;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (fisher_layout(h, mid, K, P, covpts).total <= workspace_bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  const int group = lo;
-  SpProblem Q;   // (no data: M = 0, flux null)
-  Q.S = S, Q.K = K, Q.t = t_dev, Q.diag = diag_dev, Q.stars = stars_dev;
-  Q.covpts = covpts, Q.tab = tab_dev, Q.meanvar = meanvar_dev, Q.xp = h->d_xp;
-  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = (hipStream_t)stream;
-  for (int s0 = 0; s0 < S; s0 += group) {
-    const int n = S - s0 < group ? S - s0 : group;
-    const int rc = fisher_group(h, Q.slice(s0, s0 + n), P, ntab, dyp_dev, dmean_dev, fisher_dev + (size_t)s0 * P * P,
-                                dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr,
-                                status_dev ? status_dev + s0 : nullptr, workspace_dev);
-    if (rc) return rc;
-  }
-  return SP_OK;
+  const int group = sp_star_group(S, workspace_bytes, [&](int n) { return fisher_layout(h, n, K, P, covpts).total; });
+  if (!group) return SP_ERR_INVALID;
+  // (no data: M = 0, flux null)
+  const SpProblem Q = sp_make_problem(h, 0, S, K, 0, t_dev, nullptr, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
+                                      temporal, normalized, norm_order, zmax, stream);
+  return sp_for_star_groups(S, group, [&](int s0, int n) {
+    return fisher_group(h, Q.slice(s0, s0 + n), P, ntab, dyp_dev, dmean_dev, fisher_dev + (size_t)s0 * P * P,
+                        dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr, status_dev ? status_dev + s0 : nullptr,
+                        workspace_dev);
+  });
 }
 
 }  // extern "C"

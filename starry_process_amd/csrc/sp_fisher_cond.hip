@@ -294,35 +294,24 @@ int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask, con
                           int temporal, int normalized, int norm_order, double zmax, double *fisher_dev, double *dcov_dev,
                           uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !t_dev || !stars_dev || !rta1_dev || !fisher_dev || !workspace_dev || S < 0 || K < 2 || Ph < 0 || Ph > 5 ||
+  if (!h || !t_dev || !stars_dev || !fisher_dev || !workspace_dev || S < 0 || K < 2 || Ph < 0 || Ph > 5 ||
       (star_mask & ~3) || (Ph > 0 && (!dmu_dev || !dsig_dev)) || norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+      !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
   const int P = Ph + (star_mask & 1) + ((star_mask >> 1) & 1);
   if (P < 1 || P > SP_FISHER_PMAX) return SP_ERR_INVALID;
-  if (!h->have_moments) return SP_ERR_STATE;
+  if (const int rc = sp_branch_check(h, 1, rta1_dev, nullptr, nullptr, 0)) return rc;
   if (S == 0) return SP_OK;
-  // the largest group the workspace holds (the layout grows with the number of stars)
-  if (fisher_cond_layout(h, 1, K, P).total > workspace_bytes) return SP_ERR_INVALID;
-  int lo = 1, hi = S < 65535 ? S : 65535;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (fisher_cond_layout(h, mid, K, P).total <= workspace_bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  const int group = lo;
-  SpProblem Q;   // (no data: M = 0, flux null)
-  Q.S = S, Q.K = K, Q.t = t_dev, Q.diag = diag_dev, Q.stars = stars_dev;
-  Q.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
-  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = (hipStream_t)stream;
-  for (int s0 = 0; s0 < S; s0 += group) {
-    const int n = S - s0 < group ? S - s0 : group;
-    const int rc = fisher_cond_group(h, Q.slice(s0, s0 + n), Ph, star_mask, rta1_dev, dmu_dev, dsig_dev,
-                                     fisher_dev + (size_t)s0 * P * P, dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr,
-                                     status_dev ? status_dev + s0 : nullptr, workspace_dev);
-    if (rc) return rc;
-  }
-  return SP_OK;
+  const int group = sp_star_group(S, workspace_bytes, [&](int n) { return fisher_cond_layout(h, n, K, P).total; });
+  if (!group) return SP_ERR_INVALID;
+  // (no data: M = 0, flux null)
+  const SpProblem Q = sp_make_problem(h, 1, S, K, 0, t_dev, nullptr, diag_dev, stars_dev, 0, nullptr, nullptr, temporal,
+                                      normalized, norm_order, zmax, stream);
+  return sp_for_star_groups(S, group, [&](int s0, int n) {
+    return fisher_cond_group(h, Q.slice(s0, s0 + n), Ph, star_mask, rta1_dev, dmu_dev, dsig_dev,
+                             fisher_dev + (size_t)s0 * P * P, dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr,
+                             status_dev ? status_dev + s0 : nullptr, workspace_dev);
+  });
 }
 
 }  // extern "C"

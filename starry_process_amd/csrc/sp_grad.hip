@@ -528,11 +528,10 @@ int grad_marginal(sp_handle *h, const SpProblem &P, void *workspace_dev, double 
                   double *meanbar_dev, uint32_t *status_dev, double *starbar_dev) {
   const int S = P.S, K = P.K, M = P.M;
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !P.t || !P.flux || !P.stars || !P.tab || !P.meanvar || !workspace_dev || !lnlike_dev ||
-      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || M < 1 || P.covpts < 1 || P.order < 0 ||
-      P.order > SP_NORM_MAXORDER)
+  if (!h || !P.t || !P.flux || !P.stars || !workspace_dev || !lnlike_dev || !ybar_dev || !meanbar_dev || S < 0 || K < 2 ||
+      M < 1 || P.order < 0 || P.order > SP_NORM_MAXORDER)
     return SP_ERR_INVALID;
-  if (h->xp_covpts != P.covpts) return SP_ERR_STATE;
+  if (const int rc = sp_branch_check(h, 0, nullptr, P.tab, P.meanvar, P.covpts)) return rc;
   if (S == 0) return SP_OK;
   const GradLayout G = grad_layout(h, S, K, M, P.covpts);
   char *base = static_cast<char *>(workspace_dev);
@@ -625,10 +624,8 @@ int sp_lnlike_grad_marginal_multi(sp_handle *h, int S, int K, int M, const doubl
                                   const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
                                   void *workspace_dev, double *lnlike_dev, double *ybar_dev, double *meanbar_dev,
                                   uint32_t *status_dev, void *stream) {
-  SpProblem P;
-  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
-  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h ? h->d_xp : nullptr;
-  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  const SpProblem P = sp_make_problem(h, 0, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
+                                      temporal, normalized, norm_order, zmax, stream);
   return grad_marginal(h, P, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, nullptr);
 }
 
@@ -639,10 +636,8 @@ int sp_lnlike_grad_marginal_stars(sp_handle *h, int S, int K, int M, const doubl
                                   uint32_t *status_dev, double *starbar_dev, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!starbar_dev) return SP_ERR_INVALID;
-  SpProblem P;
-  P.S = S, P.K = K, P.M = M, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
-  P.covpts = covpts, P.tab = tab_dev, P.meanvar = meanvar_dev, P.xp = h ? h->d_xp : nullptr;
-  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  const SpProblem P = sp_make_problem(h, 0, S, K, M, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
+                                      temporal, normalized, norm_order, zmax, stream);
   return grad_marginal(h, P, workspace_dev, lnlike_dev, ybar_dev, meanbar_dev, status_dev, starbar_dev);
 }
 

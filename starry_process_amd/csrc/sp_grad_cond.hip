@@ -432,11 +432,10 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
                                double *mubar_dev, double *sigbar_dev, double *starbar_dev, uint32_t *status_dev,
                                void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !t_dev || !flux_dev || !stars_dev || !rta1_dev || !workspace_dev || !lnlike_dev || !mubar_dev ||
-      !sigbar_dev || !starbar_dev || S < 0 || K < 2 || norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+  if (!h || !t_dev || !flux_dev || !stars_dev || !workspace_dev || !lnlike_dev || !mubar_dev || !sigbar_dev ||
+      !starbar_dev || S < 0 || K < 2 || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
-  if (!h->have_moments) return SP_ERR_STATE;
+  if (const int rc = sp_branch_check(h, 1, rta1_dev, nullptr, nullptr, 0)) return rc;
   if (S == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   const int Kr = sp_roundup(K, SP_NB), N = h->N, ntr = Kr / SP_NB, ntri = ntr * (ntr + 1) / 2;
@@ -445,10 +444,8 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   char *base = static_cast<char *>(workspace_dev);
   const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
   double *theta = V.theta(), *cs = V.cs(), *vrow = V.vrow();
-  SpProblem P;
-  P.S = S, P.K = K, P.M = 1, P.t = t_dev, P.flux = flux_dev, P.diag = diag_dev, P.stars = stars_dev;
-  P.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
-  P.temporal = temporal, P.normalized = normalized, P.order = norm_order, P.zmax = zmax, P.st = st;
+  const SpProblem P = sp_make_problem(h, 1, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, 0, nullptr, nullptr, temporal,
+                                      normalized, norm_order, zmax, stream);
   double *Cinv = at<double>(base, G.cinv), *vec = at<double>(base, G.vec), *dots = at<double>(base, G.dots);
   double *hcoef = at<double>(base, G.hcoef), *logdet = at<double>(base, G.logdet), *meanbar = at<double>(base, G.meanbar);
   double *A = at<double>(base, G.A), *AT = at<double>(base, G.AT), *B = at<double>(base, G.B), *BT = at<double>(base, G.BT);

@@ -316,6 +316,57 @@ struct SpProblem {
   }
 };
 
+// ---- What the C entry points of the ensemble sweeps share behind their own argument checks ("Star groups")
+static inline bool sp_temporal_valid(int temporal) {
+  return !(temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED);
+}
+// what a branch needs: the conditional one rta1 and the handle's moments, the marginal one the tables of the handle's
+// lag grid.  A missing argument (SP_ERR_INVALID) is reported before a handle that is not ready (SP_ERR_STATE)
+static inline int sp_branch_check(const sp_handle *h, int conditional, const double *rta1, const double *tab,
+                                  const double *meanvar, int covpts) {
+  if (conditional) {
+    if (!rta1) return SP_ERR_INVALID;
+    if (!h->have_moments) return SP_ERR_STATE;
+  } else {
+    if (!tab || !meanvar || covpts < 1) return SP_ERR_INVALID;
+    if (h->xp_covpts != covpts) return SP_ERR_STATE;
+  }
+  return SP_OK;
+}
+// the problem of an entry point's arguments (M = 0, flux = null: no data).  The conditional branch has no table: covpts =
+// 1; tab, meanvar and xp stay null.  h may be null (an entry point that fills its problem before it checks h)
+static inline SpProblem sp_make_problem(const sp_handle *h, int conditional, int S, int K, int M, const double *t,
+                                        const double *flux, const double *diag, const sp_star *stars, int covpts,
+                                        const double *tab, const double *meanvar, int temporal, int normalized,
+                                        int order, double zmax, void *stream) {
+  SpProblem P;
+  P.S = S, P.K = K, P.M = M, P.t = t, P.flux = flux, P.diag = diag, P.stars = stars;
+  if (conditional) P.covpts = 1;
+  else P.covpts = covpts, P.tab = tab, P.meanvar = meanvar, P.xp = h ? h->d_xp : nullptr;
+  P.temporal = temporal, P.normalized = normalized, P.order = order, P.zmax = zmax, P.st = (hipStream_t)stream;
+  return P;
+}
+// the largest group the workspace holds, bytes_of(n) the layout's total for n resident stars (it grows with n; a group
+// is a grid dimension); 0: not even one star fits
+template <class F>
+static inline int sp_star_group(int S, size_t workspace_bytes, F bytes_of) {
+  if (bytes_of(1) > workspace_bytes) return 0;
+  int lo = 1, hi = S < 65535 ? S : 65535;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (bytes_of(mid) <= workspace_bytes) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// fn(s0, n) for the groups [s0, s0 + n) of S stars in order, up to the first that does not return 0
+template <class F>
+static inline int sp_for_star_groups(int S, int group, F fn) {
+  for (int s0 = 0; s0 < S; s0 += group)
+    if (const int rc = fn(s0, S - s0 < group ? S - s0 : group)) return rc;
+  return SP_OK;
+}
+
 // What the workgroup that factors a group's LAST pivot block does behind it (sp_panel.hip): the
 // log-likelihood reduction of its star (sp_reduce.h), when the residual / normalisation rows live in
 // that block's row tile and the block is factored in a panel launch's tail (sp_panel_fuses_reduce).
@@ -560,9 +611,27 @@ int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, c
 // ... its first half alone: everything up to C in the corner of the system (raw is then scratch of its own)
 int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A,
                               double *B, double *raw, double *partial);
-// sp_loo.hip: the opening the leave-one-out and the leave-block-out sweeps (sp_lbo.hip) share.  sp_loo_layout_bytes: the
-// workspace of S resident stars (sp_loo_workspace_bytes without its argument checks).  sp_loo_open: C into the corner of
-// the system (sp_launch_marginal_system / sp_launch_cond_covariance), spd_identity_factor, then the column pass: white =
+// The scratch of that forward in a sweep that takes either branch: the design matrices A, B = A Sigma_y [S][Kr][N] and
+// the raw covariance [S][Kr][Kr]; nothing in the marginal branch
+struct SpCondCarve {
+  size_t A, B, raw;
+  void take(SpCarve &c, const sp_handle *h, int S, int K, int conditional) {
+    const size_t Kr = sp_roundup(K, SP_NB), d = sizeof(double);
+    A = c.take(conditional ? d * S * Kr * h->N : 0);
+    B = c.take(conditional ? d * S * Kr * h->N : 0);
+    raw = c.take(conditional ? d * S * Kr * Kr : 0);
+  }
+};
+// C into the corner of the system V factors, either branch (G carved from `base`; part: the forward's `partial`)
+static inline int sp_launch_system_corner(sp_handle *h, const SpProblem &Q, const SpViews &V, int conditional,
+                                          const double *rta1, void *base, const SpCondCarve &G, double *part) {
+  if (!conditional) return sp_launch_marginal_system(Q, V);
+  return sp_launch_cond_covariance(h, Q, V, rta1, at<double>(base, G.A), at<double>(base, G.B), at<double>(base, G.raw),
+                                   part);
+}
+// sp_loo.hip: the opening the leave-one-out and the leave-block-out sweeps (sp_lbo.hip) share.  sp_loo_layout: the
+// workspace of S resident stars (its total: sp_loo_workspace_bytes without its argument checks).  sp_loo_open: C into the
+// corner of the system (sp_launch_system_corner), spd_identity_factor, then the column pass: white =
 // L^-1 r of star s into white[s * wstride .. + K) (NaN for a star that did not factor or is ragged).  `out`: where Y =
 // L^-T lies (row m of star s at sys + s * stride + (K + m) * ld) and the per-star arrays behind it.
 struct SpLooSystem {
@@ -572,9 +641,21 @@ struct SpLooSystem {
   const int32_t *info;
   const double *logdet;
 };
-size_t sp_loo_layout_bytes(const sp_handle *h, int S, int K, int conditional);
+struct SpLooLayout {
+  size_t inv, logdet;
+  SpCondCarve cond;
+  size_t total;
+};
+SpLooLayout sp_loo_layout(const sp_handle *h, int S, int K, int conditional);
 int sp_loo_open(sp_handle *h, const SpProblem &Q, int conditional, const double *rta1, void *workspace, double *white,
                 long wstride, SpLooSystem *out);
+// sp_linear.hip: the workspace of S resident stars with q regressors (its total: sp_lnlike_linear_workspace_bytes)
+struct SpLinLayout {
+  size_t lik, gpart;
+  SpCondCarve cond;
+  size_t total;
+};
+SpLinLayout sp_lin_layout(const sp_handle *h, int S, int K, int q, int conditional);
 // sp_lnlike.hip: the tangents of the design matrices sp_launch_design left in place (V's cs, vrow, theta), Kr rows per
 // star: dA_inc = d A / d inc per radian (dR [S][NWIG], dv [S][N]: scratch), dA_per = d A / d period; either may be null
 int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,

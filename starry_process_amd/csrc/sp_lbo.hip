@@ -308,7 +308,7 @@ struct LboLayout {
 LboLayout lbo_layout(const sp_handle *h, int S, int K, int conditional, int nblocks) {
   LboLayout G;
   SpCarve c;
-  G.loo = c.take(sp_loo_layout_bytes(h, S, K, conditional));   // (first: sp_loo_open carves it from the base)
+  G.loo = c.take(sp_loo_layout(h, S, K, conditional).total);   // (first: sp_loo_open carves it from the base)
   G.bands = c.take(sizeof(int32_t) * ((size_t)nblocks + 1));
   G.bad = c.take(sizeof(int32_t) * (size_t)S * nblocks);
   G.total = c.off;
@@ -332,15 +332,9 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !edges_dev || !rows_dev || !lpd_dev || !lnlike_dev || !workspace_dev ||
       S < 0 || K < 2 || nblocks < 1 || nblocks > K || norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+      !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
-  if (conditional) {
-    if (!rta1_dev) return SP_ERR_INVALID;
-    if (!h->have_moments) return SP_ERR_STATE;
-  } else {
-    if (!tab_dev || !meanvar_dev || covpts < 1) return SP_ERR_INVALID;
-    if (h->xp_covpts != covpts) return SP_ERR_STATE;
-  }
+  if (const int rc = sp_branch_check(h, conditional, rta1_dev, tab_dev, meanvar_dev, covpts)) return rc;
   if (S == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   // the partition decides the grid and what the kernels may index: it is read back and checked here
@@ -355,30 +349,17 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
     bmax = w > bmax ? w : bmax;
   }
   const int nbands = lbo_count_bands(e);
-  // the largest group the workspace holds (the layout grows with the number of stars; a group is a grid dimension)
-  if (lbo_layout(h, 1, K, conditional, nblocks).total > workspace_bytes) return SP_ERR_INVALID;
-  int lo = 1, hi = S < 65535 ? S : 65535;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (lbo_layout(h, mid, K, conditional, nblocks).total <= workspace_bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  const int group = lo;
+  const int group =
+      sp_star_group(S, workspace_bytes, [&](int n) { return lbo_layout(h, n, K, conditional, nblocks).total; });
+  if (!group) return SP_ERR_INVALID;
   const LboLayout G = lbo_layout(h, group, K, conditional, nblocks);
   char *base = static_cast<char *>(workspace_dev);
   int32_t *bands = at<int32_t>(base, G.bands), *bad = at<int32_t>(base, G.bad);
   hipLaunchKernelGGL(lbo_bands_kernel, dim3(1), dim3(64), 0, st, nblocks, edges_dev, bands);
   SP_LAUNCH_CHECK();
-  SpProblem Q;
-  Q.S = S, Q.K = K, Q.M = 1, Q.t = t_dev, Q.flux = flux_dev, Q.diag = diag_dev, Q.stars = stars_dev;
-  if (conditional) {
-    Q.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
-  } else {
-    Q.covpts = covpts, Q.tab = tab_dev, Q.meanvar = meanvar_dev, Q.xp = h->d_xp;
-  }
-  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = st;
-  for (int s0 = 0; s0 < S; s0 += group) {
-    const int n = S - s0 < group ? S - s0 : group;
+  const SpProblem Q = sp_make_problem(h, conditional, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev,
+                                      meanvar_dev, temporal, normalized, norm_order, zmax, stream);
+  return sp_for_star_groups(S, group, [&](int s0, int n) -> int {
     const SpProblem P = Q.slice(s0, s0 + n);
     double *rows = rows_dev + (size_t)s0 * 4 * K, *lpd = lpd_dev + (size_t)s0 * nblocks;
     double *cov = cov_dev ? cov_dev + (size_t)s0 * nblocks * bmax * bmax : nullptr;
@@ -391,8 +372,8 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
     hipLaunchKernelGGL(lbo_finish_kernel, dim3(n), dim3(256), 0, st, K, nblocks, rows, P.stars, Y.coef, Y.info, Y.logdet,
                        bad, normalized, zmax, lnlike_dev + s0, status_dev ? status_dev + s0 : nullptr);
     SP_LAUNCH_CHECK();
-  }
-  return SP_OK;
+    return SP_OK;
+  });
 }
 
 }  // extern "C"

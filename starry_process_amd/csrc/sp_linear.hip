@@ -242,25 +242,21 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
   }
 }
 
-struct LinLayout {
-  size_t lik, gpart, A, B, raw, total;
-};
-LinLayout lin_layout(const sp_handle *h, int S, int K, int q, int conditional) {
-  const int Kr = sp_roundup(K, SP_NB);
-  const size_t d = sizeof(double);
-  LinLayout G;
+}  // namespace
+
+SpLinLayout sp_lin_layout(const sp_handle *h, int S, int K, int q, int conditional) {
+  SpLinLayout G;
   SpCarve c;
   // the likelihood's lean layout with a system of 1 + q riding rows (no K identity rows: sp_sweep_views would reserve
   // them), then the chunks' Gram parts
   G.lik = c.take(make_layout(h, S, K, 1 + q, true, true).total);
-  G.gpart = c.take(d * (size_t)S * lin_nsplit(K) * (lin_npair(q) + 1));
-  // the conditional branch's forward: the design matrices, A Sigma_y and the raw covariance (sp_launch_cond_covariance)
-  G.A = c.take(conditional ? d * (size_t)S * Kr * h->N : 0);
-  G.B = c.take(conditional ? d * (size_t)S * Kr * h->N : 0);
-  G.raw = c.take(conditional ? d * (size_t)S * Kr * Kr : 0);
+  G.gpart = c.take(sizeof(double) * (size_t)S * lin_nsplit(K) * (lin_npair(q) + 1));
+  G.cond.take(c, h, S, K, conditional);
   G.total = c.off;
   return G;
 }
+
+namespace {
 
 // one group of stars (Q: their problem; the slices of the inputs and outputs already taken)
 int lin_group(sp_handle *h, const SpProblem &Q, int q, int conditional, const double *rta1, const double *basis,
@@ -268,18 +264,13 @@ int lin_group(sp_handle *h, const SpProblem &Q, int q, int conditional, const do
               void *workspace) {
   const int S = Q.S, K = Q.K, Kr = sp_roundup(K, SP_NB);
   hipStream_t st = Q.st;
-  const LinLayout G = lin_layout(h, S, K, q, conditional);
+  const SpLinLayout G = sp_lin_layout(h, S, K, q, conditional);
   char *base = static_cast<char *>(workspace);
   const SpViews V{make_layout(h, S, K, 1 + q, true, true), base + G.lik};
   const int Kp = V.L.Kp;
   double *gpart = at<double>(base, G.gpart);
   int rc;
-  if (conditional)
-    rc = sp_launch_cond_covariance(h, Q, V, rta1, at<double>(base, G.A), at<double>(base, G.B), at<double>(base, G.raw),
-                                   V.part());
-  else
-    rc = sp_launch_marginal_system(Q, V);
-  if (rc) return rc;
+  if ((rc = sp_launch_system_corner(h, Q, V, conditional, rta1, base, G.cond, V.part()))) return rc;
   SP_HIP(hipMemsetAsync(V.info(), 0, sizeof(int32_t) * S, st));
   hipLaunchKernelGGL(lin_rows_kernel, dim3((Kp + 255) / 256, Kp - K + 1, S), dim3(256), 0, st, K, q, Kr, Kp, V.sys(), Q.flux,
                      basis, Q.stars, (const SpCoef *)V.coef());
@@ -301,7 +292,7 @@ extern "C" {
 
 size_t sp_lnlike_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts, int conditional) {
   if (!h || S < 0 || K < 2 || q < 1 || q > LIN_QMAX || (!conditional && covpts < 1)) return 0;
-  return lin_layout(h, S, K, q, conditional).total;
+  return sp_lin_layout(h, S, K, q, conditional).total;
 }
 
 int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const double *flux_dev,
@@ -313,43 +304,21 @@ int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, con
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !basis_dev || !basis_var_dev || !lnlike_dev || !lnlike0_dev ||
       !wmean_dev || !workspace_dev || S < 0 || K < 2 || q < 1 || q > LIN_QMAX || norm_order < 0 ||
-      norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+      norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
-  if (conditional) {
-    if (!rta1_dev) return SP_ERR_INVALID;
-    if (!h->have_moments) return SP_ERR_STATE;
-  } else {
-    if (!tab_dev || !meanvar_dev || covpts < 1) return SP_ERR_INVALID;
-    if (h->xp_covpts != covpts) return SP_ERR_STATE;
-  }
+  if (const int rc = sp_branch_check(h, conditional, rta1_dev, tab_dev, meanvar_dev, covpts)) return rc;
   if (S == 0) return SP_OK;
-  // the largest group the workspace holds (the layout grows with the number of stars; a group is a grid dimension)
-  if (lin_layout(h, 1, K, q, conditional).total > workspace_bytes) return SP_ERR_INVALID;
-  int lo = 1, hi = S < 65535 ? S : 65535;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (lin_layout(h, mid, K, q, conditional).total <= workspace_bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  const int group = lo;
-  SpProblem Q;
-  Q.S = S, Q.K = K, Q.M = 1, Q.t = t_dev, Q.flux = flux_dev, Q.diag = diag_dev, Q.stars = stars_dev;
-  if (conditional) {
-    Q.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
-  } else {
-    Q.covpts = covpts, Q.tab = tab_dev, Q.meanvar = meanvar_dev, Q.xp = h->d_xp;
-  }
-  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = (hipStream_t)stream;
-  for (int s0 = 0; s0 < S; s0 += group) {
-    const int n = S - s0 < group ? S - s0 : group;
-    const int rc = lin_group(h, Q.slice(s0, s0 + n), q, conditional ? 1 : 0, rta1_dev, basis_dev + (size_t)s0 * q * K,
-                             basis_var_dev + (size_t)s0 * q, lnlike_dev + s0, lnlike0_dev + s0,
-                             wmean_dev + (size_t)s0 * q, wcov_dev ? wcov_dev + (size_t)s0 * q * q : nullptr,
-                             status_dev ? status_dev + s0 : nullptr, workspace_dev);
-    if (rc) return rc;
-  }
-  return SP_OK;
+  const int group =
+      sp_star_group(S, workspace_bytes, [&](int n) { return sp_lin_layout(h, n, K, q, conditional).total; });
+  if (!group) return SP_ERR_INVALID;
+  const SpProblem Q = sp_make_problem(h, conditional, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev,
+                                      meanvar_dev, temporal, normalized, norm_order, zmax, stream);
+  return sp_for_star_groups(S, group, [&](int s0, int n) {
+    return lin_group(h, Q.slice(s0, s0 + n), q, conditional ? 1 : 0, rta1_dev, basis_dev + (size_t)s0 * q * K,
+                     basis_var_dev + (size_t)s0 * q, lnlike_dev + s0, lnlike0_dev + s0, wmean_dev + (size_t)s0 * q,
+                     wcov_dev ? wcov_dev + (size_t)s0 * q * q : nullptr, status_dev ? status_dev + s0 : nullptr,
+                     workspace_dev);
+  });
 }
 
 }  // extern "C"

@@ -169,30 +169,18 @@ __global__ __launch_bounds__(256) void loo_rows_kernel(int K, long ld, long stri
   }
 }
 
-struct LooLayout {
-  size_t inv, logdet, A, B, raw, total;
-};
-LooLayout loo_layout(const sp_handle *h, int S, int K, int conditional) {
-  const int Kr = sp_roundup(K, SP_NB);
-  const size_t d = sizeof(double);
-  LooLayout G;
+}  // namespace
+
+SpLooLayout sp_loo_layout(const sp_handle *h, int S, int K, int conditional) {
+  SpLooLayout G;
   SpCarve c;
   // the SPD inverse's own workspace: the system Y is left in, the small per-star arrays and `part`, which takes the
   // column pass's blocks ([S][Kr / 64][K] doubles of its [S][Kp / 64][K])
-  G.inv = c.take(make_layout(h, S, K, Kr, true, true).total);
-  G.logdet = c.take(d * S);
-  // the conditional branch's forward: the design matrices, A Sigma_y and the raw covariance (sp_launch_cond_covariance)
-  G.A = c.take(conditional ? d * (size_t)S * Kr * h->N : 0);
-  G.B = c.take(conditional ? d * (size_t)S * Kr * h->N : 0);
-  G.raw = c.take(conditional ? d * (size_t)S * Kr * Kr : 0);
+  G.inv = c.take(make_layout(h, S, K, sp_roundup(K, SP_NB), true, true).total);
+  G.logdet = c.take(sizeof(double) * S);
+  G.cond.take(c, h, S, K, conditional);
   G.total = c.off;
   return G;
-}
-
-}  // namespace
-
-size_t sp_loo_layout_bytes(const sp_handle *h, int S, int K, int conditional) {
-  return loo_layout(h, S, K, conditional).total;
 }
 
 // The opening the leave-one-out and the leave-block-out sweeps share (sp_internal.h): C into the corner of the system,
@@ -201,18 +189,13 @@ int sp_loo_open(sp_handle *h, const SpProblem &Q, int conditional, const double 
                 long wstride, SpLooSystem *out) {
   const int S = Q.S, K = Q.K, Kr = sp_roundup(K, SP_NB), nrb = Kr / LOO_RB;
   hipStream_t st = Q.st;
-  const LooLayout G = loo_layout(h, S, K, conditional);
+  const SpLooLayout G = sp_loo_layout(h, S, K, conditional);
   char *base = static_cast<char *>(workspace);
   const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
   double *logdet = at<double>(base, G.logdet), *part = V.part();
   const long ld = V.L.Kp, stride = (long)V.L.Kp * V.L.Kp;
   int rc;
-  if (conditional)
-    rc = sp_launch_cond_covariance(h, Q, V, rta1, at<double>(base, G.A), at<double>(base, G.B), at<double>(base, G.raw),
-                                   part);
-  else
-    rc = sp_launch_marginal_system(Q, V);
-  if (rc) return rc;
+  if ((rc = sp_launch_system_corner(h, Q, V, conditional, rta1, base, G.cond, part))) return rc;
   if ((rc = spd_identity_factor(h, S, K, V.L, V.ws, logdet, st))) return rc;
   hipLaunchKernelGGL(loo_white_part_kernel, dim3((K + LOO_CB - 1) / LOO_CB, nrb, S), dim3(256), 0, st, K, ld, stride,
                      V.sys(), Q.flux, Q.stars, (const SpCoef *)V.coef(), part);
@@ -250,7 +233,7 @@ extern "C" {
 
 size_t sp_loo_workspace_bytes(sp_handle *h, int S, int K, int covpts, int conditional) {
   if (!h || S < 0 || K < 2 || (!conditional && covpts < 1)) return 0;
-  return loo_layout(h, S, K, conditional).total;
+  return sp_loo_layout(h, S, K, conditional).total;
 }
 
 int sp_loo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev, const double *diag_dev,
@@ -260,41 +243,19 @@ int sp_loo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
                     size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !loo_dev || !lnlike_dev || !workspace_dev || S < 0 || K < 2 ||
-      norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
-      (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED))
+      norm_order < 0 || norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
-  if (conditional) {
-    if (!rta1_dev) return SP_ERR_INVALID;
-    if (!h->have_moments) return SP_ERR_STATE;
-  } else {
-    if (!tab_dev || !meanvar_dev || covpts < 1) return SP_ERR_INVALID;
-    if (h->xp_covpts != covpts) return SP_ERR_STATE;
-  }
+  if (const int rc = sp_branch_check(h, conditional, rta1_dev, tab_dev, meanvar_dev, covpts)) return rc;
   if (S == 0) return SP_OK;
-  // the largest group the workspace holds (the layout grows with the number of stars; a group is a grid dimension)
-  if (loo_layout(h, 1, K, conditional).total > workspace_bytes) return SP_ERR_INVALID;
-  int lo = 1, hi = S < 65535 ? S : 65535;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (loo_layout(h, mid, K, conditional).total <= workspace_bytes) lo = mid;
-    else hi = mid - 1;
-  }
-  const int group = lo;
-  SpProblem Q;
-  Q.S = S, Q.K = K, Q.M = 1, Q.t = t_dev, Q.flux = flux_dev, Q.diag = diag_dev, Q.stars = stars_dev;
-  if (conditional) {
-    Q.covpts = 1;   // (the conditional branch: no table; tab, meanvar, xp stay null)
-  } else {
-    Q.covpts = covpts, Q.tab = tab_dev, Q.meanvar = meanvar_dev, Q.xp = h->d_xp;
-  }
-  Q.temporal = temporal, Q.normalized = normalized, Q.order = norm_order, Q.zmax = zmax, Q.st = (hipStream_t)stream;
-  for (int s0 = 0; s0 < S; s0 += group) {
-    const int n = S - s0 < group ? S - s0 : group;
-    const int rc = loo_group(h, Q.slice(s0, s0 + n), conditional ? 1 : 0, rta1_dev, loo_dev + (size_t)s0 * 5 * K,
-                             lnlike_dev + s0, status_dev ? status_dev + s0 : nullptr, workspace_dev);
-    if (rc) return rc;
-  }
-  return SP_OK;
+  const int group =
+      sp_star_group(S, workspace_bytes, [&](int n) { return sp_loo_layout(h, n, K, conditional).total; });
+  if (!group) return SP_ERR_INVALID;
+  const SpProblem Q = sp_make_problem(h, conditional, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev,
+                                      meanvar_dev, temporal, normalized, norm_order, zmax, stream);
+  return sp_for_star_groups(S, group, [&](int s0, int n) {
+    return loo_group(h, Q.slice(s0, s0 + n), conditional ? 1 : 0, rta1_dev, loo_dev + (size_t)s0 * 5 * K,
+                     lnlike_dev + s0, status_dev ? status_dev + s0 : nullptr, workspace_dev);
+  });
 }
 
 }  // extern "C"

@@ -130,8 +130,7 @@ int sp_plan_data(sp_handle *h, int S, int K, int M, const double *t_dev, const d
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !out || !t_dev || !flux_dev || !stars_dev || !workspace_dev || S < 1 || K < 2 || M < 1 || covpts < 1)
     return SP_ERR_INVALID;
-  if (temporal != SP_TEMPORAL_NONE && temporal != SP_TEMPORAL_MATERN32 && temporal != SP_TEMPORAL_EXPSQUARED)
-    return SP_ERR_INVALID;
+  if (!sp_temporal_valid(temporal)) return SP_ERR_INVALID;
   *out = nullptr;
   hipStream_t st = (hipStream_t)stream;
   const int np = covpts + 4;

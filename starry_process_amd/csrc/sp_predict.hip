@@ -384,8 +384,7 @@ int assemble_chunk(sp_handle *h, const PredictLayout &L, void *ws, const Predict
 
 int check_in(const sp_handle *h, int S, const PredictIn &in) {
   if (S < 0 || in.K < 1 || in.Ks < 1 || !in.t || !in.ts || !in.flux || !in.stars) return SP_ERR_INVALID;
-  if (in.temporal != SP_TEMPORAL_NONE && in.temporal != SP_TEMPORAL_MATERN32 && in.temporal != SP_TEMPORAL_EXPSQUARED)
-    return SP_ERR_INVALID;
+  if (!sp_temporal_valid(in.temporal)) return SP_ERR_INVALID;
   if (in.covpts < 1) return SP_ERR_INVALID;   // (sizes the workspace in both branches)
   if (in.conditional) {
     if (!in.rta1) return SP_ERR_INVALID;

@@ -161,6 +161,36 @@ class Engine(object):
             workspace = self._grad_ws = self._scratch(nbytes)
         return workspace
 
+    def _group_scratch(self, bytes_of, S, workspace, max_workspace_bytes=None):
+        """The workspace of a sweep that takes its S stars in groups: the caller's, or fresh scratch (kept on the
+        engine) for all S -- ``bytes_of(n)``: the driver's ``*_workspace_bytes`` query for n stars -- or of
+        ``max_workspace_bytes`` where that is less, which must hold one star."""
+        if workspace is not None:
+            return workspace
+        need = int(bytes_of(S))
+        if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
+            one = int(bytes_of(1))
+            if int(max_workspace_bytes) < one:
+                raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
+                                 % (int(max_workspace_bytes), one))
+            need = int(max_workspace_bytes)
+        self._grad_ws = self._scratch(need)
+        return self._grad_ws
+
+    def _ensemble_inputs(self, t, flux, stars, diag, rta1, conditional, what=None):
+        """What the ensemble sweeps take alike, as the library wants it: t, flux [S, K] (with ``what``, the caller's
+        name for itself: K >= 2), the stars' device copy, diag and rta1 (or None) in float64, ``conditional`` as int."""
+        torch = _torch()
+        t, flux = self.f64(t), self.f64(flux)
+        if flux.dim() != 2 or t.shape != flux.shape:
+            raise ValueError("t and flux must both be (S, K)")
+        if what is not None and flux.shape[1] < 2:
+            raise ValueError("%s needs at least two cadences" % what)
+        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
+        diag = None if diag is None else self.f64(diag)
+        rta1 = None if rta1 is None else self.f64(rta1)
+        return t, flux, sd, diag, rta1, int(bool(conditional))
+
     def _out_status(self, S, out, status):
         """(out, status) of a likelihood call over S systems: the caller's tensors, or fresh ones (status zeroed)."""
         if out is None:
@@ -675,22 +705,16 @@ class Engine(object):
         raise ValueError("mode must be True, False or \"diag\"")
 
     def _predict_call(self, fn, t, ts, flux, stars, diag, conditional, covpts, tab, meanvar, rta1, temporal, extra):
-        torch = _torch()
-        t, flux = self.f64(t), self.f64(flux)
-        if flux.dim() != 2 or t.shape != flux.shape:
-            raise ValueError("t and flux must both be (S, K)")
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional)
         S, K = flux.shape
         ts = None if ts is None else self.f64(ts)
         if ts is not None and (ts.dim() != 2 or ts.shape[0] != S or ts.shape[1] < 1):
             raise ValueError("ts must be (S, Ks)")
         Ks = K if ts is None else int(ts.shape[1])
-        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
-        diag = None if diag is None else self.f64(diag)
-        rta1 = None if rta1 is None else self.f64(rta1)
         ws = self._scratch(self._L.sp_predict_workspace_bytes(self._h, S, K, Ks, int(covpts)))
         out = extra(S, K, Ks)
         check(fn(self._h, S, K, Ks, self._p(t), self._p(ts), self._p(flux), self._p(diag), self._p(sd),
-                 int(bool(conditional)), int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
+                 conditional, int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
                  TEMPORAL[temporal], *([x if isinstance(x, int) else self._p(x) for x in out] + [self._p(ws),
                                                                                                  self._stream()])))
         return out
@@ -1387,8 +1411,8 @@ class Engine(object):
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         dcov = self.empty(S, P, K, K) if return_tangents else None
         if S > 0:
-            if workspace is None:
-                workspace = self._grad_ws = self.fisher_workspace(S, K, P, covpts)
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_fisher_workspace_bytes(self._h, n, K, P, int(covpts)), S, workspace)
             check(self._L.sp_fisher_marginal(
                 self._h, S, K, P, self._p(t), self._p(diag), self._p(stars_dev), int(covpts), self._p(tab),
                 self._p(meanvar), self._p(dyp.contiguous()), self._p(dmean.contiguous()), TEMPORAL[temporal],
@@ -1424,8 +1448,8 @@ class Engine(object):
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         dcov = self.empty(S, P, K, K) if return_tangents else None
         if S > 0:
-            if workspace is None:
-                workspace = self._grad_ws = self.fisher_conditional_workspace(S, K, P)
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_fisher_conditional_workspace_bytes(self._h, n, K, P), S, workspace)
             check(self._L.sp_fisher_conditional(
                 self._h, S, K, Ph, mask, self._p(t), self._p(diag), self._p(stars_dev), self._p(rta1), self._p(dmu),
                 self._p(dsig), TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(fisher),
@@ -1450,28 +1474,15 @@ class Engine(object):
         instead.  A workspace that holds fewer than S stars makes the call work through them in groups, with the
         same bits."""
         torch = _torch()
-        t, flux = self.f64(t), self.f64(flux)
-        if flux.dim() != 2 or t.shape != flux.shape:
-            raise ValueError("t and flux must both be (S, K)")
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
+                                                                     "leave-one-out")
         S, K = flux.shape
-        if K < 2:
-            raise ValueError("leave-one-out needs at least two cadences")
-        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
-        diag = None if diag is None else self.f64(diag)
-        rta1 = None if rta1 is None else self.f64(rta1)
-        conditional = int(bool(conditional))
         loo, lnlike = self.empty(S, 5, K), self.empty(S)
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         if S > 0:
-            if workspace is None:
-                need = int(self._L.sp_loo_workspace_bytes(self._h, S, K, int(covpts), conditional))
-                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
-                    one = int(self._L.sp_loo_workspace_bytes(self._h, 1, K, int(covpts), conditional))
-                    if int(max_workspace_bytes) < one:
-                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
-                                         % (int(max_workspace_bytes), one))
-                    need = int(max_workspace_bytes)
-                workspace = self._grad_ws = self._scratch(need)
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_loo_workspace_bytes(self._h, n, K, int(covpts), conditional), S, workspace,
+                max_workspace_bytes)
             check(self._L.sp_loo_ensemble(
                 self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), conditional, int(covpts),
                 self._p(tab), self._p(meanvar), self._p(rta1), TEMPORAL[temporal], int(bool(normalized)),
@@ -1497,12 +1508,9 @@ class Engine(object):
         (``lbo_workspace``); ``max_workspace_bytes`` caps the scratch allocated here instead.  A workspace that holds
         fewer than S stars makes the call work through them in groups, with the same bits."""
         torch = _torch()
-        t, flux = self.f64(t), self.f64(flux)
-        if flux.dim() != 2 or t.shape != flux.shape:
-            raise ValueError("t and flux must both be (S, K)")
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
+                                                                     "leave-block-out")
         S, K = flux.shape
-        if K < 2:
-            raise ValueError("leave-block-out needs at least two cadences")
         if isinstance(edges, torch.Tensor):
             # (a device tensor is the caller's word: sp_lbo_ensemble checks it; its widest block sizes `cov`)
             ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
@@ -1514,23 +1522,13 @@ class Engine(object):
             bmax = int(np.diff(eh).max())
             ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
         nb = int(ed.numel()) - 1
-        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
-        diag = None if diag is None else self.f64(diag)
-        rta1 = None if rta1 is None else self.f64(rta1)
-        conditional = int(bool(conditional))
         rows, lpd, lnlike = self.empty(S, 4, K), self.empty(S, nb), self.empty(S)
         cov = self.empty(S, nb, bmax, bmax) if return_cov else None
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         if S > 0:
-            if workspace is None:
-                need = int(self._L.sp_lbo_workspace_bytes(self._h, S, K, int(covpts), conditional, nb))
-                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
-                    one = int(self._L.sp_lbo_workspace_bytes(self._h, 1, K, int(covpts), conditional, nb))
-                    if int(max_workspace_bytes) < one:
-                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
-                                         % (int(max_workspace_bytes), one))
-                    need = int(max_workspace_bytes)
-                workspace = self._grad_ws = self._scratch(need)
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_lbo_workspace_bytes(self._h, n, K, int(covpts), conditional, nb), S, workspace,
+                max_workspace_bytes)
             check(self._L.sp_lbo_ensemble(
                 self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), conditional, int(covpts),
                 self._p(tab), self._p(meanvar), self._p(rta1), TEMPORAL[temporal], int(bool(normalized)),
@@ -1557,12 +1555,10 @@ class Engine(object):
         caps the scratch allocated here instead.  A workspace that holds fewer than S stars makes the call work
         through them in groups, with the same bits."""
         torch = _torch()
-        t, flux, basis, basis_var = self.f64(t), self.f64(flux), self.f64(basis), self.f64(basis_var)
-        if flux.dim() != 2 or t.shape != flux.shape:
-            raise ValueError("t and flux must both be (S, K)")
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
+                                                                     "the likelihood with regressors")
         S, K = flux.shape
-        if K < 2:
-            raise ValueError("the likelihood with regressors needs at least two cadences")
+        basis, basis_var = self.f64(basis), self.f64(basis_var)
         if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
             raise ValueError("`basis` must be (S, q, K)")
         q = int(basis.shape[1])
@@ -1571,23 +1567,13 @@ class Engine(object):
         if tuple(basis_var.shape) != (S, q):
             raise ValueError("`basis_var` must be (S, q)")
         basis, basis_var = basis.contiguous(), basis_var.contiguous()
-        sd = stars if isinstance(stars, torch.Tensor) else self.stars_to_device(stars)
-        diag = None if diag is None else self.f64(diag)
-        rta1 = None if rta1 is None else self.f64(rta1)
-        conditional = int(bool(conditional))
         lnlike, lnlike0, wmean = self.empty(S), self.empty(S), self.empty(S, q)
         wcov = self.empty(S, q, q) if return_cov else None
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         if S > 0:
-            if workspace is None:
-                need = int(self._L.sp_lnlike_linear_workspace_bytes(self._h, S, K, q, int(covpts), conditional))
-                if max_workspace_bytes is not None and int(max_workspace_bytes) < need:
-                    one = int(self._L.sp_lnlike_linear_workspace_bytes(self._h, 1, K, q, int(covpts), conditional))
-                    if int(max_workspace_bytes) < one:
-                        raise ValueError("max_workspace_bytes = %d holds no star: one needs %d bytes"
-                                         % (int(max_workspace_bytes), one))
-                    need = int(max_workspace_bytes)
-                workspace = self._grad_ws = self._scratch(need)
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_lnlike_linear_workspace_bytes(self._h, n, K, q, int(covpts), conditional), S,
+                workspace, max_workspace_bytes)
             check(self._L.sp_lnlike_linear(
                 self._h, S, K, q, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(basis),
                 self._p(basis_var), conditional, int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),

@@ -278,6 +278,28 @@ def test_one_star_resident_gives_the_same_bits(iso):
                                 p, None, p, one - 1, e._stream()) == -1
 
 
+def test_one_star_resident_gives_the_same_bits_in_the_conditional_branch():
+    """The same with the inclinations given (ydeg 5, S = 3, K = 129): the workspace then holds the design matrices and
+    the raw covariance behind the system, per resident star."""
+    sp = SP5(normalized=True, marginalize_over_inclination=False)
+    t, flux, kw = _inputs(3, 129, seed=5)
+    flux = 1.0 + flux
+    kw["baseline_mean"] = 1.0 + kw["baseline_mean"]
+    dcov = 2e-6 * (1 + np.random.RandomState(2).rand(3, 129))
+    edges = _irregular(129)
+    full = sp.lbo_ensemble(t, flux, dcov, edges, return_cov=True, **kw)
+    assert np.all(full["status"] == 0) and np.all(np.isfinite(full["lnlike"]))
+    e = sp._engine
+    nb = len(edges) - 1
+    one = int(e._L.sp_lbo_workspace_bytes(e._h, 1, 129, 300, 1, nb))
+    two = int(e._L.sp_lbo_workspace_bytes(e._h, 2, 129, 300, 1, nb))
+    assert int(e._L.sp_lbo_workspace_bytes(e._h, 1, 129, 300, 0, nb)) < one < two
+    for cap in (one, two - 1):
+        assert _same_bits(sp.lbo_ensemble(t, flux, dcov, edges, return_cov=True, max_workspace_bytes=cap, **kw), full)
+    with pytest.raises(ValueError):
+        sp.lbo_ensemble(t, flux, dcov, edges, max_workspace_bytes=one - 1, **kw)
+
+
 def test_single_star_form_is_row_zero_of_the_ensemble():
     sp = SP15(marginalize_over_inclination=False)
     t, flux, kw = _inputs(1, 70)

@@ -260,6 +260,34 @@ def test_one_star_resident_gives_the_same_bits(iso):
         call(t, flux, dcov, U, lam, max_workspace_bytes=one - 1, **kw)
 
 
+def test_one_star_resident_gives_the_same_bits_in_the_conditional_branch():
+    """The same with the inclinations given (ydeg 5, S = 3, K = 129): the workspace then holds the design matrices and
+    the raw covariance behind the system, per resident star."""
+    from starry_process_amd import linear
+
+    sp = SP5(normalized=True, marginalize_over_inclination=False)
+    S, K = 3, 129
+    t, flux, kw = _inputs(S, K, seed=5)
+    edges = [0, 40, 90, 129]
+    U = linear.stack_bases(linear.offset_basis(K, edges), linear.polynomial_basis(t, 2, edges))
+    lam = np.array([1e-4] * 3 + [2.5e-5] * 6)
+    flux = 1.0 + _trended(flux, U, lam, 8)
+    kw["baseline_mean"] = 1.0 + kw["baseline_mean"]
+    dcov = 2e-6 * (1 + np.random.RandomState(2).rand(S, K))
+    call = sp.log_likelihood_linear_ensemble
+    full = call(t, flux, dcov, U, lam, **kw)
+    assert np.all(full["status"] == 0) and np.all(np.isfinite(full["lnlike"]))
+    e = sp._engine
+    q = U.shape[1]
+    one = int(e._L.sp_lnlike_linear_workspace_bytes(e._h, 1, K, q, 300, 1))
+    two = int(e._L.sp_lnlike_linear_workspace_bytes(e._h, 2, K, q, 300, 1))
+    assert int(e._L.sp_lnlike_linear_workspace_bytes(e._h, 1, K, q, 300, 0)) < one < two
+    assert _same_bits(call(t, flux, dcov, U, lam, max_workspace_bytes=one, **kw), full)
+    assert _same_bits(call(t, flux, dcov, U, lam, max_workspace_bytes=two - 1, **kw), full)
+    with pytest.raises(ValueError):
+        call(t, flux, dcov, U, lam, max_workspace_bytes=one - 1, **kw)
+
+
 def test_bad_arguments_at_the_c_level_leave_the_outputs_untouched(iso):
     import torch
 

@@ -202,6 +202,26 @@ def test_one_star_resident_gives_the_same_bits(iso):
                                 e._stream()) == -1
 
 
+def test_one_star_resident_gives_the_same_bits_in_the_conditional_branch():
+    """The same with the inclinations given (ydeg 5, S = 3, K = 129): the workspace then holds the design matrices and
+    the raw covariance behind the system, per resident star."""
+    sp = SP5(normalized=True, marginalize_over_inclination=False)
+    t, flux, kw = _inputs(3, 129, seed=5)
+    flux = 1.0 + flux
+    kw["baseline_mean"] = 1.0 + kw["baseline_mean"]
+    dcov = 2e-6 * (1 + np.random.RandomState(2).rand(3, 129))
+    full = sp.loo_ensemble(t, flux, dcov, **kw)
+    assert np.all(full["status"] == 0) and np.all(np.isfinite(full["lnlike"]))
+    e = sp._engine
+    one = int(e._L.sp_loo_workspace_bytes(e._h, 1, 129, 300, 1))
+    two = int(e._L.sp_loo_workspace_bytes(e._h, 2, 129, 300, 1))
+    assert int(e._L.sp_loo_workspace_bytes(e._h, 1, 129, 300, 0)) < one < two
+    assert _same_bits(sp.loo_ensemble(t, flux, dcov, max_workspace_bytes=one, **kw), full)
+    assert _same_bits(sp.loo_ensemble(t, flux, dcov, max_workspace_bytes=two - 1, **kw), full)
+    with pytest.raises(ValueError):
+        sp.loo_ensemble(t, flux, dcov, max_workspace_bytes=one - 1, **kw)
+
+
 def test_a_star_that_does_not_factor_leaves_its_neighbours_alone(iso):
     sp, t, flux, dcov, kw, full = iso
     bad = dcov.copy()
