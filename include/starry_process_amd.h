@@ -699,6 +699,51 @@ int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, con
                      uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
                      void *stream);
 
+/* ---- The ensemble gradient with linear regressors marginalised out, marginal branch -----------------------------------
+ * The reverse sweep of sp_lnlike_linear's value: sp_lnlike_grad_marginal_stars for the model flux_s = process + U_s w +
+ * noise, w ~ N(0, diag lambda_s), one light curve per star (flux_dev [S, K]), every cadence valid.  basis_dev [S, q, K]
+ * and basis_var_dev [S, q] as sp_lnlike_linear takes them; C, r, alpha = C^-1 r, the normalisation and the table as
+ * sp_lnlike_grad_marginal.  With D = diag sqrt(lambda) and C~ = C + U Lambda U^T (never formed):
+ *   P = U^T C^-1 U,   h = D U^T alpha,   G_q = I + D P D = L_G L_G^T,   v = L_G^-1 h
+ *   Z = C^-1 U D L_G^-T,   C~^-1 = C^-1 - Z Z^T,   alpha~ = alpha - Z v
+ *   lnlike_dev [S]:   -1/2 r^T alpha~ - 1/2 log det C - sum log (L_G)_jj - K/2 log 2 pi   (sp_lnlike_linear's lnlike)
+ *   d lnL / dC = (B B^T - C^-1) / 2,  B = [alpha~, z_1 .. z_q], pulled back through the normalisation and the cubic
+ *   interpolation exactly as sp_lnlike_grad_marginal pulls (alpha alpha^T - C^-1) / 2 back:
+ *   ybar_dev [S, covpts + 4], meanbar_dev [S]:  d lnL_s / d (the star's kernel table, its flux mean)
+ *   starbar_dev [S, SP_STARBAR] (may be NULL):  the slots of sp_lnlike_grad_marginal_stars -- period, tau, baseline_mean
+ *                     (sum_i alpha~_i), baseline_var <G~, 1 1^T>, log of a common factor on the data variances <G~, D>, 0
+ *   lambar_dev [S, q] (may be NULL):  d lnL_s / d lambda_sj = (g_j^2 - H_jj) / 2,  g = U^T alpha~,
+ *                     H = U^T C~^-1 U = P - P D G_q^-1 D P -- the derivative with respect to lambda itself, finite at
+ *                     lambda_j = 0; nothing is divided by lambda, and lambda_j = 0 gives z_j = 0 exactly
+ *   wmean_dev [S, q] (may be NULL):  D L_G^-T v, the posterior mean of the weights (sp_lnlike_linear's wmean)
+ * C^-1 comes from sp_spd_inverse_batched's machinery; ONE pass over its lower 64 x 64 tiles gives C^-1 [p, q, 1, r, U]
+ * on the fp64 matrix cores whatever q, one wavefront per star finishes the q x q system, and one pass over the lower
+ * tiles forms the blocks of B B^T on the matrix cores and scatters into the table's adjoint and the period / tau sums.
+ * Sums run in a fixed order, each wavefront adds into bins of its own: the same bits run after run, alone or among
+ * other stars, at any position.  status_dev [S] (may be NULL).  Per star:
+ *   covariance that does not factor, or z > zmax:  lnlike = -inf; zeros in ybar, meanbar, starbar, lambar and wmean;
+ *                                                  SP_STAR_NOT_PD / SP_STAR_ZMAX
+ *   ragged star (0 < nobs < K):                    NaN in every output, SP_STAR_NAN
+ *   a NaN reaching G_q, v or lnL (a negative or non-finite lambda, say):  NaN in every output, SP_STAR_NAN
+ * No star affects another.  q outside 1 .. 32, K < 2 or a null required pointer: SP_ERR_INVALID, nothing launched; so
+ * is a lag grid whose bins do not fit the scatter's LDS beside the star's table (covpts + 4 > 1536; four copies of the
+ * bins up to covpts + 4 = 614, one beyond).  A host-only handle: SP_ERR_NO_DEVICE, before everything else.  S = 0: SP_OK,
+ * nothing touched.  All launches go to `stream`; nothing is synchronised.
+ * workspace_dev: sp_lnlike_grad_linear_workspace_bytes(h, S, K, q, covpts) bytes (0 for a null handle, S < 0, K < 2,
+ * q outside 1 .. 32 or covpts < 1): sp_lnlike_grad_workspace_bytes' system and inverse, a K x roundup(4 + q, 16) panel
+ * per star and its roundup(K, 64) / 64 slots, (q + 1)(q + 2) / 2 + q^2 + 3 q + 14 doubles per star and two per lower
+ * tile (each region rounded up to 256 bytes).                                                                         */
+size_t sp_lnlike_grad_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts);
+int sp_lnlike_grad_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const double *flux_dev /* [S, K] */,
+                          const double *diag_dev, const sp_star *stars_dev, const double *basis_dev /* [S, q, K] */,
+                          const double *basis_var_dev /* [S, q] */, int covpts, const double *tab_dev,
+                          const double *meanvar_dev, int temporal, int normalized, int norm_order, double zmax,
+                          void *workspace_dev, double *lnlike_dev /* [S] */, double *ybar_dev /* [S, covpts + 4] */,
+                          double *meanbar_dev /* [S] */, uint32_t *status_dev /* [S], may be NULL */,
+                          double *starbar_dev /* NULL or [S, SP_STARBAR] */,
+                          double *lambar_dev /* NULL or [S, q]: d lnL_s / d lambda_sj */,
+                          double *wmean_dev /* NULL or [S, q] */, void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

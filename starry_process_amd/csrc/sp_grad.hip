@@ -135,16 +135,23 @@ __global__ __launch_bounds__(256) void grad_matvec_reduce_kernel(int K, int ntr,
 // on the data variances: dC = D, <G, D> = (sum_m alpha_m^T D alpha_m - M tr(C^-1 D)) / 2 (AD, mt[4]) -- D and b 1 1^T are
 // added behind the normalisation, so none of the three passes through it.  starbar[s][2..5]; slots 0 and 1 are
 // grad_stars_kernel's.
-template <bool STARS>
+// LIN (sp_lnlike_grad_linear, sp_grad_linear.hip): q linear regressors marginalised out of ONE light curve,
+//   G~ = (B B^T - C^-1) / 2,  B = [alpha~, z_1 .. z_q] in vec[s][3 .. 3 + q]  (M = 1 + q columns, NV columns per star).
+// Every quadratic form above is summed over the columns of B; every term of C^-1 alone counts ONCE; the one form that
+// used C alpha = r, sum_b b^T C b, comes from the q x q stage (lin[s][0]: r^T alpha~ - |L_G^-T v|^2 + q - tr(G_q^-1)) and
+// so does lnL (lin[s][1]); d lnL / dr = -alpha~ alone (O1).  lin[s][2] != 0: a NaN reached the q x q system -- that
+// star and a ragged one are NaN in EVERY output (hcoef and w NaN: the scatter then writes NaN into the table's adjoint).
+template <bool STARS, bool LIN>
 __global__ __launch_bounds__(256) void grad_scalars_kernel(
-    int K, int Kr, int M, const double *__restrict__ Cinv, const double *__restrict__ flux,
+    int K, int Kr, int M, int NV, const double *__restrict__ lin, const double *__restrict__ Cinv,
+    const double *__restrict__ flux,
     const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef, const double *__restrict__ qv,
     const double *__restrict__ diag, const double *__restrict__ logdet, const int32_t *__restrict__ info,
     int normalized, int order, double zmax, double *__restrict__ vec, double *__restrict__ dots /* [S][M][2] */,
     double *__restrict__ lnlike, double *__restrict__ meanbar, double *__restrict__ hcoef, uint32_t *__restrict__ status,
     double *__restrict__ starbar /* [S][SP_STARBAR], STARS only */) {
   __shared__ double red[5][4];
-  const int s = blockIdx.x, tid = threadIdx.x, NV = M + 3;
+  const int s = blockIdx.x, tid = threadIdx.x;
   const sp_star st = stars[s];
   const SpCoef c = coef[s];
   const double shift = c.gpmean + st.baseline_mean;
@@ -177,13 +184,13 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
   // per light curve: r.a, a.p, a.q, a.1, a.D.a -- summed as the forms the adjoints need
   double R = 0.0, P2 = 0.0, Q2 = 0.0, PQ = 0.0, O2 = 0.0, O1 = 0.0, AD = 0.0;
   for (int m = 0; m < M; ++m) {
-    const double *al = V + (size_t)(3 + m) * K, *f = flux + ((size_t)s * M + m) * K;
+    const double *al = V + (size_t)(3 + m) * K, *f = LIN ? nullptr : flux + ((size_t)s * M + m) * K;
     double d[5] = {0, 0, 0, 0, 0};
     for (int i = tid; i < K; i += 256) {
       const double a = al[i];
       const double q = normalized ? qv[(size_t)s * K + i] : 0.0;
       const double D = diag ? diag[(size_t)s * K + i] : st.data_var;
-      d[0] += (f[i] - shift) * a;
+      if (!LIN) d[0] += (f[i] - shift) * a;
       d[1] += a * (1.0 - q);
       d[2] += a * q;
       d[3] += a;
@@ -195,7 +202,7 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
     Q2 += d[2] * d[2];
     PQ += d[1] * d[2];
     O2 += d[3] * d[3];
-    O1 += d[3];
+    if (!LIN || m == 0) O1 += d[3];
     AD += d[4];
     if (tid == 0) {
       dots[((size_t)s * M + m) * 2] = d[1];
@@ -203,7 +210,9 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
     }
   }
   __syncthreads();       // (dots: written by thread 0, read by all below -- through memory, same workgroup)
-  const double Kd = (double)K, Md = (double)M;
+  if (LIN) R = lin[(size_t)s * SP_GRAD_LIN_SCAL];
+  const bool linnan = LIN && lin[(size_t)s * SP_GRAD_LIN_SCAL + 2] != 0.0;
+  const double Kd = (double)K, Md = LIN ? 1.0 : (double)M;
   // (the sweep takes every cadence as valid: a ragged star -- 0 < nobs < K -- would get a silently wrong value from
   //  the K-long products above; it gets NaN and SP_STAR_NAN instead)
   const bool ragged = st.nobs > 0 && st.nobs < K;
@@ -250,16 +259,26 @@ __global__ __launch_bounds__(256) void grad_scalars_kernel(
     }
     const double u = 0.5 * (up - Md * cp), v = 0.5 * (vq - Md * cq);
     V[i] = bad ? 0.0 : gscale_u * u + gscale_v * v + wconst;
+    if (LIN && (ragged || (linnan && !bad))) V[i] = __builtin_nan("");
   }
   if (tid == 0) {
-    const double ll = -0.5 * R - 0.5 * Md * logdet[s] - 0.5 * Md * Kd * 1.8378770664093453;   // log(2 pi)
+    const double ll = LIN ? lin[(size_t)s * SP_GRAD_LIN_SCAL + 1]
+                          : -0.5 * R - 0.5 * Md * logdet[s] - 0.5 * Md * Kd * 1.8378770664093453;   // log(2 pi)
     const bool dead = bad || !(ll == ll);
     lnlike[s] = ragged ? __builtin_nan("") : (dead ? -INFINITY : ll);
     meanbar[s] = dead ? 0.0 : mbar;
     hcoef[s] = dead ? 0.0 : c1;           // (0: the scatter adds nothing for a star the likelihood rejects)
     if (status) status[s] = ((info && info[s]) ? SP_STAR_NOT_PD : 0u) | ((normalized && c.z > zmax) ? SP_STAR_ZMAX : 0u) |
                             (((!(ll == ll) && !bad) || ragged) ? SP_STAR_NAN : 0u);
-    if (STARS) {
+    if (LIN && (ragged || (!bad && (linnan || !(ll == ll))))) {
+      const double nanv = __builtin_nan("");
+      lnlike[s] = nanv;
+      meanbar[s] = nanv;
+      hcoef[s] = nanv;
+      if (status) status[s] |= SP_STAR_NAN;
+      double *sb = starbar + (size_t)s * SP_STARBAR;
+      sb[2] = sb[3] = sb[4] = sb[5] = nanv;
+    } else if (STARS) {
       double *sb = starbar + (size_t)s * SP_STARBAR;
       const double nanv = __builtin_nan("");
       sb[2] = ragged ? nanv : (dead ? 0.0 : O1);
@@ -588,13 +607,36 @@ int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cin
     SP_LAUNCH_CHECK();
   }
   if (starbar)
-    hipLaunchKernelGGL(grad_scalars_kernel<true>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+    hipLaunchKernelGGL((grad_scalars_kernel<true, false>), dim3(S), dim3(256), 0, st, K, Kr, M, M + 3, nullptr, Cinv, flux, stars,
                        (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
                        hcoef, status, starbar);
   else
-    hipLaunchKernelGGL(grad_scalars_kernel<false>, dim3(S), dim3(256), 0, st, K, Kr, M, Cinv, flux, stars,
+    hipLaunchKernelGGL((grad_scalars_kernel<false, false>), dim3(S), dim3(256), 0, st, K, Kr, M, M + 3, nullptr, Cinv, flux, stars,
                        (const SpCoef *)coef, qv, diag, logdet, info, normalized, order, zmax, vec, dots, lnlike, meanbar,
                        hcoef, status, starbar);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+// The sweep's scalars with q regressors marginalised out (grad_scalars_kernel<true, true>): vec [S][NV][K] holds C^-1 p,
+// C^-1 q, C^-1 1, then B = [alpha~, z_1 .. z_q]; lin [S][SP_GRAD_LIN_SCAL] the q x q stage's scalars; starbar is required
+int sp_launch_grad_scalars_linear(const SpProblem &P, const SpViews &V, int q, int NV, const double *lin,
+                                  const double *Cinv, const double *logdet, double *vec, double *dots, double *hcoef,
+                                  double *lnlike, double *meanbar, uint32_t *status, double *starbar) {
+  hipLaunchKernelGGL((grad_scalars_kernel<true, true>), dim3(P.S), dim3(256), 0, P.st, P.K, sp_roundup(P.K, SP_NB), 1 + q,
+                     NV, lin, Cinv, P.flux, P.stars, (const SpCoef *)V.coef(), V.qv(), P.diag, logdet, V.info(),
+                     P.normalized, P.order, P.zmax, vec, dots, lnlike, meanbar, hcoef, status, starbar);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+// the fixed-order sums behind a scatter over the lower tiles: the tiles' partial tables into ybar [S][np], their
+// (period, tau) pairs into starbar[s][0..1]
+int sp_launch_grad_tile_sums(int S, int K, int np, int ntiles, const sp_star *stars, const double *partial, double *ybar,
+                             const double *spart, double *starbar, hipStream_t st) {
+  hipLaunchKernelGGL(grad_bins_reduce_kernel, dim3((np + 63) / 64, S), dim3(256), 0, st, np, ntiles, partial, ybar);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_stars_reduce_kernel, dim3(S), dim3(256), 0, st, K, ntiles, stars, spart, starbar);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }

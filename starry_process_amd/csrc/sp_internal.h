@@ -601,6 +601,18 @@ int sp_launch_marginal_system(const SpProblem &P, const SpViews &V);
 int sp_launch_grad_front(const SpProblem &P, const SpViews &V, const double *Cinv, const double *logdet, double *vec,
                          double *dots, double *hcoef, double *partial, double *lnlike, double *meanbar, uint32_t *status,
                          double *starbar);
+// sp_grad.hip, for the sweep with linear regressors marginalised out (sp_grad_linear.hip).  The q x q stage's scalars per
+// star, lin [S][SP_GRAD_LIN_SCAL]: [0] sum_b b^T C b over the columns of B = [alpha~, z_1 .. z_q], [1] lnL, [2] nonzero: a
+// NaN reached G_q, v or lnL.  sp_launch_grad_scalars_linear: grad_scalars_kernel under "every term of C^-1 alone counts
+// once, every quadratic form is summed over B" on vec [S][NV][K] = C^-1 p, C^-1 q, C^-1 1, then B; starbar required.
+// sp_launch_grad_tile_sums: the fixed-order sums of the scatter's per-tile tables (partial [S][ntiles][np] -> ybar) and of
+// the period / tau pairs (spart [S][ntiles][2] -> starbar[s][0..1]).
+constexpr int SP_GRAD_LIN_SCAL = 4;
+int sp_launch_grad_scalars_linear(const SpProblem &P, const SpViews &V, int q, int NV, const double *lin,
+                                  const double *Cinv, const double *logdet, double *vec, double *dots, double *hcoef,
+                                  double *lnlike, double *meanbar, uint32_t *status, double *starbar);
+int sp_launch_grad_tile_sums(int S, int K, int np, int ntiles, const sp_star *stars, const double *partial, double *ybar,
+                             const double *spart, double *starbar, hipStream_t st);
 
 // sp_grad_cond.hip: the forward of the conditional branch's sweeps (gradient, Fisher information): the design matrices
 // A [S][Kr][N], B = A Sigma_y, the raw covariance (A Sigma_y A^T) o T into raw [S][Kr][Kr] (lower tiles; raw may be Cinv,

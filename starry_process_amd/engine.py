@@ -1582,6 +1582,43 @@ class Engine(object):
                 int(workspace.numel()), self._stream()))
         return lnlike, lnlike0, wmean, wcov, status
 
+    def grad_linear_workspace(self, S, K, q, covpts=300):
+        """Device scratch of ``lnlike_grad_linear`` (sp_lnlike_grad_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_lnlike_grad_linear_workspace_bytes(self._h, int(S), int(K), int(q), int(covpts)))
+
+    def lnlike_grad_linear(self, t, flux, stars_dev, basis, basis_var, tab, meanvar, diag=None, covpts=300,
+                           temporal=None, normalized=True, norm_order=20, zmax=0.023, workspace=None):
+        """Device half of the ensemble gradient with q linear regressors per star marginalised out
+        (sp_lnlike_grad_linear): t, flux [S, K]; basis [S, q, K], regressor j of star s along row j; basis_var [S, q],
+        the prior variances of the weights -> (lnlike [S], ybar [S, covpts + 4], meanbar [S], starbar [S, 6],
+        lambar [S, q], w_mean [S, q], status [S]): ``lnlike_linear``'s likelihood, its derivatives with respect to each
+        star's kernel table, flux mean and own parameters as ``lnlike_grad_marginal_stars`` returns them, with respect
+        to the prior variances themselves, and the posterior mean of the weights."""
+        torch = _torch()
+        S, K = t.shape
+        if tuple(flux.shape) != (S, K):
+            raise ValueError("`flux` must be (S, K): one light curve per star")
+        basis, basis_var = self.f64(basis), self.f64(basis_var)
+        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
+            raise ValueError("`basis` must be (S, q, K)")
+        q = int(basis.shape[1])
+        if not 1 <= q <= 32:
+            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
+        if tuple(basis_var.shape) != (S, q):
+            raise ValueError("`basis_var` must be (S, q)")
+        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        nbytes = int(self._L.sp_lnlike_grad_linear_workspace_bytes(self._h, S, K, q, int(covpts)))
+        ws = self._grad_scratch(nbytes, workspace)
+        out, ybar, mbar, sbar = self.empty(S), self.empty(S, covpts + 4), self.empty(S), self.empty(S, 6)
+        lbar, wmean = self.empty(S, q), self.empty(S, q)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        check(self._L.sp_lnlike_grad_linear(
+            self._h, S, K, q, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(basis),
+            self._p(basis_var), int(covpts), self._p(tab), self._p(meanvar), TEMPORAL[temporal], int(bool(normalized)),
+            int(norm_order), float(zmax), self._p(ws), self._p(out), self._p(ybar), self._p(mbar), self._p(status),
+            self._p(sbar), self._p(lbar), self._p(wmean), self._stream()))
+        return out, ybar, mbar, sbar, lbar, wmean, status
+
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 

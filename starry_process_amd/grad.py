@@ -358,16 +358,18 @@ def hyper_gradient(t, flux, data_var, r=defaults["r"], dr=defaults["dr"], a=defa
 _WRT = ("p", "tau", "baseline_mean", "baseline_var", "log_var")
 
 
-def _check_wrt(wrt, has_tau):
+def _check_wrt(wrt, has_tau, has_basis=False):
     """``wrt`` as a tuple of known names (None stays None); ValueError otherwise.  No device work."""
     if wrt is None:
         return None
     wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
     for name in wrt:
-        if name not in _WRT:
-            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT)))
+        if name not in _WRT and name != "basis_var":
+            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT + ("basis_var",))))
     if "tau" in wrt and not has_tau:
         raise ValueError("wrt: 'tau' needs a timescale (EnsembleGradient(..., tau=...))")
+    if "basis_var" in wrt and not has_basis:
+        raise ValueError("wrt: 'basis_var' needs regressors (EnsembleGradient(..., basis=..., basis_var=...))")
     return wrt
 
 
@@ -566,15 +568,35 @@ class EnsembleGradient(_MarginalSweep):
     quadrature rule differentiated with respect to its exponents -- the reference's analytic latitude derivatives,
     ops/include/latitude.h:21-173), and one table evaluation per parameter turns a tangent of the moments into the
     tangent of the table, on two more streams while the sweep runs.  With a spread of radii (dr) or exact=False:
-    central differences of the table (step h), as in round 4."""
+    central differences of the table (step h), as in round 4.
+
+    Linear regressors (``basis``, ``basis_var``): flux = process + U w + noise with w ~ N(0,
+    diag(basis_var)), the model of ``log_likelihood_linear_ensemble`` -- segment offsets, instrumental trends,
+    systematics vectors, marginalised without the K x K matrix.  ``basis`` (K, q) shared or (S, K, q), ``basis_var``
+    scalar, (q,) or (S, q), validated as that method validates them; one light curve per star.  The call then returns
+    the marginalised likelihood and ITS gradient (sp_lnlike_grad_linear), ``wrt`` also takes "basis_var" -- (S, q), the
+    derivative with respect to the prior variances themselves, finite at 0 -- and ``w_mean`` (S, q) holds the posterior
+    mean of the weights after a call.  ``upload_basis_var`` changes the variances without sending the basis again (a
+    sampler's step in lambda)."""
 
     def __init__(self, t, flux, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, baseline_mean=0.0,
                  normalized=True, covpts=None, tau=None, temporal_kernel="matern32", device=None, h=1.0e-4,
-                 upstream_kwargs=None, exact=True):
+                 upstream_kwargs=None, exact=True, basis=None, basis_var=None):
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim not in (2, 3):
             raise ValueError("flux must be (S, K) or (S, M, K)")
         M = flux.shape[1] if flux.ndim == 3 else 1
+        U = lam = None
+        if basis is None and basis_var is not None:
+            raise ValueError("`basis_var` needs a `basis`")
+        if basis is not None:
+            from .linear import check_regressors
+
+            if flux.ndim == 3:
+                raise ValueError("regressors are served for one light curve per star: `flux` must be (S, K) with a `basis`")
+            if basis_var is None:
+                raise ValueError("a `basis` needs the prior variances of its weights, `basis_var`")
+            U, lam = check_regressors(basis, basis_var, flux.shape[0], flux.shape[1])
         # (the star records carry no inclination on the marginal branch: make_stars' own default)
         stars, utab = self._setup(t, flux, ferr, p, None, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel,
                                   device)
@@ -582,10 +604,29 @@ class EnsembleGradient(_MarginalSweep):
         self._ntab = utab.shape[0]
         self._table = _torch().as_tensor(stars["table"].astype(np.int64), device=e.device)
         self._configure(covpts, normalized, h, upstream_kwargs, exact)
-        self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
+        self._basis = self._basis_var = self.w_mean = None
+        self._q = 0
+        if U is None:
+            self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
+        else:
+            self._q = U.shape[2]
+            self._basis = e.f64(np.ascontiguousarray(np.swapaxes(U, 1, 2)))      # [S, q, K]: a regressor along a row
+            self._basis_var = e.f64(lam)
+            self._ws = e.grad_linear_workspace(self.S, self.K, self._q, self._covpts)
+            _torch().cuda.synchronize(e.device)
         self.lnlike = None
 
     _WRT = _WRT
+
+    def upload_basis_var(self, basis_var):
+        """New prior variances of the regressors' weights -- scalar, (q,) or (S, q), finite and >= 0 -- for the calls
+        that follow; the basis stays on the device."""
+        from .linear import check_regressor_variances
+
+        if self._basis is None:
+            raise ValueError("`basis_var` needs regressors (EnsembleGradient(..., basis=..., basis_var=...))")
+        lam = check_regressor_variances(basis_var, self.S, self._q)
+        self._basis_var = self._e.f64(lam)
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
                  wrt=None):
@@ -599,18 +640,27 @@ class EnsembleGradient(_MarginalSweep):
         float, the sum over the stars (the constructor takes one timescale).  Where the ensemble shares a baseline (or a
         noise factor), as in calibrate/log_prob.py:7-106, the derivative with respect to the shared value is the sum of
         the array.  A star the likelihood rejects adds zeros.  d/dp is the derivative of the interpolant inside its
-        segments, as ``log_likelihood_with_grad``'s."""
+        segments, as ``log_likelihood_with_grad``'s.
+
+        With regressors: the likelihood and every derivative above are those of the marginalised model; wrt may hold
+        "basis_var": an array [S, q], d lnL_s / d of the prior variance of star s's regressor j.  New prior variances:
+        ``upload_basis_var`` ahead of the call."""
         import torch
 
-        wrt = _check_wrt(wrt, self._temporal is not None)
+        wrt = _check_wrt(wrt, self._temporal is not None, self._basis is not None)
         e = self._e
         # main stream: the tables at the point, then the sweep
         tab, mv, point = self._at_point(r, a, b, c, n, dr)
         with torch.cuda.stream(self._stream):
             sweep_kw = dict(diag=self._diag, covpts=self._covpts, temporal=self._temporal,
                             normalized=self._normalized, workspace=self._ws)
-            sbar = None
-            if wrt is None:
+            sbar = lbar = wmean = None
+            if self._basis is not None:
+                lnl, ybar, mbar, sbar, lbar, wmean, status = e.lnlike_grad_linear(
+                    self._t, self._flux, self._stars, self._basis, self._basis_var, tab, mv, **sweep_kw)
+                if wrt is None:
+                    sbar = None
+            elif wrt is None:
                 lnl, ybar, mbar, status = e.lnlike_grad_marginal(self._t, self._flux, self._stars, tab, mv, **sweep_kw)
             else:
                 lnl, ybar, mbar, sbar, status = e.lnlike_grad_marginal_stars(self._t, self._flux, self._stars, tab, mv,
@@ -631,15 +681,25 @@ class EnsembleGradient(_MarginalSweep):
                 parts.insert(0, (DY * Yb).sum(dim=(1, 2)) + (DM * Mb).sum(dim=1))
             if sbar is not None:
                 parts.append(sbar.reshape(-1))
+            if lbar is not None:
+                parts += [lbar.reshape(-1), wmean.reshape(-1)]
             host = torch.cat(parts).cpu().numpy()    # (on the main stream, which has waited for the others)
         ng = len(names)
         self.lnlike = host[ng:ng + self.S].copy()
         self.status = host[ng + self.S:ng + 2 * self.S].astype(np.uint32)
         total = float(self.lnlike.sum())
         grad = {k: float(v) for k, v in zip(names, host[:ng])}
+        if lbar is not None:
+            sq = self.S * self._q
+            self.w_mean = host[-sq:].reshape(self.S, self._q).copy()
+            if wrt is not None and "basis_var" in wrt:
+                grad["basis_var"] = host[-2 * sq:-sq].reshape(self.S, self._q).copy()
+            host = host[:-2 * sq]
         if sbar is not None:
             sb = host[ng + 2 * self.S:].reshape(self.S, -1)
             for k in wrt:
+                if k == "basis_var":
+                    continue
                 col = sb[:, self._WRT.index(k)]
                 grad[k] = float(col.sum()) if k == "tau" else col.copy()
         return total, grad
@@ -649,7 +709,8 @@ def ensemble_gradient(t, flux, ferr=1.0e-3, p=1.0, r=defaults["r"], a=defaults["
                       c=defaults["c"], n=defaults["n"], dr=None, wrt=None, **kwargs):
     """One-shot form of ``EnsembleGradient``: (sum of log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .});
     wrt: the per-star derivatives to return as well (``EnsembleGradient.__call__``)."""
-    wrt = _check_wrt(wrt, bool(kwargs.get("tau")))          # (before any data goes to the device)
+    # (before any data goes to the device)
+    wrt = _check_wrt(wrt, bool(kwargs.get("tau")), kwargs.get("basis") is not None)
     return EnsembleGradient(t, flux, ferr=ferr, p=p, **kwargs)(r=r, a=a, b=b, c=c, n=n, dr=dr, wrt=wrt)
 
 

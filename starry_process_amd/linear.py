@@ -6,6 +6,38 @@ import numpy as np
 __all__ = ["offset_basis", "polynomial_basis", "stack_bases"]
 
 
+def check_regressors(basis, basis_var, S, K):
+    """``basis`` (K, q) shared or (S, K, q) and ``basis_var`` scalar, (q,) or (S, q) as the ensemble calls with
+    regressors take them (``log_likelihood_linear_ensemble``, ``grad.EnsembleGradient``): returns (U (S, K, q),
+    lam (S, q) contiguous) in float64; ValueError for another shape, q outside 1 .. 32, a non-finite basis or a variance
+    that is negative or not finite.  Host work only."""
+    U = np.asarray(basis, dtype=np.float64)
+    if U.ndim == 2 and U.shape[0] == K:
+        U = np.broadcast_to(U, (S,) + U.shape)
+    if U.ndim != 3 or U.shape[0] != S or U.shape[1] != K:
+        raise ValueError("`basis` must be (K, q) or (S, K, q) with S = %d, K = %d, not %s"
+                         % (S, K, np.shape(basis)))
+    q = U.shape[2]
+    if not 1 <= q <= 32:
+        raise ValueError("1 to 32 regressors are served, not %d" % q)
+    if not np.all(np.isfinite(U)):
+        raise ValueError("`basis` must be finite")
+    return U, check_regressor_variances(basis_var, S, q)
+
+
+def check_regressor_variances(basis_var, S, q):
+    """``basis_var`` scalar, (q,) or (S, q), finite and >= 0 -> (S, q) contiguous float64; ValueError otherwise."""
+    lam = np.asarray(basis_var, dtype=np.float64)
+    if lam.ndim == 0 or lam.shape == (q,) or lam.shape == (S, q):
+        lam = np.ascontiguousarray(np.broadcast_to(lam, (S, q)))
+    else:
+        raise ValueError("`basis_var` must be a scalar, (q,) or (S, q) with S = %d, q = %d, not %s"
+                         % (S, q, lam.shape))
+    if not np.all(np.isfinite(lam)) or np.any(lam < 0):
+        raise ValueError("`basis_var` must be finite and >= 0")
+    return lam
+
+
 def _segment_edges(edges, K):
     """``edges`` as an int64 array 0 = e_0 < e_1 < ... < e_n = K (None: one segment)."""
     if edges is None:

@@ -900,25 +900,9 @@ class StarryProcess(object):
                                       "scalar or (S,), and the structured part as `basis`, `basis_var`")
         if K < 2:
             raise ValueError("the likelihood with regressors needs at least two cadences")
-        U = np.asarray(basis, dtype=np.float64)
-        if U.ndim == 2 and U.shape[0] == K:
-            U = np.broadcast_to(U, (S,) + U.shape)
-        if U.ndim != 3 or U.shape[0] != S or U.shape[1] != K:
-            raise ValueError("`basis` must be (K, q) or (S, K, q) with S = %d, K = %d, not %s"
-                             % (S, K, np.shape(basis)))
-        q = U.shape[2]
-        if not 1 <= q <= 32:
-            raise ValueError("1 to 32 regressors are served, not %d" % q)
-        if not np.all(np.isfinite(U)):
-            raise ValueError("`basis` must be finite")
-        lam = np.asarray(basis_var, dtype=np.float64)
-        if lam.ndim == 0 or lam.shape == (q,) or lam.shape == (S, q):
-            lam = np.ascontiguousarray(np.broadcast_to(lam, (S, q)))
-        else:
-            raise ValueError("`basis_var` must be a scalar, (q,) or (S, q) with S = %d, q = %d, not %s"
-                             % (S, q, lam.shape))
-        if not np.all(np.isfinite(lam)) or np.any(lam < 0):
-            raise ValueError("`basis_var` must be finite and >= 0")
+        from .linear import check_regressors
+
+        U, lam = check_regressors(basis, basis_var, S, K)
         Ut = np.ascontiguousarray(np.swapaxes(U, 1, 2))          # [S, q, K]: a regressor along a row
         e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
