@@ -699,6 +699,40 @@ int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, con
                      uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
                      void *stream);
 
+/* ---- Leave-block-out predictive checks with linear regressors marginalised out, either branch -------------------------
+ * sp_lbo_ensemble for the model of sp_lnlike_linear: flux_s = process + U_s w + noise, w ~ N(0, diag lambda_s).  The
+ * predictive distribution of a held-out block carries the uncertainty of the weights: with C = L L^T, r, Y = L^-T and
+ * y = Y^T r as sp_lbo_ensemble forms them, D = diag sqrt(lambda) and C~ = C + U Lambda U^T (never formed),
+ *   W = Y^T U,  G_q = I + D W^T W D = L_G L_G^T,  v = L_G^-1 D W^T y,  w_mean = D L_G^-T v,  T = W D L_G^-T,
+ *   y~ = y - W w_mean,  C~^-1 = Y (I - T T^T) Y^T,  alpha~ = C~^-1 r = Y y~,
+ *   block B:  G~ = (C~^-1)_BB = Y_B Y_B^T - (Y_B T)(Y_B T)^T = L_G~ L_G~^T,
+ *             cov_B = G~^-1,  mu_B = flux_B - G~^-1 alpha~_B,  u_B = L_G~^-1 alpha~_B,
+ *             lpd_B = -1/2 u_B^T u_B + sum log (L_G~)_ii - b/2 log 2 pi   (= lnL(all cadences) - lnL(those outside B)).
+ * rows_dev [S, 4, K]: mu, var, u and y~, the whitened DETRENDED residual L^-1 (r - U w_mean), whose covariance under the
+ * model is I - T T^T; lnlike_dev, lnlike0_dev, wmean_dev: those of sp_lnlike_linear.  Nothing is divided by lambda:
+ * lambda_j = 0 switches regressor j off exactly, and with every lambda zero mu, var, u, lpd and cov have the bits of
+ * sp_lbo_ensemble's.  basis_dev, basis_var_dev and q in 1 .. 32 as sp_lnlike_linear; the partition, the branches, the
+ * groups and the one synchronisation of `stream` as sp_lbo_ensemble.  No atomics, every sum in one fixed order: a star's
+ * bits do not depend on its neighbours, its position, the grouping or the run.
+ * Per star: not positive definite -> NaN everywhere, SP_STAR_NOT_PD;  ragged, or a NaN reaching G_q, v or a likelihood
+ *   (a negative, infinite or NaN lambda): NaN everywhere, SP_STAR_NAN;  z > zmax: lnlike = lnlike0 = -inf,
+ *   SP_STAR_ZMAX, rows and weights still computed;  a block whose G~ has a pivot that is not positive: NaN in that
+ *   block, SP_STAR_NAN on the star, its other blocks untouched.
+ * A null required pointer, K < 2, q outside 1 .. 32, a bad partition or a workspace too small for one star:
+ * SP_ERR_INVALID, nothing launched and nothing written.  A host-only handle: SP_ERR_NO_DEVICE, before everything else.
+ * S = 0: SP_OK.  sp_lbo_linear_workspace_bytes: 0 for arguments sp_lbo_linear refuses.                                */
+size_t sp_lbo_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts, int conditional, int nblocks);
+int sp_lbo_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const double *flux_dev /* [S, K] */,
+                  const double *diag_dev, const sp_star *stars_dev, const double *basis_dev /* [S, q, K] */,
+                  const double *basis_var_dev /* [S, q] */, int conditional, int covpts, const double *tab_dev,
+                  const double *meanvar_dev, const double *rta1_dev, int temporal, int normalized, int norm_order,
+                  double zmax, int nblocks, const int32_t *edges_dev /* [nblocks + 1] */,
+                  double *rows_dev /* [S, 4, K]: mu, var, u, y~ */, double *lpd_dev /* [S, nblocks] */,
+                  double *cov_dev /* NULL or [S, nblocks, bmax, bmax] */, double *lnlike_dev /* [S] */,
+                  double *lnlike0_dev /* [S] */, double *wmean_dev /* [S, q] */,
+                  uint32_t *status_dev /* [S], may be NULL */, void *workspace_dev, size_t workspace_bytes,
+                  void *stream);
+
 /* ---- The ensemble gradient with linear regressors marginalised out, marginal branch -----------------------------------
  * The reverse sweep of sp_lnlike_linear's value: sp_lnlike_grad_marginal_stars for the model flux_s = process + U_s w +
  * noise, w ~ N(0, diag lambda_s), one light curve per star (flux_dev [S, K]), every cadence valid.  basis_dev [S, q, K]

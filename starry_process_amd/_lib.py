@@ -109,6 +109,9 @@ PROTOTYPES = {
     "sp_lnlike_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
     "sp_lnlike_linear": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                               _V, _V, ctypes.c_size_t, _V]),
+    "sp_lbo_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I, _I]),
+    "sp_lbo_linear": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _I, _V, _V, _V, _V,
+                           _V, _V, _V, _V, _V, ctypes.c_size_t, _V]),
     "sp_lnlike_grad_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_lnlike_grad_linear": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V, _V,
                                    _V, _V, _V, _V]),

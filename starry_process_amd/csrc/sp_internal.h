@@ -668,6 +668,28 @@ struct SpLinLayout {
   size_t total;
 };
 SpLinLayout sp_lin_layout(const sp_handle *h, int S, int K, int q, int conditional);
+// sp_linear.hip: the Gram pass over 1 + q rows [y; W^T] of every star and the q x q finish, as sp_lnlike_linear runs
+// them.  Row a of star s at rows + s * sstride + a * rstride.  diag: L_ii of star s at diag + s * dstride + i * dstep, or
+// null, and then logdet [S] = log det C goes to the finish.  gpart: sp_lin_gpart_bytes(S, K, q) of scratch.  mix (may be
+// null) [S][32][32]: M = D L_G^-T, upper triangular, zeros around it, NaN for a star that holds NaN.
+size_t sp_lin_gpart_bytes(int S, int K, int q);
+int sp_launch_lin_gram(int S, int K, int q, const double *rows, long sstride, long rstride, const double *diag,
+                       long dstride, long dstep, const sp_star *stars, const int32_t *info, double *gpart,
+                       hipStream_t st);
+int sp_launch_lin_finish(int S, int K, int q, const double *gpart, const double *logdet, const double *bvar,
+                         const sp_star *stars, const SpCoef *coef, const int32_t *info, int normalized, double zmax,
+                         double *lnlike, double *lnlike0, double *wmean, double *wcov, double *mix, uint32_t *status,
+                         hipStream_t st);
+// sp_lbo.hip: what the leave-block-out sweep with regressors (sp_lbo_linear.hip) shares with sp_lbo_ensemble.  A block
+// holds at most SP_LBO_R cadences; sp_lbo_count_bands: the bands of a checked partition e[0 .. nblocks];
+// sp_launch_lbo_bands: the same bands on the device, bands [nblocks + 1]; sp_launch_lbo_band_linear: lbo_band_kernel with
+// the downdate G~ = Y_B Y_B^T - Z_B Z_B^T, Z_B = Y_B T, T [S][K][32] (columns >= q zero), alpha against row 3 of `rows`.
+constexpr int SP_LBO_R = 64;
+int sp_lbo_count_bands(const int32_t *e, int nblocks);
+int sp_launch_lbo_bands(int nblocks, const int32_t *edges, int32_t *bands, hipStream_t st);
+int sp_launch_lbo_band_linear(int nbands, int S, int K, const SpLooSystem &Y, int nblocks, int bmax, const int32_t *edges,
+                              const int32_t *bands, const double *flux, const sp_star *stars, double *rows, double *lpd,
+                              double *cov, int32_t *bad, int q, const double *T, hipStream_t st);
 // sp_lnlike.hip: the tangents of the design matrices sp_launch_design left in place (V's cs, vrow, theta), Kr rows per
 // star: dA_inc = d A / d inc per radian (dR [S][NWIG], dv [S][N]: scratch), dA_per = d A / d period; either may be null
 int sp_launch_design_tangents(sp_handle *h, const SpViews &V, const sp_star *stars, const double *rta1, const double *t,

@@ -18,6 +18,10 @@
 // var = the columns' squared norms; cov = W^T W of the round's blocks by the four wavefronts together.  Only rows and
 // columns < K of Y are read and nothing left of the diagonal (loo_pair, sp_sweep.h).  Every sum has a fixed order and
 // every output element one writer: no atomics.
+//
+// lbo_band_kernel<true> is the same kernel for the model with linear regressors marginalised out (sp_lbo_linear.hip,
+// which launches it through sp_launch_lbo_band_linear): alpha against y~, and G downdated by Z_B Z_B^T, Z_B = Y_B T
+// accumulated beside G in the Gram pass.  The instantiation without the flag performs the operations it always did.
 #include <vector>
 
 #include "sp_internal.h"
@@ -25,12 +29,15 @@
 
 namespace {
 
-constexpr int LBO_R = 64;        // rows of a band: the widest block, and the edge of the Gram matrix
+constexpr int LBO_R = SP_LBO_R;  // rows of a band: the widest block, and the edge of the Gram matrix
 constexpr int LBO_CB = 32;       // columns of a tile of Y
 constexpr int LBO_TLD = 34;      // row stride of a tile in LDS: rows 16 apart in a fragment read fall on distinct banks
 constexpr int LBO_GLD = 65;      // row stride of the Gram matrix in LDS
 constexpr int LBO_SM = 2 * LBO_R * LBO_TLD;   // two tiles, then (the tiles done with) the Gram matrix: 34 816 bytes
 static_assert(LBO_SM >= LBO_R * LBO_GLD, "the Gram matrix takes the tiles' place");
+constexpr int LBO_Q = 32;        // LIN: columns of T (the regressors, padded with zeros)
+constexpr int LBO_TT = LBO_Q * LBO_TLD;       // LIN: a tile of T in LDS, transposed: [column of T][column of Y]
+static_assert(LBO_SM >= LBO_R * LBO_TLD, "Z_B takes the tiles' place before the Gram matrix does");
 typedef double lbo_d4 __attribute__((ext_vector_type(4)));
 
 // the bands of a partition: consecutive blocks while their rows fit LBO_R.  bands[i] = first block of band i,
@@ -49,15 +56,17 @@ __global__ void lbo_bands_kernel(int nblocks, const int32_t *__restrict__ edges,
   }
   bands[nb + 1] = nblocks;
 }
-int lbo_count_bands(const std::vector<int32_t> &e) {
+}  // namespace
+int sp_lbo_count_bands(const int32_t *e, int nblocks) {
   int nb = 0, rows = 0;
-  for (size_t j = 0; j + 1 < e.size(); ++j) {
+  for (int j = 0; j < nblocks; ++j) {
     const int w = e[j + 1] - e[j];
     if (rows + w > LBO_R) ++nb, rows = 0;
     rows += w;
   }
   return nb + 1;
 }
+namespace {
 
 // sum over i = i0 .. b - 1, i >= c, of W[i][a] W[i][c], W = L_G^-1 kept transposed at Wt (Wt[c * LBO_GLD + i] = W[i][c]),
 // in the order of i: an entry of cov = W^T W (a <= c); a == c: the variance, the same bits as the diagonal of cov
@@ -70,7 +79,11 @@ __device__ __forceinline__ double lbo_dot(const double *__restrict__ Wt, int a, 
 }
 
 // grid (nbands, S), 256 threads.  rows [S][4][K]: mu, var, u, white (white already written); lpd [S][nblocks];
-// cov null or [S][nblocks][bmax][bmax]; bad [S][nblocks]: 1 where the block's G had a pivot that is not positive
+// cov null or [S][nblocks][bmax][bmax]; bad [S][nblocks]: 1 where the block's G had a pivot that is not positive.
+// LIN (sp_lbo_linear.hip: q regressors marginalised out): row 3 of `rows` holds y~ = y - T v, and the Gram pass also
+// stages the tile of Tm [S][K][LBO_Q] that belongs to each tile of Y and accumulates Z_B = Y_B T beside G; G is
+// downdated by Z_B Z_B^T before the blocks are factored: G~ = (C~^-1)_BB.  Without LIN, q and Tm are not read.
+template <bool LIN>
 __global__ __launch_bounds__(256) void lbo_band_kernel(int K, long ld, long stride, int nblocks, int bmax,
                                                        const int32_t *__restrict__ edges,
                                                        const int32_t *__restrict__ bands,
@@ -78,8 +91,10 @@ __global__ __launch_bounds__(256) void lbo_band_kernel(int K, long ld, long stri
                                                        const sp_star *__restrict__ stars,
                                                        const int32_t *__restrict__ info, double *__restrict__ rows,
                                                        double *__restrict__ lpd, double *__restrict__ cov,
-                                                       int32_t *__restrict__ bad) {
+                                                       int32_t *__restrict__ bad, int q,
+                                                       const double *__restrict__ Tm) {
   __shared__ __attribute__((aligned(16))) double sm[LBO_SM];
+  __shared__ double tsm[LIN ? 2 * LBO_TT : 1];
   __shared__ double wb[2][LBO_CB];
   __shared__ double al[LBO_R], ub[LBO_R], dg[LBO_R];
   __shared__ int boff[LBO_R + 1], okf[4];
@@ -115,6 +130,7 @@ __global__ __launch_bounds__(256) void lbo_band_kernel(int K, long ld, long stri
   // loads: thread -> the column pair tid & 15 of the rows (tid >> 4) + 16 i of a tile
   const int lp = tid & 15, lr = tid >> 4;
   loo_v2 yreg[4];
+  loo_v2 treg[2];                                    // LIN: the pairs tid and tid + 256 of the 32 x 16 pairs of T's tile
   double wreg = 0.0;
   auto load = [&](int tt) {
     const int j = cbeg + LBO_CB * tt + 2 * lp;
@@ -127,16 +143,35 @@ __global__ __launch_bounds__(256) void lbo_band_kernel(int K, long ld, long stri
       const int c = cbeg + LBO_CB * tt + tid;
       wreg = c < K ? white[c] : 0.0;
     }
+    if constexpr (LIN) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int e = tid + 256 * i, c = cbeg + LBO_CB * tt + (e >> 4);
+        treg[i] = c < K ? *reinterpret_cast<const loo_v2 *>(Tm + ((size_t)s * K + c) * LBO_Q + 2 * (e & 15))
+                        : loo_v2{0.0, 0.0};
+      }
+    }
   };
   auto store = [&](int buf) {
     double *T = sm + buf * (LBO_R * LBO_TLD);
 #pragma unroll
     for (int i = 0; i < 4; ++i) *reinterpret_cast<loo_v2 *>(T + (lr + 16 * i) * LBO_TLD + 2 * lp) = yreg[i];
     if (tid < LBO_CB) wb[buf][tid] = wreg;
+    if constexpr (LIN) {
+      double *Tt = tsm + buf * LBO_TT;
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int e = tid + 256 * i;
+        Tt[(2 * (e & 15)) * LBO_TLD + (e >> 4)] = treg[i].x;
+        Tt[(2 * (e & 15) + 1) * LBO_TLD + (e >> 4)] = treg[i].y;
+      }
+    }
   };
   lbo_d4 acc[4];
 #pragma unroll
   for (int n = 0; n < 4; ++n) acc[n] = lbo_d4{0.0, 0.0, 0.0, 0.0};
+  lbo_d4 zacc[2] = {lbo_d4{0.0, 0.0, 0.0, 0.0}, lbo_d4{0.0, 0.0, 0.0, 0.0}};   // LIN: the wavefront's 16 rows of Z_B
+  const bool zwide = q > 16;                         // (uniform: one accumulator serves q <= 16)
   double asum = 0.0;
   const int fr = lane & 15, fq = lane >> 4;          // fragment row and k of this lane
   const int arow = tid >> 2, apart = tid & 3;        // alpha: row tid / 4, the columns 8 (tid % 4) .. + 7 of a tile
@@ -154,10 +189,34 @@ __global__ __launch_bounds__(256) void lbo_band_kernel(int K, long ld, long stri
         const double b = T[(16 * n + fr) * LBO_TLD + 4 * kk + fq];
         acc[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[n], 0, 0, 0);
       }
+      if constexpr (LIN) {
+        const double *Tt = tsm + (tt & 1) * LBO_TT;
+        zacc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Tt[fr * LBO_TLD + 4 * kk + fq], zacc[0], 0, 0, 0);
+        if (zwide)
+          zacc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Tt[(16 + fr) * LBO_TLD + 4 * kk + fq], zacc[1], 0, 0, 0);
+      }
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) asum = fma(T[arow * LBO_TLD + 8 * apart + k], wb[tt & 1][8 * apart + k], asum);
     if (tt + 1 < ntiles) store((tt + 1) & 1);
+    __syncthreads();
+  }
+  if constexpr (LIN) {
+    // Z_B into the tiles' place (every wavefront is past the last tile's barrier), then each wavefront takes Z_B Z_B^T
+    // off its own block row of G, in the order of T's columns
+    double *Zs = sm;
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) Zs[(16 * wave + fq + 4 * r) * LBO_TLD + 16 * n + fr] = zacc[n][r];
+    __syncthreads();
+#pragma unroll
+    for (int kk = 0; kk < LBO_Q / 4; ++kk) {
+      const double a = -Zs[(16 * wave + fr) * LBO_TLD + 4 * kk + fq];
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+        acc[n] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, Zs[(16 * n + fr) * LBO_TLD + 4 * kk + fq], acc[n], 0, 0, 0);
+    }
     __syncthreads();
   }
   // the Gram matrix takes the tiles' place (every wavefront is past the last tile's barrier)
@@ -317,6 +376,21 @@ LboLayout lbo_layout(const sp_handle *h, int S, int K, int conditional, int nblo
 
 }  // namespace
 
+int sp_launch_lbo_bands(int nblocks, const int32_t *edges, int32_t *bands, hipStream_t st) {
+  hipLaunchKernelGGL(lbo_bands_kernel, dim3(1), dim3(64), 0, st, nblocks, edges, bands);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+int sp_launch_lbo_band_linear(int nbands, int S, int K, const SpLooSystem &Y, int nblocks, int bmax, const int32_t *edges,
+                              const int32_t *bands, const double *flux, const sp_star *stars, double *rows, double *lpd,
+                              double *cov, int32_t *bad, int q, const double *T, hipStream_t st) {
+  hipLaunchKernelGGL(lbo_band_kernel<true>, dim3(nbands, S), dim3(256), 0, st, K, Y.ld, Y.stride, nblocks, bmax, edges,
+                     bands, Y.sys, flux, stars, Y.info, rows, lpd, cov, bad, q, T);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
 extern "C" {
 
 size_t sp_lbo_workspace_bytes(sp_handle *h, int S, int K, int covpts, int conditional, int nblocks) {
@@ -348,15 +422,14 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
     if (w < 1 || w > LBO_R) return SP_ERR_INVALID;
     bmax = w > bmax ? w : bmax;
   }
-  const int nbands = lbo_count_bands(e);
+  const int nbands = sp_lbo_count_bands(e.data(), nblocks);
   const int group =
       sp_star_group(S, workspace_bytes, [&](int n) { return lbo_layout(h, n, K, conditional, nblocks).total; });
   if (!group) return SP_ERR_INVALID;
   const LboLayout G = lbo_layout(h, group, K, conditional, nblocks);
   char *base = static_cast<char *>(workspace_dev);
   int32_t *bands = at<int32_t>(base, G.bands), *bad = at<int32_t>(base, G.bad);
-  hipLaunchKernelGGL(lbo_bands_kernel, dim3(1), dim3(64), 0, st, nblocks, edges_dev, bands);
-  SP_LAUNCH_CHECK();
+  if (const int rc = sp_launch_lbo_bands(nblocks, edges_dev, bands, st)) return rc;
   const SpProblem Q = sp_make_problem(h, conditional, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev,
                                       meanvar_dev, temporal, normalized, norm_order, zmax, stream);
   return sp_for_star_groups(S, group, [&](int s0, int n) -> int {
@@ -366,8 +439,9 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
     SpLooSystem Y;
     const int rc = sp_loo_open(h, P, conditional ? 1 : 0, rta1_dev, base + G.loo, rows + 3 * (size_t)K, 4 * (long)K, &Y);
     if (rc) return rc;
-    hipLaunchKernelGGL(lbo_band_kernel, dim3(nbands, n), dim3(256), 0, st, K, Y.ld, Y.stride, nblocks, bmax, edges_dev,
-                       bands, Y.sys, P.flux, P.stars, Y.info, rows, lpd, cov, bad);
+    hipLaunchKernelGGL(lbo_band_kernel<false>, dim3(nbands, n), dim3(256), 0, st, K, Y.ld, Y.stride, nblocks, bmax,
+                       edges_dev, bands, Y.sys, P.flux, P.stars, Y.info, rows, lpd, cov, bad, 0,
+                       (const double *)nullptr);
     SP_LAUNCH_CHECK();
     hipLaunchKernelGGL(lbo_finish_kernel, dim3(n), dim3(256), 0, st, K, nblocks, rows, P.stars, Y.coef, Y.info, Y.logdet,
                        bad, normalized, zmax, lnlike_dev + s0, status_dev ? status_dev + s0 : nullptr);

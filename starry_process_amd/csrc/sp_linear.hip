@@ -12,7 +12,8 @@
 // place; one pass along those rows gives their (1 + q) x (1 + q) Gram matrix and sum log L_ii, and one wavefront per
 // star finishes the q x q system in LDS.  Every sum has a fixed order (registers, LDS, the chunks of a star one after
 // another), every output element one writer: no atomics, the same bits run after run, a star's bits independent of its
-// neighbours, its position and the grouping.
+// neighbours, its position and the grouping.  The Gram pass and the finish take the rows' base pointer and strides and are
+// exported (sp_launch_lin_gram, sp_launch_lin_finish): sp_lbo_linear.hip runs them on its own rows [y; W^T].
 #include "sp_internal.h"
 #include "sp_sweep.h"
 
@@ -61,9 +62,11 @@ __global__ __launch_bounds__(256) void lin_rows_kernel(int K, int q, int Kr, int
 // of sum log L_ii: gpart[s][chunk][pair], pairs (a, b), a >= b, counted row by row, then the logarithms' sum.  Each
 // riding row is read once, along the row, LIN_TC columns at a time into LDS; a thread owns up to three pairs and adds
 // their products in the order of the columns.  A star that did not factor or is ragged is left to the finish (NaN).
-// grid (nsplit, S)
-__global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int Kp, int chunk, const double *__restrict__ sys,
-                                                       const sp_star *__restrict__ stars,
+// Row a of star s lies at rows + s * sstride + a * rstride; L_ii of star s at diag + s * dstride + i * dstep (diag null:
+// the logarithms' sum is left zero and the finish takes log det C from its caller).  grid (nsplit, S)
+__global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int chunk, const double *__restrict__ rows,
+                                                       long sstride, long rstride, const double *__restrict__ diag,
+                                                       long dstride, long dstep, const sp_star *__restrict__ stars,
                                                        const int32_t *__restrict__ info, double *__restrict__ gpart) {
   __shared__ double T[LIN_RMAX * LIN_TLD];
   __shared__ double red[4];
@@ -71,8 +74,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int Kp, int
   const sp_star st = stars[s];
   if (info[s] != 0 || (st.nobs > 0 && st.nobs < K)) return;
   const int c0 = blockIdx.x * chunk, c1 = c0 + chunk < K ? c0 + chunk : K;
-  const double *S0 = sys + (size_t)s * Kp * Kp;
-  const double *Y = S0 + (size_t)K * Kp;
+  const double *Y = rows + (size_t)s * sstride;
   int pa[3], pb[3];
   double acc[3] = {0.0, 0.0, 0.0};
 #pragma unroll
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int Kp, int
     __syncthreads();
     for (int e = tid; e < R * LIN_TC; e += 256) {
       const int a = e / LIN_TC, c = e % LIN_TC;
-      T[a * LIN_TLD + c] = c < n ? Y[(size_t)a * Kp + t0 + c] : 0.0;
+      T[a * LIN_TLD + c] = c < n ? Y[(size_t)a * rstride + t0 + c] : 0.0;
     }
     __syncthreads();
 #pragma unroll
@@ -104,22 +106,26 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int Kp, int
   for (int k = 0; k < 3; ++k)
     if (tid + 256 * k < np) out[tid + 256 * k] = acc[k];
   double lg = 0.0;
-  for (int i = c0 + tid; i < c1; i += 256) lg += log(S0[(size_t)i * Kp + i]);
+  if (diag)
+    for (int i = c0 + tid; i < c1; i += 256) lg += log(diag[(size_t)s * dstride + (size_t)i * dstep]);
   lg = sp_block_sum_256(lg, red);
   if (tid == 0) out[np] = lg;
 }
 
 // The finish, one wavefront per star: the chunks' parts added in their order, G = I + D W^T W D and h = D W^T y, the
 // Cholesky factor of G in LDS (a lane per row), v, the two likelihoods, w_mean and, with wcov, L_G^-1 (a lane per
-// column) and w_cov = D L_G^-T L_G^-1 D -- its lower triangle, mirrored: exactly symmetric.  grid (S)
+// column) and w_cov = D L_G^-T L_G^-1 D -- its lower triangle, mirrored: exactly symmetric.  logdet (may be null):
+// log det C per star, in place of twice the chunks' sums of logarithms.  mix (may be null) [S][32][32]: M = D L_G^-T, upper
+// triangular, zeros around it (w_mean = M v; sp_lbo_linear.hip mixes the rows of W^T with it).  grid (S)
 __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit, const double *__restrict__ gpart,
+                                                        const double *__restrict__ logdet,
                                                         const double *__restrict__ bvar,
                                                         const sp_star *__restrict__ stars,
                                                         const SpCoef *__restrict__ coef,
                                                         const int32_t *__restrict__ info, int normalized, double zmax,
                                                         double *__restrict__ lnlike, double *__restrict__ lnlike0,
                                                         double *__restrict__ wmean, double *__restrict__ wcov,
-                                                        uint32_t *__restrict__ status) {
+                                                        double *__restrict__ mix, uint32_t *__restrict__ status) {
   constexpr int LD = LIN_RMAX + 1;
   __shared__ double Mg[LIN_RMAX * LD];     // the Gram matrix of the riding rows, both triangles
   __shared__ double G[LIN_QMAX * LD];      // G, then L_G (lower triangle)
@@ -133,8 +139,11 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
   const bool rej = normalized && coef[s].z > zmax;
   const double nanv = __builtin_nan("");
   double *wm = wmean + (size_t)s * q, *wc = wcov ? wcov + (size_t)s * q * q : nullptr;
+  double *mx = mix ? mix + (size_t)s * LIN_QMAX * LIN_QMAX : nullptr;
   if (ragged || notpd) {
     if (lane < q) wm[lane] = nanv;
+    if (mx)
+      for (int e = lane; e < LIN_QMAX * LIN_QMAX; e += 64) mx[e] = nanv;
     if (wc)
       for (int e = lane; e < q * q; e += 64) wc[e] = nanv;
     if (lane == 0) {
@@ -156,7 +165,7 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
   if (lane == 0) {
     double lg = 0.0;
     for (int c = 0; c < nsplit; ++c) lg += P[(size_t)c * (np + 1) + np];
-    sc[0] = lg;
+    sc[0] = logdet ? 0.5 * logdet[s] : lg;
     bad = 0;
   }
   if (lane < q) dv[lane] = sqrt(bvar[(size_t)s * q + lane]);
@@ -207,7 +216,7 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
       else if (lane < i) hk -= G[i * LD + lane] * xi;
     }
   }
-  if (chol_ok && wc && lane < q) {
+  if (chol_ok && (wc || mx) && lane < q) {
     // column `lane` of L_G^-1
     const int j = lane;
     X[j * LD + j] = 1.0 / G[j * LD + j];
@@ -235,6 +244,11 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
       wc[(size_t)j * q + i] = v;
     }
   }
+  if (mx)
+    for (int e = lane; e < LIN_QMAX * LIN_QMAX; e += 64) {
+      const int a = e / LIN_QMAX, c = e % LIN_QMAX;
+      mx[e] = isnan_ ? nanv : (a <= c && c < q ? dv[a] * X[c * LD + a] : 0.0);
+    }
   if (lane == 0) {
     lnlike[s] = rej ? -INFINITY : (isnan_ ? nanv : ll);
     lnlike0[s] = rej ? -INFINITY : (isnan_ ? nanv : ll0);
@@ -244,16 +258,42 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
 
 }  // namespace
 
+size_t sp_lin_gpart_bytes(int S, int K, int q) {
+  return sizeof(double) * (size_t)S * lin_nsplit(K) * (lin_npair(q) + 1);
+}
+
 SpLinLayout sp_lin_layout(const sp_handle *h, int S, int K, int q, int conditional) {
   SpLinLayout G;
   SpCarve c;
   // the likelihood's lean layout with a system of 1 + q riding rows (no K identity rows: sp_sweep_views would reserve
   // them), then the chunks' Gram parts
   G.lik = c.take(make_layout(h, S, K, 1 + q, true, true).total);
-  G.gpart = c.take(sizeof(double) * (size_t)S * lin_nsplit(K) * (lin_npair(q) + 1));
+  G.gpart = c.take(sp_lin_gpart_bytes(S, K, q));
   G.cond.take(c, h, S, K, conditional);
   G.total = c.off;
   return G;
+}
+
+// the exported launchers (sp_internal.h): the leave-block-out sweep with regressors (sp_lbo_linear.hip) runs the same two
+// kernels on its own rows [y; W^T]
+int sp_launch_lin_gram(int S, int K, int q, const double *rows, long sstride, long rstride, const double *diag,
+                       long dstride, long dstep, const sp_star *stars, const int32_t *info, double *gpart,
+                       hipStream_t st) {
+  const int nsplit = lin_nsplit(K), chunk = nsplit == 1 ? K : LIN_CHUNK;
+  hipLaunchKernelGGL(lin_gram_kernel, dim3(nsplit, S), dim3(256), 0, st, K, q, chunk, rows, sstride, rstride, diag, dstride,
+                     dstep, stars, info, gpart);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
+int sp_launch_lin_finish(int S, int K, int q, const double *gpart, const double *logdet, const double *bvar,
+                         const sp_star *stars, const SpCoef *coef, const int32_t *info, int normalized, double zmax,
+                         double *lnlike, double *lnlike0, double *wmean, double *wcov, double *mix, uint32_t *status,
+                         hipStream_t st) {
+  hipLaunchKernelGGL(lin_finish_kernel, dim3(S), dim3(64), 0, st, K, q, lin_nsplit(K), gpart, logdet, bvar, stars, coef, info,
+                     normalized, zmax, lnlike, lnlike0, wmean, wcov, mix, status);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
 }
 
 namespace {
@@ -277,13 +317,11 @@ int lin_group(sp_handle *h, const SpProblem &Q, int q, int conditional, const do
   SP_LAUNCH_CHECK();
   // (no fused reduction: y and the rows of W^T stay in the rows K .. K + q)
   if ((rc = sp_launch_cholesky_systems(h, V.sys(), S, K, Kp, V.info(), V.invL(), st))) return rc;
-  const int nsplit = lin_nsplit(K), chunk = nsplit == 1 ? K : LIN_CHUNK;
-  hipLaunchKernelGGL(lin_gram_kernel, dim3(nsplit, S), dim3(256), 0, st, K, q, Kp, chunk, V.sys(), Q.stars, V.info(), gpart);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lin_finish_kernel, dim3(S), dim3(64), 0, st, K, q, nsplit, gpart, bvar, Q.stars,
-                     (const SpCoef *)V.coef(), V.info(), Q.normalized, Q.zmax, lnlike, lnlike0, wmean, wcov, status);
-  SP_LAUNCH_CHECK();
-  return SP_OK;
+  if ((rc = sp_launch_lin_gram(S, K, q, V.sys() + (size_t)K * Kp, (long)Kp * Kp, Kp, V.sys(), (long)Kp * Kp, Kp + 1, Q.stars,
+                               V.info(), gpart, st)))
+    return rc;
+  return sp_launch_lin_finish(S, K, q, gpart, nullptr, bvar, Q.stars, (const SpCoef *)V.coef(), V.info(), Q.normalized,
+                              Q.zmax, lnlike, lnlike0, wmean, wcov, nullptr, status, st);
 }
 
 }  // namespace

@@ -1582,6 +1582,65 @@ class Engine(object):
                 int(workspace.numel()), self._stream()))
         return lnlike, lnlike0, wmean, wcov, status
 
+    def lbo_linear_workspace(self, S, K, q, covpts=300, conditional=False, nblocks=1):
+        """Device scratch that holds ``S`` stars of ``lbo_linear`` at once (sp_lbo_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_lbo_linear_workspace_bytes(self._h, int(S), int(K), int(q), int(covpts),
+                                                                   int(bool(conditional)), int(nblocks)))
+
+    def lbo_linear(self, t, flux, stars, edges, basis, basis_var, diag=None, conditional=False, covpts=300, tab=None,
+                   meanvar=None, rta1=None, temporal=None, normalized=True, norm_order=20, zmax=0.023,
+                   return_cov=False, workspace=None, max_workspace_bytes=None):
+        """Leave-block-out predictive checks of S light curves with q linear regressors per star marginalised out
+        (sp_lbo_linear): ``lbo_ensemble`` for the model of ``lnlike_linear``.  t, flux, stars, edges, diag and the
+        branch arguments as ``lbo_ensemble``; basis [S, q, K] and basis_var [S, q] as ``lnlike_linear``.  Returns
+        (rows [S, 4, K], lpd [S, nblocks], cov [S, nblocks, bmax, bmax] or None, lnlike [S], lnlike0 [S], w_mean
+        [S, q], status [S]) on the device; the rows: the blocks' predictive means, variances and whitened residuals u
+        -- the uncertainty of the weights included -- and the whitened DETRENDED residual L^-1 (r - U w_mean) of the
+        whole light curve.  lnlike, lnlike0 and w_mean are ``lnlike_linear``'s.  A star whose covariance does not
+        factor, a ragged one, or one with a variance that is negative or not finite holds NaN; a normalised star with
+        z > zmax has lnlike = lnlike0 = -inf and finite rows.  workspace: a byte tensor (``lbo_linear_workspace``);
+        ``max_workspace_bytes`` caps the scratch allocated here instead.  A workspace that holds fewer than S stars
+        makes the call work through them in groups, with the same bits."""
+        torch = _torch()
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
+                                                                     "leave-block-out with regressors")
+        S, K = flux.shape
+        basis, basis_var = self.f64(basis), self.f64(basis_var)
+        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
+            raise ValueError("`basis` must be (S, q, K)")
+        q = int(basis.shape[1])
+        if not 1 <= q <= 32:
+            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
+        if tuple(basis_var.shape) != (S, q):
+            raise ValueError("`basis_var` must be (S, q)")
+        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        if isinstance(edges, torch.Tensor):
+            # (a device tensor is the caller's word: sp_lbo_linear checks it; its widest block sizes `cov`)
+            ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
+            if ed.dim() != 1 or ed.numel() < 2:
+                raise ValueError("`edges` must be a 1-D array of at least two block edges")
+            bmax = int((ed[1:] - ed[:-1]).max()) if return_cov else 0
+        else:
+            eh = block_edges(edges, K)
+            bmax = int(np.diff(eh).max())
+            ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
+        nb = int(ed.numel()) - 1
+        rows, lpd = self.empty(S, 4, K), self.empty(S, nb)
+        lnlike, lnlike0, wmean = self.empty(S), self.empty(S), self.empty(S, q)
+        cov = self.empty(S, nb, bmax, bmax) if return_cov else None
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S > 0:
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_lbo_linear_workspace_bytes(self._h, n, K, q, int(covpts), conditional, nb), S,
+                workspace, max_workspace_bytes)
+            check(self._L.sp_lbo_linear(
+                self._h, S, K, q, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(basis),
+                self._p(basis_var), conditional, int(covpts), self._p(tab), self._p(meanvar), self._p(rta1),
+                TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), nb, self._p(ed), self._p(rows),
+                self._p(lpd), self._p(cov), self._p(lnlike), self._p(lnlike0), self._p(wmean), self._p(status),
+                self._p(workspace), int(workspace.numel()), self._stream()))
+        return rows, lpd, cov, lnlike, lnlike0, wmean, status
+
     def grad_linear_workspace(self, S, K, q, covpts=300):
         """Device scratch of ``lnlike_grad_linear`` (sp_lnlike_grad_linear_workspace_bytes)."""
         return self._scratch(self._L.sp_lnlike_grad_linear_workspace_bytes(self._h, int(S), int(K), int(q), int(covpts)))

@@ -40,6 +40,19 @@ def _neg_inf_if_nan(x):
     return np.where(np.isnan(x), -np.inf, x)
 
 
+def _one_star_regressors(basis, basis_var):
+    """``basis`` (K, q) and ``basis_var`` scalar or (q,) of one light curve as the ensemble calls take them ((1, K, q),
+    the variances as given); None stays None.  ValueError for another shape."""
+    if basis is None:
+        return None, basis_var
+    U = np.asarray(basis, dtype=np.float64)
+    if U.ndim != 2:
+        raise ValueError("`basis` must be (K, q)")
+    if basis_var is not None and np.ndim(basis_var) > 1:
+        raise ValueError("`basis_var` must be a scalar or (q,)")
+    return U[None], basis_var
+
+
 def sample_columns(params, marginalize_over_inclination, time_variable):
     """``stars.SampleColumns.from_params`` as a tuple: (params, the same names in the batch's order, whether dr is a
     column, the free terms in that order)."""
@@ -704,7 +717,7 @@ class StarryProcess(object):
 
     # -- model checking: leave-one-out predictive distributions (sp_loo_ensemble) ---------------------------
     def loo_ensemble(self, t, flux, data_cov, i=None, p=None, u=None, baseline_mean=0.0, baseline_var=0.0,
-                     max_workspace_bytes=None):
+                     max_workspace_bytes=None, basis=None, basis_var=None):
         """Leave-one-out predictive checks of S light curves in one device call (Rasmussen & Williams 5.4.2): what
         the process, fitted to all the other cadences of a star, predicts for each cadence.  Nothing is refitted:
         with C the covariance ``log_likelihood_ensemble`` factors, r its residual, alpha = C^-1 r, d = diag(C^-1),
@@ -722,7 +735,22 @@ class StarryProcess(object):
         ``lnlike`` (-inf where ``log_likelihood_ensemble`` gives -inf) and ``status`` (S,).  A star whose covariance
         does not factor has NaN in its rows.  ``max_workspace_bytes`` caps the device scratch: the stars are then
         worked through in groups, with the same bits.  A full-matrix ``data_cov``, a matrix ``baseline_var`` and
-        ragged input (lists of light curves of different lengths) are not served."""
+        ragged input (lists of light curves of different lengths) are not served.
+
+        ``basis``, ``basis_var`` (as ``log_likelihood_linear_ensemble`` takes them): the checks of the model flux =
+        process + U w + noise, w ~ N(0, diag(basis_var)), through ``lbo_ensemble(..., block=1, basis=...)`` -- see
+        there.  ``mu`` and ``var`` then include the trend and the uncertainty of the weights, ``z`` is that call's
+        ``u``, ``white`` holds the whitened DETRENDED residual, and the dict gains ``lnlike0``, ``w_mean`` and
+        ``trend``."""
+        if basis is None and basis_var is not None:
+            raise ValueError("`basis_var` needs a `basis`")
+        if basis is not None:
+            out = self.lbo_ensemble(t, flux, data_cov, 1, i=i, p=p, u=u, baseline_mean=baseline_mean,
+                                    baseline_var=baseline_var, max_workspace_bytes=max_workspace_bytes, basis=basis,
+                                    basis_var=basis_var, _name="loo_ensemble")
+            out["z"] = out.pop("u")
+            del out["edges"]
+            return out
         e, f = self._engine, self._flux
         try:
             flux = np.asarray(flux, dtype=np.float64)
@@ -759,9 +787,10 @@ class StarryProcess(object):
         return out
 
     def loo(self, t, flux, data_cov, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]],
-            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"]):
-        """``loo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances.  The same dict
-        without the leading axis."""
+            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"], basis=None,
+            basis_var=None):
+        """``loo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances; basis None or
+        (K, q); basis_var a scalar or (q,).  The same dict without the leading axis."""
         dc = np.asarray(data_cov, dtype=np.float64)
         if dc.ndim >= 2:
             raise NotImplementedError("loo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
@@ -773,13 +802,15 @@ class StarryProcess(object):
             raise ValueError("`flux` must be one light curve of K cadences")
         if dc.ndim == 1:
             dc = dc.reshape(1, -1)
+        basis, basis_var = _one_star_regressors(basis, basis_var)
         out = self.loo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, i=i, p=p, u=u,
-                                baseline_mean=baseline_mean, baseline_var=baseline_var)
+                                baseline_mean=baseline_mean, baseline_var=baseline_var, basis=basis,
+                                basis_var=basis_var)
         return {k: v[0] for k, v in out.items()}
 
     # -- model checking: leave-block-out predictive distributions (sp_lbo_ensemble) -------------------------
     def lbo_ensemble(self, t, flux, data_cov, block, i=None, p=None, u=None, baseline_mean=0.0, baseline_var=0.0,
-                     return_cov=False, max_workspace_bytes=None):
+                     return_cov=False, max_workspace_bytes=None, basis=None, basis_var=None, _name="lbo_ensemble"):
         """Leave-block-out predictive checks of S light curves in one device call (h-block cross-validation): what
         the process, fitted to the cadences OUTSIDE a block B of consecutive ones, predicts for the whole block.
         Nothing is refitted: with C the covariance ``log_likelihood_ensemble`` factors, r its residual, alpha = C^-1 r
@@ -799,35 +830,65 @@ class StarryProcess(object):
         (S,); with ``return_cov`` also ``cov`` (S, nb, bmax, bmax), bmax the widest block: the block's covariance in the
         corner of its slot, the rest NaN.  A star whose covariance does not factor has NaN in its rows.
         ``max_workspace_bytes`` caps the device scratch: the stars are then worked through in groups, with the same
-        bits."""
-        e, f = self._engine, self._flux
+        bits.
+
+        With ``basis`` (K, q) shared or (S, K, q) and ``basis_var`` scalar, (q,) or (S, q), as
+        ``log_likelihood_linear_ensemble`` takes and refuses them, the checks are those of the model flux = process +
+        U w + noise, w ~ N(0, diag(basis_var)) (sp_lbo_linear): C above becomes C~ = C + U diag(basis_var) U^T, never
+        formed.  ``mu``, ``var`` and ``cov`` are predictive for the DATA, the trend and the uncertainty of the weights
+        included -- most of it when a block is a large part of a regressor's support; ``lpd`` of a block is lnlike of
+        all cadences minus lnlike of those outside it.  ``white`` then holds the whitened DETRENDED residual L^-1 (r -
+        U w_mean), whose covariance under the model is I - T T^T (q degrees of freedom fewer, like the residuals of
+        any regression), ``lnlike`` is ``log_likelihood_linear_ensemble``'s, and the dict gains ``lnlike0`` (S,),
+        ``w_mean`` (S, q) and ``trend`` (S, K) = U w_mean.  Without ``basis`` nothing changes."""
+        if basis is None and basis_var is not None:
+            raise ValueError("`basis_var` needs a `basis`")
         try:
             flux = np.asarray(flux, dtype=np.float64)
             tt = np.asarray(t, dtype=np.float64)
         except (ValueError, TypeError):
-            raise ValueError("lbo_ensemble does not serve ragged input (lists of light curves of different lengths): "
-                             "pass `t` and `flux` as (S, K) arrays")
+            raise ValueError("%s does not serve ragged input (lists of light curves of different lengths): "
+                             "pass `t` and `flux` as (S, K) arrays" % _name)
         if flux.ndim != 2:
             raise ValueError("`flux` must be (S, K)")
         S, K = flux.shape
         dc = np.asarray(data_cov, dtype=np.float64)
         if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
-            raise NotImplementedError("lbo_ensemble does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
-                                      "(S, K) variances")
+            raise NotImplementedError("%s does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
+                                      "(S, K) variances" % _name)
         if np.ndim(baseline_var) >= 2:
-            raise NotImplementedError("lbo_ensemble does not serve a matrix `baseline_var`: pass a scalar or (S,)")
+            raise NotImplementedError("%s does not serve a matrix `baseline_var`: pass a scalar or (S,)" % _name)
         edges = block_edges(block, K)
+        if basis is not None:
+            from .linear import check_regressors
+
+            if K < 2:
+                raise ValueError("the checks with regressors need at least two cadences")
+            if basis_var is None:
+                raise ValueError("`basis` needs a `basis_var`")
+            U, lam = check_regressors(basis, basis_var, S, K)
+            Ut = np.ascontiguousarray(np.swapaxes(U, 1, 2))          # [S, q, K]: a regressor along a row
+        e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
         f._bind()
         rta1 = e.f64(e.rTA1L(utab))
         tab = mv = None
         if self._marginalize_over_inclination:
             tab, mv = e.kernel_table(rta1, self._covpts)
-        rows, lpd, cov, lnlike, status = e.lbo_ensemble(
-            t, flux, stars, edges, diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts,
-            tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
-            norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
-            max_workspace_bytes=max_workspace_bytes)
+        branch = dict(diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
+                      meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
+                      norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
+                      max_workspace_bytes=max_workspace_bytes)
+        extra = {}
+        if basis is not None:
+            Ud = e.f64(Ut)
+            rows, lpd, cov, lnlike, lnlike0, wmean, status = e.lbo_linear(t, flux, stars, edges, Ud, lam, **branch)
+            extra["lnlike0"] = _neg_inf_if_nan(lnlike0.cpu().numpy())
+            extra["w_mean"] = wmean.cpu().numpy()
+            # (U w_mean on the device; a weight switched off contributes an exact zero)
+            extra["trend"] = (Ud * wmean[:, :, None]).sum(dim=1).cpu().numpy()
+        else:
+            rows, lpd, cov, lnlike, status = e.lbo_ensemble(t, flux, stars, edges, **branch)
         rows = rows.cpu().numpy()
         out = {name: np.ascontiguousarray(rows[:, k]) for k, name in enumerate(("mu", "var", "u", "white"))}
         out["lpd"] = lpd.cpu().numpy()
@@ -836,13 +897,15 @@ class StarryProcess(object):
         if return_cov:
             out["cov"] = cov.cpu().numpy()
         out["lnlike"] = _neg_inf_if_nan(lnlike.cpu().numpy())
+        out.update(extra)
         out["status"] = status.cpu().numpy()
         return out
 
     def lbo(self, t, flux, data_cov, block, i=defaults["i"], p=defaults["p"], u=defaults["u"][: defaults["udeg"]],
-            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"], return_cov=False):
-        """``lbo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances.  The same dict
-        without the leading axis (``edges`` as it is)."""
+            baseline_mean=defaults["baseline_mean"], baseline_var=defaults["baseline_var"], return_cov=False,
+            basis=None, basis_var=None):
+        """``lbo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances; basis None or
+        (K, q); basis_var a scalar or (q,).  The same dict without the leading axis (``edges`` as it is)."""
         dc = np.asarray(data_cov, dtype=np.float64)
         if dc.ndim >= 2:
             raise NotImplementedError("lbo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
@@ -854,8 +917,10 @@ class StarryProcess(object):
             raise ValueError("`flux` must be one light curve of K cadences")
         if dc.ndim == 1:
             dc = dc.reshape(1, -1)
+        basis, basis_var = _one_star_regressors(basis, basis_var)
         out = self.lbo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, block, i=i, p=p, u=u,
-                                baseline_mean=baseline_mean, baseline_var=baseline_var, return_cov=return_cov)
+                                baseline_mean=baseline_mean, baseline_var=baseline_var, return_cov=return_cov,
+                                basis=basis, basis_var=basis_var)
         return {k: (v if k == "edges" else v[0]) for k, v in out.items()}
 
     # -- linear regressors marginalised out of the likelihood (sp_lnlike_linear) ------------------------------
