@@ -63,14 +63,24 @@ CASES = [
 DR_CASE = dict(id="norm-dr-K65", K=65, normalized=True, dr=5.0)
 
 
-def _times(K):
+def _times(K, span=None):
     """[3, K]: sorted, unevenly spaced cadences over the span, different for every star."""
     rng = np.random.RandomState(100 + K)
-    return np.sort(rng.uniform(0.0, SPAN, size=(3, K)), axis=1)
+    return np.sort(rng.uniform(0.0, SPAN if span is None else span, size=(3, K)), axis=1)
+
+
+def _geometry(case):
+    """(times [3, K], periods [3], limb darkening [3, 2], ydeg) of a case: this module's stars at degree YDEG, or the case's
+    own ("span", "periods", "u", "ydeg": the cases of tests/test_gpu_norm_series.py, which also set "ferr", "hp" and
+    "norm_order")."""
+    return (_times(case["K"], case.get("span")), np.asarray(case.get("periods", PERIODS)), np.asarray(case.get("u", U)),
+            case.get("ydeg", YDEG))
 
 
 def _ferr(case):
     K = case["K"]
+    if "ferr" in case:
+        return case["ferr"]
     if case.get("percadence"):
         return 1.0e-3 * (1.0 + np.random.RandomState(7).uniform(0.0, 1.0, size=(3, K)))
     return 1.0e-3
@@ -80,18 +90,18 @@ def _ferr(case):
 _moments_cache = {}
 
 
-def _oracle_moments(hp):
+def _oracle_moments(hp, ydeg=YDEG):
     """(mu_y, Sigma_y) of the oracle's own upstream quadrature at the hyperparameters hp (cached: every case and star
     differences the same moments)."""
     import oracle.sp_oracle as orc
     from starry_process_amd.upstream import ab_to_alphabeta, size_moments
 
-    key = tuple(sorted(hp.items()))
+    key = (ydeg,) + tuple(sorted(hp.items()))
     if key not in _moments_cache:
-        s1, eigS = size_moments(hp["r"], hp.get("dr"), YDEG)
+        s1, eigS = size_moments(hp["r"], hp.get("dr"), ydeg)
         cols = s1[None, :] if hp.get("dr") is None else eigS.T[np.abs(eigS).sum(axis=0) > 0.0]
         alpha, beta = ab_to_alphabeta(hp["a"], hp["b"])
-        _moments_cache[key] = orc.ylm_moments_quadrature(s1, cols, alpha, beta, hp["c"], hp["n"], YDEG)
+        _moments_cache[key] = orc.ylm_moments_quadrature(s1, cols, alpha, beta, hp["c"], hp["n"], ydeg)
     return _moments_cache[key]
 
 
@@ -99,15 +109,16 @@ def _oracle_C(case, hp, s):
     """(C [K, K], m) of star s: the covariance the likelihood factors and the mean of its flux GP."""
     import oracle.sp_oracle as orc
 
-    mu, Sig = _oracle_moments(hp)
-    op = orc.OracleProcess(mu, Sig, ydeg=YDEG, udeg=2, normalized=case["normalized"], tau=case.get("tau"),
+    times, periods, u, ydeg = _geometry(case)
+    mu, Sig = _oracle_moments(hp, ydeg)
+    op = orc.OracleProcess(mu, Sig, ydeg=ydeg, udeg=2, normalized=case["normalized"], tau=case.get("tau"),
                            temporal_kernel=getattr(orc, ORACLE_KERNEL[case.get("temporal", "matern32")]),
-                           covpts=case.get("covpts", 300))
-    t = _times(case["K"])[s]
-    C = op.cov(t, p=PERIODS[s], u=U[s])
+                           covpts=case.get("covpts", 300), normalization_order=case.get("norm_order", 20))
+    t = times[s]
+    C = op.cov(t, p=periods[s], u=u[s])
     var = np.broadcast_to(np.asarray(_ferr(case)) ** 2, (3, case["K"]))[s]
     C = C + np.diag(var) + case.get("baseline_var", 0.0)
-    m = 0.0 if case["normalized"] else float(op.flux_mean_cov(t, p=PERIODS[s], u=U[s])[0])
+    m = 0.0 if case["normalized"] else float(op.flux_mean_cov(t, p=periods[s], u=u[s])[0])
     return C, m
 
 
@@ -126,7 +137,7 @@ def _reference(case, h=H):
     key = (case["id"], h)
     if key in _ref_cache:
         return _ref_cache[key]
-    hp0 = dict(HP)
+    hp0 = dict(case.get("hp", HP))        # ("hp", "norm_order": the cases of tests/test_gpu_norm_series.py)
     names = NAMES
     if case.get("dr") is not None:
         hp0["dr"] = case["dr"]
@@ -176,9 +187,10 @@ def _measure_delta():
 def _fisher(case, stars=slice(None), **kw):
     from starry_process_amd.grad import EnsembleFisher
 
-    t, ferr = _times(case["K"])[stars], _ferr(case)
+    times, periods, u, ydeg = _geometry(case)
+    t, ferr = times[stars], _ferr(case)
     ferr = ferr[stars] if np.ndim(ferr) == 2 else ferr
-    return EnsembleFisher(t, ferr=ferr, p=PERIODS[stars], u=U[stars], ydeg=YDEG, normalized=case["normalized"],
+    return EnsembleFisher(t, ferr=ferr, p=periods[stars], u=u[stars], ydeg=ydeg, normalized=case["normalized"],
                           tau=case.get("tau"), temporal_kernel=case.get("temporal", "matern32"),
                           baseline_var=case.get("baseline_var", 0.0), covpts=case.get("covpts"), **kw)
 

@@ -83,14 +83,24 @@ def _ydeg(case):
     return case.get("ydeg", 5)
 
 
-def _times(K):
+def _times(K, span=None):
     """[3, K]: sorted, unevenly spaced cadences over the span, different for every star."""
     rng = np.random.RandomState(100 + K)
-    return np.sort(rng.uniform(0.0, SPAN, size=(3, K)), axis=1)
+    return np.sort(rng.uniform(0.0, SPAN if span is None else span, size=(3, K)), axis=1)
+
+
+def _geometry(case):
+    """(times [3, K], periods [3], inclinations [3], limb darkening [3, 2]) of a case: this module's stars, or the case's
+    own ("span", "periods", "incs", "u": the cases of tests/test_gpu_norm_series.py, which also set "ferr", "hp" and
+    "norm_order")."""
+    return (_times(case["K"], case.get("span")), np.asarray(case.get("periods", PERIODS)),
+            np.asarray(case.get("incs", INCS)), np.asarray(case.get("u", U)))
 
 
 def _ferr(case):
     K = case["K"]
+    if "ferr" in case:
+        return case["ferr"]
     if case.get("percadence"):
         return 1.0e-3 * (1.0 + np.random.RandomState(7).uniform(0.0, 1.0, size=(3, K)))
     return 1.0e-3
@@ -122,12 +132,14 @@ def _oracle_C(case, x, s):
     mu, Sig = _oracle_moments({k: x[k] for k in NAMES}, _ydeg(case))
     op = orc.OracleProcess(mu, Sig, ydeg=_ydeg(case), udeg=2, marginalize_over_inclination=False,
                            normalized=case["normalized"], tau=case.get("tau"),
-                           temporal_kernel=getattr(orc, ORACLE_KERNEL[case.get("temporal", "matern32")]))
-    t = _times(case["K"])[s]
-    C = op.cov(t, i=x["i"], p=x["p"], u=U[s])
+                           temporal_kernel=getattr(orc, ORACLE_KERNEL[case.get("temporal", "matern32")]),
+                           normalization_order=case.get("norm_order", 20))
+    times, _, _, u = _geometry(case)
+    t = times[s]
+    C = op.cov(t, i=x["i"], p=x["p"], u=u[s])
     var = np.broadcast_to(np.asarray(_ferr(case)) ** 2, (3, case["K"]))[s]
     C = C + np.diag(var) + case.get("baseline_var", 0.0)
-    m = 0.0 if case["normalized"] else float(op.flux_mean_cov(t, i=x["i"], p=x["p"], u=U[s])[0])
+    m = 0.0 if case["normalized"] else float(op.flux_mean_cov(t, i=x["i"], p=x["p"], u=u[s])[0])
     return C, m
 
 
@@ -150,7 +162,8 @@ def _reference(case, h=H):
     K, P = case["K"], len(ALL)
     dC, dm, F = np.empty((3, P, K, K)), np.empty((3, P)), np.empty((3, P, P))
     for s in range(3):
-        x0 = dict(HP, i=float(INCS[s]), p=float(PERIODS[s]))
+        # ("hp", "norm_order": the cases of tests/test_gpu_norm_series.py)
+        x0 = dict(case.get("hp", HP), i=float(_geometry(case)[2][s]), p=float(_geometry(case)[1][s]))
         C0, _ = _oracle_C(case, x0, s)
         for k, name in enumerate(ALL):
             step = h * max(abs(x0[name]), 0.1)
@@ -194,9 +207,10 @@ def _measure_delta():
 def _fisher(case, stars=slice(None), **kw):
     from starry_process_amd.grad import EnsembleFisherConditional
 
-    t, ferr = _times(case["K"])[stars], _ferr(case)
+    times, periods, incs, u = _geometry(case)
+    t, ferr = times[stars], _ferr(case)
     ferr = ferr[stars] if np.ndim(ferr) == 2 else ferr
-    return EnsembleFisherConditional(t, ferr=ferr, p=PERIODS[stars], i=INCS[stars], u=U[stars], ydeg=_ydeg(case),
+    return EnsembleFisherConditional(t, ferr=ferr, p=periods[stars], i=incs[stars], u=u[stars], ydeg=_ydeg(case),
                                      normalized=case["normalized"], tau=case.get("tau"),
                                      temporal_kernel=case.get("temporal", "matern32"), baseline_var=case.get("baseline_var", 0.0), **kw)
 
@@ -294,7 +308,7 @@ def _device_inputs(case):
     """What Engine.fisher_conditional takes, through EnsembleFisherConditional's own chain: (the sweep, dmu, dSig), the
     engine's moments set at HP."""
     ef = _fisher(case)
-    dmu, dSig = ef._moment_tangents(NAMES, *[float(HP[k]) for k in NAMES])
+    dmu, dSig = ef._moment_tangents(NAMES, *[float(case.get("hp", HP)[k]) for k in NAMES])
     return ef, dmu, dSig
 
 
