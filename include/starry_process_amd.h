@@ -855,6 +855,40 @@ int sp_predict_ensemble(sp_handle *h, int S, int K, int Ks, const double *t_dev,
                         int temporal, int mode, double *mu_dev, double *var_dev, double *cov_dev, int32_t *info_dev,
                         void *workspace_dev, void *stream);
 
+/* ---- conditional light curves with linear regressors marginalised out (csrc/sp_predict.hip) -----------
+ * sp_predict_ensemble for the model of sp_lnlike_linear: flux_s = process + U_s w + noise, w ~ N(0, diag lambda_s).
+ * The arguments of sp_predict_ensemble, and q in 1 .. 32, basis_dev [S, q, K] (regressor j of star s along row j),
+ * basis_var_dev [S, q] = lambda, basis_sample_dev [S, Ks, q] = the regressors at the sample times, or NULL (zeros: the
+ * process alone is predicted, the trend removed, the uncertainty of the weights still carried).  With C = L L^T, r, K_st
+ * and K_ss as sp_predict_ensemble forms them, D = diag sqrt(lambda), and the riding rows Y = K_st L^-T, y = L^-1 r,
+ * W^T = (L^-1 U)^T of ONE system of leading dimension roundup(K + Ks + 1 + q, 64):
+ *   G_q = I + D W^T W D = L_G L_G^T,  v = L_G^-1 D W^T y,  M = D L_G^-T,  w_mean = M v,
+ *   R = U_s - Y W,  Z = R M,  mu = mean + Y y + R w_mean,  cov = K_ss - Y Y^T + Z Z^T,
+ * the conditional of f_s + U_s w given the data under C + U Lambda U^T, which is never formed.  Nothing is divided by
+ * lambda: lambda_j = 0 switches regressor j off exactly (w_mean[j] = 0, column j of M zero); every lambda zero: Z = 0.
+ * mu_dev [S, Ks] has the same bits in every mode; var_dev [S, Ks] (SP_PREDICT_VAR) from the same single pass over Y,
+ * nothing Ks x Ks formed; cov_dev [S, Ks, Ks] (SP_PREDICT_COV) exactly symmetric.  info_dev [S] (may be NULL) as
+ * sp_predict_ensemble.  wmean_dev [S, q], lnlike_dev [S], lnlike0_dev [S] (the likelihood with and without the
+ * regressors, sp_lnlike_linear's formulas on this call's factor), status_dev [S]: each may be NULL.
+ * Per star: C does not factor -> NaN in every output, SP_STAR_NOT_PD;  a NaN reaching G_q or v (a negative lambda,
+ * say), or 0 < stars[s].nobs < K -> NaN in every output, SP_STAR_NAN.  No star affects another; no atomics, every sum
+ * in one fixed order: a star's bits do not depend on its neighbours, its position or the passes.
+ * A host-only handle: SP_ERR_NO_DEVICE, before everything else.  A null required pointer, q outside 1 .. 32, what
+ * sp_predict_ensemble refuses, or a workspace too small for one star: SP_ERR_INVALID, nothing launched.  S = 0: SP_OK.
+ * workspace_dev: workspace_bytes bytes; sp_predict_linear_workspace_bytes(h, S, K, Ks, q, covpts) holds a pass of as
+ * many stars as sp_predict_workspace_bytes' (0 for arguments the call refuses), a smaller one makes the passes
+ * shorter, with the same bits.  All launches go to `stream`; nothing is synchronised.                                 */
+size_t sp_predict_linear_workspace_bytes(sp_handle *h, int S, int K, int Ks, int q, int covpts);
+int sp_predict_linear(sp_handle *h, int S, int K, int Ks, int q, const double *t_dev, const double *ts_dev,
+                      const double *flux_dev, const double *diag_dev, const sp_star *stars_dev,
+                      const double *basis_dev /* [S, q, K] */, const double *basis_sample_dev /* NULL or [S, Ks, q] */,
+                      const double *basis_var_dev /* [S, q] */, int conditional, int covpts, const double *tab_dev,
+                      const double *meanvar_dev, const double *rta1_dev, int temporal, int mode, double *mu_dev,
+                      double *var_dev, double *cov_dev, int32_t *info_dev, double *wmean_dev /* NULL or [S, q] */,
+                      double *lnlike_dev /* NULL or [S] */, double *lnlike0_dev /* NULL or [S] */,
+                      uint32_t *status_dev /* NULL or [S] */, void *workspace_dev, size_t workspace_bytes,
+                      void *stream);
+
 /* ---- posterior of the spherical-harmonic map given a light curve (sp.py:518-641, sample_ylm_conditional) ----
  * For S stars with the conditional path's design matrices A_s = sp_design_matrix(t, stars, rta1) [K, N]:
  *   W   = Sigma_y^-1 + A^T C^-1 A,   C = diag(data var) + baseline_var 1 1^T     (sp.py:601-628)

@@ -120,6 +120,9 @@ PROTOTYPES = {
     "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),
     "sp_predict_ensemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _V, _V, _V,
                                  _V]),
+    "sp_predict_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
+    "sp_predict_linear": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _V, _V, _V,
+                               _V, _V, _V, _V, _V, _V, ctypes.c_size_t, _V]),
     "sp_ylm_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I]),
     "sp_ylm_conditional_batched": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "sp_ylm_conditional_whitened": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _V, _V]),

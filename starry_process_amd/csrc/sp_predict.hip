@@ -23,6 +23,10 @@
 // K_ss -= Y Y^T runs on the matrix cores, lower tiles, and sp_launch_mirror_lower, sp_pixel.hip, makes it exactly
 // symmetric).
 //
+// sp_predict_linear (below) is the same call for the model with q linear regressors marginalised out: their
+// rows ride below the residual row of the same system, and predict_reduce_linear_kernel takes the place of
+// predict_reduce_kernel.
+//
 // Compiled with -ffp-contract=off (Makefile: NOCONTRACT): the spline index and the entries must be the dense
 // assembly's, operation for operation.
 #include "sp_internal.h"
@@ -256,12 +260,197 @@ __global__ __launch_bounds__(256) void predict_reduce_kernel(const double *__res
   }
 }
 
+// ---- with q linear regressors marginalised out (sp_predict_linear) ----------------------------------
+// The q regressor rows ride below the residual row: after the factorisation the rows K + Ks .. K + Ks + q of a system
+// hold [y; W^T] = [L^-1 r; (L^-1 U)^T], and sp_linear.hip's Gram pass and finish give w_mean and M = D L_G^-T.
+constexpr int PL_QMAX = 32;      // regressors per star, and the columns of Z
+constexpr int PL_JB = 64;        // sample rows per workgroup (wavefront w: 16 w .. 16 w + 15)
+constexpr int PL_KB = 32;        // columns of Y per tile
+constexpr int PL_LD = 34;        // row stride of a tile in LDS: a fragment read of 16 rows x 2 columns (a group of 32
+                                 // lanes of ds_read_b64) falls on 32 distinct 8-byte banks; rows stay 16-byte aligned
+constexpr int PL_MLD = PL_QMAX + 1;
+typedef double pl_d4 __attribute__((ext_vector_type(4)));
+
+// the regressor rows K + Ks + 1 .. K + Ks + q of every system, columns < K, as given: no mean is subtracted (the flux
+// slot of the assembly would).  The assembly has left those rows as padding -- zeros and a unit diagonal, what the
+// factorisation expects right of column K - 1 of a riding row -- and that part stays.  grid (ceil(K / 256), q, S)
+__global__ __launch_bounds__(256) void predict_rows_linear_kernel(int K, int Ks, int q, long ld, long stride,
+                                                                  const double *__restrict__ basis,
+                                                                  double *__restrict__ sys) {
+  const int s = blockIdx.z, a = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= K) return;
+  sys[(size_t)s * stride + (size_t)(K + Ks + 1 + a) * ld + c] = basis[((size_t)s * q + a) * K + c];
+}
+
+// bad[s]: the star's outputs are NaN (its covariance did not factor, or the q x q finish flagged it).  grid ceil(S / 256)
+__global__ void predict_linear_flags_kernel(int S, const int32_t *__restrict__ info, const uint32_t *__restrict__ status,
+                                            int32_t *__restrict__ bad) {
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < S) bad[s] = (info[s] != 0 || (status[s] & (SP_STAR_NOT_PD | SP_STAR_NAN)) != 0) ? 1 : 0;
+}
+
+// One pass over the Ks riding rows Y of the factored systems: Y_j . y, (VAR) |Y_j|^2 and P_j = Y_j W from the same
+// loads, then per sample row R_j = U_s[j] - P_j, mu_j = (mean + Y_j . y) + R_j . w_mean, Z_j = R_j M and (VAR) var_j =
+// ((kss_j + baseline_var) - |Y_j|^2) + |Z_j|^2; (ZOUT) Z_j into zout [S][Ks][32] for the full covariance.
+// A workgroup owns PL_JB sample rows, a wavefront 16 of them, over all K columns: no partial sums between workgroups.
+// Tiles of PL_KB columns of Y and of [y; W^T] go through LDS (16-byte loads along the rows, zeros at columns >= K and
+// rows >= Ks), the next tile's loads in flight while this one is multiplied, one barrier per tile.  P runs on the fp64
+// matrix cores: A = a tile of 16 regressors x 4 columns, B = 4 columns x the wavefront's 16 sample rows, so lane
+// (fr, fq) = (lane & 15, lane >> 4) holds P[sample fr][regressor 16 mt + fq + 4 r] in acc[mt][r]; the same lane adds
+// its B operand into Y_j . y and |Y_j|^2 (the columns c = fq mod 4, in order; the four fq by two butterfly steps).
+// MT: the tiles of 16 regressors (1: q <= 16).  The epilogue's sums run over the regressors in order.  Every sum has a
+// fixed order that does not depend on VAR / ZOUT; every output element has one writer.  grid (ceil(Ks / PL_JB), S)
+template <int MT, bool VAR, bool ZOUT>
+__global__ __launch_bounds__(256) void predict_reduce_linear_kernel(
+    const double *__restrict__ sys, long ld, long stride, int K, int Ks, int q, const int32_t *__restrict__ bad,
+    const sp_star *__restrict__ stars, const double *__restrict__ mean, const double *__restrict__ kss, int kss_per_row,
+    const double *__restrict__ bsample, const double *__restrict__ wmean, const double *__restrict__ mix,
+    double *__restrict__ mu, double *__restrict__ var, double *__restrict__ zout) {
+  constexpr int NW = 16 * MT + 1;                       // rows of a tile of [y; W^T]
+  constexpr int WL = MT + 1;                            // ... and a thread's 16-byte loads of it
+  __shared__ __attribute__((aligned(16))) double Ys[2][PL_JB * PL_LD];
+  __shared__ __attribute__((aligned(16))) double Ws[2][NW * PL_LD];
+  static_assert(2 * PL_JB * PL_LD >= 4 * 16 * PL_MLD + PL_QMAX * PL_MLD + PL_QMAX, "the epilogue reuses Ys");
+  const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j0 = PL_JB * blockIdx.x;
+  const double nanv = __builtin_nan("");
+  if (bad[s]) {
+    for (int e = tid; e < PL_JB; e += 256)
+      if (j0 + e < Ks) {
+        mu[(size_t)s * Ks + j0 + e] = nanv;
+        if (VAR) var[(size_t)s * Ks + j0 + e] = nanv;
+      }
+    if (ZOUT)
+      for (int e = tid; e < PL_JB * PL_QMAX; e += 256)
+        if (j0 + (e >> 5) < Ks) zout[((size_t)s * Ks + j0) * PL_QMAX + e] = nanv;
+    return;
+  }
+  const double *M0 = sys + (size_t)s * stride;
+  const double *Y = M0 + (size_t)K * ld;                // the sample rows
+  const double *W = M0 + (size_t)(K + Ks) * ld;         // y, then the rows of W^T
+  const int ntiles = (K + PL_KB - 1) / PL_KB;
+  // loads: thread -> the column pair tid & 15 of the rows (tid >> 4) + 16 i of a tile
+  const int lp = tid & 15, lr = tid >> 4;
+  // (every load is issued without a condition, at an address clamped into the star's rows, so that all of a tile's
+  //  loads are in flight together; what lies at columns >= K or rows >= Ks is masked on the way into LDS)
+  dd2 yreg[4], wreg[WL];
+  const double *yrow[4], *wrow[WL];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) yrow[i] = Y + (size_t)(j0 + lr + 16 * i < Ks ? j0 + lr + 16 * i : Ks - 1) * ld;
+#pragma unroll
+  for (int i = 0; i < WL; ++i) wrow[i] = W + (size_t)(lr + 16 * i <= q ? lr + 16 * i : 0) * ld;
+  auto load = [&](int tt) {
+    const int c = PL_KB * tt + 2 * lp, cc = c < K ? c : 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) yreg[i] = *reinterpret_cast<const dd2 *>(yrow[i] + cc);
+#pragma unroll
+    for (int i = 0; i < WL; ++i) wreg[i] = *reinterpret_cast<const dd2 *>(wrow[i] + cc);
+  };
+  auto store = [&](int buf, int tt) {
+    const int c = PL_KB * tt + 2 * lp;
+    const bool c0 = c < K, c1 = c + 1 < K;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bool rowok = j0 + lr + 16 * i < Ks;
+      *reinterpret_cast<dd2 *>(&Ys[buf][(lr + 16 * i) * PL_LD + 2 * lp]) =
+          dd2{rowok && c0 ? yreg[i].x : 0.0, rowok && c1 ? yreg[i].y : 0.0};
+    }
+#pragma unroll
+    for (int i = 0; i < WL; ++i) {
+      const bool rowok = lr + 16 * i <= q;
+      if (lr + 16 * i < NW)
+        *reinterpret_cast<dd2 *>(&Ws[buf][(lr + 16 * i) * PL_LD + 2 * lp]) =
+            dd2{rowok && c0 ? wreg[i].x : 0.0, rowok && c1 ? wreg[i].y : 0.0};
+    }
+  };
+  pl_d4 acc[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) acc[mt] = pl_d4{0.0, 0.0, 0.0, 0.0};
+  double dot = 0.0, nrm = 0.0;
+  const int fr = lane & 15, fq = lane >> 4;
+  load(0);
+  store(0, 0);
+  __syncthreads();
+  for (int tt = 0; tt < ntiles; ++tt) {
+    if (tt + 1 < ntiles) load(tt + 1);
+    const double *Yt = Ys[tt & 1] + (16 * wave + fr) * PL_LD, *Wt = Ws[tt & 1];
+#pragma unroll
+    for (int kk = 0; kk < PL_KB / 4; ++kk) {
+      const double b = Yt[4 * kk + fq];
+      dot += b * Wt[4 * kk + fq];
+      if (VAR) nrm += b * b;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+        acc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(Wt[(1 + 16 * mt + fr) * PL_LD + 4 * kk + fq], b, acc[mt], 0, 0, 0);
+    }
+    if (tt + 1 < ntiles) store((tt + 1) & 1, tt + 1);
+    __syncthreads();
+  }
+  // (every wavefront is past its last read of the tiles: the epilogue's tables take their place)
+  double *Rs = &Ys[0][0] + wave * 16 * PL_MLD;          // the wavefront's R [16][q]
+  double *Ms = &Ys[0][0] + 4 * 16 * PL_MLD;             // M [32][32], upper triangular
+  double *wm = Ms + PL_QMAX * PL_MLD;
+  for (int e = tid; e < PL_QMAX * PL_QMAX; e += 256)
+    Ms[(e >> 5) * PL_MLD + (e & 31)] = mix[(size_t)s * PL_QMAX * PL_QMAX + e];
+  if (tid < PL_QMAX) wm[tid] = tid < q ? wmean[(size_t)s * q + tid] : 0.0;
+  const int jw = j0 + 16 * wave;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int a = 16 * mt + fq + 4 * r, j = jw + fr;
+      double v = 0.0;
+      if (a < q && j < Ks) v = (bsample ? bsample[((size_t)s * Ks + j) * q + a] : 0.0) - acc[mt][r];
+      Rs[fr * PL_MLD + a] = v;
+    }
+  dot += __shfl_xor(dot, 16, 64);
+  dot += __shfl_xor(dot, 32, 64);
+  if (VAR) {
+    nrm += __shfl_xor(nrm, 16, 64);
+    nrm += __shfl_xor(nrm, 32, 64);
+  }
+  __syncthreads();
+  const int j = jw + fr, nq = q < 16 * MT ? q : 16 * MT;
+  const double *Rj = Rs + fr * PL_MLD;
+  double tr = 0.0;
+  for (int a = 0; a < nq; ++a) tr = fma(Rj[a], wm[a], tr);
+  double zz = 0.0;
+  if (VAR || ZOUT) {
+    double z[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) z[i] = 0.0;
+    for (int a = 0; a < nq; ++a) {
+      const double ra = Rj[a];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) z[i] = fma(ra, Ms[a * PL_MLD + 8 * fq + i], z[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) zz = fma(z[i], z[i], zz);
+    zz += __shfl_xor(zz, 16, 64);
+    zz += __shfl_xor(zz, 32, 64);
+    if (ZOUT && j < Ks) {
+      double *zo = zout + ((size_t)s * Ks + j) * PL_QMAX + 8 * fq;
+#pragma unroll
+      for (int i = 0; i < 8; i += 2) *reinterpret_cast<dd2 *>(zo + i) = dd2{z[i], z[i + 1]};
+    }
+  }
+  if (fq == 0 && j < Ks) {
+    mu[(size_t)s * Ks + j] = (dot + mean[s]) + tr;
+    if (VAR) {
+      const double prior = kss[kss_per_row ? (size_t)s * Ks + j : (size_t)s] + stars[s].baseline_var;
+      var[(size_t)s * Ks + j] = (prior - nrm) + zz;
+    }
+  }
+}
+
 // the workspace: every region holds `chunk` blocks, one per star of a pass
 struct PredictLayout {
   int Kp, Kall, chunk, np;
   size_t info, mean, kss0, th_t, th_s, ptab, invL, tall, kss, A, B, sys, bytes;
-  PredictLayout(const sp_handle *h, int S, int K, int Ks, int covpts) {
-    Kp = sp_roundup(K + Ks + 1, SP_NB);
+  // (q regressors: sp_predict_linear's regions, carved behind the others)
+  size_t gpart = 0, mix = 0, wmean = 0, lnl = 0, status = 0, bad = 0, Z = 0;
+  PredictLayout(const sp_handle *h, int S, int K, int Ks, int covpts, int q = 0) {
+    Kp = sp_roundup(K + Ks + 1 + q, SP_NB);
     Kall = K + Ks;
     np = covpts + 4;
     const size_t d = sizeof(double);
@@ -280,6 +469,15 @@ struct PredictLayout {
       A = take(d * (size_t)Kall * h->N);
       B = take(d * (size_t)Kall * h->N);
       sys = take(d * (size_t)Kp * Kp);
+      if (q > 0) {
+        gpart = c.take(sp_lin_gpart_bytes(n, K, q));
+        mix = take(d * PL_QMAX * PL_QMAX);
+        wmean = take(d * q);
+        lnl = take(d * 2);
+        status = take(sizeof(uint32_t));
+        bad = take(sizeof(int32_t));
+        Z = take(d * (size_t)Ks * PL_QMAX);
+      }
       return c.off;
     };
     const size_t per = carve(1);
@@ -288,6 +486,9 @@ struct PredictLayout {
     const size_t fit = sp_proc_tuning().predict_chunk_bytes / per;
     chunk = fit < 1 ? 1 : (fit < (size_t)S ? (int)fit : S);
     if (chunk > 65535) chunk = 65535;
+    // (with regressors a pass takes the stars it takes without them: the budget counts the regions above `gpart`, and
+    //  the size query is never below sp_predict_workspace_bytes')
+    if (q > 0) chunk = PredictLayout(h, S, K, Ks, covpts).chunk;
     bytes = carve(chunk);
   }
 };
@@ -498,6 +699,125 @@ int sp_predict_ensemble(sp_handle *h, int S, int K, int Ks, const double *t_dev,
       if ((rc = sp_launch_gemm_nt(Y, ld, stride, Y, ld, stride, C, Ks, skk, Ks, Ks, K, -1.0, 1, 1, nb, st))) return rc;
       // (exactly symmetric; NaN everywhere for a star whose K_tt did not factor)
       if ((rc = sp_launch_mirror_lower(C, Ks, (long)Ks, skk, nb, st, info))) return rc;
+    }
+    if (info_dev)
+      SP_HIP(hipMemcpyAsync(info_dev + c0, info, sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, st));
+  }
+  return SP_OK;
+}
+
+size_t sp_predict_linear_workspace_bytes(sp_handle *h, int S, int K, int Ks, int q, int covpts) {
+  if (!h || S < 1 || K < 1 || Ks < 1 || covpts < 1 || q < 1 || q > PL_QMAX) return 0;
+  return PredictLayout(h, S, K, Ks, covpts, q).bytes;
+}
+
+int sp_predict_linear(sp_handle *h, int S, int K, int Ks, int q, const double *t_dev, const double *ts_dev,
+                      const double *flux_dev, const double *diag_dev, const sp_star *stars_dev,
+                      const double *basis_dev, const double *basis_sample_dev, const double *basis_var_dev,
+                      int conditional, int covpts, const double *tab_dev, const double *meanvar_dev,
+                      const double *rta1_dev, int temporal, int mode, double *mu_dev, double *var_dev, double *cov_dev,
+                      int32_t *info_dev, double *wmean_dev, double *lnlike_dev, double *lnlike0_dev,
+                      uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!h || !basis_dev || !basis_var_dev || q < 1 || q > PL_QMAX) return SP_ERR_INVALID;
+  const PredictIn in{K, Ks, t_dev, ts_dev ? ts_dev : t_dev, flux_dev, diag_dev, stars_dev, conditional, covpts,
+                     tab_dev, meanvar_dev, rta1_dev, temporal};
+  int rc = check_in(h, S, in);
+  if (rc) return rc;
+  if ((!ts_dev && Ks != K) || mode < SP_PREDICT_MEAN || mode > SP_PREDICT_COV) return SP_ERR_INVALID;
+  if (S == 0) return SP_OK;
+  if (!mu_dev || !workspace_dev || (mode == SP_PREDICT_VAR && !var_dev) || (mode == SP_PREDICT_COV && !cov_dev))
+    return SP_ERR_INVALID;
+  // (the stars of a pass: as many as the caller's workspace holds, at most those of the size query)
+  PredictLayout L(h, S, K, Ks, covpts, q);
+  if (workspace_bytes < L.bytes) {
+    int n = L.chunk;
+    while (n > 1 && PredictLayout(h, n, K, Ks, covpts, q).bytes > workspace_bytes) n = n / 2;
+    L = PredictLayout(h, n, K, Ks, covpts, q);
+    if (L.bytes > workspace_bytes) return SP_ERR_INVALID;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  void *ws = workspace_dev;
+  const int Kp = L.Kp, N = h->N;
+  const long ld = Kp, stride = (long)Kp * Kp, skk = (long)Ks * Ks;
+  double *sys = at<double>(ws, L.sys), *gpart = at<double>(ws, L.gpart), *mix = at<double>(ws, L.mix);
+  double *Z = at<double>(ws, L.Z);
+  int32_t *info = at<int32_t>(ws, L.info), *bad = at<int32_t>(ws, L.bad);
+  const bool same = in.ts == in.t;
+  for (int c0 = 0; c0 < S; c0 += L.chunk) {
+    const int nb = S - c0 < L.chunk ? S - c0 : L.chunk;
+    const sp_star *stars = stars_dev + c0;
+    if ((rc = assemble_chunk(h, L, ws, in, c0, nb, sys, st))) return rc;
+    hipLaunchKernelGGL(predict_rows_linear_kernel, dim3((K + 255) / 256, q, nb), dim3(256), 0, st, K, Ks, q, ld, stride,
+                       basis_dev + (size_t)c0 * q * K, sys);
+    SP_LAUNCH_CHECK();
+    if ((rc = sp_launch_cholesky_systems(h, sys, nb, K, Kp, info, at<double>(ws, L.invL), st))) return rc;
+    // the q x q stage on the rows [y; W^T] (sp_linear.hip): lnlike, lnlike0, w_mean, M and the status words
+    double *wmean = wmean_dev ? wmean_dev + (size_t)c0 * q : at<double>(ws, L.wmean);
+    double *lnl = lnlike_dev ? lnlike_dev + c0 : at<double>(ws, L.lnl);
+    double *lnl0 = lnlike0_dev ? lnlike0_dev + c0 : at<double>(ws, L.lnl) + nb;
+    uint32_t *status = status_dev ? status_dev + c0 : at<uint32_t>(ws, L.status);
+    if ((rc = sp_launch_lin_gram(nb, K, q, sys + (size_t)(K + Ks) * ld, stride, ld, sys, stride, ld + 1, stars, info,
+                                 gpart, st)))
+      return rc;
+    if ((rc = sp_launch_lin_finish(nb, K, q, gpart, nullptr, basis_var_dev + (size_t)c0 * q, stars, nullptr, info, 0, 0.0,
+                                   lnl, lnl0, wmean, nullptr, mix, status, st)))
+      return rc;
+    hipLaunchKernelGGL(predict_linear_flags_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, nb, info, status, bad);
+    SP_LAUNCH_CHECK();
+    const double *mean = at<double>(ws, L.mean);
+    const double *kss = conditional ? at<double>(ws, L.kss) : at<double>(ws, L.kss0);
+    const double *bs = basis_sample_dev ? basis_sample_dev + (size_t)c0 * Ks * q : nullptr;
+    const dim3 grid((Ks + PL_JB - 1) / PL_JB, nb);
+    double *mu = mu_dev + (size_t)c0 * Ks;
+    double *var = mode == SP_PREDICT_VAR ? var_dev + (size_t)c0 * Ks : nullptr;
+#define PL_LAUNCH(MT, VAR, ZOUT)                                                                                       \
+  hipLaunchKernelGGL((predict_reduce_linear_kernel<MT, VAR, ZOUT>), grid, dim3(256), 0, st, sys, ld, stride, K, Ks, q, \
+                     bad, stars, mean, kss, conditional ? 1 : 0, bs, wmean, mix, mu, var, Z)
+    if (q <= 16) {
+      if (mode == SP_PREDICT_VAR) PL_LAUNCH(1, true, false);
+      else if (mode == SP_PREDICT_COV) PL_LAUNCH(1, false, true);
+      else PL_LAUNCH(1, false, false);
+    } else {
+      if (mode == SP_PREDICT_VAR) PL_LAUNCH(2, true, false);
+      else if (mode == SP_PREDICT_COV) PL_LAUNCH(2, false, true);
+      else PL_LAUNCH(2, false, false);
+    }
+#undef PL_LAUNCH
+    SP_LAUNCH_CHECK();
+    if (mode == SP_PREDICT_COV) {
+      // K_ss (lower tiles) into the caller's matrix, K_ss -= Y Y^T and K_ss += Z Z^T on the matrix cores, the mirror
+      double *C = cov_dev + (size_t)c0 * skk;
+      PredictAsm a{};
+      a.K = K;
+      a.Ks = Ks;
+      a.covpts = conditional ? 1 : covpts;
+      a.t = t_dev + (size_t)c0 * K;
+      a.ts = in.ts + (size_t)c0 * Ks;
+      a.stars = stars;
+      a.out = C;
+      a.ldo = Ks;
+      a.strideo = skk;
+      a.wide = (Ks & 1) == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
+      const int ntr = (Ks + 63) / 64;
+      if (!conditional) {
+        a.th_t = at<double>(ws, L.th_t);
+        a.th_s = same ? a.th_t : at<double>(ws, L.th_s);
+        a.ptab = at<double>(ws, L.ptab);
+        if ((rc = launch_assemble<true, true>(a, temporal, ntr, nb, st))) return rc;
+      } else {
+        const long sAB = (long)(same ? K : L.Kall) * N;
+        const double *A = at<double>(ws, L.A), *B = at<double>(ws, L.B);
+        if ((rc = sp_launch_gemm_nt(B, N, sAB, A, N, sAB, C, Ks, skk, Ks, Ks, N, 1.0, 0, 1, nb, st))) return rc;
+        if ((rc = launch_assemble<false, true>(a, temporal, ntr, nb, st))) return rc;
+      }
+      const double *Y = sys + (size_t)K * Kp;
+      if ((rc = sp_launch_gemm_nt(Y, ld, stride, Y, ld, stride, C, Ks, skk, Ks, Ks, K, -1.0, 1, 1, nb, st))) return rc;
+      const long sz = (long)Ks * PL_QMAX;
+      if ((rc = sp_launch_gemm_nt(Z, PL_QMAX, sz, Z, PL_QMAX, sz, C, Ks, skk, Ks, Ks, PL_QMAX, 1.0, 1, 1, nb, st)))
+        return rc;
+      // (exactly symmetric; NaN everywhere for a star that did not factor or that the q x q stage flagged)
+      if ((rc = sp_launch_mirror_lower(C, Ks, (long)Ks, skk, nb, st, bad))) return rc;
     }
     if (info_dev)
       SP_HIP(hipMemcpyAsync(info_dev + c0, info, sizeof(int32_t) * nb, hipMemcpyDeviceToDevice, st));

@@ -757,6 +757,61 @@ class Engine(object):
                                                    covpts, tab, meanvar, rta1, temporal, extra)
         return mu, (cov if m == 2 else var), info
 
+    def predict_linear_workspace(self, S, K, Ks, q, covpts=300):
+        """Device scratch of ``predict_linear`` (sp_predict_linear_workspace_bytes): it stops growing with S where a
+        pass of stars is full."""
+        return self._scratch(self._L.sp_predict_linear_workspace_bytes(self._h, int(S), int(K), int(Ks), int(q),
+                                                                       int(covpts)))
+
+    def predict_linear(self, t, ts, flux, stars, basis, basis_var, basis_sample=None, diag=None, conditional=False,
+                       covpts=300, tab=None, meanvar=None, rta1=None, temporal=None, mode=True, workspace=None):
+        """``predict_ensemble`` with q linear regressors per star marginalised out (sp_predict_linear): the model of
+        ``lnlike_linear``, flux = process + U w + noise, w ~ N(0, diag(basis_var)).  The arguments of
+        ``predict_ensemble``, and basis [S, q, K], basis_var [S, q] as ``lnlike_linear`` takes them; basis_sample
+        [S, Ks, q]: the regressors at the sample times, or None -- the process alone, the trend removed, the
+        uncertainty of the weights still carried.  Returns (mu [S, Ks], cov [S, Ks, Ks] / var [S, Ks] / None by
+        ``mode``, info [S], w_mean [S, q], lnlike [S], lnlike0 [S], status [S]) on the device.  A star whose
+        covariance does not factor (info != 0, SP_STAR_NOT_PD) or that holds a NaN (SP_STAR_NAN) has NaN outputs.
+        workspace: a byte tensor (``predict_linear_workspace``); a smaller one makes the passes of stars shorter."""
+        torch = _torch()
+        m = self._predict_mode(mode)
+        t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional)
+        S, K = flux.shape
+        ts = None if ts is None else self.f64(ts)
+        if ts is not None and (ts.dim() != 2 or ts.shape[0] != S or ts.shape[1] < 1):
+            raise ValueError("ts must be (S, Ks)")
+        Ks = K if ts is None else int(ts.shape[1])
+        basis, basis_var = self.f64(basis), self.f64(basis_var)
+        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
+            raise ValueError("`basis` must be (S, q, K)")
+        q = int(basis.shape[1])
+        if not 1 <= q <= 32:
+            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
+        if tuple(basis_var.shape) != (S, q):
+            raise ValueError("`basis_var` must be (S, q)")
+        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        if basis_sample is not None:
+            basis_sample = self.f64(basis_sample)
+            if tuple(basis_sample.shape) != (S, Ks, q):
+                raise ValueError("`basis_sample` must be (S, Ks, q)")
+            basis_sample = basis_sample.contiguous()
+        mu = self.empty(S, Ks)
+        var = self.empty(S, Ks) if m == 1 else None
+        cov = self.empty(S, Ks, Ks) if m == 2 else None
+        info = torch.zeros(S, dtype=torch.int32, device=self.device)
+        wmean, lnlike, lnlike0 = self.empty(S, q), self.empty(S), self.empty(S)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S > 0:
+            if workspace is None:
+                workspace = self.predict_linear_workspace(S, K, Ks, q, covpts)
+            check(self._L.sp_predict_linear(
+                self._h, S, K, Ks, q, self._p(t), self._p(ts), self._p(flux), self._p(diag), self._p(sd),
+                self._p(basis), self._p(basis_sample), self._p(basis_var), conditional, int(covpts), self._p(tab),
+                self._p(meanvar), self._p(rta1), TEMPORAL[temporal], m, self._p(mu), self._p(var), self._p(cov),
+                self._p(info), self._p(wmean), self._p(lnlike), self._p(lnlike0), self._p(status),
+                self._p(workspace), int(workspace.numel()), self._stream()))
+        return mu, (cov if m == 2 else var), info, wmean, lnlike, lnlike0, status
+
     def ylm_precision(self, mean_ylm, cov_ylm):
         """(Sigma_y^-1, Sigma_y^-1 mu_y) the way the reference forms them (sp.py:267-271: cho_factor, then
         cho_solve against I and mu_y), on the device.  NaN if Sigma_y is not positive definite."""

@@ -1,9 +1,11 @@
 """Host builders of regressor matrices for ``StarryProcess.log_likelihood_linear`` and
 ``log_likelihood_linear_ensemble``: per-segment offsets (Kepler quarters, TESS sectors) and slow per-segment trends.
-Each returns a ``(K, q)`` float64 array, one regressor per column; ``stack_bases`` puts them side by side."""
+Each returns a ``(K, q)`` float64 array, one regressor per column; ``stack_bases`` puts them side by side.
+``offset_basis_at`` and ``polynomial_basis_at`` evaluate the same columns at other times (``predict_ensemble``'s
+``basis_sample``)."""
 import numpy as np
 
-__all__ = ["offset_basis", "polynomial_basis", "stack_bases"]
+__all__ = ["offset_basis", "polynomial_basis", "offset_basis_at", "polynomial_basis_at", "stack_bases"]
 
 
 def check_regressors(basis, basis_var, S, K):
@@ -87,6 +89,58 @@ def polynomial_basis(t, degree, edges=None):
         x = 2.0 * (ts - ts.min()) / span - 1.0
         V = np.polynomial.legendre.legvander(x, degree)
         U[ed[j]:ed[j + 1], j * degree:(j + 1) * degree] = V[:, 1:]
+    return U
+
+
+def _segment_of(t_sample, t, edges):
+    """(ts, t, ed, seg): the sample times (1-D float64), the cadences (strictly increasing), the checked edges and the
+    segment of every sample time: j when t[e_j] <= ts < t[e_j+1]; before the first cadence the first segment, after
+    the last cadence the last."""
+    t = np.asarray(t, dtype=np.float64)
+    ts = np.asarray(t_sample, dtype=np.float64)
+    if t.ndim != 1 or t.size < 1 or not np.all(np.isfinite(t)):
+        raise ValueError("`t` must be a finite 1-D array")
+    if np.any(np.diff(t) <= 0):
+        raise ValueError("`t` must be strictly increasing")
+    if ts.ndim != 1 or ts.size < 1 or not np.all(np.isfinite(ts)):
+        raise ValueError("`t_sample` must be a finite 1-D array")
+    ed = _segment_edges(edges, t.size)
+    seg = np.clip(np.searchsorted(t[ed[:-1]], ts, side="right") - 1, 0, ed.size - 2)
+    return ts, t, ed, seg
+
+
+def offset_basis_at(t_sample, t, edges):
+    """The columns of ``offset_basis(len(t), edges)`` at the times ``t_sample``: column j is 1 where the sample time
+    belongs to segment j -- t[e_j] <= t_sample < t[e_j+1]; times before the first cadence belong to the first segment,
+    times after the last cadence to the last.  ``t``: the strictly increasing cadences the edges index.  Returns
+    (Ks, n); ``offset_basis_at(t, t, edges)`` is ``offset_basis(len(t), edges)`` bit for bit."""
+    ts, t, ed, seg = _segment_of(t_sample, t, edges)
+    U = np.zeros((ts.size, ed.size - 1))
+    U[np.arange(ts.size), seg] = 1.0
+    return U
+
+
+def polynomial_basis_at(t_sample, t, degree, edges=None):
+    """The columns of ``polynomial_basis(t, degree, edges)`` at the times ``t_sample``: the Legendre columns of the
+    segment a sample time belongs to (``offset_basis_at``'s rule) in that segment's own rescaled time -- outside the
+    segment's cadences the polynomials are extrapolated -- and zeros in the other segments' columns.  A segment of
+    one cadence has zero columns, as in ``polynomial_basis``.  Returns (Ks, n degree);
+    ``polynomial_basis_at(t, t, degree, edges)`` is ``polynomial_basis(t, degree, edges)`` bit for bit."""
+    degree = int(degree)
+    if degree < 1:
+        raise ValueError("`degree` must be at least 1")
+    ts, t, ed, seg = _segment_of(t_sample, t, edges)
+    n = ed.size - 1
+    U = np.zeros((ts.size, n * degree))
+    for j in range(n):
+        tj = t[ed[j]:ed[j + 1]]
+        span = tj.max() - tj.min()
+        if not span > 0:
+            continue
+        own = seg == j
+        x = 2.0 * (ts[own] - tj.min()) / span - 1.0
+        V = np.polynomial.legendre.legvander(x, degree)
+        U[own, j * degree:(j + 1) * degree] = V[:, 1:]
     return U
 
 

@@ -652,13 +652,18 @@ class StarryProcess(object):
         return Eager(np.array(mu)[None, :] + (L @ z).T)
 
     # -- conditioning on the data of an ensemble: S stars in one device call (sp_predict_ensemble) -----------
-    def _predict_ensemble_dev(self, t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var, mode):
-        """(mu, cov / var / None, info) as device tensors: the arguments of the ensemble calls through the engine."""
+    def _predict_ensemble_dev(self, t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var, mode,
+                              basis=None, basis_var=None, basis_sample=None):
+        """(mu, cov / var / None, info) as device tensors: the arguments of the ensemble calls through the engine.
+        With ``basis``: ``Engine.predict_linear`` in place of ``Engine.predict_ensemble`` -- its whole tuple, (mu,
+        second, info, w_mean, lnlike, lnlike0, status); the regressor arguments are checked on the host before any
+        device work."""
         if self._normalized:
             raise NotImplementedError("Method not implemented when the flux is normalized.")
-        e, f = self._engine, self._flux
+        if basis is None and (basis_var is not None or basis_sample is not None):
+            raise ValueError("`basis_var` and `basis_sample` need a `basis`")
         t, flux, stars, utab, diag = self._ensemble_args(t, flux, data_cov, i, p, u, baseline_mean, baseline_var)
-        S = flux.shape[0]
+        S, K = flux.shape
         ts = None
         if t_sample is not None:
             ts = np.asarray(t_sample, dtype=np.float64)
@@ -667,17 +672,39 @@ class StarryProcess(object):
             elif ts.ndim != 2 or ts.shape[0] != S or ts.shape[1] < 1:
                 raise ValueError("`t_sample` must be (Ks,) or (S, Ks) with S = %d, not %s" % (S, ts.shape))
             ts = np.ascontiguousarray(ts)
+        if basis is not None:
+            from .linear import check_regressors
+
+            if basis_var is None:
+                raise ValueError("`basis` needs a `basis_var`")
+            U, lam = check_regressors(basis, basis_var, S, K)
+            q, Ks = U.shape[2], (K if ts is None else ts.shape[1])
+            Us = None
+            if basis_sample is not None:
+                Us = np.asarray(basis_sample, dtype=np.float64)
+                if Us.shape == (Ks, q):
+                    Us = np.broadcast_to(Us, (S, Ks, q))
+                if Us.shape != (S, Ks, q):
+                    raise ValueError("`basis_sample` must be (Ks, q) or (S, Ks, q) with S = %d, Ks = %d, q = %d, not %s"
+                                     % (S, Ks, q, np.shape(basis_sample)))
+                if not np.all(np.isfinite(Us)):
+                    raise ValueError("`basis_sample` must be finite")
+                Us = np.ascontiguousarray(Us)
+        e, f = self._engine, self._flux
         f._bind()
         rta1 = e.f64(e.rTA1L(utab))
         tab = mv = None
         if self._marginalize_over_inclination:
             tab, mv = e.kernel_table(rta1, self._covpts)
-        return e.predict_ensemble(t, ts, flux, stars, diag=diag, conditional=not self._marginalize_over_inclination,
-                                  covpts=self._covpts, tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal,
-                                  mode=mode)
+        branch = dict(diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
+                      meanvar=mv, rta1=rta1, temporal=self._temporal, mode=mode)
+        if basis is not None:
+            Ut = e.f64(np.ascontiguousarray(np.swapaxes(U, 1, 2)))          # [S, q, K]: a regressor along a row
+            return e.predict_linear(t, ts, flux, stars, Ut, lam, None if Us is None else e.f64(Us), **branch)
+        return e.predict_ensemble(t, ts, flux, stars, **branch)
 
     def predict_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
-                         baseline_var=0.0, return_cov=True):
+                         baseline_var=0.0, return_cov=True, basis=None, basis_var=None, basis_sample=None):
         """``predict`` for S stars in one device call: the light curve distributions conditioned on the observed
         fluxes, each star with its own period, inclination, limb darkening, baseline and noise.
 
@@ -686,24 +713,34 @@ class StarryProcess(object):
         return_cov=True: (mu (S, Ks), cov (S, Ks, Ks)), each covariance exactly symmetric; "diag": (mu, var (S, Ks))
         without forming any Ks x Ks matrix; False: mu alone.  A star whose covariance at the observed times does
         not factor gets NaN in all its outputs (``predict``'s rule, per star).  Not implemented for normalized
-        processes, as in the reference."""
+        processes, as in the reference.
+
+        ``basis`` (K, q) shared or (S, K, q) and ``basis_var`` scalar, (q,) or (S, q), as
+        ``log_likelihood_linear_ensemble`` takes and refuses them: the conditional under the model flux = process +
+        U w + noise, w ~ N(0, diag(basis_var)) (sp_predict_linear), the weights marginalised out and their
+        uncertainty carried into ``cov`` / ``var``.  ``basis_sample`` (Ks, q) or (S, Ks, q): the regressors at the
+        sample times (``linear.offset_basis_at``, ``linear.polynomial_basis_at``) -- the prediction is then process
+        + trend, what the data will look like; None: the process alone, the trend removed.  Without ``basis``
+        nothing changes."""
         if not (return_cov is True or return_cov is False or (isinstance(return_cov, str) and return_cov == "diag")):
             raise ValueError("`return_cov` must be True, False or \"diag\"")
-        mu, second, _ = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
-                                                  return_cov)
+        mu, second = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
+                                                return_cov, basis, basis_var, basis_sample)[:2]
         if return_cov is False:
             return Eager(mu.cpu().numpy())
         return Eager(mu.cpu().numpy()), Eager(second.cpu().numpy())
 
     def sample_conditional_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
-                                    baseline_var=0.0, nsamples=1, eps=1e-12, seed=None):
+                                    baseline_var=0.0, nsamples=1, eps=1e-12, seed=None, basis=None, basis_var=None,
+                                    basis_sample=None):
         """Samples from the conditional distributions of S stars, shape (S, nsamples, Ks): ``predict_ensemble``, then
         mu_s + L_s z_s with L_s the Cholesky factor of the posterior covariance + eps I (one batched factorisation)
         and z = RandomState(seed).randn(S, Ks, nsamples) -- the constructor's seed when ``seed`` is None; with one
-        star, the deviates ``sample_conditional`` draws.  The product runs on the device."""
+        star, the deviates ``sample_conditional`` draws.  The product runs on the device.  ``basis``, ``basis_var``
+        and ``basis_sample`` as ``predict_ensemble`` takes them."""
+        mu, cov = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
+                                             True, basis, basis_var, basis_sample)[:2]
         e = self._engine
-        mu, cov, _ = self._predict_ensemble_dev(t, flux, data_cov, t_sample, i, p, u, baseline_mean, baseline_var,
-                                                True)
         S, Ks = mu.shape
         nsamples = int(nsamples)
         cov.diagonal(dim1=1, dim2=2).add_(float(eps))
