@@ -838,10 +838,12 @@ class Engine(object):
         S, K = flux.shape
         sd = self.stars_to_device(stars)
         diag = None if diag is None else self.f64(diag)
+        # (held until the call is enqueued: an upload that is dropped at once gives its block to the next one)
+        rta1, sinv, sinvmu = self.f64(rta1), self.f64(sinv), self.f64(sinvmu)
         ws, ymu, ycov, ycho, status = self._ylm_buffers(S, K, with_cho)
         check(self._L.sp_ylm_conditional_batched(
-            self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(self.f64(rta1)),
-            self._p(self.f64(sinv)), self._p(self.f64(sinvmu)), self._p(ymu), self._p(ycov), self._p(ycho),
+            self._h, S, K, self._p(t), self._p(flux), self._p(diag), self._p(sd), self._p(rta1),
+            self._p(sinv), self._p(sinvmu), self._p(ymu), self._p(ycov), self._p(ycho),
             self._p(status), self._p(ws), self._stream()))
         return ymu, ycov, ycho, status
 
@@ -850,9 +852,10 @@ class Engine(object):
         r [S, K] = L^-1 (flux - baseline_mean) for a full data covariance C = L L^T."""
         B, r = self.f64(B), self.f64(r)
         S, K, _ = B.shape
+        sinv, sinvmu = self.f64(sinv), self.f64(sinvmu)
         ws, ymu, ycov, ycho, status = self._ylm_buffers(S, K, with_cho)
         check(self._L.sp_ylm_conditional_whitened(
-            self._h, S, K, self._p(B), self._p(r), self._p(self.f64(sinv)), self._p(self.f64(sinvmu)),
+            self._h, S, K, self._p(B), self._p(r), self._p(sinv), self._p(sinvmu),
             self._p(ymu), self._p(ycov), self._p(ycho), self._p(status), self._p(ws), self._stream()))
         return ymu, ycov, ycho, status
 
@@ -1282,10 +1285,11 @@ class Engine(object):
         if ns > state["ns"]:
             raise ValueError("the posterior was computed for at most %d samples per star" % state["ns"])
         z, e = self.f64(z).reshape(S, ns, self.N), self.f64(e).reshape(S, ns, n)
+        cho_ylm = self.f64(cho_ylm)
         y = self.empty(S, ns, self.N)
         check(self._L.sp_ylm_inclination_samples(
             self._h, S, state["ntab"], state["P"], ns, self._p(state["stars"]), self._p(state["mean_ylm"]),
-            self._p(self.f64(cho_ylm)), self._p(comp), self._p(z), self._p(e), self._p(y), self._p(state["ws"]),
+            self._p(cho_ylm), self._p(comp), self._p(z), self._p(e), self._p(y), self._p(state["ws"]),
             self._stream()))
         return y
 
