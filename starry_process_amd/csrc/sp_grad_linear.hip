@@ -16,8 +16,8 @@
 //                      (NC = 4 + q rounded up to 16) by v_mfma_f64_16x16x4_f64, one writer per (block, slot)
 //   gl_panel_reduce    the slots added in their order -> vec [S][NC][K] (a column per row: the layout of sp_grad.hip)
 //   gl_gram_kernel     [r, u_1 .. u_q]^T [alpha, C^-1 u_1 .. C^-1 u_q], lower pairs, a fixed order per pair
-//   gl_finish_kernel   one wavefront per star, in LDS: G_q, L_G, v, L_G^-1, tr G_q^-1, g, diag H, w_mean, lnL, and the
-//                      mixing matrix D L_G^-T
+//   gl_finish_kernel   one wavefront per star, in LDS: the q x q stage it shares with sp_linear.hip (sp_linq.h: G_q, L_G,
+//                      v, L_G^-1), then tr G_q^-1, g, diag H, w_mean, lnL, and the mixing matrix D L_G^-T
 //   gl_mix_kernel      alpha~ and Z in place of alpha and C^-1 U in the panel
 //   (sp_grad.hip)      the scalars under "C^-1 counts once, forms are summed over B"
 //   gl_scatter_kernel  one workgroup per lower tile: the 64 x 64 block of B B^T on the matrix cores, then the scatter into
@@ -27,13 +27,11 @@
 // writer: the same bits run after run, a star's bits independent of its neighbours and its position.
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_linq.h"
 #include "sp_mm.h"
-#include "sp_sweep.h"
 
 namespace {
 
-constexpr int GL_QMAX = 32;                 // regressors per star
-constexpr int GL_RMAX = GL_QMAX + 1;        // columns of B; rows of the Gram matrix
 constexpr int GL_BLD = 37;                  // LDS row of a tile edge's B rows: 1 + q padded to 4, <= 36; odd
 constexpr int GL_TC = 64;                   // cadences of the Gram kernel's rows staged at a time
 constexpr int GL_LDS_BUDGET = 24 * 1024;    // dynamic LDS of the scatter (bins, table) beside its 37 KB of B rows
@@ -156,18 +154,13 @@ __global__ __launch_bounds__(256) void gl_gram_kernel(int K, int q, int NC, cons
                                                       const sp_star *__restrict__ stars,
                                                       const SpCoef *__restrict__ coef, const double *__restrict__ vec,
                                                       double *__restrict__ gram) {
-  __shared__ double TL[GL_RMAX][GL_TC + 1], TR[GL_RMAX][GL_TC + 1];
+  __shared__ double TL[SP_LIN_RMAX][sp_linq_tile_ld(GL_TC)], TR[SP_LIN_RMAX][sp_linq_tile_ld(GL_TC)];
   const int s = blockIdx.x, tid = threadIdx.x, R = q + 1, np = R * (R + 1) / 2;
   const double shift = coef[s].gpmean + stars[s].baseline_mean;
   const double *V = vec + ((size_t)s * NC + 3) * K;
   int pa[3], pb[3];
   double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int p = tid + 256 * k;
-    pa[k] = pb[k] = 0;
-    if (p < np) sp_lower_tile_decode(p, pa[k], pb[k]);
-  }
+  sp_linq_pairs(tid, np, pa, pb);
   for (int t0 = 0; t0 < K; t0 += GL_TC) {
     __syncthreads();
     for (int e = tid; e < R * GL_TC; e += 256) {
@@ -181,23 +174,15 @@ __global__ __launch_bounds__(256) void gl_gram_kernel(int K, int q, int NC, cons
       TR[a][c] = r;
     }
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (tid + 256 * k >= np) continue;
-      const double *ra = TL[pa[k]], *rb = TR[pb[k]];
-      double a = acc[k];
-#pragma unroll 8
-      for (int c = 0; c < GL_TC; ++c) a += ra[c] * rb[c];
-      acc[k] = a;
-    }
+    sp_linq_tile_dots<GL_TC>(tid, np, &TL[0][0], &TR[0][0], pa, pb, acc);
   }
 #pragma unroll
   for (int k = 0; k < 3; ++k)
     if (tid + 256 * k < np) gram[(size_t)s * np + tid + 256 * k] = acc[k];
 }
 
-// The q x q stage, one wavefront per star, in LDS (the Cholesky factor, the two solves and L_G^-1 as lin_finish_kernel
-// takes them: a lane per row, the solved entry round by a shuffle).  Leaves for the kernels behind it
+// The q x q stage, one wavefront per star, in LDS (sp_linq.h: the Cholesky factor, the two solves and L_G^-1, the code
+// lin_finish_kernel runs), then what is this kernel's own: |x|^2, tr G_q^-1, g and diag H.  Leaves for the kernels behind it
 //   lin [S][SP_GRAD_LIN_SCAL]: sum_b b^T C b = r^T alpha~ - |L_G^-T v|^2 + q - tr G_q^-1 (from D U^T alpha~ = L_G^-T v), lnL,
 //                              the NaN flag;
 //   mix [S][q][q]: mix[k][j] = d_k (L_G^-1)[j][k], j >= k, else 0 -- Z = (C^-1 U) mix;   wm [S][q]: w_mean = D L_G^-T v
@@ -212,81 +197,26 @@ __global__ __launch_bounds__(64) void gl_finish_kernel(int K, int q, const doubl
                                                        double *__restrict__ lin, double *__restrict__ mix,
                                                        double *__restrict__ wm, double *__restrict__ lambar,
                                                        double *__restrict__ wmean) {
-  constexpr int LD = GL_RMAX + 1;
-  __shared__ double Mg[GL_RMAX * LD];     // the Gram matrix, both triangles: [0][0] r.alpha, [1 + j][0] u_j.alpha, [1 + j][1 + k] P
-  __shared__ double G[GL_QMAX * LD];      // G_q, then L_G (lower triangle)
-  __shared__ double X[GL_QMAX * LD];      // L_G^-1 (lower triangle)
-  __shared__ double dv[GL_QMAX], xw[GL_QMAX];
-  __shared__ int bad;
+  constexpr int LD = SP_LINQ_LD;
+  __shared__ SpLinqLds W;
+  __shared__ double xw[SP_LIN_QMAX];
   const int s = blockIdx.x, lane = threadIdx.x, R = q + 1, np = R * (R + 1) / 2;
   const sp_star st = stars[s];
   const bool ragged = st.nobs > 0 && st.nobs < K;
   const bool rej = info[s] != 0 || (normalized && coef[s].z > zmax);
   const double nanv = __builtin_nan("");
-  for (int p = lane; p < np; p += 64) {
-    int ia, ib;
-    sp_lower_tile_decode(p, ia, ib);
-    const double a = gram[(size_t)s * np + p];
-    Mg[ia * LD + ib] = a;
-    Mg[ib * LD + ia] = a;
-  }
-  for (int e = lane; e < GL_QMAX * LD; e += 64) X[e] = 0.0;
-  if (lane < q) dv[lane] = sqrt(bvar[(size_t)s * q + lane]);
-  if (lane == 0) bad = 0;
-  __syncthreads();
-  double hk = 0.0;   // lane k: h_k, then v_k, then x_k = (L_G^-T v)_k (zero beyond the regressors)
-  if (lane < q) {
-    const double di = dv[lane];
-    for (int j = 0; j <= lane; ++j) G[lane * LD + j] = (lane == j ? 1.0 : 0.0) + (di * dv[j]) * Mg[(1 + lane) * LD + 1 + j];
-    hk = di * Mg[(1 + lane) * LD];
-  }
-  // L_G, right-looking: column j scaled by its pivot, then every row below takes its rank-one update
-  for (int j = 0; j < q; ++j) {
-    __syncthreads();
-    const double pj = G[j * LD + j];
-    if (!(pj > 0.0)) {   // (G_q >= I: only a NaN or an overflow gets here)
-      if (lane == 0) bad = 1;
-      break;
-    }
-    const double ljj = sqrt(pj);
-    double lij = 0.0;
-    if (lane > j && lane < q) lij = G[lane * LD + j] / ljj;
-    __syncthreads();
-    if (lane == j) G[j * LD + j] = ljj;
-    if (lane > j && lane < q) G[lane * LD + j] = lij;
-    __syncthreads();
-    if (lane > j && lane < q)
-      for (int k = j + 1; k <= lane; ++k) G[lane * LD + k] -= lij * G[k * LD + j];
-  }
-  __syncthreads();
-  const bool chol_ok = bad == 0;
-  double q2 = nanv, slg = nanv, x2 = nanv, trg = nanv;
+  // (X zeroed first: a failed factorisation stores defined values)
+  for (int e = lane; e < SP_LIN_QMAX * LD; e += 64) W.X[e] = 0.0;
+  double hk, q2, slg;   // lane k: x_k = (L_G^-T v)_k;  v^T v;  sum log (L_G)_jj
+  const bool chol_ok = sp_linq_stage(
+      W, q, lane, [&](int p) { return gram[(size_t)s * np + p]; }, bvar + (size_t)s * q, true, hk, q2, slg);
+  const double *Mg = W.Mg, *X = W.X, *dv = W.dv;
+  double x2 = nanv, trg = nanv;
   if (chol_ok) {
-    for (int i = 0; i < q; ++i) {
-      const double vi = __shfl(hk, i, 64) / G[i * LD + i];
-      if (lane == i) hk = vi;
-      else if (lane > i && lane < q) hk -= G[lane * LD + i] * vi;
-    }
-    q2 = __shfl(sp_wave_sum(hk * hk), 0, 64);
-    slg = __shfl(sp_wave_sum(lane < q ? log(G[lane * LD + lane]) : 0.0), 0, 64);
-    for (int i = q - 1; i >= 0; --i) {
-      const double xi = __shfl(hk, i, 64) / G[i * LD + i];
-      if (lane == i) hk = xi;
-      else if (lane < i) hk -= G[i * LD + lane] * xi;
-    }
     x2 = __shfl(sp_wave_sum(hk * hk), 0, 64);
     double tj = 0.0;
-    if (lane < q) {
-      // column `lane` of L_G^-1, and its part of tr G_q^-1 = |L_G^-1|_F^2
-      const int j = lane;
-      X[j * LD + j] = 1.0 / G[j * LD + j];
-      for (int i = j + 1; i < q; ++i) {
-        double a = 0.0;
-        for (int k = j; k < i; ++k) a += G[i * LD + k] * X[k * LD + j];
-        X[i * LD + j] = -a / G[i * LD + i];
-      }
-      for (int i = j; i < q; ++i) tj += X[i * LD + j] * X[i * LD + j];
-    }
+    if (lane < q)   // column `lane`'s part of tr G_q^-1 = |L_G^-1|_F^2
+      for (int i = lane; i < q; ++i) tj += X[i * LD + lane] * X[i * LD + lane];
     trg = __shfl(sp_wave_sum(tj), 0, 64);
   }
   if (lane < q) xw[lane] = dv[lane] * hk;
@@ -312,8 +242,8 @@ __global__ __launch_bounds__(64) void gl_finish_kernel(int K, int q, const doubl
     if (lambar) lambar[(size_t)s * q + j] = ragged ? nanv : (rej ? 0.0 : (isnan_ ? nanv : lam));
     if (wmean) wmean[(size_t)s * q + j] = ragged ? nanv : (rej ? 0.0 : (isnan_ ? nanv : xw[j]));
     wm[(size_t)s * q + j] = xw[j];
-    for (int k = 0; k < q; ++k) mix[((size_t)s * q + k) * q + j] = j >= k ? dv[k] * X[j * LD + k] : 0.0;
   }
+  sp_linq_store_mix(W, q, lane, mix + (size_t)s * q * q, q, q);
   if (lane == 0) {
     double *o = lin + (size_t)s * SP_GRAD_LIN_SCAL;
     o[0] = forms;
@@ -328,7 +258,7 @@ __global__ __launch_bounds__(64) void gl_finish_kernel(int K, int q, const doubl
 // grid (ceil(K / 256), S)
 __global__ __launch_bounds__(256) void gl_mix_kernel(int K, int q, int NC, const double *__restrict__ mix,
                                                      const double *__restrict__ wm, double *__restrict__ vec) {
-  __shared__ double ms[GL_QMAX * GL_QMAX], ws[GL_QMAX];
+  __shared__ double ms[SP_LIN_QMAX * SP_LIN_QMAX], ws[SP_LIN_QMAX];
   const int s = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   for (int e = threadIdx.x; e < q * q; e += 256) ms[e] = mix[(size_t)s * q * q + e];
   if (threadIdx.x < q) ws[threadIdx.x] = wm[(size_t)s * q + threadIdx.x];
@@ -493,7 +423,7 @@ inline int gl_bin_copies(int covpts) {
 extern "C" {
 
 size_t sp_lnlike_grad_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts) {
-  if (!h || S < 0 || K < 2 || q < 1 || q > GL_QMAX || covpts < 1) return 0;
+  if (!h || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX || covpts < 1) return 0;
   return grad_lin_layout(h, S, K, q, covpts).total;
 }
 
@@ -505,7 +435,7 @@ int sp_lnlike_grad_linear(sp_handle *h, int S, int K, int q, const double *t_dev
                           double *starbar_dev, double *lambar_dev, double *wmean_dev, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !basis_dev || !basis_var_dev || !workspace_dev || !lnlike_dev ||
-      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || q < 1 || q > GL_QMAX || norm_order < 0 ||
+      !ybar_dev || !meanbar_dev || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX || norm_order < 0 ||
       norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
   if (const int rc = sp_branch_check(h, 0, nullptr, tab_dev, meanvar_dev, covpts)) return rc;

@@ -15,11 +15,12 @@
 #include <vector>
 
 #include "sp_internal.h"
-#include "sp_sweep.h"
+#include "sp_linq.h"
 
 namespace {
 
-constexpr int LBL_QMAX = 32;     // regressors per star, and the columns of T
+constexpr int LBL_MLD = SP_LIN_QMAX + 1;   // row stride of the mixing matrix in LDS (SP_LIN_QMAX: also the columns of T)
+static_assert(SP_LIN_QMAX == 32, "lbl_mix_kernel deals T's columns 32 to a row of threads (tid & 31, 8 rows a pass)");
 constexpr int LBL_CS = 64;       // columns of Y a workgroup of the column pass owns (wavefront w: 16 w .. 16 w + 15)
 constexpr int LBL_KB = 32;       // rows of Y per tile
 constexpr int LBL_YLD = 80;      // row stride of a tile of Y in LDS: the rows k, k + 1 of a fragment read fall in
@@ -114,9 +115,9 @@ __global__ __launch_bounds__(256) void lbl_mix_kernel(int K, int q, const double
                                                       const sp_star *__restrict__ stars,
                                                       const int32_t *__restrict__ info, double *__restrict__ T,
                                                       double *__restrict__ rows) {
-  __shared__ double Ws[LBL_QMAX * 65];
-  __shared__ double Ms[LBL_QMAX * (LBL_QMAX + 1)];
-  __shared__ double wm[LBL_QMAX];
+  __shared__ double Ws[SP_LIN_QMAX * 65];
+  __shared__ double Ms[SP_LIN_QMAX * LBL_MLD];
+  __shared__ double wm[SP_LIN_QMAX];
   const int s = blockIdx.y, tid = threadIdx.x, jb = 64 * blockIdx.x;
   const sp_star sr = stars[s];
   double *yt = rows + ((size_t)s * 4 + 3) * K;
@@ -129,16 +130,16 @@ __global__ __launch_bounds__(256) void lbl_mix_kernel(int K, int q, const double
     const int a = e >> 6, jl = e & 63;
     Ws[a * 65 + jl] = jb + jl < K ? R[(size_t)(1 + a) * Kw + jb + jl] : 0.0;
   }
-  for (int e = tid; e < q * LBL_QMAX; e += 256)
-    Ms[(e >> 5) * (LBL_QMAX + 1) + (e & 31)] = mix[(size_t)s * LBL_QMAX * LBL_QMAX + e];
+  for (int e = tid; e < q * SP_LIN_QMAX; e += 256)
+    Ms[(e / SP_LIN_QMAX) * LBL_MLD + e % SP_LIN_QMAX] = mix[(size_t)s * SP_LIN_QMAX * SP_LIN_QMAX + e];
   if (tid < q) wm[tid] = wmean[(size_t)s * q + tid];
   __syncthreads();
   const int c = tid & 31;
   for (int jl = tid >> 5; jl < 64; jl += 8) {
     if (jb + jl >= K) break;
     double v = 0.0;
-    for (int a = 0; a < q; ++a) v = fma(Ws[a * 65 + jl], Ms[a * (LBL_QMAX + 1) + c], v);
-    T[((size_t)s * K + jb + jl) * LBL_QMAX + c] = v;
+    for (int a = 0; a < q; ++a) v = fma(Ws[a * 65 + jl], Ms[a * LBL_MLD + c], v);
+    T[((size_t)s * K + jb + jl) * SP_LIN_QMAX + c] = v;
   }
   if (tid < 64 && jb + tid < K) {
     double v = 0.0;
@@ -168,8 +169,8 @@ LblLayout lbl_layout(const sp_handle *h, int S, int K, int q, int conditional, i
   G.bad = c.take(sizeof(int32_t) * (size_t)S * nblocks);
   G.rw = c.take(sizeof(double) * (size_t)S * (1 + q) * sp_roundup(K, 2));      // y, then the rows of W^T
   G.gpart = c.take(sp_lin_gpart_bytes(S, K, q));
-  G.mix = c.take(sizeof(double) * (size_t)S * LBL_QMAX * LBL_QMAX);
-  G.T = c.take(sizeof(double) * (size_t)S * K * LBL_QMAX);
+  G.mix = c.take(sizeof(double) * (size_t)S * SP_LIN_QMAX * SP_LIN_QMAX);
+  G.T = c.take(sizeof(double) * (size_t)S * K * SP_LIN_QMAX);
   G.total = c.off;
   return G;
 }
@@ -179,7 +180,7 @@ LblLayout lbl_layout(const sp_handle *h, int S, int K, int q, int conditional, i
 extern "C" {
 
 size_t sp_lbo_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts, int conditional, int nblocks) {
-  if (!h || S < 0 || K < 2 || q < 1 || q > LBL_QMAX || (!conditional && covpts < 1) || nblocks < 1 || nblocks > K)
+  if (!h || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX || (!conditional && covpts < 1) || nblocks < 1 || nblocks > K)
     return 0;
   return lbl_layout(h, S, K, q, conditional, nblocks).total;
 }
@@ -192,7 +193,7 @@ int sp_lbo_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const 
                   uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !basis_dev || !basis_var_dev || !edges_dev || !rows_dev || !lpd_dev ||
-      !lnlike_dev || !lnlike0_dev || !wmean_dev || !workspace_dev || S < 0 || K < 2 || q < 1 || q > LBL_QMAX ||
+      !lnlike_dev || !lnlike0_dev || !wmean_dev || !workspace_dev || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX ||
       nblocks < 1 || nblocks > K || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
   if (const int rc = sp_branch_check(h, conditional, rta1_dev, tab_dev, meanvar_dev, covpts)) return rc;

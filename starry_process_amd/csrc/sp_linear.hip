@@ -13,16 +13,16 @@
 // star finishes the q x q system in LDS.  Every sum has a fixed order (registers, LDS, the chunks of a star one after
 // another), every output element one writer: no atomics, the same bits run after run, a star's bits independent of its
 // neighbours, its position and the grouping.  The Gram pass and the finish take the rows' base pointer and strides and are
-// exported (sp_launch_lin_gram, sp_launch_lin_finish): sp_lbo_linear.hip runs them on its own rows [y; W^T].
+// exported (sp_launch_lin_gram, sp_launch_lin_finish): sp_lbo_linear.hip and sp_predict.hip run them on their own rows
+// [y; W^T].  Their pair ownership, tile product and q x q stage are sp_linq.h's, which the gradient sweep
+// (sp_grad_linear.hip) calls too: one copy, the same bits in both.
 #include "sp_internal.h"
-#include "sp_sweep.h"
+#include "sp_linq.h"
 
 namespace {
 
-constexpr int LIN_QMAX = 32;                 // regressors per star
-constexpr int LIN_RMAX = LIN_QMAX + 1;       // riding rows: the residual, then the regressors
 constexpr int LIN_TC = 128;                  // columns of the riding rows staged in LDS at a time
-constexpr int LIN_TLD = LIN_TC + 1;          // (odd: the rows of a tile start in different banks)
+constexpr int LIN_TLD = sp_linq_tile_ld(LIN_TC);   // the row stride sp_linq_tile_dots<LIN_TC> reads a tile with
 constexpr int LIN_CHUNK = 512;               // columns per workgroup once a star's columns are split
 constexpr int LIN_SPLIT_K = 1000;            // ... which they are from this K on
 
@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int chunk, 
                                                        long sstride, long rstride, const double *__restrict__ diag,
                                                        long dstride, long dstep, const sp_star *__restrict__ stars,
                                                        const int32_t *__restrict__ info, double *__restrict__ gpart) {
-  __shared__ double T[LIN_RMAX * LIN_TLD];
+  __shared__ double T[SP_LIN_RMAX * LIN_TLD];
   __shared__ double red[4];
   const int s = blockIdx.y, tid = threadIdx.x, R = q + 1, np = R * (R + 1) / 2;
   const sp_star st = stars[s];
@@ -77,12 +77,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int chunk, 
   const double *Y = rows + (size_t)s * sstride;
   int pa[3], pb[3];
   double acc[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int p = tid + 256 * k;
-    pa[k] = pb[k] = 0;
-    if (p < np) sp_lower_tile_decode(p, pa[k], pb[k]);
-  }
+  sp_linq_pairs(tid, np, pa, pb);
   for (int t0 = c0; t0 < c1; t0 += LIN_TC) {
     const int n = c1 - t0 < LIN_TC ? c1 - t0 : LIN_TC;
     __syncthreads();
@@ -91,15 +86,7 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int chunk, 
       T[a * LIN_TLD + c] = c < n ? Y[(size_t)a * rstride + t0 + c] : 0.0;
     }
     __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      if (tid + 256 * k >= np) continue;
-      const double *ra = T + pa[k] * LIN_TLD, *rb = T + pb[k] * LIN_TLD;
-      double a = acc[k];
-#pragma unroll 8
-      for (int c = 0; c < LIN_TC; ++c) a += ra[c] * rb[c];
-      acc[k] = a;
-    }
+    sp_linq_tile_dots<LIN_TC>(tid, np, T, T, pa, pb, acc);
   }
   double *out = gpart + ((size_t)s * gridDim.x + blockIdx.x) * (np + 1);
 #pragma unroll
@@ -112,9 +99,10 @@ __global__ __launch_bounds__(256) void lin_gram_kernel(int K, int q, int chunk, 
   if (tid == 0) out[np] = lg;
 }
 
-// The finish, one wavefront per star: the chunks' parts added in their order, G = I + D W^T W D and h = D W^T y, the
-// Cholesky factor of G in LDS (a lane per row), v, the two likelihoods, w_mean and, with wcov, L_G^-1 (a lane per
-// column) and w_cov = D L_G^-T L_G^-1 D -- its lower triangle, mirrored: exactly symmetric.  logdet (may be null):
+// The finish, one wavefront per star: the chunks' parts added in their order, the q x q stage (sp_linq.h: G = I + D W^T
+// W D and h = D W^T y, the Cholesky factor of G in LDS, v and, with wcov or mix, L_G^-1), then what is this kernel's
+// own: the two likelihoods, w_mean and w_cov = D L_G^-T L_G^-1 D -- its lower triangle, mirrored: exactly symmetric --
+// and the status word.  A ragged star or one that did not factor returns before it touches the Gram parts.  logdet (may be null):
 // log det C per star, in place of twice the chunks' sums of logarithms.  mix (may be null) [S][32][32]: M = D L_G^-T, upper
 // triangular, zeros around it (w_mean = M v; sp_lbo_linear.hip mixes the rows of W^T with it).  grid (S)
 __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit, const double *__restrict__ gpart,
@@ -126,24 +114,20 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
                                                         double *__restrict__ lnlike, double *__restrict__ lnlike0,
                                                         double *__restrict__ wmean, double *__restrict__ wcov,
                                                         double *__restrict__ mix, uint32_t *__restrict__ status) {
-  constexpr int LD = LIN_RMAX + 1;
-  __shared__ double Mg[LIN_RMAX * LD];     // the Gram matrix of the riding rows, both triangles
-  __shared__ double G[LIN_QMAX * LD];      // G, then L_G (lower triangle)
-  __shared__ double X[LIN_QMAX * LD];      // L_G^-1 (lower triangle)
-  __shared__ double dv[LIN_QMAX];
+  constexpr int LD = SP_LINQ_LD;
+  __shared__ SpLinqLds W;
   __shared__ double sc[1];
-  __shared__ int bad;
   const int s = blockIdx.x, lane = threadIdx.x, R = q + 1, np = R * (R + 1) / 2;
   const sp_star st = stars[s];
   const bool ragged = st.nobs > 0 && st.nobs < K, notpd = info[s] != 0;
   const bool rej = normalized && coef[s].z > zmax;
   const double nanv = __builtin_nan("");
   double *wm = wmean + (size_t)s * q, *wc = wcov ? wcov + (size_t)s * q * q : nullptr;
-  double *mx = mix ? mix + (size_t)s * LIN_QMAX * LIN_QMAX : nullptr;
+  double *mx = mix ? mix + (size_t)s * SP_LIN_QMAX * SP_LIN_QMAX : nullptr;
   if (ragged || notpd) {
     if (lane < q) wm[lane] = nanv;
     if (mx)
-      for (int e = lane; e < LIN_QMAX * LIN_QMAX; e += 64) mx[e] = nanv;
+      for (int e = lane; e < SP_LIN_QMAX * SP_LIN_QMAX; e += 64) mx[e] = nanv;
     if (wc)
       for (int e = lane; e < q * q; e += 64) wc[e] = nanv;
     if (lane == 0) {
@@ -154,79 +138,21 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
     return;
   }
   const double *P = gpart + (size_t)s * nsplit * (np + 1);
-  for (int p = lane; p < np; p += 64) {
-    double a = 0.0;
-    for (int c = 0; c < nsplit; ++c) a += P[(size_t)c * (np + 1) + p];
-    int ia, ib;
-    sp_lower_tile_decode(p, ia, ib);
-    Mg[ia * LD + ib] = a;
-    Mg[ib * LD + ia] = a;
-  }
   if (lane == 0) {
     double lg = 0.0;
     for (int c = 0; c < nsplit; ++c) lg += P[(size_t)c * (np + 1) + np];
     sc[0] = logdet ? 0.5 * logdet[s] : lg;
-    bad = 0;
   }
-  if (lane < q) dv[lane] = sqrt(bvar[(size_t)s * q + lane]);
+  // (a pair's chunk parts added in the order of the chunks)
+  const auto pair = [&](int p) {
+    double a = 0.0;
+    for (int c = 0; c < nsplit; ++c) a += P[(size_t)c * (np + 1) + p];
+    return a;
+  };
+  double hk, q2, slg;   // lane k: x_k = (L_G^-T v)_k;  v^T v;  sum log (L_G)_jj
+  const bool chol_ok = sp_linq_stage(W, q, lane, pair, bvar + (size_t)s * q, wc || mx, hk, q2, slg);
   __syncthreads();
-  double hk = 0.0;   // lane k: h_k, then v_k, then x_k (zero beyond the regressors)
-  if (lane < q) {
-    const double di = dv[lane];
-    for (int j = 0; j <= lane; ++j) G[lane * LD + j] = (lane == j ? 1.0 : 0.0) + (di * dv[j]) * Mg[(1 + lane) * LD + 1 + j];
-    hk = di * Mg[(1 + lane) * LD];
-  }
-  // L_G, right-looking: column j scaled by its pivot, then every row below takes its rank-one update
-  for (int j = 0; j < q; ++j) {
-    __syncthreads();
-    const double pj = G[j * LD + j];
-    if (!(pj > 0.0)) {   // (G >= I: only a NaN or an overflow gets here)
-      if (lane == 0) bad = 1;
-      break;
-    }
-    const double ljj = sqrt(pj);
-    double lij = 0.0;
-    if (lane > j && lane < q) lij = G[lane * LD + j] / ljj;
-    __syncthreads();
-    if (lane == j) G[j * LD + j] = ljj;
-    if (lane > j && lane < q) {
-      G[lane * LD + j] = lij;
-    }
-    __syncthreads();
-    if (lane > j && lane < q)
-      for (int k = j + 1; k <= lane; ++k) G[lane * LD + k] -= lij * G[k * LD + j];
-  }
-  __syncthreads();
-  const bool chol_ok = bad == 0;
-  double q2 = nanv, slg = nanv;
-  if (chol_ok) {
-    // v = L_G^-1 h and x = L_G^-T v by columns, a lane per unknown: the solved entry goes round by a shuffle and every
-    // lane behind it takes its product off -- lane k's subtractions in the order of the columns.  Then v^T v and
-    // sum log (L_G)_jj over the wavefront's shuffle tree.
-    for (int i = 0; i < q; ++i) {
-      const double vi = __shfl(hk, i, 64) / G[i * LD + i];
-      if (lane == i) hk = vi;
-      else if (lane > i && lane < q) hk -= G[lane * LD + i] * vi;
-    }
-    q2 = __shfl(sp_wave_sum(hk * hk), 0, 64);
-    slg = __shfl(sp_wave_sum(lane < q ? log(G[lane * LD + lane]) : 0.0), 0, 64);
-    for (int i = q - 1; i >= 0; --i) {
-      const double xi = __shfl(hk, i, 64) / G[i * LD + i];
-      if (lane == i) hk = xi;
-      else if (lane < i) hk -= G[i * LD + lane] * xi;
-    }
-  }
-  if (chol_ok && (wc || mx) && lane < q) {
-    // column `lane` of L_G^-1
-    const int j = lane;
-    X[j * LD + j] = 1.0 / G[j * LD + j];
-    for (int i = j + 1; i < q; ++i) {
-      double a = 0.0;
-      for (int k = j; k < i; ++k) a += G[i * LD + k] * X[k * LD + j];
-      X[i * LD + j] = -a / G[i * LD + i];
-    }
-  }
-  __syncthreads();
+  const double *Mg = W.Mg, *X = W.X, *dv = W.dv;
   const double yy = Mg[0], slog = sc[0];
   const double c2pi = 0.5 * (double)K * 1.8378770664093453;   // K/2 log(2 pi)
   const double ll0 = (-0.5 * yy - slog) - c2pi;
@@ -244,11 +170,10 @@ __global__ __launch_bounds__(64) void lin_finish_kernel(int K, int q, int nsplit
       wc[(size_t)j * q + i] = v;
     }
   }
-  if (mx)
-    for (int e = lane; e < LIN_QMAX * LIN_QMAX; e += 64) {
-      const int a = e / LIN_QMAX, c = e % LIN_QMAX;
-      mx[e] = isnan_ ? nanv : (a <= c && c < q ? dv[a] * X[c * LD + a] : 0.0);
-    }
+  if (mx && isnan_)
+    for (int e = lane; e < SP_LIN_QMAX * SP_LIN_QMAX; e += 64) mx[e] = nanv;
+  else if (mx)
+    sp_linq_store_mix(W, q, lane, mx, SP_LIN_QMAX, SP_LIN_QMAX);
   if (lane == 0) {
     lnlike[s] = rej ? -INFINITY : (isnan_ ? nanv : ll);
     lnlike0[s] = rej ? -INFINITY : (isnan_ ? nanv : ll0);
@@ -329,7 +254,7 @@ int lin_group(sp_handle *h, const SpProblem &Q, int q, int conditional, const do
 extern "C" {
 
 size_t sp_lnlike_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts, int conditional) {
-  if (!h || S < 0 || K < 2 || q < 1 || q > LIN_QMAX || (!conditional && covpts < 1)) return 0;
+  if (!h || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX || (!conditional && covpts < 1)) return 0;
   return sp_lin_layout(h, S, K, q, conditional).total;
 }
 
@@ -341,7 +266,7 @@ int sp_lnlike_linear(sp_handle *h, int S, int K, int q, const double *t_dev, con
                      uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !flux_dev || !stars_dev || !basis_dev || !basis_var_dev || !lnlike_dev || !lnlike0_dev ||
-      !wmean_dev || !workspace_dev || S < 0 || K < 2 || q < 1 || q > LIN_QMAX || norm_order < 0 ||
+      !wmean_dev || !workspace_dev || S < 0 || K < 2 || q < 1 || q > SP_LIN_QMAX || norm_order < 0 ||
       norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
     return SP_ERR_INVALID;
   if (const int rc = sp_branch_check(h, conditional, rta1_dev, tab_dev, meanvar_dev, covpts)) return rc;

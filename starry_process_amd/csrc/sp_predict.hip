@@ -31,6 +31,7 @@
 // assembly's, operation for operation.
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_linq.h"   // (the bound on q alone: nothing here calls its functions, which want default contraction)
 
 namespace {
 
@@ -263,12 +264,13 @@ __global__ __launch_bounds__(256) void predict_reduce_kernel(const double *__res
 // ---- with q linear regressors marginalised out (sp_predict_linear) ----------------------------------
 // The q regressor rows ride below the residual row: after the factorisation the rows K + Ks .. K + Ks + q of a system
 // hold [y; W^T] = [L^-1 r; (L^-1 U)^T], and sp_linear.hip's Gram pass and finish give w_mean and M = D L_G^-T.
-constexpr int PL_QMAX = 32;      // regressors per star, and the columns of Z
+// (SP_LIN_QMAX, sp_linq.h: regressors per star, and the columns of Z)
 constexpr int PL_JB = 64;        // sample rows per workgroup (wavefront w: 16 w .. 16 w + 15)
 constexpr int PL_KB = 32;        // columns of Y per tile
 constexpr int PL_LD = 34;        // row stride of a tile in LDS: a fragment read of 16 rows x 2 columns (a group of 32
                                  // lanes of ds_read_b64) falls on 32 distinct 8-byte banks; rows stay 16-byte aligned
-constexpr int PL_MLD = PL_QMAX + 1;
+constexpr int PL_MLD = SP_LIN_QMAX + 1;   // row stride of the mixing matrix in LDS
+static_assert(SP_LIN_QMAX == 32, "predict_reduce_linear_kernel: two tiles of 16 regressors, Z's columns 8 to a lane group");
 typedef double pl_d4 __attribute__((ext_vector_type(4)));
 
 // the regressor rows K + Ks + 1 .. K + Ks + q of every system, columns < K, as given: no mean is subtracted (the flux
@@ -310,7 +312,7 @@ __global__ __launch_bounds__(256) void predict_reduce_linear_kernel(
   constexpr int WL = MT + 1;                            // ... and a thread's 16-byte loads of it
   __shared__ __attribute__((aligned(16))) double Ys[2][PL_JB * PL_LD];
   __shared__ __attribute__((aligned(16))) double Ws[2][NW * PL_LD];
-  static_assert(2 * PL_JB * PL_LD >= 4 * 16 * PL_MLD + PL_QMAX * PL_MLD + PL_QMAX, "the epilogue reuses Ys");
+  static_assert(2 * PL_JB * PL_LD >= 4 * 16 * PL_MLD + SP_LIN_QMAX * PL_MLD + SP_LIN_QMAX, "the epilogue reuses Ys");
   const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j0 = PL_JB * blockIdx.x;
   const double nanv = __builtin_nan("");
@@ -321,8 +323,8 @@ __global__ __launch_bounds__(256) void predict_reduce_linear_kernel(
         if (VAR) var[(size_t)s * Ks + j0 + e] = nanv;
       }
     if (ZOUT)
-      for (int e = tid; e < PL_JB * PL_QMAX; e += 256)
-        if (j0 + (e >> 5) < Ks) zout[((size_t)s * Ks + j0) * PL_QMAX + e] = nanv;
+      for (int e = tid; e < PL_JB * SP_LIN_QMAX; e += 256)
+        if (j0 + e / SP_LIN_QMAX < Ks) zout[((size_t)s * Ks + j0) * SP_LIN_QMAX + e] = nanv;
     return;
   }
   const double *M0 = sys + (size_t)s * stride;
@@ -389,10 +391,10 @@ __global__ __launch_bounds__(256) void predict_reduce_linear_kernel(
   // (every wavefront is past its last read of the tiles: the epilogue's tables take their place)
   double *Rs = &Ys[0][0] + wave * 16 * PL_MLD;          // the wavefront's R [16][q]
   double *Ms = &Ys[0][0] + 4 * 16 * PL_MLD;             // M [32][32], upper triangular
-  double *wm = Ms + PL_QMAX * PL_MLD;
-  for (int e = tid; e < PL_QMAX * PL_QMAX; e += 256)
-    Ms[(e >> 5) * PL_MLD + (e & 31)] = mix[(size_t)s * PL_QMAX * PL_QMAX + e];
-  if (tid < PL_QMAX) wm[tid] = tid < q ? wmean[(size_t)s * q + tid] : 0.0;
+  double *wm = Ms + SP_LIN_QMAX * PL_MLD;
+  for (int e = tid; e < SP_LIN_QMAX * SP_LIN_QMAX; e += 256)
+    Ms[(e / SP_LIN_QMAX) * PL_MLD + e % SP_LIN_QMAX] = mix[(size_t)s * SP_LIN_QMAX * SP_LIN_QMAX + e];
+  if (tid < SP_LIN_QMAX) wm[tid] = tid < q ? wmean[(size_t)s * q + tid] : 0.0;
   const int jw = j0 + 16 * wave;
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
@@ -429,7 +431,7 @@ __global__ __launch_bounds__(256) void predict_reduce_linear_kernel(
     zz += __shfl_xor(zz, 16, 64);
     zz += __shfl_xor(zz, 32, 64);
     if (ZOUT && j < Ks) {
-      double *zo = zout + ((size_t)s * Ks + j) * PL_QMAX + 8 * fq;
+      double *zo = zout + ((size_t)s * Ks + j) * SP_LIN_QMAX + 8 * fq;
 #pragma unroll
       for (int i = 0; i < 8; i += 2) *reinterpret_cast<dd2 *>(zo + i) = dd2{z[i], z[i + 1]};
     }
@@ -471,12 +473,12 @@ struct PredictLayout {
       sys = take(d * (size_t)Kp * Kp);
       if (q > 0) {
         gpart = c.take(sp_lin_gpart_bytes(n, K, q));
-        mix = take(d * PL_QMAX * PL_QMAX);
+        mix = take(d * SP_LIN_QMAX * SP_LIN_QMAX);
         wmean = take(d * q);
         lnl = take(d * 2);
         status = take(sizeof(uint32_t));
         bad = take(sizeof(int32_t));
-        Z = take(d * (size_t)Ks * PL_QMAX);
+        Z = take(d * (size_t)Ks * SP_LIN_QMAX);
       }
       return c.off;
     };
@@ -707,7 +709,7 @@ int sp_predict_ensemble(sp_handle *h, int S, int K, int Ks, const double *t_dev,
 }
 
 size_t sp_predict_linear_workspace_bytes(sp_handle *h, int S, int K, int Ks, int q, int covpts) {
-  if (!h || S < 1 || K < 1 || Ks < 1 || covpts < 1 || q < 1 || q > PL_QMAX) return 0;
+  if (!h || S < 1 || K < 1 || Ks < 1 || covpts < 1 || q < 1 || q > SP_LIN_QMAX) return 0;
   return PredictLayout(h, S, K, Ks, covpts, q).bytes;
 }
 
@@ -719,7 +721,7 @@ int sp_predict_linear(sp_handle *h, int S, int K, int Ks, int q, const double *t
                       int32_t *info_dev, double *wmean_dev, double *lnlike_dev, double *lnlike0_dev,
                       uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
-  if (!h || !basis_dev || !basis_var_dev || q < 1 || q > PL_QMAX) return SP_ERR_INVALID;
+  if (!h || !basis_dev || !basis_var_dev || q < 1 || q > SP_LIN_QMAX) return SP_ERR_INVALID;
   const PredictIn in{K, Ks, t_dev, ts_dev ? ts_dev : t_dev, flux_dev, diag_dev, stars_dev, conditional, covpts,
                      tab_dev, meanvar_dev, rta1_dev, temporal};
   int rc = check_in(h, S, in);
@@ -813,8 +815,8 @@ int sp_predict_linear(sp_handle *h, int S, int K, int Ks, int q, const double *t
       }
       const double *Y = sys + (size_t)K * Kp;
       if ((rc = sp_launch_gemm_nt(Y, ld, stride, Y, ld, stride, C, Ks, skk, Ks, Ks, K, -1.0, 1, 1, nb, st))) return rc;
-      const long sz = (long)Ks * PL_QMAX;
-      if ((rc = sp_launch_gemm_nt(Z, PL_QMAX, sz, Z, PL_QMAX, sz, C, Ks, skk, Ks, Ks, PL_QMAX, 1.0, 1, 1, nb, st)))
+      const long sz = (long)Ks * SP_LIN_QMAX;
+      if ((rc = sp_launch_gemm_nt(Z, SP_LIN_QMAX, sz, Z, SP_LIN_QMAX, sz, C, Ks, skk, Ks, Ks, SP_LIN_QMAX, 1.0, 1, 1, nb, st)))
         return rc;
       // (exactly symmetric; NaN everywhere for a star that did not factor or that the q x q stage flagged)
       if ((rc = sp_launch_mirror_lower(C, Ks, (long)Ks, skk, nb, st, bad))) return rc;

@@ -12,6 +12,7 @@ import numpy as np
 from . import _lib
 from . import hostconst
 from ._lib import STAR_DTYPE, TEMPORAL, SPError, c_void_p, check, hptr
+from .linear import MAX_REGRESSORS
 from .stars import make_stars, sample_parameters, samples_in_bounds, stars_for_samples  # noqa: F401
 
 __all__ = ["Engine", "DataPlan", "get_engine", "make_stars", "stars_for_samples", "sample_parameters", "samples_in_bounds"]
@@ -190,6 +191,34 @@ class Engine(object):
         diag = None if diag is None else self.f64(diag)
         rta1 = None if rta1 is None else self.f64(rta1)
         return t, flux, sd, diag, rta1, int(bool(conditional))
+
+    def _regressor_inputs(self, basis, basis_var, S, K):
+        """(basis [S, q, K], basis_var [S, q], q) of the calls with regressors: float64, contiguous, shapes checked."""
+        basis, basis_var = self.f64(basis), self.f64(basis_var)
+        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
+            raise ValueError("`basis` must be (S, q, K)")
+        q = int(basis.shape[1])
+        if not 1 <= q <= MAX_REGRESSORS:
+            raise ValueError("1 to %d regressors per star are served, not %d" % (MAX_REGRESSORS, q))
+        if tuple(basis_var.shape) != (S, q):
+            raise ValueError("`basis_var` must be (S, q)")
+        return basis.contiguous(), basis_var.contiguous(), q
+
+    def _block_edges_dev(self, edges, K, return_cov):
+        """(ed, nb, bmax) of the leave-block-out calls: the edges as an int32 device tensor, the number of blocks and
+        the widest block.  ``edges``: an int32 device tensor or anything ``block_edges`` takes."""
+        torch = _torch()
+        if isinstance(edges, torch.Tensor):
+            # (a device tensor is the caller's word: the library checks it; its widest block sizes `cov`)
+            ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
+            if ed.dim() != 1 or ed.numel() < 2:
+                raise ValueError("`edges` must be a 1-D array of at least two block edges")
+            bmax = int((ed[1:] - ed[:-1]).max()) if return_cov else 0
+        else:
+            eh = block_edges(edges, K)
+            bmax = int(np.diff(eh).max())
+            ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
+        return ed, int(ed.numel()) - 1, bmax
 
     def _out_status(self, S, out, status):
         """(out, status) of a likelihood call over S systems: the caller's tensors, or fresh ones (status zeroed)."""
@@ -781,15 +810,7 @@ class Engine(object):
         if ts is not None and (ts.dim() != 2 or ts.shape[0] != S or ts.shape[1] < 1):
             raise ValueError("ts must be (S, Ks)")
         Ks = K if ts is None else int(ts.shape[1])
-        basis, basis_var = self.f64(basis), self.f64(basis_var)
-        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
-            raise ValueError("`basis` must be (S, q, K)")
-        q = int(basis.shape[1])
-        if not 1 <= q <= 32:
-            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
-        if tuple(basis_var.shape) != (S, q):
-            raise ValueError("`basis_var` must be (S, q)")
-        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
         if basis_sample is not None:
             basis_sample = self.f64(basis_sample)
             if tuple(basis_sample.shape) != (S, Ks, q):
@@ -1570,17 +1591,7 @@ class Engine(object):
         t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
                                                                      "leave-block-out")
         S, K = flux.shape
-        if isinstance(edges, torch.Tensor):
-            # (a device tensor is the caller's word: sp_lbo_ensemble checks it; its widest block sizes `cov`)
-            ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
-            if ed.dim() != 1 or ed.numel() < 2:
-                raise ValueError("`edges` must be a 1-D array of at least two block edges")
-            bmax = int((ed[1:] - ed[:-1]).max()) if return_cov else 0
-        else:
-            eh = block_edges(edges, K)
-            bmax = int(np.diff(eh).max())
-            ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
-        nb = int(ed.numel()) - 1
+        ed, nb, bmax = self._block_edges_dev(edges, K, return_cov)
         rows, lpd, lnlike = self.empty(S, 4, K), self.empty(S, nb), self.empty(S)
         cov = self.empty(S, nb, bmax, bmax) if return_cov else None
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
@@ -1617,15 +1628,7 @@ class Engine(object):
         t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
                                                                      "the likelihood with regressors")
         S, K = flux.shape
-        basis, basis_var = self.f64(basis), self.f64(basis_var)
-        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
-            raise ValueError("`basis` must be (S, q, K)")
-        q = int(basis.shape[1])
-        if not 1 <= q <= 32:
-            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
-        if tuple(basis_var.shape) != (S, q):
-            raise ValueError("`basis_var` must be (S, q)")
-        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
         lnlike, lnlike0, wmean = self.empty(S), self.empty(S), self.empty(S, q)
         wcov = self.empty(S, q, q) if return_cov else None
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
@@ -1664,26 +1667,8 @@ class Engine(object):
         t, flux, sd, diag, rta1, conditional = self._ensemble_inputs(t, flux, stars, diag, rta1, conditional,
                                                                      "leave-block-out with regressors")
         S, K = flux.shape
-        basis, basis_var = self.f64(basis), self.f64(basis_var)
-        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
-            raise ValueError("`basis` must be (S, q, K)")
-        q = int(basis.shape[1])
-        if not 1 <= q <= 32:
-            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
-        if tuple(basis_var.shape) != (S, q):
-            raise ValueError("`basis_var` must be (S, q)")
-        basis, basis_var = basis.contiguous(), basis_var.contiguous()
-        if isinstance(edges, torch.Tensor):
-            # (a device tensor is the caller's word: sp_lbo_linear checks it; its widest block sizes `cov`)
-            ed = edges.to(device=self.device, dtype=torch.int32).contiguous()
-            if ed.dim() != 1 or ed.numel() < 2:
-                raise ValueError("`edges` must be a 1-D array of at least two block edges")
-            bmax = int((ed[1:] - ed[:-1]).max()) if return_cov else 0
-        else:
-            eh = block_edges(edges, K)
-            bmax = int(np.diff(eh).max())
-            ed = torch.as_tensor(eh, dtype=torch.int32).to(self.device)
-        nb = int(ed.numel()) - 1
+        basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
+        ed, nb, bmax = self._block_edges_dev(edges, K, return_cov)
         rows, lpd = self.empty(S, 4, K), self.empty(S, nb)
         lnlike, lnlike0, wmean = self.empty(S), self.empty(S), self.empty(S, q)
         cov = self.empty(S, nb, bmax, bmax) if return_cov else None
@@ -1716,15 +1701,7 @@ class Engine(object):
         S, K = t.shape
         if tuple(flux.shape) != (S, K):
             raise ValueError("`flux` must be (S, K): one light curve per star")
-        basis, basis_var = self.f64(basis), self.f64(basis_var)
-        if basis.dim() != 3 or basis.shape[0] != S or basis.shape[2] != K:
-            raise ValueError("`basis` must be (S, q, K)")
-        q = int(basis.shape[1])
-        if not 1 <= q <= 32:
-            raise ValueError("1 to 32 regressors per star are served, not %d" % q)
-        if tuple(basis_var.shape) != (S, q):
-            raise ValueError("`basis_var` must be (S, q)")
-        basis, basis_var = basis.contiguous(), basis_var.contiguous()
+        basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
         nbytes = int(self._L.sp_lnlike_grad_linear_workspace_bytes(self._h, S, K, q, int(covpts)))
         ws = self._grad_scratch(nbytes, workspace)
         out, ybar, mbar, sbar = self.empty(S), self.empty(S, covpts + 4), self.empty(S), self.empty(S, 6)

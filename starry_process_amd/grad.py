@@ -586,17 +586,12 @@ class EnsembleGradient(_MarginalSweep):
         if flux.ndim not in (2, 3):
             raise ValueError("flux must be (S, K) or (S, M, K)")
         M = flux.shape[1] if flux.ndim == 3 else 1
-        U = lam = None
-        if basis is None and basis_var is not None:
-            raise ValueError("`basis_var` needs a `basis`")
-        if basis is not None:
-            from .linear import check_regressors
+        from .linear import _regressor_args
 
-            if flux.ndim == 3:
-                raise ValueError("regressors are served for one light curve per star: `flux` must be (S, K) with a `basis`")
-            if basis_var is None:
-                raise ValueError("a `basis` needs the prior variances of its weights, `basis_var`")
-            U, lam = check_regressors(basis, basis_var, flux.shape[0], flux.shape[1])
+        if basis is not None and flux.ndim == 3:
+            raise ValueError("regressors are served for one light curve per star: `flux` must be (S, K) with a `basis`")
+        U, Ut, lam = _regressor_args(basis, basis_var, flux.shape[0], flux.shape[1],
+                                     "a `basis` needs the prior variances of its weights, `basis_var`")
         # (the star records carry no inclination on the marginal branch: make_stars' own default)
         stars, utab = self._setup(t, flux, ferr, p, None, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel,
                                   device)
@@ -610,7 +605,7 @@ class EnsembleGradient(_MarginalSweep):
             self._ws = e.grad_workspace(self.S, self.K, self._covpts, M)
         else:
             self._q = U.shape[2]
-            self._basis = e.f64(np.ascontiguousarray(np.swapaxes(U, 1, 2)))      # [S, q, K]: a regressor along a row
+            self._basis = e.f64(Ut)
             self._basis_var = e.f64(lam)
             self._ws = e.grad_linear_workspace(self.S, self.K, self._q, self._covpts)
             _torch().cuda.synchronize(e.device)

@@ -7,6 +7,8 @@ import numpy as np
 
 __all__ = ["offset_basis", "polynomial_basis", "offset_basis_at", "polynomial_basis_at", "stack_bases"]
 
+MAX_REGRESSORS = 32   # regressors per star: SP_LIN_QMAX of csrc/sp_linq.h
+
 
 def check_regressors(basis, basis_var, S, K):
     """``basis`` (K, q) shared or (S, K, q) and ``basis_var`` scalar, (q,) or (S, q) as the ensemble calls with
@@ -20,11 +22,27 @@ def check_regressors(basis, basis_var, S, K):
         raise ValueError("`basis` must be (K, q) or (S, K, q) with S = %d, K = %d, not %s"
                          % (S, K, np.shape(basis)))
     q = U.shape[2]
-    if not 1 <= q <= 32:
-        raise ValueError("1 to 32 regressors are served, not %d" % q)
+    if not 1 <= q <= MAX_REGRESSORS:
+        raise ValueError("1 to %d regressors are served, not %d" % (MAX_REGRESSORS, q))
     if not np.all(np.isfinite(U)):
         raise ValueError("`basis` must be finite")
     return U, check_regressor_variances(basis_var, S, q)
+
+
+def _regressor_args(basis, basis_var, S, K, need_var="`basis` needs a `basis_var`", required=False):
+    """The ``basis=``, ``basis_var=`` pair of an ensemble call: (U, Ut, lam) as ``check_regressors`` checks them, Ut
+    [S, q, K] the contiguous copy with a regressor along a row (what the device takes).  Where the pair is optional:
+    (None, None, None) without a basis, and ValueError for one of the pair without the other (``need_var``: the
+    caller's words for a basis without variances).  ``required``: both go to ``check_regressors`` as they are."""
+    if not required:
+        if basis is None:
+            if basis_var is not None:
+                raise ValueError("`basis_var` needs a `basis`")
+            return None, None, None
+        if basis_var is None:
+            raise ValueError(need_var)
+    U, lam = check_regressors(basis, basis_var, S, K)
+    return U, np.ascontiguousarray(np.swapaxes(U, 1, 2)), lam
 
 
 def check_regressor_variances(basis_var, S, q):

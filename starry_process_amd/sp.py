@@ -27,6 +27,7 @@ import numpy as np
 from .defaults import defaults
 from .engine import block_edges, get_engine
 from .flux import FluxIntegral
+from .linear import _regressor_args
 from .ops import AlphaBetaOp, CheckBoundsOp, Eager, _is_torch
 from .pixel import latlon_to_xyz, mollweide_grid
 from .stars import SampleColumns, check_period_inclination, ensemble_stars, ipt_in_bounds, make_stars  # noqa: F401
@@ -672,12 +673,8 @@ class StarryProcess(object):
             elif ts.ndim != 2 or ts.shape[0] != S or ts.shape[1] < 1:
                 raise ValueError("`t_sample` must be (Ks,) or (S, Ks) with S = %d, not %s" % (S, ts.shape))
             ts = np.ascontiguousarray(ts)
+        U, Ut, lam = _regressor_args(basis, basis_var, S, K)
         if basis is not None:
-            from .linear import check_regressors
-
-            if basis_var is None:
-                raise ValueError("`basis` needs a `basis_var`")
-            U, lam = check_regressors(basis, basis_var, S, K)
             q, Ks = U.shape[2], (K if ts is None else ts.shape[1])
             Us = None
             if basis_sample is not None:
@@ -699,8 +696,7 @@ class StarryProcess(object):
         branch = dict(diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
                       meanvar=mv, rta1=rta1, temporal=self._temporal, mode=mode)
         if basis is not None:
-            Ut = e.f64(np.ascontiguousarray(np.swapaxes(U, 1, 2)))          # [S, q, K]: a regressor along a row
-            return e.predict_linear(t, ts, flux, stars, Ut, lam, None if Us is None else e.f64(Us), **branch)
+            return e.predict_linear(t, ts, flux, stars, e.f64(Ut), lam, None if Us is None else e.f64(Us), **branch)
         return e.predict_ensemble(t, ts, flux, stars, **branch)
 
     def predict_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
@@ -896,15 +892,9 @@ class StarryProcess(object):
         if np.ndim(baseline_var) >= 2:
             raise NotImplementedError("%s does not serve a matrix `baseline_var`: pass a scalar or (S,)" % _name)
         edges = block_edges(block, K)
-        if basis is not None:
-            from .linear import check_regressors
-
-            if K < 2:
-                raise ValueError("the checks with regressors need at least two cadences")
-            if basis_var is None:
-                raise ValueError("`basis` needs a `basis_var`")
-            U, lam = check_regressors(basis, basis_var, S, K)
-            Ut = np.ascontiguousarray(np.swapaxes(U, 1, 2))          # [S, q, K]: a regressor along a row
+        if basis is not None and K < 2:
+            raise ValueError("the checks with regressors need at least two cadences")
+        _, Ut, lam = _regressor_args(basis, basis_var, S, K)
         e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
         f._bind()
@@ -1002,10 +992,7 @@ class StarryProcess(object):
                                       "scalar or (S,), and the structured part as `basis`, `basis_var`")
         if K < 2:
             raise ValueError("the likelihood with regressors needs at least two cadences")
-        from .linear import check_regressors
-
-        U, lam = check_regressors(basis, basis_var, S, K)
-        Ut = np.ascontiguousarray(np.swapaxes(U, 1, 2))          # [S, q, K]: a regressor along a row
+        _, Ut, lam = _regressor_args(basis, basis_var, S, K, required=True)
         e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
         f._bind()

@@ -12,10 +12,13 @@ sp_lnlike_linear; the device half is tests/test_gpu_linear.py).  No GPU compute 
     the NumPy restatement of the D-form identities the GPU tests take as the formula, against both.
 """
 import ctypes
+import os
+import re
 
 import numpy as np
 import pytest
 
+from conftest import ROOT
 from oracle import sp_oracle as orc
 from starry_process_amd import _lib
 from starry_process_amd import linear
@@ -182,6 +185,19 @@ def test_refusals_are_raised_before_any_device_work():
     # (the checks passed, the next thing is the engine: nothing of the device was touched before)
     with pytest.raises(AttributeError):
         ens(t, flux, 1e-6, U, 0.0)
+
+
+def test_the_bound_on_the_regressors_is_defined_once():
+    """linear.MAX_REGRESSORS is csrc/sp_linq.h's SP_LIN_QMAX, and no source under csrc/ defines a *_QMAX of its own."""
+    csrc = os.path.join(ROOT, "starry_process_amd", "csrc")
+    defs = {}
+    for name in sorted(os.listdir(csrc)):
+        if name.endswith((".h", ".hip", ".cpp")):
+            with open(os.path.join(csrc, name)) as f:
+                for m in re.finditer(r"^\s*(?:#\s*define\s+|(?:static\s+)?constexpr\s+\w+\s+)(\w*_QMAX)\b\s*=?\s*(\w+)",
+                                     f.read(), re.M):
+                    defs.setdefault(m.group(1), []).append((name, m.group(2)))
+    assert defs == {"SP_LIN_QMAX": [("sp_linq.h", str(linear.MAX_REGRESSORS))]}
 
 
 def test_offset_basis():
