@@ -686,6 +686,11 @@ int sp_launch_lin_finish(int S, int K, int q, const double *gpart, const double 
 // the downdate G~ = Y_B Y_B^T - Z_B Z_B^T, Z_B = Y_B T, T [S][K][32] (columns >= q zero), alpha against row 3 of `rows`.
 constexpr int SP_LBO_R = 64;
 int sp_lbo_count_bands(const int32_t *e, int nblocks);
+// the partition both drivers take: sp_lbo_check_partition checks e[0 .. nblocks] on the host -- e_0 = 0, e_nblocks = K,
+// every width in 1 .. SP_LBO_R, else SP_ERR_INVALID -- and gives the widest block and the number of bands;
+// sp_lbo_read_partition copies the edges back from the device on `st`, waits for them and checks them
+int sp_lbo_check_partition(const int32_t *e, int nblocks, int K, int *bmax, int *nbands);
+int sp_lbo_read_partition(const int32_t *edges_dev, int nblocks, int K, hipStream_t st, int *bmax, int *nbands);
 int sp_launch_lbo_bands(int nblocks, const int32_t *edges, int32_t *bands, hipStream_t st);
 int sp_launch_lbo_band_linear(int nbands, int S, int K, const SpLooSystem &Y, int nblocks, int bmax, const int32_t *edges,
                               const int32_t *bands, const double *flux, const sp_star *stars, double *rows, double *lpd,

@@ -61,10 +61,28 @@ int sp_lbo_count_bands(const int32_t *e, int nblocks) {
   int nb = 0, rows = 0;
   for (int j = 0; j < nblocks; ++j) {
     const int w = e[j + 1] - e[j];
-    if (rows + w > LBO_R) ++nb, rows = 0;
+    if (rows + w > SP_LBO_R) ++nb, rows = 0;
     rows += w;
   }
   return nb + 1;
+}
+int sp_lbo_check_partition(const int32_t *e, int nblocks, int K, int *bmax, int *nbands) {
+  if (e[0] != 0 || e[nblocks] != K) return SP_ERR_INVALID;
+  int widest = 0;
+  for (int j = 0; j < nblocks; ++j) {
+    const int w = e[j + 1] - e[j];
+    if (w < 1 || w > SP_LBO_R) return SP_ERR_INVALID;
+    widest = w > widest ? w : widest;
+  }
+  *bmax = widest;
+  *nbands = sp_lbo_count_bands(e, nblocks);
+  return SP_OK;
+}
+int sp_lbo_read_partition(const int32_t *edges_dev, int nblocks, int K, hipStream_t st, int *bmax, int *nbands) {
+  std::vector<int32_t> e((size_t)nblocks + 1);
+  SP_HIP(hipMemcpyAsync(e.data(), edges_dev, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost, st));
+  SP_HIP(hipStreamSynchronize(st));
+  return sp_lbo_check_partition(e.data(), nblocks, K, bmax, nbands);
 }
 namespace {
 
@@ -412,17 +430,8 @@ int sp_lbo_ensemble(sp_handle *h, int S, int K, const double *t_dev, const doubl
   if (S == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   // the partition decides the grid and what the kernels may index: it is read back and checked here
-  std::vector<int32_t> e((size_t)nblocks + 1);
-  SP_HIP(hipMemcpyAsync(e.data(), edges_dev, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost, st));
-  SP_HIP(hipStreamSynchronize(st));
-  if (e[0] != 0 || e[nblocks] != K) return SP_ERR_INVALID;
-  int bmax = 0;
-  for (int j = 0; j < nblocks; ++j) {
-    const int w = e[j + 1] - e[j];
-    if (w < 1 || w > LBO_R) return SP_ERR_INVALID;
-    bmax = w > bmax ? w : bmax;
-  }
-  const int nbands = sp_lbo_count_bands(e.data(), nblocks);
+  int bmax, nbands;
+  if (const int rc = sp_lbo_read_partition(edges_dev, nblocks, K, st, &bmax, &nbands)) return rc;
   const int group =
       sp_star_group(S, workspace_bytes, [&](int n) { return lbo_layout(h, n, K, conditional, nblocks).total; });
   if (!group) return SP_ERR_INVALID;

@@ -12,8 +12,6 @@
 // (sp_lbo.hip); lbl_flags_kernel, the blocks' flags into the status words.  Nothing is divided by lambda: lambda_j = 0
 // makes column j of T and w_mean[j] exact zeros, and with every lambda zero the rows have the bits of sp_lbo_ensemble's.
 // Every sum has a fixed order and every output element one writer: no atomics.
-#include <vector>
-
 #include "sp_internal.h"
 #include "sp_linq.h"
 
@@ -200,17 +198,8 @@ int sp_lbo_linear(sp_handle *h, int S, int K, int q, const double *t_dev, const 
   if (S == 0) return SP_OK;
   hipStream_t st = (hipStream_t)stream;
   // the partition decides the grid and what the kernels may index: it is read back and checked here
-  std::vector<int32_t> e((size_t)nblocks + 1);
-  SP_HIP(hipMemcpyAsync(e.data(), edges_dev, sizeof(int32_t) * e.size(), hipMemcpyDeviceToHost, st));
-  SP_HIP(hipStreamSynchronize(st));
-  if (e[0] != 0 || e[nblocks] != K) return SP_ERR_INVALID;
-  int bmax = 0;
-  for (int j = 0; j < nblocks; ++j) {
-    const int w = e[j + 1] - e[j];
-    if (w < 1 || w > SP_LBO_R) return SP_ERR_INVALID;
-    bmax = w > bmax ? w : bmax;
-  }
-  const int nbands = sp_lbo_count_bands(e.data(), nblocks);
+  int bmax, nbands;
+  if (const int rc = sp_lbo_read_partition(edges_dev, nblocks, K, st, &bmax, &nbands)) return rc;
   const int group =
       sp_star_group(S, workspace_bytes, [&](int n) { return lbl_layout(h, n, K, q, conditional, nblocks).total; });
   if (!group) return SP_ERR_INVALID;

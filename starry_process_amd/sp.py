@@ -41,10 +41,10 @@ def _neg_inf_if_nan(x):
     return np.where(np.isnan(x), -np.inf, x)
 
 
-def _one_star_regressors(basis, basis_var):
+def _one_star_regressors(basis, basis_var, required=False):
     """``basis`` (K, q) and ``basis_var`` scalar or (q,) of one light curve as the ensemble calls take them ((1, K, q),
-    the variances as given); None stays None.  ValueError for another shape."""
-    if basis is None:
+    the variances as given); None stays None unless the basis is ``required``.  ValueError for another shape."""
+    if basis is None and not required:
         return None, basis_var
     U = np.asarray(basis, dtype=np.float64)
     if U.ndim != 2:
@@ -52,6 +52,81 @@ def _one_star_regressors(basis, basis_var):
     if basis_var is not None and np.ndim(basis_var) > 1:
         raise ValueError("`basis_var` must be a scalar or (q,)")
     return U[None], basis_var
+
+
+# how log_likelihood_linear and its ensemble form end their refusal of a matrix `baseline_var`
+_BASIS_HINT = ", and the structured part as `basis`, `basis_var`"
+
+
+def _dense_ensemble_input(name, t, flux, data_cov, baseline_var, baseline_hint=""):
+    """(t, flux (S, K), data_cov, S, K) in float64 for the ensemble method ``name``, or the refusals of what the model
+    checks do not serve, in this order: ragged input, a flux that is not (S, K), a full-matrix ``data_cov`` ((K, K)
+    with S = K is (S, K) variances) and a matrix ``baseline_var`` (``baseline_hint`` ends that message)."""
+    try:
+        flux = np.asarray(flux, dtype=np.float64)
+        tt = np.asarray(t, dtype=np.float64)
+    except (ValueError, TypeError):
+        raise ValueError("%s does not serve ragged input (lists of light curves of different lengths): "
+                         "pass `t` and `flux` as (S, K) arrays" % name)
+    if flux.ndim != 2:
+        raise ValueError("`flux` must be (S, K)")
+    S, K = flux.shape
+    dc = np.asarray(data_cov, dtype=np.float64)
+    if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
+        raise NotImplementedError("%s does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
+                                  "(S, K) variances" % name)
+    if np.ndim(baseline_var) >= 2:
+        raise NotImplementedError("%s does not serve a matrix `baseline_var`: pass a scalar or (S,)%s"
+                                  % (name, baseline_hint))
+    return tt, flux, dc, S, K
+
+
+def _one_curve(name, flux, data_cov, baseline_var, baseline_hint=""):
+    """(flux (1, K), data_cov a scalar or (1, K)) of the one-light-curve method ``name`` as its ensemble form takes
+    them, or its refusals: a full-matrix ``data_cov``, a ``baseline_var`` that is no scalar, a flux that is no row."""
+    dc = np.asarray(data_cov, dtype=np.float64)
+    if dc.ndim >= 2:
+        raise NotImplementedError("%s does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances" % name)
+    if np.ndim(baseline_var) >= 1:
+        raise NotImplementedError("%s does not serve a matrix `baseline_var`: pass a scalar%s" % (name, baseline_hint))
+    try:
+        flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
+    except (ValueError, TypeError):
+        raise ValueError("`flux` must be one light curve of K cadences")
+    return flux, (dc.reshape(1, -1) if dc.ndim == 1 else dc)
+
+
+def _star_fallback_args(s_, t, flux, stars, utab, diag):
+    """Star ``s_`` of an ensemble as the one-star dense routes take it: (t, flux, data_cov, period, u, baseline_mean,
+    baseline_var)."""
+    return (t[s_], flux[s_], diag[s_] if diag is not None else stars["data_var"][s_], stars["period"][s_],
+            utab[stars["table"][s_]], stars["baseline_mean"][s_], stars["baseline_var"][s_])
+
+
+def _one_star_noise(n, K, data_cov, **star_kw):
+    """(stars, diag) of n records with one light curve's noise: a scalar ``data_cov`` in the records, a vector as the
+    per-cadence variances diag (n, K)."""
+    stars = make_stars(n, data_var=float(data_cov) if data_cov.ndim == 0 else 0.0, **star_kw)
+    return stars, (None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (n, K)))
+
+
+def _linear_extras(Ud, wmean, lnlike0):
+    """What a result with regressors adds: ``lnlike0``, ``w_mean`` and ``trend`` = U w_mean, formed on the device (a
+    weight switched off contributes an exact zero)."""
+    trend = (Ud * wmean[:, :, None]).sum(dim=1)
+    return {"lnlike0": _neg_inf_if_nan(lnlike0.cpu().numpy()), "w_mean": wmean.cpu().numpy(),
+            "trend": trend.cpu().numpy()}
+
+
+def _affine_samples(e, mu, L, z):
+    """mu_s + L_s z_s of S stars on the device: mu [S, n], L [S, n, n] contiguous, the host deviates z (S, n, ns)
+    -> [S, ns, n]."""
+    S, n, ns = z.shape
+    zt = e.f64(np.ascontiguousarray(np.swapaxes(z, 1, 2)))
+    smp = e.empty(S, ns, n)
+    e.gemm_nt_batched(zt, L, smp)                             # (L_s z_s)^T
+    smp += mu[:, None, :]
+    return smp
 
 
 def sample_columns(params, marginalize_over_inclination, time_variable):
@@ -687,17 +762,28 @@ class StarryProcess(object):
                 if not np.all(np.isfinite(Us)):
                     raise ValueError("`basis_sample` must be finite")
                 Us = np.ascontiguousarray(Us)
-        e, f = self._engine, self._flux
-        f._bind()
+        e = self._engine
+        branch = dict(self._branch(utab, norm=False), diag=diag, mode=mode)
+        if basis is not None:
+            return e.predict_linear(t, ts, flux, stars, e.f64(Ut), lam, None if Us is None else e.f64(Us), **branch)
+        return e.predict_ensemble(t, ts, flux, stars, **branch)
+
+    def _branch(self, utab, norm=True):
+        """The opening of an ensemble method, once its refusals are raised: binds the moments, forms rTA1 of the
+        limb-darkening sets ``utab`` and, on the marginal branch, the kernel table.  Returns the keywords every engine
+        call of the ensemble takes for the instance's branch; ``norm``: with the normalisation's (the predict calls
+        take none)."""
+        e = self._engine
+        self._flux._bind()
         rta1 = e.f64(e.rTA1L(utab))
         tab = mv = None
         if self._marginalize_over_inclination:
             tab, mv = e.kernel_table(rta1, self._covpts)
-        branch = dict(diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
-                      meanvar=mv, rta1=rta1, temporal=self._temporal, mode=mode)
-        if basis is not None:
-            return e.predict_linear(t, ts, flux, stars, e.f64(Ut), lam, None if Us is None else e.f64(Us), **branch)
-        return e.predict_ensemble(t, ts, flux, stars, **branch)
+        kw = dict(conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab, meanvar=mv,
+                  rta1=rta1, temporal=self._temporal)
+        if norm:
+            kw.update(normalized=self._normalized, norm_order=self._normN, zmax=self._normzmax)
+        return kw
 
     def predict_ensemble(self, t, flux, data_cov, t_sample=None, i=None, p=None, u=None, baseline_mean=0.0,
                          baseline_var=0.0, return_cov=True, basis=None, basis_var=None, basis_sample=None):
@@ -738,15 +824,10 @@ class StarryProcess(object):
                                              True, basis, basis_var, basis_sample)[:2]
         e = self._engine
         S, Ks = mu.shape
-        nsamples = int(nsamples)
         cov.diagonal(dim1=1, dim2=2).add_(float(eps))
         L, _ = e.cho_factor(cov)                                  # (all NaN for a star that does not factor)
-        z = self._rng(seed).randn(S, Ks, nsamples)
-        zt = e.f64(np.ascontiguousarray(np.swapaxes(z, 1, 2)))
-        smp = e.empty(S, nsamples, Ks)
-        e.gemm_nt_batched(zt, L.contiguous(), smp)                # (L_s z_s)^T
-        smp += mu[:, None, :]
-        return Eager(smp.cpu().numpy())
+        z = self._rng(seed).randn(S, Ks, int(nsamples))
+        return Eager(_affine_samples(e, mu, L.contiguous(), z).cpu().numpy())
 
     # -- model checking: leave-one-out predictive distributions (sp_loo_ensemble) ---------------------------
     def loo_ensemble(self, t, flux, data_cov, i=None, p=None, u=None, baseline_mean=0.0, baseline_var=0.0,
@@ -784,34 +865,12 @@ class StarryProcess(object):
             out["z"] = out.pop("u")
             del out["edges"]
             return out
-        e, f = self._engine, self._flux
-        try:
-            flux = np.asarray(flux, dtype=np.float64)
-            tt = np.asarray(t, dtype=np.float64)
-        except (ValueError, TypeError):
-            raise ValueError("loo_ensemble does not serve ragged input (lists of light curves of different lengths): "
-                             "pass `t` and `flux` as (S, K) arrays")
-        if flux.ndim != 2:
-            raise ValueError("`flux` must be (S, K)")
-        S, K = flux.shape
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
-            raise NotImplementedError("loo_ensemble does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
-                                      "(S, K) variances")
-        if np.ndim(baseline_var) >= 2:
-            raise NotImplementedError("loo_ensemble does not serve a matrix `baseline_var`: pass a scalar or (S,)")
+        tt, flux, dc, S, K = _dense_ensemble_input("loo_ensemble", t, flux, data_cov, baseline_var)
         if K < 2:
             raise ValueError("leave-one-out needs at least two cadences")
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
-        f._bind()
-        rta1 = e.f64(e.rTA1L(utab))
-        tab = mv = None
-        if self._marginalize_over_inclination:
-            tab, mv = e.kernel_table(rta1, self._covpts)
-        loo, lnlike, status = e.loo_ensemble(
-            t, flux, stars, diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
-            meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized, norm_order=self._normN,
-            zmax=self._normzmax, max_workspace_bytes=max_workspace_bytes)
+        loo, lnlike, status = self._engine.loo_ensemble(t, flux, stars, diag=diag,
+                                                        max_workspace_bytes=max_workspace_bytes, **self._branch(utab))
         loo = loo.cpu().numpy()
         out = {name: np.ascontiguousarray(loo[:, k]) for k, name in enumerate(("mu", "var", "z", "lpd", "white"))}
         out["elpd"] = out["lpd"].sum(axis=1)
@@ -824,17 +883,7 @@ class StarryProcess(object):
             basis_var=None):
         """``loo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances; basis None or
         (K, q); basis_var a scalar or (q,).  The same dict without the leading axis."""
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim >= 2:
-            raise NotImplementedError("loo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
-        if np.ndim(baseline_var) >= 1:
-            raise NotImplementedError("loo does not serve a matrix `baseline_var`: pass a scalar")
-        try:
-            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
-        except (ValueError, TypeError):
-            raise ValueError("`flux` must be one light curve of K cadences")
-        if dc.ndim == 1:
-            dc = dc.reshape(1, -1)
+        flux, dc = _one_curve("loo", flux, data_cov, baseline_var)
         basis, basis_var = _one_star_regressors(basis, basis_var)
         out = self.loo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, i=i, p=p, u=u,
                                 baseline_mean=baseline_mean, baseline_var=baseline_var, basis=basis,
@@ -876,44 +925,19 @@ class StarryProcess(object):
         ``w_mean`` (S, q) and ``trend`` (S, K) = U w_mean.  Without ``basis`` nothing changes."""
         if basis is None and basis_var is not None:
             raise ValueError("`basis_var` needs a `basis`")
-        try:
-            flux = np.asarray(flux, dtype=np.float64)
-            tt = np.asarray(t, dtype=np.float64)
-        except (ValueError, TypeError):
-            raise ValueError("%s does not serve ragged input (lists of light curves of different lengths): "
-                             "pass `t` and `flux` as (S, K) arrays" % _name)
-        if flux.ndim != 2:
-            raise ValueError("`flux` must be (S, K)")
-        S, K = flux.shape
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
-            raise NotImplementedError("%s does not serve a full-matrix `data_cov`: pass a scalar, (S,) or "
-                                      "(S, K) variances" % _name)
-        if np.ndim(baseline_var) >= 2:
-            raise NotImplementedError("%s does not serve a matrix `baseline_var`: pass a scalar or (S,)" % _name)
+        tt, flux, dc, S, K = _dense_ensemble_input(_name, t, flux, data_cov, baseline_var)
         edges = block_edges(block, K)
         if basis is not None and K < 2:
             raise ValueError("the checks with regressors need at least two cadences")
         _, Ut, lam = _regressor_args(basis, basis_var, S, K)
-        e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
-        f._bind()
-        rta1 = e.f64(e.rTA1L(utab))
-        tab = mv = None
-        if self._marginalize_over_inclination:
-            tab, mv = e.kernel_table(rta1, self._covpts)
-        branch = dict(diag=diag, conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
-                      meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
-                      norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
-                      max_workspace_bytes=max_workspace_bytes)
+        e = self._engine
+        branch = dict(self._branch(utab), diag=diag, return_cov=return_cov, max_workspace_bytes=max_workspace_bytes)
         extra = {}
         if basis is not None:
             Ud = e.f64(Ut)
             rows, lpd, cov, lnlike, lnlike0, wmean, status = e.lbo_linear(t, flux, stars, edges, Ud, lam, **branch)
-            extra["lnlike0"] = _neg_inf_if_nan(lnlike0.cpu().numpy())
-            extra["w_mean"] = wmean.cpu().numpy()
-            # (U w_mean on the device; a weight switched off contributes an exact zero)
-            extra["trend"] = (Ud * wmean[:, :, None]).sum(dim=1).cpu().numpy()
+            extra = _linear_extras(Ud, wmean, lnlike0)
         else:
             rows, lpd, cov, lnlike, status = e.lbo_ensemble(t, flux, stars, edges, **branch)
         rows = rows.cpu().numpy()
@@ -933,17 +957,7 @@ class StarryProcess(object):
             basis=None, basis_var=None):
         """``lbo_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances; basis None or
         (K, q); basis_var a scalar or (q,).  The same dict without the leading axis (``edges`` as it is)."""
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim >= 2:
-            raise NotImplementedError("lbo does not serve a full-matrix `data_cov`: pass a scalar or (K,) variances")
-        if np.ndim(baseline_var) >= 1:
-            raise NotImplementedError("lbo does not serve a matrix `baseline_var`: pass a scalar")
-        try:
-            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
-        except (ValueError, TypeError):
-            raise ValueError("`flux` must be one light curve of K cadences")
-        if dc.ndim == 1:
-            dc = dc.reshape(1, -1)
+        flux, dc = _one_curve("lbo", flux, data_cov, baseline_var)
         basis, basis_var = _one_star_regressors(basis, basis_var)
         out = self.lbo_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, block, i=i, p=p, u=u,
                                 baseline_mean=baseline_mean, baseline_var=baseline_var, return_cov=return_cov,
@@ -974,45 +988,22 @@ class StarryProcess(object):
         symmetric (absent with ``return_cov=False``); ``trend`` (S, K) = U w_mean; ``status`` (S,).  A star whose
         covariance does not factor has NaN in its outputs.  ``max_workspace_bytes`` caps the device scratch: the stars
         are then worked through in groups, with the same bits."""
-        try:
-            flux = np.asarray(flux, dtype=np.float64)
-            tt = np.asarray(t, dtype=np.float64)
-        except (ValueError, TypeError):
-            raise ValueError("log_likelihood_linear_ensemble does not serve ragged input (lists of light curves of "
-                             "different lengths): pass `t` and `flux` as (S, K) arrays")
-        if flux.ndim != 2:
-            raise ValueError("`flux` must be (S, K)")
-        S, K = flux.shape
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim > 2 or (dc.ndim == 2 and dc.shape == (K, K) and S != K):
-            raise NotImplementedError("log_likelihood_linear_ensemble does not serve a full-matrix `data_cov`: pass a "
-                                      "scalar, (S,) or (S, K) variances")
-        if np.ndim(baseline_var) >= 2:
-            raise NotImplementedError("log_likelihood_linear_ensemble does not serve a matrix `baseline_var`: pass a "
-                                      "scalar or (S,), and the structured part as `basis`, `basis_var`")
+        tt, flux, dc, S, K = _dense_ensemble_input("log_likelihood_linear_ensemble", t, flux, data_cov, baseline_var,
+                                                   _BASIS_HINT)
         if K < 2:
             raise ValueError("the likelihood with regressors needs at least two cadences")
         _, Ut, lam = _regressor_args(basis, basis_var, S, K, required=True)
-        e, f = self._engine, self._flux
         t, flux, stars, utab, diag = self._ensemble_args(tt, flux, dc, i, p, u, baseline_mean, baseline_var)
-        f._bind()
-        rta1 = e.f64(e.rTA1L(utab))
-        tab = mv = None
-        if self._marginalize_over_inclination:
-            tab, mv = e.kernel_table(rta1, self._covpts)
+        e = self._engine
+        branch = self._branch(utab)
         Ud = e.f64(Ut)
         lnlike, lnlike0, wmean, wcov, status = e.lnlike_linear(
-            t, flux, stars, Ud, lam, diag=diag, conditional=not self._marginalize_over_inclination,
-            covpts=self._covpts, tab=tab, meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
-            norm_order=self._normN, zmax=self._normzmax, return_cov=return_cov,
-            max_workspace_bytes=max_workspace_bytes)
-        # (U w_mean on the device; a weight switched off contributes an exact zero)
-        trend = (Ud * wmean[:, :, None]).sum(dim=1)
-        out = {"lnlike": _neg_inf_if_nan(lnlike.cpu().numpy()), "lnlike0": _neg_inf_if_nan(lnlike0.cpu().numpy()),
-               "w_mean": wmean.cpu().numpy()}
+            t, flux, stars, Ud, lam, diag=diag, return_cov=return_cov, max_workspace_bytes=max_workspace_bytes,
+            **branch)
+        out = {"lnlike": _neg_inf_if_nan(lnlike.cpu().numpy()), **_linear_extras(Ud, wmean, lnlike0)}
         if return_cov:
             out["w_cov"] = wcov.cpu().numpy()
-        out["trend"] = trend.cpu().numpy()
+            out["trend"] = out.pop("trend")       # (the trend stands after w_cov)
         out["status"] = status.cpu().numpy()
         return out
 
@@ -1021,27 +1012,10 @@ class StarryProcess(object):
                               baseline_var=defaults["baseline_var"], return_cov=True):
         """``log_likelihood_linear_ensemble`` for one light curve: t, flux (K,); data_cov a scalar or (K,) variances;
         basis (K, q); basis_var a scalar or (q,).  The same dict without the leading axis."""
-        dc = np.asarray(data_cov, dtype=np.float64)
-        if dc.ndim >= 2:
-            raise NotImplementedError("log_likelihood_linear does not serve a full-matrix `data_cov`: pass a scalar "
-                                      "or (K,) variances")
-        if np.ndim(baseline_var) >= 1:
-            raise NotImplementedError("log_likelihood_linear does not serve a matrix `baseline_var`: pass a scalar, "
-                                      "and the structured part as `basis`, `basis_var`")
-        try:
-            flux = np.asarray(flux, dtype=np.float64).reshape(1, -1)
-        except (ValueError, TypeError):
-            raise ValueError("`flux` must be one light curve of K cadences")
-        if dc.ndim == 1:
-            dc = dc.reshape(1, -1)
-        U = np.asarray(basis, dtype=np.float64)
-        if U.ndim != 2:
-            raise ValueError("`basis` must be (K, q)")
-        lam = np.asarray(basis_var, dtype=np.float64)
-        if lam.ndim > 1:
-            raise ValueError("`basis_var` must be a scalar or (q,)")
-        out = self.log_likelihood_linear_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, U[None], lam,
-                                                  i=i, p=p, u=u, baseline_mean=baseline_mean,
+        flux, dc = _one_curve("log_likelihood_linear", flux, data_cov, baseline_var, _BASIS_HINT)
+        basis, basis_var = _one_star_regressors(basis, basis_var, required=True)
+        out = self.log_likelihood_linear_ensemble(np.asarray(t, dtype=np.float64).reshape(-1), flux, dc, basis,
+                                                  basis_var, i=i, p=p, u=u, baseline_mean=baseline_mean,
                                                   baseline_var=baseline_var, return_cov=return_cov)
         return {k: v[0] for k, v in out.items()}
 
@@ -1080,9 +1054,7 @@ class StarryProcess(object):
         # the Sherman-Morrison kernel needs every variance > 0; a star with one <= 0 may still have a positive
         # definite C = D + b 1 1^T, so it is factored as such (the reference's cho_factor decides, sp.py:616)
         if not full and data_cov.ndim <= 1 and bvar.ndim == 0 and np.all(data_cov > 0):
-            stars = make_stars(1, period=p, inc_deg=i, baseline_var=float(bvar),
-                               data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
-            diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (K,))[None, :]
+            stars, diag = _one_star_noise(1, K, data_cov, period=p, inc_deg=i, baseline_var=float(bvar))
             ymu, ycov, ycho, _ = e.ylm_conditional(t[None, :], r[None, :], stars, rta1, sinv, sinvmu, diag=diag,
                                                    with_cho=with_cho)
         else:
@@ -1282,21 +1254,15 @@ class StarryProcess(object):
         var = diag if diag is not None else stars["data_var"][:, None]
         incs = np.broadcast_to(np.asarray(defaults["i"] if i is None else i, dtype=np.float64), (S,))
         for s_ in np.nonzero(~np.all(var > 0, axis=1))[0]:
-            dc = diag[s_] if diag is not None else stars["data_var"][s_]
-            m1, c1, l1 = self._ylm_posterior(t[s_], flux[s_], dc, incs[s_], stars["period"][s_],
-                                             utab[stars["table"][s_]], stars["baseline_mean"][s_],
-                                             stars["baseline_var"][s_], nsamples > 0, full=True)
+            a = _star_fallback_args(s_, t, flux, stars, utab, diag)
+            m1, c1, l1 = self._ylm_posterior(*a[:3], incs[s_], *a[3:], nsamples > 0, full=True)
             ymu[s_], ycov[s_] = m1, c1
             if ycho is not None:
                 ycho[s_] = l1
         out = (Eager(ymu.cpu().numpy()), Eager(ycov.cpu().numpy()))
         if nsamples > 0:
             z = self._rng(seed).normal(size=(S, self._nylm, nsamples))
-            zt = e.f64(np.ascontiguousarray(np.swapaxes(z, 1, 2)))
-            smp = e.empty(S, nsamples, self._nylm)
-            e.gemm_nt_batched(zt, ycho, smp)                          # (ycho_s z_s)^T
-            smp += ymu[:, None, :]
-            out = out + (Eager(smp.cpu().numpy()),)
+            out = out + (Eager(_affine_samples(e, ymu, ycho, z).cpu().numpy()),)
         return out
 
     def log_likelihood_ensemble(self, t, flux, data_cov, i=None, p=None, u=None,
@@ -1311,7 +1277,6 @@ class StarryProcess(object):
         curves are padded to the longest and each star is evaluated on its own cadences
         only (``sp_star.nobs``)."""
         e = self._engine
-        f = self._flux
         nobs = 0
         if isinstance(flux, (list, tuple)) and len(flux) == 0:
             return Eager(np.empty(0))
@@ -1338,16 +1303,9 @@ class StarryProcess(object):
                                                          nobs=nobs)
         if diag is not None:
             diag = e.f64(diag)
-        f._bind()
-        rta1 = e.f64(e.rTA1L(utab))
-        tab = mv = None
-        if self._marginalize_over_inclination:
-            tab, mv = e.kernel_table(rta1, self._covpts)
-        out, status = e.lnlike_ensemble(
-            e.f64(np.ascontiguousarray(t)), e.f64(flux[:, None, :]), e.stars_to_device(stars), diag=diag,
-            conditional=not self._marginalize_over_inclination, covpts=self._covpts, tab=tab,
-            meanvar=mv, rta1=rta1, temporal=self._temporal, normalized=self._normalized,
-            norm_order=self._normN, zmax=self._normzmax)
+        branch = self._branch(utab)
+        out, status = e.lnlike_ensemble(e.f64(np.ascontiguousarray(t)), e.f64(flux[:, None, :]),
+                                        e.stars_to_device(stars), diag=diag, **branch)
         return Eager(_neg_inf_if_nan(out.cpu().numpy()))
 
     # -- conditional likelihood on a grid of inclinations (calibrate/inclination.py:9-76) ------------------
@@ -1422,9 +1380,8 @@ class StarryProcess(object):
         fast = (not self._time_variable and data_cov.ndim <= 1 and bmean.ndim == 0 and bvar.ndim == 0
                 and np.all(data_cov > 0) and np.all(np.isfinite(data_cov)))
         if fast:
-            stars = make_stars(1, period=p, baseline_var=float(bvar), baseline_mean=float(bmean),
-                               data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
-            diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (K,))[None, :]
+            stars, diag = _one_star_noise(1, K, data_cov, period=p, baseline_var=float(bvar),
+                                          baseline_mean=float(bmean))
             val, status = self._incl_basis(t[None, :], F[None, :, :], stars, u[None, :], diag, inc)
             if not np.any(status[0] & SP_STAR_NO_BASIS):
                 return Eager(_neg_inf_if_nan(val[0]))
@@ -1451,10 +1408,8 @@ class StarryProcess(object):
         else:
             dense[:] = True
         for s_ in np.nonzero(dense)[0]:
-            dc = diag[s_] if diag is not None else stars["data_var"][s_]
-            out[s_] = self._incl_dense(t[s_], flux[s_][None, :], dc, inc, stars["period"][s_],
-                                       utab[stars["table"][s_]], stars["baseline_mean"][s_],
-                                       stars["baseline_var"][s_])
+            a = _star_fallback_args(s_, t, flux, stars, utab, diag)
+            out[s_] = self._incl_dense(a[0], a[1][None, :], a[2], inc, *a[3:])
         return Eager(out)
 
     # -- surface maps with the inclination marginalised on a grid ------------------------------------
@@ -1535,11 +1490,9 @@ class StarryProcess(object):
         def components(jj, with_cho):
             n = len(jj)
             if positive:
-                stars = make_stars(n, period=p, inc_deg=inc[jj], baseline_var=float(baseline_var),
-                                   baseline_mean=float(baseline_mean),
-                                   data_var=float(data_cov) if data_cov.ndim == 0 else 0.0)
+                stars, diag = _one_star_noise(n, K, data_cov, period=p, inc_deg=inc[jj],
+                                              baseline_var=float(baseline_var), baseline_mean=float(baseline_mean))
                 stars["table"][:] = 0
-                diag = None if data_cov.ndim == 0 else np.broadcast_to(data_cov, (n, K))
                 sinv, sinvmu = self._ylm_precision()
                 m, c, l, _ = e.ylm_conditional(np.broadcast_to(t, (n, K)), np.broadcast_to(flux, (n, K)), stars,
                                                self._flux._rta1(u), sinv, sinvmu, diag=diag, with_cho=with_cho)
@@ -1595,9 +1548,8 @@ class StarryProcess(object):
         dense = np.nonzero(status.cpu().numpy() & SP_STAR_NO_BASIS)[0] if S else []
 
         def star_args(s_):
-            dc = diag[s_] if diag is not None else stars["data_var"][s_]
-            return (t[s_], flux[s_], dc, inc, logw, stars["period"][s_], utab[stars["table"][s_]],
-                    stars["baseline_mean"][s_], stars["baseline_var"][s_])
+            a = _star_fallback_args(s_, t, flux, stars, utab, diag)
+            return a[:3] + (inc, logw) + a[3:]
 
         for s_ in dense:
             w1, m1, c1, mi1 = self._ylm_marginal_dense(*star_args(s_), return_cov=return_cov)
