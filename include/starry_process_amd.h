@@ -778,6 +778,46 @@ int sp_lnlike_grad_linear(sp_handle *h, int S, int K, int q, const double *t_dev
                           double *lambar_dev /* NULL or [S, q]: d lnL_s / d lambda_sj */,
                           double *wmean_dev /* NULL or [S, q] */, void *stream);
 
+/* ---- The ensemble gradient with linear regressors marginalised out, conditional branch --------------------------------
+ * sp_lnlike_grad_conditional for the model of sp_lnlike_grad_linear: star s at its own inclination (sp_star.inc), flux_s
+ * = process + U_s w + noise, w ~ N(0, diag lambda_s), one light curve per star, every cadence valid.  C, A, T, the
+ * normalisation and the handle's moments as sp_lnlike_grad_conditional; P, G_q, v, Z, alpha~ and B = [alpha~, z_1 .. z_q]
+ * as sp_lnlike_grad_linear:
+ *   lnlike_dev [S]:   -1/2 r^T alpha~ - 1/2 log det C - sum log (L_G)_jj - K/2 log 2 pi   (sp_lnlike_linear's lnlike with
+ *                     conditional = 1)
+ *   d lnL / dC = (B B^T - C^-1) / 2, pulled back exactly as sp_lnlike_grad_conditional pulls (alpha alpha^T - C^-1) / 2
+ *   back:  H_ij = c1 (sum_b B_ib B_jb - C^-1_ij) / 2 + w_i + w_j,  Ht = H o T,  B_A = Ht A
+ *   mubar_dev [S, N], sigbar_dev [S, N, N]:  d lnL_s / d (mu_y, Sigma_y); sigbar is the symmetric adjoint A^T B_A
+ *   starbar_dev [S, SP_STARBAR]:  period, inclination per radian, baseline_mean (sum_i alpha~_i), baseline_var
+ *                     <G~, 1 1^T>, log of a common factor on the data variances <G~, D>, 0
+ *   lambar_dev [S, q] (may be NULL), wmean_dev [S, q] (may be NULL):  as sp_lnlike_grad_linear's
+ * The launches: sp_lnlike_grad_conditional's forward, sp_lnlike_grad_linear's pass over the lower tiles of C^-1 and its
+ * q x q stage, one workgroup per lower tile that forms the 64 x 64 block of B B^T on the fp64 matrix cores and multiplies
+ * the tile of Ht against A, then sp_lnlike_grad_conditional's tail.  Sums run in a fixed order and every partial result
+ * has one writer: the same bits run after run, alone or among other stars, at any position.  status_dev [S] (may be
+ * NULL).  Per star:
+ *   covariance that does not factor, or z > zmax:  lnlike = -inf; zeros in mubar, sigbar, starbar, lambar and wmean;
+ *                                                  SP_STAR_NOT_PD / SP_STAR_ZMAX
+ *   ragged star (0 < nobs < K):                    NaN in every output, SP_STAR_NAN
+ *   a NaN reaching G_q, v or lnL (a negative or non-finite lambda, say):  NaN in every output, SP_STAR_NAN
+ * No star affects another.  q outside 1 .. 32, K < 2 or a null required pointer: SP_ERR_INVALID, nothing launched; a
+ * null rta1_dev likewise, a handle without moments SP_ERR_STATE.  A host-only handle: SP_ERR_NO_DEVICE, before
+ * everything else.  S = 0: SP_OK, nothing touched.  All launches go to `stream`; nothing is synchronised.
+ * workspace_dev: sp_lnlike_grad_conditional_linear_workspace_bytes(h, S, K, q) bytes (0 for a null handle, S < 1, K < 2
+ * or q outside 1 .. 32): sp_lnlike_grad_conditional_workspace_bytes' regions with the K x roundup(4 + q, 16) panel in the
+ * place of its four vectors, the slots sized for the wider of the panel and N columns, and (q + 1)(q + 2) / 2 + q^2 +
+ * 3 q + 6 more doubles per star (each region rounded up to 256 bytes): it grows with q.                                */
+size_t sp_lnlike_grad_conditional_linear_workspace_bytes(sp_handle *h, int S, int K, int q);
+int sp_lnlike_grad_conditional_linear(sp_handle *h, int S, int K, int q, const double *t_dev,
+                                      const double *flux_dev /* [S, K] */, const double *diag_dev,
+                                      const sp_star *stars_dev, const double *basis_dev /* [S, q, K] */,
+                                      const double *basis_var_dev /* [S, q] */, const double *rta1_dev, int temporal,
+                                      int normalized, int norm_order, double zmax, void *workspace_dev,
+                                      double *lnlike_dev /* [S] */, double *mubar_dev /* [S, N] */,
+                                      double *sigbar_dev /* [S, N, N] */, double *starbar_dev /* [S, SP_STARBAR] */,
+                                      double *lambar_dev /* NULL or [S, q] */, double *wmean_dev /* NULL or [S, q] */,
+                                      uint32_t *status_dev /* [S], may be NULL */, void *stream);
+
 /* ---- fp64 NT product on the matrix cores (the kernel behind a13 / a17, exposed) -------
  *   C[b] = beta * C[b] + alpha * A[b] . B[b]^T,   beta in {0, 1}
  * A: M x K (lda), B: N x K (ldb), C: M x N (ldc), row-major, `batch` matrices strideA /

@@ -115,6 +115,9 @@ PROTOTYPES = {
     "sp_lnlike_grad_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_lnlike_grad_linear": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V, _V,
                                    _V, _V, _V, _V]),
+    "sp_lnlike_grad_conditional_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I]),
+    "sp_lnlike_grad_conditional_linear": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
+                                               _V, _V, _V, _V, _V]),
     "sp_gp_condition": (_I, [_V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
     "sp_predict_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_predict_assemble": (_I, [_V, _I, _I, _I, _V, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _V, _V, _V, _V]),

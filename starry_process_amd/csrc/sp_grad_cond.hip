@@ -336,17 +336,17 @@ __global__ __launch_bounds__(256) void grad_cond_final_kernel(
     for (size_t e = tid; e < (size_t)N * N; e += 256) sigbar[(size_t)s * N * N + e] = nanv;
 }
 
-struct GradCondLayout {
-  size_t inv, cinv, vec, dots, hcoef, logdet, meanbar, A, AT, B, BT, Abar, dR, R2, vbar, thbar, partial, total;
-};
-GradCondLayout grad_cond_layout(sp_handle *h, int S, int K) {
-  const int Kr = sp_roundup(K, SP_NB), N = h->N;
-  GradCondLayout G;
+}  // namespace
+
+// (q = 0: the regions of the q x q stage are empty and every other one is where it was before regressors)
+SpGradCondLayout sp_grad_cond_layout(const sp_handle *h, int S, int K, int q) {
+  const int Kr = sp_roundup(K, SP_NB), N = h->N, NC = q ? sp_grad_lin_ncols(q) : 4, R = q + 1;
+  SpGradCondLayout G;
   SpCarve c;
   const size_t d = sizeof(double), mat = d * (size_t)S * Kr * N;
   sp_sweep_head(c, h, S, K, G.inv, G.cinv);          // (cinv: the raw lower tiles first, then C^-1)
-  G.vec = c.take(d * (size_t)S * 4 * K);             // C^-1 [p, q, 1, r]
-  G.dots = c.take(d * (size_t)S * 2);
+  G.vec = c.take(d * (size_t)S * NC * K);            // C^-1 [p, q, 1, r]; with regressors [.., u_1 .. u_q], then w, B
+  G.dots = c.take(d * (size_t)S * R * 2);
   G.hcoef = c.take(d * S);
   G.logdet = c.take(d * S);
   G.meanbar = c.take(d * S);
@@ -359,13 +359,17 @@ GradCondLayout grad_cond_layout(sp_handle *h, int S, int K) {
   G.R2 = c.take(d * (size_t)S * h->NWIG);
   G.vbar = c.take(d * (size_t)S * N);
   G.thbar = c.take(d * (size_t)S * K);
-  // the slots of B ([S][ntr][Kr][N]); before that the row sums' and the matrix-vector products' parts
-  G.partial = c.take(d * (size_t)S * (Kr / SP_NB) * Kr * (N > 4 ? N : 4));
+  G.lin = c.take(q ? d * (size_t)S * SP_GRAD_LIN_SCAL : 0);
+  G.gram = c.take(q ? d * (size_t)S * (R * (R + 1) / 2) : 0);
+  G.mix = c.take(d * (size_t)S * q * q);
+  G.wm = c.take(d * (size_t)S * q);
+  // the slots of B ([S][ntr][Kr][N]); before that the row sums' and the matrix-vector products' parts, or the slots
+  // of the panel product ([S][ntr][K][NC]: more than N columns at low degree)
+  const size_t cols = (size_t)(N > NC ? N : NC);
+  G.partial = c.take(d * (size_t)S * (Kr / SP_NB) * Kr * cols);
   G.total = c.off;
   return G;
 }
-
-}  // namespace
 
 // The forward of the conditional branch's sweeps (this file's gradient, sp_fisher_cond.hip's Fisher information): C as the
 // likelihood sees it in the corner of the system the inverse factors, then C^-1 (lower tiles) into Cinv [S][Kr][Kr].
@@ -419,11 +423,37 @@ int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V
   return SP_OK;
 }
 
+int sp_launch_grad_cond_tail(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev,
+                             const SpGradCondTail &T) {
+  const int S = P.S, K = P.K, Kr = sp_roundup(K, SP_NB), N = h->N, ntr = Kr / SP_NB;
+  hipStream_t st = P.st;
+  const long sAB = (long)Kr * N;
+  int rc;
+  hipLaunchKernelGGL(grad_cond_reduce_kernel, dim3((N + 63) / 64, ntr, S), dim3(256), 0, st, Kr, N, T.part, T.A, T.B, T.BT,
+                     T.AT);
+  SP_LAUNCH_CHECK();
+  // ---- Sigma_y_bar = A^T B (N x N, depth Kr) and A_bar = 2 B Sigma_y (Sigma_y symmetric: B . Sigma_y^T)
+  if ((rc = sp_launch_gemm_nt(T.AT, Kr, sAB, T.BT, Kr, sAB, T.sigbar, N, (long)N * N, N, N, Kr, 1.0, 0, 0, S, st))) return rc;
+  if ((rc = sp_launch_gemm_nt(T.B, N, sAB, h->d_cov_ylm, N, 0, T.Abar, N, sAB, Kr, N, N, 2.0, 0, 0, S, st))) return rc;
+  // ---- back through the rotations, every star and row in one launch
+  if ((rc = sp_launch_Rx(h, V.cs(), S, T.R2, T.dR, st))) return rc;     // (cs: cos / sin of -inc, left by the design matrix)
+  hipLaunchKernelGGL(grad_cond_rot_kernel, dim3(K, S), dim3(256), sizeof(double) * 3 * N, st, h->ydeg, N, K, Kr, h->d_l_of,
+                     h->d_m_of, h->d_mirror, h->d_blk, h->d_Rx90, T.Abar, T.meanbar, h->d_mean_ylm, V.vrow(), V.theta(), T.B,
+                     T.thbar);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_cond_vbar_kernel, dim3((N + 63) / 64, S), dim3(256), 0, st, K, Kr, N, T.B, T.vbar);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(grad_cond_final_kernel, dim3(S), dim3(256), 0, st, N, K, Kr, h->NWIG, h->d_l_of, h->d_blk, P.stars,
+                     rta1_dev, T.dR, T.vbar, T.thbar, P.t, T.A, T.meanbar, T.mubar, T.sigbar, T.starbar);
+  SP_LAUNCH_CHECK();
+  return SP_OK;
+}
+
 extern "C" {
 
 size_t sp_lnlike_grad_conditional_workspace_bytes(sp_handle *h, int S, int K) {
   if (!h || S < 1 || K < 2) return 0;
-  return grad_cond_layout(h, S, K).total;
+  return sp_grad_cond_layout(h, S, K, 0).total;
 }
 
 int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, const double *flux_dev,
@@ -440,10 +470,9 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   hipStream_t st = (hipStream_t)stream;
   const int Kr = sp_roundup(K, SP_NB), N = h->N, ntr = Kr / SP_NB, ntri = ntr * (ntr + 1) / 2;
   if ((long)S * ntri > 0x7ffffff0L) return SP_ERR_INVALID;
-  const GradCondLayout G = grad_cond_layout(h, S, K);
+  const SpGradCondLayout G = sp_grad_cond_layout(h, S, K, 0);
   char *base = static_cast<char *>(workspace_dev);
   const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
-  double *theta = V.theta(), *cs = V.cs(), *vrow = V.vrow();
   const SpProblem P = sp_make_problem(h, 1, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, 0, nullptr, nullptr, temporal,
                                       normalized, norm_order, zmax, stream);
   double *Cinv = at<double>(base, G.cinv), *vec = at<double>(base, G.vec), *dots = at<double>(base, G.dots);
@@ -451,7 +480,6 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
   double *A = at<double>(base, G.A), *AT = at<double>(base, G.AT), *B = at<double>(base, G.B), *BT = at<double>(base, G.BT);
   double *Abar = at<double>(base, G.Abar), *dR = at<double>(base, G.dR), *R2 = at<double>(base, G.R2);
   double *vbar = at<double>(base, G.vbar), *thbar = at<double>(base, G.thbar), *partial = at<double>(base, G.partial);
-  const long sAB = (long)Kr * N;
   int rc;
   // ---- forward: C as the likelihood sees it, and its inverse
   if ((rc = sp_launch_cond_inverse(h, P, V, rta1_dev, A, B, Cinv, Cinv, partial, logdet))) return rc;
@@ -471,22 +499,10 @@ int sp_lnlike_grad_conditional(sp_handle *h, int S, int K, const double *t_dev, 
     hipLaunchKernelGGL((grad_cond_hta_kernel<SP_TEMPORAL_EXPSQUARED>), dim3(nblk), dim3(256), 0, st, K, Kr, N, S, Cinv, A,
                        t_dev, stars_dev, vec, hcoef, partial);
   SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_cond_reduce_kernel, dim3((N + 63) / 64, ntr, S), dim3(256), 0, st, Kr, N, partial, A, B, BT, AT);
-  SP_LAUNCH_CHECK();
-  // ---- Sigma_y_bar = A^T B (N x N, depth Kr) and A_bar = 2 B Sigma_y (Sigma_y symmetric: B . Sigma_y^T)
-  if ((rc = sp_launch_gemm_nt(AT, Kr, sAB, BT, Kr, sAB, sigbar_dev, N, (long)N * N, N, N, Kr, 1.0, 0, 0, S, st))) return rc;
-  if ((rc = sp_launch_gemm_nt(B, N, sAB, h->d_cov_ylm, N, 0, Abar, N, sAB, Kr, N, N, 2.0, 0, 0, S, st))) return rc;
-  // ---- back through the rotations, every star and row in one launch
-  if ((rc = sp_launch_Rx(h, cs, S, R2, dR, st))) return rc;     // (cs: cos / sin of -inc, left by the design matrix)
-  hipLaunchKernelGGL(grad_cond_rot_kernel, dim3(K, S), dim3(256), sizeof(double) * 3 * N, st, h->ydeg, N, K, Kr, h->d_l_of,
-                     h->d_m_of, h->d_mirror, h->d_blk, h->d_Rx90, Abar, meanbar, h->d_mean_ylm, vrow, theta, B, thbar);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_cond_vbar_kernel, dim3((N + 63) / 64, S), dim3(256), 0, st, K, Kr, N, B, vbar);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(grad_cond_final_kernel, dim3(S), dim3(256), 0, st, N, K, Kr, h->NWIG, h->d_l_of, h->d_blk, stars_dev,
-                     rta1_dev, dR, vbar, thbar, t_dev, A, meanbar, mubar_dev, sigbar_dev, starbar_dev);
-  SP_LAUNCH_CHECK();
-  return SP_OK;
+  // ---- the slots added up, Sigma_y_bar, A_bar, back through the rotations
+  return sp_launch_grad_cond_tail(h, P, V, rta1_dev,
+                                  SpGradCondTail{A, partial, meanbar, AT, B, BT, Abar, dR, R2, vbar, thbar, mubar_dev,
+                                                 sigbar_dev, starbar_dev});
 }
 
 }  // extern "C"

@@ -36,8 +36,6 @@ constexpr int GL_BLD = 37;                  // LDS row of a tile edge's B rows: 
 constexpr int GL_TC = 64;                   // cadences of the Gram kernel's rows staged at a time
 constexpr int GL_LDS_BUDGET = 24 * 1024;    // dynamic LDS of the scatter (bins, table) beside its 37 KB of B rows
 
-inline int gl_ncols(int q) { return sp_roundup(4 + q, 16); }
-
 // entry j of column n of the panel [p, q, 1, r, u_1 .. u_q, 0 ..]; zero beyond the K cadences
 __device__ __forceinline__ double gl_panel_entry(int s, int j, int n, int K, int q, const double *__restrict__ flux,
                                                  const double *__restrict__ basis, const double *__restrict__ qv,
@@ -387,7 +385,7 @@ struct GradLinLayout {
   size_t inv, cinv, vec, dots, hcoef, logdet, lin, gram, mix, wm, sbar, spart, partial, total;
 };
 GradLinLayout grad_lin_layout(sp_handle *h, int S, int K, int q, int covpts) {
-  const int Kr = sp_roundup(K, SP_NB), NC = gl_ncols(q), R = q + 1;
+  const int Kr = sp_roundup(K, SP_NB), NC = sp_grad_lin_ncols(q), R = q + 1;
   GradLinLayout G;
   SpCarve c;
   const size_t d = sizeof(double);
@@ -420,6 +418,33 @@ inline int gl_bin_copies(int covpts) {
 
 }  // namespace
 
+int sp_launch_grad_linear_front(const SpProblem &P, const SpViews &V, const SpGradLinFront &F) {
+  const int S = P.S, K = P.K, q = F.q, Kr = sp_roundup(K, SP_NB), ntr = Kr / 64, NC = sp_grad_lin_ncols(q);
+  hipStream_t st = P.st;
+  const SpCoef *coef = (const SpCoef *)V.coef();
+  const dim3 tiles(ntr * (ntr + 1) / 2, S);
+#define SP_PANEL(NB)                                                                                                 \
+  hipLaunchKernelGGL(gl_panel_kernel<NB>, tiles, dim3(256), 0, st, K, Kr, q, F.Cinv, P.flux, F.basis, P.stars, coef, \
+                     V.qv(), P.normalized, F.partial)
+  if (NC == 16) SP_PANEL(1);
+  else if (NC == 32) SP_PANEL(2);
+  else SP_PANEL(3);
+#undef SP_PANEL
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_panel_reduce_kernel, dim3((unsigned)(((size_t)K * NC + 255) / 256), S), dim3(256), 0, st, K, ntr, NC,
+                     q, F.partial, F.vec);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_gram_kernel, dim3(S), dim3(256), 0, st, K, q, NC, P.flux, F.basis, P.stars, coef, F.vec, F.gram);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_finish_kernel, dim3(S), dim3(64), 0, st, K, q, F.gram, F.bvar, P.stars, coef, V.info(), F.logdet,
+                     P.normalized, P.zmax, F.lin, F.mix, F.wm, F.lambar, F.wmean);
+  SP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gl_mix_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, q, NC, F.mix, F.wm, F.vec);
+  SP_LAUNCH_CHECK();
+  return sp_launch_grad_scalars_linear(P, V, q, NC, F.lin, F.Cinv, F.logdet, F.vec, F.dots, F.hcoef, F.lnlike, F.meanbar,
+                                       F.status, F.starbar);
+}
+
 extern "C" {
 
 size_t sp_lnlike_grad_linear_workspace_bytes(sp_handle *h, int S, int K, int q, int covpts) {
@@ -445,7 +470,7 @@ int sp_lnlike_grad_linear(sp_handle *h, int S, int K, int q, const double *t_dev
   const SpProblem P = sp_make_problem(h, 0, S, K, 1, t_dev, flux_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
                                       temporal, normalized, norm_order, zmax, stream);
   hipStream_t st = P.st;
-  const int Kr = sp_roundup(K, SP_NB), ntr = Kr / 64, ntiles = ntr * (ntr + 1) / 2, NC = gl_ncols(q), np = covpts + 4;
+  const int Kr = sp_roundup(K, SP_NB), ntr = Kr / 64, ntiles = ntr * (ntr + 1) / 2, NC = sp_grad_lin_ncols(q), np = covpts + 4;
   const GradLinLayout G = grad_lin_layout(h, S, K, q, covpts);
   char *base = static_cast<char *>(workspace_dev);
   const SpViews V = sp_sweep_views(h, S, K, base + G.inv);
@@ -453,30 +478,12 @@ int sp_lnlike_grad_linear(sp_handle *h, int S, int K, int q, const double *t_dev
   double *partial = at<double>(base, G.partial), *spart = at<double>(base, G.spart), *lin = at<double>(base, G.lin);
   double *gram = at<double>(base, G.gram), *mix = at<double>(base, G.mix), *wm = at<double>(base, G.wm);
   double *hcoef = at<double>(base, G.hcoef), *starbar = starbar_dev ? starbar_dev : at<double>(base, G.sbar);
-  const SpCoef *coef = (const SpCoef *)V.coef();
   if (const int rc = sp_launch_marginal_inverse(h, P, V, Cinv, logdet)) return rc;
-  const dim3 tiles(ntiles, S);
-#define SP_PANEL(NB)                                                                                                 \
-  hipLaunchKernelGGL(gl_panel_kernel<NB>, tiles, dim3(256), 0, st, K, Kr, q, Cinv, flux_dev, basis_dev, stars_dev, coef, \
-                     V.qv(), normalized, partial)
-  if (NC == 16) SP_PANEL(1);
-  else if (NC == 32) SP_PANEL(2);
-  else SP_PANEL(3);
-#undef SP_PANEL
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gl_panel_reduce_kernel, dim3((unsigned)(((size_t)K * NC + 255) / 256), S), dim3(256), 0, st, K, ntr, NC,
-                     q, partial, vec);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gl_gram_kernel, dim3(S), dim3(256), 0, st, K, q, NC, flux_dev, basis_dev, stars_dev, coef, vec, gram);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gl_finish_kernel, dim3(S), dim3(64), 0, st, K, q, gram, basis_var_dev, stars_dev, coef, V.info(), logdet,
-                     normalized, zmax, lin, mix, wm, lambar_dev, wmean_dev);
-  SP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gl_mix_kernel, dim3((K + 255) / 256, S), dim3(256), 0, st, K, q, NC, mix, wm, vec);
-  SP_LAUNCH_CHECK();
-  if (const int rc = sp_launch_grad_scalars_linear(P, V, q, NC, lin, Cinv, logdet, vec, at<double>(base, G.dots), hcoef,
-                                                   lnlike_dev, meanbar_dev, status_dev, starbar))
+  if (const int rc = sp_launch_grad_linear_front(
+          P, V, SpGradLinFront{q, basis_dev, basis_var_dev, Cinv, logdet, vec, at<double>(base, G.dots), hcoef, partial, lin,
+                               gram, mix, wm, lnlike_dev, meanbar_dev, status_dev, starbar, lambar_dev, wmean_dev}))
     return rc;
+  const dim3 tiles(ntiles, S);
   const size_t lds = sizeof(double) * (size_t)(nb + 1) * np;
 #define SP_SCATTER(TK)                                                                                               \
   hipLaunchKernelGGL(gl_scatter_kernel<TK>, tiles, dim3(256), lds, st, K, Kr, q, NC, Cinv, V.theta(), t_dev, stars_dev, \

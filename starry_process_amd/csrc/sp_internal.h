@@ -613,6 +613,24 @@ int sp_launch_grad_scalars_linear(const SpProblem &P, const SpViews &V, int q, i
                                   double *lnlike, double *meanbar, uint32_t *status, double *starbar);
 int sp_launch_grad_tile_sums(int S, int K, int np, int ntiles, const sp_star *stars, const double *partial, double *ybar,
                              const double *spart, double *starbar, hipStream_t st);
+// sp_grad_linear.hip: the front of a sweep with q regressors marginalised out, behind C^-1 (lower tiles) and log det C,
+// on either branch (sp_lnlike_grad_linear, sp_lnlike_grad_conditional_linear): the panel product C^-1 [p, q, 1, r, U] and
+// its fixed-order reduction, the Gram matrix, the q x q stage, the mix, then sp_launch_grad_scalars_linear.  Leaves
+// vec [S][NC][K], NC = sp_grad_lin_ncols(q): w in row 0, B = [alpha~, z_1 .. z_q] in rows 3 .. 3 + q; hcoef, meanbar,
+// lnlike, status, the slots 2-5 of starbar (required), lambar and wmean [S][q] (either may be null).
+// Scratch: partial [S][Kr / 64][K][NC], dots [S][1 + q][2], lin [S][SP_GRAD_LIN_SCAL], gram [S][(q + 1)(q + 2) / 2],
+// mix [S][q][q], wm [S][q].  P.flux: one light curve per star.
+static inline int sp_grad_lin_ncols(int q) { return sp_roundup(4 + q, 16); }
+struct SpGradLinFront {
+  int q;
+  const double *basis, *bvar;         // [S][q][K], [S][q]
+  const double *Cinv, *logdet;
+  double *vec, *dots, *hcoef, *partial, *lin, *gram, *mix, *wm;
+  double *lnlike, *meanbar;
+  uint32_t *status;
+  double *starbar, *lambar, *wmean;
+};
+int sp_launch_grad_linear_front(const SpProblem &P, const SpViews &V, const SpGradLinFront &F);
 
 // sp_grad_cond.hip: the forward of the conditional branch's sweeps (gradient, Fisher information): the design matrices
 // A [S][Kr][N], B = A Sigma_y, the raw covariance (A Sigma_y A^T) o T into raw [S][Kr][Kr] (lower tiles; raw may be Cinv,
@@ -623,6 +641,24 @@ int sp_launch_cond_inverse(sp_handle *h, const SpProblem &P, const SpViews &V, c
 // ... its first half alone: everything up to C in the corner of the system (raw is then scratch of its own)
 int sp_launch_cond_covariance(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev, double *A,
                               double *B, double *raw, double *partial);
+// sp_grad_cond.hip: the workspace of the conditional branch's gradient sweeps, without regressors (q = 0: what
+// sp_lnlike_grad_conditional_workspace_bytes answers) or with q of them (sp_grad_cond_linear.hip): vec widened to the
+// panel's columns, dots to 1 + q pairs, the q x q stage's scratch, and `partial` sized for the larger of its uses
+struct SpGradCondLayout {
+  size_t inv, cinv, vec, dots, hcoef, logdet, meanbar, A, AT, B, BT, Abar, dR, R2, vbar, thbar, lin, gram, mix, wm, partial,
+      total;
+};
+SpGradCondLayout sp_grad_cond_layout(const sp_handle *h, int S, int K, int q);
+// ... and the tail both sweeps run behind the slots of B = Ht A (part [S][Kr / 64][Kr][N], A [S][Kr][N]): the slots
+// added in their order, Sigma_y_bar = A^T B, A_bar = 2 B Sigma_y, back through the rotations, the period and inclination
+// slots of starbar, mu_y_bar.  Reads cs, vrow and theta of V as the forward left them.
+struct SpGradCondTail {
+  const double *A, *part, *meanbar;
+  double *AT, *B, *BT, *Abar, *dR, *R2, *vbar, *thbar;
+  double *mubar, *sigbar, *starbar;
+};
+int sp_launch_grad_cond_tail(sp_handle *h, const SpProblem &P, const SpViews &V, const double *rta1_dev,
+                             const SpGradCondTail &T);
 // The scratch of that forward in a sweep that takes either branch: the design matrices A, B = A Sigma_y [S][Kr][N] and
 // the raw covariance [S][Kr][Kr]; nothing in the marginal branch
 struct SpCondCarve {

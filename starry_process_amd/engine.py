@@ -1717,6 +1717,38 @@ class Engine(object):
     def grad_conditional_workspace(self, S, K):
         return self._scratch(self._L.sp_lnlike_grad_conditional_workspace_bytes(self._h, S, K))
 
+    def grad_conditional_linear_workspace(self, S, K, q):
+        """Device scratch of ``lnlike_grad_conditional_linear`` (sp_lnlike_grad_conditional_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_lnlike_grad_conditional_linear_workspace_bytes(self._h, int(S), int(K), int(q)))
+
+    def lnlike_grad_conditional_linear(self, t, flux, stars_dev, basis, basis_var, rta1, diag=None, temporal=None,
+                                       normalized=True, norm_order=20, zmax=0.023, workspace=None):
+        """Device half of the CONDITIONAL branch's ensemble gradient with q linear regressors per star marginalised out
+        (sp_lnlike_grad_conditional_linear), at the engine's current moments: t, flux [S, K]; basis [S, q, K], regressor
+        j of star s along row j; basis_var [S, q], the prior variances of the weights; rta1 [ntab, N] -> (lnlike [S],
+        mubar [S, N], sigbar [S, N, N], starbar [S, 6], lambar [S, q], w_mean [S, q], status [S]):
+        ``lnlike_linear(conditional=True)``'s likelihood, its derivatives as ``lnlike_grad_conditional`` returns them,
+        with respect to the prior variances themselves, and the posterior mean of the weights."""
+        torch = _torch()
+        S, K = t.shape
+        if tuple(flux.shape) != (S, K):
+            raise ValueError("`flux` must be (S, K): one light curve per star")
+        basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
+        N = self.N
+        out, mubar, sigbar, sbar = self.empty(S), self.empty(S, N), self.empty(S, N, N), self.empty(S, 6)
+        lbar, wmean = self.empty(S, q), self.empty(S, q)
+        status = torch.zeros(S, dtype=torch.int32, device=self.device)
+        if S == 0:
+            return out, mubar, sigbar, sbar, lbar, wmean, status
+        nbytes = int(self._L.sp_lnlike_grad_conditional_linear_workspace_bytes(self._h, S, K, q))
+        ws = self._grad_scratch(nbytes, workspace)
+        check(self._L.sp_lnlike_grad_conditional_linear(
+            self._h, S, K, q, self._p(t), self._p(flux), self._p(diag), self._p(stars_dev), self._p(basis),
+            self._p(basis_var), self._p(rta1), TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax),
+            self._p(ws), self._p(out), self._p(mubar), self._p(sigbar), self._p(sbar), self._p(lbar), self._p(wmean),
+            self._p(status), self._stream()))
+        return out, mubar, sigbar, sbar, lbar, wmean, status
+
     def grad_workspace(self, S, K, covpts, M=1):
         return self._scratch(self._L.sp_lnlike_grad_workspace_bytes_multi(self._h, S, K, int(M), int(covpts)))
 

@@ -888,7 +888,7 @@ def ensemble_gradient_conditional(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], 
 _WRT_COND = ("p", "i", "baseline_mean", "baseline_var", "log_var")
 
 
-def _check_wrt_conditional(wrt):
+def _check_wrt_conditional(wrt, has_basis=False):
     """``wrt`` as a tuple of names the conditional sweep serves (None stays None); ValueError otherwise.  No device
     work."""
     if wrt is None:
@@ -899,8 +899,10 @@ def _check_wrt_conditional(wrt):
             raise ValueError("wrt: 'tau' is not differentiated on the conditional branch (the sweep applies the temporal "
                              "kernel but takes no derivative with respect to its timescale; the marginal branch does: "
                              "EnsembleGradient)")
-        if name not in _WRT_COND:
-            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT_COND)))
+        if name not in _WRT_COND and name != "basis_var":
+            raise ValueError("wrt: unknown name %r (one of %s)" % (name, ", ".join(_WRT_COND + ("basis_var",))))
+    if "basis_var" in wrt and not has_basis:
+        raise ValueError("wrt: 'basis_var' needs regressors (EnsembleGradientConditional(..., basis=..., basis_var=...))")
     return wrt
 
 
@@ -917,23 +919,54 @@ class EnsembleGradientConditional(_EnsembleSweep):
     contracted with the moments' exact tangents (``ylm_moments_device_grad``) on the device -- c and n in closed form,
     with the rule of ``ensemble_gradient_conditional`` on the boundary c = 0 or n = 0 -- and one small transfer leaves
     the GPU per call.  One light curve per star; scalar or per-cadence ``ferr``; ``tau``: the temporal kernel
-    multiplies the covariance (no derivative with respect to it on this branch)."""
+    multiplies the covariance (no derivative with respect to it on this branch).
+
+    Linear regressors (``basis``, ``basis_var``): flux = process + U w + noise with w ~ N(0,
+    diag(basis_var)), the model of ``log_likelihood_linear_ensemble`` and of ``EnsembleGradient(basis=...)``, validated
+    as they validate it.  The call then returns the marginalised likelihood and ITS gradient
+    (sp_lnlike_grad_conditional_linear): every name keeps its meaning, ``wrt`` also takes "basis_var" -- (S, q), the
+    derivative with respect to the prior variances themselves, finite at 0 -- and ``w_mean`` (S, q) holds the posterior
+    mean of the weights after a call.  ``upload_basis_var`` changes the variances without sending the basis again."""
 
     _WRT = _WRT_COND
+    _basis = None       # (no regressors until the constructor has uploaded some)
 
     def __init__(self, t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], u=None, ydeg=15, baseline_var=0.0,
                  baseline_mean=0.0, normalized=True, tau=None, temporal_kernel="matern32", device=None,
-                 upstream_kwargs=None):
+                 upstream_kwargs=None, basis=None, basis_var=None):
         flux = np.asarray(flux, dtype=np.float64)
         if flux.ndim != 2:
             raise ValueError("flux must be (S, K)")
+        from .linear import _regressor_args
+
+        U, Ut, lam = _regressor_args(basis, basis_var, flux.shape[0], flux.shape[1],
+                                     "a `basis` needs the prior variances of its weights, `basis_var`")
         # (the inclinations' bounds are not checked on this branch)
         self._setup(t, flux, ferr, p, i, u, ydeg, baseline_mean, baseline_var, tau, temporal_kernel, device)
         self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
-        self._ws = self._e.grad_conditional_workspace(self.S, self.K)
+        self._basis = self._basis_var = self.w_mean = None
+        self._q = 0
+        if U is None:
+            self._ws = self._e.grad_conditional_workspace(self.S, self.K)
+        else:
+            self._q = U.shape[2]
+            self._basis = self._e.f64(Ut)
+            self._basis_var = self._e.f64(lam)
+            self._ws = self._e.grad_conditional_linear_workspace(self.S, self.K, self._q)
+            _torch().cuda.synchronize(self._e.device)
         self.lnlike = self.status = None
 
     _open = staticmethod(get_engine)
+
+    def upload_basis_var(self, basis_var):
+        """New prior variances of the regressors' weights -- scalar, (q,) or (S, q), finite and >= 0 -- for the calls
+        that follow; the basis stays on the device."""
+        from .linear import check_regressor_variances
+
+        if self._basis is None:
+            raise ValueError("`basis_var` needs regressors (EnsembleGradientConditional(..., basis=..., basis_var=...))")
+        lam = check_regressor_variances(basis_var, self.S, self._q)
+        self._basis_var = self._e.f64(lam)
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=None):
         """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .}).
@@ -941,19 +974,29 @@ class EnsembleGradientConditional(_EnsembleSweep):
         wrt: None, or a tuple of names out of ("i", "p", "baseline_mean", "baseline_var", "log_var"): the dict then also
         holds arrays [S], d lnL_s / d of star s's inclination (per DEGREE, as ``log_likelihood_with_grad`` returns it),
         period (the integer part of t / p is data), baseline mean, baseline variance and the log of a common factor on
-        its data variances -- from the same sweep and the same transfer.  A star the likelihood rejects adds zeros."""
+        its data variances -- from the same sweep and the same transfer.  A star the likelihood rejects adds zeros.
+
+        With regressors: the likelihood and every derivative above are those of the marginalised model; wrt may hold
+        "basis_var": an array [S, q], d lnL_s / d of the prior variance of star s's regressor j.  New prior variances:
+        ``upload_basis_var`` ahead of the call."""
         import torch
 
         from .upstream_device import ylm_moments_device, ylm_moments_device_grad
 
-        wrt = _check_wrt_conditional(wrt)
+        wrt = _check_wrt_conditional(wrt, self._basis is not None)
         e = self._e
         r, a, b, c, n = float(r), float(a), float(b), float(c), float(n)
         mu, Sig, dmu, dSig = ylm_moments_device_grad(e, r=r, a=a, b=b, c=c, n=n, **self._ukw)
         e.set_moments_dev(mu, Sig)
-        lnl, mubar, sigbar, sbar, status = e.lnlike_grad_conditional(
-            self._t, self._flux, self._stars, self._rta1, diag=self._diag, temporal=self._temporal,
-            normalized=self._normalized, workspace=self._ws)
+        sweep_kw = dict(diag=self._diag, temporal=self._temporal, normalized=self._normalized, workspace=self._ws)
+        tail = []
+        if self._basis is None:
+            lnl, mubar, sigbar, sbar, status = e.lnlike_grad_conditional(self._t, self._flux, self._stars, self._rta1,
+                                                                         **sweep_kw)
+        else:
+            lnl, mubar, sigbar, sbar, lbar, wmean, status = e.lnlike_grad_conditional_linear(
+                self._t, self._flux, self._stars, self._basis, self._basis_var, self._rta1, **sweep_kw)
+            tail = [lbar.reshape(-1), wmean.reshape(-1)]
         # the stars' adjoints added up (a reduction over the leading axis: no atomics, the same order every call)
         gmu, gSig = mubar.sum(dim=0), sigbar.sum(dim=0)
         eps = _upstream_eps(mu.shape[0], self._ukw, like=mu)
@@ -962,14 +1005,23 @@ class EnsembleGradientConditional(_EnsembleSweep):
         g_c, g_n = _cn_chain(*inner(mu, Sig), c, n, unit=lambda: inner(
             *ylm_moments_device(e, r=r, a=a, b=b, c=1.0, n=1.0, **self._ukw)))
         # ONE transfer: [gradient | per-star values | per-star status | per-star derivatives]
-        host = torch.cat([g_rab, torch.stack([g_c, g_n]), lnl, status.to(torch.float64), sbar.reshape(-1)]).cpu().numpy()
+        # (with regressors, behind them: d lnL / d basis_var | the weights' posterior means)
+        host = torch.cat([g_rab, torch.stack([g_c, g_n]), lnl, status.to(torch.float64), sbar.reshape(-1)] + tail).cpu().numpy()
         S = self.S
         self.lnlike = host[5:5 + S].copy()
         self.status = host[5 + S:5 + 2 * S].astype(np.uint32)
         grad = {k: float(v) for k, v in zip(("r", "a", "b", "c", "n"), host[:5])}
+        if tail:
+            sq = S * self._q
+            self.w_mean = host[-sq:].reshape(S, self._q).copy()
+            if wrt is not None and "basis_var" in wrt:
+                grad["basis_var"] = host[-2 * sq:-sq].reshape(S, self._q).copy()
+            host = host[:-2 * sq]
         if wrt is not None:
             sb = host[5 + 2 * S:].reshape(S, -1)
             for k in wrt:
+                if k == "basis_var":
+                    continue
                 col = sb[:, _WRT_COND.index(k)]
                 grad[k] = col * (np.pi / 180.0) if k == "i" else col.copy()
         return float(self.lnlike.sum()), grad
@@ -978,8 +1030,9 @@ class EnsembleGradientConditional(_EnsembleSweep):
 def ensemble_gradient_conditional_device(t, flux, ferr=1.0e-3, p=1.0, i=defaults["i"], r=defaults["r"], a=defaults["a"],
                                          b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=("i", "p"), **kwargs):
     """One-shot form of ``EnsembleGradientConditional`` with the return of ``ensemble_gradient_conditional``:
-    (sum_s lnL_s, {"r", "a", "b", "c", "n": floats, and the names of ``wrt``: arrays [S]}, lnL [S])."""
-    wrt = _check_wrt_conditional(wrt)          # (before any data goes to the device)
+    (sum_s lnL_s, {"r", "a", "b", "c", "n": floats, and the names of ``wrt``: arrays [S]}, lnL [S]).  ``basis``,
+    ``basis_var`` among the keywords: the regressors of the marginalised model, and "basis_var" a name of ``wrt``."""
+    wrt = _check_wrt_conditional(wrt, kwargs.get("basis") is not None)          # (before any data goes to the device)
     eg = EnsembleGradientConditional(t, flux, ferr=ferr, p=p, i=i, **kwargs)
     total, grad = eg(r=r, a=a, b=b, c=c, n=n, wrt=wrt)
     return total, grad, eg.lnlike
