@@ -595,6 +595,44 @@ int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask /* b
                           double zmax, double *fisher_dev /* [S, P, P] */, double *dcov_dev /* NULL or [S, P, K, K] */,
                           uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* ---- Fisher information with q linear regressors per star marginalised out, either branch -----------------------
+ * The model of sp_lnlike_grad_linear: flux = process + U w + noise, w ~ N(0, diag lambda), so that star s has the
+ * covariance C~_s = C_s + U_s diag(lambda_s) U_s^T with C_s the covariance of sp_fisher_marginal (sp_fisher_conditional).
+ * The parameters enter neither U nor lambda, d_i C~ = d_i C, and
+ *   F~_s[i, j] = 1/2 tr(C~^-1 d_i C  C~^-1 d_j C) + (d_i m)(d_j m) 1^T C~^-1 1        -> fisher_dev [S, P, P]
+ * is the plain sweep's F_s with a correction of low rank: with V = C^-1 U, G_q = I + D U^T V D = L_G L_G^T, D = diag
+ * sqrt(lambda), Z = V D L_G^-T (C~^-1 = C^-1 - Z Z^T), E_i = d_i C Z, X_i = C^-1 E_i and N_i = Z^T E_i,
+ *   F~_s[i, j] = 1/2 tr(G_i G_j) - <E_i, X_j> + 1/2 tr(N_i N_j) + (d_i m)(d_j m) (1^T C^-1 1 - |Z^T 1|^2).
+ * C~ is never formed and nothing is divided by lambda: lambda_j = 0 switches regressor j off exactly, and with every
+ * variance zero F~_s is F_s bit for bit.  E_i and X_i are skinny products on the matrix cores that read every tile of
+ * d_i C and of C^-1 once; every sum has a fixed order and one writer: the same bits run after run, F~_s exactly symmetric.
+ *   basis_dev [S, q, K]     regressor j of star s along row j, q in 1 .. 32
+ *   basis_var_dev [S, q]    the prior variances lambda of the weights, finite and >= 0
+ * Every other argument, dcov_dev (the tangents d_i C, which the regressors do not alter) and the per-star rules are the
+ * plain calls'; in addition a star with a negative or non-finite variance, or whose G_q a NaN reaches: NaN, SP_STAR_NAN.
+ * No star affects another; a star's bits depend neither on its neighbours nor on the grouping.  The workspace holds, per
+ * resident star, the plain sweep's and (2 P + 2) panels of 32 x roundup(K, 64) doubles
+ * (sp_fisher_linear_workspace_bytes, sp_fisher_conditional_linear_workspace_bytes: 0 for a null handle, q outside 1 .. 32 or
+ * arguments the plain functions answer 0 for).  A null required pointer (basis_dev, basis_var_dev among them), q outside
+ * 1 .. 32, a workspace too small for one star: SP_ERR_INVALID, nothing launched.  A host-only handle: SP_ERR_NO_DEVICE.
+ * S = 0: SP_OK, nothing touched.  All launches go to `stream`; nothing is synchronised.                              */
+size_t sp_fisher_linear_workspace_bytes(sp_handle *h, int S, int K, int P, int q, int covpts);
+int sp_fisher_marginal_linear(sp_handle *h, int S, int K, int P, int q, const double *t_dev, const double *diag_dev,
+                              const sp_star *stars_dev, const double *basis_dev /* [S, q, K] */,
+                              const double *basis_var_dev /* [S, q] */, int covpts, const double *tab_dev,
+                              const double *meanvar_dev, const double *dyp_dev, const double *dmean_dev, int temporal,
+                              int normalized, int norm_order, double zmax, double *fisher_dev, double *dcov_dev,
+                              uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+size_t sp_fisher_conditional_linear_workspace_bytes(sp_handle *h, int S, int K, int P, int q);
+int sp_fisher_conditional_linear(sp_handle *h, int S, int K, int Ph, int star_mask /* bit 0: i, bit 1: p */, int q,
+                                 const double *t_dev, const double *diag_dev, const sp_star *stars_dev,
+                                 const double *basis_dev /* [S, q, K] */, const double *basis_var_dev /* [S, q] */,
+                                 const double *rta1_dev, const double *dmu_dev /* [Ph, N] */,
+                                 const double *dsig_dev /* [Ph, N, N] */, int temporal, int normalized, int norm_order,
+                                 double zmax, double *fisher_dev /* [S, P, P] */,
+                                 double *dcov_dev /* NULL or [S, P, K, K] */, uint32_t *status_dev, void *workspace_dev,
+                                 size_t workspace_bytes, void *stream);
+
 /* ---- Leave-one-out predictive checks of an ensemble (Rasmussen & Williams 5.4.2), either branch -------------------
  * For star s, with C_s the covariance the likelihood and the sweeps above factor (marginal branch: conditional == 0,
  * the kernel tables of the handle's last sp_kernel_table; conditional branch: the star's own inclination, rta1_dev and

@@ -100,6 +100,12 @@ PROTOTYPES = {
     "sp_fisher_conditional_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I]),
     "sp_fisher_conditional": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                                    ctypes.c_size_t, _V]),
+    "sp_fisher_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I, _I]),
+    "sp_fisher_marginal_linear": (_I, [_V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V,
+                                       _V, _V, ctypes.c_size_t, _V]),
+    "sp_fisher_conditional_linear_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
+    "sp_fisher_conditional_linear": (_I, [_V, _I, _I, _I, _I, _I, _V, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _D, _V, _V,
+                                          _V, _V, ctypes.c_size_t, _V]),
     "sp_loo_workspace_bytes": (ctypes.c_size_t, [_V, _I, _I, _I, _I]),
     "sp_loo_ensemble": (_I, [_V, _I, _I, _V, _V, _V, _V, _I, _I, _V, _V, _V, _I, _I, _I, _D, _V, _V, _V, _V,
                              ctypes.c_size_t, _V]),

@@ -23,6 +23,7 @@
 // neighbour's addition.
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_linq.h"   // (the bound on q alone: its functions are not for a source without contraction)
 #include "sp_sweep.h"
 
 namespace {
@@ -304,11 +305,17 @@ __global__ __launch_bounds__(256) void fisher_trace_kernel(int Kr, int P, const 
 // the four wavefronts), the mean term, the failure semantics and the status word.  One workgroup per star.
 //   ragged (0 < nobs < K): NaN, SP_STAR_NAN;  z > zmax: zeros, SP_STAR_ZMAX;  else not positive definite: NaN,
 //   SP_STAR_NOT_PD (the bit is set whenever the factorisation failed)
+// LIN: regressors marginalised out (sp_fisher_linear.hip).  corr [S][npairs][2] holds <E_i, X_j> and tr(N_i N_j), down [S]
+// |Z^T 1|^2, lflag [S] the q x q stage's failure: F~[i][j] = (1/2 tr - <E_i, X_j>) + 1/2 tr(N_i N_j) + (d_i m)(d_j m)
+// (1^T C^-1 1 - |Z^T 1|^2); a flagged star that is neither rejected nor unfactored holds NaN, SP_STAR_NAN.  Without LIN
+// the three pointers are not read and the kernel is the one it was.
+template <bool LIN>
 __global__ __launch_bounds__(256) void fisher_finish_kernel(
     int K, int Kr, int P, int ntab, const sp_star *__restrict__ stars, const SpCoef *__restrict__ coef,
     const int32_t *__restrict__ info, const double *__restrict__ part, const double *__restrict__ ones,
     const double *__restrict__ dmean, int per_star, int normalized, double zmax, double *__restrict__ fisher,
-    uint32_t *__restrict__ status) {
+    uint32_t *__restrict__ status, const double *__restrict__ corr, const double *__restrict__ down,
+    const int32_t *__restrict__ lflag) {
   __shared__ double red[4];
   __shared__ double tr[SP_FISHER_PMAX * (SP_FISHER_PMAX + 1) / 2];
   __shared__ int nonfinite;
@@ -327,10 +334,19 @@ __global__ __launch_bounds__(256) void fisher_finish_kernel(
   double o11 = 0.0;
   if (!normalized)
     for (int k = 0; k < ntr; ++k) o11 += ones[(size_t)s * ntr + k];
+  bool lnan = false;
+  if (LIN) {
+    if (!normalized) o11 = o11 - down[s];
+    lnan = lflag[s] != 0 && !rej && !notpd;
+  }
   double val = 0.0;
   if (tid < P * P) {
     const int i = tid / P, j = tid % P, lo = i < j ? i : j, hi = i < j ? j : i;
     val = 0.5 * tr[pair_index(lo, hi, P)];
+    if (LIN) {
+      const double *cr = corr + ((size_t)s * npairs + pair_index(lo, hi, P)) * 2;
+      val = (val - cr[0]) + 0.5 * cr[1];
+    }
     if (!normalized) {
       // (the product of the two mean tangents in the order of the pair, so that F[i][j] and F[j][i] are the same bits)
       const int col = per_star ? s : st.table;
@@ -341,18 +357,21 @@ __global__ __launch_bounds__(256) void fisher_finish_kernel(
     if (ragged) val = __builtin_nan("");
     else if (rej) val = 0.0;
     else if (notpd) val = __builtin_nan("");
+    else if (lnan) val = __builtin_nan("");
     if (!(ragged || notpd) && !(fabs(val) <= 1.79769313486231570e308)) atomicOr(&nonfinite, 1);
     fisher[((size_t)s * P + i) * P + j] = val;
   }
   __syncthreads();
   if (tid == 0 && status)
-    status[s] = (notpd ? SP_STAR_NOT_PD : 0u) | (rej ? SP_STAR_ZMAX : 0u) | ((ragged || nonfinite) ? SP_STAR_NAN : 0u);
+    status[s] = (notpd ? SP_STAR_NOT_PD : 0u) | (rej ? SP_STAR_ZMAX : 0u) |
+                ((ragged || nonfinite || lnan) ? SP_STAR_NAN : 0u);
 }
 
 struct FisherLayout {
   size_t inv, cinv, dC, G, drow, dsc, part, ones, total;
+  SpFisherLinCarve lin;               // with regressors (q > 0): the low-rank stage's scratch behind the sweep's own
 };
-FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts) {
+FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts, int q = 0) {
   const int Kr = sp_roundup(K, SP_NB);
   const size_t d = sizeof(double), ntr = Kr / SP_NB, kr2 = (size_t)Kr * Kr;
   FisherLayout F;
@@ -365,19 +384,21 @@ FisherLayout fisher_layout(sp_handle *h, int S, int K, int P, int covpts) {
   F.dsc = c.take(d * (size_t)S * P * SP_FS_N);
   F.part = c.take(d * (size_t)S * (P * (P + 1) / 2) * ntr * ntr);
   F.ones = c.take(d * (size_t)S * ntr);
+  F.lin = SpFisherLinCarve{};
+  if (q) F.lin = sp_fisher_lin_carve(c, S, K, P, q);
   F.total = c.off;
   return F;
 }
 
-// one group of stars (Q: their problem; the slices of the per-star outputs already taken)
+// one group of stars (Q: their problem; the slices of the per-star outputs and of the regressors already taken)
 int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double *dyp, const double *dmean, double *fisher,
-                 double *dcov, uint32_t *status, void *workspace) {
+                 double *dcov, uint32_t *status, void *workspace, const SpFisherLin &lin) {
   const int S = Q.S, K = Q.K, covpts = Q.covpts, temporal = Q.temporal, normalized = Q.normalized, order = Q.order;
   const double *t = Q.t, *tab = Q.tab;
   const sp_star *stars = Q.stars;
   hipStream_t st = Q.st;
   const int Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB, np = covpts + 4;
-  const FisherLayout F = fisher_layout(h, S, K, P, covpts);
+  const FisherLayout F = fisher_layout(h, S, K, P, covpts, lin.q);
   char *base = static_cast<char *>(workspace);
   const SpViews V = sp_sweep_views(h, S, K, base + F.inv);
   double *theta = V.theta(), *qv = V.qv(), *coef = V.coef();
@@ -401,7 +422,11 @@ int fisher_group(sp_handle *h, const SpProblem &Q, int P, int ntab, const double
                        covpts, tab, dyp, temporal, normalized, qv, (const SpCoef *)coef, drow, dsc, dC, dcov);
     SP_LAUNCH_CHECK();
   }
-  return sp_launch_fisher_close(Q, V, P, ntab, 0, Cinv, dC, G, part, ones, dmean, fisher, status);
+  if (!lin.q) return sp_launch_fisher_close(Q, V, P, ntab, 0, Cinv, dC, G, part, ones, dmean, fisher, status);
+  // the regressors: the low-rank corrections of every pair, |Z^T 1|^2 and the q x q stage's flag (sp_fisher_linear.hip)
+  if ((rc = sp_launch_fisher_linear(Q, P, lin.q, lin.basis, lin.bvar, Cinv, dC, base, F.lin))) return rc;
+  const SpFisherLinOut out{at<double>(base, F.lin.corr), at<double>(base, F.lin.down), at<int32_t>(base, F.lin.flag)};
+  return sp_launch_fisher_close(Q, V, P, ntab, 0, Cinv, dC, G, part, ones, dmean, fisher, status, &out);
 }
 
 }  // namespace
@@ -426,7 +451,7 @@ int sp_launch_fisher_coef(int S, int K, int P, int ntab, int per_star, const sp_
 
 int sp_launch_fisher_close(const SpProblem &Q, const SpViews &V, int P, int ntab, int per_star, const double *Cinv,
                            const double *dC, double *G, double *part, double *ones, const double *dmean, double *fisher,
-                           uint32_t *status) {
+                           uint32_t *status, const SpFisherLinOut *lin) {
   const int S = Q.S, K = Q.K, normalized = Q.normalized, Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB;
   const size_t kr2 = (size_t)Kr * Kr;
   hipStream_t st = Q.st;
@@ -442,8 +467,14 @@ int sp_launch_fisher_close(const SpProblem &Q, const SpViews &V, int P, int ntab
     hipLaunchKernelGGL(fisher_ones_kernel, dim3(ntr, S), dim3(256), 0, st, K, Kr, Cinv, ones);
     SP_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(fisher_finish_kernel, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, Q.stars, (const SpCoef *)V.coef(),
-                     V.info(), part, ones, dmean, per_star, normalized, Q.zmax, fisher, status);
+  if (lin)
+    hipLaunchKernelGGL(fisher_finish_kernel<true>, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, Q.stars,
+                       (const SpCoef *)V.coef(), V.info(), part, ones, dmean, per_star, normalized, Q.zmax, fisher, status,
+                       lin->corr, lin->down, lin->flag);
+  else
+    hipLaunchKernelGGL(fisher_finish_kernel<false>, dim3(S), dim3(256), 0, st, K, Kr, P, ntab, Q.stars,
+                       (const SpCoef *)V.coef(), V.info(), part, ones, dmean, per_star, normalized, Q.zmax, fisher, status,
+                       (const double *)nullptr, (const double *)nullptr, (const int32_t *)nullptr);
   SP_LAUNCH_CHECK();
   return SP_OK;
 }
@@ -455,11 +486,16 @@ size_t sp_fisher_workspace_bytes(sp_handle *h, int S, int K, int P, int covpts) 
   return fisher_layout(h, S, K, P, covpts).total;
 }
 
-int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, const double *diag_dev,
-                       const sp_star *stars_dev, int covpts, const double *tab_dev, const double *meanvar_dev,
-                       const double *dyp_dev, const double *dmean_dev, int temporal, int normalized, int norm_order,
-                       double zmax, double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
-                       size_t workspace_bytes, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// the marginal sweep, without regressors (lin.q == 0: sp_fisher_marginal) or with them (sp_fisher_marginal_linear)
+int fisher_marginal_sweep(sp_handle *h, int S, int K, int P, const SpFisherLin &lin, const double *t_dev,
+                          const double *diag_dev, const sp_star *stars_dev, int covpts, const double *tab_dev,
+                          const double *meanvar_dev, const double *dyp_dev, const double *dmean_dev, int temporal,
+                          int normalized, int norm_order, double zmax, double *fisher_dev, double *dcov_dev,
+                          uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !stars_dev || !dyp_dev || !dmean_dev || !fisher_dev || !workspace_dev || S < 0 || K < 2 || P < 1 ||
       P > FP_MAX || covpts < 1 || norm_order < 0 || norm_order > SP_NORM_MAXORDER || !sp_temporal_valid(temporal))
@@ -471,7 +507,8 @@ int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, c
   if (h->tab_ntab < 1) return SP_ERR_STATE;
   const int ntab = h->tab_ntab;
   if (S == 0) return SP_OK;
-  const int group = sp_star_group(S, workspace_bytes, [&](int n) { return fisher_layout(h, n, K, P, covpts).total; });
+  const int group =
+      sp_star_group(S, workspace_bytes, [&](int n) { return fisher_layout(h, n, K, P, covpts, lin.q).total; });
   if (!group) return SP_ERR_INVALID;
   // (no data: M = 0, flux null)
   const SpProblem Q = sp_make_problem(h, 0, S, K, 0, t_dev, nullptr, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev,
@@ -479,8 +516,40 @@ int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, c
   return sp_for_star_groups(S, group, [&](int s0, int n) {
     return fisher_group(h, Q.slice(s0, s0 + n), P, ntab, dyp_dev, dmean_dev, fisher_dev + (size_t)s0 * P * P,
                         dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr, status_dev ? status_dev + s0 : nullptr,
-                        workspace_dev);
+                        workspace_dev, lin.slice(s0, K));
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sp_fisher_marginal(sp_handle *h, int S, int K, int P, const double *t_dev, const double *diag_dev,
+                       const sp_star *stars_dev, int covpts, const double *tab_dev, const double *meanvar_dev,
+                       const double *dyp_dev, const double *dmean_dev, int temporal, int normalized, int norm_order,
+                       double zmax, double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
+                       size_t workspace_bytes, void *stream) {
+  return fisher_marginal_sweep(h, S, K, P, SpFisherLin{}, t_dev, diag_dev, stars_dev, covpts, tab_dev, meanvar_dev, dyp_dev,
+                               dmean_dev, temporal, normalized, norm_order, zmax, fisher_dev, dcov_dev, status_dev,
+                               workspace_dev, workspace_bytes, stream);
+}
+
+size_t sp_fisher_linear_workspace_bytes(sp_handle *h, int S, int K, int P, int q, int covpts) {
+  if (!h || S < 1 || K < 2 || P < 1 || P > FP_MAX || q < 1 || q > SP_LIN_QMAX || covpts < 1) return 0;
+  return fisher_layout(h, S, K, P, covpts, q).total;
+}
+
+int sp_fisher_marginal_linear(sp_handle *h, int S, int K, int P, int q, const double *t_dev, const double *diag_dev,
+                              const sp_star *stars_dev, const double *basis_dev, const double *basis_var_dev, int covpts,
+                              const double *tab_dev, const double *meanvar_dev, const double *dyp_dev,
+                              const double *dmean_dev, int temporal, int normalized, int norm_order, double zmax,
+                              double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
+                              size_t workspace_bytes, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!basis_dev || !basis_var_dev || q < 1 || q > SP_LIN_QMAX) return SP_ERR_INVALID;
+  return fisher_marginal_sweep(h, S, K, P, SpFisherLin{q, basis_dev, basis_var_dev}, t_dev, diag_dev, stars_dev, covpts,
+                               tab_dev, meanvar_dev, dyp_dev, dmean_dev, temporal, normalized, norm_order, zmax, fisher_dev,
+                               dcov_dev, status_dev, workspace_dev, workspace_bytes, stream);
 }
 
 }  // extern "C"

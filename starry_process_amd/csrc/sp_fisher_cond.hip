@@ -26,6 +26,7 @@
 // the same products only if no product is fused into a neighbour's addition.
 #include "sp_internal.h"
 #include "sp_cov.h"
+#include "sp_linq.h"   // (the bound on q alone: its functions are not for a source without contraction)
 #include "sp_sweep.h"
 
 namespace {
@@ -197,8 +198,9 @@ __global__ __launch_bounds__(256) void fisher_cond_tangent_kernel(
 
 struct FisherCondLayout {
   size_t inv, cinv, raw, A, B1, W, dR, dv, dC, G, rpart, drow, dsc, dmean, part, ones, fpart, total;
+  SpFisherLinCarve lin;               // with regressors (q > 0): the low-rank stage's scratch behind the sweep's own
 };
-FisherCondLayout fisher_cond_layout(sp_handle *h, int S, int K, int P) {
+FisherCondLayout fisher_cond_layout(sp_handle *h, int S, int K, int P, int q = 0) {
   const int Kr = sp_roundup(K, SP_NB), N = h->N;
   const size_t d = sizeof(double), ntr = Kr / SP_NB, kr2 = (size_t)Kr * Kr, mat = d * (size_t)S * Kr * N;
   FisherCondLayout F;
@@ -219,18 +221,21 @@ FisherCondLayout fisher_cond_layout(sp_handle *h, int S, int K, int P) {
   F.part = c.take(d * (size_t)S * (P * (P + 1) / 2) * ntr * ntr);
   F.ones = c.take(d * (size_t)S * ntr);
   F.fpart = c.take(d * (size_t)S * ntr * K);         // the forward's partial row sums
+  F.lin = SpFisherLinCarve{};
+  if (q) F.lin = sp_fisher_lin_carve(c, S, K, P, q);
   F.total = c.off;
   return F;
 }
 
-// one group of stars (Q: their problem; the slices of the per-star outputs already taken)
+// one group of stars (Q: their problem; the slices of the per-star outputs and of the regressors already taken)
 int fisher_cond_group(sp_handle *h, const SpProblem &Q, int Ph, int star_mask, const double *rta1, const double *dmu,
-                      const double *dsig, double *fisher, double *dcov, uint32_t *status, void *workspace) {
+                      const double *dsig, double *fisher, double *dcov, uint32_t *status, void *workspace,
+                      const SpFisherLin &lin) {
   const int S = Q.S, K = Q.K, N = h->N, normalized = Q.normalized;
   const int P = Ph + (star_mask & 1) + ((star_mask >> 1) & 1);
   hipStream_t st = Q.st;
   const int Kr = sp_roundup(K, SP_NB), ntr = Kr / SP_NB, ntri = ntr * (ntr + 1) / 2;
-  const FisherCondLayout F = fisher_cond_layout(h, S, K, P);
+  const FisherCondLayout F = fisher_cond_layout(h, S, K, P, lin.q);
   char *base = static_cast<char *>(workspace);
   const SpViews V = sp_sweep_views(h, S, K, base + F.inv);
   double *Cinv = at<double>(base, F.cinv), *raw = at<double>(base, F.raw), *A = at<double>(base, F.A);
@@ -277,7 +282,11 @@ int fisher_cond_group(sp_handle *h, const SpProblem &Q, int Ph, int star_mask, c
     SP_LAUNCH_CHECK();
   }
   // 5. G_i = C^-1 d_i C, the traces, F_s
-  return sp_launch_fisher_close(Q, V, P, S, 1, Cinv, dC, G, part, ones, dmean, fisher, status);
+  if (!lin.q) return sp_launch_fisher_close(Q, V, P, S, 1, Cinv, dC, G, part, ones, dmean, fisher, status);
+  // the regressors: the low-rank corrections of every pair, |Z^T 1|^2 and the q x q stage's flag (sp_fisher_linear.hip)
+  if ((rc = sp_launch_fisher_linear(Q, P, lin.q, lin.basis, lin.bvar, Cinv, dC, base, F.lin))) return rc;
+  const SpFisherLinOut out{at<double>(base, F.lin.corr), at<double>(base, F.lin.down), at<int32_t>(base, F.lin.flag)};
+  return sp_launch_fisher_close(Q, V, P, S, 1, Cinv, dC, G, part, ones, dmean, fisher, status, &out);
 }
 
 }  // namespace
@@ -289,10 +298,15 @@ size_t sp_fisher_conditional_workspace_bytes(sp_handle *h, int S, int K, int P) 
   return fisher_cond_layout(h, S, K, P).total;
 }
 
-int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask, const double *t_dev, const double *diag_dev,
-                          const sp_star *stars_dev, const double *rta1_dev, const double *dmu_dev, const double *dsig_dev,
-                          int temporal, int normalized, int norm_order, double zmax, double *fisher_dev, double *dcov_dev,
-                          uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+}  // extern "C"
+
+namespace {
+
+// the conditional sweep, without regressors (lin.q == 0: sp_fisher_conditional) or with them
+int fisher_cond_sweep(sp_handle *h, int S, int K, int Ph, int star_mask, const SpFisherLin &lin, const double *t_dev,
+                      const double *diag_dev, const sp_star *stars_dev, const double *rta1_dev, const double *dmu_dev,
+                      const double *dsig_dev, int temporal, int normalized, int norm_order, double zmax, double *fisher_dev,
+                      double *dcov_dev, uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
   if (h && h->device < 0) return SP_ERR_NO_DEVICE;
   if (!h || !t_dev || !stars_dev || !fisher_dev || !workspace_dev || S < 0 || K < 2 || Ph < 0 || Ph > 5 ||
       (star_mask & ~3) || (Ph > 0 && (!dmu_dev || !dsig_dev)) || norm_order < 0 || norm_order > SP_NORM_MAXORDER ||
@@ -302,7 +316,7 @@ int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask, con
   if (P < 1 || P > SP_FISHER_PMAX) return SP_ERR_INVALID;
   if (const int rc = sp_branch_check(h, 1, rta1_dev, nullptr, nullptr, 0)) return rc;
   if (S == 0) return SP_OK;
-  const int group = sp_star_group(S, workspace_bytes, [&](int n) { return fisher_cond_layout(h, n, K, P).total; });
+  const int group = sp_star_group(S, workspace_bytes, [&](int n) { return fisher_cond_layout(h, n, K, P, lin.q).total; });
   if (!group) return SP_ERR_INVALID;
   // (no data: M = 0, flux null)
   const SpProblem Q = sp_make_problem(h, 1, S, K, 0, t_dev, nullptr, diag_dev, stars_dev, 0, nullptr, nullptr, temporal,
@@ -310,8 +324,39 @@ int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask, con
   return sp_for_star_groups(S, group, [&](int s0, int n) {
     return fisher_cond_group(h, Q.slice(s0, s0 + n), Ph, star_mask, rta1_dev, dmu_dev, dsig_dev,
                              fisher_dev + (size_t)s0 * P * P, dcov_dev ? dcov_dev + (size_t)s0 * P * K * K : nullptr,
-                             status_dev ? status_dev + s0 : nullptr, workspace_dev);
+                             status_dev ? status_dev + s0 : nullptr, workspace_dev, lin.slice(s0, K));
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int sp_fisher_conditional(sp_handle *h, int S, int K, int Ph, int star_mask, const double *t_dev, const double *diag_dev,
+                          const sp_star *stars_dev, const double *rta1_dev, const double *dmu_dev, const double *dsig_dev,
+                          int temporal, int normalized, int norm_order, double zmax, double *fisher_dev, double *dcov_dev,
+                          uint32_t *status_dev, void *workspace_dev, size_t workspace_bytes, void *stream) {
+  return fisher_cond_sweep(h, S, K, Ph, star_mask, SpFisherLin{}, t_dev, diag_dev, stars_dev, rta1_dev, dmu_dev, dsig_dev,
+                           temporal, normalized, norm_order, zmax, fisher_dev, dcov_dev, status_dev, workspace_dev,
+                           workspace_bytes, stream);
+}
+
+size_t sp_fisher_conditional_linear_workspace_bytes(sp_handle *h, int S, int K, int P, int q) {
+  if (!h || S < 1 || K < 2 || P < 1 || P > SP_FISHER_PMAX || q < 1 || q > SP_LIN_QMAX) return 0;
+  return fisher_cond_layout(h, S, K, P, q).total;
+}
+
+int sp_fisher_conditional_linear(sp_handle *h, int S, int K, int Ph, int star_mask, int q, const double *t_dev,
+                                 const double *diag_dev, const sp_star *stars_dev, const double *basis_dev,
+                                 const double *basis_var_dev, const double *rta1_dev, const double *dmu_dev,
+                                 const double *dsig_dev, int temporal, int normalized, int norm_order, double zmax,
+                                 double *fisher_dev, double *dcov_dev, uint32_t *status_dev, void *workspace_dev,
+                                 size_t workspace_bytes, void *stream) {
+  if (h && h->device < 0) return SP_ERR_NO_DEVICE;
+  if (!basis_dev || !basis_var_dev || q < 1 || q > SP_LIN_QMAX) return SP_ERR_INVALID;
+  return fisher_cond_sweep(h, S, K, Ph, star_mask, SpFisherLin{q, basis_dev, basis_var_dev}, t_dev, diag_dev, stars_dev,
+                           rta1_dev, dmu_dev, dsig_dev, temporal, normalized, norm_order, zmax, fisher_dev, dcov_dev,
+                           status_dev, workspace_dev, workspace_bytes, stream);
 }
 
 }  // extern "C"

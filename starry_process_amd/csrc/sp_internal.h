@@ -749,9 +749,33 @@ int sp_launch_fisher_coef(int S, int K, int P, int ntab, int per_star, const sp_
                           const double *qv, const double *dmean, int order, double *drow, double *dsc, hipStream_t st);
 // G_i = C^-1 d_i C (dC, G [S][P][Kr][Kr]), the pair traces (part [S][P (P + 1) / 2][(Kr / 64)^2]), 1^T C^-1 1 (ones
 // [S][Kr / 64]; unnormalised), then F_s with the mean term, the failure semantics and the status word, on V's coef and info
+// With regressors marginalised out (lin: what sp_launch_fisher_linear left; null without): F~_s[i, j] = 1/2 tr - corr[0] +
+// 1/2 corr[1] + (d_i m)(d_j m) (1^T C^-1 1 - down), NaN and SP_STAR_NAN for a star whose flag is set
+struct SpFisherLinOut {
+  const double *corr, *down;          // [S][P (P + 1) / 2][2], [S]
+  const int32_t *flag;                // [S]
+};
 int sp_launch_fisher_close(const SpProblem &Q, const SpViews &V, int P, int ntab, int per_star, const double *Cinv,
                            const double *dC, double *G, double *part, double *ones, const double *dmean, double *fisher,
-                           uint32_t *status);
+                           uint32_t *status, const SpFisherLinOut *lin = nullptr);
+// sp_fisher_linear.hip: the low-rank stage of the Fisher sweeps with q regressors per star marginalised out (DESIGN.md
+// 28), behind the mirrored inverse Cinv [S][Kr][Kr] and the tangents dC [S][P][Kr][Kr] (zero from K on), in front of
+// sp_launch_fisher_close.  basis [S][q][K], bvar [S][q].  Its scratch per group of stars, carved behind the sweep's own:
+// V = C^-1 U, Z^T, E_i = d_i C Z and X_i = C^-1 E_i as panels [32][Kr], the Gram entries, M, N_i and what the close reads.
+struct SpFisherLinCarve {
+  size_t V, c1, Z, E, X, gram, mix, N, corr, down, flag;
+};
+SpFisherLinCarve sp_fisher_lin_carve(SpCarve &c, int S, int K, int P, int q);
+int sp_launch_fisher_linear(const SpProblem &Q, int P, int q, const double *basis, const double *bvar, const double *Cinv,
+                            const double *dC, void *base, const SpFisherLinCarve &L);
+// the regressors of a Fisher sweep (q = 0, null pointers: none) and the slice of a group of stars
+struct SpFisherLin {
+  int q = 0;
+  const double *basis = nullptr, *bvar = nullptr;
+  SpFisherLin slice(int s0, int K) const {
+    return q ? SpFisherLin{q, basis + (size_t)s0 * q * K, bvar + (size_t)s0 * q} : SpFisherLin{};
+  }
+};
 
 // grid of a grid-stride kernel: blocks of 256 threads covering `total` elements, at most `max_blocks` of them
 static inline unsigned grid_for(size_t total, size_t max_blocks = 8192) {

@@ -1475,22 +1475,42 @@ class Engine(object):
         """Device scratch that holds ``S`` stars of ``fisher_marginal`` at once (sp_fisher_workspace_bytes)."""
         return self._scratch(self._L.sp_fisher_workspace_bytes(self._h, int(S), int(K), int(P), int(covpts)))
 
+    def fisher_linear_workspace(self, S, K, P, q, covpts):
+        """Device scratch that holds ``S`` stars of ``fisher_marginal(basis=...)`` at once
+        (sp_fisher_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_fisher_linear_workspace_bytes(self._h, int(S), int(K), int(P), int(q),
+                                                                      int(covpts)))
+
     def fisher_marginal(self, t, stars_dev, tab, meanvar, dyp, dmean, diag=None, covpts=300, temporal=None,
-                        normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False):
+                        normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False, basis=None,
+                        basis_var=None):
         """Device half of the ensemble's Fisher information (sp_fisher_marginal): t [S, K], the kernel tables of the
         engine's last ``kernel_table`` (tab [ntab, 5, covpts + 4], meanvar [ntab, 2]) and the tangents of their first
         rows and of the flux means with respect to P parameters (dyp [P, ntab, covpts + 4], dmean [P, ntab]) ->
         (fisher [S, P, P], status [S]) and, with ``return_tangents``, dcov [S, P, K, K]: the tangents of the stars'
         covariances.  workspace: a byte tensor (``fisher_workspace``); one that holds fewer than S stars makes the call
-        work through the stars in groups, with the same bits."""
+        work through the stars in groups, with the same bits.  basis [S, q, K], basis_var [S, q]: q linear regressors
+        per star marginalised out (sp_fisher_marginal_linear; the workspace is then ``fisher_linear_workspace``'s)."""
         torch = _torch()
         S, K = t.shape
         P = int(dyp.shape[0])
         assert tuple(dyp.shape) == (P, tab.shape[0], covpts + 4) and tuple(dmean.shape) == (P, tab.shape[0])
+        if basis is None and basis_var is not None:
+            raise ValueError("`basis_var` needs a `basis`")
+        if basis is not None:
+            basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
         fisher = self.empty(S, P, P)
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         dcov = self.empty(S, P, K, K) if return_tangents else None
-        if S > 0:
+        if S > 0 and basis is not None:
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_fisher_linear_workspace_bytes(self._h, n, K, P, q, int(covpts)), S, workspace)
+            check(self._L.sp_fisher_marginal_linear(
+                self._h, S, K, P, q, self._p(t), self._p(diag), self._p(stars_dev), self._p(basis), self._p(basis_var),
+                int(covpts), self._p(tab), self._p(meanvar), self._p(dyp.contiguous()), self._p(dmean.contiguous()),
+                TEMPORAL[temporal], int(bool(normalized)), int(norm_order), float(zmax), self._p(fisher), self._p(dcov),
+                self._p(status), self._p(workspace), int(workspace.numel()), self._stream()))
+        elif S > 0:
             workspace = self._group_scratch(
                 lambda n: self._L.sp_fisher_workspace_bytes(self._h, n, K, P, int(covpts)), S, workspace)
             check(self._L.sp_fisher_marginal(
@@ -1504,18 +1524,31 @@ class Engine(object):
         """Device scratch that holds ``S`` stars of ``fisher_conditional`` at once (sp_fisher_conditional_workspace_bytes)."""
         return self._scratch(self._L.sp_fisher_conditional_workspace_bytes(self._h, int(S), int(K), int(P)))
 
+    def fisher_conditional_linear_workspace(self, S, K, P, q):
+        """Device scratch that holds ``S`` stars of ``fisher_conditional(basis=...)`` at once
+        (sp_fisher_conditional_linear_workspace_bytes)."""
+        return self._scratch(self._L.sp_fisher_conditional_linear_workspace_bytes(self._h, int(S), int(K), int(P),
+                                                                                  int(q)))
+
     def fisher_conditional(self, t, stars_dev, rta1, dmu, dsig, star_params=("i", "p"), diag=None, temporal=None,
-                           normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False):
+                           normalized=True, norm_order=20, zmax=0.023, workspace=None, return_tangents=False, basis=None,
+                           basis_var=None):
         """Device half of the conditional branch's Fisher information (sp_fisher_conditional), at the engine's current
         moments: t [S, K], stars_dev (each star's inclination in sp_star.inc, radians), rta1 [ntab, N] and the moments'
         tangents with respect to Ph shared hyperparameters (dmu [Ph, N], dsig [Ph, N, N]; None for Ph = 0) ->
         (fisher [S, P, P], status [S]) and, with ``return_tangents``, dcov [S, P, K, K].  The rows of a star's block: the
         Ph hyperparameters, then its inclination (per RADIAN) when "i" is in ``star_params``, then its period when "p"
         is.  workspace: a byte tensor (``fisher_conditional_workspace``); one that holds fewer than S stars makes the
-        call work through the stars in groups, with the same bits."""
+        call work through the stars in groups, with the same bits.  basis [S, q, K], basis_var [S, q]: q linear
+        regressors per star marginalised out (sp_fisher_conditional_linear; the workspace is then
+        ``fisher_conditional_linear_workspace``'s)."""
         torch = _torch()
         S, K = t.shape
         N = self.N
+        if basis is None and basis_var is not None:
+            raise ValueError("`basis_var` needs a `basis`")
+        if basis is not None:
+            basis, basis_var, q = self._regressor_inputs(basis, basis_var, S, K)
         Ph = 0 if dmu is None else int(dmu.shape[0])
         mask = (1 if "i" in star_params else 0) | (2 if "p" in star_params else 0)
         P = Ph + (mask & 1) + (mask >> 1)
@@ -1527,7 +1560,15 @@ class Engine(object):
         fisher = self.empty(S, P, P)
         status = torch.zeros(S, dtype=torch.int32, device=self.device)
         dcov = self.empty(S, P, K, K) if return_tangents else None
-        if S > 0:
+        if S > 0 and basis is not None:
+            workspace = self._group_scratch(
+                lambda n: self._L.sp_fisher_conditional_linear_workspace_bytes(self._h, n, K, P, q), S, workspace)
+            check(self._L.sp_fisher_conditional_linear(
+                self._h, S, K, Ph, mask, q, self._p(t), self._p(diag), self._p(stars_dev), self._p(basis),
+                self._p(basis_var), self._p(rta1), self._p(dmu), self._p(dsig), TEMPORAL[temporal],
+                int(bool(normalized)), int(norm_order), float(zmax), self._p(fisher), self._p(dcov), self._p(status),
+                self._p(workspace), int(workspace.numel()), self._stream()))
+        elif S > 0:
             workspace = self._group_scratch(
                 lambda n: self._L.sp_fisher_conditional_workspace_bytes(self._h, n, K, P), S, workspace)
             check(self._L.sp_fisher_conditional(

@@ -546,7 +546,22 @@ class _MarginalSweep(_EnsembleSweep):
         return dy, dm, events
 
 
-class EnsembleGradient(_MarginalSweep):
+class _RegressorVariances(object):
+    """``upload_basis_var`` of the four sweeps that take ``basis=``: they keep the basis in ``_basis`` (None without
+    one), its variances in ``_basis_var`` and the number of regressors in ``_q``."""
+
+    def upload_basis_var(self, basis_var):
+        """New prior variances of the regressors' weights -- scalar, (q,) or (S, q), finite and >= 0 -- for the calls
+        that follow; the basis stays on the device."""
+        from .linear import check_regressor_variances
+
+        if self._basis is None:
+            raise ValueError("`basis_var` needs regressors (%s(..., basis=..., basis_var=...))" % type(self).__name__)
+        lam = check_regressor_variances(basis_var, self.S, self._q)
+        self._basis_var = self._e.f64(lam)
+
+
+class EnsembleGradient(_MarginalSweep, _RegressorVariances):
     """Log-likelihood of an ENSEMBLE of light curves and its gradient with respect to the spot hyperparameters
     (r, a, b, c, n[, dr]) in ONE device sweep per evaluation -- what ``theano.grad`` of the summed
     ``sp.log_likelihood`` is in the reference (tests/test_lnlike.py:100-136, calibrate/log_prob.py:53-91), for every
@@ -612,16 +627,6 @@ class EnsembleGradient(_MarginalSweep):
         self.lnlike = None
 
     _WRT = _WRT
-
-    def upload_basis_var(self, basis_var):
-        """New prior variances of the regressors' weights -- scalar, (q,) or (S, q), finite and >= 0 -- for the calls
-        that follow; the basis stays on the device."""
-        from .linear import check_regressor_variances
-
-        if self._basis is None:
-            raise ValueError("`basis_var` needs regressors (EnsembleGradient(..., basis=..., basis_var=...))")
-        lam = check_regressor_variances(basis_var, self.S, self._q)
-        self._basis_var = self._e.f64(lam)
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], dr=None,
                  wrt=None):
@@ -729,6 +734,32 @@ def _check_params(params, has_dr):
     return params
 
 
+def _fisher_regressors(basis, basis_var, S, K):
+    """The ``basis=``, ``basis_var=`` pair of the Fisher classes, checked on the host (``linear.check_regressors``):
+    (Ut [S, q, K], lam [S, q], q), or (None, None, 0) without a basis.  ValueError for one of the pair without the
+    other, a shape that does not fit, more than MAX_REGRESSORS columns, a non-finite basis, a negative or non-finite
+    variance.  No device work."""
+    from .linear import _regressor_args
+
+    U, Ut, lam = _regressor_args(basis, basis_var, S, K, "a `basis` needs the prior variances of its weights, `basis_var`")
+    return (None, None, 0) if U is None else (Ut, lam, U.shape[2])
+
+
+class _FisherRegressors(_RegressorVariances):
+    """What the two Fisher classes share for ``basis=``: the upload behind ``_setup`` and the engine call's keywords."""
+
+    def _regressor_kwargs(self):
+        """The engine call's ``basis=``, ``basis_var=``; nothing without regressors (the call is then the plain one)."""
+        return {"basis": self._basis, "basis_var": self._basis_var} if self._q else {}
+
+    def _upload_regressors(self, Ut, lam, q):
+        self._q = q
+        self._basis = self._basis_var = None
+        if q:
+            self._basis, self._basis_var = self._e.f64(Ut), self._e.f64(lam)
+            _torch().cuda.synchronize(self._e.device)
+
+
 def fisher_max_covpts(P):
     """The largest lag grid ``covpts`` the Fisher sweep serves for P parameters: its tangent kernel keeps P + 1 tables
     of covpts + 4 doubles beside 1152 doubles of tile vectors in 60 KB of LDS (sp_fisher_marginal refuses beyond) --
@@ -736,7 +767,7 @@ def fisher_max_covpts(P):
     return (60 * 1024 // 8 - 1152) // (int(P) + 1) - 4
 
 
-class EnsembleFisher(_MarginalSweep):
+class EnsembleFisher(_MarginalSweep, _FisherRegressors):
     """Expected (Fisher) information of an ENSEMBLE of light curves about the spot hyperparameters, in one device sweep
     and without any flux: how well S light curves with these cadences, periods and noise CAN constrain (r, a, b, c, n
     [, dr]) -- the design question behind the reference's calibration runs, which it answers with a sampler over a
@@ -754,18 +785,27 @@ class EnsembleFisher(_MarginalSweep):
     (exact in r, a, b, c, n; central differences of step h with a spread of radii or exact=False); the device forms the
     tangents of the covariances from them, C^-1 d_i C on the matrix cores and the pair traces (sp_fisher_marginal,
     DESIGN.md 17).  max_workspace_bytes: a bound on the device scratch; the stars are then worked through in groups,
-    with the same bits."""
+    with the same bits.
+
+    basis, basis_var: q <= 32 linear regressors per star marginalised out, as ``EnsembleGradient(basis=...)`` takes
+    them -- (K, q) or (S, K, q); scalar, (q,) or (S, q), finite and >= 0.  The star's covariance is then C + U diag(
+    basis_var) U^T: F is the information that is left about the hyperparameters when the regressors' weights (segment
+    offsets, trends, systematics) are nuisance parameters, and ``cramer_rao(F)`` the Laplace error bar at an optimum
+    ``EnsembleGradient(basis=...)`` served (sp_fisher_marginal_linear).  ``upload_basis_var`` changes the
+    variances without sending the basis again; a variance of zero switches its regressor off exactly."""
 
     def __init__(self, t, ferr=1.0e-3, p=1.0, u=None, ydeg=15, baseline_var=0.0, normalized=True, covpts=None,
                  tau=None, temporal_kernel="matern32", device=None, h=1.0e-4, upstream_kwargs=None, exact=True,
-                 max_workspace_bytes=None):
+                 max_workspace_bytes=None, basis=None, basis_var=None):
         t = np.asarray(t, dtype=np.float64)
         if t.ndim not in (1, 2):
             raise ValueError("t must be (K,) or (S, K)")
         S = t.shape[0] if t.ndim == 2 else (np.asarray(p).shape[0] if np.ndim(p) == 1 else 1)
+        regressors = _fisher_regressors(basis, basis_var, S, t.shape[-1])      # (before anything touches the device)
         stars, utab = self._setup(t, np.zeros((S, t.shape[-1])), ferr, p, None, u, ydeg, 0.0, baseline_var, tau,
                                   temporal_kernel, device)
         self._flux = None
+        self._upload_regressors(*regressors)
         self._configure(covpts, normalized, h, upstream_kwargs, exact)
         self._max_ws = None if max_workspace_bytes is None else int(max_workspace_bytes)
         self._ws = None
@@ -774,7 +814,10 @@ class EnsembleFisher(_MarginalSweep):
     def _workspace(self, P):
         """Scratch for P parameters: every star at once, or as many as ``max_workspace_bytes`` allows."""
         e = self._e
-        need = int(e._L.sp_fisher_workspace_bytes(e._h, self.S, self.K, P, self._covpts))
+        if self._q:
+            need = int(e._L.sp_fisher_linear_workspace_bytes(e._h, self.S, self.K, P, self._q, self._covpts))
+        else:
+            need = int(e._L.sp_fisher_workspace_bytes(e._h, self.S, self.K, P, self._covpts))
         nbytes = need if self._max_ws is None else min(need, self._max_ws)
         if self._ws is None or self._ws.numel() != nbytes:
             self._ws = e._scratch(nbytes)
@@ -804,7 +847,8 @@ class EnsembleFisher(_MarginalSweep):
             DY, DM = torch.stack([dy[k] for k in names]), torch.stack([dm[k] for k in names])
             out = e.fisher_marginal(self._t, self._stars, tab, mv, DY, DM, diag=self._diag, covpts=self._covpts,
                                     temporal=self._temporal, normalized=self._normalized,
-                                    workspace=self._workspace(len(names)), return_tangents=return_tangents)
+                                    workspace=self._workspace(len(names)), return_tangents=return_tangents,
+                                    **self._regressor_kwargs())
             per_star, status = out[0].cpu().numpy(), out[1].cpu().numpy().astype(np.uint32)
             self.tangents = out[2].cpu().numpy() if return_tangents else None
         self.per_star, self.status, self.names = per_star, status, names
@@ -906,7 +950,7 @@ def _check_wrt_conditional(wrt, has_basis=False):
     return wrt
 
 
-class EnsembleGradientConditional(_EnsembleSweep):
+class EnsembleGradientConditional(_EnsembleSweep, _RegressorVariances):
     """The CONDITIONAL branch (``marginalize_over_inclination=False``: star s at its own inclination i_s) of the ensemble
     log-likelihood and its gradient in ONE device sweep per evaluation -- what ``ensemble_gradient_conditional`` computes
     star by star through the autograd graph, for the whole batch at once (sp_lnlike_grad_conditional).
@@ -957,16 +1001,6 @@ class EnsembleGradientConditional(_EnsembleSweep):
         self.lnlike = self.status = None
 
     _open = staticmethod(get_engine)
-
-    def upload_basis_var(self, basis_var):
-        """New prior variances of the regressors' weights -- scalar, (q,) or (S, q), finite and >= 0 -- for the calls
-        that follow; the basis stays on the device."""
-        from .linear import check_regressor_variances
-
-        if self._basis is None:
-            raise ValueError("`basis_var` needs regressors (EnsembleGradientConditional(..., basis=..., basis_var=...))")
-        lam = check_regressor_variances(basis_var, self.S, self._q)
-        self._basis_var = self._e.f64(lam)
 
     def __call__(self, r=defaults["r"], a=defaults["a"], b=defaults["b"], c=defaults["c"], n=defaults["n"], wrt=None):
         """(sum of the stars' log-likelihoods, {"r": ., "a": ., "b": ., "c": ., "n": .}).
@@ -1088,7 +1122,7 @@ def _moment_tangents(e, ukw, names, r, a, b, c, n):
     return mu, Sig, torch.stack([tang[k][0] for k in names]), torch.stack([tang[k][1] for k in names])
 
 
-class EnsembleFisherConditional(_EnsembleSweep):
+class EnsembleFisherConditional(_EnsembleSweep, _FisherRegressors):
     """Expected (Fisher) information of an ENSEMBLE of light curves on the CONDITIONAL branch (star s at its own
     inclination i_s), in one device sweep and without any flux: how well these cadences, periods and noise CAN constrain
     the shared spot hyperparameters (r, a, b, c, n) AND every star's own inclination and period.  Per star, with C_s the
@@ -1108,19 +1142,27 @@ class EnsembleFisherConditional(_EnsembleSweep):
     r, a, b and closed forms for c and n; the device forms the design matrices' tangents with respect to i and p, the
     tangents of the covariances, C^-1 d_i C on the matrix cores and the pair traces (sp_fisher_conditional, DESIGN.md
     18).  Inclinations in degrees: the rows and columns of "i" are per degree.  max_workspace_bytes: a bound on the device
-    scratch; the stars are then worked through in groups, with the same bits."""
+    scratch; the stars are then worked through in groups, with the same bits.
+
+    basis, basis_var: q <= 32 linear regressors per star marginalised out, as ``EnsembleFisher(basis=...)`` takes them:
+    the information with the regressors' weights as nuisance parameters, the error bar at an optimum of
+    ``EnsembleGradientConditional(basis=...)`` (sp_fisher_conditional_linear); ``upload_basis_var`` changes
+    the variances without sending the basis again."""
 
     _open = staticmethod(get_engine)
 
     def __init__(self, t, ferr=1.0e-3, p=1.0, i=defaults["i"], u=None, ydeg=15, baseline_var=0.0, normalized=True,
-                 tau=None, temporal_kernel="matern32", device=None, upstream_kwargs=None, max_workspace_bytes=None):
+                 tau=None, temporal_kernel="matern32", device=None, upstream_kwargs=None, max_workspace_bytes=None,
+                 basis=None, basis_var=None):
         t = np.asarray(t, dtype=np.float64)
         if t.ndim not in (1, 2):
             raise ValueError("t must be (K,) or (S, K)")
         S = t.shape[0] if t.ndim == 2 else max([np.asarray(x).shape[0] for x in (p, i) if np.ndim(x) == 1] or [1])
+        regressors = _fisher_regressors(basis, basis_var, S, t.shape[-1])      # (before anything touches the device)
         # (the inclinations' bounds are not checked on this branch)
         self._setup(t, np.zeros((S, t.shape[-1])), ferr, p, i, u, ydeg, 0.0, baseline_var, tau, temporal_kernel, device)
         self._flux = None
+        self._upload_regressors(*regressors)
         self._normalized, self._ukw = bool(normalized), dict(upstream_kwargs or {})
         self._max_ws = None if max_workspace_bytes is None else int(max_workspace_bytes)
         self._ws = None
@@ -1129,7 +1171,10 @@ class EnsembleFisherConditional(_EnsembleSweep):
     def _workspace(self, P):
         """Scratch for P parameters: every star at once, or as many as ``max_workspace_bytes`` allows."""
         e = self._e
-        need = int(e._L.sp_fisher_conditional_workspace_bytes(e._h, self.S, self.K, P))
+        if self._q:
+            need = int(e._L.sp_fisher_conditional_linear_workspace_bytes(e._h, self.S, self.K, P, self._q))
+        else:
+            need = int(e._L.sp_fisher_conditional_workspace_bytes(e._h, self.S, self.K, P))
         nbytes = need if self._max_ws is None else min(need, self._max_ws)
         if self._ws is None or self._ws.numel() != nbytes:
             self._ws = e._scratch(nbytes)
@@ -1154,7 +1199,7 @@ class EnsembleFisherConditional(_EnsembleSweep):
         Ph, P = len(names), len(names) + len(star_names)
         out = e.fisher_conditional(self._t, self._stars, self._rta1, dmu, dSig, star_params=star_names, diag=self._diag,
                                    temporal=self._temporal, normalized=self._normalized, workspace=self._workspace(P),
-                                   return_tangents=return_tangents)
+                                   return_tangents=return_tangents, **self._regressor_kwargs())
         per_star, status = out[0].cpu().numpy(), out[1].cpu().numpy().astype(np.uint32)
         # the device's order (hyperparameters, i, p) -> params + star_params; "i" per degree
         device_order = list(names) + [k for k in _FISHER_STAR_PARAMS if k in star_names]
